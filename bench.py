@@ -21,10 +21,15 @@ line carries the C4 significance pass (200 cameras / N per rank, RCCL integer al
 score exchange, prune mask compared with the single-rank mask).  `--mode fwd` has no collective (a
 forward-only render has nothing to exchange); `--mode count` times the C4 pass itself.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times
+exactly --steps steps and prints the headline (`value`, `ms_per_step`); `--dump-outputs DIR` also writes
+what the last timed step returned to its caller.  Everything else is measured or checked only with --full:
   roofline     -- dominant kernel, algorithmic bytes / measured (hipEvent) launch time vs 8 TB/s
   cpu_baseline -- the CPU oracle (oracle/, a port; the reference has no CPU render path) on the
                   host cores, bounded sample, rank 0 at N=1 only
+and the orbit statistics, the ~1 s steady-state loop, the literal-getter / same-scene / camera-batch /
+heavier-scene legs, the C4 leg and the cross-rank digests at N > 1, the epilogue and 1-GPU mask check of
+--mode count.
 """
 import argparse
 import json
@@ -111,6 +116,10 @@ def parse():
                     help="exercise the launcher, the process group, the camera sharding and the significance reduction on a tiny CPU scene "
                          "with a synthetic per-view counter (no GPU, no rendering): what tests/test_bench_launcher.py drives at world 2")
     ap.add_argument("--no-verify-1gpu", action="store_true", help="--mode count, N > 1: skip recomputing the single-rank prune mask on rank 0")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps, run every other measurement and check of the line (roofline, "
+                    "CPU baseline, the untimed legs, the cross-rank checks); a plain run does only what `value` and `ms_per_step` need")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned to its caller as DIR/<name>.npy "
+                    "(float32 / float64; per-Gaussian arrays cut to a fixed, seeded sample of rows)")
     return ap.parse_args()
 
 
@@ -156,6 +165,31 @@ def mask_digest(mask):
     """sha256 of the prune mask's bytes (uint8 0/1 per Gaussian): equal digests <=> Hamming distance 0."""
     import hashlib
     return hashlib.sha256(mask.detach().to("cpu", torch.uint8).contiguous().numpy().tobytes()).hexdigest()
+
+
+DUMP_ROWS = 1 << 16          # --dump-outputs: rows kept of an array with more (the per-Gaussian ones: 3 M rows at C3)
+DUMP_BYTES = 64 << 20        # --dump-outputs: cap on all files together (C3 fwdbwd: the 25 MB image + 16 MB of sampled rows)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array as out_dir/<name>.npy: floating point as float32, integers as float64 (exact).  An array with more than DUMP_ROWS
+    rows keeps the rows of one fixed, seeded sample (the same rows for every array of that length), so that two builds compare row for row."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows, total = {}, 0
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        n = t.shape[0] if t.dim() else 0
+        if n > DUMP_ROWS:
+            if n not in rows:
+                rows[n] = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_ROWS].sort().values
+            t = t[rows[n].to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if (a.dtype.kind in "iu" or a.dtype == np.float64) else np.float32)
+        total += a.nbytes
+        if total > DUMP_BYTES:
+            raise SystemExit(f"--dump-outputs: the outputs exceed {DUMP_BYTES >> 20} MB at {name} (smaller --width / --height)")
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def dry_run(args, rank, world):
@@ -412,6 +446,11 @@ def main():
 
     KV = max(1, args.views_per_rank) if args.mode == "fwdbwd" else 1
     sh_sink = {"fwdbwd": None, "distill": None}
+    last = {}       # --dump-outputs: what the latest step handed its caller (render package, loss, the model whose .grad it filled)
+
+    def keep(pkg, loss=None, model=None):
+        if args.dump_outputs:
+            last.update(pkg=pkg, loss=loss, model=model)
 
     def step(i, collectives=True):
         k = view_of_step(my_views, i * KV)
@@ -438,9 +477,10 @@ def main():
                     vis = pkg["visibility_filter"].clone() if vis is None else vis.logical_or_(pkg["visibility_filter"])
             if collectives and dp_step:     # (the rank-0-only measurement legs below must not enter a collective)
                 exchange(params, vis, sink, pc, overlap)
+            keep(pkg, loss, pc)
         elif args.mode == "fwd":
             with torch.no_grad():
-                render(cams[k], pc, pipe, bg)
+                keep(render(cams[k], pc, pipe, bg))
         elif args.mode == "distill":
             for p in sparams:
                 p.grad = None
@@ -453,6 +493,7 @@ def main():
                                                  render_fn=rf)
             if collectives and dp_step:
                 exchange(sparams, spkg["visibility_filter"], sink, student)
+            keep(spkg, _l, student)
         else:
             # --mode count outside prune_list_sharded (the per-kernel bracket pass): the SAME variant the timed pass runs -- getters
             # hoisted, colours skipped -- so that `kernels_ms` and the hipEvent bracket describe lg_blend_fwd<COUNT, no colour> and a K1
@@ -479,10 +520,13 @@ def main():
             if args.mode == "fwdbwd":
                 for p in (g._xyz, g._features_dc, g._features_rest, g._scaling, g._rotation, g._opacity):
                     p.grad = None
-                photometric(render(cams[k], g, pipe, bg)["render"], gts[k]).backward()
+                pkg = render(cams[k], g, pipe, bg)
+                loss = photometric(pkg["render"], gts[k])
+                loss.backward()
+                keep(pkg, loss, g)
             else:
                 with torch.no_grad():
-                    render(cams[k], g, pipe, bg)
+                    keep(render(cams[k], g, pipe, bg))
 
         def run(w, first, count):
             torch.cuda.set_device(dev)
@@ -540,20 +584,23 @@ def main():
             cnt, imp = prune_list_sharded(pc, cl, pipe, bg, force_collectives=world > 1, streams=args.count_streams, weight_policy=args.weight_policy)
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            last.update(gaussians_count=cnt, important_score=imp)
         from lightgaussian_amd import prune as _prune
-        # config C4's epilogue, the reference's own formulation (calculate_v_imp_score(v_pow=0.1) + prune_gaussians(0.66)): every
-        # rank holds the same reduced scores, hence the same mask; its digest goes into the JSON line
-        with torch.no_grad():
-            mask_all = _prune.prune_mask(0.66, _prune.calculate_v_imp_score(pc, imp, 0.1))
         extra["significance_pass"] = {"views": args.steps * world, "seconds": round(elapsed, 4),
                                       "score_checksum": float(imp.double().sum().item()), "hits": int(cnt.sum().item()),
-                                      "views_in_flight_per_rank": args.count_streams, "weight_policy": args.weight_policy, "rccl_world_size": dist.get_world_size() if world > 1 else 1,
-                                      "prune_ratio": 0.66, "v_pow": 0.1, "pruned": int(mask_all.sum().item()), "mask_sha256": mask_digest(mask_all)}
-        if world > 1:
+                                      "views_in_flight_per_rank": args.count_streams, "weight_policy": args.weight_policy, "rccl_world_size": dist.get_world_size() if world > 1 else 1}
+        if args.full:
+            # config C4's epilogue, the reference's own formulation (calculate_v_imp_score(v_pow=0.1) + prune_gaussians(0.66)): every
+            # rank holds the same reduced scores, hence the same mask; its digest goes into the JSON line
+            with torch.no_grad():
+                mask_all = _prune.prune_mask(0.66, _prune.calculate_v_imp_score(pc, imp, 0.1))
+            extra["significance_pass"].update({"prune_ratio": 0.66, "v_pow": 0.1, "pruned": int(mask_all.sum().item()), "mask_sha256": mask_digest(mask_all)})
+        if args.full and world > 1:
             digests = [None] * world
             dist.all_gather_object(digests, extra["significance_pass"]["mask_sha256"])
             extra["significance_pass"]["mask_identical_on_all_ranks"] = len(set(digests)) == 1
-        if rank == 0 and world > 1 and not args.no_verify_1gpu:
+        if args.full and rank == 0 and world > 1 and not args.no_verify_1gpu:
             # the same camera list on ONE rank (the plain single-process loop): the mask must not depend on the GPU count
             with torch.no_grad():
                 c1, i1 = prune_list_sharded(pc, cl, pipe, bg, streams=args.count_streams, weight_policy=args.weight_policy, local_only=True)
@@ -561,7 +608,7 @@ def main():
             extra["significance_pass"].update({"mask_equals_1gpu": bool(torch.equal(m1, mask_all)), "counts_equal_1gpu": bool(torch.equal(c1, cnt)),
                                                "scores_bit_identical_1gpu": bool(torch.equal(i1, imp)), "mask_sha256_1gpu": mask_digest(m1)})
             del c1, i1, m1
-        if rank == 0:
+        if args.full and rank == 0:
             # the epilogue itself (untimed w.r.t. `value`): device-resident radix selects (prune_epilogue) next to the reference's
             # torch formulation (2 full sorts + host indexing)
             def timed(fn, reps=5):
@@ -628,9 +675,25 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # The contract times EXACTLY `steps` steps; at ~2 ms per step a small K is a very short window (r1: 41 ms).  When it is
+    if args.dump_outputs and rank == 0:
+        if "pkg" in last:
+            out = {"image": last["pkg"]["render"], "radii": last["pkg"]["radii"], "visibility_filter": last["pkg"]["visibility_filter"]}
+            if last["loss"] is not None:
+                out["loss"] = torch.tensor(float(last["loss"]), dtype=torch.float64)
+            m = last["model"]
+            if last["pkg"]["viewspace_points"].grad is not None:
+                out["grad_viewspace_points"] = last["pkg"]["viewspace_points"].grad
+            for name in ("_xyz", "_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity"):
+                if m is not None and getattr(m, name).grad is not None:
+                    out["grad" + name] = getattr(m, name).grad
+        else:
+            out = {k: last[k] for k in ("gaussians_count", "important_score")}
+        dump_outputs(args.dump_outputs, out)
+        del out
+    last.clear()
+    # The contract times EXACTLY `steps` steps; at ~2 ms per step a small K is a very short window (r1: 41 ms).  With --full, when it is
     # under half a second, the same loop is run again for about one second (every rank, same barriers) and reported beside it.
-    if elapsed < 0.5 and args.mode in ("fwdbwd", "fwd", "distill") and args.views_in_flight == 1:
+    if args.full and elapsed < 0.5 and args.mode in ("fwdbwd", "fwd", "distill") and args.views_in_flight == 1:
         n_long = int(math.ceil(1.0 / max(elapsed / args.steps, 1e-5)))
         barrier()
         t0 = time.perf_counter()
@@ -644,23 +707,15 @@ def main():
             dt = float(t.item())
         extra["steady_state"] = {"steps": n_long, "seconds": round(dt, 4), "views_per_s": round(world * KV * n_long / dt, 3),
                                  "distinct_cameras": len({view_of_step(my_views, (args.warmup + i) * KV + j) for i in range(n_long) for j in range(KV)}),
-                                 "note": "same loop as `value`, run for ~1 s because the contract's timed region was under 0.5 s"}
+                                 "note": "same step as `value`, run for ~1 s because the --steps region was under 0.5 s (a burst: clocks may not "
+                                         "have settled); `value` and `ms_per_step` stay the --steps region"}
     extra["timed_seconds"] = round(elapsed, 4)
     ms_per_step = elapsed / args.steps * 1e3
     value = world * KV * args.steps / elapsed  # whole-job views/s: every rank did `steps` steps of KV views
-    extra["value_contract_region"] = round(value, 3)     # exactly --steps steps between the barriers (the driver's K); `value` is the same loop run for ~1 s when that region is under 0.5 s
-    if "steady_state" in extra:
-        # r2 verdict: a timed region of a few tens of ms is a burst (clocks have not settled); `value` is the sustained loop of the
-        # SAME step, and the contract's K-step region is reported beside it
-        extra["contract_region"] = {"steps": args.steps, "seconds": round(elapsed, 4), "views_per_s": round(value, 3), "ms_per_step": round(ms_per_step, 4),
-                                    "note": "exactly --steps steps between the barriers; under 0.5 s, so `value` / `ms_per_step` are taken from the ~1 s loop (timed_steps)"}
-        value = extra["steady_state"]["views_per_s"]
-        ms_per_step = extra["steady_state"]["seconds"] / extra["steady_state"]["steps"] * 1e3
-        extra["timed_steps"] = extra["steady_state"]["steps"]
-        extra["timed_seconds"] = extra["steady_state"]["seconds"]
+    extra["value_contract_region"] = round(value, 3)     # exactly --steps steps between the barriers: the same region as `value`
 
     c4 = None
-    if multi and args.mode == "fwdbwd" and not args.no_c4_leg:
+    if args.full and multi and args.mode == "fwdbwd" and not args.no_c4_leg:
         # ---- config C4 inside the same line: the significance pass over 200 cameras, 200 / N per rank, RCCL reduction, the
         #      reference's epilogue, and the mask against the single-rank pass (every rank takes part: collectives) ----
         from lightgaussian_amd import prune as _prune
@@ -692,7 +747,7 @@ def main():
             del c1, i1, m1
         del cnt, imp, mask_all
         extra["c4_significance_pass"] = c4
-    if dp_step and args.mode in ("fwdbwd", "distill") and dist.is_initialized():
+    if args.full and dp_step and args.mode in ("fwdbwd", "distill") and dist.is_initialized():
         # every rank holds the same averaged gradients after a step: compare a digest of the last step's (all six tensors) across the ranks
         import hashlib
         step(0)                    # (one more step on a FIXED camera: the digest is a function of the inputs, not of how many steps the ~1 s loop ran)
@@ -730,14 +785,6 @@ def main():
                                           "compute_ms = ms_per_step - allreduce_ms"}
     result = None
     if rank == 0:
-        # V (visible Gaussians) and R (tile instances) of EVERY camera this rank's loops cycle through (r4 verdict: the line used to
-        # quote view 0's): the roofline's algorithmic bytes use the orbit means, since every timing is an average over the orbit
-        orbit_V, orbit_R = [], []
-        with torch.no_grad():
-            for k in my_views:
-                orbit_V.append(int((render(cams[k], pc, pipe, bg)["radii"] > 0).sum().item()))
-                orbit_R.append(int(_lib.last_stats()["num_rendered"]))
-        vis, R, P = int(round(sum(orbit_V) / len(orbit_V))), int(round(sum(orbit_R) / len(orbit_R))), W * H
         result = {
             "metric": "views/sec fwd+bwd @1080p (N Gaussians)" if args.mode == "fwdbwd" else f"views/sec {args.mode} @{H}p (N Gaussians)",
             "value": round(value, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -746,11 +793,6 @@ def main():
             "config": {"workload": f"{N} synthetic Gaussians (SURVEY 8d generator, seed {syn.SEED}{', heavy-tailed variant' if args.scene == 'heavy' else ''}), {W}x{H}, SH degree {args.sh_degree}, "
                                    f"{args.mode} through gaussian_renderer.render, {args.views}-camera orbit",
                        "n_gaussians": N, "width": W, "height": H, "mode": args.mode, "views": args.views,
-                       "visible_gaussians": vis, "tile_instances": R,
-                       "orbit": {"cameras": len(my_views), "distinct_targets": len(gts) if args.mode == "fwdbwd" else None,
-                                 "visible_gaussians": {"mean": vis, "max": max(orbit_V), "min": min(orbit_V), "view0": orbit_V[0]},
-                                 "tile_instances": {"mean": R, "max": max(orbit_R), "min": min(orbit_R), "view0": orbit_R[0]},
-                                 "note": "every step renders camera my_views[i % cameras] against its own target; visible_gaussians / tile_instances above are the orbit means"},
                        "exp": "canonical" if (args.exact_exp or args.mode == "count") else "hardware",
                        "forward": {False: "exact (lg_forward: blocking read-back of the instance count)", "validated": "bounded + validated "
                                    "(lg_forward_bounded with host status: capacity from earlier views, status read after the view is enqueued)",
@@ -771,8 +813,24 @@ def main():
             result["test_mode"] = "LG_BENCH_SHARE_GPU=1: all ranks on cuda:0, collectives over gloo -- a functional check of the multi-rank step, not a measurement"
         result.update(extra)
 
+    if rank == 0 and args.full:
+        # V (visible Gaussians) and R (tile instances) of EVERY camera this rank's loops cycle through (r4 verdict: the line used to
+        # quote view 0's): the roofline's algorithmic bytes use the orbit means, since every timing is an average over the orbit
+        orbit_V, orbit_R = [], []
+        with torch.no_grad():
+            for k in my_views:
+                orbit_V.append(int((render(cams[k], pc, pipe, bg)["radii"] > 0).sum().item()))
+                orbit_R.append(int(_lib.last_stats()["num_rendered"]))
+        vis, R, P = int(round(sum(orbit_V) / len(orbit_V))), int(round(sum(orbit_R) / len(orbit_R))), W * H
+        result["config"].update({
+            "visible_gaussians": vis, "tile_instances": R,
+            "orbit": {"cameras": len(my_views), "distinct_targets": len(gts) if args.mode == "fwdbwd" else None,
+                      "visible_gaussians": {"mean": vis, "max": max(orbit_V), "min": min(orbit_V), "view0": orbit_V[0]},
+                      "tile_instances": {"mean": R, "max": max(orbit_R), "min": min(orbit_R), "view0": orbit_R[0]},
+                      "note": "every step renders camera my_views[i % cameras] against its own target; visible_gaussians / tile_instances above are the orbit means"}})
+
     # ---- roofline leg: per-kernel hipEvent timings of the same step (separate, untimed pass) ----
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         rasterizer.set_option("profile", True)
         _lib.profile_reset()
         nprof = max(3, min(10, args.steps))
@@ -872,7 +930,7 @@ def main():
         result["kernels_ms_note"] = "per-kernel hipEvent brackets (separate untimed pass) add ~4 % each: their sum exceeds ms_per_step"
 
     # ---- the same step with the reference's literal getter pattern (torch exp/sigmoid/normalize/cat per call), untimed leg ----
-    if rank == 0 and not args.no_fuse and not args.no_literal and args.mode in ("fwdbwd", "fwd", "distill"):
+    if rank == 0 and args.full and not args.no_fuse and not args.no_literal and args.mode in ("fwdbwd", "fwd", "distill"):
         rasterizer.set_option("fuse_getters", False)
         nlit = max(5, min(30, args.steps))
         for i in range(3):
@@ -888,7 +946,7 @@ def main():
                                             "note": "set_option('fuse_getters', False): getters evaluated by torch on every render call, as the reference does"}
 
     # ---- the other two rates north_star asks for, on the same scene (rank 0, untimed w.r.t. `value`, no collectives) ----
-    if rank == 0 and args.mode == "fwdbwd" and not args.no_literal:
+    if rank == 0 and args.full and args.mode == "fwdbwd" and not args.no_literal:
         from lightgaussian_amd.prune import _FrozenGetters
         def rate(fn, n=30):
             for i in range(3):
@@ -908,7 +966,7 @@ def main():
                                                       "colours skipped); see --mode fwd / --mode count for the full runs"}
 
     # ---- camera batch of 3: independent views in flight (informational; `value` above is one view per step, as the reference trains) ----
-    if rank == 0 and args.mode in ("fwdbwd", "fwd") and args.views_in_flight == 1 and not args.no_literal:
+    if rank == 0 and args.full and args.mode in ("fwdbwd", "fwd") and args.views_in_flight == 1 and not args.no_literal:
         def batch_rate(runner):
             runner(0, 6)
             torch.cuda.synchronize()
@@ -925,7 +983,7 @@ def main():
                                             "memory-bound stages of another; host_threads_variant = round 1's thread-per-stream scheme"}
 
     # ---- heavier workloads beside the headline (r1 verdict: R/N = 1.38 of the frozen scene is light next to real captures) ----
-    if rank == 0 and args.mode == "fwdbwd" and not args.no_literal and args.scene == "uniform" and abs(args.scale - 0.004) < 1e-12:
+    if rank == 0 and args.full and args.mode == "fwdbwd" and not args.no_literal and args.scene == "uniform" and abs(args.scale - 0.004) < 1e-12:
         def scene_rate(gc, nsteps=60):
             # the same step as `value` on another scene: ground truth = render of a perturbed copy (sigma 0.01), 8 cameras of the orbit
             gen2 = torch.Generator("cpu").manual_seed(syn.SEED + 2)
@@ -962,7 +1020,7 @@ def main():
         del big, heavy
 
     # ---- cpu_baseline leg: the oracle on the host cores, bounded sample ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, g_cpu, W, H)
 
     if rank == 0:

@@ -13,11 +13,10 @@ import torch
 import dropin_common
 from lightgaussian_amd import run as lg_run
 
-pytestmark = pytest.mark.skipif(not dropin_common.available(), reason="/root/reference is not present on this box")
-
-
 @pytest.fixture()
 def ref():
+    if not dropin_common.available():
+        pytest.skip("the reference tree is not present")
     mods = dropin_common.load()
     lu = importlib.import_module("utils.loss_utils")
     vq = importlib.import_module("vectree.vq")

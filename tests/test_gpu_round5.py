@@ -277,7 +277,7 @@ def _bench_two_ranks(tmp_path, *extra):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(common.ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--n-gaussians", "150000", "--width", "480",
-           "--height", "272", "--views", "8", "--scale", "0.02", "--no-cpu-baseline", "--no-roofline", "--no-literal", "--no-c4-leg", *extra]
+           "--height", "272", "--views", "8", "--scale", "0.02", "--full", "--no-cpu-baseline", "--no-roofline", "--no-literal", "--no-c4-leg", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=common.ROOT, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-3000:]
@@ -315,7 +315,7 @@ def _bench_ranks_on_one_gpu(world, *extra):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(common.ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--n-gaussians", "150000", "--width", "480", "--height", "272",
-           "--scale", "0.02", "--no-cpu-baseline", "--no-roofline", "--no-literal", *extra]
+           "--scale", "0.02", "--full", "--no-cpu-baseline", "--no-roofline", "--no-literal", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=common.ROOT, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-3000:]

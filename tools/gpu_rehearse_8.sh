@@ -7,7 +7,7 @@ export LG_BENCH_SHARE_GPU=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 W=${1:-8}
 shift
 TAG=${W}ranks_one_gpu$(echo "$*" | tr -c "a-zA-Z0-9\n" "_" | sed "s/_*$//; s/^_*/_/; s/^_$//")
-timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $W --backend gloo \
+timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $W --backend gloo --full \
     --steps 4 --warmup 1 --no-cpu-baseline --no-literal "$@" > gpurun_out/r05_rehearsal_${TAG}.json 2> gpurun_out/r05_rehearsal_${TAG}.err
 echo rc=$?
 tail -c 1500 gpurun_out/r05_rehearsal_${TAG}.err

@@ -3,12 +3,12 @@
 # rocprofv3 evidence (tools/gpu_profile.sh -> gpurun_out/<round>_profile_<mode>.json + kernel stats CSV; copy them to profiles/).
 #   gpurun --timeout 2400 -- 'bash tools/gpu_round.sh'
 mkdir -p gpurun_out; export TMPDIR=/tmp
-run() { timeout -s KILL 600 python bench.py --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
+run() { timeout -s KILL 600 python bench.py --full --no-cpu-baseline "$@" 2>&1 | tail -1 | python -c "
 import sys, json
 d=json.loads(sys.stdin.read().strip()); c=d['config']; print('$*', '->', d['value'], 'views/s', d['ms_per_step'], 'ms', 'burst', (d.get('contract_region') or {}).get('views_per_s'), 'V', c['visible_gaussians'], 'R', c['tile_instances'], d.get('kernels_ms'), 'batch3', (d.get('camera_batch_3') or {}), (d.get('significance_pass') or {}), (d.get('literal_getter_pattern') or {}))" | cut -c1-1800; }
 timeout -s KILL 2400 python -m pytest tests -m gpu -q --tb=short 2>&1 | tail -15 > gpurun_out/round_pytest.log; grep -E "passed|failed" gpurun_out/round_pytest.log | tail -1; grep -E "^FAILED|^E  " gpurun_out/round_pytest.log | cut -c1-300 | head
 timeout -s KILL 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-( time timeout -s KILL 900 python bench.py ) > gpurun_out/round_bench_default.log 2>&1; tail -5 gpurun_out/round_bench_default.log | cut -c1-7000
+( time timeout -s KILL 900 python bench.py --full ) 2>&1 | tail -5 | cut -c1-7000
 run --n-gaussians 1000000 --mode fwd --steps 100 --no-literal
 run --n-gaussians 3000000 --mode fwd --steps 100 --no-literal
 run --n-gaussians 3000000 --mode count --steps 100
@@ -40,7 +40,7 @@ timeout -s KILL 300 python tools/vq_bench.py 2>&1 | tail -4
 timeout -s KILL 420 python tools/gpu_fuzz.py 150 2>&1 | tail -2 | cut -c1-300
 timeout -s KILL 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | cut -c1-300
 # the data-parallel step and the C4 leg of `bench.py --gpus N` through RCCL at world size 1 (the collectives are real, the wire is not)
-timeout -s KILL 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-literal --force-collectives 2>/dev/null | grep "^{" | tail -1 | python -c "
+timeout -s KILL 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-literal --force-collectives 2>/dev/null | grep "^{" | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('forced collectives:', d['value'], 'views/s', d.get('data_parallel'), d.get('c4_significance_pass'))" | cut -c1-1500
 for v in "--dense-allreduce" "--visible-allreduce" "--views-per-rank 4" "--dp-overlap"; do

@@ -4,14 +4,14 @@
 run() { # label, lib, bench args...
   local label=$1 lib=$2; shift 2
   if [ "$lib" = "-" ]; then unset LIGHTGAUSSIAN_HIP_LIB; else export LIGHTGAUSSIAN_HIP_LIB=$PWD/$lib; fi
-  timeout -s KILL 300 python bench.py "$@" --no-cpu-baseline --no-literal 2>/dev/null | tail -1 > gpurun_out/ab_tmp.json
-  python - "$label" "$lib" <<'PY'
+  timeout -s KILL 300 python bench.py "$@" --full --no-cpu-baseline --no-literal 2>/dev/null | tail -1 > "$J"
+  python - "$label" "$lib" "$J" <<'PY'
 import json, sys
-d = json.load(open("gpurun_out/ab_tmp.json")); k = d.get("kernels_ms", {})
+d = json.load(open(sys.argv[3])); k = d.get("kernels_ms", {})
 print(sys.argv[1], sys.argv[2], "value", d["value"], "k1", k.get("preprocess"), "k9", k.get("preprocess_bwd"), flush=True)
 PY
 }
-mkdir -p gpurun_out
+J=$(mktemp)
 for lib in "$@"; do
 run c3 $lib --mode fwdbwd --steps 50
 run c3 $lib --mode fwdbwd --steps 50
