@@ -1,6 +1,7 @@
 // lg_api.hip -- C ABI (include/lightgaussian.h) of the gfx950 (CDNA4, wave64) LightGaussian rasterizer.
 // The single translation unit of liblightgaussian_hip.so; the kernels live in the headers it includes:
 //   lg_math.h        scalar float arithmetic shared with the CPU test harness (canonical operation order)
+//   lg_plan.h        host-side plans of one forward, plain C++ (also compiled by the CPU tests): KeyPlan (sort-key layout), ForwardPlan (kernel variants)
 //   lg_host.h        error strings, optional hipEvent profiler, scratch carving (GeomView / ImgView / BinView)
 //   lg_wave.h        wave64 primitives (DPP / permlane reductions)
 //   lg_preprocess.h  K1 lg_preprocess<RAW>, K8+K9 lg_preprocess_bwd<RAW>            (per Gaussian, HBM-bound)
@@ -35,6 +36,22 @@
 
 // ------------------------------------------------------------------------------------------------
 // host side
+// What every entry point derives from (view, N): the tile grid, the padded grid of the per-tile kernels, the segment length and the
+// Gaussian-id field of the list entries -- the backward and the lg_debug_* readers see what the forward saw.
+struct ViewGeom { int W, H, gx, gy, ntiles, ntiles_pad, S, gid_bits; uint32_t gid_mask; };
+static ViewGeom view_geom(const lg_view* v, int N)
+{
+    ViewGeom q;
+    q.W = v->image_width; q.H = v->image_height;
+    q.gx = (q.W + LG_TILE - 1) / LG_TILE; q.gy = (q.H + LG_TILE - 1) / LG_TILE;
+    q.ntiles = (int)((int64_t)q.gx * q.gy);
+    q.ntiles_pad = (int)(((int64_t)q.ntiles + LG_TILE_GRID_ALIGN - 1) / LG_TILE_GRID_ALIGN * LG_TILE_GRID_ALIGN); // grid of the per-tile kernels
+    q.S = lg_segment_of(v);     // list entries per segment of a long tile (checkpoints for the backward): part of the view
+    q.gid_bits = lg_gid_bits(N);
+    q.gid_mask = lg_gid_mask(q.gid_bits);
+    return q;
+}
+
 static int check_args(const lg_view* v, const lg_gaussians* g)
 {
     if (!v || !g) return fail(LG_ERR_INVALID_ARGUMENT, "null view/gaussians");
@@ -62,10 +79,11 @@ static int check_args(const lg_view* v, const lg_gaussians* g)
     }
     if (!v->bg || !v->viewmatrix || !v->projmatrix || !v->campos || !g->means3D || !g->opacities)
         return fail(LG_ERR_INVALID_ARGUMENT, "missing required pointer");
-    const int gx = (v->image_width + LG_TILE - 1) / LG_TILE, gy = (v->image_height + LG_TILE - 1) / LG_TILE;
-    if (gx >= 65536 || gy >= 65536) return fail(LG_ERR_INVALID_ARGUMENT, "image too large");
+    const ViewGeom q = view_geom(v, g->N);
+    if (q.gx >= 65536 || q.gy >= 65536) return fail(LG_ERR_INVALID_ARGUMENT, "image too large");
     return LG_OK;
 }
+
 
 // 64-byte pinned host slots for the forward's read-back, recycled through a process-wide free list (a thread_local slot
 // would be allocated -- and leaked -- by every short-lived host thread of the views-in-flight helpers).
@@ -103,131 +121,106 @@ struct PinnedSlot {
         }                                                                                    \
     } while (0)
 
-// Layout of the sort key of one view: tile | (depth bits - bias) >> store_drop | Gaussian id.  Exact forward: from the
-// read-back depth maximum.  Bounded forward: from the caller's depth bound (nothing is read back).
 #define LG_STATUS_PENDING 0xFFFFFFFFu   // sentinel of the host-visible status word 0 (a real abort word has only its low bits set)
-#define LG_NARROW_KEY_BITS 40   // LG_FLAG_NARROW_KEY (cross-check): lay the key out as if only this many bits were available
-struct KeyPlan {
-    int tile_bits, gid_bits, depth_bits;   // field widths; depth_bits = width of the FULL depth pattern (minus bias) of this view
-    int store_drop;                        // low depth bits that are not stored in the key (the fields exceed 64 bits): 0 at C3
-    bool two_stage;                        // radix passes on the tile bits only + lg_tile_sort (default); false = LG_FLAG_SORT_ALL_BITS
-    uint32_t gid_mask;
-    int stored() const { return depth_bits - store_drop; }
-    int tile_shift() const { return gid_bits + stored(); }
-    // bit span of the global radix passes: the tile field (at least one bit: a single-tile image still needs its keys moved to the
-    // output buffer), preceded by every stored depth bit in the one-stage scheme
-    int sort_begin() const { return two_stage ? tile_shift() : gid_bits; }
-    int sort_end() const { return tile_shift() + (tile_bits > 0 ? tile_bits : 1); }
-};
-static KeyPlan make_key_plan(int ntiles, int N, uint32_t dmax_bits, uint32_t flags)
+
+// ---- template selection: one place per kernel, and exactly the instantiations named here ----
+static_assert(LG_W_ALPHA == LG_WEIGHT_ALPHA && LG_W_ALPHA_T == LG_WEIGHT_ALPHA_T, "ForwardPlan::fscore is the kernels' FSCORE");
+using PreprocessKernel = decltype(&lg_preprocess<false, false>);
+static PreprocessKernel preprocess_kernel(bool raw, bool direct)
 {
-    KeyPlan k;
-    k.tile_bits = bits_for((uint32_t)ntiles);
-    k.gid_bits = bits_for((uint32_t)(N > 1 ? N : 2));
-    const uint32_t dspan = dmax_bits > LG_DEPTH_BIAS ? dmax_bits - LG_DEPTH_BIAS : 0u;
-    k.depth_bits = bits_for(dspan + 1u) > 0 ? bits_for(dspan + 1u) : 1;
-    // The three fields must fit 64 bits.  When they do not (6 M Gaussians at 3840x2160: 15 + 27 + 23 = 65; 20 M at 1080p; ...)
-    // the lowest depth bits are left out of the key and the tile sort reads the full depth pattern from the binning record
-    // (tinfo) -- r2 fell back to a (tile << 32 | depth, id) pair sort through hipCUB there, without the bounded
-    // forward, the graph and the fused histograms.  At least one depth bit is always stored (tile <= 32 bits, id <= 29).
-    const int avail = (flags & LG_FLAG_NARROW_KEY) ? LG_NARROW_KEY_BITS : 64;
-    k.store_drop = std::max(0, std::min(k.depth_bits - 1, k.tile_bits + k.depth_bits + k.gid_bits - avail));
-    // Two-stage sort (default, round 3): the global radix passes cover the tile bits only (13 bits at 1080p: two 8-bit passes
-    // instead of the four that tile + 19 depth bits took in round 2) and lg_tile_sort orders every list on ALL depth bits inside
-    // LDS.  LG_FLAG_SORT_ALL_BITS keeps the one-stage scheme -- every stored bit through the global passes, lg_tile_ranges
-    // finishing the bits a key beyond 64 bits does not store -- as an independent cross-check.
-    k.two_stage = !(flags & LG_FLAG_SORT_ALL_BITS);
-    k.gid_mask = k.gid_bits >= 32 ? 0xFFFFFFFFu : ((1u << k.gid_bits) - 1u);
-    return k;
+    static const PreprocessKernel k[2][2] = { { lg_preprocess<false, false>, lg_preprocess<false, true> }, { lg_preprocess<true, false>, lg_preprocess<true, true> } };
+    return k[raw][direct];
+}
+using BlendFwdKernel = decltype(&lg_blend_fwd<false, 0, true, true>);
+static BlendFwdKernel blend_fwd_kernel(const ForwardPlan& p)
+{
+    static const BlendFwdKernel color[2] = { lg_blend_fwd<false, 0, false, true>, lg_blend_fwd<false, 0, true, true> };    // [exact]
+    static const BlendFwdKernel count_image[3][2] = { { lg_blend_fwd<true, 0, false, true>, lg_blend_fwd<true, 0, true, true> },   // [policy][exact]
+                                                      { lg_blend_fwd<true, LG_W_ALPHA, false, true>, lg_blend_fwd<true, LG_W_ALPHA, true, true> },
+                                                      { lg_blend_fwd<true, LG_W_ALPHA_T, false, true>, lg_blend_fwd<true, LG_W_ALPHA_T, true, true> } };
+    static const BlendFwdKernel significance[3] = { lg_blend_fwd<true, 0, true, false>, lg_blend_fwd<true, LG_W_ALPHA, true, false>,
+                                                    lg_blend_fwd<true, LG_W_ALPHA_T, true, false> };                           // [policy]
+    const int w = p.fscore == LG_W_ALPHA ? 1 : p.fscore == LG_W_ALPHA_T ? 2 : 0;
+    return !p.count ? color[p.exact] : p.color ? count_image[w][p.exact] : significance[w];
+}
+using BlendBwdKernel = decltype(&lg_blend_bwd<true>);
+static BlendBwdKernel blend_bwd_kernel(bool exact) { return exact ? lg_blend_bwd<true> : lg_blend_bwd<false>; }
+using PreprocessBwdKernel = decltype(&lg_preprocess_bwd<false, false>);
+static PreprocessBwdKernel preprocess_bwd_kernel(bool raw, bool jac)
+{
+    static const PreprocessBwdKernel k[2][2] = { { lg_preprocess_bwd<false, false>, lg_preprocess_bwd<false, true> },
+                                                 { lg_preprocess_bwd<true, false>, lg_preprocess_bwd<true, true> } };
+    return k[raw][jac];
 }
 
 // Arguments of the capacity-bounded forward (lg_forward_bounded); NULL = exact forward with its one read-back.
 struct Bounded { void* binning; int64_t capacity; float max_depth; uint32_t* status; uint32_t* host_status; };
 
-static int forward_impl(const lg_view* v, const lg_gaussians* g, void* geom_p, void* img_p, lg_alloc_fn alloc, void* alloc_user,
-                        const Bounded* bounded, int weight_policy, float* out_color, int32_t* out_radii, int32_t* out_count,
-                        float* out_score, void** binning_out, int64_t* num_rendered, void* stream_p)
-{
-    int rc = check_args(v, g);
-    if (rc != LG_OK) return rc;
-    if (!geom_p || !img_p || !out_color || (!out_radii && g->N > 0) || (!alloc && !bounded)) return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
-    const bool count = out_count != nullptr;
-    if (count && !out_score) return fail(LG_ERR_INVALID_ARGUMENT, "count needs score");
-    if (count && (weight_policy < 0 || weight_policy > 3)) return fail(LG_ERR_INVALID_ARGUMENT, "bad weight policy");
-    // per-hit weights are summed in Q24.40 per view: a Gaussian can collect at most 0.99 per pixel
-    if (count && weight_policy >= LG_WEIGHT_ALPHA && (int64_t)v->image_width * v->image_height > (1ll << 24))
-        return fail(LG_ERR_INVALID_ARGUMENT, "ALPHA / ALPHA_T weights: images beyond 2^24 pixels overflow the Q24.40 per-view sums");
-    hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, fast = v->flags & LG_FLAG_FAST_EXP;
-    const int N = g->N, W = v->image_width, H = v->image_height;
-    const int gx = (W + LG_TILE - 1) / LG_TILE, gy = (H + LG_TILE - 1) / LG_TILE, ntiles = gx * gy;
-    const int ntiles_pad = (ntiles + LG_TILE_GRID_ALIGN - 1) / LG_TILE_GRID_ALIGN * LG_TILE_GRID_ALIGN; // grid of the per-tile kernels
-    const int nblk = (N + LG_PP - 1) / LG_PP;
-    GeomView geo = carve_geom(geom_p, N);
-    ImgView img = carve_img(img_p, W, H);
-    const int S = lg_segment_of(v);     // list entries per segment of a long tile (checkpoints for the backward): part of the view
-    if (binning_out) *binning_out = nullptr;
-    if (num_rendered) *num_rendered = 0;
-
-    KeyPlan kp{};
-    BinView bin{};
-    int64_t cap = 0;          // instances the binning buffer holds: R itself (exact) or the caller's capacity (bounded)
-    if (bounded) {
-        if (!bounded->binning || bounded->capacity <= 0 || bounded->capacity >= (1ll << 30) || !(bounded->max_depth > 0.2f))
-            return fail(LG_ERR_INVALID_ARGUMENT, "lg_forward_bounded: binning buffer, 0 < max_rendered < 2^30 and max_depth > 0.2 required");
-        kp = make_key_plan(ntiles, N, __builtin_bit_cast(uint32_t, bounded->max_depth), v->flags);
-        cap = bounded->capacity;
-        bin = carve_bin(bounded->binning, cap, W, H, S);
-        if (binning_out) *binning_out = bounded->binning;
-        if (num_rendered) *num_rendered = cap;
-        if (N == 0) {
-            HIP_TRY(lg_zero_async(geo.counters, 16, stream));
-            if (bounded->status) HIP_TRY(lg_zero_async(bounded->status, 16, stream));
-            HIP_TRY(lg_zero_async(bin.ranges, (size_t)ntiles * 8, stream));
-        }
-    }
+// One forward: forward_impl checks and fills the arguments, then runs the stages in order.  The stages read the two plans (lg_plan.h);
+// none of them looks at v->flags to pick a kernel variant.
+struct Forward {
+    const lg_view* v; const lg_gaussians* g; const Bounded* bounded; lg_alloc_fn alloc; void* alloc_user; int weight_policy;
+    float* out_color; int32_t* out_radii; int32_t* out_count; float* out_score; void** binning_out; int64_t* num_rendered;
+    hipStream_t stream; bool debug, prof;
+    int N, nblk; ViewGeom q; GeomView geo; ImgView img; BinView bin;
+    KeyPlan kp; ForwardPlan plan;
+    int64_t cap;            // instances the binning buffer holds: R itself (exact) or the caller's capacity (bounded)
+    bool k1_cleared_sort;   // bounded forward: K1 also cleared the sort's histograms / tickets / states (the buffer and the key layout were known already)
     // validated bounded forward: K2 writes its four status words STRAIGHT into pinned host memory (system-scope release on word 0)
     // and the host waits for word 0 to leave its sentinel once everything of the view has been
     // enqueued -- no device-to-host copy node behind K2 (a 4 us blit kernel + its launch gap on the critical path of every view)
     PinnedSlot vslot;
+    uint32_t* device_status() const { return bounded ? bounded->status : nullptr; }
+    int front_end();    // K1, K2; the exact forward's read-back and allocation, or the bounded forward's buffer and status slot.  Leaves kp, plan, bin, cap
+    int binning();      // duplicate, sort, tile ranges or tile sort
+    int blend();        // K6 and its long-tile chain
+    int score();
+    int epilogue();     // LG_FLAG_DEBUG's look at the abort word; the validated forward's status words
+};
+
+int Forward::front_end()
+{
+    const bool count = out_count != nullptr;
+    if (bounded) {
+        if (!bounded->binning || bounded->capacity <= 0 || bounded->capacity >= (1ll << 30) || !(bounded->max_depth > 0.2f))
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_forward_bounded: binning buffer, 0 < max_rendered < 2^30 and max_depth > 0.2 required");
+        kp = make_key_plan(q.ntiles, N, __builtin_bit_cast(uint32_t, bounded->max_depth), v->flags);
+        cap = bounded->capacity;
+        bin = carve_bin(bounded->binning, cap, q.W, q.H, q.S);
+        if (N == 0) {
+            HIP_TRY(lg_zero_async(geo.counters, 16, stream));
+            if (bounded->status) HIP_TRY(lg_zero_async(bounded->status, 16, stream));
+            HIP_TRY(lg_zero_async(bin.ranges, (size_t)q.ntiles * 8, stream));
+        }
+    }
+    // The exact forward learns its instance count from K2 and makes the plan again with it, below: until then it is the plan of a view
+    // with instances.  K1 and K2 read only what does not depend on the count (k1_skip_color, k1_clears_count: tests/test_forward_plan.py).
+    plan = make_forward_plan(v->flags, count, weight_policy, N, bounded ? cap : 1);
     const bool host_words = bounded && bounded->host_status;
     if (host_words) {
         if (!vslot.p) return fail(LG_ERR_ALLOC, "hipHostMalloc of the status slot failed");
         if (N > 0) { vslot.p[1] = vslot.p[2] = vslot.p[3] = 0u; __atomic_store_n(&vslot.p[0], LG_STATUS_PENDING, __ATOMIC_RELEASE); }
         else memset(vslot.p, 0, 16);
     }
-    // bounded forward: K1 also clears the sort's histograms / tickets / states (the buffer and the key layout are known already)
     uint32_t* k1_clear = nullptr;
     uint32_t k1_nclear = 0;
-    if (bounded && N > 0 && cap > 0) {
-        const LgSortLayout SL0 = lg_sort_layout((size_t)cap);
-        const int sb = kp.sort_begin(), se = kp.sort_end();
+    if (bounded && plan.live) {
         k1_clear = (uint32_t*)bin.sort_temp;
-        k1_nclear = (uint32_t)(lg_sort_clear_bytes(SL0, (unsigned)((se - sb + 7) / 8)) / 4);
+        k1_nclear = (uint32_t)(lg_sort_clear_bytes(lg_sort_layout((size_t)cap), (unsigned)kp.sort_passes()) / 4);
     }
+    k1_cleared_sort = k1_clear != nullptr;
     if (N > 0) {
         {
             ProfScope ps(prof, "preprocess", stream);
+            // SH rows are read directly by their lanes (dword-aligned dwordx4 loads); LG_K1_LDS=1 selects the LDS-staged reads
+            const bool direct = !(v->flags & LG_FLAG_K1_LDS), raw = v->flags & LG_FLAG_RAW_PARAMS;
             // K1 runs faster with FEWER waves in flight where it reads SH rows: unused dynamic LDS caps it at 12 waves per CU there (the sweep,
             // K9's opposite behaviour and the significance pass's A/B: EXPERIMENTS.md, "K1 / K9")
-            // (the count / score accumulators are cleared here for the integer weights; the per-hit policies accumulate in the slots and
-            //  lg_score_slots writes both outputs)
-            int32_t* const k1_zero_count = (count && weight_policy >= LG_WEIGHT_ALPHA) ? nullptr : out_count;
-            const size_t k1_dyn = (g->shs && !g->colors_precomp && !(v->flags & LG_FLAG_SKIP_COLOR)) ? LG_K1_PAD_LDS : 0;
-#define LAUNCH_PP(RAWP, DIR)                                                                                                         \
-    lg_preprocess<RAWP, DIR><<<nblk, LG_PP, (DIR) ? k1_dyn : 0, stream>>>(N, g->M, v->sh_degree, W, H, v->tanfovx, v->tanfovy,                          \
-                                                                      v->scale_modifier, v->prefiltered, (v->flags & LG_FLAG_SKIP_COLOR) ? 1 : 0, v->viewmatrix, v->projmatrix, \
-                                                                      v->campos, g->means3D, g->shs, g->shs_rest, g->colors_precomp,   \
-                                                                      g->opacities, g->scales, g->rotations, g->cov3D_precomp, geo, out_radii, k1_zero_count, out_score, \
-                                                                      k1_clear, k1_nclear, (v->flags & LG_FLAG_SAVE_SH_JACOBIAN) ? 1 : 0)
-            // SH rows are read directly by their lanes (dword-aligned dwordx4 loads); LG_K1_LDS=1 selects the LDS-staged reads
-            const bool direct = !(v->flags & LG_FLAG_K1_LDS);
-            const bool raw = v->flags & LG_FLAG_RAW_PARAMS;
-            if (raw && direct) LAUNCH_PP(true, true);
-            else if (raw) LAUNCH_PP(true, false);
-            else if (direct) LAUNCH_PP(false, true);
-            else LAUNCH_PP(false, false);
-#undef LAUNCH_PP
+            const size_t k1_dyn = (direct && g->shs && !g->colors_precomp && !plan.k1_skip_color) ? LG_K1_PAD_LDS : 0;
+            preprocess_kernel(raw, direct)<<<nblk, LG_PP, k1_dyn, stream>>>(
+                N, g->M, v->sh_degree, q.W, q.H, v->tanfovx, v->tanfovy, v->scale_modifier, v->prefiltered, plan.k1_skip_color ? 1 : 0, v->viewmatrix,
+                v->projmatrix, v->campos, g->means3D, g->shs, g->shs_rest, g->colors_precomp, g->opacities, g->scales, g->rotations, g->cov3D_precomp, geo,
+                out_radii, plan.k1_clears_count ? out_count : nullptr, out_score, k1_clear, k1_nclear, (v->flags & LG_FLAG_SAVE_SH_JACOBIAN) ? 1 : 0);
         }
         KCHECK("lg_preprocess");
         {
@@ -238,11 +231,10 @@ static int forward_impl(const lg_view* v, const lg_gaussians* g, void* geom_p, v
                                                                                   geo.part_dmax, geo.part_prefix, geo.counters + 8,
                                                                                   bounded ? (uint32_t)cap : 0xFFFFFFFFu,
                                                                                   bounded ? kp.depth_bits : 32, geo.counters,
-                                                                                  host_words ? vslot.p : (bounded ? (uint32_t*)bounded->status : nullptr));
+                                                                                  host_words ? vslot.p : device_status());
         }
         KCHECK("lg_scan_blocks");
     }
-    int64_t R = cap;
     if (!bounded) {
         uint32_t h_counters[4] = {0, 0, 0, 0};
         if (N > 0) {
@@ -257,122 +249,94 @@ static int forward_impl(const lg_view* v, const lg_gaussians* g, void* geom_p, v
             if (v->prefiltered && h_counters[1]) return fail(LG_ERR_PREFILTERED, "Point is filtered although prefiltered is set. This shouldn't happen!");
             if (h_counters[0] & 1u) return fail(LG_ERR_INVALID_ARGUMENT, "more than 2^32-1 tile instances in one view");
         }
-        R = h_counters[3];
-        if (R >= (1ll << 30)) return fail(LG_ERR_INVALID_ARGUMENT, "more than 2^30-1 tile instances in one view");
-        kp = make_key_plan(ntiles, N, h_counters[2], v->flags);
-        void* bin_p = alloc(alloc_user, carve_bin(nullptr, R, W, H, S).total);
+        cap = h_counters[3];
+        if (cap >= (1ll << 30)) return fail(LG_ERR_INVALID_ARGUMENT, "more than 2^30-1 tile instances in one view");
+        kp = make_key_plan(q.ntiles, N, h_counters[2], v->flags);
+        plan = make_forward_plan(v->flags, count, weight_policy, N, cap);
+        void* bin_p = alloc(alloc_user, carve_bin(nullptr, cap, q.W, q.H, q.S).total);
         if (!bin_p) return fail(LG_ERR_ALLOC, "binning allocator returned NULL");
         if (binning_out) *binning_out = bin_p;
-        bin = carve_bin(bin_p, R, W, H, S);
-        cap = R;
-        if (num_rendered) *num_rendered = R;
-        if (R == 0) HIP_TRY(lg_zero_async(bin.ranges, (size_t)ntiles * 8, stream)); // otherwise cleared by lg_duplicate
-    } else {
-        // (bounded->status is written by lg_scan_blocks itself, or cleared above for N == 0: no copy node)
-        // (validated mode: K2 wrote the words into vslot.p itself; the host looks at them at the end of this function)
+        bin = carve_bin(bin_p, cap, q.W, q.H, q.S);
+        if (num_rendered) *num_rendered = cap;
+        if (cap == 0) HIP_TRY(lg_zero_async(bin.ranges, (size_t)q.ntiles * 8, stream)); // otherwise cleared by lg_duplicate
     }
-    g_stats.num_rendered = bounded ? -1 : R;
+    // (bounded->status is written by lg_scan_blocks itself, or cleared above for N == 0: no copy node; validated mode: K2 wrote the
+    // words into vslot.p itself and the host looks at them in epilogue())
+    g_stats.num_rendered = bounded ? -1 : cap;
     g_stats.num_visible = -1; // not tracked on the device (see lg_preprocess); callers count radii > 0
+    return LG_OK;
+}
 
+int Forward::binning()
+{
+    if (!plan.live) return LG_OK;
     const int sort_begin = kp.sort_begin(), sort_end = kp.sort_end();
-    if (cap > 0 && N > 0) {
-        const LgSortLayout SL = lg_sort_layout((size_t)cap);
-        // one clear for the digit histograms, the tile tickets and the look-back states of every radix pass (exact forward: the
-        // buffer was allocated a moment ago; the bounded forward's K1 did it already)
-        if (!k1_clear) HIP_TRY(lg_zero_async(bin.sort_temp, lg_sort_clear_bytes(SL, (unsigned)((sort_end - sort_begin + 7) / 8)), stream));
-        uint32_t* hist = (uint32_t*)((char*)bin.sort_temp + SL.hist_off);
-        {
-            ProfScope ps(prof, "duplicate", stream);
-            const int dgrid = std::max(1, std::min((nblk + 4 * LG_DUP_WAVES - 1) / (4 * LG_DUP_WAVES), LG_DUP_GRID));
-            lg_duplicate<<<dgrid, LG_DUP_THREADS, 0, stream>>>(N, nblk, gx, kp.stored(), kp.store_drop, kp.gid_bits, sort_begin, sort_end, (uint32_t)cap, geo.touched,
-                                                              geo.blk_off, geo.part_prefix, geo.counters, geo.offsets, geo.tinfo, bin.keys_in, ntiles, bin.ranges, hist,
-                                                              kp.two_stage ? 0xFFFFFFFFu : 0u, bin.long_tiles);
-        }
-        KCHECK("lg_duplicate");
-        {
-            ProfScope ps(prof, "sort", stream);
-            size_t tb = bin.sort_temp_bytes;
-            // two-stage scheme: the last pass also leaves the tile ranges (no lg_tile_ranges launch)
-            HIP_TRY(lg_sort_keys(bin.sort_temp, tb, bin.keys_in, bin.entries, (uint32_t)cap, sort_begin, sort_end, geo.counters, true, stream,
-                                 LG_SORT_POLL_BUDGET, kp.two_stage ? bin.ranges : nullptr, kp.tile_shift()));
-        }
-        KCHECK("lg_sort_keys");
-        if (!kp.two_stage) {
-            ProfScope ps(prof, "tile_ranges", stream);
-            const uint32_t rgrid = (uint32_t)((cap + 255) / 256);
-            lg_tile_ranges<<<rgrid, 256, 0, stream>>>(geo.counters, kp.tile_shift(), kp.gid_bits, kp.gid_mask, kp.two_stage ? 0 : kp.store_drop, kp.store_drop,
-                                                      bin.entries, bin.keys_in, geo.tinfo, bin.ranges, bounded ? bounded->status : nullptr);
-        }
-        KCHECK("lg_tile_ranges");
-        if (kp.two_stage) {
-            // second stage: one WAVE per tile orders its list by depth in LDS (lists up to 1024 entries; up to 4096: a whole workgroup,
-            // same launch); the few longer ones go through a persistent grid of 1024-thread workgroups (an empty launch otherwise)
-            ProfScope ps(prof, "tile_sort", stream);
-            lg_tile_sort<<<(ntiles + 3) / 4 + ntiles, LG_TS_THREADS, 0, stream>>>(ntiles, geo.counters, bin.ranges, bin.entries, kp.gid_bits, kp.gid_mask, kp.store_drop,
-                                                                                  kp.depth_bits, geo.tinfo, bin.long_tiles, bounded ? bounded->status : nullptr);
-            lg_tile_sort_long<<<std::min(ntiles, LG_TL_GRID), LG_TL_THREADS, 0, stream>>>(geo.counters, bin.ranges, bin.entries, bin.keys_in, kp.gid_bits, kp.gid_mask,
-                                                                                          kp.store_drop, kp.depth_bits, geo.tinfo, bin.long_tiles);
-            KCHECK("lg_tile_sort");
-        }
-    }
-    const uint32_t gid_mask = kp.gid_mask;
-    // (count / score accumulators of the count variant were cleared by lg_preprocess)
-    // Long tiles of the hardware-exp colour forward: which lists go through the parallel kernels below is decided ON THE DEVICE
-    // from this view's own instance count (lg_par_min, lg_binning.h) -- no history, no host hint: two renders of the same
-    // inputs run the same kernels on the same lists whatever the process rendered before.  LG_FLAG_LONG_SERIAL / _PARALLEL
-    // override the default rule per call; the canonical / count variants always walk serially (bit-pinned).
-    // Round 5: the significance-only pass (count forward, canonical arithmetic, no colour, integer weights) has a parallel long-tile walk
-    // of its own (lg_count_seg / _rewalk / _fixup: bit-identical counts through interval comparisons + an exact fix-up); count forwards
-    // that return an image and the float weight policies walk serially.
-    const bool cnt_par = count && !fast && (v->flags & LG_FLAG_SKIP_COLOR) && (weight_policy == LG_WEIGHT_ONE || weight_policy == LG_WEIGHT_OPACITY);
-    // The default rule ("auto") applies to the colour forward only.  For the significance pass it was measured and lost (heavy-tailed scene,
-    // four views in flight as prune_list_sharded runs them: 1150 views/s against 1497 serial): the serial walk of a pile stops
-    // early in every wave whose pixels saturate, the parallel one walks every segment twice, and with other views in flight the device is
-    // never idle behind the one long walk -- total work decides, not the critical path.  LG_FLAG_LONG_PARALLEL selects it explicitly.
-    const int long_mode = (!count && fast && cap > 0 && N > 0) ? ((v->flags & LG_FLAG_LONG_SERIAL) ? 0 : (v->flags & LG_FLAG_LONG_PARALLEL) ? 2 : 1)
-                        : (cnt_par && cap > 0 && N > 0 && (v->flags & LG_FLAG_LONG_PARALLEL)) ? 2 : 0;
-    const bool par_long = long_mode != 0;
+    const LgSortLayout SL = lg_sort_layout((size_t)cap);
+    // one clear for the digit histograms, the tile tickets and the look-back states of every radix pass (exact forward: the
+    // buffer was allocated a moment ago; the bounded forward's K1 did it already)
+    if (!k1_cleared_sort) HIP_TRY(lg_zero_async(bin.sort_temp, lg_sort_clear_bytes(SL, (unsigned)kp.sort_passes()), stream));
+    uint32_t* hist = (uint32_t*)((char*)bin.sort_temp + SL.hist_off);
     {
-        ProfScope ps(prof, count ? "blend_fwd_count" : "blend_fwd", stream);
-        // + 1: the last workgroup builds the backward's work list from the tile ranges (colour forwards only: the
-        // significance-only pass has no backward)
-        const bool nocolor_pass = count && !fast && (v->flags & LG_FLAG_SKIP_COLOR);
-        dim3 grid(ntiles_pad + ((nocolor_pass && !par_long) ? 0 : 1)), block(256);     // (the parallel long-tile walk needs the par_work list)
-#define LAUNCH_FWD(CNT, FS, EX, COL)                                                                                                 \
-    lg_blend_fwd<CNT, FS, EX, COL><<<grid, block, 0, stream>>>(W, H, gx, ntiles, ntiles_pad, bin.ranges, bin.entries, gid_mask, geo.rec, v->bg, \
-                                                         out_color, img.final_T, img.n_contrib, out_count, (unsigned long long*)bin.keys_in, geo.tinfo, (uint32_t)cap, S, bin.ckpt, bin.work, bin.meta, bin.par_work, geo.counters, long_mode, bin.par_arrived)
-        // per-hit weights (ALPHA / ALPHA_T): the kernel is instantiated per policy and adds {count | Q8.40 weight} words into the instances'
-        // pre-sort slots -- the radix sort's input buffer, free since lg_tile_sort and cleared here
-        const int fs = !count ? 0 : weight_policy == LG_WEIGHT_ALPHA ? 2 : weight_policy == LG_WEIGHT_ALPHA_T ? 3 : 0;
-        // (the significance-only variant writes every slot exactly once -- its waves merge in LDS -- and needs no clear)
-        if (fs && cap > 0 && N > 0 && !(!fast && (v->flags & LG_FLAG_SKIP_COLOR))) HIP_TRY(lg_zero_async(bin.keys_in, (size_t)cap * 8, stream));
-        const bool nocolor = count && !fast && (v->flags & LG_FLAG_SKIP_COLOR);   // significance-only pass: no colour, no per-pixel outputs
-        if (!count) { if (fast) LAUNCH_FWD(false, 0, false, true); else LAUNCH_FWD(false, 0, true, true); }
-        else if (nocolor) {
-            if (fs == 2) LAUNCH_FWD(true, LG_W_ALPHA, true, false);
-            else if (fs == 3) LAUNCH_FWD(true, LG_W_ALPHA_T, true, false);
-            else LAUNCH_FWD(true, 0, true, false);
-        }
-        else if (!fs) { if (fast) LAUNCH_FWD(true, 0, false, true); else LAUNCH_FWD(true, 0, true, true); }
-        else if (fs == 2) { if (fast) LAUNCH_FWD(true, LG_W_ALPHA, false, true); else LAUNCH_FWD(true, LG_W_ALPHA, true, true); }
-        else { if (fast) LAUNCH_FWD(true, LG_W_ALPHA_T, false, true); else LAUNCH_FWD(true, LG_W_ALPHA_T, true, true); }
-#undef LAUNCH_FWD
+        ProfScope ps(prof, "duplicate", stream);
+        const int dgrid = std::max(1, std::min((nblk + 4 * LG_DUP_WAVES - 1) / (4 * LG_DUP_WAVES), LG_DUP_GRID));
+        lg_duplicate<<<dgrid, LG_DUP_THREADS, 0, stream>>>(N, nblk, q.gx, kp.stored(), kp.store_drop, kp.gid_bits, sort_begin, sort_end, (uint32_t)cap, geo.touched,
+                                                          geo.blk_off, geo.part_prefix, geo.counters, geo.offsets, geo.tinfo, bin.keys_in, q.ntiles, bin.ranges, hist,
+                                                          kp.two_stage ? 0xFFFFFFFFu : 0u, bin.long_tiles);
+    }
+    KCHECK("lg_duplicate");
+    {
+        ProfScope ps(prof, "sort", stream);
+        size_t tb = bin.sort_temp_bytes;
+        // two-stage scheme: the last pass also leaves the tile ranges (no lg_tile_ranges launch)
+        HIP_TRY(lg_sort_keys(bin.sort_temp, tb, bin.keys_in, bin.entries, (uint32_t)cap, sort_begin, sort_end, geo.counters, true, stream,
+                             LG_SORT_POLL_BUDGET, kp.two_stage ? bin.ranges : nullptr, kp.tile_shift()));
+    }
+    KCHECK("lg_sort_keys");
+    if (!kp.two_stage) {
+        ProfScope ps(prof, "tile_ranges", stream);
+        const uint32_t rgrid = (uint32_t)((cap + 255) / 256);
+        lg_tile_ranges<<<rgrid, 256, 0, stream>>>(geo.counters, kp.tile_shift(), kp.gid_bits, kp.gid_mask, kp.store_drop, kp.store_drop,
+                                                  bin.entries, bin.keys_in, geo.tinfo, bin.ranges, device_status());
+    } else {
+        // second stage: one WAVE per tile orders its list by depth in LDS (lists up to 1024 entries; up to 4096: a whole workgroup,
+        // same launch); the few longer ones go through a persistent grid of 1024-thread workgroups (an empty launch otherwise)
+        ProfScope ps(prof, "tile_sort", stream);
+        lg_tile_sort<<<(q.ntiles + 3) / 4 + q.ntiles, LG_TS_THREADS, 0, stream>>>(q.ntiles, geo.counters, bin.ranges, bin.entries, kp.gid_bits, kp.gid_mask, kp.store_drop,
+                                                                                  kp.depth_bits, geo.tinfo, bin.long_tiles, device_status());
+        lg_tile_sort_long<<<std::min(q.ntiles, LG_TL_GRID), LG_TL_THREADS, 0, stream>>>(geo.counters, bin.ranges, bin.entries, bin.keys_in, kp.gid_bits, kp.gid_mask,
+                                                                                        kp.store_drop, kp.depth_bits, geo.tinfo, bin.long_tiles);
+    }
+    KCHECK("lg_tile_sort");
+    return LG_OK;
+}
+
+int Forward::blend()
+{
+    const int W = q.W, H = q.H, gx = q.gx, S = q.S;
+    const uint32_t gid_mask = kp.gid_mask;
+    {
+        // (count / score accumulators of the count variant were cleared by lg_preprocess; the slots of the per-hit variants that do not merge, here)
+        ProfScope ps(prof, plan.count ? "blend_fwd_count" : "blend_fwd", stream);
+        if (plan.clear_slots) HIP_TRY(lg_zero_async(bin.keys_in, (size_t)cap * 8, stream));
+        const dim3 grid(q.ntiles_pad + (plan.work_list_group ? 1 : 0)), block(256);
+        blend_fwd_kernel(plan)<<<grid, block, 0, stream>>>(W, H, gx, q.ntiles, q.ntiles_pad, bin.ranges, bin.entries, gid_mask, geo.rec, v->bg, out_color, img.final_T,
+                                                           img.n_contrib, out_count, (unsigned long long*)bin.keys_in, geo.tinfo, (uint32_t)cap, S, bin.ckpt,
+                                                           bin.work, bin.meta, bin.par_work, geo.counters, plan.long_mode, bin.par_arrived);
     }
     KCHECK("lg_blend_fwd");
     // (a second HIP stream for the long-tile chain / for the memory-bound front of other views: EXPERIMENTS.md, "streams")
-    if (par_long && cnt_par) {
+    // persistent grids over the par_work list left by the forward's work-list workgroup (meta[4] items; none on scenes
+    // without outlier lists: each launch is then one scalar load per workgroup)
+    const uint32_t pgrid = (uint32_t)std::min<int64_t>((int64_t)q.ntiles + cap / S + 1, LG_PAR_GRID);
+    if (plan.long_chain == LG_CHAIN_COUNT) {
         ProfScope ps(prof, "blend_fwd_count_long", stream);
-        const uint32_t pgrid = (uint32_t)std::min<int64_t>((int64_t)ntiles + cap / S + 1, LG_PAR_GRID);
         const float band_mul = (v->flags & LG_FLAG_COUNT_WIDE_BAND) ? 4096.0f : 1.0f;
         lg_count_seg<<<pgrid, 256, 0, stream>>>(W, H, gx, S, bin.par_work, bin.meta, bin.ranges, bin.entries, gid_mask, geo.rec, bin.ckpt, bin.ckpt_last, bin.par_arrived, band_mul);
         lg_count_rewalk<<<pgrid, 256, 0, stream>>>(W, H, gx, S, bin.par_work, bin.meta, bin.ranges, bin.entries, gid_mask, geo.rec, bin.ckpt, bin.ckpt_last, out_count, band_mul);
         lg_count_fixup<<<std::min<uint32_t>(pgrid, 256u), 256, 0, stream>>>(W, H, gx, S, bin.par_work, bin.meta, bin.ranges, bin.entries, gid_mask, geo.rec, bin.ckpt_last, out_count);
         KCHECK("lg_count_long");
-    } else if (par_long) {
-        // persistent grids over the par_work list left by the forward's work-list workgroup (meta[4] items; none on scenes
-        // without outlier lists: each launch is then one scalar load per workgroup)
+    } else if (plan.long_chain == LG_CHAIN_COLOR) {
         ProfScope ps(prof, "blend_fwd_long", stream);
-        const uint32_t pgrid = (uint32_t)std::min<int64_t>((int64_t)ntiles + cap / S + 1, LG_PAR_GRID);
         // (pass 2, the per-tile scan, runs inside the first launch: the workgroup that finishes a tile's last segment does it)
         lg_blend_fwd_seg<<<pgrid, 256, 0, stream>>>(W, H, gx, S, bin.par_work, bin.meta, bin.ranges, bin.entries, gid_mask, geo.rec, bin.ckpt, bin.ckpt_last,
                                                    bin.par_arrived, v->bg, out_color, img.final_T, img.n_contrib);
@@ -380,14 +344,25 @@ static int forward_impl(const lg_view* v, const lg_gaussians* g, void* geom_p, v
                                                       out_color, img.final_T, img.n_contrib, bin.ckpt, bin.ckpt_last);
         KCHECK("lg_blend_fwd_long");
     }
-    if (count && N > 0) {
+    return LG_OK;
+}
+
+int Forward::score()
+{
+    if (plan.score == LG_SCORE_NONE) return LG_OK;
+    {
         ProfScope ps(prof, "score", stream);
-        if (weight_policy == LG_WEIGHT_ONE || weight_policy == LG_WEIGHT_OPACITY)
-            lg_score_kernel<<<(N + 255) / 256, 256, 0, stream>>>(N, out_count, weight_policy == LG_WEIGHT_OPACITY ? g->opacities : nullptr, out_score, v->count_sum);
-        else
+        if (plan.score == LG_SCORE_SLOTS)
             lg_score_slots<<<(N + 255) / 256, 256, 0, stream>>>(N, geo.touched, geo.offsets, (const unsigned long long*)bin.keys_in, (uint32_t)cap, out_count, out_score, v->count_sum, geo.counters);
-        KCHECK("lg_score_kernel");
+        else
+            lg_score_kernel<<<(N + 255) / 256, 256, 0, stream>>>(N, out_count, plan.score == LG_SCORE_COUNT_OPACITY ? g->opacities : nullptr, out_score, v->count_sum);
     }
+    KCHECK("lg_score_kernel");
+    return LG_OK;
+}
+
+int Forward::epilogue()
+{
     if (debug && N > 0) {
         // debug: the abort word as it stands at the END of the view (the radix sort's look-back can only report after K2)
         uint32_t h_abort = 0;
@@ -417,6 +392,35 @@ static int forward_impl(const lg_view* v, const lg_gaussians* g, void* geom_p, v
     }
     return LG_OK;
 }
+
+static int forward_impl(const lg_view* v, const lg_gaussians* g, void* geom_p, void* img_p, lg_alloc_fn alloc, void* alloc_user,
+                        const Bounded* bounded, int weight_policy, float* out_color, int32_t* out_radii, int32_t* out_count,
+                        float* out_score, void** binning_out, int64_t* num_rendered, void* stream_p)
+{
+    int rc = check_args(v, g);
+    if (rc != LG_OK) return rc;
+    if (!geom_p || !img_p || !out_color || (!out_radii && g->N > 0) || (!alloc && !bounded)) return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
+    const bool count = out_count != nullptr;
+    if (count && !out_score) return fail(LG_ERR_INVALID_ARGUMENT, "count needs score");
+    if (count && (weight_policy < 0 || weight_policy > 3)) return fail(LG_ERR_INVALID_ARGUMENT, "bad weight policy");
+    // per-hit weights are summed in Q24.40 per view: a Gaussian can collect at most 0.99 per pixel
+    if (count && weight_policy >= LG_WEIGHT_ALPHA && (int64_t)v->image_width * v->image_height > (1ll << 24))
+        return fail(LG_ERR_INVALID_ARGUMENT, "ALPHA / ALPHA_T weights: images beyond 2^24 pixels overflow the Q24.40 per-view sums");
+    Forward f{};
+    f.v = v; f.g = g; f.bounded = bounded; f.alloc = alloc; f.alloc_user = alloc_user; f.weight_policy = weight_policy;
+    f.out_color = out_color; f.out_radii = out_radii; f.out_count = out_count; f.out_score = out_score;
+    f.binning_out = binning_out; f.num_rendered = num_rendered;
+    f.stream = (hipStream_t)stream_p; f.debug = v->flags & LG_FLAG_DEBUG; f.prof = v->flags & LG_FLAG_PROFILE;
+    f.N = g->N; f.nblk = (f.N + LG_PP - 1) / LG_PP;
+    f.q = view_geom(v, f.N);
+    f.geo = carve_geom(geom_p, f.N);
+    f.img = carve_img(img_p, f.q.W, f.q.H);
+    if (binning_out) *binning_out = nullptr;
+    if (num_rendered) *num_rendered = 0;
+    if ((rc = f.front_end()) != LG_OK || (rc = f.binning()) != LG_OK || (rc = f.blend()) != LG_OK || (rc = f.score()) != LG_OK) return rc;
+    return f.epilogue();
+}
+
 
 extern "C" int lg_forward(const lg_view* view, const lg_gaussians* g, void* geom, void* img, lg_alloc_fn alloc, void* alloc_user,
                           float* out_color, int32_t* out_radii, void** binning_out, int64_t* num_rendered, void* stream)
@@ -462,29 +466,21 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
         (g->cov3D_precomp && !dL_dcov3D))
         return fail(LG_ERR_INVALID_ARGUMENT, "missing gradient output for a provided input");
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, fast = v->flags & LG_FLAG_FAST_EXP;
-    const int N = g->N, W = v->image_width, H = v->image_height;
-    if (N == 0) return LG_OK;
-    const int gx = (W + LG_TILE - 1) / LG_TILE, gy = (H + LG_TILE - 1) / LG_TILE, ntiles = gx * gy;
-    const int ntiles_pad = (ntiles + LG_TILE_GRID_ALIGN - 1) / LG_TILE_GRID_ALIGN * LG_TILE_GRID_ALIGN; // grid of the per-tile kernels
+    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE;
+    const int N = g->N;
+    const ViewGeom q = view_geom(v, N);     // S must be the forward's (same lg_view); the kernels compare it with meta[2] and refuse otherwise
+    const int W = q.W, H = q.H, S = q.S;
     GeomView geo = carve_geom(const_cast<void*>(geom_p), N);
     ImgView img = carve_img(const_cast<void*>(img_p), W, H);
-    const int S = lg_segment_of(v);   // must be the forward's (same lg_view); the kernels compare it with meta[2] and refuse otherwise
     BinView bin = carve_bin(const_cast<void*>(bin_p), R, W, H, S);
-    const int gid_bits = bits_for((uint32_t)(N > 1 ? N : 2));          // same field width as the forward used
-    const uint32_t gid_mask = gid_bits >= 32 ? 0xFFFFFFFFu : ((1u << gid_bits) - 1u);
     float* rows = (float*)scratch; // [R][12] gradient rows, every row written by lg_blend_bwd
-    const uint32_t max_items = (uint32_t)(ntiles + R / S + 1);
+    const uint32_t max_items = (uint32_t)(q.ntiles + R / S + 1);
     // (the work list of the backward blend -- one item per (tile, segment of S entries), longest first -- was left in the binning
     // buffer by the forward: one extra workgroup of lg_blend_fwd)
     if (R > 0) {
         ProfScope ps(prof, "blend_bwd", stream);
-        if (fast)
-            lg_blend_bwd<false><<<max_items, 64, 0, stream>>>(W, H, gx, S, bin.work, bin.meta, bin.ranges, bin.entries, gid_mask, geo.tinfo, geo.rec, v->bg,
-                                                              img.final_T, img.n_contrib, dL_dcolor, bin.ckpt, rows);
-        else
-            lg_blend_bwd<true><<<max_items, 64, 0, stream>>>(W, H, gx, S, bin.work, bin.meta, bin.ranges, bin.entries, gid_mask, geo.tinfo, geo.rec, v->bg,
-                                                             img.final_T, img.n_contrib, dL_dcolor, bin.ckpt, rows);
+        blend_bwd_kernel(!(v->flags & LG_FLAG_FAST_EXP))<<<max_items, 64, 0, stream>>>(W, H, q.gx, S, bin.work, bin.meta, bin.ranges, bin.entries, q.gid_mask, geo.tinfo,
+                                                                                       geo.rec, v->bg, img.final_T, img.n_contrib, dL_dcolor, bin.ckpt, rows);
     }
     KCHECK("lg_blend_bwd");
     {
@@ -498,17 +494,13 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
         const int per = (nblk + chunks - 1) / chunks;
         for (int first_blk = 0; first_blk < nblk; first_blk += per) {
             const int nb = std::min(per, nblk - first_blk);
-#define LAUNCH_PPB(RAWP, JACP)                                                                                                       \
-    lg_preprocess_bwd<RAWP, JACP><<<nb, LG_PP, 0, stream>>>(                                                                                \
-        N, first_blk, g->M, v->sh_degree, W, H, v->tanfovx, v->tanfovy, v->scale_modifier, v->viewmatrix, v->projmatrix, v->campos, g->means3D,  \
-        g->shs, g->shs_rest, g->colors_precomp, g->opacities, g->scales, g->rotations, g->cov3D_precomp, radii, geo.rec,   \
-        geo.counters, bin.meta, (uint32_t)S, geo.touched, geo.offsets, reinterpret_cast<const float4*>(rows), geo.shjac, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dshs_rest, dL_dcolors, dL_dopacity,   \
-        dL_dscales, dL_drotations, dL_dcov3D)
             // (the view of a backward is the view of its forward: LG_FLAG_SAVE_SH_JACOBIAN says K1 left the SH direction Jacobians)
             const bool jac = (v->flags & LG_FLAG_SAVE_SH_JACOBIAN) && g->shs && (dL_dshs || rgb_only);
-            if (v->flags & LG_FLAG_RAW_PARAMS) { if (jac) LAUNCH_PPB(true, true); else LAUNCH_PPB(true, false); }
-            else { if (jac) LAUNCH_PPB(false, true); else LAUNCH_PPB(false, false); }
-#undef LAUNCH_PPB
+            preprocess_bwd_kernel(v->flags & LG_FLAG_RAW_PARAMS, jac)<<<nb, LG_PP, 0, stream>>>(
+                N, first_blk, g->M, v->sh_degree, W, H, v->tanfovx, v->tanfovy, v->scale_modifier, v->viewmatrix, v->projmatrix, v->campos, g->means3D,
+                g->shs, g->shs_rest, g->colors_precomp, g->opacities, g->scales, g->rotations, g->cov3D_precomp, radii, geo.rec, geo.counters, bin.meta,
+                (uint32_t)S, geo.touched, geo.offsets, reinterpret_cast<const float4*>(rows), geo.shjac, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dshs_rest,
+                dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D);
             if (on_chunk) on_chunk(user, first_blk * LG_PP, std::min(N - first_blk * LG_PP, nb * LG_PP));
         }
     }
@@ -858,10 +850,9 @@ extern "C" int lg_debug_tile_lists(const lg_view* v, const void* bin_p, int64_t 
 {
     if (!v || !bin_p || !out_ranges || !out_entries || R < 0 || v->image_width <= 0 || v->image_height <= 0)
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_debug_tile_lists: missing buffer");
-    const int W = v->image_width, H = v->image_height;
-    const size_t ntiles = (size_t)((W + LG_TILE - 1) / LG_TILE) * ((H + LG_TILE - 1) / LG_TILE);
-    BinView bin = carve_bin(const_cast<void*>(bin_p), R, W, H, lg_segment_of(v));
-    hipError_t e = hipMemcpyAsync(out_ranges, bin.ranges, ntiles * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream_p);
+    const ViewGeom q = view_geom(v, 0);
+    BinView bin = carve_bin(const_cast<void*>(bin_p), R, q.W, q.H, q.S);
+    hipError_t e = hipMemcpyAsync(out_ranges, bin.ranges, (size_t)q.ntiles * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream_p);
     if (e == hipSuccess && R > 0) e = hipMemcpyAsync(out_entries, bin.entries, (size_t)R * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream_p);
     if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_debug_tile_lists copy", e);
     return LG_OK;
@@ -870,7 +861,8 @@ extern "C" int lg_debug_tile_lists(const lg_view* v, const void* bin_p, int64_t 
 extern "C" int lg_debug_view_meta(const lg_view* v, const void* bin_p, int64_t R, uint32_t* out_meta16, void* stream_p)
 {
     if (!v || !bin_p || !out_meta16 || R < 0 || v->image_width <= 0 || v->image_height <= 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_debug_view_meta: missing buffer");
-    BinView bin = carve_bin(const_cast<void*>(bin_p), R, v->image_width, v->image_height, lg_segment_of(v));
+    const ViewGeom q = view_geom(v, 0);
+    BinView bin = carve_bin(const_cast<void*>(bin_p), R, q.W, q.H, q.S);
     hipError_t e = hipMemcpyAsync(out_meta16, bin.meta, 64, hipMemcpyDeviceToDevice, (hipStream_t)stream_p);
     if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_debug_view_meta copy", e);
     return LG_OK;
@@ -881,14 +873,13 @@ extern "C" int lg_debug_last_contributor(const lg_view* v, int32_t N, const void
 {
     if (!v || N <= 0 || !geom_p || !bin_p || !img_p || !out_ids || v->image_width <= 0 || v->image_height <= 0)
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_debug_last_contributor: missing buffer");
-    const int W = v->image_width, H = v->image_height, gx = (W + LG_TILE - 1) / LG_TILE;
+    const ViewGeom q = view_geom(v, N);
+    const int W = q.W, H = q.H;
     GeomView geo = carve_geom(const_cast<void*>(geom_p), N);
     ImgView img = carve_img(const_cast<void*>(img_p), W, H);
-    BinView bin = carve_bin(const_cast<void*>(bin_p), R, W, H, lg_segment_of(v));
-    const int gid_bits = bits_for((uint32_t)(N > 1 ? N : 2));
-    const uint32_t gid_mask = gid_bits >= 32 ? 0xFFFFFFFFu : ((1u << gid_bits) - 1u);
+    BinView bin = carve_bin(const_cast<void*>(bin_p), R, W, H, q.S);
     const size_t P = (size_t)W * H;
-    lg_debug_last_contributor_kernel<<<(unsigned)((P + 255) / 256), 256, 0, (hipStream_t)stream_p>>>(W, H, gx, bin.ranges, bin.entries, gid_mask, img.n_contrib,
+    lg_debug_last_contributor_kernel<<<(unsigned)((P + 255) / 256), 256, 0, (hipStream_t)stream_p>>>(W, H, q.gx, bin.ranges, bin.entries, q.gid_mask, img.n_contrib,
                                                                                                   geo.counters, out_ids);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_debug_last_contributor launch", e);

@@ -18,7 +18,7 @@
 // (Two single-workgroup versions of this kernel -- a load per iteration, then all loads in flight from registers -- both
 // measured 50 us at C3: a lone workgroup on an otherwise idle device is slow whatever it does; so are the 10 us of
 // lg_work_order's 8160 tiles.  46 workgroups finish the same work in a few microseconds.)
-#define LG_DEPTH_BIAS (124u << 23) // bit pattern of 0.125f < the 0.2 near plane
+// (LG_DEPTH_BIAS, the bias the depth patterns of the keys are stored with: lg_plan.h, next to the key layout)
 #define LG_PART 1024               // words per part = threads per workgroup
 
 __global__ void __launch_bounds__(LG_PART)

@@ -16,6 +16,7 @@
 #include "../../include/lightgaussian.h"
 #include "../../include/lightgaussian_debug.h"
 #include "lg_math.h"
+#include "lg_plan.h"
 
 // ------------------------------------------------------------------------------------------------
 // error plumbing
@@ -181,12 +182,6 @@ struct BinView {
                                     //     then -- per-hit weight policies -- the per-instance {count | weight} words of lg_blend_fwd<COUNT, FSCORE>
     void* sort_temp; size_t sort_temp_bytes; size_t total;
 };
-static int bits_for(uint32_t n) // smallest b with 2^b >= n
-{
-    int b = 0;
-    while (b < 32 && (1ull << b) < n) b++;
-    return b;
-}
 static BinView carve_bin(void* base, int64_t R, int W, int H, int seg)
 {
     BinView v; memset(&v, 0, sizeof(v)); size_t off = 0; char* p = (char*)base;

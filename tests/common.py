@@ -64,6 +64,29 @@ def harness():
     return lib
 
 
+_PLAN_HARNESS = None
+
+
+def plan_harness():
+    """g++ build of the product's host-side plans (lg_plan.h: KeyPlan, ForwardPlan), next to the math harness."""
+    global _PLAN_HARNESS
+    if _PLAN_HARNESS is not None:
+        return _PLAN_HARNESS
+    d = os.path.join(ROOT, "tests", "cpu_harness")
+    so = os.path.join(d, "liblg_plan_harness.so")
+    srcs = [os.path.join(d, "lg_plan_harness.cpp"), os.path.join(ROOT, "lightgaussian_amd", "csrc", "lg_plan.h"),
+            os.path.join(ROOT, "include", "lightgaussian.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-Wall", "-Wextra", "-Werror", srcs[0], "-o", so])
+    lib = C.CDLL(so)
+    lib.h_key_plan.restype = None
+    lib.h_key_plan.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.h_forward_plan.restype = None
+    lib.h_forward_plan.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
+    _PLAN_HARNESS = lib
+    return lib
+
+
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
