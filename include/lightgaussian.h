@@ -285,6 +285,25 @@ size_t lg_vq_scratch_bytes(int32_t K, int32_t d);
 int lg_vq_nearest(int32_t n, int32_t d, int32_t K, const float* x, const float* codebook, int32_t* out_index, void* scratch,
                   uint32_t flags, void* stream);
 
+/* --- VecTree codebook training step ----------------------------------------------------------------
+ * One iteration of the importance-weighted EMA k-means of vectree/vq.py:262-299 (EuclideanCodebook.forward in training mode,
+ * temperature 0, no DDP, threshold_ema_dead_code 0), as vectree/vectree.py:196-204 drives it (n = 80 000 sampled rows, K = 8192,
+ * d = 27 / 48).  With w = weight * n / sum(weight) (all ones when weight is NULL):
+ *     out_index[i] = argmin_c |x[i] - embed[c]|^2 on the codebook as handed in (lg_vq_nearest, ties to the lowest c)
+ *     size[c] = sum of w[i], esum[c] = sum of w[i] * x[i] over the rows with out_index[i] == c
+ *     cluster_size <- decay * cluster_size + (1 - decay) * size
+ *     smoothed = (cluster_size + eps) / (sum(cluster_size) + K * eps) * sum(cluster_size)          (the updated cluster_size)
+ *     embed <- decay * embed + (1 - decay) * esum / smoothed[:, None]                              (a code without rows decays)
+ * x [n,d], weight [n] or NULL, embed [K,d] in/out, cluster_size [K] in/out: fp32 device; out_index [n] int32.
+ * No n x K intermediate and no float atomics: the rows of every code are listed in ascending row order (stable radix sort of
+ * (code, row) on the code bits) and added in that order inside chunks of 256 rows; a code's chunk sums are added in chunk order
+ * -- the result is a function of the inputs alone, bit for bit.  Every launch on `stream`, no host synchronisation; an all-zero
+ * weight gives the reference's NaN.  scratch: lg_vq_ema_scratch_bytes(n, K, d), linear in n and K * d; 0 for the shapes
+ * lg_vq_scratch_bytes refuses (and for n >= 2^30).  lg_vq_ema_step needs n >= 1. */
+size_t lg_vq_ema_scratch_bytes(int32_t n, int32_t K, int32_t d);
+int lg_vq_ema_step(int32_t n, int32_t d, int32_t K, const float* x, const float* weight, float* embed, float* cluster_size,
+                   double decay, double eps, int32_t* out_index, void* scratch, uint32_t flags, void* stream);
+
 /* out[j] = (((rows[0][j] + rows[1][j]) + rows[2][j]) + ...) over V rows of n floats (row pitch row_stride floats): the
  * sequential in-place float accumulation of per-view scores in prune.py:144-155, in view order, as one launch. */
 int lg_ordered_sum(int32_t V, int64_t n, const float* rows, int64_t row_stride, float* out, void* stream);

@@ -12,6 +12,7 @@
 //   lg_knn.h         distCUDA2 (simple-knn): exact 3-nearest-neighbour mean squared distance on a multi-level uniform grid
 //   lg_compact.h     lg_compact_plan / lg_compact_rows: one scan + one launch compacting all Gaussian tensors after a prune
 //   lg_vq.h          lg_vq_nearest: nearest-code search of the VecTree quantiser on f32 MFMA (32x32x2), fused row argmin
+//   lg_vq_train.h    lg_vq_ema_step: one EMA k-means step of the VecTree codebook (search, inverted index, ordered segmented sum, EMA)
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound)
 //
 // Pipeline of one view:
@@ -33,6 +34,7 @@
 #include "lg_knn.h"
 #include "lg_compact.h"
 #include "lg_vq.h"
+#include "lg_vq_train.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -725,6 +727,66 @@ extern "C" int lg_vq_nearest(int32_t n, int32_t d, int32_t K, const float* x, co
     }
 #undef LAUNCH_VQ
     KCHECK("lg_vq_nearest_kernel");
+    return LG_OK;
+}
+
+// ---- VecTree codebook training step (vectree/vq.py:262-299, training mode) ----
+extern "C" size_t lg_vq_ema_scratch_bytes(int32_t n, int32_t K, int32_t d)
+{
+    if (n < 0 || n >= (1 << 30) || lg_vq_scratch_bytes(K, d) == 0) return 0;
+    return carve_vq_ema(nullptr, (size_t)n, (size_t)K, (size_t)d).total;
+}
+
+extern "C" int lg_vq_ema_step(int32_t n, int32_t d, int32_t K, const float* x, const float* weight, float* embed, float* cluster_size,
+                              double decay, double eps, int32_t* out_index, void* scratch, uint32_t flags, void* stream_p)
+{
+    if (n <= 0 || n >= (1 << 30) || K <= 0 || d <= 0 || lg_vq_dk2(d) == 0)
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_ema_step: need 1 <= n < 2^30, K >= 1, 1 <= d <= 63");
+    if (!x || !embed || !cluster_size || !out_index || !scratch) return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = flags & LG_FLAG_DEBUG, prof = flags & LG_FLAG_PROFILE;
+    const VqEmaView v = carve_vq_ema(scratch, (size_t)n, (size_t)K, (size_t)d);
+    {
+        ProfScope ps(prof, "vq_ema_search", stream);
+        const int rc = lg_vq_nearest(n, d, K, x, embed, out_index, v.cbA, flags & ~(uint32_t)LG_FLAG_PROFILE, stream_p);
+        if (rc != LG_OK) return rc;
+    }
+    const uint32_t un = (uint32_t)n, uK = (uint32_t)K;
+    const uint32_t nwpart = (un + LG_VQ_WSUM_TILE - 1) / LG_VQ_WSUM_TILE;
+    int code_bits = 1;
+    while (code_bits < 31 && (1u << code_bits) < uK) code_bits++;
+    const uint32_t* sort_err = (const uint32_t*)((char*)v.sort_temp + lg_sort_layout((size_t)n).ticket_off) + 15;
+    {
+        ProfScope ps(prof, "vq_ema_index", stream);
+        lg_vq_keys<<<nwpart, 256, 0, stream>>>(un, uK, out_index, weight, v.keys_in, v.wpart);
+        KCHECK("lg_vq_keys");
+        size_t tb = v.sort_temp_bytes;
+        HIP_TRY(lg_sort_keys(v.sort_temp, tb, v.keys_in, v.keys_out, un, 32, 32 + code_bits, nullptr, false, stream));
+        KCHECK("lg_sort_keys");
+        lg_vq_starts<<<(un + 255) / 256, 256, 0, stream>>>(un, uK, v.keys_out, v.start);
+        KCHECK("lg_vq_starts");
+        lg_vq_chunk_scan<<<1, LG_VQ_RED_THREADS, 0, stream>>>(uK, v.start, v.chunk_off, nwpart, weight ? v.wpart : nullptr, v.scal);
+        KCHECK("lg_vq_chunk_scan");
+    }
+    const float decay_f = (float)decay, one_minus = (float)(1.0 - decay);      // what torch makes of mul_(decay).add_(new, alpha = 1 - decay)
+    {
+        ProfScope ps(prof, "vq_ema_sum", stream);
+        const unsigned grid = (unsigned)((v.max_chunks + 3) / 4);
+        if (weight) lg_vq_chunk_sum<true><<<grid, 256, 0, stream>>>(un, d, uK, x, weight, v.scal, v.keys_out, v.start, v.chunk_off, v.partial);
+        else lg_vq_chunk_sum<false><<<grid, 256, 0, stream>>>(un, d, uK, x, weight, v.scal, v.keys_out, v.start, v.chunk_off, v.partial);
+        KCHECK("lg_vq_chunk_sum");
+        lg_vq_combine<<<(unsigned)(((size_t)K * (d + 1) + 255) / 256), 256, 0, stream>>>(uK, d, v.chunk_off, v.partial, v.esum, cluster_size, decay_f,
+                                                                                          one_minus, sort_err);
+        KCHECK("lg_vq_combine");
+    }
+    {
+        ProfScope ps(prof, "vq_ema_epilogue", stream);
+        lg_vq_size_sum<<<1, LG_VQ_RED_THREADS, 0, stream>>>(uK, cluster_size, v.scal);
+        KCHECK("lg_vq_size_sum");
+        lg_vq_epilogue<<<(unsigned)(((size_t)K * d + 255) / 256), 256, 0, stream>>>(uK, d, v.esum, cluster_size, v.scal, embed, decay_f, one_minus,
+                                                                                    (float)eps, (float)((double)K * eps));
+        KCHECK("lg_vq_epilogue");
+    }
     return LG_OK;
 }
 

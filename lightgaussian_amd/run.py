@@ -42,6 +42,12 @@ the modules themselves and in every module that already imported them by name --
     scene.gaussian_model.GaussianModel.prune_gaussians lightgaussian_amd.prune.prune_gaussians                    (radix select + the above)
     vectree.vq: -torch.cdist(x, c) -> argmax           lightgaussian_amd.vq.nearest_code                          (both sites: EuclideanCodebook.forward
                                                                                                                    :262-266 and kmeans() :131-137)
+    vectree.vq EuclideanCodebook.forward (training)    lightgaussian_amd.vq.ema_update                            (one_hot + einsum + the two EMAs of :278-298 as
+                                                                                                                   one fused step; every other configuration -- eval,
+                                                                                                                   CPU, cosine, expiry, DDP, temperature -- runs the
+                                                                                                                   reference's own forward)
+The VQ module is found under whatever name it was imported: `vectree.vq`, or top-level `vq` when the script is vectree/vectree.py
+itself (its `from vq import VectorQuantize` resolves through the script's directory, which comes first on sys.path).
 Same signatures, same return values (tests/test_dropin_runner.py asserts the call contracts on the reference's own modules;
 tests/test_gpu_dropin_runner.py runs the body of prune_finetune.py:150-170 through the patched names against the unpatched
 literal path).  unpatch_reference() restores everything.  There is no CPU fallback behind any of these: CPU tensors raise.
@@ -163,7 +169,40 @@ class _LazyNegDist:
         return getattr(self.materialize(), name)
 
 
-def _patch_vq(vq_mod):
+def _fused_train_step_applies(self, x, weight, noop):
+    """EuclideanCodebook.forward may go to vq.ema_update: training mode, the reference-shaped module (cluster_size, embed as a
+    BUFFER -- not learnable --, decay, eps, codebook_size), temperature 0, no code expiry, no DDP reduction, initialised, and a
+    HIP float32 input with d <= 63 whose leading dimension matches the number of codebooks."""
+    import torch
+    if not getattr(self, "training", False):
+        return False
+    bufs = getattr(self, "_buffers", {})
+    if "embed" not in bufs or "cluster_size" not in bufs or not all(hasattr(self, a) for a in ("decay", "eps", "codebook_size", "initted")):
+        return False
+    if getattr(self, "sample_codebook_temp", None) != 0 or getattr(self, "threshold_ema_dead_code", None) != 0:
+        return False
+    if noop is None or getattr(self, "all_reduce_fn", None) is not noop:
+        return False
+    embed, cs = bufs["embed"], bufs["cluster_size"]
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() >= 3 and 1 <= x.shape[-1] <= 63 and x.numel() > 0):
+        return False
+    if not (embed.is_cuda and cs.is_cuda and embed.dtype == torch.float32 and cs.dtype == torch.float32 and embed.dim() == 3
+            and embed.is_contiguous() and cs.is_contiguous() and embed.shape[-1] == x.shape[-1] and embed.shape[1] == self.codebook_size):
+        return False
+    h = 1 if x.dim() < 4 else x.shape[0]
+    if h != embed.shape[0]:
+        return False
+    rows = x.numel() // (h * x.shape[-1])
+    if weight is not None and not (torch.is_tensor(weight) and weight.is_cuda and weight.numel() in (rows, h * rows)):
+        return False
+    if not self.__dict__.get("_lg_initted", False):           # `initted` only ever goes from False to True: read it back once
+        if not bool(self.initted):
+            return False
+        self.__dict__["_lg_initted"] = True
+    return True
+
+
+def _patch_vq(vq_mod, name="vectree.vq"):
     import torch
 
     class _TorchProxy:
@@ -198,10 +237,75 @@ def _patch_vq(vq_mod):
             t = t.materialize()
         return orig_gumbel(t, temperature=temperature, dim=dim)
 
-    _set(vq_mod, "torch", _TorchProxy(), "vectree.vq.torch (cdist -> deferred, argmax -> nearest_code)")
+    _set(vq_mod, "torch", _TorchProxy(), f"{name}.torch (cdist -> deferred, argmax -> nearest_code)")
     _PATCHED.append((vq_mod, "gumbel_sample", orig_gumbel))
     vq_mod.gumbel_sample = gumbel_sample
-    _REPORT["vectree.vq.gumbel_sample"] = {"old": "vectree.vq.gumbel_sample", "new": "lightgaussian_amd.run gumbel_sample -> lightgaussian_amd.vq.nearest_code"}
+    _REPORT[f"{name}.gumbel_sample"] = {"old": f"{name}.gumbel_sample", "new": "lightgaussian_amd.run gumbel_sample -> lightgaussian_amd.vq.nearest_code"}
+
+    cls = vq_mod.EuclideanCodebook
+    orig_forward = cls.forward
+    noop = getattr(vq_mod, "noop", None)
+
+    def forward(self, x, *args, **kwargs):
+        """vectree/vq.py:262-304 EuclideanCodebook.forward(x, weight=None, verbose=False) -> (quantize, embed_ind).  The training
+        step of the reference-shaped module on HIP rows is one fused call (lightgaussian_amd.vq.ema_update, on the module's own
+        buffers, in place); everything else is the original forward."""
+        weight = args[0] if args else kwargs.get("weight")
+        if not _fused_train_step_applies(self, x, weight, noop):
+            return orig_forward(self, x, *args, **kwargs)
+        from . import vq as lg_vq
+        needs_codebook_dim = x.dim() < 4
+        xs = x.unsqueeze(0) if needs_codebook_dim else x
+        shape = xs.shape
+        with torch.no_grad():
+            ind, quant = lg_vq.ema_update(xs.reshape(shape[0], -1, shape[-1]), self.embed, self.cluster_size, weight=weight,
+                                          decay=self.decay, eps=self.eps, return_quantized=True)
+        embed_ind, quantize = ind.view(*shape[:-1]), quant.view(*shape)
+        if needs_codebook_dim:
+            quantize, embed_ind = quantize[0], embed_ind[0]
+        return quantize, embed_ind
+
+    _set(cls, "forward", forward, f"{name}.EuclideanCodebook.forward (training step -> ema_update)")
+
+
+def _is_reference_vq_file(path):
+    return bool(path) and os.path.normpath(path).endswith(os.path.join("vectree", "vq.py"))
+
+
+def _reference_vq_modules():
+    """[(report name, module)]: the reference's vectree/vq.py under every name it is, or is about to be, imported by.
+      vectree.vq   the checkout's root is on sys.path (trainers, tests); skipped when `vectree` resolves to the SCRIPT vectree.py
+                   -- which is no package, and importing it would run the script's own imports
+      vq           vectree/vectree.py run as the script: its directory is first on sys.path and it does `from vq import VectorQuantize`
+    plus any module already loaded from a .../vectree/vq.py that defines EuclideanCodebook and VectorQuantize."""
+    import importlib.util
+    found = []
+
+    def add(name, mod):
+        if mod is not None and all(mod is not m for _, m in found):
+            found.append((name, mod))
+
+    if "vectree.vq" in sys.modules:
+        add("vectree.vq", sys.modules["vectree.vq"])
+    else:
+        try:
+            pkg = sys.modules.get("vectree")
+            is_pkg = hasattr(pkg, "__path__") if pkg is not None else \
+                getattr(importlib.util.find_spec("vectree"), "submodule_search_locations", None) is not None
+        except Exception:  # noqa: BLE001
+            is_pkg = False
+        if is_pkg:
+            add("vectree.vq", _module("vectree.vq"))
+    try:
+        spec = sys.modules["vq"].__spec__ if "vq" in sys.modules else importlib.util.find_spec("vq")
+    except Exception:  # noqa: BLE001
+        spec = None
+    if spec is not None and _is_reference_vq_file(getattr(spec, "origin", None)):
+        add("vq", _module("vq"))
+    for name, mod in list(sys.modules.items()):
+        if _is_reference_vq_file(getattr(mod, "__file__", None)) and hasattr(mod, "EuclideanCodebook") and hasattr(mod, "VectorQuantize"):
+            add(name, mod)
+    return found
 
 
 def patch_reference(verbose=False, data_parallel=False):
@@ -240,10 +344,13 @@ def patch_reference(verbose=False, data_parallel=False):
         gm_cls = (getattr(gm, "GaussianModel", None) if gm is not None else None) or (getattr(sc, "GaussianModel", None) if sc is not None else None)
         dp.install(gm_cls, getattr(sc, "Scene", None) if sc is not None else None)
         _REPORT["data_parallel"] = {"old": "one trajectory per process", "new": "lightgaussian_amd.dp: camera shard per rank + gradient all-reduce before optimizer.step"}
-    vq_mod = _module("vectree.vq")
-    if vq_mod is not None and hasattr(vq_mod, "EuclideanCodebook") and not isinstance(getattr(vq_mod, "torch", None), type(None)) \
-            and type(getattr(vq_mod, "torch")).__name__ != "_TorchProxy":
-        _patch_vq(vq_mod)
+    vq_mods = _reference_vq_modules()
+    if not vq_mods:
+        _REPORT.setdefault("vectree.vq", {"skipped": "vectree/vq.py not importable as vectree.vq or vq"})
+    for name, vq_mod in vq_mods:
+        if hasattr(vq_mod, "EuclideanCodebook") and getattr(vq_mod, "torch", None) is not None \
+                and type(getattr(vq_mod, "torch")).__name__ != "_TorchProxy":
+            _patch_vq(vq_mod, name)
     if verbose:
         for k, v in _REPORT.items():
             print(f"[lightgaussian_amd.run] {k}: {v}", file=sys.stderr)

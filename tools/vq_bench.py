@@ -2,7 +2,17 @@
 """Nearest-code search at the reference's shapes (vectree/vectree.py: 8192-entry codebook, 27 / 48 feature dimensions, 8192-row
 chunks over all Gaussians): lg_vq_nearest (f32 MFMA, fused argmin) next to the reference's torch formulation
 (-torch.cdist(x, embed).argmax(-1), vectree/vq.py:265-266) on the same GPU.  Also times the compaction after a prune
-(prune.compact_tensors vs 21 boolean-index kernels)."""
+(prune.compact_tensors vs 21 boolean-index kernels).
+
+--leg train: one TRAINING iteration of the codebook at the reference's shapes (vectree.py:196-204: n = 80 000 sampled rows,
+K = 8192, d = 27 / 48), device-resident inputs, warm, alternating blocks of
+  (a) the parent path: the reference's formulation with only the search fused -- nearest_code, then one_hot (n x K), the two
+      reductions against it and the two EMAs in torch, written here from the formulas in lightgaussian_amd/vq.py ema_update;
+  (b) vq.ema_update (lg_vq_ema_step).
+Prints ms / iteration of both and their ratio, and checks (b)'s post-state against (a)'s: indices equal, both compared with a
+float64 evaluation from those indices under the parity rule of tests/test_gpu_vq_train.py (4 x (a)'s own deviation, floor
+2^-22).  --fused-only skips (a): the form to run under `rocprofv3 --kernel-trace --stats` for the per-kernel split of (b)."""
+import argparse
 import os
 import sys
 import time
@@ -12,6 +22,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lightgaussian_amd import vq, prune
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--leg", choices=("all", "search", "compact", "train"), default="all")
+ap.add_argument("--iters", type=int, default=200, help="training iterations per timing (train leg)")
+ap.add_argument("--fused-only", action="store_true")
+args = ap.parse_args()
 dev = torch.device("cuda:0")
 
 
@@ -24,7 +39,7 @@ def timed(fn, reps=5):
     return (time.perf_counter() - t0) / reps * 1e3, out
 
 
-for d in (27, 48):
+for d in (27, 48) if args.leg in ("all", "search") else ():
     n, K = 1_200_000, 8192
     g = torch.Generator().manual_seed(d)
     embed = (torch.randn(K, d, generator=g) * 0.3).to(dev)
@@ -42,16 +57,85 @@ for d in (27, 48):
     print(f"vq d={d}: n={n} K={K}  lg_vq_nearest {ms_hip:.2f} ms ({flops / ms_hip / 1e9:.1f} TFLOP/s f32)  torch cdist+argmax {ms_ref:.2f} ms  "
           f"index agreement {agree:.6f}")
 
-N = 3_000_000
-g = torch.Generator().manual_seed(1)
-shapes = [(N, 3), (N, 1, 3), (N, 15, 3), (N, 1), (N, 3), (N, 4)]
-ts = []
-for s in shapes:
-    for _ in range(3):                                    # parameter + two Adam moments
-        ts.append(torch.randn(*s, generator=g).to(dev))
-ts += [torch.rand(N, 1, generator=g).to(dev), torch.rand(N, 1, generator=g).to(dev), torch.rand(N, generator=g).to(dev)]
-keep = (torch.rand(N, generator=g) > 0.66).to(dev)
-ms_hip, outs = timed(lambda: prune.compact_tensors(ts, keep))
-ms_ref, refs = timed(lambda: [t[keep] for t in ts])
-print(f"compaction of 21 tensors at N={N} (keep {int(keep.sum())}): compact_tensors {ms_hip:.2f} ms  torch boolean indexing {ms_ref:.2f} ms  "
-      f"equal {all(torch.equal(a, b) for a, b in zip(outs, refs))}")
+def compact_leg():
+    N = 3_000_000
+    g = torch.Generator().manual_seed(1)
+    shapes = [(N, 3), (N, 1, 3), (N, 15, 3), (N, 1), (N, 3), (N, 4)]
+    ts = []
+    for s in shapes:
+        for _ in range(3):                                    # parameter + two Adam moments
+            ts.append(torch.randn(*s, generator=g).to(dev))
+    ts += [torch.rand(N, 1, generator=g).to(dev), torch.rand(N, 1, generator=g).to(dev), torch.rand(N, generator=g).to(dev)]
+    keep = (torch.rand(N, generator=g) > 0.66).to(dev)
+    ms_hip, outs = timed(lambda: prune.compact_tensors(ts, keep))
+    ms_ref, refs = timed(lambda: [t[keep] for t in ts])
+    print(f"compaction of 21 tensors at N={N} (keep {int(keep.sum())}): compact_tensors {ms_hip:.2f} ms  torch boolean indexing {ms_ref:.2f} ms  "
+          f"equal {all(torch.equal(a, b) for a, b in zip(outs, refs))}")
+
+
+def parent_step(x, w, embed, cluster_size, decay=0.8, eps=1e-5):
+    """The training step as the reference formulates it, with the search already fused (what this package ran before ema_update)."""
+    n, K = x.shape[0], embed.shape[0]
+    wn = (w * n / w.sum()).unsqueeze(1)
+    ind = vq.nearest_code(x, embed)
+    onehot = torch.nn.functional.one_hot(ind, K).to(x.dtype)
+    cluster_size.mul_(decay).add_((onehot * wn).sum(0), alpha=1 - decay)
+    rows_sum = torch.einsum("nd,nc->cd", x * wn, onehot)
+    total = cluster_size.sum()
+    smoothed = (cluster_size + eps) / (total + K * eps) * total
+    embed.mul_(decay).add_(rows_sum / smoothed.unsqueeze(1), alpha=1 - decay)
+    return ind
+
+
+def train_leg(iters, fused_only):
+    import numpy as np
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import vq_train_common as vc                                    # the float64 restatement and the parity rule of the tests
+    for d in (27, 48):
+        n, K = 80_000, 8192
+        g = torch.Generator(device=dev).manual_seed(d)
+        embed0 = torch.randn(K, d, device=dev, generator=g) * 0.3
+        x = embed0[torch.randint(0, K, (n,), device=dev, generator=g)] + 0.1 * torch.randn(n, d, device=dev, generator=g)
+        w = torch.exp(1.5 * torch.randn(n, device=dev, generator=g))          # heavy-tailed importance
+        cs0 = torch.rand(K, device=dev, generator=g) * 10
+
+        def block(step, reps):
+            e, c = embed0.clone(), cs0.clone()
+            step(x, w, e, c); step(x, w, e, c)                                 # warm
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(reps):
+                step(x, w, e, c)
+            t1.record(); t1.synchronize()
+            return t0.elapsed_time(t1)
+
+        fused = lambda x_, w_, e_, c_: vq.ema_update(x_, e_, c_, weight=w_)    # noqa: E731
+        rounds = 4
+        reps = (iters + rounds - 1) // rounds
+        ms_a = ms_b = 0.0
+        for _ in range(rounds):                                                # alternate, so that both see the same clocks
+            if not fused_only:
+                ms_a += block(parent_step, reps)
+            ms_b += block(fused, reps)
+        ms_a, ms_b = ms_a / (rounds * reps), ms_b / (rounds * reps)
+        if fused_only:
+            print(f"vq train d={d}: n={n} K={K}  ema_update {ms_b:.3f} ms / iteration ({rounds * reps} iterations)")
+            continue
+        ea, ca, eb, cb = embed0.clone(), cs0.clone(), embed0.clone(), cs0.clone()
+        ia, ib = parent_step(x, w, ea, ca), vq.ema_update(x, eb, cb, weight=w)
+        same_ind = bool(torch.equal(ia, ib))
+        e64, c64, _, _ = vc.ema_step_f64(x.cpu().numpy(), w.cpu().numpy(), embed0.cpu().numpy(), cs0.cpu().numpy(), ib.cpu().numpy())
+        dev_a = (vc.row_error(ea.cpu().numpy(), e64), vc.row_error(ca.cpu().numpy(), c64))
+        dev_b = (vc.row_error(eb.cpu().numpy(), e64), vc.row_error(cb.cpu().numpy(), c64))
+        ok = same_ind and dev_b[0] <= vc.bound(dev_a[0]) and dev_b[1] <= vc.bound(dev_a[1])
+        print(f"vq train d={d}: n={n} K={K}  parent path (nearest_code + one_hot + einsum + EMA) {ms_a:.3f} ms  ema_update {ms_b:.3f} ms  "
+              f"ratio {ms_a / ms_b:.2f}x  ({rounds * reps} iterations each)  indices equal {same_ind}  deviation from float64 embed / cluster_size: "
+              f"parent {dev_a[0]:.3g} / {dev_a[1]:.3g}, ema_update {dev_b[0]:.3g} / {dev_b[1]:.3g}  within the parity rule {ok}")
+        if not (ok and ms_b < ms_a):
+            raise SystemExit("vq train leg: ema_update must agree with the parent path and be faster")
+
+
+if args.leg in ("all", "compact"):
+    compact_leg()
+if args.leg in ("all", "train"):
+    train_leg(args.iters, args.fused_only)
