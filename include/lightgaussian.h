@@ -304,6 +304,20 @@ size_t lg_vq_ema_scratch_bytes(int32_t n, int32_t K, int32_t d);
 int lg_vq_ema_step(int32_t n, int32_t d, int32_t K, const float* x, const float* weight, float* embed, float* cluster_size,
                    double decay, double eps, int32_t* out_index, void* scratch, uint32_t flags, void* stream);
 
+/* --- colours of a VecTree-compressed model ----------------------------------------------------------
+ * The read side of the reference's extreme_saving model (vectree/utils.py:5-65 load_vqgaussian, scene/gaussian_model.py:420-461
+ * load_vq) without the dequantised table: out_rgb[i] = max(eval_sh(sh_degree, row(slot[i]), normalize(means3D[i] - campos)) + 0.5, 0),
+ * the colors_precomp of lg_gaussians, by the same lg_sh_to_rgb K1 evaluates on a float32 SH tensor -- equal to the dense path's
+ * colours bit for bit.  rows_f16: fp16 table, row r at rows_f16 + r * row_stride_bytes (16-byte aligned base, stride a multiple
+ * of 16 and >= 6 M), 3 M halfs per row in the file's order f_dc_0..2, f_rest_0.. (channel-major: coefficient m >= 1 of channel c
+ * at 3 + c (M - 1) + m - 1); by convention the K codebook rows, then the non-VQ rows.  slot [N] uint32: row of each Gaussian,
+ * NOT range-checked (the table's length is not an argument).  M in {1, 4, 9, 16}, (sh_degree + 1)^2 <= M: only the 16-byte
+ * chunks holding an active coefficient are read.  Per Gaussian: 12 + 4 + 6 (sh_degree + 1)^2 bytes read, 12 written.
+ * means3D [N,3], campos [3], out_rgb [N,3]: fp32 device.  One launch on `stream`, no host synchronisation.
+ * flags: LG_FLAG_DEBUG, LG_FLAG_PROFILE. */
+int lg_vq_colors(int32_t N, int32_t M, int32_t sh_degree, const float* means3D, const float* campos, const uint32_t* slot,
+                 const void* rows_f16, int32_t row_stride_bytes, float* out_rgb, uint32_t flags, void* stream);
+
 /* out[j] = (((rows[0][j] + rows[1][j]) + rows[2][j]) + ...) over V rows of n floats (row pitch row_stride floats): the
  * sequential in-place float accumulation of per-view scores in prune.py:144-155, in view order, as one launch. */
 int lg_ordered_sum(int32_t V, int64_t n, const float* rows, int64_t row_stride, float* out, void* stream);

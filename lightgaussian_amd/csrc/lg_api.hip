@@ -13,6 +13,7 @@
 //   lg_compact.h     lg_compact_plan / lg_compact_rows: one scan + one launch compacting all Gaussian tensors after a prune
 //   lg_vq.h          lg_vq_nearest: nearest-code search of the VecTree quantiser on f32 MFMA (32x32x2), fused row argmin
 //   lg_vq_train.h    lg_vq_ema_step: one EMA k-means step of the VecTree codebook (search, inverted index, ordered segmented sum, EMA)
+//   lg_vq_color.h    lg_vq_colors: per-Gaussian colours of a VecTree-compressed model (fp16 row table + slot) through the same lg_sh_to_rgb as K1
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound)
 //
 // Pipeline of one view:
@@ -35,6 +36,7 @@
 #include "lg_compact.h"
 #include "lg_vq.h"
 #include "lg_vq_train.h"
+#include "lg_vq_color.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -727,6 +729,34 @@ extern "C" int lg_vq_nearest(int32_t n, int32_t d, int32_t K, const float* x, co
     }
 #undef LAUNCH_VQ
     KCHECK("lg_vq_nearest_kernel");
+    return LG_OK;
+}
+
+// ---- colours of a VecTree-compressed model (lg_vq_color.h) ----
+extern "C" int lg_vq_colors(int32_t N, int32_t M, int32_t sh_degree, const float* means3D, const float* campos, const uint32_t* slot,
+                            const void* rows_f16, int32_t row_stride_bytes, float* out_rgb, uint32_t flags, void* stream_p)
+{
+    if (N < 0 || !(M == 1 || M == 4 || M == 9 || M == 16) || sh_degree < 0 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > M)
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_colors: N >= 0, M in {1, 4, 9, 16}, (D + 1)^2 <= M required");
+    if (row_stride_bytes < 6 * M || (row_stride_bytes & 15) != 0 || ((uintptr_t)rows_f16 & 15) != 0)
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_colors: rows must be 16-byte aligned, row_stride_bytes a multiple of 16 and >= 6 M");
+    if (N == 0) return LG_OK;
+    if (!means3D || !campos || !slot || !rows_f16 || !out_rgb) return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_colors: missing buffer");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = flags & LG_FLAG_DEBUG, prof = flags & LG_FLAG_PROFILE;
+    const uint32_t need = lg_vq_need_mask(M, sh_degree);
+    const unsigned grid = (unsigned)((N + LG_PP - 1) / LG_PP);
+    ProfScope ps(prof, "vq_colors", stream);
+#define LAUNCH_VQC(MM) lg_vq_colors_kernel<MM><<<grid, LG_PP, 0, stream>>>(N, sh_degree, need, means3D, campos, slot, (const unsigned char*)rows_f16, \
+                                                                          (uint32_t)row_stride_bytes, out_rgb)
+    switch (M) {
+        case 1: LAUNCH_VQC(1); break;
+        case 4: LAUNCH_VQC(4); break;
+        case 9: LAUNCH_VQC(9); break;
+        default: LAUNCH_VQC(16); break;
+    }
+#undef LAUNCH_VQC
+    KCHECK("lg_vq_colors_kernel");
     return LG_OK;
 }
 

@@ -15,6 +15,7 @@ import torch
 from . import rasterizer as _rasterizer
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_raw
 from .sh_utils import eval_sh
+from .vectree import CompressedGaussians
 
 
 def _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, f_count):
@@ -114,6 +115,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     are evaluated INSIDE the kernels from the raw parameters (render_fused: no torch.cat of the SH tensors, no
     activation kernels; same values to ~1e-7, gradients land on the raw parameters exactly as autograd would route
     them).  set_option("fuse_getters", False) restores the reference's literal call pattern."""
+    if isinstance(pc, CompressedGaussians) and override_color is None:
+        return render_compressed(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, options=options)
     if (_rasterizer.resolve_options(options)["fuse_getters"] and override_color is None and not pipe.convert_SHs_python
             and not pipe.compute_cov3D_python and _has_reference_getters(pc)):
         return render_fused(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, options=options)
@@ -131,6 +134,21 @@ def _render_unfused(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, 
         scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
             "radii": radii}
+
+
+def render_compressed(viewpoint_camera, cg, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, *, options=None):
+    """render() of a vectree.CompressedGaussians (the reference's extreme_saving model, Scene(load_vq=True)) from its compressed
+    form: lg_vq_colors turns (camera, fp16 SH row table + slot) into one RGB triple per Gaussian, and the unfused forward takes
+    them as colors_precomp -- the [N, 3 M] float32 SH tensor is never built.  Same result dict as render(), same image bits as
+    render() of cg.to_dense() with fuse_getters off.  Forward-only: runs under torch.no_grad(), nothing requires grad (to train,
+    use cg.to_dense()).  The Python-side alternates of `pipe` need the dense tensors and are refused."""
+    if pipe.convert_SHs_python or pipe.compute_cov3D_python:
+        raise NotImplementedError("convert_SHs_python / compute_cov3D_python need the dequantised tensors: render cg.to_dense() instead")
+    with torch.no_grad():
+        colors = cg.colors(viewpoint_camera.camera_center)
+        pkg = _render_unfused(viewpoint_camera, cg, pipe, bg_color, scaling_modifier, colors, options)
+    pkg["viewspace_points"] = pkg["viewspace_points"].detach()
+    return pkg
 
 
 def count_render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, *, options=None):

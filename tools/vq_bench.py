@@ -11,7 +11,14 @@ K = 8192, d = 27 / 48), device-resident inputs, warm, alternating blocks of
   (b) vq.ema_update (lg_vq_ema_step).
 Prints ms / iteration of both and their ratio, and checks (b)'s post-state against (a)'s: indices equal, both compared with a
 float64 evaluation from those indices under the parity rule of tests/test_gpu_vq_train.py (4 x (a)'s own deviation, floor
-2^-22).  --fused-only skips (a): the form to run under `rocprofv3 --kernel-trace --stats` for the per-kernel split of (b)."""
+2^-22).  --fused-only skips (a): the form to run under `rocprofv3 --kernel-trace --stats` for the per-kernel split of (b).
+
+--leg render (not part of "all"): a VecTree-compressed model (vq_ratio 0.6, K = 8192, SH degree 2 and 3, N = 1 M and 3 M, the
+synthetic scene and its orbit cameras at 1080p) rendered forward-only, per view and warm, in alternating repeats of
+  (a) render() of cg.to_dense() under no_grad -- the dequantised float32 model, the only way to show it without lg_vq_colors;
+  (b) render_compressed(cg): lg_vq_colors + the forward on colors_precomp.
+Prints the median and the min..max over the repeats of both, lg_vq_colors alone under an event bracket with
+GB/s by its byte model, 12 + 4 + 6 (D + 1)^2 read and 12 written per Gaussian, and cg.nbytes() against the dense model's bytes."""
 import argparse
 import os
 import sys
@@ -23,9 +30,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lightgaussian_amd import vq, prune
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--leg", choices=("all", "search", "compact", "train"), default="all")
+ap.add_argument("--leg", choices=("all", "search", "compact", "train", "render"), default="all")
 ap.add_argument("--iters", type=int, default=200, help="training iterations per timing (train leg)")
 ap.add_argument("--fused-only", action="store_true")
+ap.add_argument("--sizes", type=int, nargs="+", default=[1_000_000, 3_000_000], help="Gaussians (render leg)")
+ap.add_argument("--repeats", type=int, default=7, help="timed repeats over all views (render leg, at least 5)")
+ap.add_argument("--views", type=int, default=8, help="orbit cameras (render leg)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 
@@ -135,6 +145,76 @@ def train_leg(iters, fused_only):
             raise SystemExit("vq train leg: ema_update must agree with the parent path and be faster")
 
 
+def render_leg(sizes, repeats, n_views):
+    import statistics
+    from lightgaussian_amd import synthetic as syn, vectree
+    from lightgaussian_amd.gaussian_renderer import render, render_compressed
+    repeats = max(repeats, 5)
+    W, H, K = 1920, 1080, 8192
+    pipe = syn.PipelineParams()
+    bg = torch.zeros(3, device=dev)
+    cams = [syn.orbit_camera(k, n_views, W, H).to(dev) for k in range(n_views)]
+
+    def spread(ms):
+        return f"{statistics.median(ms):.3f} ms (min {min(ms):.3f}, max {max(ms):.3f})"
+
+    def per_view(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for cam in cams:
+            fn(cam)
+        t1.record(); t1.synchronize()
+        return t0.elapsed_time(t1) / len(cams)
+
+    for N in sizes:
+        for deg in (2, 3):
+            d = 3 * (deg + 1) ** 2
+            g = syn.make_gaussians(N, sh_degree=deg)
+            gen = torch.Generator().manual_seed(N + deg)
+            feats = torch.cat([g._xyz, torch.zeros(N, 3), g._features_dc.transpose(1, 2).reshape(N, 3),
+                               g._features_rest.transpose(1, 2).reshape(N, -1), g._opacity, g._scaling, g._rotation], dim=1)
+            codebook = feats[torch.randint(0, N, (K,), generator=gen), 6:6 + d]
+            mask = torch.zeros(N, dtype=torch.bool)
+            mask[torch.topk(torch.rand(N, generator=gen), k=int(N * (1 - 0.6))).indices] = True
+            ind = vq.nearest_code(feats[:, 6:6 + d].to(dev), codebook.to(dev)).cpu()
+            cg = vectree.CompressedGaussians.from_packed(vectree.pack(feats, mask, codebook, ind), dev)
+            del feats, g
+            dense = cg.to_dense()
+            dense_bytes = sum(t.numel() * 4 for t in (dense._xyz, dense._features_dc, dense._features_rest, dense._opacity, dense._scaling, dense._rotation))
+            with torch.no_grad():
+                fa = lambda cam: render(cam, dense, pipe, bg)                       # noqa: E731
+                fb = lambda cam: render_compressed(cam, cg, pipe, bg)              # noqa: E731
+                for _ in range(2):
+                    per_view(fa); per_view(fb)
+                ms_a, ms_b = [], []
+                for _ in range(repeats):                                           # alternate, so that both see the same clocks
+                    ms_a.append(per_view(fa)); ms_b.append(per_view(fb))
+                ia, ib = fa(cams[1])["render"], fb(cams[1])["render"]
+                err = float((ia - ib).abs().max() / ia.abs().max())
+            out = torch.empty(N, 3, device=dev)
+            model = N * (12 + 4 + 6 * (deg + 1) ** 2 + 12)
+            ms_c = []
+            for _ in range(2 + repeats):
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                for cam in cams:
+                    cg.colors(cam.camera_center, out=out)
+                t1.record(); t1.synchronize()
+                ms_c.append(t0.elapsed_time(t1) / len(cams))
+            ms_c = ms_c[2:]
+            a, b = statistics.median(ms_a), statistics.median(ms_b)
+            verdict = "faster" if b < min(ms_a) else "slower" if b > max(ms_a) else "within the spread of (a)"
+            print(f"vq render N={N} degree={deg} {W}x{H} {n_views} views x {repeats} repeats, per view:  (a) render(to_dense()) {spread(ms_a)}  "
+                  f"(b) render_compressed {spread(ms_b)}  (b)/(a) {b / a:.3f} ({verdict})  image agreement {err:.2e}")
+            print(f"    lg_vq_colors alone, back to back (its working set stays in the 256 MB Infinity Cache): {spread(ms_c)}  "
+                  f"{model / statistics.median(ms_c) / 1e6:.0f} GB/s by the byte model ({model // N} B / Gaussian)")
+            print(f"    resident bytes: compressed {cg.nbytes() / 1e6:.1f} MB, dense {dense_bytes / 1e6:.1f} MB, ratio {dense_bytes / cg.nbytes():.2f}x")
+            del cg, dense, out
+            torch.cuda.empty_cache()
+
+
+if args.leg == "render":
+    render_leg(args.sizes, args.repeats, args.views)
 if args.leg in ("all", "compact"):
     compact_leg()
 if args.leg in ("all", "train"):
