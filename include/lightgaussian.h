@@ -72,7 +72,7 @@ enum {
                                     default two stages -- radix passes on the tile bits, then each list ordered by depth inside LDS.  Same lists. */
     LG_FLAG_K1_LDS = 256,        /* K1 stages SH rows through LDS instead of per-lane reads */
     LG_FLAG_LONG_SERIAL = 512,   /* long per-tile lists of the hardware-exp colour forward: walk every list serially inside the blend kernel */
-    LG_FLAG_LONG_PARALLEL = 1024, /* ... walk the segments of EVERY multi-segment list in parallel (lg_blend_fwd_seg / _scan / _rewalk).
+    LG_FLAG_LONG_PARALLEL = 1024, /* ... walk the segments of EVERY multi-segment list in parallel (lg_blend_fwd_seg, which also scans, / lg_blend_fwd_rewalk).
                               Neither flag (default): only lists longer than two segments and four times the view's mean list --
                               decided on the device from this view's own instance count, so the choice never depends on what the
                               process rendered before.  Images of the parallel walk agree with the serial one to float rounding

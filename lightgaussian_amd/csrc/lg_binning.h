@@ -818,7 +818,7 @@ lg_tile_sort_long(const uint32_t* __restrict__ counters, const uint2* __restrict
 // Runs as ONE EXTRA WORKGROUP of the forward blend (lg_blend_fwd, block index ntiles_pad): the ranges are final by then, and
 // the 10 us a lone workgroup needs for 8160 tiles hide behind the blend instead of standing in front of the backward.
 // It also lists the items of the tiles whose list goes through the parallel long-tile forward (par_work, meta[4] items;
-// lg_blend_fwd_seg / _scan / _rewalk): the lists longer than lg_par_min() -- a pure function of THIS view's device-side
+// lg_blend_fwd_seg with its lg_scan_tile, lg_blend_fwd_rewalk): the lists longer than lg_par_min() -- a pure function of THIS view's device-side
 // numbers (long-tile mode of the call, S, instance count R, tile count), the same one the tile workgroups of lg_blend_fwd
 // evaluate to leave those lists alone.
 __device__ __forceinline__ uint32_t lg_par_min(int long_mode, int S, uint32_t R, int ntiles)

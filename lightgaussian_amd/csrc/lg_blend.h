@@ -17,14 +17,19 @@
 #define LG_XCD_RUN_LOG2 2 // runs of 4 consecutive tiles per XCD
 #endif
 #define LG_TILE_GRID_ALIGN (8 << LG_XCD_RUN_LOG2)
-__device__ __forceinline__ int xcd_tile(int b, int ntiles_pad)
+__device__ __forceinline__ int xcd_tile(int b)
 {
-    (void)ntiles_pad;
     const int r = b >> 3; // index of this workgroup inside its XCD's stream
     return ((r >> LG_XCD_RUN_LOG2) << (LG_XCD_RUN_LOG2 + 3)) + ((b & 7) << LG_XCD_RUN_LOG2) + (r & ((1 << LG_XCD_RUN_LOG2) - 1));
 }
 
 #define LG_Q 64 // LDS queue depth per wave = one batch
+
+// pair power of a binning record (rows a = {x, y, ha, nb}, b = {hc, opacity, r, g}) at a pixel: lg_pair_power, lg_math.h
+__device__ __forceinline__ float lg_rec_power(const float4& a, const float4& b, float pxf, float pyf, float& dx, float& dy)
+{
+    return lg_pair_power(a.x, a.y, a.z, a.w, b.x, pxf, pyf, dx, dy);
+}
 
 // Threshold guard of the hardware-exp variants.  alpha >= 1/255 is a discontinuity of the algorithm: a pair
 // that flips in or out changes its pixel by up to T/255.  v_exp_f32 and the canonical lg_exp differ by a few 1e-7
@@ -35,7 +40,7 @@ __device__ __forceinline__ float guard_alpha(float alpha, float opacity, float p
 {
     const bool near = fabsf(alpha - LG_ALPHA_MIN) < 2.0e-8f;
     if (__ballot(near) != 0) {
-        const float ac = fminf(LG_ALPHA_MAX, opacity * lg_exp(fminf(power_le0, 0.0f)));
+        const float ac = lg_alpha_exact(opacity, power_le0);
         alpha = near ? ac : alpha;
     }
     return alpha;
@@ -77,6 +82,68 @@ __device__ __forceinline__ bool lg_block_hit(const float4& r0, const float4& r1,
     return box && (reach || !e.cull);
 }
 
+// A wave's 8 x 8 pixel block inside its 16 x 16 tile: sub-block `sub` (0..3, row-major: the wave index of K6 and of the long-tile
+// kernels, the per-lane pixel index of K7) starts at (wx0, wy0); lane l holds pixel (l & 7, l >> 3) of it, which is slot pix() of the
+// tile's checkpoint records (lg_math.h, LG_CKPT_PIX).
+struct LgBlock {
+    int sub, wx0, wy0, pxi, pyi;
+    uint32_t lane;
+    bool inside;
+    // (a function: most callers want the slot once, after their walk)
+    __device__ __forceinline__ uint32_t pix() const { return ((uint32_t)(sub >> 1) * 8u + (lane >> 3)) * 16u + (uint32_t)(sub & 1) * 8u + (lane & 7u); }
+};
+__device__ __forceinline__ LgBlock lg_block(int W, int H, int tx, int ty, int sub, uint32_t lane)
+{
+    LgBlock g;
+    g.sub = sub; g.lane = lane;
+    g.wx0 = tx * LG_TILE + (sub & 1) * 8; g.wy0 = ty * LG_TILE + (sub >> 1) * 8;
+    g.pxi = g.wx0 + (int)(lane & 7); g.pyi = g.wy0 + (int)(lane >> 3);
+    g.inside = g.pxi < W && g.pyi < H;
+    return g;
+}
+
+// what a finished pixel leaves: final transmittance, contributor index of its last contribution, colour over the background
+__device__ __forceinline__ void lg_store_pixel(int W, int H, int pxi, int pyi, float T, uint32_t last, float C0, float C1, float C2,
+                                               const float* __restrict__ bg, float* __restrict__ out_color, float* __restrict__ final_T,
+                                               uint32_t* __restrict__ n_contrib)
+{
+    const size_t pid = (size_t)pyi * W + pxi, HW = (size_t)H * W;
+    final_T[pid] = T;
+    n_contrib[pid] = last;
+    out_color[pid] = fmaf(T, bg[0], C0);
+    out_color[HW + pid] = fmaf(T, bg[1], C1);
+    out_color[2 * HW + pid] = fmaf(T, bg[2], C2);
+}
+
+// The front of a list walk, one batch of up to 64 entries: lane l gathers list entry `entry` (when `valid`), loads its three record
+// rows and tests its footprint (box x +- hx, y +- hy -- hx = inf when culling is off -- then the ellipse: lg_block_hit) against the
+// wave's 8 x 8 block at (bx0, by0); the hits are compacted in list order into the wave's LDS queue.  Returns the hit mask -- 0, before
+// anything is written, when nothing hits.  patch(r2) may stash something in the words of r2 that nothing reads after the block test
+// (.y / .z, the box half-extents) before the row is queued.  Used by lg_walk_block and lg_count_walk; lg_blend_fwd carries the same
+// steps written out (see there).
+template <typename Patch>
+__device__ __forceinline__ uint64_t lg_batch_front(bool valid, uint32_t entry, const uint64_t* entries, uint32_t gid_mask,
+                                                   const float4* rec, float bx0, float by0, float4* q0, float4* q1, float4* q2,
+                                                   Patch patch)
+{
+    bool hit = false;
+    float4 r0, r1, r2;
+    if (valid) {
+        const uint32_t id = (uint32_t)entries[entry] & gid_mask;
+        r0 = rec[LG_REC_F4 * (size_t)id]; r1 = rec[LG_REC_F4 * (size_t)id + 1]; r2 = rec[LG_REC_F4 * (size_t)id + 2];
+        hit = lg_block_hit(r0, r1, r2, lg_reach(r0, r1, r2), bx0, by0);
+    }
+    const uint64_t mask = __ballot(hit);
+    if (mask == 0) return 0;
+    if (hit) {
+        const uint32_t pos = prefix_popc(mask);
+        patch(r2);
+        q0[pos] = r0; q1[pos] = r1; q2[pos] = r2;
+    }
+    __builtin_amdgcn_wave_barrier();
+    return mask;
+}
+
 // Select-based (no divergent control flow) front-to-back step of one list entry for the 64 pixels of a wave.  The lanes' `done` state
 // (saturated or outside the image) is ONE scalar lane mask: every compare is balloted, the masks are combined as 64-bit scalars and the
 // contributing set goes back to a lane predicate through llvm.amdgcn.inverse.ballot (no instruction) -- 9 scalar instructions per pair step
@@ -86,8 +153,8 @@ template <bool EXACT, bool COLOR = true>
 __device__ __forceinline__ uint64_t fwd_pair_m(const float4& a, const float4& b, const float4& c, uint64_t& donem, float pxf, float pyf, float& T,
                                                float& C0, float& C1, float& C2, uint32_t& last, uint32_t rel, float& alpha_out, float& w_out)
 {
-    const float dx = a.x - pxf, dy = a.y - pyf;
-    const float power = fmaf(fmaf(a.z, dx, a.w * dy), dx, (b.x * dy) * dy);
+    float dx, dy;
+    const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
     const float ex = EXACT ? lg_exp(fminf(power, 0.0f)) : __expf(power);
     float alpha = fminf(LG_ALPHA_MAX, b.y * ex);
     if (!EXACT) alpha = guard_alpha(alpha, b.y, power);
@@ -196,28 +263,26 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
         return;
     }
     // (quarter-wave walk, longest-list-first dispatch: EXPERIMENTS.md, "K6 structure")
-    const int tile = xcd_tile(blockIdx.x, ntiles_pad);
+    const int tile = xcd_tile(blockIdx.x);
     if (tile >= ntiles) return;
     const int wave = threadIdx.x >> 6;
     const uint32_t lane = threadIdx.x & 63;
     const int tx = tile % gx, ty = tile / gx;
-    const int wx0 = tx * LG_TILE + (wave & 1) * 8, wy0 = ty * LG_TILE + (wave >> 1) * 8;
-    const int pxi = wx0 + (int)(lane & 7), pyi = wy0 + (int)(lane >> 3);
-    const bool inside = pxi < W && pyi < H;
-    const float pxf = (float)pxi, pyf = (float)pyi;
-    const float bx0 = (float)wx0, bx1 = (float)(wx0 + 7), by0 = (float)wy0, by1 = (float)(wy0 + 7);
+    const LgBlock g = lg_block(W, H, tx, ty, wave, lane);
+    const float pxf = (float)g.pxi, pyf = (float)g.pyi;
+    const float bx0 = (float)g.wx0, by0 = (float)g.wy0;
     const uint2 range = ranges[tile];
-    const uint32_t pix_in_tile = (uint32_t)(pyi - ty * LG_TILE) * 16u + (uint32_t)(pxi - tx * LG_TILE);   // checkpoint slot of this pixel
+    // == g.pix(), spelled from the pixel's coordinates: the lane form re-orders this kernel's address arithmetic, and its code is kept as measured
+    const uint32_t pix = (uint32_t)(g.pyi - ty * LG_TILE) * 16u + (uint32_t)(g.pxi - tx * LG_TILE);
 
     float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
     uint32_t last = 0;
-    uint64_t donem = ~__builtin_amdgcn_ballot_w64(inside);    // saturated or outside the image: one scalar mask per wave (fwd_pair_m)
+    uint64_t donem = ~__builtin_amdgcn_ballot_w64(g.inside);    // saturated or outside the image: one scalar mask per wave (fwd_pair_m)
     // Long list (more than one segment of S entries): leave a checkpoint record per pixel at the end of every segment --
     // {T there, colour accumulated INSIDE the segment (absolute weights alpha T: a sum of non-negative terms, no
-    // cancellation)} -- from which the backward starts each segment independently (lg_blend_bwd).  Record j of this tile is
-    // ckpt[(2 (range.x / S) + j) * 256 + pixel]; 2 floor(x / S) leaves room for ceil(n / S) records before the next long tile.
+    // cancellation)} -- from which the backward starts each segment independently (lg_blend_bwd).  (Record layout: lg_ckpt_base, lg_math.h.)
     const bool longt = COLOR && (range.y - range.x) > (uint32_t)S;            // block-uniform
-    // lists longer than par_min (when set): their segments are walked in parallel by lg_blend_fwd_seg / _scan / _rewalk (below) --
+    // lists longer than par_min (when set): their segments are walked in parallel by lg_blend_fwd_seg (with its lg_scan_tile) / lg_blend_fwd_rewalk (below) --
     // or, in the significance-only pass (no colour: par_min is only non-zero there for the integer weights), by lg_count_seg / _rewalk / _fixup
     if ((longt || !COLOR) && par_min != 0u && (range.y - range.x) > par_min) return;
     if (MERGE) {
@@ -259,11 +324,11 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
         float Cs0 = 0.0f, Cs1 = 0.0f, Cs2 = 0.0f;
         uint32_t seg = 0;
         float4* ck = nullptr;
-        if (LONG) ck = ckpt + (size_t)2 * (range.x / (uint32_t)S) * 256 + pix_in_tile;
+        if (LONG) ck = ckpt + lg_ckpt_base(range.x, (uint32_t)S) + pix;
         // (software pipeline over the batches: EXPERIMENTS.md, "K6 structure")
         for (uint32_t base = range.x; base < range.y; base += LG_Q) {
             if (LONG && base != range.x && (base - range.x) % (uint32_t)S == 0u) {
-                ck[(size_t)seg * 256] = make_float4(T, Cs0, Cs1, Cs2);
+                ck[(size_t)seg * LG_CKPT_PIX] = make_float4(T, Cs0, Cs1, Cs2);
                 seg++; Cs0 = Cs1 = Cs2 = 0.0f;
             }
             if (~donem == 0ull) {            // every pixel of this wave is saturated or outside
@@ -271,12 +336,13 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
                 break;
             }
             const uint32_t idx = base + lane;
+            // lg_batch_front, written out: called as a function the record rows are no longer carried around the batch loop and hipcc
+            // allocates this kernel's registers anew (4 to 12 VGPRs fewer, other code) -- the measured code is kept.  Keep the two in step.
             bool hit = false;
             float4 r0, r1, r2;
             if (idx < range.y) {
                 const uint32_t id = (uint32_t)entries[idx] & gid_mask;
                 r0 = rec[LG_REC_F4 * (size_t)id]; r1 = rec[LG_REC_F4 * (size_t)id + 1]; r2 = rec[LG_REC_F4 * (size_t)id + 2];
-                // footprint box (x +- hx, y +- hy) vs this wave's 8x8 pixel block; hx = inf when culling is off
                 hit = lg_block_hit(r0, r1, r2, lg_reach(r0, r1, r2), bx0, by0);
             }
             const uint64_t mask = __ballot(hit);
@@ -351,22 +417,16 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
         if (LONG) {
             // the current segment's record, and -- when the wave stopped early -- those of the segments it never entered
             // (nothing contributed there: T stays, colour 0), so that every record of the tile is valid for every pixel
-            const uint32_t nseg = (range.y - range.x + (uint32_t)S - 1u) / (uint32_t)S;
+            const uint32_t nseg = lg_nseg(range.y - range.x, (uint32_t)S);
             for (; seg < nseg; seg++) {
-                ck[(size_t)seg * 256] = make_float4(T, Cs0, Cs1, Cs2);
+                ck[(size_t)seg * LG_CKPT_PIX] = make_float4(T, Cs0, Cs1, Cs2);
                 Cs0 = Cs1 = Cs2 = 0.0f;
             }
         }
     };
     if (longt) walk(std::true_type{}); else walk(std::false_type{});
-    if (COLOR && inside) {   // !COLOR: forward-only significance pass, nothing per pixel is kept
-        const size_t pid = (size_t)pyi * W + pxi, HW = (size_t)H * W;
-        final_T[pid] = T;
-        n_contrib[pid] = last;
-        out_color[pid] = fmaf(T, bg[0], C0);
-        out_color[HW + pid] = fmaf(T, bg[1], C1);
-        out_color[2 * HW + pid] = fmaf(T, bg[2], C2);
-    }
+    // (!COLOR: forward-only significance pass, nothing per pixel is kept)
+    if (COLOR && g.inside) lg_store_pixel(W, H, g.pxi, g.pyi, T, last, C0, C1, C2, bg, out_color, final_T, n_contrib);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -381,7 +441,7 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
 //           the end of the segment, colour accumulated inside it} the backward starts from); a pixel whose transmittance would
 //           fall under the threshold INSIDE segment s* (T P_s* < 1e-4, with a margin) is parked at s*;
 //   pass 3  lg_blend_fwd_rewalk: one workgroup per (long tile, segment) again: the pixels parked at this segment walk it
-//           sequentially from their true T with the published pair step (fwd_pair) -- exact stop position, exact contributor
+//           sequentially from their true T with the published pair step (fwd_pair_m) -- exact stop position, exact contributor
 //           index -- and are finished there.  Parallel over the segments like pass 1: no tile waits for a serial chain.
 // Same include / exclude decisions as the serial walk (alpha tests do not depend on T; termination is resolved by the exact
 // re-walk); transmittances are regrouped products, so images agree to float rounding, not bit for bit -- the canonical
@@ -395,8 +455,8 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
 __device__ __forceinline__ void fwd_free(const float4& a, const float4& b, const float4& c, bool live, float pxf, float pyf, float& T,
                                          float& C0, float& C1, float& C2, uint32_t& last, uint32_t rel)
 {
-    const float dx = a.x - pxf, dy = a.y - pyf;
-    const float power = fmaf(fmaf(a.z, dx, a.w * dy), dx, (b.x * dy) * dy);
+    float dx, dy;
+    const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
     float alpha = fminf(LG_ALPHA_MAX, b.y * __expf(power));
     alpha = guard_alpha(alpha, b.y, power);
     const bool ok = live && (power <= 0.0f) && (alpha >= LG_ALPHA_MIN);
@@ -404,6 +464,39 @@ __device__ __forceinline__ void fwd_free(const float4& a, const float4& b, const
     C0 = fmaf(b.z, w, C0); C1 = fmaf(b.w, w, C1); C2 = fmaf(c.x, w, C2);
     T = ok ? T * (1.0f - alpha) : T;
     last = ok ? rel : last;
+}
+
+// One item of the par_work list: segment `seg` of long tile `tile` = entries [lo, hi) of the tile's list (positions relative to range.x)
+struct LgSegItem { int tile, tx, ty; uint32_t seg, n, nseg, lo, hi; uint2 range; };
+__device__ __forceinline__ LgSegItem lg_seg_item(const uint2* __restrict__ par_work, uint32_t it, const uint2* __restrict__ ranges, int gx, int S)
+{
+    LgSegItem item;
+    const uint2 raw = par_work[it];
+    item.tile = (int)raw.x; item.seg = raw.y;
+    item.range = ranges[item.tile];
+    item.n = item.range.y - item.range.x;
+    item.nseg = lg_nseg(item.n, (uint32_t)S);
+    item.tx = item.tile % gx; item.ty = item.tile / gx;
+    item.lo = item.seg * (uint32_t)S; item.hi = min(item.n, item.lo + (uint32_t)S);
+    return item;
+}
+
+// "The last segment of a tile to arrive scans the tile": every workgroup of pass 1 releases its records and counts its arrival (one
+// agent-scope counter per tile, zeroed by the work-list workgroup of lg_blend_fwd); the one that finds every other segment in acquires
+// their records and runs scan().  Nothing waits (no spinning, no co-residency assumption).  s_last: one LDS word of the caller.
+template <typename Scan>
+__device__ __forceinline__ void lg_tile_last_arrival(uint32_t* par_arrived, int tile, uint32_t nseg, uint32_t* s_last, Scan scan)
+{
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0)
+        *s_last = (__hip_atomic_fetch_add(&par_arrived[tile], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == nseg - 1u) ? 1u : 0u;
+    __syncthreads();
+    if (*s_last) {
+        __threadfence();
+        scan();
+    }
+    __syncthreads();                                            // (s_last is rewritten by the next item)
 }
 
 // One batch-by-batch walk of list entries [lo, hi) of a tile by one wave (its 8x8 block): gather, block test, ballot compaction
@@ -416,20 +509,8 @@ __device__ __forceinline__ void lg_walk_block(uint32_t list0, uint32_t lo, uint3
     for (uint32_t base = lo; base < hi; base += LG_Q) {
         if (stop()) break;
         const uint32_t idx = base + lane;
-        bool hit = false;
-        float4 r0, r1, r2;
-        if (idx < hi) {
-            const uint32_t id = (uint32_t)entries[list0 + idx] & gid_mask;
-            r0 = rec[LG_REC_F4 * (size_t)id]; r1 = rec[LG_REC_F4 * (size_t)id + 1]; r2 = rec[LG_REC_F4 * (size_t)id + 2];
-            hit = lg_block_hit(r0, r1, r2, lg_reach(r0, r1, r2), bx0, by0);
-        }
-        uint64_t mask = __ballot(hit);
+        uint64_t mask = lg_batch_front(idx < hi, list0 + idx, entries, gid_mask, rec, bx0, by0, q0, q1, q2, [](float4&) {});
         if (mask == 0) continue;
-        if (hit) {
-            const uint32_t pos = prefix_popc(mask);
-            q0[pos] = r0; q1[pos] = r1; q2[pos] = r2;
-        }
-        __builtin_amdgcn_wave_barrier();
         uint32_t j = 0;
         while (mask) {
             const uint32_t src = (uint32_t)__builtin_ctzll(mask);
@@ -453,20 +534,16 @@ __device__ __forceinline__ void lg_scan_tile(int W, int H, int gx, int S, int ti
                                              float* __restrict__ out_color, float* __restrict__ final_T, uint32_t* __restrict__ n_contrib,
                                              float4* __restrict__ ckpt, uint32_t* __restrict__ ckpt_last, int wave, uint32_t lane)
 {
-    const uint32_t n = range.y - range.x;
-    const uint32_t nseg = (n + (uint32_t)S - 1u) / (uint32_t)S;
-    const int tx = tile % gx, ty = tile / gx;
-    const int pxi = tx * LG_TILE + (wave & 1) * 8 + (int)(lane & 7), pyi = ty * LG_TILE + (wave >> 1) * 8 + (int)(lane >> 3);
-    const bool inside = pxi < W && pyi < H;
-    const uint32_t pix = ((uint32_t)(wave >> 1) * 8u + (lane >> 3)) * 16u + (uint32_t)(wave & 1) * 8u + (lane & 7u);
-    float4* ck = ckpt + (size_t)2 * (range.x / (uint32_t)S) * 256 + pix;
-    uint32_t* cl = ckpt_last + (size_t)2 * (range.x / (uint32_t)S) * 256 + pix;
+    const uint32_t nseg = lg_nseg(range.y - range.x, (uint32_t)S);
+    const LgBlock g = lg_block(W, H, tile % gx, tile / gx, wave, lane);
+    float4* ck = ckpt + lg_ckpt_base(range.x, (uint32_t)S) + g.pix();
+    uint32_t* cl = ckpt_last + lg_ckpt_base(range.x, (uint32_t)S) + g.pix();
     float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
     uint32_t last = 0, sstar = LG_NO_SEG;
-    if (inside) {
+    if (g.inside) {
         for (uint32_t s = 0; s < nseg; s++) {
-            const float4 r = ck[(size_t)s * 256];
-            const uint32_t ll = cl[(size_t)s * 256];
+            const float4 r = ck[(size_t)s * LG_CKPT_PIX];
+            const uint32_t ll = cl[(size_t)s * LG_CKPT_PIX];
             const float Tend = T * r.x;
             // would this pixel stop inside the segment?  (T P_s < 1e-4 up to the rounding of the regrouped product: the margin
             // only sends a few more pixels through the exact re-walk)
@@ -475,18 +552,13 @@ __device__ __forceinline__ void lg_scan_tile(int W, int H, int gx, int S, int ti
             C0 += in0; C1 += in1; C2 += in2;
             T = Tend;
             last = ll ? ll : last;
-            ck[(size_t)s * 256] = make_float4(T, in0, in1, in2);   // what the backward starts segment s from
+            ck[(size_t)s * LG_CKPT_PIX] = make_float4(T, in0, in1, in2);   // what the backward starts segment s from
         }
         if (sstar == LG_NO_SEG) {
-            const size_t pid = (size_t)pyi * W + pxi, HW = (size_t)H * W;
-            final_T[pid] = T;
-            n_contrib[pid] = last;
-            out_color[pid] = fmaf(T, bg[0], C0);
-            out_color[HW + pid] = fmaf(T, bg[1], C1);
-            out_color[2 * HW + pid] = fmaf(T, bg[2], C2);
+            lg_store_pixel(W, H, g.pxi, g.pyi, T, last, C0, C1, C2, bg, out_color, final_T, n_contrib);
         } else {
-            ck[(size_t)sstar * 256] = make_float4(T, C0, C1, C2);
-            if (sstar > 0u) cl[(size_t)sstar * 256] = last;       // (s* = 0: nothing contributed before it)
+            ck[(size_t)sstar * LG_CKPT_PIX] = make_float4(T, C0, C1, C2);
+            if (sstar > 0u) cl[(size_t)sstar * LG_CKPT_PIX] = last;       // (s* = 0: nothing contributed before it)
         }
     }
     cl[0] = sstar;                                                  // read by every (tile, segment) item of lg_blend_fwd_rewalk
@@ -508,39 +580,19 @@ lg_blend_fwd_seg(int W, int H, int gx, int S, const uint2* __restrict__ par_work
     const int wave = threadIdx.x >> 6;
     const uint32_t lane = threadIdx.x & 63;
     for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
-        const uint2 item = par_work[it];
-        const int tile = (int)item.x;
-        const uint2 range = ranges[tile];
-        const uint32_t n = range.y - range.x;
-        const int tx = tile % gx, ty = tile / gx;
-        const int wx0 = tx * LG_TILE + (wave & 1) * 8, wy0 = ty * LG_TILE + (wave >> 1) * 8;
-        const int pxi = wx0 + (int)(lane & 7), pyi = wy0 + (int)(lane >> 3);
-        const bool inside = pxi < W && pyi < H;
-        const float pxf = (float)pxi, pyf = (float)pyi;
-        const uint32_t lo = item.y * (uint32_t)S, hi = min(n, lo + (uint32_t)S);
+        const LgSegItem item = lg_seg_item(par_work, it, ranges, gx, S);
+        const LgBlock g = lg_block(W, H, item.tx, item.ty, wave, lane);
+        const float pxf = (float)g.pxi, pyf = (float)g.pyi;
         float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
         uint32_t last = 0;
-        lg_walk_block(range.x, lo, hi, entries, gid_mask, rec, (float)wx0, (float)wy0, q0[wave], q1[wave], q2[wave], lane,
-                      [&](const float4& a, const float4& b, const float4& c, uint32_t rel) { fwd_free(a, b, c, inside, pxf, pyf, T, C0, C1, C2, last, rel); },
+        lg_walk_block(item.range.x, item.lo, item.hi, entries, gid_mask, rec, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], q2[wave], lane,
+                      [&](const float4& a, const float4& b, const float4& c, uint32_t rel) { fwd_free(a, b, c, g.inside, pxf, pyf, T, C0, C1, C2, last, rel); },
                       [&]() { return false; });
-        const uint32_t pix = ((uint32_t)(wave >> 1) * 8u + (lane >> 3)) * 16u + (uint32_t)(wave & 1) * 8u + (lane & 7u);
-        const size_t slot = ((size_t)2 * (range.x / (uint32_t)S) + item.y) * 256 + pix;
+        const size_t slot = lg_ckpt_base(item.range.x, (uint32_t)S) + (size_t)item.seg * LG_CKPT_PIX + g.pix();
         ckpt[slot] = make_float4(T, C0, C1, C2);
         ckpt_last[slot] = last;
-        // the last segment of this tile to arrive scans the tile (lg_scan_tile): release my records, count my arrival, and --
-        // if every segment of the tile is in -- acquire the others' records
-        __threadfence();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t nseg = (n + (uint32_t)S - 1u) / (uint32_t)S;
-            s_last = (__hip_atomic_fetch_add(&par_arrived[tile], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == nseg - 1u) ? 1u : 0u;
-        }
-        __syncthreads();
-        if (s_last) {
-            __threadfence();
-            lg_scan_tile(W, H, gx, S, tile, range, bg, out_color, final_T, n_contrib, ckpt, ckpt_last, wave, lane);
-        }
-        __syncthreads();                                            // (s_last is rewritten by the next item)
+        lg_tile_last_arrival(par_arrived, item.tile, item.nseg, &s_last,
+                             [&]() { lg_scan_tile(W, H, gx, S, item.tile, item.range, bg, out_color, final_T, n_contrib, ckpt, ckpt_last, wave, lane); });
     }
 }
 
@@ -559,36 +611,28 @@ lg_blend_fwd_rewalk(int W, int H, int gx, int S, const uint2* __restrict__ par_w
     const int wave = threadIdx.x >> 6;
     const uint32_t lane = threadIdx.x & 63;
     for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
-        const uint2 item = par_work[it];
-        const int tile = (int)item.x;
-        const uint2 range = ranges[tile];
-        const uint32_t n = range.y - range.x;
-        const uint32_t nseg = (n + (uint32_t)S - 1u) / (uint32_t)S;
-        const int tx = tile % gx, ty = tile / gx;
-        const int wx0 = tx * LG_TILE + (wave & 1) * 8, wy0 = ty * LG_TILE + (wave >> 1) * 8;
-        const int pxi = wx0 + (int)(lane & 7), pyi = wy0 + (int)(lane >> 3);
-        const bool inside = pxi < W && pyi < H;
-        const float pxf = (float)pxi, pyf = (float)pyi;
-        const uint32_t pix = ((uint32_t)(wave >> 1) * 8u + (lane >> 3)) * 16u + (uint32_t)(wave & 1) * 8u + (lane & 7u);
-        float4* ck = ckpt + (size_t)2 * (range.x / (uint32_t)S) * 256 + pix;
-        const uint32_t* cl = ckpt_last + (size_t)2 * (range.x / (uint32_t)S) * 256 + pix;
-        const bool mine = inside && cl[0] == item.y;                    // parked at this segment
+        const LgSegItem item = lg_seg_item(par_work, it, ranges, gx, S);
+        const LgBlock g = lg_block(W, H, item.tx, item.ty, wave, lane);
+        const float pxf = (float)g.pxi, pyf = (float)g.pyi;
+        float4* ck = ckpt + lg_ckpt_base(item.range.x, (uint32_t)S) + g.pix();
+        const uint32_t* cl = ckpt_last + lg_ckpt_base(item.range.x, (uint32_t)S) + g.pix();
+        const bool mine = g.inside && cl[0] == item.seg;                   // parked at this segment
         if (__ballot(mine) == 0) continue;
         float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
         uint32_t last = 0;
         if (mine) {
-            const float4 st = ck[(size_t)item.y * 256];
+            const float4 st = ck[(size_t)item.seg * LG_CKPT_PIX];
             T = st.x; C0 = st.y; C1 = st.z; C2 = st.w;
-            last = item.y > 0u ? cl[(size_t)item.y * 256] : 0u;
+            last = item.seg > 0u ? cl[(size_t)item.seg * LG_CKPT_PIX] : 0u;
         }
         uint64_t dnm = ~__builtin_amdgcn_ballot_w64(mine);              // finished (or not parked here): one scalar mask per wave (fwd_pair_m)
-        uint32_t cur = item.y, mynext = item.y;                         // mynext: first segment this pixel did not enter
-        for (; cur < nseg && ~dnm != 0ull; cur++) {                     // wave-uniform
+        uint32_t cur = item.seg, mynext = item.seg;                           // mynext: first segment this pixel did not enter
+        for (; cur < item.nseg && ~dnm != 0ull; cur++) {                   // wave-uniform
             float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
             uint32_t ls = 0;
             const bool entered = !__builtin_amdgcn_inverse_ballot_w64(dnm);
-            const uint32_t lo = cur * (uint32_t)S, hi = min(n, lo + (uint32_t)S);
-            lg_walk_block(range.x, lo, hi, entries, gid_mask, rec, (float)wx0, (float)wy0, q0[wave], q1[wave], q2[wave], lane,
+            const uint32_t lo = cur * (uint32_t)S, hi = min(item.n, lo + (uint32_t)S);
+            lg_walk_block(item.range.x, lo, hi, entries, gid_mask, rec, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], q2[wave], lane,
                           [&](const float4& a, const float4& b, const float4& c, uint32_t rel) {
                               float alpha = 0.0f, w = 0.0f;
                               (void)fwd_pair_m<false, true>(a, b, c, dnm, pxf, pyf, T, s0, s1, s2, ls, rel, alpha, w);
@@ -597,18 +641,13 @@ lg_blend_fwd_rewalk(int W, int H, int gx, int S, const uint2* __restrict__ par_w
             if (entered) {
                 C0 += s0; C1 += s1; C2 += s2;
                 last = ls ? ls : last;
-                ck[(size_t)cur * 256] = make_float4(T, s0, s1, s2);
+                ck[(size_t)cur * LG_CKPT_PIX] = make_float4(T, s0, s1, s2);
                 mynext = cur + 1u;
             }
         }
         if (mine) {
-            for (uint32_t j = mynext; j < nseg; j++) ck[(size_t)j * 256] = make_float4(T, 0.0f, 0.0f, 0.0f);   // segments never entered
-            const size_t pid = (size_t)pyi * W + pxi, HW = (size_t)H * W;
-            final_T[pid] = T;
-            n_contrib[pid] = last;
-            out_color[pid] = fmaf(T, bg[0], C0);
-            out_color[HW + pid] = fmaf(T, bg[1], C1);
-            out_color[2 * HW + pid] = fmaf(T, bg[2], C2);
+            for (uint32_t j = mynext; j < item.nseg; j++) ck[(size_t)j * LG_CKPT_PIX] = make_float4(T, 0.0f, 0.0f, 0.0f);   // segments never entered
+            lg_store_pixel(W, H, g.pxi, g.pyi, T, last, C0, C1, C2, bg, out_color, final_T, n_contrib);
         }
     }
 }
@@ -648,9 +687,9 @@ lg_blend_fwd_rewalk(int W, int H, int gx, int S, const uint2* __restrict__ par_w
 // canonical alpha of one (entry, pixel) pair + the T-independent half of its include decision
 __device__ __forceinline__ uint64_t lg_count_alpha(const float4& a, const float4& b, float pxf, float pyf, float& alpha)
 {
-    const float dx = a.x - pxf, dy = a.y - pyf;
-    const float power = fmaf(fmaf(a.z, dx, a.w * dy), dx, (b.x * dy) * dy);
-    alpha = fminf(LG_ALPHA_MAX, b.y * lg_exp(fminf(power, 0.0f)));
+    float dx, dy;
+    const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
+    alpha = lg_alpha_exact(b.y, power);
     return __builtin_amdgcn_ballot_w64(power <= 0.0f) & __builtin_amdgcn_ballot_w64(alpha >= LG_ALPHA_MIN);
 }
 
@@ -664,21 +703,10 @@ __device__ __forceinline__ void lg_count_walk(uint32_t list0, uint32_t lo, uint3
     for (uint32_t base = lo; base < hi; base += LG_Q) {
         if (stop()) break;
         const uint32_t idx = base + lane;
-        bool hit = false;
-        float4 r0, r1, r2;
-        if (idx < hi) {
-            const uint32_t id = (uint32_t)entries[list0 + idx] & gid_mask;
-            r0 = rec[LG_REC_F4 * (size_t)id]; r1 = rec[LG_REC_F4 * (size_t)id + 1]; r2 = rec[LG_REC_F4 * (size_t)id + 2];
-            hit = lg_block_hit(r0, r1, r2, lg_reach(r0, r1, r2), bx0, by0);
-        }
-        const uint64_t mask = __ballot(hit);
-        if (mask == 0) continue;
-        if (hit) {
-            const uint32_t pos = prefix_popc(mask);
+        const uint64_t mask = lg_batch_front(idx < hi, list0 + idx, entries, gid_mask, rec, bx0, by0, q0, q1, q2, [&](float4& r2) {
             r2.y = __uint_as_float(idx + 1u);                      // 1-based position in the tile's list (the box half-extent is not needed any more)
-            q0[pos] = r0; q1[pos] = r1; q2[pos] = r2;
-        }
-        __builtin_amdgcn_wave_barrier();
+        });
+        if (mask == 0) continue;
         const uint32_t nhit = (uint32_t)__popcll(mask);
         int mycnt = 0;
         for (uint32_t j = 0; j < nhit; j++) {
@@ -691,31 +719,27 @@ __device__ __forceinline__ void lg_count_walk(uint32_t list0, uint32_t lo, uint3
     }
 }
 
-// pass 2 (see above); slot layout of a long tile as in the colour forward: record j at ckpt[(2 (range.x / S) + j) * 256 + pixel]
+// pass 2 (see above); records of a long tile laid out as in the colour forward (lg_ckpt_base, lg_math.h)
 __device__ __forceinline__ void lg_count_scan_tile(int W, int H, int gx, int S, int tile, const uint2 range, float4* __restrict__ ckpt,
                                                    uint32_t* __restrict__ ckpt_last, int wave, uint32_t lane, float band_mul)
 {
-    const uint32_t n = range.y - range.x;
-    const uint32_t nseg = (n + (uint32_t)S - 1u) / (uint32_t)S;
-    const int tx = tile % gx, ty = tile / gx;
-    const int pxi = tx * LG_TILE + (wave & 1) * 8 + (int)(lane & 7), pyi = ty * LG_TILE + (wave >> 1) * 8 + (int)(lane >> 3);
-    const bool inside = pxi < W && pyi < H;
-    const uint32_t pix = ((uint32_t)(wave >> 1) * 8u + (lane >> 3)) * 16u + (uint32_t)(wave & 1) * 8u + (lane & 7u);
-    float4* ck = ckpt + (size_t)2 * (range.x / (uint32_t)S) * 256 + pix;
-    uint32_t* cl = ckpt_last + (size_t)2 * (range.x / (uint32_t)S) * 256 + pix;
+    const uint32_t nseg = lg_nseg(range.y - range.x, (uint32_t)S);
+    const LgBlock g = lg_block(W, H, tile % gx, tile / gx, wave, lane);
+    float4* ck = ckpt + lg_ckpt_base(range.x, (uint32_t)S) + g.pix();
+    uint32_t* cl = ckpt_last + lg_ckpt_base(range.x, (uint32_t)S) + g.pix();
     float T = 1.0f;
     uint32_t K = 0, sstar = LG_NO_SEG;
     const float P0 = ck[0].x;
-    if (inside) {
+    if (g.inside) {
         for (uint32_t s = 0; s < nseg; s++) {
-            const float P = s == 0u ? P0 : ck[(size_t)s * 256].x;
-            const uint32_t k = cl[(size_t)s * 256];
+            const float P = s == 0u ? P0 : ck[(size_t)s * LG_CKPT_PIX].x;
+            const uint32_t k = cl[(size_t)s * LG_CKPT_PIX];
             const float Tend = T * P;
             // certainly alive through segment s?  (the regrouped and the sequential product of K + k factors agree to the band)
             if (!(Tend >= LG_T_MIN * (1.0f + LG_CNT_BAND(K + k + s)))) { sstar = s; break; }
             T = Tend; K += k;
         }
-        if (sstar != LG_NO_SEG) { float4 r = ck[(size_t)sstar * 256]; r.z = T; r.w = __uint_as_float(K); ck[(size_t)sstar * 256] = r; }
+        if (sstar != LG_NO_SEG) { float4 r = ck[(size_t)sstar * LG_CKPT_PIX]; r.z = T; r.w = __uint_as_float(K); ck[(size_t)sstar * LG_CKPT_PIX] = r; }
     }
     // word y of record 0: where this pixel is parked (read by every item of lg_count_rewalk); last-word of record 0: its flag (0 = none)
     { float4 r = ck[0]; r.x = P0; r.y = __uint_as_float(sstar); ck[0] = r; }
@@ -741,9 +765,9 @@ __device__ __forceinline__ void lg_count_exact_pixel(const uint2 range, const ui
         if (e < n) {
             id = (uint32_t)entries[range.x + e] & gid_mask;
             const float4 a = rec[LG_REC_F4 * (size_t)id], b = rec[LG_REC_F4 * (size_t)id + 1];
-            const float dx = a.x - pxf, dy = a.y - pyf;
-            const float power = fmaf(fmaf(a.z, dx, a.w * dy), dx, (b.x * dy) * dy);
-            alpha = fminf(LG_ALPHA_MAX, b.y * lg_exp(fminf(power, 0.0f)));
+            float dx, dy;
+            const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
+            alpha = lg_alpha_exact(b.y, power);
             ok = (power <= 0.0f) && (alpha >= LG_ALPHA_MIN);
         }
         uint64_t cntm = 0ull;
@@ -770,17 +794,12 @@ lg_count_seg(int W, int H, int gx, int S, const uint2* __restrict__ par_work, co
     const int wave = threadIdx.x >> 6;
     const uint32_t lane = threadIdx.x & 63;
     for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
-        const uint2 item = par_work[it];
-        const int tile = (int)item.x;
-        const uint2 range = ranges[tile];
-        const uint32_t n = range.y - range.x;
-        const int tx = tile % gx, ty = tile / gx;
-        const int wx0 = tx * LG_TILE + (wave & 1) * 8, wy0 = ty * LG_TILE + (wave >> 1) * 8;
-        const float pxf = (float)(wx0 + (int)(lane & 7)), pyf = (float)(wy0 + (int)(lane >> 3));
-        const uint32_t lo = item.y * (uint32_t)S, hi = min(n, lo + (uint32_t)S);
+        const LgSegItem item = lg_seg_item(par_work, it, ranges, gx, S);
+        const LgBlock g = lg_block(W, H, item.tx, item.ty, wave, lane);
+        const float pxf = (float)g.pxi, pyf = (float)g.pyi;
         float P = 1.0f;
         uint32_t k = 0;
-        lg_count_walk(range.x, lo, hi, entries, gid_mask, rec, (float)wx0, (float)wy0, q0[wave], q1[wave], q2[wave], lane, nullptr,
+        lg_count_walk(item.range.x, item.lo, item.hi, entries, gid_mask, rec, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], q2[wave], lane, nullptr,
                       [&](const float4& a, const float4& b, uint32_t) -> uint64_t {
                           float alpha;
                           const bool ok = __builtin_amdgcn_inverse_ballot_w64(lg_count_alpha(a, b, pxf, pyf, alpha));
@@ -790,22 +809,11 @@ lg_count_seg(int W, int H, int gx, int S, const uint2* __restrict__ par_work, co
                           return 0ull;
                       },
                       [&]() { return false; });
-        const uint32_t pix = ((uint32_t)(wave >> 1) * 8u + (lane >> 3)) * 16u + (uint32_t)(wave & 1) * 8u + (lane & 7u);
-        const size_t slot = ((size_t)2 * (range.x / (uint32_t)S) + item.y) * 256 + pix;
+        const size_t slot = lg_ckpt_base(item.range.x, (uint32_t)S) + (size_t)item.seg * LG_CKPT_PIX + g.pix();
         ckpt[slot] = make_float4(P, 0.0f, 0.0f, 0.0f);
         ckpt_last[slot] = k;
-        __threadfence();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t nseg = (n + (uint32_t)S - 1u) / (uint32_t)S;
-            s_last = (__hip_atomic_fetch_add(&par_arrived[tile], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == nseg - 1u) ? 1u : 0u;
-        }
-        __syncthreads();
-        if (s_last) {
-            __threadfence();
-            lg_count_scan_tile(W, H, gx, S, tile, range, ckpt, ckpt_last, wave, lane, band_mul);
-        }
-        __syncthreads();
+        lg_tile_last_arrival(par_arrived, item.tile, item.nseg, &s_last,
+                             [&]() { lg_count_scan_tile(W, H, gx, S, item.tile, item.range, ckpt, ckpt_last, wave, lane, band_mul); });
     }
 }
 
@@ -819,30 +827,22 @@ lg_count_rewalk(int W, int H, int gx, int S, const uint2* __restrict__ par_work,
     const int wave = threadIdx.x >> 6;
     const uint32_t lane = threadIdx.x & 63;
     for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
-        const uint2 item = par_work[it];
-        const int tile = (int)item.x;
-        const uint2 range = ranges[tile];
-        const uint32_t n = range.y - range.x;
-        const uint32_t nseg = (n + (uint32_t)S - 1u) / (uint32_t)S;
-        const int tx = tile % gx, ty = tile / gx;
-        const int wx0 = tx * LG_TILE + (wave & 1) * 8, wy0 = ty * LG_TILE + (wave >> 1) * 8;
-        const int pxi = wx0 + (int)(lane & 7), pyi = wy0 + (int)(lane >> 3);
-        const bool inside = pxi < W && pyi < H;
-        const float pxf = (float)pxi, pyf = (float)pyi;
-        const uint32_t pix = ((uint32_t)(wave >> 1) * 8u + (lane >> 3)) * 16u + (uint32_t)(wave & 1) * 8u + (lane & 7u);
-        const float4* ck = ckpt + (size_t)2 * (range.x / (uint32_t)S) * 256 + pix;
-        uint32_t* cl = ckpt_last + (size_t)2 * (range.x / (uint32_t)S) * 256 + pix;
+        const LgSegItem item = lg_seg_item(par_work, it, ranges, gx, S);
+        const LgBlock g = lg_block(W, H, item.tx, item.ty, wave, lane);
+        const float pxf = (float)g.pxi, pyf = (float)g.pyi;
+        const float4* ck = ckpt + lg_ckpt_base(item.range.x, (uint32_t)S) + g.pix();
+        uint32_t* cl = ckpt_last + lg_ckpt_base(item.range.x, (uint32_t)S) + g.pix();
         const uint32_t sstar = __float_as_uint(ck[0].y);
-        const bool mine = inside && sstar == item.y;                                     // parked at this segment
-        uint64_t freem = __builtin_amdgcn_ballot_w64(inside && (sstar == LG_NO_SEG || item.y < sstar));   // certainly alive through it
+        const bool mine = g.inside && sstar == item.seg;                                    // parked at this segment
+        uint64_t freem = __builtin_amdgcn_ballot_w64(g.inside && (sstar == LG_NO_SEG || item.seg < sstar));   // certainly alive through it
         uint64_t alivem = __builtin_amdgcn_ballot_w64(mine);
         if ((freem | alivem) == 0ull) continue;
         float T = 1.0f;
         uint32_t K = 0, flag = 0;
-        if (mine) { const float4 st = ck[(size_t)item.y * 256]; T = st.z; K = __float_as_uint(st.w); }
-        for (uint32_t cur = item.y; cur < nseg && (freem | alivem) != 0ull; cur++) {    // wave-uniform
-            const uint32_t lo = cur * (uint32_t)S, hi = min(n, lo + (uint32_t)S);
-            lg_count_walk(range.x, lo, hi, entries, gid_mask, rec, (float)wx0, (float)wy0, q0[wave], q1[wave], q2[wave], lane, count,
+        if (mine) { const float4 st = ck[(size_t)item.seg * LG_CKPT_PIX]; T = st.z; K = __float_as_uint(st.w); }
+        for (uint32_t cur = item.seg; cur < item.nseg && (freem | alivem) != 0ull; cur++) {   // wave-uniform
+            const uint32_t lo = cur * (uint32_t)S, hi = min(item.n, lo + (uint32_t)S);
+            lg_count_walk(item.range.x, lo, hi, entries, gid_mask, rec, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], q2[wave], lane, count,
                           [&](const float4& a, const float4& b, uint32_t rel) -> uint64_t {
                               float alpha;
                               const uint64_t okm = lg_count_alpha(a, b, pxf, pyf, alpha);
@@ -877,21 +877,16 @@ lg_count_fixup(int W, int H, int gx, int S, const uint2* __restrict__ par_work, 
     const int wave = threadIdx.x >> 6;
     const uint32_t lane = threadIdx.x & 63;
     for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
-        const uint2 item = par_work[it];
-        if (item.y != 0u) continue;                                                      // one item per long tile
-        const int tile = (int)item.x;
-        const uint2 range = ranges[tile];
-        const uint32_t n = range.y - range.x;
-        const int tx = tile % gx, ty = tile / gx;
-        const int pxi = tx * LG_TILE + (wave & 1) * 8 + (int)(lane & 7), pyi = ty * LG_TILE + (wave >> 1) * 8 + (int)(lane >> 3);
-        const uint32_t pix = ((uint32_t)(wave >> 1) * 8u + (lane >> 3)) * 16u + (uint32_t)(wave & 1) * 8u + (lane & 7u);
-        const uint32_t myflag = (pxi < W && pyi < H) ? ckpt_last[(size_t)2 * (range.x / (uint32_t)S) * 256 + pix] : 0u;
+        const LgSegItem item = lg_seg_item(par_work, it, ranges, gx, S);
+        if (item.seg != 0u) continue;                                                       // one item per long tile
+        const LgBlock g = lg_block(W, H, item.tx, item.ty, wave, lane);
+        const uint32_t myflag = g.inside ? ckpt_last[lg_ckpt_base(item.range.x, (uint32_t)S) + g.pix()] : 0u;
         for (uint64_t todo = __builtin_amdgcn_ballot_w64(myflag != 0u); todo != 0ull; todo &= todo - 1ull) {
             const int src = (int)__builtin_ctzll(todo);
             const uint32_t jstar = (uint32_t)__builtin_amdgcn_readlane((int)myflag, src);
             if (lane == 0u) atomicAdd(&meta[5], 1u);
-            const float pxf = (float)__builtin_amdgcn_readlane(pxi, src), pyf = (float)__builtin_amdgcn_readlane(pyi, src);
-            lg_count_exact_pixel(range, entries, gid_mask, rec, pxf, pyf, jstar, count, lane);
+            const float pxf = (float)__builtin_amdgcn_readlane(g.pxi, src), pyf = (float)__builtin_amdgcn_readlane(g.pyi, src);
+            lg_count_exact_pixel(item.range, entries, gid_mask, rec, pxf, pyf, jstar, count, lane);
         }
     }
 }
@@ -1001,8 +996,8 @@ __device__ __forceinline__ bool bwd_pair(const float4& a, const float4& b, const
                                          float g0, float g1, float g2, float& a0, float& a1, float& a2, float& last_alpha,
                                          float& lc0, float& lc1, float& lc2, float (&p)[9])
 {
-    const float dx = a.x - pxf, dy = a.y - pyf;
-    const float power = fmaf(fmaf(a.z, dx, a.w * dy), dx, (b.x * dy) * dy);
+    float dx, dy;
+    const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
     if (power > 0.0f) return false;
     const float op = b.y;
     if (EXACT) {
@@ -1044,9 +1039,9 @@ __device__ __forceinline__ uint64_t bwd_pair_fast(const float4& a, const float4&
                                                   float& T, float Tfb, float g0, float g1, float g2, float& S, float (&p)[9])
 {
 #pragma clang fp contract(fast)
-    const float dx = a.x - pxf, dy = a.y - pyf;
-    const float power = fmaf(fmaf(a.z, dx, a.w * dy), dx, (b.x * dy) * dy); // identical to the forward's expression
-    const float G = __expf(power);                       // (power > 0: rejected by `ok`; see fwd_pair)
+    float dx, dy;
+    const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
+    const float G = __expf(power);                       // (power > 0: rejected by `ok`; see fwd_pair_m)
     const float op = b.y;
     const float alpha = guard_alpha(fminf(LG_ALPHA_MAX, op * G), op, power); // same decisions as the forward
     // the three compares as scalar lane masks, the valid set back to a predicate through inverse.ballot (round 5, as fwd_pair_m): the mask is
@@ -1118,10 +1113,10 @@ lg_blend_bwd(int W, int H, int gx, int S, const uint2* __restrict__ work, const 
     uint32_t wmax = 0;
 #pragma unroll
     for (int s = 0; s < 4; s++) {
-        const int pxi = tx * LG_TILE + (s & 1) * 8 + (int)(lane & 7), pyi = ty * LG_TILE + (s >> 1) * 8 + (int)(lane >> 3);
-        const bool inside = pxi < W && pyi < H;
-        const size_t pid = (size_t)pyi * W + pxi;
-        pxf[s] = (float)pxi; pyf[s] = (float)pyi;
+        const LgBlock g = lg_block(W, H, tx, ty, s, lane);
+        const bool inside = g.inside;
+        const size_t pid = (size_t)g.pyi * W + g.pxi;
+        pxf[s] = (float)g.pxi; pyf[s] = (float)g.pyi;
         inside4[s] = inside;
         T[s] = inside ? final_T[pid] : 0.0f;
         last[s] = inside ? n_contrib[pid] : 0u;
@@ -1138,21 +1133,21 @@ lg_blend_bwd(int W, int H, int gx, int S, const uint2* __restrict__ work, const 
     const uint32_t n_list = range.y - range.x;
     if (n_list == 0) return;
     // this work item = list entries [seg_lo, seg_hi) of the tile (the whole list unless it is longer than S)
-    const uint32_t nseg = (n_list + (uint32_t)S - 1u) / (uint32_t)S;
+    const uint32_t nseg = lg_nseg(n_list, (uint32_t)S);
     const uint32_t seg_lo = item.y * (uint32_t)S, seg_hi = min(n_list, seg_lo + (uint32_t)S);
     if (wmax > seg_hi) wmax = seg_hi;
     if (item.y + 1u < nseg) {
         // not the last segment: start from the forward's checkpoints instead of the end of the list.  T = transmittance at
         // the end of this segment; colour behind = (colour accumulated inside all later segments) / T -- a quotient of a sum
         // of non-negative terms, as well conditioned as the published back-to-front accumulation.
-        const float4* cr = ckpt + (size_t)2 * (range.x / (uint32_t)S) * 256;
+        const float4* cr = ckpt + lg_ckpt_base(range.x, (uint32_t)S);                 // (record layout: lg_math.h)
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            const uint32_t pix = ((uint32_t)(s >> 1) * 8u + (lane >> 3)) * 16u + (uint32_t)(s & 1) * 8u + (lane & 7u);
-            const float4 here = cr[(size_t)item.y * 256 + pix];
+            const uint32_t pix = lg_block(W, H, tx, ty, s, lane).pix();
+            const float4 here = cr[(size_t)item.y * LG_CKPT_PIX + pix];
             float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
             for (uint32_t j = nseg - 1u; j > item.y; j--) {            // back to front, like the replay itself
-                const float4 r = cr[(size_t)j * 256 + pix];
+                const float4 r = cr[(size_t)j * LG_CKPT_PIX + pix];
                 b0 += r.y; b1 += r.z; b2 += r.w;
             }
             if (inside4[s]) {

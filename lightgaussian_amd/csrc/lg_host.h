@@ -176,7 +176,7 @@ struct BinView {
                                     //      (0 = none), 4 = number of par_work items (all written by lg_work_order_body)
     float4* ckpt;                   // [2 (R / S + 1)][256] checkpoint records {T, segment colour} of long tiles (lg_blend_fwd)
     uint32_t* ckpt_last;            // [2 (R / S + 1)][256] last contributing list position per (segment, pixel): pass 1 -> join of
-                                    //     the parallel long-tile forward (lg_blend_fwd_seg / _scan / _rewalk)
+                                    //     the parallel long-tile forward (lg_blend_fwd_seg with its lg_scan_tile, lg_blend_fwd_rewalk)
     uint64_t* entries;              // [R] sorted list entries = the sorted keys (tile | depth | id); the low bits_for(N) bits are the Gaussian id
     uint64_t* keys_in;              // [R] radix-sort input; free after the sort: ping-pong buffer of lg_tile_sort_long / of lg_tile_ranges' long runs,
                                     //     then -- per-hit weight policies -- the per-instance {count | weight} words of lg_blend_fwd<COUNT, FSCORE>
@@ -195,8 +195,8 @@ static BinView carve_bin(void* base, int64_t R, int W, int H, int seg)
     v.par_work = (uint2*)take(((size_t)gx * gy + n / S + 1) * 8);
     v.par_arrived = (uint32_t*)take((size_t)gx * gy * 4);
     v.long_tiles = (uint32_t*)take(((size_t)gx * gy + 1) * 4);
-    v.ckpt = (float4*)take(2 * (n / S + 1) * 256 * 16);
-    v.ckpt_last = (uint32_t*)take(2 * (n / S + 1) * 256 * 4);
+    v.ckpt = (float4*)take(lg_ckpt_records(n, S) * LG_CKPT_PIX * 16);                 // (record layout: lg_math.h)
+    v.ckpt_last = (uint32_t*)take(lg_ckpt_records(n, S) * LG_CKPT_PIX * 4);
     v.entries = (uint64_t*)take(n * 8);
     v.keys_in = (uint64_t*)take(n * 8);
     const size_t tb = lg_sort_layout(n).total;

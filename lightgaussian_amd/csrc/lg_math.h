@@ -12,6 +12,7 @@
 // utils/sh_utils.py:26-103, utils/general_utils.py:68-119, scene/cameras.py:70-85.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -301,21 +302,44 @@ LG_HD void lg_sh_to_rgb(int deg, const float* sh, float px, float py, float pz, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The two expressions every include / exclude decision of the blend kernels rests on, written ONCE: the forward, count and
+// backward pair steps of lg_blend.h all call them, and so does lg_blend_pair below, which tests/cpu_harness pins against the
+// oracle -- a one-token slip here breaks bit parity on a handful of pixels per view.
+// lg_pair_power: power = ha dx^2 + nb dx dy + hc dy^2 of the pixel (pxf, pyf) under the splat centred at (gx, gy), canonical order.
+LG_HD float lg_pair_power(float gx, float gy, float ha, float nb, float hc, float pxf, float pyf, float& dx, float& dy)
+{
+    dx = gx - pxf; dy = gy - pyf;
+    return fmaf(fmaf(ha, dx, nb * dy), dx, (hc * dy) * dy);
+}
+// lg_alpha_exact: the canonical alpha (lg_exp; the clamp of the power only matters for pairs that `power <= 0` rejects anyway)
+LG_HD float lg_alpha_exact(float op, float power) { return fminf(LG_ALPHA_MAX, op * lg_exp(fminf(power, 0.0f))); }
+
+// ---------------------------------------------------------------------------------------------
+// Checkpoint records of long tiles (lists of more than one segment of S entries; ckpt / ckpt_last of BinView, lg_host.h): a
+// record holds one word per pixel of a 16 x 16 tile, and record j of the tile whose list starts at entry `first` is
+//   ckpt[lg_ckpt_base(first, S) + j * LG_CKPT_PIX + pixel]     (pixel = 16 row + column inside the tile)
+// 2 floor(first / S) leaves room for the tile's ceil(n / S) records before the next long tile's, so 2 (R / S + 1) records hold
+// any view of R instances (carve_bin).  The forward's writers and the backward's reader must agree on this to the word.
+#define LG_CKPT_PIX (LG_TILE * LG_TILE)
+LG_HD uint32_t lg_nseg(uint32_t n, uint32_t S) { return (n + S - 1u) / S; }                  // segments of a list of n entries
+LG_HD size_t lg_ckpt_base(uint32_t first, uint32_t S) { return (size_t)2 * (first / S) * LG_CKPT_PIX; }
+LG_HD size_t lg_ckpt_records(size_t R, size_t S) { return 2 * (R / S + 1); }
+
+// ---------------------------------------------------------------------------------------------
 // One (pixel, Gaussian) evaluation of the forward blend, canonical order.
 // Returns 0 = rejected, 1 = contributes (T, C updated), 2 = pixel saturated (done).
 template <bool EXACT>
 LG_HD int lg_blend_pair(float gx, float gy, float ha, float nb, float hc, float op, float r, float g, float b, float pxf,
                         float pyf, float& T, float& C0, float& C1, float& C2, float& alpha_out)
 {
-    const float dx = gx - pxf, dy = gy - pyf;
-    const float power = fmaf(fmaf(ha, dx, nb * dy), dx, (hc * dy) * dy);
-    if (power > 0.0f) return 0;
+    float dx, dy;
+    const float power = lg_pair_power(gx, gy, ha, nb, hc, pxf, pyf, dx, dy);
+    if (!(power <= 0.0f)) return 0;             // the kernels' test (a NaN power is rejected, as there)
 #if defined(__HIP_DEVICE_COMPILE__)
-    const float ex = EXACT ? lg_exp(power) : __expf(power);
+    const float alpha = EXACT ? lg_alpha_exact(op, power) : fminf(LG_ALPHA_MAX, op * __expf(power));
 #else
-    const float ex = lg_exp(power);
+    const float alpha = lg_alpha_exact(op, power);
 #endif
-    const float alpha = fminf(LG_ALPHA_MAX, op * ex);
     if (alpha < LG_ALPHA_MIN) return 0;
     const float test_T = T * (1.0f - alpha);
     if (test_T < LG_T_MIN) return 2;
