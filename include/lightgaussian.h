@@ -318,6 +318,34 @@ int lg_vq_ema_step(int32_t n, int32_t d, int32_t K, const float* x, const float*
 int lg_vq_colors(int32_t N, int32_t M, int32_t sh_degree, const float* means3D, const float* campos, const uint32_t* slot,
                  const void* rows_f16, int32_t row_stride_bytes, float* out_rgb, uint32_t flags, void* stream);
 
+/* --- backward of lg_vq_colors: fine-tuning a compressed model in place -------------------------------
+ * dL_drgb [N,3] (what lg_backward leaves for colors_precomp) -> the gradient of the row table and the colour part of dL/dmeans3D:
+ *   dL_drows[r][idx(M,k,c)] = sum over i with slot[i] = r of  [rgb_{i,c} not clamped] B_k(normalize(means3D[i] - campos)) dL_drgb[i][c]
+ *                             for k < (sh_degree + 1)^2;  exactly 0 for the other columns and for a codebook row no Gaussian uses
+ *   dL_dmeans3D[i]          = the view-direction term (colour -> direction -> position); NULL: not computed
+ * dL_drows is [n_rows][3 M] float32, UNPADDED, columns in the file's order of a row (see lg_vq_colors).  The arithmetic per
+ * Gaussian is the dense backward's own (the values of the fp16 row the forward read, the clamp re-evaluated from them): the
+ * gradient row of a Gaussian with a row of its own equals the dense model's dL/dSH row bit for bit.
+ * Rows r >= K (one Gaussian each, by the format) are written by their Gaussian; a slot >= n_rows is ignored.  Rows r < K are a
+ * segmented sum over the model's code index.  SUMMATION ORDER: the Gaussians of a code are added in ascending Gaussian index
+ * inside chunks of 256 consecutive list entries, acc = acc + term starting from 0; the chunk sums are then added in chunk order.
+ * No float atomics: the result is a function of the arguments alone, bit-identical run to run and across streams.
+ * Every element of dL_drows is final when the call's work on `stream` completes (no caller-side clear).
+ *
+ * lg_vq_code_index builds the index of a model ONCE (the assignment does not change during fine-tuning): slot [N] uint32,
+ * slot < K = a code; index: lg_vq_code_index_bytes(N, K) device bytes that must stay alive and unmodified while used;
+ * scratch: lg_vq_code_index_scratch_bytes(N, K) device bytes, free again when the stream has passed the call.
+ * lg_vq_colors_bwd: scratch of lg_vq_colors_bwd_scratch_bytes(N, M, K) device bytes (the chunk sums), private to the stream.
+ * 0 <= N < 2^30, 1 <= K <= 2^24, K <= n_rows < 2^31 (the size queries return 0 otherwise).  All launches on `stream`, no host
+ * synchronisation.  flags: LG_FLAG_DEBUG, LG_FLAG_PROFILE. */
+size_t lg_vq_code_index_bytes(int32_t N, int32_t K);
+size_t lg_vq_code_index_scratch_bytes(int32_t N, int32_t K);
+int lg_vq_code_index(int32_t N, int32_t K, const uint32_t* slot, void* index, void* scratch, void* stream);
+size_t lg_vq_colors_bwd_scratch_bytes(int32_t N, int32_t M, int32_t K);
+int lg_vq_colors_bwd(int32_t N, int32_t M, int32_t sh_degree, int32_t K, int64_t n_rows, const float* means3D, const float* campos,
+                     const uint32_t* slot, const void* rows_f16, int32_t row_stride_bytes, const float* dL_drgb, const void* index,
+                     float* dL_drows, float* dL_dmeans3D, void* scratch, uint32_t flags, void* stream);
+
 /* out[j] = (((rows[0][j] + rows[1][j]) + rows[2][j]) + ...) over V rows of n floats (row pitch row_stride floats): the
  * sequential in-place float accumulation of per-view scores in prune.py:144-155, in view order, as one launch. */
 int lg_ordered_sum(int32_t V, int64_t n, const float* rows, int64_t row_stride, float* out, void* stream);

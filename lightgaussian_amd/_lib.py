@@ -34,7 +34,9 @@ EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scr
            "lg_compact_plan", "lg_compact_rows", "lg_vq_scratch_bytes", "lg_vq_nearest", "lg_debug_sort_temp_bytes",
            "lg_debug_sort_keys", "lg_build_id", "lg_backward_chunked", "lg_debug_activations", "lg_view_status",
            "lg_debug_sort_orphan", "lg_debug_last_contributor", "lg_debug_tile_lists", "lg_geom_visible_offset",
-           "lg_sh_grad_from_rgb", "lg_debug_view_meta", "lg_vq_ema_scratch_bytes", "lg_vq_ema_step", "lg_vq_colors"]
+           "lg_sh_grad_from_rgb", "lg_debug_view_meta", "lg_vq_ema_scratch_bytes", "lg_vq_ema_step", "lg_vq_colors",
+           "lg_vq_code_index_bytes", "lg_vq_code_index_scratch_bytes", "lg_vq_code_index", "lg_vq_colors_bwd_scratch_bytes",
+           "lg_vq_colors_bwd"]
 
 
 class lg_view(C.Structure):
@@ -136,6 +138,14 @@ def load():
     lib.lg_vq_ema_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, C.c_uint32, vp]
     lib.lg_vq_colors.restype = C.c_int
     lib.lg_vq_colors.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, C.c_uint32, vp]
+    lib.lg_vq_code_index_bytes.restype = C.c_size_t; lib.lg_vq_code_index_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.lg_vq_code_index_scratch_bytes.restype = C.c_size_t; lib.lg_vq_code_index_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.lg_vq_code_index.restype = C.c_int
+    lib.lg_vq_code_index.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp]
+    lib.lg_vq_colors_bwd_scratch_bytes.restype = C.c_size_t; lib.lg_vq_colors_bwd_scratch_bytes.argtypes = [C.c_int32] * 3
+    lib.lg_vq_colors_bwd.restype = C.c_int
+    lib.lg_vq_colors_bwd.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp,
+                                     C.c_uint32, vp]
     lib.lg_debug_sort_temp_bytes.restype = C.c_size_t; lib.lg_debug_sort_temp_bytes.argtypes = [C.c_int64]
     lib.lg_debug_sort_keys.restype = C.c_int
     lib.lg_debug_sort_keys.argtypes = [C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp]

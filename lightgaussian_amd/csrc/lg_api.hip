@@ -14,6 +14,8 @@
 //   lg_vq.h          lg_vq_nearest: nearest-code search of the VecTree quantiser on f32 MFMA (32x32x2), fused row argmin
 //   lg_vq_train.h    lg_vq_ema_step: one EMA k-means step of the VecTree codebook (search, inverted index, ordered segmented sum, EMA)
 //   lg_vq_color.h    lg_vq_colors: per-Gaussian colours of a VecTree-compressed model (fp16 row table + slot) through the same lg_sh_to_rgb as K1
+//   lg_vq_color_bwd.h lg_vq_code_index / lg_vq_colors_bwd: its backward -- per-row gradients of the row table (ordered segmented sum over a
+//                    per-model inverted index for the codebook rows) and the colour part of dL/dxyz
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound)
 //
 // Pipeline of one view:
@@ -37,6 +39,7 @@
 #include "lg_vq.h"
 #include "lg_vq_train.h"
 #include "lg_vq_color.h"
+#include "lg_vq_color_bwd.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -816,6 +819,109 @@ extern "C" int lg_vq_ema_step(int32_t n, int32_t d, int32_t K, const float* x, c
         lg_vq_epilogue<<<(unsigned)(((size_t)K * d + 255) / 256), 256, 0, stream>>>(uK, d, v.esum, cluster_size, v.scal, embed, decay_f, one_minus,
                                                                                     (float)eps, (float)((double)K * eps));
         KCHECK("lg_vq_epilogue");
+    }
+    return LG_OK;
+}
+
+// ---- backward of lg_vq_colors (lg_vq_color_bwd.h) ----
+static bool vq_index_shape_ok(int32_t N, int32_t K) { return N >= 0 && N < (1 << 30) && K >= 1 && K <= (1 << 24); }
+
+extern "C" size_t lg_vq_code_index_bytes(int32_t N, int32_t K)
+{
+    return vq_index_shape_ok(N, K) ? carve_vq_index(nullptr, (size_t)N, (size_t)K).total : 0;
+}
+
+extern "C" size_t lg_vq_code_index_scratch_bytes(int32_t N, int32_t K)
+{
+    return vq_index_shape_ok(N, K) ? carve_vq_index_scratch(nullptr, (size_t)N).total : 0;
+}
+
+extern "C" int lg_vq_code_index(int32_t N, int32_t K, const uint32_t* slot, void* index, void* scratch, void* stream_p)
+{
+    if (!vq_index_shape_ok(N, K)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_code_index: need 0 <= N < 2^30, 1 <= K <= 2^24");
+    if (!index || (N > 0 && (!slot || !scratch))) return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_code_index: missing buffer");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = false;
+    const VqIndexView v = carve_vq_index(index, (size_t)N, (size_t)K);
+    if (N == 0) {                                   // every list empty: start = chunk_off = 0, no error
+        HIP_TRY(hipMemsetAsync(index, 0, v.total, stream));
+        return LG_OK;
+    }
+    const VqIndexScratch s = carve_vq_index_scratch(scratch, (size_t)N);
+    const uint32_t un = (uint32_t)N, uK = (uint32_t)K;
+    int code_bits = 1;
+    while ((1u << code_bits) <= uK) code_bits++;    // the pseudo-code K of the non-VQ Gaussians included
+    lg_vq_slot_keys<<<(un + 255) / 256, 256, 0, stream>>>(un, uK, slot, s.keys_in);
+    KCHECK("lg_vq_slot_keys");
+    size_t tb = s.sort_temp_bytes;
+    HIP_TRY(lg_sort_keys(s.sort_temp, tb, s.keys_in, s.keys_out, un, 32, 32 + code_bits, nullptr, false, stream));
+    KCHECK("lg_sort_keys");
+    lg_vq_starts<<<(un + 255) / 256, 256, 0, stream>>>(un, uK + 1u, s.keys_out, v.start);
+    KCHECK("lg_vq_starts");
+    lg_vq_chunk_scan<<<1, LG_VQ_RED_THREADS, 0, stream>>>(uK, v.start, v.chunk_off, 0u, nullptr, nullptr);
+    KCHECK("lg_vq_chunk_scan");
+    const uint32_t* sort_err = (const uint32_t*)((char*)s.sort_temp + lg_sort_layout((size_t)N).ticket_off) + 15;
+    lg_vq_index_ids<<<(un + 255) / 256, 256, 0, stream>>>(un, s.keys_out, sort_err, v.ids, v.err);
+    KCHECK("lg_vq_index_ids");
+    return LG_OK;
+}
+
+extern "C" size_t lg_vq_colors_bwd_scratch_bytes(int32_t N, int32_t M, int32_t K)
+{
+    if (!vq_index_shape_ok(N, K) || M < 1 || M > 16) return 0;
+    return align_up(std::max<size_t>(lg_vq_bwd_max_chunks((size_t)N, (size_t)K), 1) * 3 * (size_t)M * sizeof(float));
+}
+
+extern "C" int lg_vq_colors_bwd(int32_t N, int32_t M, int32_t sh_degree, int32_t K, int64_t n_rows, const float* means3D, const float* campos,
+                                const uint32_t* slot, const void* rows_f16, int32_t row_stride_bytes, const float* dL_drgb, const void* index,
+                                float* dL_drows, float* dL_dmeans3D, void* scratch, uint32_t flags, void* stream_p)
+{
+    if (!vq_index_shape_ok(N, K) || !(M == 1 || M == 4 || M == 9 || M == 16) || sh_degree < 0 || sh_degree > 3 ||
+        (sh_degree + 1) * (sh_degree + 1) > M || n_rows < K || n_rows >= ((int64_t)1 << 31))
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_colors_bwd: 0 <= N < 2^30, M in {1, 4, 9, 16}, (D + 1)^2 <= M, K <= n_rows < 2^31 required");
+    if (row_stride_bytes < 6 * M || (row_stride_bytes & 15) != 0 || ((uintptr_t)rows_f16 & 15) != 0)
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_colors_bwd: rows must be 16-byte aligned, row_stride_bytes a multiple of 16 and >= 6 M");
+    if (!dL_drows || !index || !scratch || !rows_f16 || (N > 0 && (!means3D || !campos || !slot || !dL_drgb)))
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_colors_bwd: missing buffer");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = flags & LG_FLAG_DEBUG, prof = flags & LG_FLAG_PROFILE;
+    const uint32_t need = lg_vq_need_mask(M, sh_degree);
+    const VqIndexView v = carve_vq_index(const_cast<void*>(index), (size_t)N, (size_t)K);
+    const unsigned char* rows = (const unsigned char*)rows_f16;
+    const uint32_t stride = (uint32_t)row_stride_bytes, uK = (uint32_t)K;
+    float* partial = (float*)scratch;
+    if (N > 0) {
+        ProfScope ps(prof, "vq_colors_bwd_rows", stream);
+        const unsigned grid = (unsigned)((N + LG_VQ_BWD_WAVE - 1) / LG_VQ_BWD_WAVE);
+#define LAUNCH_VQB(MM) lg_vq_colors_bwd_rows_kernel<MM><<<grid, LG_VQ_BWD_WAVE, 0, stream>>>(N, sh_degree, need, uK, (uint32_t)n_rows, means3D, campos, \
+                                                                                           slot, rows, stride, dL_drgb, dL_drows, dL_dmeans3D)
+        switch (M) {
+            case 1: LAUNCH_VQB(1); break;
+            case 4: LAUNCH_VQB(4); break;
+            case 9: LAUNCH_VQB(9); break;
+            default: LAUNCH_VQB(16); break;
+        }
+#undef LAUNCH_VQB
+        KCHECK("lg_vq_colors_bwd_rows_kernel");
+    }
+    {
+        ProfScope ps(prof, "vq_colors_bwd_codes", stream);
+        const unsigned grid = (unsigned)lg_vq_bwd_max_chunks((size_t)N, (size_t)K);
+        if (grid > 0) {
+#define LAUNCH_VQB(MM) lg_vq_colors_bwd_chunk_kernel<MM><<<grid, LG_VQ_BWD_WAVE, 0, stream>>>(sh_degree, need, uK, means3D, campos, rows, stride, dL_drgb, \
+                                                                                            v.ids, v.start, v.chunk_off, v.err, partial)
+            switch (M) {
+                case 1: LAUNCH_VQB(1); break;
+                case 4: LAUNCH_VQB(4); break;
+                case 9: LAUNCH_VQB(9); break;
+                default: LAUNCH_VQB(16); break;
+            }
+#undef LAUNCH_VQB
+            KCHECK("lg_vq_colors_bwd_chunk_kernel");
+        }
+        lg_vq_colors_bwd_combine<<<(unsigned)(((size_t)K * 3 * M + 255) / 256), 256, 0, stream>>>(uK, (uint32_t)(3 * M), v.chunk_off, partial, v.err,
+                                                                                                 dL_drows);
+        KCHECK("lg_vq_colors_bwd_combine");
     }
     return LG_OK;
 }

@@ -15,7 +15,7 @@ import torch
 from . import rasterizer as _rasterizer
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_raw
 from .sh_utils import eval_sh
-from .vectree import CompressedGaussians
+from .vectree import CompressedGaussians, TrainableCompressed
 
 
 def _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, f_count):
@@ -115,6 +115,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     are evaluated INSIDE the kernels from the raw parameters (render_fused: no torch.cat of the SH tensors, no
     activation kernels; same values to ~1e-7, gradients land on the raw parameters exactly as autograd would route
     them).  set_option("fuse_getters", False) restores the reference's literal call pattern."""
+    if isinstance(pc, TrainableCompressed) and override_color is None:
+        return render_compressed_trainable(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, options=options)
     if isinstance(pc, CompressedGaussians) and override_color is None:
         return render_compressed(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, options=options)
     if (_rasterizer.resolve_options(options)["fuse_getters"] and override_color is None and not pipe.convert_SHs_python
@@ -149,6 +151,16 @@ def render_compressed(viewpoint_camera, cg, pipe, bg_color: torch.Tensor, scalin
         pkg = _render_unfused(viewpoint_camera, cg, pipe, bg_color, scaling_modifier, colors, options)
     pkg["viewspace_points"] = pkg["viewspace_points"].detach()
     return pkg
+
+
+def render_compressed_trainable(viewpoint_camera, tc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, *, options=None):
+    """The grad-enabled twin of render_compressed for a vectree.TrainableCompressed: the same kernels on the same float16 rows
+    (the image bits are render_compressed's), with autograd attached -- tc.colors() is differentiable (lg_vq_colors_bwd), the
+    rasterizer returns dL/dcolors_precomp and the geometry gradients, viewspace_points stays attached for its .grad."""
+    if pipe.convert_SHs_python or pipe.compute_cov3D_python:
+        raise NotImplementedError("convert_SHs_python / compute_cov3D_python need the dequantised tensors: render tc.to_dense() instead")
+    colors = tc.colors(viewpoint_camera.camera_center)
+    return _render_unfused(viewpoint_camera, tc, pipe, bg_color, scaling_modifier, colors, options)
 
 
 def count_render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, *, options=None):

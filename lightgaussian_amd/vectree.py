@@ -18,7 +18,9 @@ columns, d = 27 (SH degree 2) or 48 (degree 3).
 pack / save / load / unpack speak that format bit for bit in both directions; quantize_model is the whole of
 Quantization.quantize() on the GPU (vq.train_codebook, vq.nearest_code); CompressedGaussians keeps a loaded model on the
 device in its compressed form and colors() / gaussian_renderer.render_compressed() render it without ever building the
-[N, d] float32 SH table (csrc/lg_vq_color.h).
+[N, d] float32 SH table (csrc/lg_vq_color.h).  CompressedGaussians.trainable() makes that form trainable in place
+(TrainableCompressed: float32 masters of the rows and of the other attributes, a straight-through forward on their float16
+values, lg_vq_colors_bwd of csrc/lg_vq_color_bwd.h as the backward of colors()); repack() gives the model back as the seven arrays.
 """
 import ctypes as C
 import math
@@ -205,7 +207,8 @@ class CompressedGaussians:
         rows     float16 [K + n_nonvq, row_stride / 2]: the codebook rows, then the non-VQ rows, each padded with zeros to a
                  multiple of 16 bytes (d = 27: 54 -> 64 bytes; d = 48: 96)
         slot     uint32 [N]: the row of each Gaussian -- its code for a VQ row, K + its rank among the non-VQ rows otherwise
-    The raw attributes as stored stay on the host for to_dense().  Forward-only: no tensor here takes gradients."""
+    The raw attributes as stored stay on the host for to_dense().  Forward-only: no tensor here takes gradients; trainable()
+    returns the form that does."""
 
     def __init__(self, xyz, opacity, scaling, rotation, rows, slot, codebook_size, sh_dim, other_raw):
         self.xyz, self.opacity, self.scaling, self.rotation = xyz, opacity, scaling, rotation
@@ -291,6 +294,11 @@ class CompressedGaussians:
             _scaling=other[:, 1:4].contiguous(), _rotation=other[:, 4:8].contiguous(), _opacity=other[:, 0:1].contiguous(),
             active_sh_degree=self.active_sh_degree, max_sh_degree=self.max_sh_degree)
 
+    def trainable(self, params=("rows",)):
+        """This model as a TrainableCompressed: float32 masters, the tensors named in `params` (of "rows", "xyz", "opacity",
+        "scaling", "rotation") as nn.Parameters.  The model itself is left as it is (the trainable copy owns its tensors)."""
+        return TrainableCompressed(self, params)
+
     def colors(self, camera_center, sh_degree=None, out=None, flags=0):
         """[N, 3] float32: clamp_min(eval_sh(degree, SH row, normalised view direction) + 0.5, 0) of every Gaussian for a camera
         at `camera_center` -- lg_vq_colors, one HIP launch on the current stream, no synchronisation.  HIP tensors only."""
@@ -309,3 +317,184 @@ class CompressedGaussians:
             _lib.check(lib.lg_vq_colors(N, self.sh_dim // 3, D, self.xyz.data_ptr(), cam.data_ptr(), self._slot.data_ptr(),
                                         self.rows.data_ptr(), self.row_stride, out.data_ptr(), int(flags), stream))
         return out
+
+
+class _RoundHalf(torch.autograd.Function):
+    """x -> float32(float16(x)) with a straight-through gradient: the forward sees the value the file will hold."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.half().float()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+class _VqColors(torch.autograd.Function):
+    """colors() of a TrainableCompressed: lg_vq_colors forward on the fp16 table, lg_vq_colors_bwd backward onto the float32
+    master of the rows (straight-through) and, when it takes gradients, onto xyz."""
+
+    @staticmethod
+    def forward(ctx, rows_master, xyz, model, cam, D):
+        ctx.model, ctx.cam, ctx.D = model, cam, D
+        return CompressedGaussians.colors(model, cam, sh_degree=D)
+
+    @staticmethod
+    def backward(ctx, g):
+        m = ctx.model
+        dev, N, d, K = m._xyz.device, m.num, m.sh_dim, m.codebook_size
+        g = g.to(torch.float32).contiguous()
+        lib = _lib.load()
+        drows = torch.empty((m.rows.shape[0], d), dtype=torch.float32, device=dev)
+        dxyz = torch.empty((N, 3), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        scratch = torch.empty(max(int(lib.lg_vq_colors_bwd_scratch_bytes(N, d // 3, K)), 16), dtype=torch.uint8, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with torch.cuda.device(dev):
+            _lib.check(lib.lg_vq_colors_bwd(N, d // 3, ctx.D, K, m.rows.shape[0], m._xyz.data_ptr(), ctx.cam.data_ptr(), m._slot.data_ptr(),
+                                            m.rows.data_ptr(), m.row_stride, g.data_ptr(), m._index.data_ptr(), drows.data_ptr(),
+                                            dxyz.data_ptr() if dxyz is not None else None, scratch.data_ptr(), 0, stream))
+        return (drows if ctx.needs_input_grad[0] else None), dxyz, None, None, None
+
+
+class TrainableCompressed(CompressedGaussians):
+    """A CompressedGaussians that can be fine-tuned in its compressed form (CompressedGaussians.trainable()):
+        _rows     float32 master [K + n_nonvq, d] of the row table, unpadded, in the file's column order
+        _xyz      float32 [N, 3]
+        _opacity  [N, 1], _scaling [N, 3], _rotation [N, 4]: float32 masters of the raw other attributes
+    each an nn.Parameter when named in `params`.  The forward is straight-through on the values the file will hold: colors()
+    reads the padded float16 table `rows` (= _rows.half(); sync_rows() refreshes it after an optimizer step, colors() does so
+    itself when _rows has been modified in place), the geometry getters return the activation of raw.half().float() -- what is
+    trained is exactly what repack() / save() write.  slot (the assignment) is fixed; its inverted index for the backward is
+    built once, here."""
+    PARAMS = ("rows", "xyz", "opacity", "scaling", "rotation")
+
+    def __init__(self, cg, params=("rows",)):
+        params = (params,) if isinstance(params, str) else tuple(params)
+        unknown = [p for p in params if p not in self.PARAMS]
+        if unknown:
+            raise ValueError(f"trainable: unknown parameter names {unknown}; choose from {self.PARAMS}")
+        d = cg.sh_dim
+        dev = cg.xyz.device
+        self._slot = cg._slot
+        self.codebook_size, self.sh_dim = cg.codebook_size, d
+        self.max_sh_degree, self.active_sh_degree = cg.max_sh_degree, cg.active_sh_degree
+        self.rows = cg.rows.detach().clone()
+        other = cg._other_raw.to(dev).float()
+
+        def own(name, t):
+            t = t.detach().clone().contiguous()
+            return torch.nn.Parameter(t) if name in params else t
+
+        self._rows = own("rows", self.rows[:, :d].float())
+        self._xyz = own("xyz", cg.xyz)
+        self._opacity = own("opacity", other[:, 0:1])
+        self._scaling = own("scaling", other[:, 1:4])
+        self._rotation = own("rotation", other[:, 4:8])
+        # the activations of a tensor that is not trained never change: keep the source's
+        self._fixed = {"opacity": cg.opacity, "scaling": cg.scaling, "rotation": cg.rotation}
+        self._synced = self._rows._version
+        self._index = None
+        if dev.type == "cuda":
+            self._build_index()
+
+    def _build_index(self):
+        """lg_vq_code_index: the inverted index of slot[] (per code, its Gaussians in ascending order), once per model."""
+        if not self._xyz.is_cuda:
+            raise RuntimeError("TrainableCompressed runs on the MI355X HIP library only (no CPU fallback): use to_dense()")
+        lib = _lib.load()
+        dev, N, K = self._xyz.device, self.num, self.codebook_size
+        nbytes = int(lib.lg_vq_code_index_bytes(N, K))
+        if nbytes == 0:
+            raise ValueError(f"trainable: no code index for N = {N}, K = {K}")
+        self._index = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(max(int(lib.lg_vq_code_index_scratch_bytes(N, K)), 16), dtype=torch.uint8, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with torch.cuda.device(dev):
+            _lib.check(lib.lg_vq_code_index(N, K, self._slot.data_ptr(), self._index.data_ptr(), scratch.data_ptr(), stream))
+
+    def parameters(self):
+        """The tensors named in trainable(params=...), for an optimizer."""
+        return [t for t in (self._rows, self._xyz, self._opacity, self._scaling, self._rotation) if isinstance(t, torch.nn.Parameter)]
+
+    @property
+    def xyz(self):
+        return self._xyz
+
+    @property
+    def get_xyz(self):
+        return self._xyz
+
+    def _activated(self, name, raw, fn):
+        if not raw.requires_grad:
+            return self._fixed[name]
+        return fn(_RoundHalf.apply(raw))
+
+    @property
+    def get_opacity(self):
+        return self._activated("opacity", self._opacity, torch.sigmoid)
+
+    @property
+    def get_scaling(self):
+        return self._activated("scaling", self._scaling, torch.exp)
+
+    @property
+    def get_rotation(self):
+        return self._activated("rotation", self._rotation, torch.nn.functional.normalize)
+
+    opacity, scaling, rotation = get_opacity, get_scaling, get_rotation
+
+    @property
+    def _other_raw(self):
+        """other_attribute as the file will hold it: float16 [N, 8]"""
+        return torch.cat([self._opacity, self._scaling, self._rotation], dim=1).detach().half()
+
+    def to_dense(self):
+        """CompressedGaussians.to_dense() of the model as it stands now (detached: the dense model has leaves of its own)."""
+        with torch.no_grad():
+            if self._rows._version != self._synced:
+                self.sync_rows()
+            return super().to_dense()
+
+    def sync_rows(self):
+        """rows[:, :d] <- _rows.half(): the float16 table the forward reads.  The zero padding of every row is not touched."""
+        with torch.no_grad():
+            self.rows[:, :self.sh_dim].copy_(self._rows)
+        self._synced = self._rows._version
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self._xyz, self._opacity, self._scaling, self._rotation, self._slot, self.rows,
+                                                          self._rows) + (() if self._index is None else (self._index,)))
+
+    def colors(self, camera_center, sh_degree=None, out=None, flags=0):
+        """CompressedGaussians.colors() on the float16 values of _rows, differentiable: dL/d_rows (and dL/d_xyz when _xyz
+        takes gradients) by lg_vq_colors_bwd -- a fixed-order segmented sum onto the codebook rows, no atomics."""
+        if not self._xyz.is_cuda:
+            raise RuntimeError("CompressedGaussians.colors runs on the MI355X HIP library only (no CPU fallback): use to_dense()")
+        if self._rows._version != self._synced:
+            self.sync_rows()
+        if out is not None or flags or not (torch.is_grad_enabled() and (self._rows.requires_grad or self._xyz.requires_grad)):
+            return CompressedGaussians.colors(self, camera_center, sh_degree, out, flags)
+        D = self.active_sh_degree if sh_degree is None else int(sh_degree)
+        cam = camera_center.detach().to(device=self._xyz.device, dtype=torch.float32).contiguous()
+        return _VqColors.apply(self._rows, self._xyz, self, cam, D)
+
+    def repack(self):
+        """The seven arrays of pack() for save(): indices and mask as the model came (they follow from slot), rows and
+        attributes cast to float16, xyz float32.  Of an untouched trainable(): the dict it was loaded from, bit for bit."""
+        K, d, N = self.codebook_size, self.sh_dim, self.num
+        bits = _bits_of(K)
+        slot = _np(self._slot).astype(np.int64)
+        mask = slot >= K
+        shifts = np.arange(bits - 1, -1, -1, dtype=np.int64)
+        bit_rows = ((slot[~mask][:, None] >> shifts[None, :]) & 1).astype(np.bool_)
+        rows = _np(self._rows.detach().half())
+        return {
+            "metadata": {"input_pc_num": int(N), "input_pc_dim": int(6 + d + 8), "codebook_size": int(K), "codebook_dim": int(d)},
+            "vq_indexs": np.packbits(bit_rows.reshape(-1)),
+            "codebook": np.ascontiguousarray(rows[:K]),
+            "non_vq_mask": np.packbits(mask),
+            "non_vq_feats": np.ascontiguousarray(rows[K:]),
+            "other_attribute": np.ascontiguousarray(_np(self._other_raw)),
+            "xyz": np.ascontiguousarray(_np(self._xyz.detach()), dtype=np.float32),
+        }

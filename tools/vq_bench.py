@@ -18,7 +18,16 @@ synthetic scene and its orbit cameras at 1080p) rendered forward-only, per view 
   (a) render() of cg.to_dense() under no_grad -- the dequantised float32 model, the only way to show it without lg_vq_colors;
   (b) render_compressed(cg): lg_vq_colors + the forward on colors_precomp.
 Prints the median and the min..max over the repeats of both, lg_vq_colors alone under an event bracket with
-GB/s by its byte model, 12 + 4 + 6 (D + 1)^2 read and 12 written per Gaussian, and cg.nbytes() against the dense model's bytes."""
+GB/s by its byte model, 12 + 4 + 6 (D + 1)^2 read and 12 written per Gaussian, and cg.nbytes() against the dense model's bytes.
+
+--leg finetune (not part of "all"): forward + backward of an L1 loss per view on the same models and cameras, warm, in
+alternating repeats of
+  (a) render(cg.to_dense()) with the getters fused;
+  (b) the same with fuse_getters off -- the like-for-like comparand: the compressed path feeds the unfused forward;
+  (c) render(cg.trainable(all five tensors)): the compressed model trained in place, lg_vq_colors_bwd in the backward.
+Every tensor of either model takes gradients (SH rows, xyz, opacity, scaling, rotation).
+Prints median (min..max) of the three, and the peak allocated memory of one step of (a) and (c), gradient buffers included.
+--only-compressed runs (c) alone: the form to run under `rocprofv3 --kernel-trace --stats` for the new kernels' own times."""
 import argparse
 import os
 import sys
@@ -30,9 +39,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lightgaussian_amd import vq, prune
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--leg", choices=("all", "search", "compact", "train", "render"), default="all")
+ap.add_argument("--leg", choices=("all", "search", "compact", "train", "render", "finetune"), default="all")
 ap.add_argument("--iters", type=int, default=200, help="training iterations per timing (train leg)")
 ap.add_argument("--fused-only", action="store_true")
+ap.add_argument("--only-compressed", action="store_true", help="finetune leg: leg (c) alone")
+ap.add_argument("--degrees", type=int, nargs="+", default=[2, 3], help="SH degrees (finetune leg)")
 ap.add_argument("--sizes", type=int, nargs="+", default=[1_000_000, 3_000_000], help="Gaussians (render leg)")
 ap.add_argument("--repeats", type=int, default=7, help="timed repeats over all views (render leg, at least 5)")
 ap.add_argument("--views", type=int, default=8, help="orbit cameras (render leg)")
@@ -213,6 +224,93 @@ def render_leg(sizes, repeats, n_views):
             torch.cuda.empty_cache()
 
 
+def finetune_leg(sizes, degrees, repeats, n_views, only_compressed):
+    import statistics
+    from lightgaussian_amd import synthetic as syn, vectree
+    from lightgaussian_amd.gaussian_renderer import render
+    repeats = max(repeats, 5)
+    W, H, K = 1920, 1080, 8192
+    pipe = syn.PipelineParams()
+    bg = torch.zeros(3, device=dev)
+    cams = [syn.orbit_camera(k, n_views, W, H).to(dev) for k in range(n_views)]
+    target = torch.full((3, H, W), 0.25, device=dev)
+
+    def spread(ms):
+        return f"{statistics.median(ms):.3f} ms (min {min(ms):.3f}, max {max(ms):.3f})"
+
+    def step(model, leaves, cam, options):
+        for t in leaves:
+            t.grad = None
+        (render(cam, model, pipe, bg, options=options)["render"] - target).abs().mean().backward()
+
+    def per_view(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for cam in cams:
+            fn(cam)
+        t1.record(); t1.synchronize()
+        return t0.elapsed_time(t1) / len(cams)
+
+    def peak_of(fn):
+        fn(cams[0]); torch.cuda.synchronize(); torch.cuda.empty_cache(); torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn(cams[0]); torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated(), base
+
+    for N in sizes:
+        for deg in degrees:
+            d = 3 * (deg + 1) ** 2
+            g = syn.make_gaussians(N, sh_degree=deg)
+            gen = torch.Generator().manual_seed(N + deg)
+            feats = torch.cat([g._xyz, torch.zeros(N, 3), g._features_dc.transpose(1, 2).reshape(N, 3),
+                               g._features_rest.transpose(1, 2).reshape(N, -1), g._opacity, g._scaling, g._rotation], dim=1)
+            codebook = feats[torch.randint(0, N, (K,), generator=gen), 6:6 + d]
+            mask = torch.zeros(N, dtype=torch.bool)
+            mask[torch.topk(torch.rand(N, generator=gen), k=int(N * (1 - 0.6))).indices] = True
+            ind = vq.nearest_code(feats[:, 6:6 + d].to(dev), codebook.to(dev)).cpu()
+            cg = vectree.CompressedGaussians.from_packed(vectree.pack(feats, mask, codebook, ind), dev)
+            del feats, g
+            tc = cg.trainable(vectree.TrainableCompressed.PARAMS)
+            fc = lambda cam: step(tc, tc.parameters(), cam, None)                  # noqa: E731
+            if only_compressed:
+                for _ in range(2):
+                    per_view(fc)
+                ms_c = [per_view(fc) for _ in range(repeats)]
+                print(f"vq finetune N={N} degree={deg} {W}x{H} {n_views} views x {repeats} repeats, fwd+bwd per view:  (c) trainable compressed {spread(ms_c)}")
+                del cg, tc
+                torch.cuda.empty_cache()
+                continue
+            dense = cg.to_dense()
+            dense.requires_grad_(True)
+            sh_leaves = [dense._xyz, dense._features_dc, dense._features_rest, dense._opacity, dense._scaling, dense._rotation]
+            fa = lambda cam: step(dense, sh_leaves, cam, None)                     # noqa: E731
+            fb = lambda cam: step(dense, sh_leaves, cam, {"fuse_getters": False})  # noqa: E731
+            for _ in range(2):
+                per_view(fa); per_view(fb); per_view(fc)
+            ms_a, ms_b, ms_c = [], [], []
+            for _ in range(repeats):                                               # alternate, so that all see the same clocks
+                ms_a.append(per_view(fa)); ms_b.append(per_view(fb)); ms_c.append(per_view(fc))
+            b, c = statistics.median(ms_b), statistics.median(ms_c)
+            verdict = "faster" if c < min(ms_b) else "slower" if c > max(ms_b) else "within the spread of (b)"
+            print(f"vq finetune N={N} degree={deg} {W}x{H} {n_views} views x {repeats} repeats, fwd+bwd per view:  (a) dense, fused getters {spread(ms_a)}  "
+                  f"(b) dense, unfused {spread(ms_b)}  (c) trainable compressed {spread(ms_c)}  (c)/(b) {c / b:.3f} ({verdict})  "
+                  f"(c)/(a) {c / statistics.median(ms_a):.3f}")
+            for t in sh_leaves + tc.parameters():
+                t.grad = None
+            pa, ba = peak_of(fa)
+            for t in sh_leaves:
+                t.grad = None
+            pc, bc = peak_of(fc)
+            print(f"    peak allocated during one step, gradients included (both models resident: {bc / 1e6:.0f} MB before the step): "
+                  f"(a) {pa / 1e6:.1f} MB  (c) {pc / 1e6:.1f} MB;  step-local (a) {(pa - ba) / 1e6:.1f} MB  (c) {(pc - bc) / 1e6:.1f} MB;  "
+                  f"resident model bytes: trainable compressed {tc.nbytes() / 1e6:.1f} MB, dense "
+                  f"{sum(t.numel() * 4 for t in (dense._xyz, dense._features_dc, dense._features_rest, dense._opacity, dense._scaling, dense._rotation)) / 1e6:.1f} MB")
+            del cg, tc, dense, sh_leaves
+            torch.cuda.empty_cache()
+
+
+if args.leg == "finetune":
+    finetune_leg(args.sizes, args.degrees, args.repeats, args.views, args.only_compressed)
 if args.leg == "render":
     render_leg(args.sizes, args.repeats, args.views)
 if args.leg in ("all", "compact"):
