@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Fine-tune a VecTree-compressed model in its compressed form and write it back as an extreme_saving directory.
 
-    python examples/finetune_compressed.py [--load DIR] [--save DIR] [--steps 200] [--codebook 256] [--n 50000]
+    python examples/finetune_compressed.py [--load DIR] [--save DIR] [--steps 200] [--codebook 256] [--n 50000] [--hip-adam]
 
 Without --load a synthetic scene is quantised here (vectree.quantize_model); the training targets are renders of the
 unquantised scene.  With --load the directory is read (vectree.CompressedGaussians.load) and the targets are renders of the
@@ -27,6 +27,7 @@ ap.add_argument("--lr", type=float, default=2e-3)
 ap.add_argument("--n", type=int, default=50000, help="Gaussians of the synthetic scene")
 ap.add_argument("--codebook", type=int, default=256)
 ap.add_argument("--views", type=int, default=8)
+ap.add_argument("--hip-adam", action="store_true", help="step with lightgaussian_amd.optim.HipAdam (one lg_adam_step launch) instead of torch.optim.Adam")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -47,7 +48,11 @@ with torch.no_grad():
     targets = [render(cam, teacher, pipe, bg)["render"].clone() for cam in cams]
 
 tc = cg.trainable(("rows",))
-opt = torch.optim.Adam(tc.parameters(), lr=args.lr)
+if args.hip_adam:
+    from lightgaussian_amd import optim
+    opt = optim.HipAdam(tc.parameters(), lr=args.lr)
+else:
+    opt = torch.optim.Adam(tc.parameters(), lr=args.lr)
 
 
 def mean_l1():
@@ -62,7 +67,7 @@ for step in range(args.steps):
     (render(cam, tc, pipe, bg)["render"] - target).abs().mean().backward()
     opt.step()
     tc.sync_rows()                       # the forward reads the float16 table: refresh it from the master
-print(f"mean L1 after {args.steps} steps: {mean_l1():.6f}")
+print(f"mean L1 after {args.steps} steps of {type(opt).__name__}: {mean_l1():.6f}")
 if args.save:
     vectree.save(args.save, tc.repack())
     print(f"wrote {args.save}: {sum(os.path.getsize(os.path.join(args.save, f)) for f in os.listdir(args.save)) / 1e6:.2f} MB")

@@ -9,7 +9,7 @@ with this repo's drop-in pieces: gaussian_renderer.render (HIP rasterizer, gette
 loss_utils.l1_loss / ssim (one fused HIP launch for both).  The optimizer is torch.optim.Adam as in the reference
 (scene/gaussian_model.py:training_setup).
 
-    python examples/finetune_step.py [--n-gaussians 3000000] [--iters 100]
+    python examples/finetune_step.py [--n-gaussians 3000000] [--iters 100] [--fused-adam | --hip-adam]
 """
 import argparse
 import os
@@ -33,7 +33,10 @@ def main():
     ap.add_argument("--iters", type=int, default=60)
     ap.add_argument("--lambda-dssim", type=float, default=0.2)     # arguments/__init__.py
     ap.add_argument("--fused-adam", action="store_true", help="what `python -m lightgaussian_amd.run --fused-adam` switches on")
+    ap.add_argument("--hip-adam", action="store_true", help="what `python -m lightgaussian_amd.run --hip-adam` switches on: one lg_adam_step launch per step")
     args = ap.parse_args()
+    if args.fused_adam and args.hip_adam:
+        raise SystemExit("--fused-adam and --hip-adam exclude each other")
     dev = torch.device("cuda", 0)
     truth = syn.make_gaussians(args.n_gaussians).to(dev)
     cams = [syn.orbit_camera(k, args.views, args.width, args.height).to(dev) for k in range(args.views)]
@@ -50,9 +53,13 @@ def main():
     if args.fused_adam:
         from lightgaussian_amd import run as lg_run
         lg_run.fused_adam(True)
+    if args.hip_adam:
+        from lightgaussian_amd import run as lg_run
+        lg_run.hip_adam(True)
     opt = torch.optim.Adam([{"params": [g._xyz], "lr": 1.6e-6}, {"params": [g._features_dc], "lr": 2.5e-3},
                             {"params": [g._features_rest], "lr": 2.5e-3 / 20.0}, {"params": [g._opacity], "lr": 0.05},
                             {"params": [g._scaling], "lr": 0.005}, {"params": [g._rotation], "lr": 0.001}], lr=0.0, eps=1e-15)
+    which = f"{type(opt).__name__}{' fused=True' if opt.param_groups[0].get('fused') else ''}"
     first = last = None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -73,7 +80,7 @@ def main():
     dt = time.perf_counter() - t0
     n = min(args.views, args.iters)
     print(f"{args.iters} iterations, {args.n_gaussians} Gaussians, {args.width}x{args.height}: {dt / args.iters * 1e3:.2f} ms/iteration "
-          f"(render fwd+bwd + L1/SSIM + Adam{' fused' if args.fused_adam else ''}); mean loss first {n} iterations {first / n:.5f} -> last {n} {last / n:.5f}")
+          f"(render fwd+bwd + L1/SSIM + optimizer {which}); mean loss first {n} iterations {first / n:.5f} -> last {n} {last / n:.5f}")
     assert last < first, "the loss did not go down"
 
 

@@ -346,6 +346,37 @@ int lg_vq_colors_bwd(int32_t N, int32_t M, int32_t sh_degree, int32_t K, int64_t
                      const uint32_t* slot, const void* rows_f16, int32_t row_stride_bytes, const float* dL_drgb, const void* index,
                      float* dL_drows, float* dL_dmeans3D, void* scratch, uint32_t flags, void* stream);
 
+/* --- Adam / AdamW step ------------------------------------------------------------------------------
+ * The optimizer.step() of the reference's training_setup (scene/gaussian_model.py: torch.optim.AdamW(l, lr=0.0, eps=1e-15) over six
+ * one-tensor groups with an lr each) for a caller without torch: applies grad to param and to the two moments lg_compact_rows moves.
+ * Per element, float32, correctly rounded divide / sqrt, the sum closing each line one explicit fmaf, nothing else contracted, t = step:
+ *     g' = g + weight_decay * p  (L2 form, only for weight_decay != 0)     p = p * (1 - lr * weight_decay)  (LG_ADAM_DECOUPLED_WD)
+ *     exp_avg    = exp_avg + (1 - beta1) * (g' - exp_avg)
+ *     exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) * (g' * g')
+ *     p          = p - step_size * (exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps)),   step_size = lr / (1 - beta1^t)
+ * step_size, sqrt(1 - beta2^t), 1 - lr * weight_decay, 1 - beta1 and 1 - beta2 are evaluated in double and rounded once to float:
+ * torch's default (non-fused, non-capturable) Adam / AdamW.  No amsgrad, no maximize.  Non-finite gradients propagate.
+ * tensors: HOST array; the four device tensors of an entry are float32, contiguous, numel elements each and do not overlap.
+ * Entries with numel == 0 are skipped.  The table travels in the kernel arguments, LG_ADAM_MAX_TENSORS (8) tensors per launch:
+ * no device allocation, no host-to-device copy, no synchronisation, every launch on `stream`.  A workgroup owns one span of
+ * LG_ADAM_SPAN (4096) elements of one tensor; 16-byte aligned tensors go through 16-byte loads and stores.  28 bytes of traffic
+ * per element.  flags: LG_ADAM_DECOUPLED_WD, LG_FLAG_PROFILE (one "adam" entry per launch); LG_FLAG_DEBUG does not apply.
+ * LG_ERR_INVALID_ARGUMENT, before any device call: num_tensors < 0, a beta outside [0, 1), numel < 0, step < 1, a null or
+ * misaligned pointer with numel > 0. */
+typedef struct lg_adam_tensor {
+    float* param; const float* grad; float* exp_avg; float* exp_avg_sq;   /* device, float32, contiguous */
+    int64_t numel;
+    double lr, weight_decay;
+    int64_t step;                      /* the step being taken, >= 1 */
+} lg_adam_tensor;
+#define LG_ADAM_DECOUPLED_WD 1u          /* AdamW: p *= 1 - lr*wd; otherwise g += wd*p (Adam's L2 form) */
+#define LG_ADAM_MAX_TENSORS 8            /* tensors per launch */
+#ifndef LG_ADAM_SPAN
+#define LG_ADAM_SPAN 4096                /* elements per workgroup (a build-time choice of the library, by measurement) */
+#endif
+int lg_adam_step(int32_t num_tensors, const lg_adam_tensor* tensors /* host */, double beta1, double beta2, double eps,
+                 uint32_t flags, void* stream);
+
 /* out[j] = (((rows[0][j] + rows[1][j]) + rows[2][j]) + ...) over V rows of n floats (row pitch row_stride floats): the
  * sequential in-place float accumulation of per-view scores in prune.py:144-155, in view order, as one launch. */
 int lg_ordered_sum(int32_t V, int64_t n, const float* rows, int64_t row_stride, float* out, void* stream);

@@ -24,6 +24,9 @@ FLAG_NARROW_KEY, FLAG_SORT_ALL_BITS, FLAG_K1_LDS = 64, 128, 256
 FLAG_LONG_SERIAL, FLAG_LONG_PARALLEL = 512, 1024
 FLAG_SAVE_SH_JACOBIAN = 2048
 FLAG_COUNT_WIDE_BAND = 8192
+ADAM_DECOUPLED_WD = 1       # lg_adam_step flags: LG_ADAM_DECOUPLED_WD (AdamW), FLAG_PROFILE
+ADAM_MAX_TENSORS = 8        # LG_ADAM_MAX_TENSORS: tensors per launch of lg_adam_step
+ADAM_SPAN = 4096            # LG_ADAM_SPAN: elements per workgroup of lg_adam_step
 ABI_VERSION = 7     # include/lightgaussian.h LG_ABI_VERSION this binding was written against (load() refuses another)
 
 EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scratch_bytes", "lg_forward",
@@ -36,7 +39,7 @@ EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scr
            "lg_debug_sort_orphan", "lg_debug_last_contributor", "lg_debug_tile_lists", "lg_geom_visible_offset",
            "lg_sh_grad_from_rgb", "lg_debug_view_meta", "lg_vq_ema_scratch_bytes", "lg_vq_ema_step", "lg_vq_colors",
            "lg_vq_code_index_bytes", "lg_vq_code_index_scratch_bytes", "lg_vq_code_index", "lg_vq_colors_bwd_scratch_bytes",
-           "lg_vq_colors_bwd"]
+           "lg_vq_colors_bwd", "lg_adam_step"]
 
 
 class lg_view(C.Structure):
@@ -58,6 +61,11 @@ class lg_kernel_time(C.Structure):
 
 class lg_stats(C.Structure):
     _fields_ = [("num_rendered", C.c_int64), ("num_visible", C.c_int64)]
+
+
+class lg_adam_tensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("numel", C.c_int64), ("lr", C.c_double), ("weight_decay", C.c_double), ("step", C.c_int64)]
 
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
@@ -146,6 +154,8 @@ def load():
     lib.lg_vq_colors_bwd.restype = C.c_int
     lib.lg_vq_colors_bwd.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp,
                                      C.c_uint32, vp]
+    lib.lg_adam_step.restype = C.c_int
+    lib.lg_adam_step.argtypes = [C.c_int32, P(lg_adam_tensor), C.c_double, C.c_double, C.c_double, C.c_uint32, vp]
     lib.lg_debug_sort_temp_bytes.restype = C.c_size_t; lib.lg_debug_sort_temp_bytes.argtypes = [C.c_int64]
     lib.lg_debug_sort_keys.restype = C.c_int
     lib.lg_debug_sort_keys.argtypes = [C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp]

@@ -1,0 +1,116 @@
+// lg_adam.h -- lg_adam_step: one Adam / AdamW step over up to LG_ADAM_MAX_TENSORS tensors per launch.
+// Replaces the optimizer.step() of the reference's training_setup (scene/gaussian_model.py: torch.optim.AdamW(l, lr=0.0, eps=1e-15),
+// six one-tensor groups with an lr each): torch's default step is ~8 multi-tensor kernels over parameters and moments, this is ONE
+// launch that reads param, grad, exp_avg, exp_avg_sq once (16 B per element) and writes param and the moments once (12 B).
+//
+// Layout.  The per-tensor table travels BY VALUE in the kernel arguments (no device allocation, no copy, no synchronisation).
+// Every workgroup owns ONE contiguous span of LG_ADAM_SPAN elements of ONE tensor: first_wg[t] is the first workgroup of tensor t,
+// the search over the table is wave-uniform, so pointers and hyper-parameters stay in SGPRs.  A full span of a tensor whose four
+// pointers are 16-byte aligned goes through dwordx4 loads / stores, all of them issued before the arithmetic; a tensor with a
+// misaligned pointer and the last, partial span of any tensor go one dword per lane.  param, exp_avg and exp_avg_sq of an
+// element are read and written by the same lane; grad is only read.  No LDS, no atomics, no scratch.
+//
+// Arithmetic per element, float32, no implicit contraction, correctly rounded divide and square root (the library's flags):
+//     g' = g + wd * p   (L2 form, only when wd != 0)        p = p * (1 - lr wd)   (decoupled form)
+//     m  = m + (1 - beta1) * (g' - m)                       v = beta2 * v + (1 - beta2) * (g' * g')
+//     p  = p - step_size * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps))
+// The sum that closes each of the four lines is ONE explicit fmaf (a single rounding, written out -- not left to the compiler):
+// fmaf(wd, p, g), fmaf(1 - beta1, g' - m, m) as ATen's lerp, fmaf(1 - beta2, round(g' g'), round(beta2 v)) as ATen's addcmul a + alpha (b c), fmaf(-step_size, q, p).
+// step_size = lr / (1 - beta1^t), sqrt(1 - beta2^t), 1 - lr wd, 1 - beta1, 1 - beta2 are evaluated in double on the host and rounded
+// once to float -- what torch's default (non-capturable) step does.  Non-finite gradients propagate.
+// Part of liblightgaussian_hip.so (single translation unit: lg_api.hip includes the lg_*.h kernel headers).
+#pragma once
+
+#include "lg_host.h"
+
+// LG_ADAM_MAX_TENSORS (8) and LG_ADAM_SPAN (elements per workgroup: 256 lanes x LG_ADAM_SPAN / 1024 dwordx4 per stream; 4096 by
+// measurement on the MI355X, EXPERIMENTS "Adam step"; -DLG_ADAM_SPAN=... for an A/B build) come from include/lightgaussian.h.
+// 1: grad (read once, never written) is loaded nontemporally.  Measured on the MI355X (EXPERIMENTS, "Adam step").
+#ifndef LG_ADAM_NT_GRAD
+#define LG_ADAM_NT_GRAD 1
+#endif
+#define LG_ADAM_THREADS 256
+#define LG_ADAM_VEC (LG_ADAM_SPAN / (LG_ADAM_THREADS * 4))
+static_assert(LG_ADAM_SPAN % (LG_ADAM_THREADS * 4) == 0 && LG_ADAM_VEC >= 1, "a span is a whole number of dwordx4 per lane");
+
+typedef float lg_adam_f4 __attribute__((ext_vector_type(4)));
+
+struct LgAdamTable {
+    float* param[LG_ADAM_MAX_TENSORS];
+    const float* grad[LG_ADAM_MAX_TENSORS];
+    float* exp_avg[LG_ADAM_MAX_TENSORS];
+    float* exp_avg_sq[LG_ADAM_MAX_TENSORS];
+    int64_t numel[LG_ADAM_MAX_TENSORS];
+    uint32_t first_wg[LG_ADAM_MAX_TENSORS];     // first workgroup of tensor t; 0xFFFFFFFF for the unused entries
+    float step_size[LG_ADAM_MAX_TENSORS];       // lr / (1 - beta1^step)
+    float bc2_sqrt[LG_ADAM_MAX_TENSORS];        // sqrt(1 - beta2^step)
+    float decay[LG_ADAM_MAX_TENSORS];           // decoupled: 1 - lr wd;  L2 form: wd
+    uint32_t vec_mask;                          // bit t: all four pointers of tensor t are 16-byte aligned
+    float one_minus_beta1, beta2, one_minus_beta2, eps;
+};
+
+template <bool DECOUPLED>
+__device__ __forceinline__ void lg_adam_element(float& p, float g, float& m, float& v, float decay, float step_size, float bc2_sqrt,
+                                                float om_b1, float b2, float om_b2, float eps)
+{
+    if (DECOUPLED) p = p * decay;
+    else if (decay != 0.0f) g = fmaf(decay, p, g);      // (uniform: torch skips the term for wd == 0, so an infinite p gives no 0 * inf)
+    m = fmaf(om_b1, g - m, m);
+    v = fmaf(om_b2, g * g, b2 * v);
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    p = fmaf(-step_size, m / denom, p);
+}
+
+template <bool DECOUPLED>
+__global__ void __launch_bounds__(LG_ADAM_THREADS) lg_adam_kernel(const LgAdamTable a)
+{
+    const uint32_t wg = blockIdx.x;
+    uint32_t t = 0;
+#pragma unroll
+    for (int k = 1; k < LG_ADAM_MAX_TENSORS; k++) t += wg >= a.first_wg[k] ? 1u : 0u;   // first_wg ascends: t = the last entry <= wg
+    float* __restrict__ const P = a.param[t];
+    const float* __restrict__ const G = a.grad[t];
+    float* __restrict__ const M = a.exp_avg[t];
+    float* __restrict__ const V = a.exp_avg_sq[t];
+    const float decay = a.decay[t], step_size = a.step_size[t], bc2_sqrt = a.bc2_sqrt[t];
+    const float om_b1 = a.one_minus_beta1, b2 = a.beta2, om_b2 = a.one_minus_beta2, eps = a.eps;
+    const int64_t base = (int64_t)(wg - a.first_wg[t]) * LG_ADAM_SPAN;
+    const int64_t left = a.numel[t] - base;             // > 0 by the host's workgroup count
+    if (((a.vec_mask >> t) & 1u) && left >= LG_ADAM_SPAN) {
+        lg_adam_f4 p[LG_ADAM_VEC], g[LG_ADAM_VEC], m[LG_ADAM_VEC], v[LG_ADAM_VEC];
+#pragma unroll
+        for (int u = 0; u < LG_ADAM_VEC; u++) {
+            const int64_t i = base + (int64_t)(u * LG_ADAM_THREADS + (int)threadIdx.x) * 4;
+#if LG_ADAM_NT_GRAD
+            g[u] = __builtin_nontemporal_load((const lg_adam_f4*)(G + i));
+#else
+            g[u] = *(const lg_adam_f4*)(G + i);
+#endif
+            p[u] = *(const lg_adam_f4*)(P + i);
+            m[u] = *(const lg_adam_f4*)(M + i);
+            v[u] = *(const lg_adam_f4*)(V + i);
+        }
+        __builtin_amdgcn_sched_barrier(0);              // every load of the span is in flight before the first dependent instruction
+#pragma unroll
+        for (int u = 0; u < LG_ADAM_VEC; u++) {
+            const int64_t i = base + (int64_t)(u * LG_ADAM_THREADS + (int)threadIdx.x) * 4;
+            float pe[4] = { p[u].x, p[u].y, p[u].z, p[u].w }, me[4] = { m[u].x, m[u].y, m[u].z, m[u].w };
+            float ve[4] = { v[u].x, v[u].y, v[u].z, v[u].w };
+            const float ge[4] = { g[u].x, g[u].y, g[u].z, g[u].w };
+#pragma unroll
+            for (int c = 0; c < 4; c++) lg_adam_element<DECOUPLED>(pe[c], ge[c], me[c], ve[c], decay, step_size, bc2_sqrt, om_b1, b2, om_b2, eps);
+            *(lg_adam_f4*)(P + i) = lg_adam_f4{ pe[0], pe[1], pe[2], pe[3] };
+            *(lg_adam_f4*)(M + i) = lg_adam_f4{ me[0], me[1], me[2], me[3] };
+            *(lg_adam_f4*)(V + i) = lg_adam_f4{ ve[0], ve[1], ve[2], ve[3] };
+        }
+    } else {
+        const int n = (int)(left < LG_ADAM_SPAN ? left : LG_ADAM_SPAN);
+        for (int k = (int)threadIdx.x; k < n; k += LG_ADAM_THREADS) {
+            const int64_t i = base + k;
+            float p = P[i], m = M[i], v = V[i];
+            const float g = G[i];
+            lg_adam_element<DECOUPLED>(p, g, m, v, decay, step_size, bc2_sqrt, om_b1, b2, om_b2, eps);
+            P[i] = p; M[i] = m; V[i] = v;
+        }
+    }
+}

@@ -16,6 +16,7 @@
 //   lg_vq_color.h    lg_vq_colors: per-Gaussian colours of a VecTree-compressed model (fp16 row table + slot) through the same lg_sh_to_rgb as K1
 //   lg_vq_color_bwd.h lg_vq_code_index / lg_vq_colors_bwd: its backward -- per-row gradients of the row table (ordered segmented sum over a
 //                    per-model inverted index for the codebook rows) and the colour part of dL/dxyz
+//   lg_adam.h        lg_adam_step: one Adam / AdamW step over all parameter tensors of the model in one launch (table by value, dwordx4)
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound)
 //
 // Pipeline of one view:
@@ -40,6 +41,7 @@
 #include "lg_vq_train.h"
 #include "lg_vq_color.h"
 #include "lg_vq_color_bwd.h"
+#include "lg_adam.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -923,6 +925,69 @@ extern "C" int lg_vq_colors_bwd(int32_t N, int32_t M, int32_t sh_degree, int32_t
                                                                                                  dL_drows);
         KCHECK("lg_vq_colors_bwd_combine");
     }
+    return LG_OK;
+}
+
+// ---- Adam / AdamW step (lg_adam.h) ----
+extern "C" int lg_adam_step(int32_t num_tensors, const lg_adam_tensor* tensors, double beta1, double beta2, double eps, uint32_t flags,
+                            void* stream_p)
+{
+    // everything is checked before the first HIP call: a refused step has touched nothing
+    if (num_tensors < 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: num_tensors < 0");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: betas must lie in [0, 1)");
+    if (num_tensors > 0 && !tensors) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: missing tensor table");
+    for (int t = 0; t < num_tensors; t++) {
+        const lg_adam_tensor& x = tensors[t];
+        if (x.numel < 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: numel < 0");
+        if (x.step < 1) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: step < 1 (the step being taken counts from 1)");
+        if (x.numel == 0) continue;                     // skipped: its pointers are not looked at
+        if (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq)
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: null param / grad / exp_avg / exp_avg_sq with numel > 0");
+        if ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 3) != 0)
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: float32 tensors must be 4-byte aligned");
+        if ((x.numel + LG_ADAM_SPAN - 1) / LG_ADAM_SPAN > 0x7FFFFFFFll)
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: tensor beyond 2^31 - 1 spans");
+    }
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = false, prof = flags & LG_FLAG_PROFILE, decoupled = flags & LG_ADAM_DECOUPLED_WD;
+    LgAdamTable a;
+    int filled = 0;
+    uint32_t wgs = 0;
+    auto reset = [&]() {
+        memset(&a, 0, sizeof(a));
+        for (int k = 0; k < LG_ADAM_MAX_TENSORS; k++) a.first_wg[k] = 0xFFFFFFFFu;
+        a.one_minus_beta1 = (float)(1.0 - beta1); a.beta2 = (float)beta2; a.one_minus_beta2 = (float)(1.0 - beta2); a.eps = (float)eps;
+        filled = 0; wgs = 0;
+    };
+    auto launch = [&]() -> int {
+        ProfScope ps(prof, "adam", stream);
+        if (decoupled) lg_adam_kernel<true><<<wgs, LG_ADAM_THREADS, 0, stream>>>(a);
+        else lg_adam_kernel<false><<<wgs, LG_ADAM_THREADS, 0, stream>>>(a);
+        KCHECK("lg_adam_kernel");
+        return LG_OK;
+    };
+    reset();
+    for (int t = 0; t < num_tensors; t++) {
+        const lg_adam_tensor& x = tensors[t];
+        if (x.numel == 0) continue;
+        const uint32_t need = (uint32_t)((x.numel + LG_ADAM_SPAN - 1) / LG_ADAM_SPAN);
+        if (filled == LG_ADAM_MAX_TENSORS || (filled > 0 && wgs + need > 0x7FFFFFFFu)) {
+            const int rc = launch();
+            if (rc != LG_OK) return rc;
+            reset();
+        }
+        const int k = filled++;
+        a.param[k] = x.param; a.grad[k] = x.grad; a.exp_avg[k] = x.exp_avg; a.exp_avg_sq[k] = x.exp_avg_sq;
+        a.numel[k] = x.numel;
+        a.first_wg[k] = wgs;
+        // torch's default step: the three scalars in double, each rounded once to float
+        a.step_size[k] = (float)(x.lr / (1.0 - pow(beta1, (double)x.step)));
+        a.bc2_sqrt[k] = (float)sqrt(1.0 - pow(beta2, (double)x.step));
+        a.decay[k] = decoupled ? (float)(1.0 - x.lr * x.weight_decay) : (float)x.weight_decay;
+        if ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 15) == 0) a.vec_mask |= 1u << k;
+        wgs += need;
+    }
+    if (filled > 0) return launch();
     return LG_OK;
 }
 

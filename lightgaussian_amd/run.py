@@ -14,6 +14,9 @@
          all four are deterministic and bit-pinned)
     python -m lightgaussian_amd.run --fused-adam /path/to/prune_finetune.py ...
         (opt-in, outside the replaced path: torch.optim.Adam as the trainers construct it, but with fused=True -- fused_adam() below)
+    python -m lightgaussian_amd.run --hip-adam /path/to/prune_finetune.py ...
+        (opt-in, excludes --fused-adam: the trainers' torch.optim.Adam / AdamW instance becomes the subclass of its own class whose
+         step() is one lg_adam_step launch over all parameter tensors -- hip_adam() below, lightgaussian_amd/optim.py)
     python -m lightgaussian_amd.run --lazy-loss /path/to/prune_finetune.py ...
         (opt-in: l1_loss() / ssim() return lazy scalars, loss_utils.LazyLoss -- the trainers' `(1 - lambda) * Ll1 + lambda * (1 - ssim)`
          line launches nothing, backward() feeds the two coefficients to the fused loss node, loss.item() reads a pinned copy;
@@ -397,6 +400,36 @@ def fused_adam(enable=True):
         torch.optim.Adam.__init__ = _ADAM_INIT.pop("orig")
 
 
+_HIP_ADAM_INIT = {}
+
+
+def hip_adam(enable=True):
+    """run.py --hip-adam (opt-in, like fused_adam() and instead of it): every torch.optim.Adam -- AdamW included, which subclasses it --
+    created while this is active, over CUDA float parameters and without an explicit fused / foreach argument, is turned into the
+    HIP-stepping subclass of its own class (lightgaussian_amd.optim.convert): still an instance of the class the trainer asked for,
+    same param_groups, same state layout as torch's default step (step on the CPU, exp_avg / exp_avg_sq by key -- the prune / densify
+    surgery and the checkpoints work unchanged), but step() is ONE lg_adam_step launch over all parameter tensors.  Optimizers over
+    CPU tensors, or with an explicit fused / foreach, stay plain torch.  hip_adam(False) puts torch's constructor back."""
+    import torch
+    if enable and "orig" not in _HIP_ADAM_INIT:
+        orig = torch.optim.Adam.__init__
+        _HIP_ADAM_INIT["orig"] = orig
+
+        def __init__(self, params, *args, **kw):
+            params = list(params)
+            orig(self, params, *args, **kw)
+            # (AdamW's constructor hands fused=None / foreach=None down explicitly: None is "not chosen")
+            if kw.get("fused") is None and kw.get("foreach") is None:
+                flat = [p for g in self.param_groups for p in g["params"]]
+                if flat and all(torch.is_tensor(p) and p.is_cuda and p.is_floating_point() for p in flat):
+                    from . import optim
+                    optim.convert(self)
+
+        torch.optim.Adam.__init__ = __init__
+    elif not enable and "orig" in _HIP_ADAM_INIT:
+        torch.optim.Adam.__init__ = _HIP_ADAM_INIT.pop("orig")
+
+
 _EVENT_ELAPSED = {}
 
 
@@ -452,7 +485,7 @@ def _redirect_model_path(argv, rank):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    distributed = no_patch = verbose = adam = lazy = no_timing = False
+    distributed = no_patch = verbose = adam = hip = lazy = no_timing = False
     backend = "nccl"
     dp_overlap = False
     weight_policy = None
@@ -468,6 +501,8 @@ def main(argv=None):
             dp_overlap = True
         elif flag == "--fused-adam":
             adam = True
+        elif flag == "--hip-adam":
+            hip = True
         elif flag == "--lazy-loss":
             lazy = True
         elif flag == "--no-iter-timing":
@@ -479,7 +514,9 @@ def main(argv=None):
         elif flag.startswith("--backend="):       # gloo: CPU tests of the launcher with a stand-in trainer (the rasterizer has no CPU path)
             backend = flag.split("=", 1)[1]
         else:
-            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --lazy-loss --no-iter-timing --weight-policy=NAME, then the script and ITS arguments)")
+            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --lazy-loss --no-iter-timing --weight-policy=NAME, then the script and ITS arguments)")
+    if adam and hip:
+        raise SystemExit("lightgaussian_amd.run: --fused-adam and --hip-adam exclude each other (one optimizer step per run)")
     if not argv:
         raise SystemExit(__doc__)
     script = os.path.abspath(argv[0])
@@ -524,6 +561,8 @@ def main(argv=None):
         rasterizer.set_option("weight_policy", rasterizer.weight_policy_id(weight_policy))     # process default of every count_render of the run
     if adam:
         fused_adam(True)
+    if hip:
+        hip_adam(True)
     if lazy:
         # l1_loss() / ssim() hand out lazy scalars (loss_utils.LazyLoss): the trainers' loss line costs no kernels and their
         # per-iteration loss.item() does not wait for the backward.  This (main) thread only; the trainers are single-threaded.
@@ -551,6 +590,8 @@ def main(argv=None):
             event_timing(None)
         if adam:
             fused_adam(False)
+        if hip:
+            hip_adam(False)
         if distributed:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized():
