@@ -377,6 +377,50 @@ typedef struct lg_adam_tensor {
 int lg_adam_step(int32_t num_tensors, const lg_adam_tensor* tensors /* host */, double beta1, double beta2, double eps,
                  uint32_t flags, void* stream);
 
+/* --- densification: view statistics and clone / split / prune ---------------------------------------
+ * GaussianModel.add_densification_stats and densify_and_prune (scene/gaussian_model.py:602-761, 784-788) for float32 device tensors.
+ * lg_densify_stats, one launch, no read-back: for every row i with update_filter[i] != 0
+ *     accum[i] += sqrt(fma(g[i][1], g[i][1], g[i][0]^2))   denom[i] += 1    max_radii2D[i] = max(max_radii2D[i], (float) radii[i])  (radii != NULL)
+ * viewspace_grad float32 [N,3], update_filter uint8 / bool [N], radii int32 [N] or NULL (then max_radii2D is not looked at).
+ * lg_densify_plan: with s = exp(scaling row), m = max s, sigma = sigmoid(opacity), g = accum / denom (NaN -> 0) per row
+ *     clone  = g >= thr_g && m <= thr_d          split = g >= thr_g && m > thr_d
+ *     pruned(sigma, mu) = sigma < min_opacity || (use_extent && mu > thr_w)
+ * writes the source map of the output rows, in this order: originals with !split that are not pruned(sigma, m); clones of those;
+ * first children, then second children, of the split rows that are not pruned(sigma, m / 1.6f) -- each group in source order.
+ * map: 2 N entries of two uint32 {source row, kind << 30 | k}, kind 0 original, 1 clone, 2 first child, 3 second child; k = rank of the
+ * parent among ALL split rows (its noise rows are k and n_s + k).  record: 8 int32 on the device {N_out, n_keep, n_clone, n_s,
+ * n_child, 0, 0, 0}.  The thresholds are floats: evaluate them in double and round once.  thr_g must be > 0, N < 2^30.
+ * scratch: lg_densify_scratch_bytes(N).
+ * lg_densify_rows, one launch (grid.y = tensor), writes N_out rows of up to LG_DENSIFY_MAX_TENSORS tensors from the map.  tensors is a
+ * HOST array; src has N rows and dst N_out rows of row_words 32-bit words (> 0), contiguous; src and dst do not overlap.  role:
+ *     LG_DENSIFY_COPY     every output row is its source row, bit for bit
+ *     LG_DENSIFY_MOMENT   originals copied, new rows zero
+ *     LG_DENSIFY_XYZ      children: R(q / |q|) (noise * exp(scaling)) + xyz, q = (r, x, y, z); row_words 3
+ *     LG_DENSIFY_SCALING  children: log(exp(scaling) / 1.6f); row_words 3
+ *     LG_DENSIFY_ZERO     every output row zero (src is not looked at)
+ * rotation [N,4], scaling [N,3]: the model's raw rows; noise float32 [noise_rows,3], noise_rows >= 2 n_s (unit normal).
+ * flags: LG_FLAG_PROFILE ("densify_stats", "densify_plan", "densify_rows").  LG_ERR_INVALID_ARGUMENT before any device call. */
+typedef struct lg_densify_tensor {
+    const void* src; void* dst;        /* device */
+    int32_t row_words;
+    int32_t role;
+} lg_densify_tensor;
+#define LG_DENSIFY_COPY 0
+#define LG_DENSIFY_MOMENT 1
+#define LG_DENSIFY_XYZ 2
+#define LG_DENSIFY_SCALING 3
+#define LG_DENSIFY_ZERO 4
+#define LG_DENSIFY_MAX_TENSORS 32
+size_t lg_densify_scratch_bytes(int32_t N);
+int lg_densify_stats(int32_t N, const float* viewspace_grad, const uint8_t* update_filter, const int32_t* radii, float* max_radii2D,
+                     float* accum, float* denom, uint32_t flags, void* stream);
+int lg_densify_plan(int32_t N, const float* scaling, const float* opacity, const float* accum, const float* denom, float thr_g,
+                    float thr_d, float thr_w, float min_opacity, int32_t use_extent, void* map, int32_t* record, void* scratch,
+                    uint32_t flags, void* stream);
+int lg_densify_rows(int32_t N, int64_t N_out, const void* map, const int32_t* record, int32_t num_tensors,
+                    const lg_densify_tensor* tensors /* host */, const float* rotation, const float* scaling, const float* noise,
+                    int64_t noise_rows, uint32_t flags, void* stream);
+
 /* out[j] = (((rows[0][j] + rows[1][j]) + rows[2][j]) + ...) over V rows of n floats (row pitch row_stride floats): the
  * sequential in-place float accumulation of per-view scores in prune.py:144-155, in view order, as one launch. */
 int lg_ordered_sum(int32_t V, int64_t n, const float* rows, int64_t row_stride, float* out, void* stream);

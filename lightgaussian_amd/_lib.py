@@ -27,6 +27,8 @@ FLAG_COUNT_WIDE_BAND = 8192
 ADAM_DECOUPLED_WD = 1       # lg_adam_step flags: LG_ADAM_DECOUPLED_WD (AdamW), FLAG_PROFILE
 ADAM_MAX_TENSORS = 8        # LG_ADAM_MAX_TENSORS: tensors per launch of lg_adam_step
 ADAM_SPAN = 4096            # LG_ADAM_SPAN: elements per workgroup of lg_adam_step
+DENSIFY_COPY, DENSIFY_MOMENT, DENSIFY_XYZ, DENSIFY_SCALING, DENSIFY_ZERO = 0, 1, 2, 3, 4     # lg_densify_tensor.role (LG_DENSIFY_*)
+DENSIFY_MAX_TENSORS = 32    # LG_DENSIFY_MAX_TENSORS: tensors per lg_densify_rows call
 ABI_VERSION = 7     # include/lightgaussian.h LG_ABI_VERSION this binding was written against (load() refuses another)
 
 EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scratch_bytes", "lg_forward",
@@ -39,7 +41,7 @@ EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scr
            "lg_debug_sort_orphan", "lg_debug_last_contributor", "lg_debug_tile_lists", "lg_geom_visible_offset",
            "lg_sh_grad_from_rgb", "lg_debug_view_meta", "lg_vq_ema_scratch_bytes", "lg_vq_ema_step", "lg_vq_colors",
            "lg_vq_code_index_bytes", "lg_vq_code_index_scratch_bytes", "lg_vq_code_index", "lg_vq_colors_bwd_scratch_bytes",
-           "lg_vq_colors_bwd", "lg_adam_step"]
+           "lg_vq_colors_bwd", "lg_adam_step", "lg_densify_scratch_bytes", "lg_densify_stats", "lg_densify_plan", "lg_densify_rows"]
 
 
 class lg_view(C.Structure):
@@ -66,6 +68,10 @@ class lg_stats(C.Structure):
 class lg_adam_tensor(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
                 ("numel", C.c_int64), ("lr", C.c_double), ("weight_decay", C.c_double), ("step", C.c_int64)]
+
+
+class lg_densify_tensor(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_words", C.c_int32), ("role", C.c_int32)]
 
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
@@ -156,6 +162,13 @@ def load():
                                      C.c_uint32, vp]
     lib.lg_adam_step.restype = C.c_int
     lib.lg_adam_step.argtypes = [C.c_int32, P(lg_adam_tensor), C.c_double, C.c_double, C.c_double, C.c_uint32, vp]
+    lib.lg_densify_scratch_bytes.restype = C.c_size_t; lib.lg_densify_scratch_bytes.argtypes = [C.c_int32]
+    lib.lg_densify_stats.restype = C.c_int
+    lib.lg_densify_stats.argtypes = [C.c_int32, vp, vp, vp, vp, vp, vp, C.c_uint32, vp]
+    lib.lg_densify_plan.restype = C.c_int
+    lib.lg_densify_plan.argtypes = [C.c_int32, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp, vp, C.c_uint32, vp]
+    lib.lg_densify_rows.restype = C.c_int
+    lib.lg_densify_rows.argtypes = [C.c_int32, C.c_int64, vp, vp, C.c_int32, P(lg_densify_tensor), vp, vp, vp, C.c_int64, C.c_uint32, vp]
     lib.lg_debug_sort_temp_bytes.restype = C.c_size_t; lib.lg_debug_sort_temp_bytes.argtypes = [C.c_int64]
     lib.lg_debug_sort_keys.restype = C.c_int
     lib.lg_debug_sort_keys.argtypes = [C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp]

@@ -17,6 +17,7 @@
 //   lg_vq_color_bwd.h lg_vq_code_index / lg_vq_colors_bwd: its backward -- per-row gradients of the row table (ordered segmented sum over a
 //                    per-model inverted index for the codebook rows) and the colour part of dL/dxyz
 //   lg_adam.h        lg_adam_step: one Adam / AdamW step over all parameter tensors of the model in one launch (table by value, dwordx4)
+//   lg_densify.h     lg_densify_stats / lg_densify_plan / lg_densify_rows: view statistics and clone / split / prune of densify_and_prune
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound)
 //
 // Pipeline of one view:
@@ -42,6 +43,7 @@
 #include "lg_vq_color.h"
 #include "lg_vq_color_bwd.h"
 #include "lg_adam.h"
+#include "lg_densify.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -988,6 +990,105 @@ extern "C" int lg_adam_step(int32_t num_tensors, const lg_adam_tensor* tensors, 
         wgs += need;
     }
     if (filled > 0) return launch();
+    return LG_OK;
+}
+
+// ---- densification (lg_densify.h) ----
+struct DensifyScratch { uint8_t* flags; uint4* blk_sum; uint4* blk_off; size_t total; };
+static DensifyScratch carve_densify(void* base, int32_t N)
+{
+    DensifyScratch d; size_t off = 0; char* p = (char*)base;
+    auto take = [&](size_t bytes) { void* r = p ? p + off : nullptr; off += align_up(bytes); return r; };
+    const size_t n = (size_t)(N > 0 ? N : 1), nb = (n + LG_DENSIFY_ROWS - 1) / LG_DENSIFY_ROWS;
+    d.flags = (uint8_t*)take(n);
+    d.blk_sum = (uint4*)take(nb * 16);
+    d.blk_off = (uint4*)take(nb * 16);
+    d.total = off;
+    return d;
+}
+extern "C" size_t lg_densify_scratch_bytes(int32_t N) { return carve_densify(nullptr, N).total; }
+
+#define LG_DENSIFY_MAX_ROWS (1 << 30)
+extern "C" int lg_densify_stats(int32_t N, const float* viewspace_grad, const uint8_t* update_filter, const int32_t* radii,
+                                float* max_radii2D, float* accum, float* denom, uint32_t flags, void* stream_p)
+{
+    if (N < 0 || N >= LG_DENSIFY_MAX_ROWS) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_stats: N outside [0, 2^30)");
+    if (N == 0) return LG_OK;
+    if (!viewspace_grad || !update_filter || !accum || !denom) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_stats: null viewspace_grad / update_filter / accum / denom");
+    if (radii && !max_radii2D) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_stats: radii without max_radii2D");
+    if ((((uintptr_t)viewspace_grad | (uintptr_t)radii | (uintptr_t)max_radii2D | (uintptr_t)accum | (uintptr_t)denom) & 3) != 0)
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_stats: 32-bit tensors must be 4-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    ProfScope ps(prof, "densify_stats", stream);
+    lg_densify_stats_kernel<<<(unsigned)((N + 255) / 256), 256, 0, stream>>>(N, viewspace_grad, update_filter, radii, max_radii2D, accum, denom);
+    KCHECK("lg_densify_stats_kernel");
+    return LG_OK;
+}
+
+extern "C" int lg_densify_plan(int32_t N, const float* scaling, const float* opacity, const float* accum, const float* denom, float thr_g,
+                               float thr_d, float thr_w, float min_opacity, int32_t use_extent, void* map, int32_t* record, void* scratch,
+                               uint32_t flags, void* stream_p)
+{
+    if (N < 0 || N >= LG_DENSIFY_MAX_ROWS) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_plan: N outside [0, 2^30)");
+    if (!(thr_g > 0.0f)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_plan: thr_g must be > 0 (clones are never split only then)");
+    if (thr_d != thr_d || thr_w != thr_w || min_opacity != min_opacity) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_plan: a NaN threshold");
+    if (!record) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_plan: null record");
+    if (N > 0 && (!scaling || !opacity || !accum || !denom || !map || !scratch))
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_plan: null scaling / opacity / accum / denom / map / scratch");
+    if ((((uintptr_t)scaling | (uintptr_t)opacity | (uintptr_t)accum | (uintptr_t)denom | (uintptr_t)record) & 3) != 0 || ((uintptr_t)map & 7) != 0 ||
+        ((uintptr_t)scratch & 15) != 0)
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_plan: misaligned tensor (float32: 4 bytes, map: 8, scratch: 16)");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    ProfScope ps(prof, "densify_plan", stream);
+    if (N == 0) { HIP_TRY(lg_zero_async(record, 32, stream)); return LG_OK; }
+    const DensifyScratch d = carve_densify(scratch, N);
+    const int nb = (N + LG_DENSIFY_ROWS - 1) / LG_DENSIFY_ROWS;
+    const LgDensifyThresholds th = { thr_g, thr_d, thr_w, min_opacity, use_extent ? 1 : 0 };
+    lg_densify_classify<<<nb, 256, 0, stream>>>(N, scaling, opacity, accum, denom, th, d.flags, d.blk_sum);
+    KCHECK("lg_densify_classify");
+    lg_densify_scan<<<1, 1024, 0, stream>>>(nb, d.blk_sum, d.blk_off, record);
+    KCHECK("lg_densify_scan");
+    lg_densify_map<<<nb, 256, 0, stream>>>(N, d.flags, d.blk_off, record, (uint2*)map);
+    KCHECK("lg_densify_map");
+    return LG_OK;
+}
+
+extern "C" int lg_densify_rows(int32_t N, int64_t N_out, const void* map, const int32_t* record, int32_t num_tensors,
+                               const lg_densify_tensor* tensors, const float* rotation, const float* scaling, const float* noise,
+                               int64_t noise_rows, uint32_t flags, void* stream_p)
+{
+    if (N < 0 || N >= LG_DENSIFY_MAX_ROWS) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: N outside [0, 2^30)");
+    if (N_out < 0 || N_out > 2 * (int64_t)N) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: N_out outside [0, 2 N]");
+    if (num_tensors < 0 || num_tensors > LG_DENSIFY_MAX_TENSORS) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: num_tensors outside [0, 32]");
+    if (noise_rows < 0 || (noise_rows > 0 && !noise)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: noise_rows < 0 or null noise");
+    if (num_tensors > 0 && !tensors) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: missing tensor table");
+    if (N_out == 0 || num_tensors == 0) return LG_OK;
+    if (!map || !record || ((uintptr_t)map & 7) != 0 || ((uintptr_t)record & 3) != 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: null or misaligned map / record");
+    LgDensifyArgs a;
+    memset(&a, 0, sizeof(a));
+    size_t widest = 1;
+    for (int t = 0; t < num_tensors; t++) {
+        const lg_densify_tensor& x = tensors[t];
+        if (x.role < LG_DENSIFY_COPY || x.role > LG_DENSIFY_ZERO) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: unknown role");
+        if (x.row_words <= 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: row_words must be > 0 (leave empty tensors out)");
+        if (!x.dst || (x.role != LG_DENSIFY_ZERO && !x.src)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: null src / dst");
+        if ((((uintptr_t)x.src | (uintptr_t)x.dst) & 3) != 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: tensors must be 4-byte aligned");
+        if ((x.role == LG_DENSIFY_XYZ || x.role == LG_DENSIFY_SCALING) && x.row_words != 3)
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: the xyz and scaling roles need row_words == 3");
+        if (x.role == LG_DENSIFY_XYZ && (!rotation || !scaling || (((uintptr_t)rotation | (uintptr_t)scaling | (uintptr_t)noise) & 3) != 0))
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_rows: the xyz role needs rotation and scaling (4-byte aligned, like noise)");
+        a.src[t] = (const uint32_t*)x.src; a.dst[t] = (uint32_t*)x.dst; a.words[t] = (uint32_t)x.row_words; a.role[t] = (uint32_t)x.role;
+        widest = std::max<size_t>(widest, (size_t)x.row_words);
+    }
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    ProfScope ps(prof, "densify_rows", stream);
+    const size_t blocks = std::min<size_t>(((size_t)N_out * widest + 1023) / 1024, 8192);
+    lg_densify_move<<<dim3((unsigned)std::max<size_t>(blocks, 1), (unsigned)num_tensors), 256, 0, stream>>>(N_out, (const uint2*)map, record, a, rotation,
+                                                                                                      scaling, noise, noise_rows);
+    KCHECK("lg_densify_move");
     return LG_OK;
 }
 

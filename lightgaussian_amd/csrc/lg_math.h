@@ -608,3 +608,26 @@ LG_HD void lg_backward_sh_jac(int deg, const float J[9], float px, float py, flo
     dmean[1] += (-ox * oy * ddx + (sum2 - oy * oy) * ddy - oz * oy * ddz) * invsum32;
     dmean[2] += (-ox * oz * ddx - oy * oz * ddy + (sum2 - oz * oz) * ddz) * invsum32;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Densification (lg_densify.h): the two formulas that make a split child from its parent's RAW rows, as
+// densify_and_split writes them (scene/gaussian_model.py:678-687, build_rotation utils/general_utils.py:84-107).
+//   s = exp(raw scaling)      the caller evaluates it (expf in the kernels, as K1 under LG_FLAG_RAW_PARAMS)
+//   xyz_child     = R(q / |q|) (noise * s) + xyz        noise: one unit-normal row per child; q in (r, x, y, z) order
+//   scaling_child = log(s / 1.6f)                       1.6f = float(0.8 * 2)
+// The norm is summed left to right and q divided by it (build_rotation's own statements); every product and sum below is
+// rounded on its own (no contraction).
+#define LG_DENSIFY_SHRINK 1.6f
+LG_HD void lg_densify_child_xyz(const float q_raw[4], const float s[3], const float noise[3], const float xyz[3], float out[3])
+{
+    const float n = sqrtf(q_raw[0] * q_raw[0] + q_raw[1] * q_raw[1] + q_raw[2] * q_raw[2] + q_raw[3] * q_raw[3]);
+    const float r = q_raw[0] / n, x = q_raw[1] / n, y = q_raw[2] / n, z = q_raw[3] / n;
+    const float v0 = noise[0] * s[0], v1 = noise[1] * s[1], v2 = noise[2] * s[2];
+    const float R00 = 1.0f - 2.0f * (y * y + z * z), R01 = 2.0f * (x * y - r * z), R02 = 2.0f * (x * z + r * y);
+    const float R10 = 2.0f * (x * y + r * z), R11 = 1.0f - 2.0f * (x * x + z * z), R12 = 2.0f * (y * z - r * x);
+    const float R20 = 2.0f * (x * z - r * y), R21 = 2.0f * (y * z + r * x), R22 = 1.0f - 2.0f * (x * x + y * y);
+    out[0] = ((R00 * v0 + R01 * v1) + R02 * v2) + xyz[0];
+    out[1] = ((R10 * v0 + R11 * v1) + R12 * v2) + xyz[1];
+    out[2] = ((R20 * v0 + R21 * v1) + R22 * v2) + xyz[2];
+}
+LG_HD float lg_densify_child_scaling(float s) { return logf(s / LG_DENSIFY_SHRINK); }

@@ -17,6 +17,9 @@
     python -m lightgaussian_amd.run --hip-adam /path/to/prune_finetune.py ...
         (opt-in, excludes --fused-adam: the trainers' torch.optim.Adam / AdamW instance becomes the subclass of its own class whose
          step() is one lg_adam_step launch over all parameter tensors -- hip_adam() below, lightgaussian_amd/optim.py)
+    python -m lightgaussian_amd.run --hip-densify /path/to/train_densify_prune.py ...
+        (opt-in: GaussianModel.add_densification_stats is one lg_densify_stats launch without a host sync, GaussianModel.densify_and_prune
+         one plan + one row-writing launch with a single 32-byte read-back -- hip_densify() below, lightgaussian_amd/densify.py)
     python -m lightgaussian_amd.run --lazy-loss /path/to/prune_finetune.py ...
         (opt-in: l1_loss() / ssim() return lazy scalars, loss_utils.LazyLoss -- the trainers' `(1 - lambda) * Ll1 + lambda * (1 - ssim)`
          line launches nothing, backward() feeds the two coefficients to the fused loss node, loss.item() reads a pinned copy;
@@ -430,6 +433,31 @@ def hip_adam(enable=True):
         torch.optim.Adam.__init__ = _HIP_ADAM_INIT.pop("orig")
 
 
+def _add_densification_stats(self, viewspace_point_tensor, update_filter):
+    """GaussianModel.add_densification_stats(viewspace_point_tensor, update_filter), scene/gaussian_model.py:784-788."""
+    from . import densify
+    densify.accumulate_stats(self, viewspace_point_tensor, update_filter)
+
+
+def _densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
+    """GaussianModel.densify_and_prune(max_grad, min_opacity, extent, max_screen_size), scene/gaussian_model.py:745-761."""
+    from . import densify
+    densify.densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size)
+
+
+def hip_densify():
+    """run.py --hip-densify (opt-in, like hip_adam()): rebinds GaussianModel.add_densification_stats and GaussianModel.densify_and_prune
+    of the reference's scene.gaussian_model to lightgaussian_amd.densify (same positional parameters).  Apply it BEFORE
+    patch_reference(data_parallel=True): the data-parallel wrapper then wraps this densify_and_prune (and keeps its own, all-reducing
+    add_densification_stats).  unpatch_reference() restores both methods.  Returns the report entries."""
+    gm = _module("scene.gaussian_model")
+    if gm is None or not hasattr(gm, "GaussianModel"):
+        return {k: v for k, v in _REPORT.items() if k == "scene.gaussian_model"}
+    _set(gm.GaussianModel, "add_densification_stats", _add_densification_stats, "scene.gaussian_model.GaussianModel.add_densification_stats")
+    _set(gm.GaussianModel, "densify_and_prune", _densify_and_prune, "scene.gaussian_model.GaussianModel.densify_and_prune")
+    return {k: v for k, v in _REPORT.items() if k.endswith(("add_densification_stats", "densify_and_prune"))}
+
+
 _EVENT_ELAPSED = {}
 
 
@@ -485,7 +513,7 @@ def _redirect_model_path(argv, rank):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    distributed = no_patch = verbose = adam = hip = lazy = no_timing = False
+    distributed = no_patch = verbose = adam = hip = lazy = no_timing = densify = False
     backend = "nccl"
     dp_overlap = False
     weight_policy = None
@@ -503,6 +531,8 @@ def main(argv=None):
             adam = True
         elif flag == "--hip-adam":
             hip = True
+        elif flag == "--hip-densify":
+            densify = True
         elif flag == "--lazy-loss":
             lazy = True
         elif flag == "--no-iter-timing":
@@ -514,7 +544,7 @@ def main(argv=None):
         elif flag.startswith("--backend="):       # gloo: CPU tests of the launcher with a stand-in trainer (the rasterizer has no CPU path)
             backend = flag.split("=", 1)[1]
         else:
-            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --lazy-loss --no-iter-timing --weight-policy=NAME, then the script and ITS arguments)")
+            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --hip-densify --lazy-loss --no-iter-timing --weight-policy=NAME, then the script and ITS arguments)")
     if adam and hip:
         raise SystemExit("lightgaussian_amd.run: --fused-adam and --hip-adam exclude each other (one optimizer step per run)")
     if not argv:
@@ -569,6 +599,8 @@ def main(argv=None):
         from . import loss_utils as _lu
         _lu.set_lazy(True)
         event_timing("skip" if no_timing else "wait")
+    if densify:
+        hip_densify()           # before patch_reference: dp.install wraps the densify_and_prune it finds
     if not no_patch:
         # --distributed is DATA-PARALLEL training (lightgaussian_amd.dp): a camera shard per rank, the gradients averaged over the
         # ranks in front of every optimizer.step(), prune_list sharded by camera; the ranks stay bit-identical replicas of one model
