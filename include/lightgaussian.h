@@ -421,6 +421,30 @@ int lg_densify_rows(int32_t N, int64_t N_out, const void* map, const int32_t* re
                     const lg_densify_tensor* tensors /* host */, const float* rotation, const float* scaling, const float* noise,
                     int64_t noise_rows, uint32_t flags, void* stream);
 
+/* --- feature blending over a view's tile lists ------------------------------------------------------
+ * lg_blend_features composites C further per-Gaussian channels with the blending weights w = alpha T of a view whose forward has
+ * run: it reads only what that forward left in `geom` and `binning` (the same lg_view -- image size, segment_length, LG_FLAG_FAST_EXP
+ * -- and the same N and num_rendered as that call; for lg_forward_bounded num_rendered is max_rendered).  Per pixel, front to back over
+ * the tile's sorted list with the forward's own pair step (canonical arithmetic, or the guarded hardware exp under LG_FLAG_FAST_EXP: the
+ * include / exclude decisions are the forward's):
+ *     F_c = fma(f_c, alpha T, F_c),  T = T (1 - alpha),  stop at T (1 - alpha) < 1e-4;   out_c = fma(T, bg_c, F_c).
+ * features [N][C] float32, 1 <= C <= LG_FEATURES_MAX; bg_features [C] or NULL (zeros); out [C][H][W]; alpha [H][W] or NULL: the sum
+ * of the weights, accumulated as a channel of ones -- bit for bit what blending a column of ones gives, 1 - T up to rounding.
+ * In canonical mode a triple of channels equals lg_forward's image of the same colours_precomp bit for bit.  A view the forward
+ * abandoned on the device (lg_forward_bounded) yields bg_features / 0.  No host round trip, no allocation, every launch on `stream`.
+ * lg_blend_features_backward: dL_dfeatures [N][C] = sum over pixels of w dL_dout -- the gradient with respect to `features` only
+ * (geometry is a constant here).  No float atomics, no memset: one row of partial sums per (tile, Gaussian) instance, then one ordered
+ * sum per Gaussian; rows of Gaussians without instances are exact zeros and the result is bit-identical run to run.
+ * scratch: lg_features_scratch_bytes(N, num_rendered, C) device bytes (the channels are processed in chunks where [num_rendered][C]
+ * floats would exceed 1 GiB).  flags of the view that apply: LG_FLAG_FAST_EXP, LG_FLAG_PROFILE ("features_fwd", "features_bwd",
+ * "features_gather"), LG_FLAG_DEBUG (synchronise and check after every launch). */
+#define LG_FEATURES_MAX 64
+size_t lg_features_scratch_bytes(int32_t N, int64_t num_rendered, int32_t C);
+int lg_blend_features(const lg_view* view, int32_t N, const void* geom, const void* binning, int64_t num_rendered,
+                      const float* features, int32_t C, const float* bg_features, float* out, float* alpha, void* stream);
+int lg_blend_features_backward(const lg_view* view, int32_t N, const void* geom, const void* binning, int64_t num_rendered,
+                               const float* dL_dout, int32_t C, float* dL_dfeatures, void* scratch, void* stream);
+
 /* out[j] = (((rows[0][j] + rows[1][j]) + rows[2][j]) + ...) over V rows of n floats (row pitch row_stride floats): the
  * sequential in-place float accumulation of per-view scores in prune.py:144-155, in view order, as one launch. */
 int lg_ordered_sum(int32_t V, int64_t n, const float* rows, int64_t row_stride, float* out, void* stream);

@@ -29,6 +29,7 @@ ADAM_MAX_TENSORS = 8        # LG_ADAM_MAX_TENSORS: tensors per launch of lg_adam
 ADAM_SPAN = 4096            # LG_ADAM_SPAN: elements per workgroup of lg_adam_step
 DENSIFY_COPY, DENSIFY_MOMENT, DENSIFY_XYZ, DENSIFY_SCALING, DENSIFY_ZERO = 0, 1, 2, 3, 4     # lg_densify_tensor.role (LG_DENSIFY_*)
 DENSIFY_MAX_TENSORS = 32    # LG_DENSIFY_MAX_TENSORS: tensors per lg_densify_rows call
+FEATURES_MAX = 64           # LG_FEATURES_MAX: channels per lg_blend_features call
 ABI_VERSION = 7     # include/lightgaussian.h LG_ABI_VERSION this binding was written against (load() refuses another)
 
 EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scratch_bytes", "lg_forward",
@@ -41,7 +42,8 @@ EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scr
            "lg_debug_sort_orphan", "lg_debug_last_contributor", "lg_debug_tile_lists", "lg_geom_visible_offset",
            "lg_sh_grad_from_rgb", "lg_debug_view_meta", "lg_vq_ema_scratch_bytes", "lg_vq_ema_step", "lg_vq_colors",
            "lg_vq_code_index_bytes", "lg_vq_code_index_scratch_bytes", "lg_vq_code_index", "lg_vq_colors_bwd_scratch_bytes",
-           "lg_vq_colors_bwd", "lg_adam_step", "lg_densify_scratch_bytes", "lg_densify_stats", "lg_densify_plan", "lg_densify_rows"]
+           "lg_vq_colors_bwd", "lg_adam_step", "lg_densify_scratch_bytes", "lg_densify_stats", "lg_densify_plan", "lg_densify_rows",
+           "lg_features_scratch_bytes", "lg_blend_features", "lg_blend_features_backward"]
 
 
 class lg_view(C.Structure):
@@ -169,6 +171,11 @@ def load():
     lib.lg_densify_plan.argtypes = [C.c_int32, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp, vp, C.c_uint32, vp]
     lib.lg_densify_rows.restype = C.c_int
     lib.lg_densify_rows.argtypes = [C.c_int32, C.c_int64, vp, vp, C.c_int32, P(lg_densify_tensor), vp, vp, vp, C.c_int64, C.c_uint32, vp]
+    lib.lg_features_scratch_bytes.restype = C.c_size_t; lib.lg_features_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
+    lib.lg_blend_features.restype = C.c_int
+    lib.lg_blend_features.argtypes = [P(lg_view), C.c_int32, vp, vp, C.c_int64, vp, C.c_int32, vp, vp, vp, vp]
+    lib.lg_blend_features_backward.restype = C.c_int
+    lib.lg_blend_features_backward.argtypes = [P(lg_view), C.c_int32, vp, vp, C.c_int64, vp, C.c_int32, vp, vp, vp]
     lib.lg_debug_sort_temp_bytes.restype = C.c_size_t; lib.lg_debug_sort_temp_bytes.argtypes = [C.c_int64]
     lib.lg_debug_sort_keys.restype = C.c_int
     lib.lg_debug_sort_keys.argtypes = [C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp]

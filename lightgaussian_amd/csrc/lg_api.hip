@@ -19,6 +19,7 @@
 //   lg_adam.h        lg_adam_step: one Adam / AdamW step over all parameter tensors of the model in one launch (table by value, dwordx4)
 //   lg_densify.h     lg_densify_stats / lg_densify_plan / lg_densify_rows: view statistics and clone / split / prune of densify_and_prune
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound)
+//   lg_features.h    lg_features_fwd / _bwd / _gather: C further per-Gaussian channels blended over the lists a forward left, and dL/dfeatures
 //
 // Pipeline of one view:
 //   K1 project + EWA + SH->RGB + exact footprint culling  ->  K2 scan of instance counts, blocking read of R
@@ -44,6 +45,7 @@
 #include "lg_vq_color_bwd.h"
 #include "lg_adam.h"
 #include "lg_densify.h"
+#include "lg_features.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1194,6 +1196,125 @@ extern "C" int lg_loss_backward(int32_t C, int32_t H, int32_t W, const float* im
         lg_loss_bwd<<<grid, LG_LOSS_STRIP, 0, stream>>>(H, W, img, gt, lv.dmu1, lv.dsig1, lv.dsig12, dL_dl1, scale_l1, dL_dssim, scale_ssim,
                                               (float)(1.0 / ((double)C * H * W)), dL_dimg);
         KCHECK("lg_loss_bwd");
+    }
+    return LG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// feature blending over the lists of a forward (lg_features.h)
+static int features_args(const char* who, const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, int32_t C)
+{
+    char msg[160];
+    const char* what = nullptr;
+    if (!v) what = "null view";
+    else if (C < 1 || C > LG_FEATURES_MAX) what = "C must be 1 .. LG_FEATURES_MAX (64) channels";
+    else if (N < 0 || N >= (1 << LG_ID_BITS)) what = "N out of range";
+    else if (R < 0 || R >= (1ll << 30)) what = "num_rendered out of range";
+    else if (v->image_width <= 0 || v->image_height <= 0) what = "bad image size";
+    else if (v->segment_length != 0 && (v->segment_length < 64 || v->segment_length % 64 != 0)) what = "lg_view.segment_length must be 0 or a multiple of 64";
+    else if (!geom_p) what = "missing geom buffer";
+    else if (N > 0 && R > 0 && !bin_p) what = "missing binning buffer";
+    if (!what) {
+        const ViewGeom q = view_geom(v, N);
+        if (q.gx >= 65536 || q.gy >= 65536) what = "image too large";
+    }
+    if (!what) return LG_OK;
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return fail(LG_ERR_INVALID_ARGUMENT, msg);
+}
+static LgFeatView features_view(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const ViewGeom& q)
+{
+    LgFeatView f;
+    const GeomView geo = carve_geom(const_cast<void*>(geom_p), N);
+    f.W = q.W; f.H = q.H; f.gx = q.gx; f.ntiles = q.ntiles; f.N = N;
+    f.live = (N > 0 && R > 0 && bin_p) ? 1 : 0;
+    f.cap = (uint32_t)R; f.gid_mask = q.gid_mask;
+    f.rec = geo.rec; f.counters = geo.counters;
+    f.ranges = nullptr; f.entries = nullptr;
+    if (f.live) {
+        const BinView bin = carve_bin(const_cast<void*>(bin_p), R, q.W, q.H, q.S);
+        f.ranges = bin.ranges; f.entries = bin.entries;
+    }
+    return f;
+}
+using FeaturesFwdKernel = decltype(&lg_features_fwd<4, true>);
+static FeaturesFwdKernel features_fwd_kernel(int cg, bool exact)
+{
+    static const FeaturesFwdKernel k[3][2] = { { lg_features_fwd<4, false>, lg_features_fwd<4, true> }, { lg_features_fwd<16, false>, lg_features_fwd<16, true> },
+                                               { lg_features_fwd<32, false>, lg_features_fwd<32, true> } };
+    return k[cg == 4 ? 0 : cg == 16 ? 1 : 2][exact];
+}
+using FeaturesBwdKernel = decltype(&lg_features_bwd<4, true>);
+static FeaturesBwdKernel features_bwd_kernel(int nv, bool exact)
+{
+    static const FeaturesBwdKernel k[3][2] = { { lg_features_bwd<4, false>, lg_features_bwd<4, true> }, { lg_features_bwd<8, false>, lg_features_bwd<8, true> },
+                                               { lg_features_bwd<16, false>, lg_features_bwd<16, true> } };
+    return k[nv == 4 ? 0 : nv == 8 ? 1 : 2][exact];
+}
+
+extern "C" size_t lg_features_scratch_bytes(int32_t N, int64_t num_rendered, int32_t C)
+{
+    (void)N;
+    if (C < 1 || C > LG_FEATURES_MAX || num_rendered < 0) return 0;
+    return align_up((size_t)(num_rendered > 0 ? num_rendered : 1) * (size_t)lg_features_chunk(num_rendered, C) * sizeof(float));
+}
+
+extern "C" int lg_blend_features(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const float* features, int32_t C,
+                                 const float* bg_features, float* out, float* alpha, void* stream_p)
+{
+    int rc = features_args("lg_blend_features", v, N, geom_p, bin_p, R, C);
+    if (rc != LG_OK) return rc;
+    if (!out || (N > 0 && !features)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_blend_features: missing features / out buffer");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, exact = !(v->flags & LG_FLAG_FAST_EXP);
+    const ViewGeom q = view_geom(v, N);
+    const LgFeatView f = features_view(v, N, geom_p, bin_p, R, q);
+    // as many channels per walk as the registers take: one walk up to 32 channels, two up to 64
+    for (int c0 = 0; c0 < C;) {
+        const int rem = C - c0, cg = rem <= 4 ? 4 : rem <= 16 ? 16 : 32;
+        {
+            ProfScope ps(prof, "features_fwd", stream);
+            features_fwd_kernel(cg, exact)<<<q.ntiles_pad, 256, 0, stream>>>(f, C, c0, features, bg_features, out, alpha);
+        }
+        KCHECK("lg_features_fwd");
+        c0 += cg;
+    }
+    return LG_OK;
+}
+
+extern "C" int lg_blend_features_backward(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const float* dL_dout, int32_t C,
+                                          float* dL_dfeatures, void* scratch, void* stream_p)
+{
+    int rc = features_args("lg_blend_features_backward", v, N, geom_p, bin_p, R, C);
+    if (rc != LG_OK) return rc;
+    if (N == 0) return LG_OK;             // nothing to write
+    if (!dL_dout || !dL_dfeatures || !scratch) return fail(LG_ERR_INVALID_ARGUMENT, "lg_blend_features_backward: missing dL_dout / dL_dfeatures / scratch buffer");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, exact = !(v->flags & LG_FLAG_FAST_EXP);
+    const ViewGeom q = view_geom(v, N);
+    const LgFeatView f = features_view(v, N, geom_p, bin_p, R, q);
+    const GeomView geo = carve_geom(const_cast<void*>(geom_p), N);
+    float* rows = (float*)scratch;        // [R][cw] partial rows of the current chunk of channels, every row written by lg_features_bwd
+    const int chunk = lg_features_chunk(R, C);
+    for (int cb = 0; cb < C; cb += chunk) {
+        const int cw = std::min(chunk, C - cb);
+        if (f.live) {
+            for (int c0 = cb; c0 < cb + cw;) {
+                const int rem = cb + cw - c0, nv = rem <= 4 ? 4 : rem <= 8 ? 8 : 16;
+                {
+                    ProfScope ps(prof, "features_bwd", stream);
+                    features_bwd_kernel(nv, exact)<<<q.ntiles_pad, 256, 0, stream>>>(f, c0, cb + cw, cb, cw, geo.tinfo, dL_dout, rows);
+                }
+                KCHECK("lg_features_bwd");
+                c0 += nv;
+            }
+        }
+        {
+            ProfScope ps(prof, "features_gather", stream);
+            const size_t n = (size_t)N * cw;
+            lg_features_gather<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(N, C, cb, cw, f.live, f.cap, geo.touched, geo.offsets, geo.counters, rows, dL_dfeatures);
+        }
+        KCHECK("lg_features_gather");
     }
     return LG_OK;
 }

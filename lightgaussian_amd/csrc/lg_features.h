@@ -1,0 +1,290 @@
+// lg_features.h -- blend C per-Gaussian feature channels over the sorted tile lists a forward left behind (lg_blend_features), and the
+// gradient of that blend with respect to the features (lg_blend_features_backward): lg_features_fwd, lg_features_bwd, lg_features_gather.
+// Part of liblightgaussian_hip.so (single translation unit: lg_api.hip includes the lg_*.h kernel headers).
+//
+// The blending weights w = alpha T of a view are a function of what its forward leaves in the geom / binning buffers -- the 48-byte
+// records, the sorted keys, the tile ranges, tinfo -- so any number of further channels is composited without K1, the scan, the
+// duplication, the radix passes and the tile sort, and the gradient with respect to the channels, dF[j][c] = sum_pixels w[p][j] g[c][p],
+// needs neither K7's back-to-front replay nor K9.
+//
+// Walk (both kernels): K6's -- a workgroup per 16 x 16 tile, a wave per 8 x 8 block, batches of 64 list entries, lg_block_hit against the
+// wave's block, hits compacted in list order into the wave's LDS queue -- but only the 32 bytes of record the pair step reads are queued,
+// next to the Gaussian id.  The pair step is lg_feature_step (lg_math.h) on lg_pair_power and on lg_alpha_exact (canonical) or the
+// forward's guarded hardware exp (LG_FLAG_FAST_EXP): the include / exclude decisions are the forward's.  Each pixel terminates on its own
+// T (1 - alpha) < 1e-4; n_contrib is not read.  Lists of any length are walked serially (no checkpoints).  Nothing spins or waits; every
+// loop is bounded by the tile's range clamped to the view's instance count (geom.counters, as every kernel behind K2), ids are
+// checked against N.  A view the forward abandoned on the device has empty lists here: the image is the background, the gradient zero.
+//
+// Forward: the feature rows of a batch's hits are staged through LDS (coalesced row segments; the pair loop reads them as broadcast
+// ds_read_b128) and CG = 4 / 16 / 32 channels are carried per walk -- one walk up to 32 channels, two up to 64.  out_c = fma(T, bg_c, F_c).
+// alpha is accumulated as one more channel whose feature is 1 (sum of w): bit for bit the blend of a column of ones, equal to 1 - T
+// up to rounding.
+//
+// Backward: K7's discipline -- no float atomics, no memset.  Per hit entry a wave reduces w g[c] over its 64 pixels through an LDS
+// transpose (lg_feat_reduce: wave_reduce9_via_lds for NV = 4 / 8 / 16 values; entries no lane of the wave hit are skipped), the four waves'
+// partials meet in LDS and one row of NV sums per (tile, Gaussian) instance goes to the instance's pre-sort slot (lg_slot_of), written
+// exactly once, zeros included.  lg_features_gather adds every Gaussian's contiguous rows in slot order: bit-identical run to run.
+#pragma once
+
+#include "lg_host.h"
+#include "lg_wave.h"
+#include "lg_blend.h"
+
+// what both kernels need of a view (by value in the kernel arguments)
+struct LgFeatView {
+    int W, H, gx, ntiles, N;
+    int live;                       // the view has Gaussians and a binning buffer with instances; otherwise every list is empty and counters is not read
+    uint32_t cap;                   // instances the binning buffer was carved for
+    uint32_t gid_mask;
+    const uint2* ranges; const uint64_t* entries; const float4* rec; const uint32_t* counters;
+};
+
+// Entries [lo, hi) of the tile's list, clamped to the view's instance count.  False: the forward abandoned the view on the device.
+__device__ __forceinline__ bool lg_feat_list(const LgFeatView& v, int tile, uint32_t& lo, uint32_t& hi)
+{
+    lo = hi = 0u;
+    if (!v.live) return true;
+    if (v.counters[0] != 0u) return false;
+    const uint32_t R = min(v.counters[3], v.cap);
+    const uint2 r = v.ranges[tile];
+    hi = min(r.y, R); lo = min(r.x, hi);
+    return true;
+}
+
+// The front of one batch: lane l takes list entry idx = base + l (when idx < hi), tests its footprint against the wave's 8 x 8 block and
+// the hits are compacted in list order into the wave's queue: record rows 0 and 1, the Gaussian id, the entry's position in the batch.
+// Returns the number of hits.
+__device__ __forceinline__ uint32_t lg_feat_front(const LgFeatView& v, uint32_t idx, uint32_t hi, float bx0, float by0, float4* q0, float4* q1,
+                                                  uint32_t* qid, uint32_t* qpos, uint32_t lane)
+{
+    bool hit = false;
+    float4 r0, r1;
+    uint32_t id = 0;
+    if (idx < hi) {
+        id = (uint32_t)v.entries[idx] & v.gid_mask;
+        if (id < (uint32_t)v.N) {
+            r0 = v.rec[LG_REC_F4 * (size_t)id]; r1 = v.rec[LG_REC_F4 * (size_t)id + 1];
+            const float4 r2 = v.rec[LG_REC_F4 * (size_t)id + 2];
+            hit = lg_block_hit(r0, r1, r2, lg_reach(r0, r1, r2), bx0, by0);
+        }
+    }
+    const uint64_t mask = __ballot(hit);
+    if (mask == 0) return 0u;
+    if (hit) {
+        const uint32_t pos = prefix_popc(mask);
+        q0[pos] = r0; q1[pos] = r1; qid[pos] = id; qpos[pos] = lane;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return (uint32_t)__popcll(mask);
+}
+
+// One (pixel, entry) step: power and alpha as the forward's pair step evaluates them (fwd_pair_m), then lg_feature_step.  Called by all
+// 64 lanes (guard_alpha ballots); w = 0 unless the entry contributes to the pixel.
+template <bool EXACT>
+__device__ __forceinline__ int lg_feat_pair(const float4& a, const float4& b, bool done, float pxf, float pyf, float& T, float& w)
+{
+    float dx, dy;
+    const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
+    float alpha;
+    if (EXACT) alpha = lg_alpha_exact(b.y, power);
+    else alpha = guard_alpha(fminf(LG_ALPHA_MAX, b.y * __expf(power)), b.y, power);
+    w = 0.0f;
+    return done ? 0 : lg_feature_step(power, alpha, T, w);
+}
+
+// ------------------------------------------------------------------------------------------------
+// forward: channels [c0, c0 + CG) of out[C][H][W] (those below C), and alpha[H][W] with the first group
+template <int CG, bool EXACT>
+__global__ void __launch_bounds__(256)
+lg_features_fwd(LgFeatView v, int C, int c0, const float* __restrict__ features, const float* __restrict__ bg, float* __restrict__ out,
+                float* __restrict__ alpha_out)
+{
+    static_assert(CG % 4 == 0, "feature rows are read as float4");
+    __shared__ float4 q0[4][LG_Q], q1[4][LG_Q];
+    __shared__ uint32_t qid[4][LG_Q], qpos[4][LG_Q];
+    __shared__ __attribute__((aligned(16))) float frow[4][LG_Q * CG];
+    const int tile = xcd_tile(blockIdx.x);
+    if (tile >= v.ntiles) return;
+    const int wave = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63;
+    const LgBlock g = lg_block(v.W, v.H, tile % v.gx, tile / v.gx, wave, lane);
+    const float pxf = (float)g.pxi, pyf = (float)g.pyi;
+    uint32_t lo, hi;
+    (void)lg_feat_list(v, tile, lo, hi);        // an abandoned view has empty lists: background, alpha 0
+
+    float T = 1.0f, A = 0.0f, F[CG];
+#pragma unroll
+    for (int c = 0; c < CG; c++) F[c] = 0.0f;
+    bool done = !g.inside;
+    for (uint32_t base = lo; base < hi; base += LG_Q) {
+        if (__ballot(!done) == 0) break;        // every pixel of this wave is saturated or outside
+        const uint32_t nhit = lg_feat_front(v, base + lane, hi, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], qid[wave], qpos[wave], lane);
+        if (nhit == 0u) continue;
+        // the hits' feature rows: CG consecutive floats per hit (zeros past channel C)
+        for (uint32_t i = lane; i < nhit * CG; i += 64u) {
+            const uint32_t j = i / CG, c = i % CG;
+            frow[wave][i] = (c0 + (int)c < C) ? features[(size_t)qid[wave][j] * C + c0 + c] : 0.0f;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (uint32_t j = 0; j < nhit; j++) {
+            const float4 a = q0[wave][j], b = q1[wave][j];
+            float w;
+            const int res = lg_feat_pair<EXACT>(a, b, done, pxf, pyf, T, w);
+            done = done || res == 2;
+            A = fmaf(1.0f, w, A);
+            const float4* fr = reinterpret_cast<const float4*>(&frow[wave][j * CG]);
+#pragma unroll
+            for (int k = 0; k < CG / 4; k++) {
+                const float4 f = fr[k];
+                F[4 * k] = fmaf(f.x, w, F[4 * k]); F[4 * k + 1] = fmaf(f.y, w, F[4 * k + 1]);
+                F[4 * k + 2] = fmaf(f.z, w, F[4 * k + 2]); F[4 * k + 3] = fmaf(f.w, w, F[4 * k + 3]);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();        // (the next batch overwrites the queue)
+    }
+    if (g.inside) {
+        const size_t pid = (size_t)g.pyi * v.W + g.pxi, HW = (size_t)v.H * v.W;
+#pragma unroll
+        for (int c = 0; c < CG; c++)
+            if (c0 + c < C) out[(size_t)(c0 + c) * HW + pid] = bg ? fmaf(T, bg[c0 + c], F[c]) : F[c];
+        if (alpha_out && c0 == 0) alpha_out[pid] = A;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward
+// lg_feat_reduce: wave_reduce9_via_lds (lg_blend.h) for NV <= 16 values.  The NV partials of every lane go to an NV x 64 matrix (row stride
+// LG_RED_STRIDE); lane 4 r + q adds columns 16 q .. 16 q + 15 of row r (four ds_read_b128, 15 adds) and two quad-DPP adds join the quarters;
+// total r of the entry is left at dst[r].  A fixed order: the sums are reproducible.  Lanes past 4 NV redo the last row.
+template <int NV>
+__device__ __forceinline__ void lg_feat_reduce(const float (&p)[NV], float* red, float* dst, uint32_t lane)
+{
+    static_assert(NV >= 1 && NV <= 16, "one row per four lanes");
+#pragma unroll
+    for (int k = 0; k < NV; k++) red[k * LG_RED_STRIDE + (int)lane] = p[k];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint32_t r = min(lane >> 2, (uint32_t)(NV - 1)), q = lane & 3u;
+    const float4* src = reinterpret_cast<const float4*>(red + r * LG_RED_STRIDE + q * 16u);
+    const float4 x0 = src[0], x1 = src[1], x2 = src[2], x3 = src[3];
+    float s = (((x0.x + x0.y) + (x0.z + x0.w)) + ((x1.x + x1.y) + (x1.z + x1.w))) +
+              (((x2.x + x2.y) + (x2.z + x2.w)) + ((x3.x + x3.y) + (x3.z + x3.w)));
+    s = dpp_add<0xB1, 0xf>(s);                      // quad_perm [1,0,3,2]
+    s = dpp_add<0x4E, 0xf>(s);                      // quad_perm [2,3,0,1]: every lane of the quad holds the row total
+    if (q == 0u && lane < 4u * NV) dst[lane >> 2] = s;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();                // (the next entry overwrites `red`)
+}
+
+// Channels [c0, c0 + NV) (those below c1) of the partial rows: rows[slot][CW], column (c0 - cb) + k, for every entry of every list.
+// The four waves of a tile walk the list batch by batch TOGETHER (two workgroup barriers per batch, reached by every thread: the trip
+// count is the tile's); a wave whose pixels are all saturated skips the batch's arithmetic, and the rows of entries nobody hit are zeros.
+#define LG_FEAT_PART_STRIDE(NV) ((NV) + 1)
+template <int NV, bool EXACT>
+__global__ void __launch_bounds__(256)
+lg_features_bwd(LgFeatView v, int c0, int c1, int cb, int CW, const uint4* __restrict__ tinfo, const float* __restrict__ dL_dout,
+                float* __restrict__ rows)
+{
+    __shared__ float4 q0[4][LG_Q], q1[4][LG_Q];
+    __shared__ uint32_t qid[4][LG_Q], qpos[4][LG_Q];
+    __shared__ __attribute__((aligned(16))) float red[4][NV * LG_RED_STRIDE];
+    __shared__ float part[4][LG_Q * LG_FEAT_PART_STRIDE(NV)];
+    __shared__ uint32_t slot[LG_Q];
+    __shared__ unsigned long long wmask[4];
+    const int tile = xcd_tile(blockIdx.x);
+    if (tile >= v.ntiles) return;
+    const int wave = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63;
+    const int tx = tile % v.gx, ty = tile / v.gx;
+    const LgBlock g = lg_block(v.W, v.H, tx, ty, wave, lane);
+    const float pxf = (float)g.pxi, pyf = (float)g.pyi;
+    uint32_t lo, hi;
+    if (!lg_feat_list(v, tile, lo, hi) || lo == hi) return;      // workgroup-uniform
+    const uint32_t slot_cap = min(v.counters[3], v.cap);         // (lo < hi: the view is live)
+
+    float gv[NV];
+    {
+        const size_t pid = (size_t)g.pyi * v.W + g.pxi, HW = (size_t)v.H * v.W;
+#pragma unroll
+        for (int k = 0; k < NV; k++) gv[k] = (g.inside && c0 + k < c1) ? dL_dout[(size_t)(c0 + k) * HW + pid] : 0.0f;
+    }
+    float T = 1.0f;
+    bool done = !g.inside;
+    for (uint32_t base = lo; base < hi; base += LG_Q) {
+        const uint32_t nbt = min((uint32_t)LG_Q, hi - base);
+        if (wave == 0) {
+            // the pre-sort slots of the batch's entries: where their rows go
+            uint32_t sl = 0xFFFFFFFFu;
+            if (lane < nbt) {
+                const uint32_t id = (uint32_t)v.entries[base + lane] & v.gid_mask;
+                if (id < (uint32_t)v.N) sl = lg_slot_of(tinfo[id], tx, ty);
+            }
+            slot[lane] = sl;
+        }
+        uint64_t hitmask = 0ull;                                  // entries of the batch this wave has a partial row for (scalar)
+        if (__ballot(!done) != 0) {
+            const uint32_t nhit = lg_feat_front(v, base + lane, hi, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], qid[wave], qpos[wave], lane);
+            for (uint32_t j = 0; j < nhit; j++) {
+                const float4 a = q0[wave][j], b = q1[wave][j];
+                float w;
+                const int res = lg_feat_pair<EXACT>(a, b, done, pxf, pyf, T, w);
+                done = done || res == 2;
+                if (__ballot(res == 1) == 0) continue;            // no pixel of the wave took the entry
+                float p[NV];
+#pragma unroll
+                for (int k = 0; k < NV; k++) p[k] = w * gv[k];
+                const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)qpos[wave][j]);
+                lg_feat_reduce<NV>(p, red[wave], &part[wave][e * LG_FEAT_PART_STRIDE(NV)], lane);
+                hitmask |= 1ull << e;
+            }
+        }
+        if (lane == 0u) wmask[wave] = hitmask;
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < nbt * NV; i += 256u) {
+            const uint32_t e = i / NV, k = i % NV;
+            float s = 0.0f;
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if ((wmask[u] >> e) & 1ull) s += part[u][e * LG_FEAT_PART_STRIDE(NV) + k];
+            const uint32_t sl = slot[e];
+            if (sl < slot_cap && c0 + (int)k < c1) rows[(size_t)sl * CW + (c0 - cb) + k] = s;
+        }
+        __syncthreads();                                          // (the next batch overwrites the queue, the partials and the slots)
+    }
+}
+
+// dF[i][cb .. cb + cw) = the sum of Gaussian i's rows (consecutive pre-sort slots offsets - touched .. offsets) in slot order; zeros
+// for a Gaussian without instances and for a view that was abandoned.  A thread per (Gaussian, channel of the chunk).
+__global__ void __launch_bounds__(256)
+lg_features_gather(int N, int C, int cb, int cw, int live, uint32_t cap, const uint32_t* __restrict__ touched, const uint32_t* __restrict__ offsets,
+                   const uint32_t* __restrict__ counters, const float* __restrict__ rows, float* __restrict__ dF)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)N * cw) return;
+    const uint32_t i = (uint32_t)(t / (size_t)cw), k = (uint32_t)(t % (size_t)cw);
+    uint32_t n = 0, base = 0;
+    if (live && counters[0] == 0u) {
+        const uint32_t R = min(counters[3], cap);
+        n = touched[i]; base = offsets[i] - n;
+        if (base >= R || n > R - base) n = 0;
+    }
+    float s = 0.0f;
+    for (uint32_t j = 0; j < n; j++) s += rows[(size_t)(base + j) * cw + k];
+    dF[(size_t)i * C + cb + k] = s;
+}
+
+// Channels per chunk of the backward: the partial rows of a chunk, [num_rendered][cw] floats, stay within LG_FEAT_SCRATCH_BUDGET bytes
+// where 16 channels do (the caller's scratch: lg_features_scratch_bytes).
+#define LG_FEAT_SCRATCH_BUDGET ((size_t)1 << 30)
+static inline int lg_features_chunk(int64_t R, int C)
+{
+    const size_t per = (size_t)(R > 0 ? R : 1) * sizeof(float);
+    const size_t fit = LG_FEAT_SCRATCH_BUDGET / per / 16 * 16;
+    return (int)std::min<size_t>((size_t)C, std::max<size_t>(16, fit));
+}

@@ -353,6 +353,22 @@ LG_HD int lg_blend_pair(float gx, float gy, float ha, float nb, float hc, float 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Feature blending (lg_features.h): the three tests of lg_blend_pair on a pair whose power (lg_pair_power) and alpha the caller has
+// evaluated -- lg_alpha_exact in canonical mode, the guarded hardware exp of the forward otherwise -- without the three colour
+// channels: the caller blends as many channels as it carries, F_c = fmaf(f_c, w, F_c), with the weight w = alpha T returned here.
+// Returns 0 = rejected (w, T untouched), 1 = contributes (w set, T advanced), 2 = pixel saturated (done).
+LG_HD int lg_feature_step(float power, float alpha, float& T, float& w)
+{
+    if (!(power <= 0.0f)) return 0;
+    if (alpha < LG_ALPHA_MIN) return 0;
+    const float test_T = T * (1.0f - alpha);
+    if (test_T < LG_T_MIN) return 2;
+    w = alpha * T;
+    T = test_T;
+    return 1;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Backward of the per-Gaussian stage (K8 + K9 fused).  acc = the 9 blend-stage sums:
 //   [0,1] d/d(mean2D pixel x,y)  [2,3,4] d/d(conic A,B,C) (B: full derivative)  [5] d/d(opacity)  [6..8] d/d(rgb)
 struct LgGradOut {

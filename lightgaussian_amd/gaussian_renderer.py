@@ -192,3 +192,43 @@ def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_mod
     # visibility_filter = radii > 0 (gaussian_renderer/__init__.py:121), as K1 left it in the forward's geom buffer: no compare kernel
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible,
             "radii": radii}
+
+
+_DEPTH_EPS = 1e-6
+
+
+def render_features(viewpoint_camera, pc, pipe, features, bg_features=None, scaling_modifier=1.0, *, options=None):
+    """Blend per-Gaussian feature channels with the view's blending weights (lightgaussian_amd.features.blend_features): ONE ordinary
+    forward, then lg_blend_features on the tile lists it left -- no second K1 / binning chain per three channels.
+
+    features: a float32 tensor [N, C], 1 <= C <= 64, or the string "depth": the single channel is then the view-space z of pc.get_xyz
+    (evaluated by torch) and the result gains "depth" = features / alpha.clamp_min(1e-6), the expected depth of what the pixel sees.
+    bg_features: [C] values behind the last Gaussian (default zeros).  The colour by-product is rendered over black.  options
+    (keyword-only): the rasterizer knobs, as for render().
+
+    Returns {"features" [C,H,W], "alpha" [H,W], "render" [3,H,W], "radii", "visibility_filter"}.  pc: a GaussianModel of the reference's
+    shape, a SyntheticGaussians, or a vectree.CompressedGaussians / TrainableCompressed (colours from lg_vq_colors, as in
+    render_compressed).  The model is a CONSTANT of this call: its getters are evaluated without grad, only `features` receives a
+    gradient (deterministic, lg_blend_features_backward); alpha, render and depth's denominator carry none."""
+    from .features import blend_features
+    compressed = isinstance(pc, CompressedGaussians)
+    if compressed and (pipe.convert_SHs_python or pipe.compute_cov3D_python):
+        raise NotImplementedError("convert_SHs_python / compute_cov3D_python need the dequantised tensors: pass pc.to_dense() instead")
+    with torch.no_grad():
+        override = pc.colors(viewpoint_camera.camera_center) if compressed else None
+        means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp = _inputs(viewpoint_camera, pc, pipe, scaling_modifier, override)
+        bg_color = torch.zeros(3, dtype=torch.float32, device=means3D.device)
+        want_depth = isinstance(features, str)
+        if want_depth:
+            if features != "depth":
+                raise ValueError(f"features must be a tensor [N, C] or the string 'depth', not {features!r}")
+            vm = viewpoint_camera.world_view_transform.to(means3D.device)
+            features = (means3D @ vm[:3, 2:3] + vm[3, 2]).contiguous()          # view-space z, [N, 1]
+    rs = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, False)
+    image, alpha, color, radii = blend_features(rs, features, means3D=means3D, opacities=opacity, scales=scales, rotations=rotations,
+                                                cov3D_precomp=cov3D_precomp, shs=shs, colors_precomp=colors_precomp, bg_features=bg_features,
+                                                options=options)
+    pkg = {"features": image, "alpha": alpha, "render": color, "radii": radii, "visibility_filter": radii > 0}
+    if want_depth:
+        pkg["depth"] = image / alpha.clamp_min(_DEPTH_EPS)
+    return pkg
