@@ -433,7 +433,7 @@ int lg_densify_rows(int32_t N, int64_t N_out, const void* map, const int32_t* re
  * In canonical mode a triple of channels equals lg_forward's image of the same colours_precomp bit for bit.  A view the forward
  * abandoned on the device (lg_forward_bounded) yields bg_features / 0.  No host round trip, no allocation, every launch on `stream`.
  * lg_blend_features_backward: dL_dfeatures [N][C] = sum over pixels of w dL_dout -- the gradient with respect to `features` only
- * (geometry is a constant here).  No float atomics, no memset: one row of partial sums per (tile, Gaussian) instance, then one ordered
+ * (the geometry gradient: lg_backward_features below).  No float atomics, no memset: one row of partial sums per (tile, Gaussian) instance, then one ordered
  * sum per Gaussian; rows of Gaussians without instances are exact zeros and the result is bit-identical run to run.
  * scratch: lg_features_scratch_bytes(N, num_rendered, C) device bytes (the channels are processed in chunks where [num_rendered][C]
  * floats would exceed 1 GiB).  flags of the view that apply: LG_FLAG_FAST_EXP, LG_FLAG_PROFILE ("features_fwd", "features_bwd",
@@ -444,6 +444,24 @@ int lg_blend_features(const lg_view* view, int32_t N, const void* geom, const vo
                       const float* features, int32_t C, const float* bg_features, float* out, float* alpha, void* stream);
 int lg_blend_features_backward(const lg_view* view, int32_t N, const void* geom, const void* binning, int64_t num_rendered,
                                const float* dL_dout, int32_t C, float* dL_dfeatures, void* scratch, void* stream);
+
+/* lg_backward_features: lg_backward for a loss on the feature image `out`, on `alpha` and on the colour image of ONE forward -- the
+ * geometry gradient of lg_blend_features.  Any of dL_dcolor [3][H][W], dL_dout [C][H][W], dL_dalpha [H][W] may be NULL (all three:
+ * zero geometry gradients).  Order on `stream`: K7 (lg_blend_bwd) when dL_dcolor is given; lg_features_bwd_geom, one back-to-front walk
+ * of the tile lists per group of up to 32 channels (dL_dalpha rides with the first), which adds the six pixel-offset moments of the
+ * feature / alpha loss to the per-instance rows K7 wrote (or writes the rows when K7 did not run); K9 (lg_preprocess_bwd) ONCE; then
+ * dL_dfeatures [N][C] (or NULL) exactly as lg_blend_features_backward computes it.  view, gaussians, radii, geom, binning, img,
+ * num_rendered and the gradient outputs dL_dmeans2D .. dL_dshs_rest: as for lg_backward, same rules (an output per provided input);
+ * features, C, bg_features: as handed to lg_blend_features.  A view the forward abandoned, or a segment_length other than the
+ * forward's, yields zero gradients.  No float atomics, no memset: bit-identical run to run.
+ * scratch: lg_backward_features_scratch_bytes(N, num_rendered, C) device bytes.  Profile entry of the walks: "features_bwd_geom". */
+size_t lg_backward_features_scratch_bytes(int32_t N, int64_t num_rendered, int32_t C);
+int lg_backward_features(const lg_view* view, const lg_gaussians* g, const int32_t* radii, const void* geom, const void* binning,
+                         const void* img, int64_t num_rendered, const float* dL_dcolor, const float* features, int32_t C,
+                         const float* bg_features, const float* dL_dout, const float* dL_dalpha, float* dL_dmeans2D,
+                         float* dL_dmeans3D, float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales,
+                         float* dL_drotations, float* dL_dcov3D, float* dL_dshs_rest, float* dL_dfeatures, void* scratch,
+                         void* stream);
 
 /* out[j] = (((rows[0][j] + rows[1][j]) + rows[2][j]) + ...) over V rows of n floats (row pitch row_stride floats): the
  * sequential in-place float accumulation of per-view scores in prune.py:144-155, in view order, as one launch. */

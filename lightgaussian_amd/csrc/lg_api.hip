@@ -460,10 +460,52 @@ extern "C" int lg_forward_bounded(const lg_view* view, const lg_gaussians* g, vo
     return forward_impl(view, g, geom, img, nullptr, nullptr, &b, weight_policy, out_color, out_radii, out_count, out_score, nullptr, nullptr, stream);
 }
 
+// K9 (lg_preprocess_bwd) over the moment rows [R][12] a blend backward left: sums every Gaussian's rows and chains them to every input.
+// Shared by lg_backward / lg_backward_chunked (rows from K7) and lg_backward_features (rows from K7 and / or lg_features_bwd_geom).
+static void preprocess_bwd_launch(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const ViewGeom& q, const GeomView& geo,
+                                  const BinView& bin, const float* rows, float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dshs,
+                                  float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                                  float* dL_dshs_rest, bool rgb_only, hipStream_t stream, int chunks, lg_chunk_fn on_chunk, void* user)
+{
+    // K9 runs over Gaussian ranges: `chunks` launches of consecutive 64-Gaussian workgroups.  After each launch is enqueued
+    // the caller is told (on_chunk): rows [first, first + count) of every gradient tensor are final once the stream reaches
+    // that point -- a data-parallel trainer starts their all-reduce there, while K9 computes the next range.
+    const int N = g->N, W = q.W, H = q.H, S = q.S;
+    ProfScope ps(v->flags & LG_FLAG_PROFILE, "preprocess_bwd", stream);
+    const int nblk = (N + LG_PP - 1) / LG_PP;
+    if (chunks < 1) chunks = 1;
+    if (chunks > nblk) chunks = nblk;
+    const int per = (nblk + chunks - 1) / chunks;
+    for (int first_blk = 0; first_blk < nblk; first_blk += per) {
+        const int nb = std::min(per, nblk - first_blk);
+        // (the view of a backward is the view of its forward: LG_FLAG_SAVE_SH_JACOBIAN says K1 left the SH direction Jacobians)
+        const bool jac = (v->flags & LG_FLAG_SAVE_SH_JACOBIAN) && g->shs && (dL_dshs || rgb_only);
+        preprocess_bwd_kernel(v->flags & LG_FLAG_RAW_PARAMS, jac)<<<nb, LG_PP, 0, stream>>>(
+            N, first_blk, g->M, v->sh_degree, W, H, v->tanfovx, v->tanfovy, v->scale_modifier, v->viewmatrix, v->projmatrix, v->campos, g->means3D,
+            g->shs, g->shs_rest, g->colors_precomp, g->opacities, g->scales, g->rotations, g->cov3D_precomp, radii, geo.rec, geo.counters, bin.meta,
+            (uint32_t)S, geo.touched, geo.offsets, reinterpret_cast<const float4*>(rows), geo.shjac, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dshs_rest,
+            dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D);
+        if (on_chunk) on_chunk(user, first_blk * LG_PP, std::min(N - first_blk * LG_PP, nb * LG_PP));
+    }
+}
+
+// what lg_backward_features adds to a backward: a loss on the feature image and / or on alpha (lg_features_bwd_geom, lg_features.h)
+struct FeatGrad { const float* features; int C; const float* bg; const float* dL_dout; const float* dL_dalpha; };
+static LgFeatView features_view(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const ViewGeom& q);
+using FeaturesBwdGeomKernel = decltype(&lg_features_bwd_geom<4, true, true>);
+static FeaturesBwdGeomKernel features_bwd_geom_kernel(int cg, bool exact, bool accum)
+{
+#define LG_FBG(CG) { { lg_features_bwd_geom<CG, false, false>, lg_features_bwd_geom<CG, false, true> }, { lg_features_bwd_geom<CG, true, false>, lg_features_bwd_geom<CG, true, true> } }
+    static const FeaturesBwdGeomKernel k[3][2][2] = { LG_FBG(4), LG_FBG(16), LG_FBG(32) };
+#undef LG_FBG
+    return k[cg == 4 ? 0 : cg == 16 ? 1 : 2][exact][accum];
+}
+
 static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const void* geom_p, const void* bin_p,
                          const void* img_p, int64_t R, const float* dL_dcolor, float* dL_dmeans2D, float* dL_dmeans3D,
                          float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
-                         float* dL_dcov3D, float* dL_dshs_rest, void* scratch, void* stream_p, int chunks, lg_chunk_fn on_chunk, void* user)
+                         float* dL_dcov3D, float* dL_dshs_rest, void* scratch, void* stream_p, int chunks, lg_chunk_fn on_chunk, void* user,
+                         const FeatGrad* fg = nullptr)
 {
     int rc = check_args(v, g);
     if (rc != LG_OK) return rc;
@@ -473,7 +515,7 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
     const bool rgb_only = g->shs && !dL_dshs && dL_dcolors;
     if (g->shs_rest && !dL_dshs_rest && !rgb_only) return fail(LG_ERR_INVALID_ARGUMENT, "missing gradient output for shs_rest");
     if (rgb_only && dL_dshs_rest) return fail(LG_ERR_INVALID_ARGUMENT, "dL_dshs_rest without dL_dshs");
-    if (!radii || !geom_p || !bin_p || !img_p || !dL_dcolor || !dL_dmeans2D || !dL_dmeans3D || !dL_dopacity || !scratch)
+    if (!radii || !geom_p || !bin_p || !img_p || (!dL_dcolor && !fg) || !dL_dmeans2D || !dL_dmeans3D || !dL_dopacity || !scratch)
         return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
     if ((g->shs && !dL_dshs && !rgb_only) || (g->colors_precomp && !dL_dcolors) || (g->scales && (!dL_dscales || !dL_drotations)) ||
         (g->cov3D_precomp && !dL_dcov3D))
@@ -490,33 +532,35 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
     const uint32_t max_items = (uint32_t)(q.ntiles + R / S + 1);
     // (the work list of the backward blend -- one item per (tile, segment of S entries), longest first -- was left in the binning
     // buffer by the forward: one extra workgroup of lg_blend_fwd)
-    if (R > 0) {
+    if (R > 0 && dL_dcolor) {
         ProfScope ps(prof, "blend_bwd", stream);
         blend_bwd_kernel(!(v->flags & LG_FLAG_FAST_EXP))<<<max_items, 64, 0, stream>>>(W, H, q.gx, S, bin.work, bin.meta, bin.ranges, bin.entries, q.gid_mask, geo.tinfo,
                                                                                        geo.rec, v->bg, img.final_T, img.n_contrib, dL_dcolor, bin.ckpt, rows);
     }
     KCHECK("lg_blend_bwd");
-    {
-        // K9 runs over Gaussian ranges: `chunks` launches of consecutive 64-Gaussian workgroups.  After each launch is enqueued
-        // the caller is told (on_chunk): rows [first, first + count) of every gradient tensor are final once the stream reaches
-        // that point -- a data-parallel trainer starts their all-reduce there, while K9 computes the next range.
-        ProfScope ps(prof, "preprocess_bwd", stream);
-        const int nblk = (N + LG_PP - 1) / LG_PP;
-        if (chunks < 1) chunks = 1;
-        if (chunks > nblk) chunks = nblk;
-        const int per = (nblk + chunks - 1) / chunks;
-        for (int first_blk = 0; first_blk < nblk; first_blk += per) {
-            const int nb = std::min(per, nblk - first_blk);
-            // (the view of a backward is the view of its forward: LG_FLAG_SAVE_SH_JACOBIAN says K1 left the SH direction Jacobians)
-            const bool jac = (v->flags & LG_FLAG_SAVE_SH_JACOBIAN) && g->shs && (dL_dshs || rgb_only);
-            preprocess_bwd_kernel(v->flags & LG_FLAG_RAW_PARAMS, jac)<<<nb, LG_PP, 0, stream>>>(
-                N, first_blk, g->M, v->sh_degree, W, H, v->tanfovx, v->tanfovy, v->scale_modifier, v->viewmatrix, v->projmatrix, v->campos, g->means3D,
-                g->shs, g->shs_rest, g->colors_precomp, g->opacities, g->scales, g->rotations, g->cov3D_precomp, radii, geo.rec, geo.counters, bin.meta,
-                (uint32_t)S, geo.touched, geo.offsets, reinterpret_cast<const float4*>(rows), geo.shjac, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dshs_rest,
-                dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D);
-            if (on_chunk) on_chunk(user, first_blk * LG_PP, std::min(N - first_blk * LG_PP, nb * LG_PP));
+    if (fg && R > 0) {
+        // lg_backward_features: the moments of the feature / alpha loss join K7's in the same rows (lg_features.h), CG channels per walk;
+        // the first walk writes whole rows, zeros included, when K7 did not run -- also when there is no image gradient at all
+        const bool exact = !(v->flags & LG_FLAG_FAST_EXP);
+        const LgFeatView f = features_view(v, N, geom_p, bin_p, R, q);
+        if (fg->dL_dout || fg->dL_dalpha || !dL_dcolor) {
+            const int nch = fg->dL_dout ? fg->C : 1;     // without dL_dout one walk: dL_dalpha's, or the zero rows
+            bool accum = dL_dcolor != nullptr;
+            for (int c0 = 0; c0 < nch;) {
+                const int rem = nch - c0, cg = rem <= 4 ? 4 : rem <= 16 ? 16 : 32;
+                {
+                    ProfScope ps(prof, "features_bwd_geom", stream);
+                    features_bwd_geom_kernel(cg, exact, accum)<<<q.ntiles_pad, 256, 0, stream>>>(f, (uint32_t)S, bin.meta, fg->C, c0, geo.tinfo, fg->features,
+                                                                                                fg->bg, fg->dL_dout, fg->dL_dalpha, img.final_T, img.n_contrib, rows);
+                }
+                KCHECK("lg_features_bwd_geom");
+                accum = true;
+                c0 += cg;
+            }
         }
     }
+    preprocess_bwd_launch(v, g, radii, q, geo, bin, rows, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
+                          dL_dcov3D, dL_dshs_rest, rgb_only, stream, chunks, on_chunk, user);
     KCHECK("lg_preprocess_bwd");
     if (debug && R > 0) {
         uint32_t h_seg = 0;
@@ -1282,13 +1326,10 @@ extern "C" int lg_blend_features(const lg_view* v, int32_t N, const void* geom_p
     return LG_OK;
 }
 
-extern "C" int lg_blend_features_backward(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const float* dL_dout, int32_t C,
-                                          float* dL_dfeatures, void* scratch, void* stream_p)
+// the launches of lg_blend_features_backward (arguments checked by the caller)
+static int features_backward_run(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const float* dL_dout, int32_t C,
+                                 float* dL_dfeatures, void* scratch, void* stream_p)
 {
-    int rc = features_args("lg_blend_features_backward", v, N, geom_p, bin_p, R, C);
-    if (rc != LG_OK) return rc;
-    if (N == 0) return LG_OK;             // nothing to write
-    if (!dL_dout || !dL_dfeatures || !scratch) return fail(LG_ERR_INVALID_ARGUMENT, "lg_blend_features_backward: missing dL_dout / dL_dfeatures / scratch buffer");
     hipStream_t stream = (hipStream_t)stream_p;
     const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, exact = !(v->flags & LG_FLAG_FAST_EXP);
     const ViewGeom q = view_geom(v, N);
@@ -1317,6 +1358,44 @@ extern "C" int lg_blend_features_backward(const lg_view* v, int32_t N, const voi
         KCHECK("lg_features_gather");
     }
     return LG_OK;
+}
+
+extern "C" int lg_blend_features_backward(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const float* dL_dout, int32_t C,
+                                          float* dL_dfeatures, void* scratch, void* stream_p)
+{
+    int rc = features_args("lg_blend_features_backward", v, N, geom_p, bin_p, R, C);
+    if (rc != LG_OK) return rc;
+    if (N == 0) return LG_OK;             // nothing to write
+    if (!dL_dout || !dL_dfeatures || !scratch) return fail(LG_ERR_INVALID_ARGUMENT, "lg_blend_features_backward: missing dL_dout / dL_dfeatures / scratch buffer");
+    return features_backward_run(v, N, geom_p, bin_p, R, dL_dout, C, dL_dfeatures, scratch, stream_p);
+}
+
+// lg_backward with a loss on the feature image and on alpha next to (or instead of) the colour loss: K7 when dL_dcolor is given, the
+// geometry walks of lg_features_bwd_geom into the same moment rows, K9 once, then dL_dfeatures as lg_blend_features_backward computes it.
+// scratch = the moment rows [R][12] | the partial rows of lg_blend_features_backward.
+extern "C" size_t lg_backward_features_scratch_bytes(int32_t N, int64_t num_rendered, int32_t C)
+{
+    if (C < 1 || C > LG_FEATURES_MAX || num_rendered < 0) return 0;
+    return lg_backward_scratch_bytes(N, num_rendered) + lg_features_scratch_bytes(N, num_rendered, C);
+}
+
+extern "C" int lg_backward_features(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const void* geom_p, const void* bin_p,
+                                    const void* img_p, int64_t R, const float* dL_dcolor, const float* features, int32_t C,
+                                    const float* bg_features, const float* dL_dout, const float* dL_dalpha, float* dL_dmeans2D,
+                                    float* dL_dmeans3D, float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales,
+                                    float* dL_drotations, float* dL_dcov3D, float* dL_dshs_rest, float* dL_dfeatures, void* scratch,
+                                    void* stream_p)
+{
+    if (!g) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_features: null gaussians");
+    int rc = features_args("lg_backward_features", v, g->N, geom_p, bin_p, R, C);
+    if (rc != LG_OK) return rc;
+    if (g->N > 0 && !features && (dL_dout || dL_dfeatures)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_features: missing features");
+    if (g->N > 0 && dL_dfeatures && !dL_dout) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_features: dL_dfeatures without dL_dout");
+    const FeatGrad fg = { features, C, bg_features, dL_dout, dL_dalpha };
+    rc = backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales,
+                       dL_drotations, dL_dcov3D, dL_dshs_rest, scratch, stream_p, 1, nullptr, nullptr, &fg);
+    if (rc != LG_OK || g->N == 0 || !dL_dfeatures) return rc;
+    return features_backward_run(v, g->N, geom_p, bin_p, R, dL_dout, C, dL_dfeatures, (char*)scratch + lg_backward_scratch_bytes(g->N, R), stream_p);
 }
 
 // diagnostics: Gaussian id of the last contributor of every pixel (0xFFFFFFFF: none) from the state a forward saved -- the

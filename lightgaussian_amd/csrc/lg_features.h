@@ -279,6 +279,167 @@ lg_features_gather(int N, int C, int cb, int cw, int live, uint32_t cap, const u
     dF[(size_t)i * C + cb + k] = s;
 }
 
+// ------------------------------------------------------------------------------------------------
+// backward with respect to the GEOMETRY: the six pixel-offset moments of a loss on out / alpha, added to (ACCUM) or written as (!ACCUM)
+// the per-instance moment rows [R][12] that K7 (lg_blend_bwd) writes and K9 (lg_preprocess_bwd) sums and chains to every input.
+// The moments are linear in the per-pixel loss gradient, so a colour loss (K7), CG channels of dL_dout per walk and dL_dalpha (with the
+// walk of channel 0) meet in the same rows and K9 runs once.
+//
+// Walk: lg_features_bwd's -- a workgroup per tile, a wave per 8 x 8 block, the four waves take a batch of 64 entries together, hits
+// through lg_feat_front -- but BACK TO FRONT: batches from the tile's last one down to its first, the hits of a batch from the last
+// to the first.  Per pixel T starts at the colour forward's final_T and an entry counts when its list position is <= the pixel's
+// n_contrib (img buffer), then lg_feature_bwd_step (lg_math.h) on the forward's own power / alpha.  Lists of any length are walked
+// serially, no checkpoints are read; every loop is bounded by the tile's range clamped to counters[3], ids are checked against N,
+// nothing spins or waits (two workgroup barriers per batch, reached by every thread: the trip count is the tile's).  A view the
+// forward abandoned and a segment length other than the forward's (meta[2]) return at once: K9 refuses those too, the gradients are
+// zero.  A wave none of whose pixels reached a batch skips its arithmetic; with ACCUM the batches behind the last one any pixel of the
+// tile reached are not visited at all, without it they get their zero rows (K9 reads every row).
+//
+// Channels [c0, c0 + CG) (those below C): g_c in registers, the feature rows of a batch's hits staged through LDS as in lg_features_fwd,
+// q = sum_c f_c g_c (+ dL_dalpha when c0 == 0).  Reduction: K7's discipline -- per hit entry lg_feat_reduce<6> over the wave's 64
+// pixels, the four waves' partials meet in LDS, thread e of the workgroup owns entry e of the batch and updates columns 0..5 of its
+// row at the pre-sort slot (lg_slot_of).  !ACCUM writes all 12 floats.  Walks are stream-ordered and a slot has one writer per walk:
+// no float atomics, no memset, bit-identical run to run.
+#define LG_FEAT_GEOM_NV 6
+template <int CG, bool EXACT, bool ACCUM>
+__global__ void __launch_bounds__(256)
+lg_features_bwd_geom(LgFeatView v, uint32_t S, const uint32_t* __restrict__ meta, int C, int c0, const uint4* __restrict__ tinfo,
+                     const float* __restrict__ features, const float* __restrict__ bg, const float* __restrict__ dL_dout,
+                     const float* __restrict__ dL_dalpha, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
+                     float* __restrict__ rows)
+{
+    static_assert(CG % 4 == 0, "feature rows are read as float4");
+    constexpr int NV = LG_FEAT_GEOM_NV;
+    __shared__ float4 q0[4][LG_Q], q1[4][LG_Q];
+    __shared__ uint32_t qid[4][LG_Q], qpos[4][LG_Q];
+    __shared__ __attribute__((aligned(16))) float frow[4][LG_Q * CG];
+    __shared__ __attribute__((aligned(16))) float red[4][NV * LG_RED_STRIDE];
+    __shared__ float part[4][LG_Q * LG_FEAT_PART_STRIDE(NV)];
+    __shared__ unsigned long long wmask[4];
+    __shared__ uint32_t wlast[4];
+    const int tile = xcd_tile(blockIdx.x);
+    if (tile >= v.ntiles) return;
+    const int wave = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63;
+    const int tx = tile % v.gx, ty = tile / v.gx;
+    const LgBlock g = lg_block(v.W, v.H, tx, ty, wave, lane);
+    const float pxf = (float)g.pxi, pyf = (float)g.pyi;
+    uint32_t lo, hi;
+    if (!lg_feat_list(v, tile, lo, hi) || lo == hi) return;      // workgroup-uniform
+    if (meta[2] != S) return;                                    // (lo < hi: the view is live, the binning buffer is there)
+    const uint32_t slot_cap = min(v.counters[3], v.cap);
+    const uint32_t n_list = hi - lo;
+
+    // per pixel: the gradient of this group of channels, the background term, the replay state
+    float gv[CG];
+    float gA = 0.0f, T = 0.0f, Tfb = 0.0f, Sb = 0.0f;
+    uint32_t last = 0u;
+    const bool have = dL_dout != nullptr;
+    {
+        const size_t pid = (size_t)g.pyi * v.W + g.pxi, HW = (size_t)v.H * v.W;
+        float bgdot = 0.0f;
+#pragma unroll
+        for (int k = 0; k < CG; k++) {
+            gv[k] = (have && g.inside && c0 + k < C) ? dL_dout[(size_t)(c0 + k) * HW + pid] : 0.0f;
+            if (bg && c0 + k < C) bgdot = fmaf(bg[c0 + k], gv[k], bgdot);
+        }
+        if (g.inside) {
+            T = final_T[pid];
+            last = min(n_contrib[pid], n_list);
+            if (dL_dalpha && c0 == 0) gA = dL_dalpha[pid];
+        }
+        Tfb = T * bgdot;
+    }
+    // the last list position any pixel of the wave / of the tile reached
+    uint32_t wl = last;
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) wl = max(wl, (uint32_t)__shfl_xor((int)wl, sh));
+    wl = (uint32_t)__builtin_amdgcn_readfirstlane((int)wl);
+    if (lane == 0u) wlast[wave] = wl;
+    __syncthreads();
+    const uint32_t tl = max(max(wlast[0], wlast[1]), max(wlast[2], wlast[3]));
+    const uint32_t n_walk = ACCUM ? tl : n_list;                 // entries this walk visits
+    if (n_walk == 0u) return;                                    // workgroup-uniform
+
+    for (int k = (int)((n_walk - 1u) / LG_Q); k >= 0; k--) {
+        const uint32_t rel0 = (uint32_t)k * LG_Q, base = lo + rel0;
+        const uint32_t nbt = min((uint32_t)LG_Q, n_list - rel0);
+        // thread e of the workgroup owns entry e of the batch: the pre-sort slot its row lives at
+        uint32_t sl = 0xFFFFFFFFu;
+        if (threadIdx.x < nbt) {
+            const uint32_t id = (uint32_t)v.entries[base + threadIdx.x] & v.gid_mask;
+            if (id < (uint32_t)v.N) sl = lg_slot_of(tinfo[id], tx, ty);
+        }
+        uint64_t hitmask = 0ull;                                  // entries of the batch this wave has a partial row for (scalar)
+        if (wl > rel0) {
+            const uint32_t nhit = lg_feat_front(v, base + lane, hi, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], qid[wave], qpos[wave], lane);
+            if (have) {
+                for (uint32_t i = lane; i < nhit * CG; i += 64u) {
+                    const uint32_t j = i / CG, c = i % CG;
+                    frow[wave][i] = (c0 + (int)c < C) ? features[(size_t)qid[wave][j] * C + c0 + c] : 0.0f;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+            for (int j = (int)nhit - 1; j >= 0; j--) {
+                const float4 a = q0[wave][j], b = q1[wave][j];
+                const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)qpos[wave][j]);
+                float dx, dy;
+                const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
+                float G, alpha;
+                if (EXACT) {
+                    G = lg_exp(fminf(power, 0.0f));
+                    alpha = fminf(LG_ALPHA_MAX, b.y * G);         // lg_alpha_exact, with its exp kept
+                } else {
+                    G = __expf(power);
+                    alpha = guard_alpha(fminf(LG_ALPHA_MAX, b.y * G), b.y, power);
+                }
+                float q = gA;
+                if (have) {
+                    const float4* fr = reinterpret_cast<const float4*>(&frow[wave][j * CG]);
+#pragma unroll
+                    for (int u = 0; u < CG / 4; u++) {
+                        const float4 f = fr[u];
+                        q = fmaf(f.x, gv[4 * u], q); q = fmaf(f.y, gv[4 * u + 1], q);
+                        q = fmaf(f.z, gv[4 * u + 2], q); q = fmaf(f.w, gv[4 * u + 3], q);
+                    }
+                }
+                float p[NV] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                float w;
+                const bool ok = lg_feature_bwd_step<EXACT>(rel0 + e + 1u <= last, power, G, alpha, dx, dy, q, Tfb, T, Sb, p, w);
+                if (__ballot(ok) == 0) continue;                  // no pixel of the wave took the entry
+                lg_feat_reduce<NV>(p, red[wave], &part[wave][e * LG_FEAT_PART_STRIDE(NV)], lane);
+                hitmask |= 1ull << e;
+            }
+        }
+        if (lane == 0u) wmask[wave] = hitmask;
+        __syncthreads();
+        if (threadIdx.x < nbt && sl < slot_cap) {
+            const uint32_t e = threadIdx.x;
+            float s[NV] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if ((wmask[u] >> e) & 1ull) {
+#pragma unroll
+                    for (int r = 0; r < NV; r++) s[r] += part[u][e * LG_FEAT_PART_STRIDE(NV) + r];
+                }
+            float4* dst = reinterpret_cast<float4*>(rows) + 3 * (size_t)sl;
+            if (ACCUM) {
+                const float4 r0 = dst[0];
+                const float2 r1 = *reinterpret_cast<const float2*>(dst + 1);
+                dst[0] = make_float4(r0.x + s[0], r0.y + s[1], r0.z + s[2], r0.w + s[3]);
+                *reinterpret_cast<float2*>(dst + 1) = make_float2(r1.x + s[4], r1.y + s[5]);
+            } else {
+                dst[0] = make_float4(s[0], s[1], s[2], s[3]);
+                dst[1] = make_float4(s[4], s[5], 0.0f, 0.0f);
+                dst[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            }
+        }
+        __syncthreads();                                          // (the next batch overwrites the queue, the partials and the masks)
+    }
+}
+
 // Channels per chunk of the backward: the partial rows of a chunk, [num_rendered][cw] floats, stay within LG_FEAT_SCRATCH_BUDGET bytes
 // where 16 channels do (the caller's scratch: lg_features_scratch_bytes).
 #define LG_FEAT_SCRATCH_BUDGET ((size_t)1 << 30)

@@ -368,6 +368,47 @@ LG_HD int lg_feature_step(float power, float alpha, float& T, float& w)
     return 1;
 }
 
+// One (pixel, entry) step of the BACK-TO-FRONT replay of the feature blend (lg_features_bwd_geom, lg_features.h): the geometry
+// gradient of  L(out_c = sum_j f[j][c] w_j + T_final bg_c,  alpha = sum_j w_j).  Per pixel, with g_c = dL/dout_c and gA = dL/dalpha:
+//   q   = sum_c f[j][c] g_c + gA       the entry's own features projected on the pixel's gradient (alpha: a column of ones, background 0)
+//   Tfb = T_final sum_c bg_c g_c       the background term
+// and the state T (starts at the forward's final_T) and S (starts at 0: the projection on g of what lies behind the entry -- the
+// published colour recurrence a <- a + alpha (c - a) is linear, so its projection obeys S <- S + alpha (q - S), as in K7's
+// bwd_pair_fast).  The entry's power (lg_pair_power, with dx, dy), G = exp(power) and alpha come from the caller exactly as the forward
+// evaluated them -- lg_exp / lg_alpha_exact in canonical mode, the guarded hardware exp otherwise -- and `live` says that the entry's
+// list position is not behind the pixel's last contributor (n_contrib): the include / exclude decisions are the forward's.
+//   inv = 1 / (1 - alpha);  Tn = T inv;  d = q - S;  dL/dalpha = d Tn - Tfb inv;  t = G dL/dalpha     (straight through the 0.99 clamp, as K7)
+//   m[0..5] += t {dx, dy, dx dx, dx dy, dy dy, 1}      the moments lg_rows_to_grads reads (m[6..8], d/d rgb, are K7's alone)
+//   w = alpha Tn  (the blending weight of the entry);  T = Tn;  S += alpha d
+// Everything is linear in (g, gA): channel groups may be replayed separately, each with its own S and Tfb, and their moments add.
+// Returns false (nothing touched) when the entry does not contribute.  EXACT = false on the device: v_rcp_f32 for inv, as K7's fast path.
+template <bool EXACT>
+LG_HD bool lg_feature_bwd_step(bool live, float power, float G, float alpha, float dx, float dy, float q, float Tfb, float& T, float& S,
+                               float* m, float& w)
+{
+    if (!live || !(power <= 0.0f) || alpha < LG_ALPHA_MIN) return false;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float inv = EXACT ? 1.0f / (1.0f - alpha) : __builtin_amdgcn_rcpf(1.0f - alpha);
+#else
+    const float inv = 1.0f / (1.0f - alpha);
+#endif
+    const float Tn = T * inv;
+    const float d = q - S;
+    const float dL_dalpha = d * Tn - Tfb * inv;
+    const float t = G * dL_dalpha;
+    const float tdx = t * dx, tdy = t * dy;
+    m[0] += tdx;
+    m[1] += tdy;
+    m[2] += tdx * dx;
+    m[3] += tdx * dy;
+    m[4] += tdy * dy;
+    m[5] += t;
+    w = alpha * Tn;
+    T = Tn;
+    S = S + alpha * d;
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Backward of the per-Gaussian stage (K8 + K9 fused).  acc = the 9 blend-stage sums:
 //   [0,1] d/d(mean2D pixel x,y)  [2,3,4] d/d(conic A,B,C) (B: full derivative)  [5] d/d(opacity)  [6..8] d/d(rgb)

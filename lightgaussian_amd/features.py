@@ -7,6 +7,11 @@ for a gradient that is linear in the weights.  blend_features runs the ordinary 
 (csrc/lg_features.h) on the lists that forward left: up to 64 channels per call, `alpha` for free, and a backward
 (lg_blend_features_backward) that walks the lists once more and gathers one row per Gaussian -- no float atomics, bit-identical
 run to run.
+
+blend_features(..., geometry_grad=True) makes the maps differentiable with respect to the GEOMETRY as well: the backward
+(lg_backward_features) runs K7 for a colour loss, adds the pixel-offset moments of the feature / alpha loss to the same per-instance
+rows with one more back-to-front walk of the lists per group of channels (lg_features_bwd_geom), and K9 once -- a joint photometric +
+depth + alpha loss costs one forward and one backward.
 """
 import ctypes as C
 import warnings
@@ -92,8 +97,81 @@ class _BlendFeatures(torch.autograd.Function):
         return (d_feat,) + none
 
 
+class _BlendFeaturesGeom(torch.autograd.Function):
+    """blend_features(geometry_grad=True): a DIFFERENTIATED forward that keeps the img buffer, as _RasterizeGaussians does; out, alpha
+    and color are differentiable, radii is not.  The backward is one lg_backward_features call."""
+
+    @staticmethod
+    def forward(ctx, features, bg_features, means3D, means2D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp, rs, options):
+        lib = _lib.load()
+        opts = _rasterizer.resolve_options(options)
+        call = _Call(rs, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, exact=False, opts=opts,
+                     differentiated=True)
+        if features.device != call.dev or features.shape[0] != call.N:
+            raise ValueError("features must hold one row per Gaussian, on the Gaussians' device")
+        dev, n, c = call.dev, call.N, int(features.shape[1])
+        h, w = int(rs.image_height), int(rs.image_width)
+        bg = _prep(bg_features, dev)
+        with torch.cuda.device(dev):
+            color, radii, _gc, _sc, geom, binning, img, num_rendered = _native_forward(lib, call, rs, False)
+            out = torch.empty((c, h, w), dtype=torch.float32, device=dev)
+            alpha = torch.empty((h, w), dtype=torch.float32, device=dev)
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(lib.lg_blend_features(C.byref(call.view), n, _ptr(geom), _ptr(binning), C.c_int64(num_rendered), _ptr(features), c,
+                                             _ptr(bg), _ptr(out), _ptr(alpha), stream))
+        ctx.raster_settings = rs
+        ctx.num_rendered = num_rendered
+        ctx.opts = {k: v for k, v in opts.items() if k not in _rasterizer._PER_CALL_ONLY}    # the backward runs with the forward's options
+        ctx.had = (shs is not None and shs.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
+                   scales is not None and scales.numel() > 0, cov3D_precomp is not None and cov3D_precomp.numel() > 0)
+        empty = torch.empty(0, dtype=torch.uint8, device=dev)
+        ctx.save_for_backward(features, bg if bg is not None else empty, call.means3D, call.sh, call.colors, call.opac, call.scales, call.rots,
+                              call.cov, radii, geom, binning if binning is not None else empty, img)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return out, alpha, color, radii
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_alpha, grad_color, _grad_radii=None):
+        lib = _lib.load()
+        rs = ctx.raster_settings
+        features, bg, means3D, sh, colors, opac, scales, rots, cov, radii, geom, binning, img = ctx.saved_tensors
+        if features.shape[0] == 0:          # an empty model: nothing was rendered, and the empty inputs were not kept
+            z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=features.device)  # noqa: E731
+            return (z(0, features.shape[1]), None, z(0, 3), z(0, 3), z(0, 1)) + (None,) * 7
+        call = _Call(rs, means3D, sh, colors, opac, scales, rots, cov, exact=False, opts=ctx.opts, differentiated=True)
+        dev, n, m = call.dev, call.N, call.M
+        c = int(features.shape[1])
+        f32 = dict(dtype=torch.float32, device=dev)
+        grad_out, grad_alpha, grad_color = _prep(grad_out, dev), _prep(grad_alpha, dev), _prep(grad_color, dev)
+        want_feat = ctx.needs_input_grad[0] and grad_out is not None
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            run = n > 0 and binning.numel() > 0       # (no Gaussians, or a forward that left no binning buffer: zero gradients)
+            new = torch.empty if run else torch.zeros
+            g_means2D = new((n, 3), **f32)
+            g_means3D = new((n, 3), **f32)
+            g_opac = new((n, 1), **f32)
+            g_sh = new((n, m, 3), **f32) if call.sh is not None else None
+            g_col = new((n, 3), **f32) if call.colors is not None else None
+            g_sc = new((n, 3), **f32) if call.scales is not None else None
+            g_rot = new((n, 4), **f32) if call.rots is not None else None
+            g_cov = new((n, 6), **f32) if call.cov is not None else None
+            g_feat = new((n, c), **f32) if want_feat else None
+            if run:
+                scratch = torch.empty(max(int(lib.lg_backward_features_scratch_bytes(n, ctx.num_rendered, c)), 1), dtype=torch.uint8, device=dev)
+                _lib.check(lib.lg_backward_features(
+                    C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img),
+                    C.c_int64(ctx.num_rendered), _ptr(grad_color), _ptr(features), c, _ptr(bg) if bg.numel() else None, _ptr(grad_out),
+                    _ptr(grad_alpha), _ptr(g_means2D), _ptr(g_means3D), _ptr(g_sh), _ptr(g_col), _ptr(g_opac), _ptr(g_sc), _ptr(g_rot),
+                    _ptr(g_cov), None, _ptr(g_feat), _ptr(scratch), stream))
+        had_sh, had_col, had_sc, had_cov = ctx.had
+        return (g_feat, None, g_means3D, g_means2D, g_opac, g_sc if had_sc else None, g_rot if had_sc else None, g_cov if had_cov else None,
+                g_sh if had_sh else None, g_col if had_col else None, None, None)
+
+
 def blend_features(raster_settings, features, *, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, shs=None,
-                   colors_precomp=None, bg_features=None, options=None):
+                   colors_precomp=None, bg_features=None, options=None, geometry_grad=False, means2D=None):
     """(features_image [C,H,W], alpha [H,W], color [3,H,W], radii [N]) of one view.
 
     Runs the ordinary forward (the colour image is a by-product; the rasterizer options -- fast_exp, segment_length, sync_free,
@@ -105,11 +183,23 @@ def blend_features(raster_settings, features, *, means3D, opacities, scales=None
     Differentiable with respect to `features` ONLY: the geometry inputs (means3D, opacities, scales, rotations, cov3D_precomp, shs,
     colors_precomp) and bg_features are constants of this function -- its backward returns None for them, and alpha / color carry no
     gradient.  A loss on feature maps that should move the geometry needs a second, ordinary render.  A warning is issued once when a
-    geometry input requires grad.  The gradient is summed in a fixed order: two backward calls give identical bits."""
+    geometry input requires grad.  The gradient is summed in a fixed order: two backward calls give identical bits.
+
+    geometry_grad=True: the forward is a differentiated one and features_image, alpha and color are all differentiable -- with respect
+    to `features` as above (the same bits) and to means3D, opacities, scales / rotations or cov3D_precomp, shs or colors_precomp, and
+    means2D ([N, 3], optional: its gradient is the view-space one densification statistics read).  Any subset of the three maps may
+    enter the loss; one backward call (lg_backward_features) serves them all, deterministic like the rasterizer's.  No warning."""
     if raster_settings.f_count:
         raise ValueError("blend_features runs on a colour forward: raster_settings.f_count must be False")
+    if means2D is not None and not geometry_grad:
+        raise ValueError("means2D receives the view-space gradient: it needs geometry_grad=True")
     _check_features(features, bg_features)
     _rasterizer._check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
+    if geometry_grad:
+        if means2D is None:
+            means2D = torch.zeros(0, dtype=torch.float32, device=means3D.device)
+        return _BlendFeaturesGeom.apply(features, bg_features, means3D, means2D, opacities, scales, rotations, cov3D_precomp, shs,
+                                        colors_precomp, raster_settings, options)
     geometry = (means3D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp)
     if not _warned[0] and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in geometry):
         _warned[0] = True

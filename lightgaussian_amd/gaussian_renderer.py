@@ -7,6 +7,7 @@ target of the rasterizer (our HIP library instead of the CUDA submodule) and tha
 created on the Gaussians' own device instead of the hard-coded "cuda" (identical on one GPU,
 required for one-process-per-GPU sharding).
 """
+import contextlib
 import math
 import threading
 
@@ -197,27 +198,39 @@ def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_mod
 _DEPTH_EPS = 1e-6
 
 
-def render_features(viewpoint_camera, pc, pipe, features, bg_features=None, scaling_modifier=1.0, *, options=None):
+def render_features(viewpoint_camera, pc, pipe, features, bg_features=None, scaling_modifier=1.0, *, options=None, geometry_grad=False,
+                    bg_color=None):
     """Blend per-Gaussian feature channels with the view's blending weights (lightgaussian_amd.features.blend_features): ONE ordinary
     forward, then lg_blend_features on the tile lists it left -- no second K1 / binning chain per three channels.
 
     features: a float32 tensor [N, C], 1 <= C <= 64, or the string "depth": the single channel is then the view-space z of pc.get_xyz
     (evaluated by torch) and the result gains "depth" = features / alpha.clamp_min(1e-6), the expected depth of what the pixel sees.
-    bg_features: [C] values behind the last Gaussian (default zeros).  The colour by-product is rendered over black.  options
-    (keyword-only): the rasterizer knobs, as for render().
+    bg_features: [C] values behind the last Gaussian (default zeros).  bg_color: the background of the colour by-product (default
+    black).  options (keyword-only): the rasterizer knobs, as for render().
 
     Returns {"features" [C,H,W], "alpha" [H,W], "render" [3,H,W], "radii", "visibility_filter"}.  pc: a GaussianModel of the reference's
     shape, a SyntheticGaussians, or a vectree.CompressedGaussians / TrainableCompressed (colours from lg_vq_colors, as in
-    render_compressed).  The model is a CONSTANT of this call: its getters are evaluated without grad, only `features` receives a
-    gradient (deterministic, lg_blend_features_backward); alpha, render and depth's denominator carry none."""
+    render_compressed).
+
+    geometry_grad=False (default): the model is a CONSTANT of this call: its getters are evaluated without grad, only `features`
+    receives a gradient (deterministic, lg_blend_features_backward); alpha, render and depth's denominator carry none.
+
+    geometry_grad=True: the getters (and the "depth" feature) are evaluated under grad, on the unfused inputs path, and "features",
+    "alpha", "render" and "depth" (numerator and denominator) are differentiable with respect to the model: one call serves a joint
+    photometric + depth + alpha loss, one backward (lg_backward_features) carries it to _xyz, _opacity, _scaling, _rotation and the
+    colours.  The result gains "viewspace_points", whose .grad is the view-space gradient densification reads.  Compressed models are
+    not supported in this mode."""
     from .features import blend_features
     compressed = isinstance(pc, CompressedGaussians)
+    if geometry_grad and isinstance(pc, (CompressedGaussians, TrainableCompressed)):
+        raise NotImplementedError("render_features(geometry_grad=True) needs the dense tensors: pass pc.to_dense() instead")
     if compressed and (pipe.convert_SHs_python or pipe.compute_cov3D_python):
         raise NotImplementedError("convert_SHs_python / compute_cov3D_python need the dequantised tensors: pass pc.to_dense() instead")
-    with torch.no_grad():
+    with contextlib.nullcontext() if geometry_grad else torch.no_grad():
         override = pc.colors(viewpoint_camera.camera_center) if compressed else None
         means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp = _inputs(viewpoint_camera, pc, pipe, scaling_modifier, override)
-        bg_color = torch.zeros(3, dtype=torch.float32, device=means3D.device)
+        if bg_color is None:
+            bg_color = torch.zeros(3, dtype=torch.float32, device=means3D.device)
         want_depth = isinstance(features, str)
         if want_depth:
             if features != "depth":
@@ -225,10 +238,13 @@ def render_features(viewpoint_camera, pc, pipe, features, bg_features=None, scal
             vm = viewpoint_camera.world_view_transform.to(means3D.device)
             features = (means3D @ vm[:3, 2:3] + vm[3, 2]).contiguous()          # view-space z, [N, 1]
     rs = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, False)
+    screenspace_points = _screenspace_points(pc) if geometry_grad else None
     image, alpha, color, radii = blend_features(rs, features, means3D=means3D, opacities=opacity, scales=scales, rotations=rotations,
                                                 cov3D_precomp=cov3D_precomp, shs=shs, colors_precomp=colors_precomp, bg_features=bg_features,
-                                                options=options)
+                                                options=options, geometry_grad=geometry_grad, means2D=screenspace_points)
     pkg = {"features": image, "alpha": alpha, "render": color, "radii": radii, "visibility_filter": radii > 0}
+    if geometry_grad:
+        pkg["viewspace_points"] = screenspace_points
     if want_depth:
         pkg["depth"] = image / alpha.clamp_min(_DEPTH_EPS)
     return pkg

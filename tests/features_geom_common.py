@@ -1,0 +1,221 @@
+"""Shared by tests/test_features_geom_host.py and tests/test_gpu_features_geom.py (test infrastructure): the scenes, the reference for
+the geometry gradient of a loss on feature / alpha / colour maps -- the oracle's own backward, summed over channel triples -- the
+tolerance rule of tests/test_gpu_parity.py::test_backward_parity, and the g++ build of tests/cpu_harness/lg_features_geom_harness.cpp."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import torch
+
+import common
+from common import syn
+from oracle import oracle
+
+GEOMETRY = ("means2D", "means3D", "opacities", "scales", "rotations")
+TOL = 1e-4
+
+# tests/test_gpu_features.py's scenes (seed 3, extent (1.5, 1, 1.5), orbit_camera(1, 7, ..., radius 4)), plus an opaque one in which
+# pixels terminate before their list ends (opacity_mean chosen on the CPU: sigmoid(4) = 0.98, test_features_geom_host.py asserts it)
+SCENES = {
+    "N300_70x45": dict(N=300, W=70, H=45, scale=0.06, opm=0.0),
+    "N64_33x17": dict(N=64, W=33, H=17, scale=0.1, opm=0.0),
+    "N400_48x48": dict(N=400, W=48, H=48, scale=0.25, opm=-2.0),
+    "N400_48x48_seg64": dict(N=400, W=48, H=48, scale=0.25, opm=-2.0, seg=64),
+    "N200_40x40_opaque": dict(N=200, W=40, H=40, scale=0.25, opm=4.0),
+}
+
+
+def scene(name):
+    c = SCENES[name]
+    g = syn.make_gaussians(c["N"], seed=3, extent=(1.5, 1.0, 1.5), log_scale_mean=math.log(c["scale"]), opacity_mean=c["opm"])
+    cam = syn.orbit_camera(1, 7, c["W"], c["H"], radius=4.0)
+    return c, g, cam
+
+
+def loss_inputs(N, Cn, H, W, bg=True, seed=11):
+    """features [N, C], bg_features [C] or None, dL_dout [C,H,W], dL_dalpha [H,W], dL_dcolor [3,H,W]: float32, fixed seed."""
+    rs = np.random.RandomState(seed + Cn)
+    F = rs.randn(N, Cn).astype(np.float32)
+    bgf = rs.randn(Cn).astype(np.float32) if bg else None
+    return F, bgf, rs.randn(Cn, H, W).astype(np.float32), rs.randn(H, W).astype(np.float32), rs.randn(3, H, W).astype(np.float32)
+
+
+_REF = {}
+
+
+def reference(name, Cn, bg, kind, color_bg=(0.1, 0.2, 0.3)):
+    """{dtype name: {tensor: float64 array}} for float64 and float32 oracles: the sum over channel triples of oracle.backward -- the
+    feature columns (and a column of ones with background 0 for alpha) padded to whole triples as colors_precomp, plus, for kind
+    "c" in kind, the backward of the scene's own SH colours over color_bg.  kind: the maps in the loss, letters of "oac" (out, alpha,
+    colour).  Computed once per key."""
+    name = name.replace("_seg64", "")         # the same scene: the segment length is the rasterizer's business
+    key = (name, Cn, bool(bg), kind)
+    if key in _REF:
+        return _REF[key]
+    c, g, cam = scene(name)
+    N, W, H = c["N"], c["W"], c["H"]
+    F, bgf, dout, dalpha, dcolor = loss_inputs(N, Cn, H, W, bg)
+    cols, grads, bgs = [], [], []
+    if "o" in kind:
+        cols.append(F); grads.append(dout); bgs.append(bgf if bgf is not None else np.zeros(Cn, np.float32))
+    if "a" in kind:
+        cols.append(np.ones((N, 1), np.float32)); grads.append(dalpha[None]); bgs.append(np.zeros(1, np.float32))
+    cols, grads, bgs = np.concatenate(cols, 1), np.concatenate(grads, 0), np.concatenate(bgs)
+    pad = (-cols.shape[1]) % 3
+    cols = np.concatenate([cols, np.zeros((N, pad), np.float32)], 1)
+    grads = np.concatenate([grads, np.zeros((pad, H, W), np.float32)], 0)
+    bgs = np.concatenate([bgs, np.zeros(pad, np.float32)])
+    out = {}
+    for dt in (np.float64, np.float32):
+        acc = {n: 0.0 for n in GEOMETRY}
+        for c0 in range(0, cols.shape[1], 3):
+            kw = common.scene_kwargs(g, cam, W, H, precolor=torch.from_numpy(cols[:, c0:c0 + 3].copy()), bg=tuple(float(b) for b in bgs[c0:c0 + 3]))
+            gr = oracle.backward(oracle.forward(dtype=dt, **kw), grads[c0:c0 + 3])
+            for n in GEOMETRY:
+                acc[n] = acc[n] + np.asarray(gr[n], np.float64)
+        if "c" in kind:
+            kw = common.scene_kwargs(g, cam, W, H, bg=color_bg)
+            gr = oracle.backward(oracle.forward(dtype=dt, **kw), dcolor)
+            for n in GEOMETRY:
+                acc[n] = acc[n] + np.asarray(gr[n], np.float64)
+        out[np.dtype(dt).name] = acc
+    _REF[key] = out
+    return out
+
+
+def rel_err(a, b):
+    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
+    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
+
+
+def elem_excess(a, b, rtol=1e-4, atol_frac=2e-5):
+    a = np.asarray(a, np.float64).reshape(-1); b = np.asarray(b, np.float64).reshape(-1)
+    bound = rtol * np.abs(b) + atol_frac * (np.abs(b).max() + 1e-300)
+    return float((np.abs(a - b) / bound).max()) if a.size else 0.0
+
+
+def assert_within(got, ref, what="", names=GEOMETRY):
+    """The rule of test_backward_parity: rel_err <= max(1e-4, 3 floor) and elem_excess <= max(1, 3 x the float32 oracle's), floor = the
+    float32 oracle's own error against the float64 one on the same sums.  Every figure is printed before it is asserted."""
+    r64, r32 = ref["float64"], ref["float32"]
+    for n in names:
+        a = np.asarray(got[n], np.float64).reshape(r64[n].shape)
+        floor, err = rel_err(r32[n], r64[n]), rel_err(a, r64[n])
+        ex, ex32 = elem_excess(a, r64[n]), elem_excess(r32[n], r64[n])
+        print(f"{what} {n}: rel_err {err:.3e} (float32 oracle {floor:.3e})  elem_excess {ex:.3f} (float32 oracle {ex32:.3f})")
+        assert np.isfinite(a).all(), f"{what} {n}: not finite"
+        assert err <= max(TOL, 3.0 * floor), f"{what} grad {n}: rel err {err:.3e} (float32 oracle floor {floor:.3e})"
+        assert ex <= max(1.0, 3.0 * ex32), f"{what} grad {n}: worst element {ex:.2f}x the element-wise bound (float32 oracle {ex32:.2f}x)"
+
+
+_HARNESS = None
+
+
+def harness():
+    global _HARNESS
+    if _HARNESS is not None:
+        return _HARNESS
+    d = os.path.join(common.ROOT, "tests", "cpu_harness")
+    so = os.path.join(d, "liblg_features_geom_harness.so")
+    srcs = [os.path.join(d, "lg_features_geom_harness.cpp"), os.path.join(common.ROOT, "lightgaussian_amd", "csrc", "lg_math.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
+                               srcs[0], "-o", so])
+    lib = C.CDLL(so)
+    P, F = C.c_void_p, C.c_float
+    lib.h_feature_bwd_step.restype = C.c_int
+    lib.h_feature_bwd_step.argtypes = [C.c_int] + [F] * 7 + [C.POINTER(F)] * 2 + [P, C.POINTER(F)]
+    lib.h_features_geom.restype = C.c_longlong
+    lib.h_features_geom.argtypes = [C.c_int] * 4 + [P] * 6 + [F, F] + [P] * 13
+    _HARNESS = lib
+    return lib
+
+
+def harness_grads(kw, features, bg=None, dL_dout=None, dL_dalpha=None):
+    """kw: common.scene_kwargs(...) (numpy, scales / rotations).  Returns ({tensor: array}, out [C,H,W], alpha [H,W], radii, pixels that
+    ended before their list did)."""
+    lib = harness()
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    means3D = f32(kw["means3D"]); N = means3D.shape[0]
+    feats = f32(features); Cn = feats.shape[1]
+    W, H = kw["W"], kw["H"]
+    op = f32(kw["opacities"]).reshape(-1); sc = f32(kw["scales"]); rot = f32(kw["rotations"])
+    vm = f32(kw["viewmatrix"]); pm = f32(kw["projmatrix"])
+    bgc, g, ga = f32(bg), f32(dL_dout), f32(dL_dalpha)
+    out = np.zeros((Cn, H, W), np.float32); alpha = np.zeros((H, W), np.float32); radii = np.zeros(N, np.int32)
+    gr = dict(means2D=np.zeros((N, 3), np.float32), means3D=np.zeros((N, 3), np.float32), opacities=np.zeros((N, 1), np.float32),
+              scales=np.zeros((N, 3), np.float32), rotations=np.zeros((N, 4), np.float32))
+    early = np.zeros(1, np.int64)
+    lib.h_features_geom(N, Cn, W, H, p(means3D), p(op), p(sc), p(rot), p(vm), p(pm), float(kw["tanfovx"]), float(kw["tanfovy"]), p(feats),
+                        p(bgc), p(g), p(ga), p(out), p(alpha), p(radii), p(gr["means2D"]), p(gr["means3D"]), p(gr["opacities"]),
+                        p(gr["scales"]), p(gr["rotations"]), p(early))
+    return gr, out, alpha, radii, int(early[0])
+
+
+def early_pixels(name):
+    """Number of pixels of the scene whose front-to-back walk ended (T (1 - alpha) < 1e-4) before the end of their tile's list, from the
+    ORACLE's state alone: its n_contrib, final_T and the tile ranges of its reference rectangles.  The first entry behind a pixel's
+    last contributor that passes the power / alpha tests can only be the entry that ended the walk."""
+    c, g, cam = scene(name)
+    W, H = c["W"], c["H"]
+    f = oracle.forward(**common.scene_kwargs(g, cam, W, H))
+    s = f.saved
+    x, y = s["xy"][:, 0].astype(np.float64), s["xy"][:, 1].astype(np.float64)
+    A, B, Cc, op = (s["conic_opacity"][:, k].astype(np.float64) for k in range(4))
+    rad = f.radii.astype(np.float64)
+    gx, gy = (W + 15) // 16, (H + 15) // 16
+    rx0 = np.clip(np.trunc((x - rad) / 16), 0, gx); rx1 = np.clip(np.trunc((x + rad + 15) / 16), 0, gx)
+    ry0 = np.clip(np.trunc((y - rad) / 16), 0, gy); ry1 = np.clip(np.trunc((y + rad + 15) / 16), 0, gy)
+    n_contrib, final_T = s["n_contrib"].reshape(H, W), s["final_T"].reshape(H, W)
+    n = 0
+    for ty in range(gy):
+        for tx in range(gx):
+            ids = np.nonzero((f.radii > 0) & (rx0 <= tx) & (tx < rx1) & (ry0 <= ty) & (ty < ry1))[0]
+            order = ids[np.argsort(s["depth"][ids], kind="stable")]
+            for py in range(ty * 16, min(H, ty * 16 + 16)):
+                for px in range(tx * 16, min(W, tx * 16 + 16)):
+                    for j in order[n_contrib[py, px]:]:
+                        dx, dy = x[j] - px, y[j] - py
+                        power = -0.5 * (A[j] * dx * dx + Cc[j] * dy * dy) - B[j] * dx * dy
+                        alpha = min(0.99, op[j] * math.exp(min(power, 0.0)))
+                        if power <= 0 and alpha >= 1.0 / 255.0:
+                            assert final_T[py, px] * (1.0 - alpha) < 1.0001e-4
+                            n += 1
+                            break
+    return n
+
+
+RAW = ("_xyz", "_opacity", "_scaling", "_rotation")
+
+
+def depth_loss_maps(H, W, seed=5):
+    rs = np.random.RandomState(seed)
+    return rs.randn(H, W), rs.randn(H, W)
+
+
+def dense_depth_reference(name):
+    """{dtype name: {raw parameter: gradient}} of  sum(depth gd + alpha ga),  depth = num / alpha.clamp_min(1e-6),  by the dense autograd
+    twin (oracle/torch_dense.py) rendering colors_precomp = [z(means3D), 1, 0] from the model's RAW parameters through its activations,
+    in float64 and in float32."""
+    from oracle import torch_dense
+    c, g, cam = scene(name)
+    W, H = c["W"], c["H"]
+    gd, ga = depth_loss_maps(H, W)
+    out = {}
+    for dd in (torch.float64, torch.float32):
+        raw = {n: getattr(g, n).to(dd).detach().clone().requires_grad_() for n in RAW}
+        vm = cam.world_view_transform.to(dd)
+        z = raw["_xyz"] @ vm[:3, 2:3] + vm[3, 2]
+        color, _radii, _cnt = torch_dense.render_dense(
+            means3D=raw["_xyz"], means2D=torch.zeros(c["N"], 3, dtype=dd), opacities=torch.sigmoid(raw["_opacity"]), W=W, H=H,
+            tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.zeros(3, dtype=dd), viewmatrix=vm,
+            projmatrix=cam.full_proj_transform.to(dd), campos=cam.camera_center.to(dd),
+            colors_precomp=torch.cat([z, torch.ones_like(z), torch.zeros_like(z)], 1), scales=torch.exp(raw["_scaling"]),
+            rotations=torch.nn.functional.normalize(raw["_rotation"]))
+        depth = color[0] / color[1].clamp_min(1e-6)
+        (depth * torch.from_numpy(gd).to(dd) + color[1] * torch.from_numpy(ga).to(dd)).sum().backward()
+        out["float64" if dd == torch.float64 else "float32"] = {n: raw[n].grad.numpy().astype(np.float64) for n in RAW}
+    return out
