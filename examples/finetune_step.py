@@ -9,7 +9,10 @@ with this repo's drop-in pieces: gaussian_renderer.render (HIP rasterizer, gette
 loss_utils.l1_loss / ssim (one fused HIP launch for both).  The optimizer is torch.optim.Adam as in the reference
 (scene/gaussian_model.py:training_setup).
 
-    python examples/finetune_step.py [--n-gaussians 3000000] [--iters 100] [--fused-adam | --hip-adam]
+    python examples/finetune_step.py [--n-gaussians 3000000] [--iters 100] [--fused-adam | --hip-adam | --hip-adam-visible]
+
+--hip-adam-visible: every step updates only the Gaussians its view saw (HipAdam.step(visible=), lg_adam_step_rows); rows outside the
+view keep parameter and moments, which is not dense Adam.  The scene's visible fraction per view is printed.
 """
 import argparse
 import os
@@ -34,9 +37,11 @@ def main():
     ap.add_argument("--lambda-dssim", type=float, default=0.2)     # arguments/__init__.py
     ap.add_argument("--fused-adam", action="store_true", help="what `python -m lightgaussian_amd.run --fused-adam` switches on")
     ap.add_argument("--hip-adam", action="store_true", help="what `python -m lightgaussian_amd.run --hip-adam` switches on: one lg_adam_step launch per step")
+    ap.add_argument("--hip-adam-visible", action="store_true", help="what `python -m lightgaussian_amd.run --hip-adam=visible` switches on: "
+                    "one lg_adam_step_rows launch per step over the rows the step's view saw")
     args = ap.parse_args()
-    if args.fused_adam and args.hip_adam:
-        raise SystemExit("--fused-adam and --hip-adam exclude each other")
+    if args.fused_adam + args.hip_adam + args.hip_adam_visible > 1:
+        raise SystemExit("--fused-adam, --hip-adam and --hip-adam-visible exclude each other")
     dev = torch.device("cuda", 0)
     truth = syn.make_gaussians(args.n_gaussians).to(dev)
     cams = [syn.orbit_camera(k, args.views, args.width, args.height).to(dev) for k in range(args.views)]
@@ -56,6 +61,14 @@ def main():
     if args.hip_adam:
         from lightgaussian_amd import run as lg_run
         lg_run.hip_adam(True)
+    step_render = render
+    if args.hip_adam_visible:
+        from lightgaussian_amd import run as lg_run
+        lg_run.hip_adam(True, visible=True)
+        step_render = lg_run.recording_render()                 # render() that also records visibility_filter for the next step
+        with torch.no_grad():
+            fr = [float(render(c, g, pipe, bg)["visibility_filter"].float().mean()) for c in cams]
+        print(f"visible fraction per view: mean {sum(fr) / len(fr):.3f} (min {min(fr):.3f}, max {max(fr):.3f})")
     opt = torch.optim.Adam([{"params": [g._xyz], "lr": 1.6e-6}, {"params": [g._features_dc], "lr": 2.5e-3},
                             {"params": [g._features_rest], "lr": 2.5e-3 / 20.0}, {"params": [g._opacity], "lr": 0.05},
                             {"params": [g._scaling], "lr": 0.005}, {"params": [g._rotation], "lr": 0.001}], lr=0.0, eps=1e-15)
@@ -65,7 +78,7 @@ def main():
     t0 = time.perf_counter()
     for it in range(args.iters):
         k = it % args.views
-        pkg = render(cams[k], g, pipe, bg)
+        pkg = step_render(cams[k], g, pipe, bg)
         image = pkg["render"]
         Ll1 = l1_loss(image, gts[k])
         loss = (1.0 - args.lambda_dssim) * Ll1 + args.lambda_dssim * (1.0 - ssim(image, gts[k]))
@@ -81,6 +94,11 @@ def main():
     n = min(args.views, args.iters)
     print(f"{args.iters} iterations, {args.n_gaussians} Gaussians, {args.width}x{args.height}: {dt / args.iters * 1e3:.2f} ms/iteration "
           f"(render fwd+bwd + L1/SSIM + optimizer {which}); mean loss first {n} iterations {first / n:.5f} -> last {n} {last / n:.5f}")
+    if args.hip_adam_visible:
+        from lightgaussian_amd import dp
+        st = dp.stats()
+        print(f"masked steps {st['adam_visible_steps']}, dense fallbacks {st['adam_dense_fallbacks']}")
+        which += " step(visible=)"
     assert last < first, "the loss did not go down"
 
 

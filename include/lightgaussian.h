@@ -377,6 +377,26 @@ typedef struct lg_adam_tensor {
 int lg_adam_step(int32_t num_tensors, const lg_adam_tensor* tensors /* host */, double beta1, double beta2, double eps,
                  uint32_t flags, void* stream);
 
+/* lg_adam_step over the rows a byte mask names (a view's visibility_filter, or the union of several views'): a tensor [rows, ...] of
+ * row_len = numel / rows elements per row is stepped with `rows` mask bytes.
+ *   row whose byte is non-zero   every element takes exactly lg_adam_step's arithmetic, with the same host-side constants; bias
+ *                                correction uses the entry's own `step`
+ *   row whose byte is zero       param, exp_avg and exp_avg_sq keep their bits: no moment decay, no weight decay in either form, and
+ *                                the row's gradient is never read (a NaN there changes nothing)
+ * This is NOT dense Adam, where an unseen row coasts on its momentum.  An entry with row_mask == NULL is a dense entry: lg_adam_step's
+ * update inside the same launch (rows is not looked at).  row_mask has byte alignment; no byte outside [row_mask, row_mask + rows) is
+ * read.  A 16-byte access wholly in unseen rows is neither loaded nor stored.  Same table by value, LG_ADAM_MAX_TENSORS entries per
+ * launch, same flags; LG_FLAG_PROFILE records one "adam_rows" entry per launch.
+ * LG_ERR_INVALID_ARGUMENT, before any device call: every case of lg_adam_step, and with a row_mask rows < 1, numel not a multiple of
+ * rows, a row of more than 2^31 - 1 elements. */
+typedef struct lg_adam_rows_tensor {
+    lg_adam_tensor t;
+    const uint8_t* row_mask;           /* device, `rows` bytes, non-zero = step the row; NULL = dense entry */
+    int64_t rows;
+} lg_adam_rows_tensor;
+int lg_adam_step_rows(int32_t num_tensors, const lg_adam_rows_tensor* tensors /* host */, double beta1, double beta2, double eps,
+                      uint32_t flags, void* stream);
+
 /* --- densification: view statistics and clone / split / prune ---------------------------------------
  * GaussianModel.add_densification_stats and densify_and_prune (scene/gaussian_model.py:602-761, 784-788) for float32 device tensors.
  * lg_densify_stats, one launch, no read-back: for every row i with update_filter[i] != 0

@@ -42,7 +42,7 @@ EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scr
            "lg_debug_sort_orphan", "lg_debug_last_contributor", "lg_debug_tile_lists", "lg_geom_visible_offset",
            "lg_sh_grad_from_rgb", "lg_debug_view_meta", "lg_vq_ema_scratch_bytes", "lg_vq_ema_step", "lg_vq_colors",
            "lg_vq_code_index_bytes", "lg_vq_code_index_scratch_bytes", "lg_vq_code_index", "lg_vq_colors_bwd_scratch_bytes",
-           "lg_vq_colors_bwd", "lg_adam_step", "lg_densify_scratch_bytes", "lg_densify_stats", "lg_densify_plan", "lg_densify_rows",
+           "lg_vq_colors_bwd", "lg_adam_step", "lg_adam_step_rows", "lg_densify_scratch_bytes", "lg_densify_stats", "lg_densify_plan", "lg_densify_rows",
            "lg_features_scratch_bytes", "lg_blend_features", "lg_blend_features_backward", "lg_backward_features_scratch_bytes",
            "lg_backward_features"]
 
@@ -71,6 +71,10 @@ class lg_stats(C.Structure):
 class lg_adam_tensor(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
                 ("numel", C.c_int64), ("lr", C.c_double), ("weight_decay", C.c_double), ("step", C.c_int64)]
+
+
+class lg_adam_rows_tensor(C.Structure):
+    _fields_ = [("t", lg_adam_tensor), ("row_mask", C.c_void_p), ("rows", C.c_int64)]
 
 
 class lg_densify_tensor(C.Structure):
@@ -165,6 +169,8 @@ def load():
                                      C.c_uint32, vp]
     lib.lg_adam_step.restype = C.c_int
     lib.lg_adam_step.argtypes = [C.c_int32, P(lg_adam_tensor), C.c_double, C.c_double, C.c_double, C.c_uint32, vp]
+    lib.lg_adam_step_rows.restype = C.c_int
+    lib.lg_adam_step_rows.argtypes = [C.c_int32, P(lg_adam_rows_tensor), C.c_double, C.c_double, C.c_double, C.c_uint32, vp]
     lib.lg_densify_scratch_bytes.restype = C.c_size_t; lib.lg_densify_scratch_bytes.argtypes = [C.c_int32]
     lib.lg_densify_stats.restype = C.c_int
     lib.lg_densify_stats.argtypes = [C.c_int32, vp, vp, vp, vp, vp, vp, C.c_uint32, vp]

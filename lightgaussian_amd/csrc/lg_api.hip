@@ -16,7 +16,8 @@
 //   lg_vq_color.h    lg_vq_colors: per-Gaussian colours of a VecTree-compressed model (fp16 row table + slot) through the same lg_sh_to_rgb as K1
 //   lg_vq_color_bwd.h lg_vq_code_index / lg_vq_colors_bwd: its backward -- per-row gradients of the row table (ordered segmented sum over a
 //                    per-model inverted index for the codebook rows) and the colour part of dL/dxyz
-//   lg_adam.h        lg_adam_step: one Adam / AdamW step over all parameter tensors of the model in one launch (table by value, dwordx4)
+//   lg_adam.h        lg_adam_step: one Adam / AdamW step over all parameter tensors of the model in one launch (table by value, dwordx4);
+//                    lg_adam_step_rows: the same step over the rows a byte mask names (row index: lg_adam_rows.h)
 //   lg_densify.h     lg_densify_stats / lg_densify_plan / lg_densify_rows: view statistics and clone / split / prune of densify_and_prune
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound)
 //   lg_features.h    lg_features_fwd / _bwd / _gather: C further per-Gaussian channels blended over the lists a forward left, and dL/dfeatures
@@ -1033,6 +1034,81 @@ extern "C" int lg_adam_step(int32_t num_tensors, const lg_adam_tensor* tensors, 
         a.bc2_sqrt[k] = (float)sqrt(1.0 - pow(beta2, (double)x.step));
         a.decay[k] = decoupled ? (float)(1.0 - x.lr * x.weight_decay) : (float)x.weight_decay;
         if ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 15) == 0) a.vec_mask |= 1u << k;
+        wgs += need;
+    }
+    if (filled > 0) return launch();
+    return LG_OK;
+}
+
+// lg_adam_step with a byte mask of rows per entry (lg_adam_rows_kernel): the checks, the host-side constants and the split into
+// launches of lg_adam_step, plus the row geometry of the masked entries
+extern "C" int lg_adam_step_rows(int32_t num_tensors, const lg_adam_rows_tensor* tensors, double beta1, double beta2, double eps,
+                                 uint32_t flags, void* stream_p)
+{
+    if (num_tensors < 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: num_tensors < 0");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: betas must lie in [0, 1)");
+    if (num_tensors > 0 && !tensors) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: missing tensor table");
+    for (int t = 0; t < num_tensors; t++) {
+        const lg_adam_tensor& x = tensors[t].t;
+        if (x.numel < 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: numel < 0");
+        if (x.step < 1) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: step < 1 (the step being taken counts from 1)");
+        if (x.numel == 0) continue;                     // skipped: its pointers, its mask and its rows are not looked at
+        if (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq)
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: null param / grad / exp_avg / exp_avg_sq with numel > 0");
+        if ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 3) != 0)
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: float32 tensors must be 4-byte aligned");
+        if ((x.numel + LG_ADAM_SPAN - 1) / LG_ADAM_SPAN > 0x7FFFFFFFll)
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: tensor beyond 2^31 - 1 spans");
+        if (!tensors[t].row_mask) continue;             // dense entry: rows is not looked at
+        const int64_t rows = tensors[t].rows;
+        if (rows < 1) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: rows < 1 with a row_mask");
+        if (x.numel % rows != 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: numel is not a multiple of rows");
+        if (x.numel / rows > (int64_t)LG_ADAM_MAX_ROW_LEN) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: a row beyond 2^31 - 1 elements");
+    }
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = false, prof = flags & LG_FLAG_PROFILE, decoupled = flags & LG_ADAM_DECOUPLED_WD;
+    LgAdamRowsTable r;
+    LgAdamTable& a = r.a;
+    int filled = 0;
+    uint32_t wgs = 0;
+    auto reset = [&]() {
+        memset(&r, 0, sizeof(r));
+        for (int k = 0; k < LG_ADAM_MAX_TENSORS; k++) { a.first_wg[k] = 0xFFFFFFFFu; r.row_len[k] = 1; }
+        a.one_minus_beta1 = (float)(1.0 - beta1); a.beta2 = (float)beta2; a.one_minus_beta2 = (float)(1.0 - beta2); a.eps = (float)eps;
+        filled = 0; wgs = 0;
+    };
+    auto launch = [&]() -> int {
+        ProfScope ps(prof, "adam_rows", stream);
+        if (decoupled) lg_adam_rows_kernel<true><<<wgs, LG_ADAM_THREADS, 0, stream>>>(r);
+        else lg_adam_rows_kernel<false><<<wgs, LG_ADAM_THREADS, 0, stream>>>(r);
+        KCHECK("lg_adam_rows_kernel");
+        return LG_OK;
+    };
+    reset();
+    for (int t = 0; t < num_tensors; t++) {
+        const lg_adam_tensor& x = tensors[t].t;
+        if (x.numel == 0) continue;
+        const uint32_t need = (uint32_t)((x.numel + LG_ADAM_SPAN - 1) / LG_ADAM_SPAN);
+        if (filled == LG_ADAM_MAX_TENSORS || (filled > 0 && wgs + need > 0x7FFFFFFFu)) {
+            const int rc = launch();
+            if (rc != LG_OK) return rc;
+            reset();
+        }
+        const int k = filled++;
+        a.param[k] = x.param; a.grad[k] = x.grad; a.exp_avg[k] = x.exp_avg; a.exp_avg_sq[k] = x.exp_avg_sq;
+        a.numel[k] = x.numel;
+        a.first_wg[k] = wgs;
+        // lg_adam_step's constants: the three scalars in double, each rounded once to float
+        a.step_size[k] = (float)(x.lr / (1.0 - pow(beta1, (double)x.step)));
+        a.bc2_sqrt[k] = (float)sqrt(1.0 - pow(beta2, (double)x.step));
+        a.decay[k] = decoupled ? (float)(1.0 - x.lr * x.weight_decay) : (float)x.weight_decay;
+        if ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 15) == 0) a.vec_mask |= 1u << k;
+        if (tensors[t].row_mask) {
+            r.row_mask[k] = tensors[t].row_mask;
+            r.row_len[k] = (uint32_t)(x.numel / tensors[t].rows);
+            r.row_rcp[k] = lg_adam_row_rcp(r.row_len[k]);
+            r.row_thr[k] = lg_adam_row_thr(r.row_len[k]);
+        }
         wgs += need;
     }
     if (filled > 0) return launch();

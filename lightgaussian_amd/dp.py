@@ -46,7 +46,7 @@ import torch.distributed as dist
 from . import parallel
 
 _STATE = {"installed": [], "group": None, "visible": {}, "lock": threading.Lock(), "steps": 0, "rows": 0, "dense_steps": 0,
-          "sinks": {}, "sh_steps": 0, "wire_bytes": 0, "sh_wire_bytes": 0, "mask_prev": None, "overlap": None, "stepped": {}}
+          "adam_visible_steps": 0, "adam_dense_fallbacks": 0, "sinks": {}, "sh_steps": 0, "wire_bytes": 0, "sh_wire_bytes": 0, "mask_prev": None, "overlap": None, "stepped": {}}
 # optimizer group name (scene/gaussian_model.py:204-211) -> attribute the fused rasterizer reports its gradient under
 _GROUP_OF = {"_xyz": "xyz", "_features_dc": "f_dc", "_features_rest": "f_rest", "_opacity": "opacity", "_scaling": "scaling", "_rotation": "rotation"}
 
@@ -252,6 +252,20 @@ def _take_visible(params):
     return hit
 
 
+def take_visible_for_step(params, closure=None):
+    """run.py --hip-adam=visible: the union of the views rendered with grad since the last step of the optimizer over `params`, for
+    HipAdam.step(visible=) -- the same record the visible-rows exchange reads -- or None: nothing was recorded (renders under
+    no_grad, a closure that has yet to render, a model without _xyz), or a densify / prune has replaced the tensors since and no
+    parameter with a gradient has the mask's row count.  None is the dense step; both outcomes are counted (stats())."""
+    vis = _take_visible(params) if closure is None else None
+    if vis is not None and vis.dtype not in (torch.bool, torch.uint8):
+        vis = vis != 0
+    if vis is not None and not any(p.grad is not None and p.dim() >= 1 and p.shape[0] == vis.shape[0] for p in params):
+        vis = None
+    _STATE["adam_visible_steps" if vis is not None else "adam_dense_fallbacks"] += 1
+    return vis
+
+
 def exchange_gradients(optimizer, check=None, force=None):
     """Average the gradients of the parameter groups of `optimizer` over the ranks (in place), right before its step().
 
@@ -357,6 +371,10 @@ def wrap_optimizer(optimizer):
     inner = optimizer.step
 
     def step(*a, **kw):
+        if kw.get("visible") is not None:
+            # (refused before anything is exchanged: every rank would have to step the union of all ranks' views)
+            raise RuntimeError("step(visible=) on a data-parallel optimizer (dp.wrap_optimizer): the replicas stay identical only under "
+                               "the union of the ranks' visibility, which is not exchanged; take the dense step")
         # (configure(force=True): exchange at world size 1 too -- the RCCL code path of a 1-GPU box, tests/test_gpu_dp_runner.py)
         exchange_gradients(optimizer)
         out = inner(*a, **kw)
@@ -504,8 +522,9 @@ def uninstall():
 
 
 def stats():
-    """Counters of the exchanges so far: steps, rows exchanged (visible mode), steps that fell back to the dense all-reduce."""
-    return {"steps": _STATE["steps"], "rows_exchanged": _STATE["rows"], "dense_steps": _STATE["dense_steps"],
+    """Counters of the exchanges so far: steps, rows exchanged (visible mode), steps that fell back to the dense all-reduce; and of
+    run.py --hip-adam=visible: optimizer steps masked by the recorded visibility, steps that took the dense step instead."""
+    return {"adam_visible_steps": _STATE["adam_visible_steps"], "adam_dense_fallbacks": _STATE["adam_dense_fallbacks"], "steps": _STATE["steps"], "rows_exchanged": _STATE["rows"], "dense_steps": _STATE["dense_steps"],
             "rank1_sh_steps": _STATE["sh_steps"], "overlapped_steps": _STATE.get("overlap_steps", 0), "bytes_on_wire": _STATE["wire_bytes"], "sh_bytes_on_wire": _STATE["sh_wire_bytes"]}
     # (bytes_on_wire: what a ring moves through this rank -- 2 (w - 1) / w of the payload for an all-reduce, payload x w for the
     #  all-gather of dRGB (own block sent once, w - 1 blocks received); an estimate from the tensor sizes, not a counter)

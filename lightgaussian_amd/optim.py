@@ -16,9 +16,19 @@ with step() replaced:
     ineligible  amsgrad / maximize / capturable / differentiable, a tensor lr, a non-float32, sparse or non-contiguous parameter,
                 gradient or moment: torch's own step, unchanged, and one warning per optimizer that names the reason
     CPU         raises: there is no CPU fallback
+    visible=    step(visible=mask), opt-in: ONE lg_adam_step_rows launch that steps only the rows a view saw.  `mask` is a contiguous
+                bool / uint8 CUDA tensor [N] (render()'s visibility_filter; the union of several views is `a.clone() | b`), read in
+                place.  Every parameter with a gradient and shape[0] == N is masked, all others are dense entries of the same launch
+                (no parameter with N rows: ValueError).  A row whose byte is non-zero takes exactly the dense arithmetic, bias
+                correction by the tensor's own step count, which advances once per call as always; a row whose byte is zero keeps
+                the bits of param, exp_avg and exp_avg_sq -- no moment decay, no weight decay in either form, its gradient never
+                read.  This is NOT dense Adam, where an unseen row coasts on its momentum.  State, hooks, version counters and
+                state_dict are those of the dense step.  An ineligible configuration raises RuntimeError here: torch's dense step
+                is never taken silently in place of a masked one.
 
 hip_step_class(cls) / convert(opt) make the HIP-stepping subclass of any Adam subclass (run.hip_adam uses them on the optimizers
-the unmodified trainers construct).  set_profile(True) records the launches under "adam" (_lib.profile_read)."""
+the unmodified trainers construct).  set_profile(True) records the launches under "adam" ("adam_rows" for step(visible=);
+_lib.profile_read)."""
 import warnings
 
 import torch
@@ -76,8 +86,23 @@ def _ineligible_tensor(t, what):
     return None
 
 
+def _check_visible(visible):
+    """Why `visible` cannot be the row mask of lg_adam_step_rows, or None."""
+    if not torch.is_tensor(visible):
+        return f"visible must be a tensor, not {type(visible).__name__}"
+    if visible.dtype not in (torch.bool, torch.uint8):
+        return f"a {str(visible.dtype).replace('torch.', '')} mask (bool or uint8: one byte per row)"
+    if visible.dim() != 1:
+        return f"a {visible.dim()}-D mask (one byte per row: [N])"
+    if not visible.is_cuda:
+        return f"a mask on {visible.device}"
+    if not visible.is_contiguous():
+        return "a non-contiguous mask"
+    return None
+
+
 class _HipStep:
-    """Mix-in in front of torch.optim.Adam (or a subclass of it): step() through lg_adam_step."""
+    """Mix-in in front of torch.optim.Adam (or a subclass of it): step() through lg_adam_step; step(visible=) through lg_adam_step_rows."""
 
     def _lg_fallback(self, reason, closure):
         if not self.__dict__.get("_lg_warned", False):
@@ -86,12 +111,26 @@ class _HipStep:
         base = next(c for c in type(self).__mro__ if "step" in c.__dict__ and not issubclass(c, _HipStep))
         return _torch_step(base)(self, closure)
 
-    def step(self, closure=None):
+    def _lg_ineligible(self, why, closure, visible):
+        if visible is not None:
+            raise RuntimeError(f"{type(self).__name__}.step(visible=): {why} is outside lg_adam_step_rows, and torch's dense step is not "
+                               "taken in place of a masked one")
+        return self._lg_fallback(why, closure)
+
+    def step(self, closure=None, *, visible=None):
         _refuse_cpu(_flat_params(self))
+        if visible is not None:
+            why = _check_visible(visible)
+            if why is not None:
+                raise RuntimeError(f"{type(self).__name__}.step(visible=): {why}")
+            rows = visible.shape[0]
+            if not any(p.grad is not None and p.dim() >= 1 and p.shape[0] == rows for p in _flat_params(self)):
+                raise ValueError(f"{type(self).__name__}.step(visible=): the mask has {rows} rows and no parameter with a gradient has "
+                                 f"{rows} as its leading dimension")
         for group in self.param_groups:
             why = _ineligible_group(group)
             if why is not None:
-                return self._lg_fallback(why, closure)
+                return self._lg_ineligible(why, closure, visible)
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -109,8 +148,10 @@ class _HipStep:
                         why = "a moment on another device"
                 if why is None and p.grad.device != p.device:
                     why = "a gradient on another device"
+                if why is None and visible is not None and p.dim() >= 1 and p.shape[0] == visible.shape[0] and p.device != visible.device:
+                    why = f"a mask on {visible.device} for a parameter on {p.device}"
                 if why is not None:
-                    self._lg_fallback(why, None)            # (the closure has run)
+                    self._lg_ineligible(why, None, visible)  # (the closure has run)
                     return loss
                 work.append((group, p))
         if not work:
@@ -131,13 +172,17 @@ class _HipStep:
                                                   float(group["weight_decay"]), int(state["step"].item())))
         lib = _lib.load()
         for (index, beta1, beta2, eps, decoupled), entries in calls.items():
-            table = (_lib.lg_adam_tensor * len(entries))()
-            for row, (p, g, m, v, lr, wd, step) in zip(table, entries):
+            table = ((_lib.lg_adam_tensor if visible is None else _lib.lg_adam_rows_tensor) * len(entries))()
+            for entry, (p, g, m, v, lr, wd, step) in zip(table, entries):
+                row = entry if visible is None else entry.t
                 row.param, row.grad, row.exp_avg, row.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
                 row.numel, row.lr, row.weight_decay, row.step = p.numel(), lr, wd, step
+                if visible is not None and p.dim() >= 1 and p.shape[0] == visible.shape[0]:     # (else a dense entry of the same launch)
+                    entry.row_mask, entry.rows = visible.data_ptr(), visible.shape[0]
             flags = (_lib.ADAM_DECOUPLED_WD if decoupled else 0) | (_lib.FLAG_PROFILE if _PROFILE[0] else 0)
             with torch.cuda.device(index):
-                _lib.check(lib.lg_adam_step(len(entries), table, beta1, beta2, eps, flags, torch.cuda.current_stream().cuda_stream))
+                call = lib.lg_adam_step if visible is None else lib.lg_adam_step_rows
+                _lib.check(call(len(entries), table, beta1, beta2, eps, flags, torch.cuda.current_stream().cuda_stream))
             torch.autograd.graph.increment_version([t for e in entries for t in e[:1] + e[2:4]])
         return loss
 

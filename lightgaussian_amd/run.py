@@ -17,6 +17,12 @@
     python -m lightgaussian_amd.run --hip-adam /path/to/prune_finetune.py ...
         (opt-in, excludes --fused-adam: the trainers' torch.optim.Adam / AdamW instance becomes the subclass of its own class whose
          step() is one lg_adam_step launch over all parameter tensors -- hip_adam() below, lightgaussian_amd/optim.py)
+    python -m lightgaussian_amd.run --hip-adam=visible /path/to/prune_finetune.py ...
+        (--hip-adam, and every step updates only the Gaussians the renders since the previous step saw: render() records its
+         visibility_filter per model, step() becomes step(visible=the union) -- one lg_adam_step_rows launch; rows no view saw keep
+         parameter and moments bit for bit, which is NOT dense Adam.  A step without a recorded visibility, or after a densify /
+         prune replaced the tensors, is the dense step and is counted: dp.stats()["adam_dense_fallbacks"].  Excludes --fused-adam
+         and --distributed: replicas would need the union of the ranks' views)
     python -m lightgaussian_amd.run --hip-densify /path/to/train_densify_prune.py ...
         (opt-in: GaussianModel.add_densification_stats is one lg_densify_stats launch without a host sync, GaussianModel.densify_and_prune
          one plan + one row-writing launch with a single 32-byte read-back -- hip_densify() below, lightgaussian_amd/densify.py)
@@ -66,7 +72,7 @@ import sys
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _PATCHED = []          # (owner object, attribute name, original value) in patch order
 _REPORT = {}
-_DP_RENDER = {}        # the visibility-recording render() of a data-parallel run (one object, so that patching stays idempotent)
+_DP_RENDER = {}        # the visibility-recording render() of a data-parallel or --hip-adam=visible run (one object, so that patching stays idempotent)
 
 
 def _rebind_everywhere(old, new):
@@ -314,8 +320,17 @@ def _reference_vq_modules():
     return found
 
 
-def patch_reference(verbose=False, data_parallel=False):
-    """data_parallel=True (run.py --distributed): additionally hang lightgaussian_amd.dp on Scene / GaussianModel and record the
+def recording_render():
+    """lightgaussian_amd.gaussian_renderer.render wrapped by dp.wrap_render: every grad-mode render also records its visibility per
+    model (dp.note_render), for the gradient exchange of a data-parallel run and for hip_adam(visible=True).  One object per process."""
+    from . import dp
+    from . import gaussian_renderer as lg_gr
+    return _DP_RENDER.setdefault("fn", dp.wrap_render(lg_gr.render))
+
+
+def patch_reference(verbose=False, data_parallel=False, record_visibility=False):
+    """record_visibility=True (run.py --hip-adam=visible): render() is recording_render().
+    data_parallel=True (run.py --distributed): additionally hang lightgaussian_amd.dp on Scene / GaussianModel and record the
     visibility of every render() for the gradient exchange in front of optimizer.step().
     Import the reference's modules (they must be importable: run from / put on sys.path the reference checkout, with this
     repo on the path for the `diff_gaussian_rasterization` / `simple_knn` shims) and rebind the symbols listed in the module
@@ -324,10 +339,7 @@ def patch_reference(verbose=False, data_parallel=False):
     from . import loss_utils as lg_loss
     gr = _module("gaussian_renderer")
     if gr is not None:
-        render = lg_gr.render
-        if data_parallel:
-            from . import dp
-            render = _DP_RENDER.setdefault("fn", dp.wrap_render(lg_gr.render))
+        render = recording_render() if (data_parallel or record_visibility) else lg_gr.render
         _set(gr, "render", render, "gaussian_renderer.render")
         _set(gr, "count_render", lg_gr.count_render, "gaussian_renderer.count_render")
     lu = _module("utils.loss_utils")
@@ -406,14 +418,37 @@ def fused_adam(enable=True):
 _HIP_ADAM_INIT = {}
 
 
-def hip_adam(enable=True):
-    """run.py --hip-adam (opt-in, like fused_adam() and instead of it): every torch.optim.Adam -- AdamW included, which subclasses it --
+def _step_visible(optimizer):
+    """optimizer.step() := step(visible=the union of the views recording_render() saw since the last step); the dense step when there
+    is none (dp.take_visible_for_step).  An explicit visible= of the caller is passed through.  Idempotent."""
+    if getattr(optimizer, "_lg_step_visible", False):
+        return optimizer
+    from . import dp
+    inner = optimizer.step
+
+    def step(closure=None, **kw):
+        if kw.get("visible") is None:
+            kw["visible"] = dp.take_visible_for_step([p for g in optimizer.param_groups for p in g["params"]], closure)
+        return inner(closure, **kw)
+
+    optimizer.step = step
+    optimizer._lg_step_visible = True
+    return optimizer
+
+
+def hip_adam(enable=True, visible=False):
+    """visible=True (run.py --hip-adam=visible): additionally every step of such an optimizer is step(visible=...) over the rows the
+    renders through recording_render() saw since its previous step (_step_visible above; lightgaussian_amd/optim.py for what a
+    masked step is).
+    run.py --hip-adam (opt-in, like fused_adam() and instead of it): every torch.optim.Adam -- AdamW included, which subclasses it --
     created while this is active, over CUDA float parameters and without an explicit fused / foreach argument, is turned into the
     HIP-stepping subclass of its own class (lightgaussian_amd.optim.convert): still an instance of the class the trainer asked for,
     same param_groups, same state layout as torch's default step (step on the CPU, exp_avg / exp_avg_sq by key -- the prune / densify
     surgery and the checkpoints work unchanged), but step() is ONE lg_adam_step launch over all parameter tensors.  Optimizers over
     CPU tensors, or with an explicit fused / foreach, stay plain torch.  hip_adam(False) puts torch's constructor back."""
     import torch
+    if enable:
+        _HIP_ADAM_INIT["visible"] = bool(visible)
     if enable and "orig" not in _HIP_ADAM_INIT:
         orig = torch.optim.Adam.__init__
         _HIP_ADAM_INIT["orig"] = orig
@@ -427,9 +462,12 @@ def hip_adam(enable=True):
                 if flat and all(torch.is_tensor(p) and p.is_cuda and p.is_floating_point() for p in flat):
                     from . import optim
                     optim.convert(self)
+                    if _HIP_ADAM_INIT.get("visible"):
+                        _step_visible(self)
 
         torch.optim.Adam.__init__ = __init__
     elif not enable and "orig" in _HIP_ADAM_INIT:
+        _HIP_ADAM_INIT.pop("visible", None)
         torch.optim.Adam.__init__ = _HIP_ADAM_INIT.pop("orig")
 
 
@@ -513,7 +551,7 @@ def _redirect_model_path(argv, rank):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    distributed = no_patch = verbose = adam = hip = lazy = no_timing = densify = False
+    distributed = no_patch = verbose = adam = hip = hip_visible = lazy = no_timing = densify = False
     backend = "nccl"
     dp_overlap = False
     weight_policy = None
@@ -531,6 +569,8 @@ def main(argv=None):
             adam = True
         elif flag == "--hip-adam":
             hip = True
+        elif flag == "--hip-adam=visible":
+            hip = hip_visible = True
         elif flag == "--hip-densify":
             densify = True
         elif flag == "--lazy-loss":
@@ -544,9 +584,14 @@ def main(argv=None):
         elif flag.startswith("--backend="):       # gloo: CPU tests of the launcher with a stand-in trainer (the rasterizer has no CPU path)
             backend = flag.split("=", 1)[1]
         else:
-            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --hip-densify --lazy-loss --no-iter-timing --weight-policy=NAME, then the script and ITS arguments)")
+            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --hip-adam=visible --hip-densify --lazy-loss --no-iter-timing --weight-policy=NAME, then the script and ITS arguments)")
     if adam and hip:
-        raise SystemExit("lightgaussian_amd.run: --fused-adam and --hip-adam exclude each other (one optimizer step per run)")
+        raise SystemExit(f"lightgaussian_amd.run: --fused-adam and {'--hip-adam=visible' if hip_visible else '--hip-adam'} exclude each other (one optimizer step per run)")
+    if hip_visible and distributed:
+        raise SystemExit("lightgaussian_amd.run: --hip-adam=visible and --distributed exclude each other (the replicas would have to step the "
+                         "union of the ranks' views, which is not exchanged)")
+    if hip_visible and no_patch:
+        raise SystemExit("lightgaussian_amd.run: --hip-adam=visible and --no-patch exclude each other (the visibility is recorded by the patched render())")
     if not argv:
         raise SystemExit(__doc__)
     script = os.path.abspath(argv[0])
@@ -592,7 +637,7 @@ def main(argv=None):
     if adam:
         fused_adam(True)
     if hip:
-        hip_adam(True)
+        hip_adam(True, visible=hip_visible)
     if lazy:
         # l1_loss() / ssim() hand out lazy scalars (loss_utils.LazyLoss): the trainers' loss line costs no kernels and their
         # per-iteration loss.item() does not wait for the backward.  This (main) thread only; the trainers are single-threaded.
@@ -604,7 +649,7 @@ def main(argv=None):
     if not no_patch:
         # --distributed is DATA-PARALLEL training (lightgaussian_amd.dp): a camera shard per rank, the gradients averaged over the
         # ranks in front of every optimizer.step(), prune_list sharded by camera; the ranks stay bit-identical replicas of one model
-        report = patch_reference(verbose=verbose, data_parallel=distributed)
+        report = patch_reference(verbose=verbose, data_parallel=distributed, record_visibility=hip_visible)
         missing = [k for k, v in report.items() if "skipped" in v]
         if missing and verbose:
             print(f"[lightgaussian_amd.run] not patched (module not importable): {missing}", file=sys.stderr)

@@ -6,6 +6,12 @@
     hip       lightgaussian_amd.optim.HipAdamW: one lg_adam_step launch  (what `run.py --hip-adam` switches on)
 
     python tools/adam_bench.py [--n 1000000 3000000] [--steps 200] [--blocks 7] [--only-hip]
+    python tools/adam_bench.py --visible-frac 1.0 0.7 0.5 0.25 0.1 [--visible-pattern random|blocks]
+
+--visible-frac F [F ...]: the legs are `hip` (the dense lg_adam_step) and, per fraction, `rows F`: HipAdamW.step(visible=mask), one
+lg_adam_step_rows launch, with F of the rows visible -- `random` rows, or contiguous `blocks` of 4096 rows (a view's Morton-ordered
+neighbourhoods).  All legs alternate in the same run; GB/s of a masked leg is the DENSE byte model over its time (what the dense
+step would have needed), so the figure to read is the time.
 
 Gradients: one third of the rows exactly zero (Gaussians outside the view), the rest normal.  Every leg steps its own copy of the
 parameters with the same gradients.  Per size: `--blocks` alternating blocks of `--steps` steps per leg after a warm-up, each block
@@ -44,6 +50,16 @@ def make_leg(kind, params0, grads):
     return opt
 
 
+def make_mask(N, frac, pattern, dev):
+    gen = torch.Generator(device=dev).manual_seed(int(frac * 1000) + 17)
+    if frac >= 1.0:
+        return torch.ones(N, dtype=torch.bool, device=dev)
+    if pattern == "random":
+        return torch.rand(N, device=dev, generator=gen) < frac
+    nb = (N + 4095) // 4096
+    return (torch.rand(nb, device=dev, generator=gen) < frac).repeat_interleave(4096)[:N].contiguous()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1_000_000, 3_000_000])
@@ -52,9 +68,15 @@ def main():
     ap.add_argument("--blocks", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--only-hip", action="store_true")
+    ap.add_argument("--visible-frac", type=float, nargs="+", default=[])
+    ap.add_argument("--visible-pattern", choices=("random", "blocks"), default="random")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
-    kinds = ("hip",) if args.only_hip else ("torch", "fused", "hip")
+    kinds = ("hip",) if (args.only_hip or args.visible_frac) else ("torch", "fused", "hip")
+    rows_kinds = {f"rows {f:g}": f for f in args.visible_frac}
+    if args.only_hip and rows_kinds:
+        kinds = ()
+    kinds = kinds + tuple(rows_kinds)
     print(f"library build {_lib.build_id()}, span {optim.SPAN}, {args.blocks} blocks of {args.steps} steps per leg")
     for N in args.n:
         gen = torch.Generator(device=dev).manual_seed(N)
@@ -65,7 +87,11 @@ def main():
             g[0::3] = 0.0
             grads[name] = g
         numel = sum(t.numel() for t in params0.values())
-        legs = {k: make_leg(k, params0, grads) for k in kinds}
+        legs = {k: make_leg("hip" if k in rows_kinds else k, params0, grads) for k in kinds}
+        masks = {k: make_mask(N, f, args.visible_pattern, dev) for k, f in rows_kinds.items()}
+        for k, m in masks.items():
+            print(f"  {k}: {args.visible_pattern}, {float(m.float().mean()):.4f} of {N} rows visible")
+            legs[k].step = (lambda o, m: lambda: type(o).step(o, visible=m))(legs[k], m)
         for opt in legs.values():
             for _ in range(args.warmup):
                 opt.step()
@@ -85,8 +111,8 @@ def main():
         for k in kinds:
             t = times[k]
             med = statistics.median(t)
-            print(f"  {k:6s} {med:.3f} ms ({min(t):.3f}..{max(t):.3f})   {gb / med * 1e3:7.1f} GB/s ({gb / max(t) * 1e3:.1f}..{gb / min(t) * 1e3:.1f})")
-        print(json.dumps({"adam_bench": {"N": N, "numel": numel, "steps": args.steps, "blocks": args.blocks, "build": _lib.build_id(),
+            print(f"  {k:9s} {med:.3f} ms ({min(t):.3f}..{max(t):.3f})   {gb / med * 1e3:7.1f} GB/s ({gb / max(t) * 1e3:.1f}..{gb / min(t) * 1e3:.1f})")
+        print(json.dumps({"adam_bench": {"N": N, "numel": numel, "steps": args.steps, "blocks": args.blocks, "build": _lib.build_id(), "visible_pattern": args.visible_pattern if rows_kinds else None,
                                          "ms_per_step": {k: [round(x, 4) for x in times[k]] for k in kinds}}}))
         del legs, params0, grads
         torch.cuda.empty_cache()
