@@ -111,6 +111,32 @@ def orbit_camera(k, n_views, width, height, radius=6.0, fovx_deg=60.0, target=(0
     return make_camera(R, T, width, height, FoVx, FoVy)
 
 
+def look_at_camera(eye, target, width, height, roll_deg=0.0, fovx_deg=60.0):
+    """Camera at `eye` looking at `target`, any pitch, then rolled by `roll_deg` about the viewing axis: the general pose of a
+    captured view (orbit_camera only ever yields a rotation about world y).  Conventions of orbit_camera: down = +y, R = camera-to-world
+    with the camera axes as columns, T = -R^T eye, FoVy from the focal length.  Roll: x' = cos x + sin y, y' = -sin x + cos y."""
+    c = np.asarray(eye, dtype=np.float64)
+    f = np.asarray(target, dtype=np.float64) - c
+    nf = np.linalg.norm(f)
+    if not nf > 0.0:
+        raise ValueError("look_at_camera: eye and target coincide")
+    f /= nf
+    down = np.array([0.0, 1.0, 0.0])
+    x = np.cross(down, f)
+    nx = np.linalg.norm(x)
+    if nx < 1e-9:
+        raise ValueError("look_at_camera: the viewing axis is parallel to world y (no level x axis to roll from)")
+    x /= nx
+    y = np.cross(f, x)
+    cr, sr = math.cos(math.radians(roll_deg)), math.sin(math.radians(roll_deg))
+    x, y = cr * x + sr * y, -sr * x + cr * y
+    R = np.stack([x, y, f], axis=1)  # camera-to-world, columns = camera axes
+    T = -R.transpose() @ c
+    FoVx = math.radians(fovx_deg)
+    FoVy = focal2fov(fov2focal(FoVx, width), height)
+    return make_camera(R, T, width, height, FoVx, FoVy)
+
+
 @dataclass
 class SyntheticGaussians:
     """Raw (pre-activation) parameters with GaussianModel's getter semantics."""

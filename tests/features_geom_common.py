@@ -27,10 +27,15 @@ SCENES = {
 }
 
 
-def scene(name):
+def scene(name, camera=None):
+    """camera: None = the orbit camera every scene was chosen under, or a name of tests/camera_common.py (pitched, rolled, inside)."""
     c = SCENES[name]
     g = syn.make_gaussians(c["N"], seed=3, extent=(1.5, 1.0, 1.5), log_scale_mean=math.log(c["scale"]), opacity_mean=c["opm"])
-    cam = syn.orbit_camera(1, 7, c["W"], c["H"], radius=4.0)
+    if camera is None:
+        cam = syn.orbit_camera(1, 7, c["W"], c["H"], radius=4.0)
+    else:
+        import camera_common
+        cam = camera_common.camera(camera, c["W"], c["H"])
     return c, g, cam
 
 
@@ -45,16 +50,16 @@ def loss_inputs(N, Cn, H, W, bg=True, seed=11):
 _REF = {}
 
 
-def reference(name, Cn, bg, kind, color_bg=(0.1, 0.2, 0.3)):
+def reference(name, Cn, bg, kind, color_bg=(0.1, 0.2, 0.3), camera=None):
     """{dtype name: {tensor: float64 array}} for float64 and float32 oracles: the sum over channel triples of oracle.backward -- the
     feature columns (and a column of ones with background 0 for alpha) padded to whole triples as colors_precomp, plus, for kind
     "c" in kind, the backward of the scene's own SH colours over color_bg.  kind: the maps in the loss, letters of "oac" (out, alpha,
-    colour).  Computed once per key."""
+    colour).  camera: as for scene().  Computed once per key."""
     name = name.replace("_seg64", "")         # the same scene: the segment length is the rasterizer's business
-    key = (name, Cn, bool(bg), kind)
+    key = (name, Cn, bool(bg), kind, camera)
     if key in _REF:
         return _REF[key]
-    c, g, cam = scene(name)
+    c, g, cam = scene(name, camera)
     N, W, H = c["N"], c["W"], c["H"]
     F, bgf, dout, dalpha, dcolor = loss_inputs(N, Cn, H, W, bg)
     cols, grads, bgs = [], [], []
@@ -196,12 +201,17 @@ def depth_loss_maps(H, W, seed=5):
     return rs.randn(H, W), rs.randn(H, W)
 
 
-def dense_depth_reference(name):
+_DEPTH_REF = {}
+
+
+def dense_depth_reference(name, camera=None):
     """{dtype name: {raw parameter: gradient}} of  sum(depth gd + alpha ga),  depth = num / alpha.clamp_min(1e-6),  by the dense autograd
     twin (oracle/torch_dense.py) rendering colors_precomp = [z(means3D), 1, 0] from the model's RAW parameters through its activations,
-    in float64 and in float32."""
+    in float64 and in float32; plus "maps": the float64 twin's (numerator, alpha, radii).  camera: as for scene().  Computed once per key."""
     from oracle import torch_dense
-    c, g, cam = scene(name)
+    if (name, camera) in _DEPTH_REF:
+        return _DEPTH_REF[(name, camera)]
+    c, g, cam = scene(name, camera)
     W, H = c["W"], c["H"]
     gd, ga = depth_loss_maps(H, W)
     out = {}
@@ -209,7 +219,7 @@ def dense_depth_reference(name):
         raw = {n: getattr(g, n).to(dd).detach().clone().requires_grad_() for n in RAW}
         vm = cam.world_view_transform.to(dd)
         z = raw["_xyz"] @ vm[:3, 2:3] + vm[3, 2]
-        color, _radii, _cnt = torch_dense.render_dense(
+        color, radii, _cnt = torch_dense.render_dense(
             means3D=raw["_xyz"], means2D=torch.zeros(c["N"], 3, dtype=dd), opacities=torch.sigmoid(raw["_opacity"]), W=W, H=H,
             tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.zeros(3, dtype=dd), viewmatrix=vm,
             projmatrix=cam.full_proj_transform.to(dd), campos=cam.camera_center.to(dd),
@@ -218,4 +228,26 @@ def dense_depth_reference(name):
         depth = color[0] / color[1].clamp_min(1e-6)
         (depth * torch.from_numpy(gd).to(dd) + color[1] * torch.from_numpy(ga).to(dd)).sum().backward()
         out["float64" if dd == torch.float64 else "float32"] = {n: raw[n].grad.numpy().astype(np.float64) for n in RAW}
+        if dd == torch.float64:
+            out["maps"] = (color[0].detach().numpy(), color[1].detach().numpy(), radii.numpy())
+    _DEPTH_REF[(name, camera)] = out
     return out
+
+
+def assert_depth_maps(num, alpha, ref_maps, what=""):
+    """A float32 depth numerator / alpha / depth = num / max(alpha, 1e-6) against the float64 twin's maps.  Numerator and alpha: the 1e-5
+    of a float32 render against the float64 one (absolute for alpha in [0, 1], relative to max |num| for the numerator: the bounds of
+    tests/test_features_geom_host.py).  Depth: first-order propagation of those two bounds through the quotient,
+    |d depth| <= (|d num| + |depth| |d alpha|) / alpha, asserted where alpha >= 1e-3 (where first order holds: |d alpha| / alpha <= 1e-2)."""
+    num, alpha = np.asarray(num, np.float64), np.asarray(alpha, np.float64)
+    n64, a64, _r = ref_maps
+    scale = np.abs(n64).max()
+    e_n, e_a = np.abs(num - n64).max(), np.abs(alpha - a64).max()
+    print(f"{what}: numerator max error {e_n:.3e} (max |num| {scale:.3e}), alpha max error {e_a:.3e}")
+    assert scale > 0 and e_n <= 1e-5 * scale and e_a <= 1e-5
+    ok = a64 >= 1e-3
+    d, d64 = num / np.maximum(alpha, 1e-6), n64 / np.maximum(a64, 1e-6)
+    bound = 1.01 * (1e-5 * scale + np.abs(d64) * 1e-5) / np.maximum(a64, 1e-3)
+    worst = float((np.abs(d - d64)[ok] / bound[ok]).max())
+    print(f"{what}: depth error at most {worst:.3f}x its bound over {int(ok.sum())} pixels")
+    assert ok.sum() > 100 and worst <= 1.0

@@ -235,3 +235,61 @@ def test_depth_and_alpha_gradients_match_the_float64_autograd_twin():
         err = fg.rel_err(gr[n], r)
         print(f"{n}: rel err against the dense twin {err:.3e}")
         assert np.abs(r).max() > 0 and err < 1e-4, f"{n}: {err}"
+
+
+CAMERA = "pitched_rolled"     # tests/camera_common.py: every entry of the view rotation is non-zero, the depth gradient gets a y component
+
+
+def test_whole_image_replay_under_a_pitched_and_rolled_camera():
+    """The reference side of tests/test_gpu_features_geom.py's camera test, verified here first: the replay of lg_feature_bwd_step and the
+    per-Gaussian chain against the summed oracle backward under a camera whose view rotation has no zero entry."""
+    name = "N300_70x45"
+    c, g, cam = fg.scene(name, CAMERA)
+    N, W, H = c["N"], c["W"], c["H"]
+    kw = common.scene_kwargs(g, cam, W, H)
+    assert np.abs(kw["viewmatrix"][:3, :3]).min() >= 0.03
+    F, bgf, dout, dalpha, _dc = fg.loss_inputs(N, CN, H, W, True)
+    gr, out, alpha, radii, _early = fg.harness_grads(kw, F, bgf, dout, dalpha)
+    out0, alpha0, radii0, _n = features_common.blend_features(kw, F, bgf)
+    assert np.array_equal(out, out0) and np.array_equal(alpha, alpha0) and np.array_equal(radii, radii0)
+    assert (radii > 0).sum() >= 100
+    fg.assert_within(gr, fg.reference(name, CN, True, "oa", camera=CAMERA), f"{name} {CAMERA}")
+    # the orbit reference is another key of the cache, not this one
+    assert fg.reference(name, CN, True, "oa", camera=CAMERA) is not fg.reference(name, CN, True, "oa")
+    for n in fg.GEOMETRY:
+        assert not gr[n][radii == 0].any(), n
+        assert np.abs(gr[n]).max() > 0, n
+
+
+def test_depth_map_and_gradient_under_a_pitched_and_rolled_camera():
+    """fg.dense_depth_reference (the GPU test's reference: gradients with respect to the RAW parameters, through the activations) against
+    the harness chain of test_depth_and_alpha_gradients_match_the_float64_autograd_twin, carried through the activations by hand in
+    float64: exp for scales, sigmoid for opacities, normalisation for rotations.  With this camera vm[6] is not 0: z depends on world y."""
+    name = "N300_70x45"
+    c, g, cam = fg.scene(name, CAMERA)
+    N, W, H = c["N"], c["W"], c["H"]
+    ref = fg.dense_depth_reference(name, CAMERA)
+    gd, ga = fg.depth_loss_maps(H, W)
+    kw = common.scene_kwargs(g, cam, W, H)
+    vm32 = cam.world_view_transform.numpy().astype(np.float32)
+    assert abs(float(vm32[1, 2])) >= 0.03
+    zf = (kw["means3D"].astype(np.float32) @ vm32[:3, 2:3] + vm32[3, 2]).astype(np.float32)
+    out, alpha, radii_h, _n = features_common.blend_features(kw, zf)
+    assert np.array_equal(radii_h, ref["maps"][2])
+    fg.assert_depth_maps(out[0], alpha, ref["maps"], f"{name} {CAMERA}")
+    a64, n64 = alpha.astype(np.float64), out[0].astype(np.float64)
+    ac = np.maximum(a64, 1e-6)
+    dout = (gd / ac)[None].astype(np.float32)
+    dalpha = (ga - np.where(a64 > 1e-6, gd * n64 / (ac * ac), 0.0)).astype(np.float32)
+    gr = fg.harness_grads(kw, zf, None, dout, dalpha)[0]
+    dF = features_common.blend_features(kw, zf, dL_dout=dout)[4]
+    g_xyz = gr["means3D"].astype(np.float64) + dF * vm32[:3, 2].astype(np.float64)[None]
+    s = g._scaling.double().exp().numpy(); o = torch.sigmoid(g._opacity.double()).numpy(); r = g._rotation.double().numpy()
+    nr = np.linalg.norm(r, axis=1, keepdims=True); q = r / nr
+    g_rot = gr["rotations"].astype(np.float64)
+    got = {"_xyz": g_xyz, "_opacity": gr["opacities"].astype(np.float64) * o * (1.0 - o), "_scaling": gr["scales"].astype(np.float64) * s,
+           "_rotation": (g_rot - q * (q * g_rot).sum(1, keepdims=True)) / nr}
+    assert np.abs(got["_xyz"][:, 1]).max() > 0
+    fg.assert_within(got, ref, f"depth {CAMERA}", names=fg.RAW)
+    # the default camera is another key, with today's values
+    assert fg.dense_depth_reference(name) is not ref

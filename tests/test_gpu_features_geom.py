@@ -238,3 +238,53 @@ def test_the_default_call_still_treats_the_geometry_as_a_constant():
     assert out.requires_grad and not alpha.requires_grad and not color.requires_grad
     out.sum().backward()
     assert case.feats.grad is not None and case.t["means3D"].grad is None and case.t["opacities"].grad is None
+
+
+CAMERA = "pitched_rolled"     # tests/camera_common.py: every entry of the view rotation is non-zero (every orbit camera has four zeros and a one)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_geometry_gradients_under_a_pitched_and_rolled_camera(mode):
+    """A feature + alpha loss under a camera whose view rotation has no zero entry: lg_backward_features' chain back to means3D, scales
+    and rotations multiplies by entries that are exactly 0 or 1 in every other test of this file.  The reference is verified on the host
+    by tests/test_features_geom_host.py."""
+    name, Cn = "N300_70x45", 17
+    cam = fg.scene(name, CAMERA)[2]
+    assert float(cam.world_view_transform[:3, :3].abs().min()) >= 0.03
+    case = Case(name, Cn, True, mode, cam=cam)
+    maps = case.maps()
+    radii = maps[3]
+    assert int((radii > 0).sum()) >= 100
+    g1 = case.grads(case.loss(maps, "oa"))
+    for n in fg.GEOMETRY + ("features",):
+        v = g1[n]
+        assert v is not None and bool(torch.isfinite(v).all()) and float(v.abs().max()) > 0, n
+        assert not v[radii == 0].any(), f"{n}: rows of Gaussians with radii == 0 must be exact zeros"
+    fg.assert_within(to_np(g1), fg.reference(name, Cn, True, "oa", COLOR_BG, camera=CAMERA), f"{name} {CAMERA} C={Cn} oa {mode}")
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_render_features_depth_under_a_pitched_and_rolled_camera(mode):
+    """The "depth" map and its gradient with respect to the raw parameters against the dense autograd twin.  vm[6] is not 0 here: the
+    view-space depth, and with it the gradient of a depth loss, has a world-y component for the first time."""
+    name = "N300_70x45"
+    c, g, cam = fg.scene(name, CAMERA)
+    W, H = c["W"], c["H"]
+    assert abs(float(cam.world_view_transform[1, 2])) >= 0.03
+    ref = fg.dense_depth_reference(name, CAMERA)
+    gd, ga = (torch.from_numpy(a).float().to(DEV) for a in fg.depth_loss_maps(H, W))
+    model = g.to(DEV)
+    for n in fg.RAW:
+        setattr(model, n, getattr(model, n).detach().clone().requires_grad_(True))
+    pkg = gaussian_renderer.render_features(cam.to(DEV), model, syn.PipelineParams(), "depth", geometry_grad=True, options=MODES[mode])
+    assert np.array_equal(pkg["radii"].cpu().numpy(), ref["maps"][2])
+    fg.assert_depth_maps(pkg["features"][0].detach().cpu().numpy(), pkg["alpha"].detach().cpu().numpy(), ref["maps"], f"{name} {CAMERA} {mode}")
+    assert same_bits(pkg["depth"].detach(), (pkg["features"] / pkg["alpha"].clamp_min(1e-6)).detach())
+    (pkg["depth"][0] * gd + pkg["alpha"] * ga).sum().backward()
+    got = {}
+    for n in fg.RAW:
+        v = getattr(model, n).grad
+        assert v is not None and bool(torch.isfinite(v).all()) and float(v.abs().max()) > 0, n
+        got[n] = v.cpu().numpy()
+    assert np.abs(got["_xyz"][:, 1]).max() > 0
+    fg.assert_within(got, ref, f"depth {CAMERA} {mode}", names=fg.RAW)

@@ -5,15 +5,16 @@ import numpy as np
 import pytest
 import torch
 
+import camera_common
 import common
 from common import syn
 from oracle import oracle, torch_dense
 
 
-def _dense_case(N, W, H, seed, precolor=False, precov=False, deg=3, big=False, opm=None):
-    g = syn.make_gaussians(N, sh_degree=3, seed=seed, extent=(1.5, 1.0, 1.5), log_scale_mean=math.log(0.15 if big else 0.05),
+def _dense_case(N, W, H, seed, precolor=False, precov=False, deg=3, big=False, opm=None, scale=None, cam=None):
+    g = syn.make_gaussians(N, sh_degree=3, seed=seed, extent=(1.5, 1.0, 1.5), log_scale_mean=math.log(scale or (0.15 if big else 0.05)),
                            opacity_mean=(opm if opm is not None else (1.0 if big else 0.0)))
-    cam = syn.orbit_camera(1, 7, W, H, radius=4.0)
+    cam = camera_common.camera(cam, W, H) if cam else syn.orbit_camera(1, 7, W, H, radius=4.0)
     dd = torch.float64
     t = dict(means3D=g.get_xyz.to(dd).requires_grad_(), opacities=g.get_opacity.to(dd).detach().requires_grad_(),
              W=W, H=H, tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.tensor([0.2, 0.5, 0.9], dtype=dd),
@@ -34,7 +35,9 @@ def _dense_case(N, W, H, seed, precolor=False, precov=False, deg=3, big=False, o
 
 @pytest.mark.parametrize("cfg", [dict(N=40, W=48, H=40, seed=1), dict(N=60, W=64, H=33, seed=2, precolor=True),
                                  dict(N=60, W=40, H=40, seed=3, precov=True, deg=2), dict(N=80, W=40, H=48, seed=4, deg=1, big=True),
-                                 dict(N=30, W=32, H=32, seed=5, deg=0, big=True), dict(N=150, W=32, H=32, seed=6, big=True, opm=3.0)],
+                                 dict(N=30, W=32, H=32, seed=5, deg=0, big=True), dict(N=150, W=32, H=32, seed=6, big=True, opm=3.0)]
+                         # general cameras (tests/camera_common.py): every entry of the view rotation is non-zero
+                         + [dict(N=60, W=48, H=40, seed=1, scale=0.08, cam=name) for name in camera_common.NAMES],
                          ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items()))
 def test_oracle_f64_matches_autograd_twin(cfg):
     t = _dense_case(**cfg)
@@ -48,6 +51,8 @@ def test_oracle_f64_matches_autograd_twin(cfg):
     gr = oracle.backward(f, gimg.numpy())
     assert np.abs(f.color - color.detach().numpy()).max() < 1e-12
     assert np.array_equal(f.radii, radii.numpy()) and np.array_equal(f.count, count.numpy())
+    if cfg.get("cam"):
+        assert np.abs(kwn["viewmatrix"][:3, :3]).min() > 0.03 and (f.radii > 0).sum() >= 5
     if cfg.get("opm") == 3.0:
         assert f.saved["final_T"].min() < 2e-4, "this case is meant to exercise early termination"
     grads = dict(t, means2D=means2D)

@@ -3,7 +3,9 @@
 Gaussians, depth slabs (long runs of equal sorted key bits), huge splats; hit counts / scores / radii / count-render image
 bit-identical to the float oracle, training render within 1e-5, gradients within max(1e-4, 3 x fp32-oracle noise floor) of the float64 oracle.
 Phase 2: getters inside the kernels against the literal getter pattern.  Phase 3 (LG_FUZZ_N3): the significance-only pass with the serial and
-the parallel long-tile walk at short segment lengths, counts and scores bit-identical to the oracle.  LG_FUZZ_FIRST: first trial number."""
+the parallel long-tile walk at short segment lengths, counts and scores bit-identical to the oracle.  LG_FUZZ_FIRST: first trial number.
+--cameras general (anywhere on the command line; default orbit, so old seeds reproduce): phase 1 and 3 draw eye, target, roll and field of
+view through synthetic.look_at_camera -- pitched, rolled, and in a third of the trials standing inside the scene's extent."""
 import math
 import os
 import sys
@@ -27,7 +29,31 @@ if os.environ.get("LG_FUZZ_LONG"):     # serial | auto | parallel: walk of multi
 if os.environ.get("LG_FUZZ_SYNC"):     # off | validated | nowait
     from lightgaussian_amd import rasterizer as _r
     _r.set_option("sync_free", {"off": False, "validated": "validated"}[os.environ["LG_FUZZ_SYNC"]])
-def make_trial(t):
+CAMERAS = "orbit"
+if __name__ == "__main__" and "--cameras" in sys.argv:
+    _i = sys.argv.index("--cameras")
+    CAMERAS = sys.argv[_i + 1]
+    del sys.argv[_i:_i + 2]
+    if CAMERAS not in ("orbit", "general"):
+        sys.exit("--cameras must be orbit or general")
+
+
+def general_camera(t, ext, W, H):
+    """Trial t's camera of --cameras general, from a stream of its own (the trial's other draws are those of the orbit trial)."""
+    rc = np.random.RandomState(4441 + 7919 * t)
+    ext = np.asarray(ext, np.float64)
+    target = rc.uniform(-0.5, 0.5, 3) * ext
+    if rc.rand() < 1.0 / 3.0:
+        eye = rc.uniform(-1.0, 1.0, 3) * ext                     # among the splats
+    else:
+        d = rc.randn(3); d[1] *= 0.6                             # mostly from the side, sometimes steeply from above or below
+        eye = target + d / np.linalg.norm(d) * rc.uniform(2.5, 7.0)
+    if np.linalg.norm(np.cross([0.0, 1.0, 0.0], target - eye)) < 1e-3 * np.linalg.norm(target - eye) or np.linalg.norm(target - eye) < 1e-3:
+        eye = eye + np.array([0.37, 0.0, 0.21])                  # (looking straight along world y has no level x axis)
+    return syn.look_at_camera(eye, target, W, H, roll_deg=float(rc.uniform(-180.0, 180.0)), fovx_deg=float(rc.uniform(35.0, 110.0)))
+
+
+def make_trial(t, cameras=None):
     """Trial t of phase 1: (kwargs for the rasterizer as torch tensors, the same as numpy, a description, the trial's RandomState --
     positioned where the gradient image is drawn next)."""
     rs = np.random.RandomState(777 + 7919 * t)          # per-trial stream: `only` reruns exactly one trial
@@ -37,12 +63,16 @@ def make_trial(t):
     deg = int(rs.randint(0, stored + 1))                 # r4: active degree <= stored degree (scene/gaussian_model.py:125-127)
     mod = float(rs.choice([1.0, 1.0, 0.5, 2.0, np.exp(rs.uniform(np.log(0.3), np.log(3.0)))]))   # r4: scaling_modifier (gaussian_renderer/__init__.py:58)
     scale = float(np.exp(rs.uniform(np.log(0.002), np.log(0.8))))
-    g = syn.make_gaussians(N, sh_degree=stored, seed=1000 + t, log_scale_mean=math.log(scale), opacity_mean=float(rs.uniform(-4, 3)),
-                           extent=(float(rs.uniform(0.3, 3)), float(rs.uniform(0.3, 2)), float(rs.uniform(0.3, 3))), log_scale_std=float(rs.uniform(0.1, 1.2)))
+    opm = float(rs.uniform(-4, 3))
+    ext = (float(rs.uniform(0.3, 3)), float(rs.uniform(0.3, 2)), float(rs.uniform(0.3, 3)))
+    g = syn.make_gaussians(N, sh_degree=stored, seed=1000 + t, log_scale_mean=math.log(scale), opacity_mean=opm, extent=ext,
+                           log_scale_std=float(rs.uniform(0.1, 1.2)))
     cam = syn.orbit_camera(int(rs.randint(0, 8)), 8, W, H, radius=float(rs.uniform(2.5, 7)))
     if rs.rand() < 0.25:   # depth slab in front of camera 0
         cam = syn.orbit_camera(0, 8, W, H, radius=5.0)
         g._xyz[:, 2] = float(rs.choice([0.0, 1e-6, 1e-4])) * torch.randn(N)
+    elif (cameras or CAMERAS) == "general":
+        cam = general_camera(t, ext, W, H)
     kw = common.scene_kwargs(g, cam, W, H, deg=stored, bg=tuple(rs.rand(3).astype(np.float32)), as_torch=True)
     kw["sh_degree"] = deg
     kw["scale_modifier"] = mod
@@ -185,6 +215,6 @@ for t in range(first, first + n3):
         bad3 += 1
         print(f"COUNT MISMATCH trial {t}: N={meta['N']} {meta['W']}x{meta['H']} S={S} wide={wide}: {', '.join(why)}")
 if __name__ == "__main__":
-    print(f"fuzz: trials {first}..{first + trials - 1}, {bad} mismatches; fused-getter phase: {n2} trials, {bad2} mismatches; "
+    print(f"fuzz ({CAMERAS} cameras): trials {first}..{first + trials - 1}, {bad} mismatches; fused-getter phase: {n2} trials, {bad2} mismatches; "
           f"significance-only phase: {n3} trials ({par_items} with multi-segment lists in the parallel walk, {fixups} exact fix-ups; {n4} per-hit-weight renders), {bad3} mismatches")
     sys.exit(1 if bad + bad2 + bad3 else 0)
