@@ -14,6 +14,9 @@
  * (rasterize_gaussians / count_gaussians / rasterize_gaussians_backward).  The entry points below
  * are what a binding of that path binds instead: plain device pointers, sizes and a stream --
  * no torch types.  INTEGRATION.md shows the ctypes stub.
+ * Beyond the reference's three: feature / depth / alpha maps over a view's tile lists (lg_blend_features, lg_backward_features) and the
+ * gradient with respect to the camera itself (lg_backward_camera: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos), which the reference's
+ * backward treats as a constant.
  *
  * Conventions
  *   - every pointer is a DEVICE pointer into memory owned by the caller, fp32 contiguous unless noted
@@ -482,6 +485,26 @@ int lg_backward_features(const lg_view* view, const lg_gaussians* g, const int32
                          float* dL_dmeans3D, float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales,
                          float* dL_drotations, float* dL_dcov3D, float* dL_dshs_rest, float* dL_dfeatures, void* scratch,
                          void* stream);
+
+/* --- camera pose gradients ---------------------------------------------------------------------------
+ * lg_backward_camera: dL/dviewmatrix [16], dL/dprojmatrix [16], dL/dcampos [3] of the loss whose backward has just run -- the
+ * backward treats lg_view.viewmatrix / projmatrix / campos as constants; this call differentiates with respect to them (pose
+ * refinement).  Call it AFTER lg_backward, lg_backward_chunked or lg_backward_features of the same view (same lg_view, lg_gaussians,
+ * radii, geom, binning, num_rendered), on the same stream, before `backward_scratch` -- the scratch buffer of that backward, which
+ * still holds the per-instance moment rows -- is reused.  Row-vector layout m[4 row + column], as the inputs.  Column 3 of the view
+ * matrix and column 2 of the projection matrix take no part in the forward: their gradients are exact zeros.  The published
+ * conventions of the backward hold here too (no gradient through the +-1.3 tan(fov) clamp, the 0.2 near plane or the radius).
+ * lg_camera_bwd (one lane per Gaussian) gathers each visible Gaussian's rows again, forms its 27 camera terms in float32 and sums them
+ * in float64 in a fixed order (wave butterfly, waves in order, one plain store per workgroup); lg_camera_reduce (one workgroup) adds
+ * the workgroup partials in a fixed order and rounds once to float32.  No atomics, no memset: bit-identical run to run.  A view the
+ * forward abandoned, a segment_length other than the forward's or a forward without LG_FLAG_SAVE_SH_JACOBIAN yield exact zeros, as
+ * lg_backward; N == 0 writes zeros.  SH inputs need LG_FLAG_SAVE_SH_JACOBIAN on the view (LG_ERR_INVALID_ARGUMENT otherwise): the
+ * camera centre enters through the view direction, whose Jacobian K1 saved.  The three outputs are required.
+ * scratch: lg_camera_scratch_bytes(N) device bytes.  Profile entries: "camera_bwd", "camera_reduce". */
+size_t lg_camera_scratch_bytes(int32_t N);
+int lg_backward_camera(const lg_view* view, const lg_gaussians* g, const int32_t* radii, const void* geom, const void* binning,
+                       int64_t num_rendered, const void* backward_scratch, float* dL_dviewmatrix, float* dL_dprojmatrix,
+                       float* dL_dcampos, void* scratch, void* stream);
 
 /* out[j] = (((rows[0][j] + rows[1][j]) + rows[2][j]) + ...) over V rows of n floats (row pitch row_stride floats): the
  * sequential in-place float accumulation of per-view scores in prune.py:144-155, in view order, as one launch. */

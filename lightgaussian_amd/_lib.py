@@ -44,7 +44,7 @@ EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scr
            "lg_vq_code_index_bytes", "lg_vq_code_index_scratch_bytes", "lg_vq_code_index", "lg_vq_colors_bwd_scratch_bytes",
            "lg_vq_colors_bwd", "lg_adam_step", "lg_adam_step_rows", "lg_densify_scratch_bytes", "lg_densify_stats", "lg_densify_plan", "lg_densify_rows",
            "lg_features_scratch_bytes", "lg_blend_features", "lg_blend_features_backward", "lg_backward_features_scratch_bytes",
-           "lg_backward_features"]
+           "lg_backward_features", "lg_camera_scratch_bytes", "lg_backward_camera"]
 
 
 class lg_view(C.Structure):
@@ -187,6 +187,9 @@ def load():
     lib.lg_backward_features.restype = C.c_int
     lib.lg_backward_features.argtypes = ([P(lg_view), P(lg_gaussians), vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp] + [vp] * 9
                                          + [vp, vp, vp])
+    lib.lg_camera_scratch_bytes.restype = C.c_size_t; lib.lg_camera_scratch_bytes.argtypes = [C.c_int32]
+    lib.lg_backward_camera.restype = C.c_int
+    lib.lg_backward_camera.argtypes = [P(lg_view), P(lg_gaussians), vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
     lib.lg_debug_sort_temp_bytes.restype = C.c_size_t; lib.lg_debug_sort_temp_bytes.argtypes = [C.c_int64]
     lib.lg_debug_sort_keys.restype = C.c_int
     lib.lg_debug_sort_keys.argtypes = [C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp]

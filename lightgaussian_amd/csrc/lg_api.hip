@@ -21,6 +21,7 @@
 //   lg_densify.h     lg_densify_stats / lg_densify_plan / lg_densify_rows: view statistics and clone / split / prune of densify_and_prune
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound)
 //   lg_features.h    lg_features_fwd / _bwd / _gather: C further per-Gaussian channels blended over the lists a forward left, and dL/dfeatures
+//   lg_camera.h      lg_camera_bwd<RAW> / lg_camera_reduce: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos from the rows a backward left (float64 ordered sums)
 //
 // Pipeline of one view:
 //   K1 project + EWA + SH->RGB + exact footprint culling  ->  K2 scan of instance counts, blocking read of R
@@ -47,6 +48,7 @@
 #include "lg_adam.h"
 #include "lg_densify.h"
 #include "lg_features.h"
+#include "lg_camera.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -596,6 +598,54 @@ extern "C" int lg_backward_chunked(const lg_view* v, const lg_gaussians* g, cons
 {
     return backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity,
                          dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest, scratch, stream_p, chunks, on_chunk, user);
+}
+
+// ---- camera pose gradients (lg_camera.h) ----
+extern "C" size_t lg_camera_scratch_bytes(int32_t N)
+{
+    const size_t nwg = ((size_t)(N > 0 ? N : 1) + LG_CAM_THREADS - 1) / LG_CAM_THREADS;
+    return align_up(nwg * LG_CAM_TERMS * sizeof(double));     // partials[workgroup][27]
+}
+
+extern "C" int lg_backward_camera(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const void* geom_p, const void* bin_p,
+                                  int64_t R, const void* backward_scratch, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos,
+                                  void* scratch, void* stream_p)
+{
+    int rc = check_args(v, g);
+    if (rc != LG_OK) return rc;
+    if (!dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_camera: the three gradient outputs are required");
+    if (!scratch) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_camera: missing scratch");
+    if (R < 0 || R >= (1ll << 30)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_camera: num_rendered out of range");
+    if (g->N > 0) {
+        if (!radii || !geom_p || !bin_p || !backward_scratch) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_camera: missing buffer");
+        if (g->shs && !(v->flags & LG_FLAG_SAVE_SH_JACOBIAN))
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_camera: SH inputs need LG_FLAG_SAVE_SH_JACOBIAN on the view (forward and backward)");
+    }
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE;
+    const int N = g->N;
+    const uint32_t nwg = N > 0 ? (uint32_t)(((size_t)N + LG_CAM_THREADS - 1) / LG_CAM_THREADS) : 0u;
+    double* partials = (double*)scratch;
+    if (N > 0) {
+        const ViewGeom q = view_geom(v, N);
+        GeomView geo = carve_geom(const_cast<void*>(geom_p), N);
+        BinView bin = carve_bin(const_cast<void*>(bin_p), R, q.W, q.H, q.S);
+        {
+            ProfScope ps(prof, "camera_bwd", stream);
+            auto kern = (v->flags & LG_FLAG_RAW_PARAMS) ? lg_camera_bwd<true> : lg_camera_bwd<false>;
+            kern<<<nwg, LG_CAM_THREADS, 0, stream>>>(N, g->M, v->sh_degree, q.W, q.H, v->tanfovx, v->tanfovy, v->scale_modifier, (uint32_t)R,
+                                                     v->viewmatrix, v->projmatrix, v->campos, g->means3D, g->shs, g->scales, g->rotations,
+                                                     g->cov3D_precomp, radii, geo.rec, geo.counters, bin.meta, (uint32_t)q.S, geo.touched,
+                                                     geo.offsets, reinterpret_cast<const float4*>(backward_scratch), geo.shjac, partials);
+        }
+        KCHECK("lg_camera_bwd");
+    }
+    {
+        ProfScope ps(prof, "camera_reduce", stream);
+        lg_camera_reduce<<<1, LG_CAM_THREADS, 0, stream>>>(nwg, partials, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos);
+    }
+    KCHECK("lg_camera_reduce");
+    return LG_OK;
 }
 
 extern "C" int lg_sh_grad_from_rgb(int32_t N, int32_t M, int32_t sh_degree, int32_t V, const float* means3D, const float* campos,

@@ -492,6 +492,77 @@ LG_HD void lg_backward_geom(const float* vm, const float* pm, float px, float py
     g.mean3D[0] = dmx; g.mean3D[1] = dmy; g.mean3D[2] = dmz;
 }
 
+// Camera terms of one Gaussian (lg_camera.h: lg_camera_bwd sums them over the visible Gaussians): what lg_backward_geom computes on
+// its way to dL/dmean3D and drops -- dt = dL/d(view-space mean) through the EWA Jacobian, dT = dL/d(T2 = J Wrot), the J entries, the
+// NDC gradient and the homogeneous divide -- chained to the camera instead of to the mean.  Row-vector layout m[4 k + c], p = the mean:
+//   t_c = sum_k p_k vm[4k+c] + vm[12+c],  T2[0][k] = J00 vm[4k] + J02 vm[4k+2],  T2[1][k] = J11 vm[4k+1] + J12 vm[4k+2]
+//     g_vm[4k+0] = p_k dtx + dT0k J00    g_vm[4k+1] = p_k dty + dT1k J11    g_vm[4k+2] = p_k dtz + dT0k J02 + dT1k J12    g_vm[12+c] = dt_c
+//   h_c = sum_k p_k pm[4k+c] + pm[12+c] (c = 0, 1, 3),  ndc = h_xy / (h_w + 1e-7):  dh = (gndx m_w, gndy m_w, -(mul1 gndx + mul2 gndy))
+//     g_pm[4k+c] = p_k dh_c              g_pm[12+c] = dh_c
+//   g_cp = -d,  d = the view-direction term lg_backward_sh_jac adds to dmean (zeros for colors_precomp)
+// out[27]: g_vm columns 0..2 of rows 0..3 (12), g_pm columns 0, 1, 3 of rows 0..3 (12), g_cp (3); column 3 of vm and column 2 of pm take
+// no part in the forward.  The lines up to dtz and the projection block are lg_backward_geom's, term for term (the clamped txc / tyc,
+// zeroed dtx / dty on clamped lanes, the 1e-7 in d2inv): duplicated, not shared, so that every existing kernel stays as it was compiled.
+// In real arithmetic  dL/dmean3D = vm[:3,:3] g_vm[3,:3] + pm[:3,:] g_pm[3,:] - g_cp  (tests/test_camera_host.py).
+#define LG_CAM_TERMS 27
+LG_HD void lg_backward_camera_terms(const float* vm, const float* pm, float px, float py, float pz, const float* S /*cov3D*/,
+                                    const float* acc, int W, int H, float tanfovx, float tanfovy, const float d[3], float* out /*[27]*/)
+{
+    const float fx = (float)W / (2.0f * tanfovx), fy = (float)H / (2.0f * tanfovy);
+    const float gndx = acc[0] * (0.5f * (float)W), gndy = acc[1] * (0.5f * (float)H);
+    float vx = vm[0] * px + vm[4] * py + vm[8] * pz + vm[12];
+    float vy = vm[1] * px + vm[5] * py + vm[9] * pz + vm[13];
+    float vz = vm[2] * px + vm[6] * py + vm[10] * pz + vm[14];
+    LgEwa e;
+    lg_ewa(vm, vx, vy, vz, fx, fy, 1.3f * tanfovx, 1.3f * tanfovy, e);
+    LgCov2D c2;
+    lg_cov2d(e.T2, S, c2);
+    const float a = c2.a, b = c2.b, c = c2.c;
+    const float gA = acc[2], gB = acc[3], gC = acc[4];
+    float denom = a * c - b * b;
+    float d2inv = 1.0f / (denom * denom + 0.0000001f);
+    float dL_da = 0.0f, dL_db = 0.0f, dL_dc = 0.0f;
+    if (d2inv != 0.0f) {
+        dL_da = d2inv * (-c * c * gA + b * c * gB + (denom - a * c) * gC);
+        dL_dc = d2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
+        dL_db = d2inv * (2.0f * b * c * gA - (denom + 2.0f * b * b) * gB + 2.0f * a * b * gC);
+    }
+    const float* U = c2.U; const float* V = c2.V;
+    float dT0[3] = { 2.0f * dL_da * U[0] + dL_db * V[0], 2.0f * dL_da * U[1] + dL_db * V[1], 2.0f * dL_da * U[2] + dL_db * V[2] };
+    float dT1[3] = { dL_db * U[0] + 2.0f * dL_dc * V[0], dL_db * U[1] + 2.0f * dL_dc * V[1], dL_db * U[2] + 2.0f * dL_dc * V[2] };
+    float dJ00 = dT0[0] * vm[0] + dT0[1] * vm[4] + dT0[2] * vm[8];
+    float dJ02 = dT0[0] * vm[2] + dT0[1] * vm[6] + dT0[2] * vm[10];
+    float dJ11 = dT1[0] * vm[1] + dT1[1] * vm[5] + dT1[2] * vm[9];
+    float dJ12 = dT1[0] * vm[2] + dT1[1] * vm[6] + dT1[2] * vm[10];
+    float tz = 1.0f / vz, tz2 = tz * tz, tz3 = tz2 * tz;
+    float dtx = (e.xclamp ? 0.0f : 1.0f) * (-fx * tz2 * dJ02);
+    float dty = (e.yclamp ? 0.0f : 1.0f) * (-fy * tz2 * dJ12);
+    float dtz = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2.0f * fx * e.txc) * tz3 * dJ02 + (2.0f * fy * e.tyc) * tz3 * dJ12;
+    // the J entries, exactly lg_ewa's expressions
+    const float J00 = fx / vz, J02 = -(fx * e.txc) / (vz * vz);
+    const float J11 = fy / vz, J12 = -(fy * e.tyc) / (vz * vz);
+    const float p[3] = { px, py, pz };
+    for (int k = 0; k < 3; k++) {
+        out[3 * k + 0] = p[k] * dtx + dT0[k] * J00;
+        out[3 * k + 1] = p[k] * dty + dT1[k] * J11;
+        out[3 * k + 2] = p[k] * dtz + dT0[k] * J02 + dT1[k] * J12;
+    }
+    out[9] = dtx; out[10] = dty; out[11] = dtz;
+    float hxm = pm[0] * px + pm[4] * py + pm[8] * pz + pm[12];
+    float hym = pm[1] * px + pm[5] * py + pm[9] * pz + pm[13];
+    float hwm = pm[3] * px + pm[7] * py + pm[11] * pz + pm[15];
+    float m_w = 1.0f / (hwm + 0.0000001f);
+    float mul1 = hxm * m_w * m_w, mul2 = hym * m_w * m_w;
+    const float dh[3] = { gndx * m_w, gndy * m_w, -(mul1 * gndx + mul2 * gndy) };
+    for (int k = 0; k < 3; k++) {
+        out[12 + 3 * k + 0] = p[k] * dh[0];
+        out[12 + 3 * k + 1] = p[k] * dh[1];
+        out[12 + 3 * k + 2] = p[k] * dh[2];
+    }
+    out[21] = dh[0]; out[22] = dh[1]; out[23] = dh[2];
+    out[24] = -d[0]; out[25] = -d[1]; out[26] = -d[2];
+}
+
 // dL/dSigma(packed) -> dL/dscale, dL/dquaternion.  Like the published implementation the
 // scale gradient carries no scale_modifier factor.
 LG_HD void lg_backward_cov3d(const float sc[3], float mod, const float q[4], const float dS[6], float dscale[3], float drot[4])

@@ -193,6 +193,8 @@ def blend_features(raster_settings, features, *, means3D, opacities, scales=None
         raise ValueError("blend_features runs on a colour forward: raster_settings.f_count must be False")
     if means2D is not None and not geometry_grad:
         raise ValueError("means2D receives the view-space gradient: it needs geometry_grad=True")
+    if _rasterizer.option_value("camera_grad", options):
+        raise NotImplementedError("camera_grad is not implemented for feature blending: use render() for the pose gradient")
     _check_features(features, bg_features)
     _rasterizer._check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
     if geometry_grad:

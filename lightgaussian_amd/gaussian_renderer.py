@@ -63,6 +63,10 @@ def _inputs(viewpoint_camera, pc, pipe, scaling_modifier, override_color):
     return means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp
 
 
+def _camera_grad(options):
+    return bool(_rasterizer.option_value("camera_grad", options))
+
+
 def _screenspace_points(pc):
     """Zero tensor whose .grad receives the 2D (NDC) mean gradients, gaussian_renderer/__init__.py:37-46.  The reference
     builds it as zeros(..., requires_grad=True) + 0 followed by retain_grad(); a plain leaf gets its .grad the same way
@@ -115,7 +119,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     With option fuse_getters (default True) and a GaussianModel carrying the reference's own activations, the getters
     are evaluated INSIDE the kernels from the raw parameters (render_fused: no torch.cat of the SH tensors, no
     activation kernels; same values to ~1e-7, gradients land on the raw parameters exactly as autograd would route
-    them).  set_option("fuse_getters", False) restores the reference's literal call pattern."""
+    them).  set_option("fuse_getters", False) restores the reference's literal call pattern.
+
+    options={"camera_grad": True}: the image is also differentiable with respect to the camera's own world_view_transform,
+    full_proj_transform and camera_center tensors, which are handed through as they are -- built under autograd (pose.PoseCamera),
+    the chain continues into the pose parameters.  Fused and unfused paths alike; compressed models are not supported."""
+    if isinstance(pc, (CompressedGaussians, TrainableCompressed)) and _camera_grad(options):
+        raise NotImplementedError("camera_grad is not implemented for compressed models: render pc.to_dense() instead")
     if isinstance(pc, TrainableCompressed) and override_color is None:
         return render_compressed_trainable(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, options=options)
     if isinstance(pc, CompressedGaussians) and override_color is None:
@@ -145,6 +155,8 @@ def render_compressed(viewpoint_camera, cg, pipe, bg_color: torch.Tensor, scalin
     them as colors_precomp -- the [N, 3 M] float32 SH tensor is never built.  Same result dict as render(), same image bits as
     render() of cg.to_dense() with fuse_getters off.  Forward-only: runs under torch.no_grad(), nothing requires grad (to train,
     use cg.to_dense()).  The Python-side alternates of `pipe` need the dense tensors and are refused."""
+    if _camera_grad(options):
+        raise NotImplementedError("camera_grad is not implemented for compressed models: render cg.to_dense() instead")
     if pipe.convert_SHs_python or pipe.compute_cov3D_python:
         raise NotImplementedError("convert_SHs_python / compute_cov3D_python need the dequantised tensors: render cg.to_dense() instead")
     with torch.no_grad():
@@ -158,6 +170,8 @@ def render_compressed_trainable(viewpoint_camera, tc, pipe, bg_color: torch.Tens
     """The grad-enabled twin of render_compressed for a vectree.TrainableCompressed: the same kernels on the same float16 rows
     (the image bits are render_compressed's), with autograd attached -- tc.colors() is differentiable (lg_vq_colors_bwd), the
     rasterizer returns dL/dcolors_precomp and the geometry gradients, viewspace_points stays attached for its .grad."""
+    if _camera_grad(options):
+        raise NotImplementedError("camera_grad is not implemented for compressed models: render tc.to_dense() instead")
     if pipe.convert_SHs_python or pipe.compute_cov3D_python:
         raise NotImplementedError("convert_SHs_python / compute_cov3D_python need the dequantised tensors: render tc.to_dense() instead")
     colors = tc.colors(viewpoint_camera.camera_center)
@@ -167,6 +181,8 @@ def render_compressed_trainable(viewpoint_camera, tc, pipe, bg_color: torch.Tens
 def count_render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, *, options=None):
     """render() + per-Gaussian hit count and Global Significance score (f_count=True).  options: as for render(), e.g.
     {"skip_color_in_count": True} for passes that only consume the counts / scores."""
+    if _camera_grad(options):
+        raise NotImplementedError("camera_grad is not implemented for count renders: use render()")
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, True), options=options)
     means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp = _inputs(
@@ -221,6 +237,8 @@ def render_features(viewpoint_camera, pc, pipe, features, bg_features=None, scal
     colours.  The result gains "viewspace_points", whose .grad is the view-space gradient densification reads.  Compressed models are
     not supported in this mode."""
     from .features import blend_features
+    if _camera_grad(options):
+        raise NotImplementedError("camera_grad is not implemented for render_features: use render() for the pose gradient")
     compressed = isinstance(pc, CompressedGaussians)
     if geometry_grad and isinstance(pc, (CompressedGaussians, TrainableCompressed)):
         raise NotImplementedError("render_features(geometry_grad=True) needs the dense tensors: pass pc.to_dense() instead")

@@ -44,7 +44,7 @@ class GaussianRasterizationSettings(NamedTuple):
 # the defaults: prune_list_sharded and backward_over_views pass what they need per call / per thread.
 _OPTIONS = {"weight_policy": _lib.WEIGHT_OPACITY, "fast_exp": True, "profile": False, "skip_color_in_count": False,
             "fuse_getters": True, "sync_free": "validated", "max_depth": 100.0, "capacity_margin": 1.25,
-            "segment_length": 0, "long_tiles": "auto", "count_long_tiles": "serial",
+            "segment_length": 0, "long_tiles": "auto", "count_long_tiles": "serial", "camera_grad": False,
             # cross-check switches of the tests: never needed in production, never read from the environment
             "sh_jacobian": True, "narrow_key": False, "sort_all_bits": False, "k1_lds": False, "count_wide_band": False}
 _PER_CALL_ONLY = ("pending", "tag", "status_override", "differentiated", "sh_grad_sink", "score_out", "count_sum")
@@ -73,6 +73,8 @@ def _validate(name, value):
         raise ValueError(f"long_tiles must be one of {_LONG_TILES}")
     if name == "count_long_tiles" and value not in ("serial", "parallel"):
         raise ValueError("count_long_tiles must be 'serial' or 'parallel'")
+    if name == "camera_grad" and not isinstance(value, bool):
+        raise ValueError("camera_grad must be True or False")
     if name == "segment_length" and (int(value) < 0 or (int(value) != 0 and (int(value) < 64 or int(value) % 64))):
         raise ValueError("segment_length must be 0 (library default, 512) or a multiple of 64")
 
@@ -121,6 +123,11 @@ def set_option(name, value):
               count_sum = a contiguous int32 [N] device tensor to which the view's gaussians_count is ADDED by the kernel that writes the
               score (lg_view.count_sum; not atomic: one view at a time per accumulator).  Together they are prune_list's
               `gaussian_list += ...; imp_list += ...` bookkeeping (prune.py:144-155) without a torch launch per view (prune_list_sharded);
+    camera_grad (default False): the render is also differentiated with respect to raster_settings.viewmatrix, .projmatrix and .campos
+              (pose refinement): the backward makes its usual lg_backward call, then lg_backward_camera on the same scratch (one more
+              gather of the gradient rows, float64 ordered sums: deterministic), and the three tensors receive [4,4], [4,4] and [3]
+              gradients; the per-Gaussian gradients are bit-identical to those with the option off.  Off: nothing changes.  Not
+              available for count renders (f_count), with sh_jacobian=False, or with a gradient-chunk hook / sh_grad_sink installed;
     count_wide_band: tests only -- LG_FLAG_COUNT_WIDE_BAND (the parallel long-tile count walk sends many more pixels through its exact fix-up);
     sh_jacobian / narrow_key / sort_all_bits / k1_lds: cross-check switches for the tests (K9 re-reads the SH coefficients instead
               of K1's saved direction Jacobian; the sort key laid out as if 40 bits were available; every key bit through the
@@ -529,6 +536,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                                 {k: v for k, v in (("means3D", g_means3D), ("shs", g_sh), ("colors_precomp", g_col if call.colors is not None else None), ("opacities", g_opac),
                                                    ("scales", g_sc), ("rotations", g_rot), ("cov3D_precomp", g_cov)) if v is not None})
             _lib.check(rc)
+            if ctx.opts["camera_grad"]:
+                ctx.cam_grads = _camera_backward(lib, call, radii, geom, binning, ctx.num_rendered, scratch, stream)
             if sink is not None:            # rgb_only backward: g_col holds dL/d(rgb of the SH expansion); the coefficient gradients are the sink's business
                 sink.add(g_col, call.cp, int(rs.sh_degree))
                 g_col = None
@@ -597,12 +606,118 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                                 {k: v for k, v in (("_xyz", g_xyz), ("_features_dc", g_dc), ("_features_rest", g_rest), ("_opacity", g_opac),
                                                    ("_scaling", g_sc), ("_rotation", g_rot)) if v is not None})
             _lib.check(rc)
+            if ctx.opts["camera_grad"]:
+                ctx.cam_grads = _camera_backward(lib, call, radii, geom, binning, ctx.num_rendered, scratch, stream)
             if sink is not None:
                 sink.add(g_rgb, call.cp, int(rs.sh_degree))
                 return g_xyz, g_means2D, None, None, g_opac, g_sc, g_rot, None, None
         if g_rest is None and ctx.rest_shape is not None:
             g_rest = torch.zeros(ctx.rest_shape, **f32)
         return g_xyz, g_means2D, g_dc, g_rest, g_opac, g_sc, g_rot, None, None
+
+
+def _camera_backward(lib, call, radii, geom, binning, num_rendered, scratch, stream):
+    """lg_backward_camera right behind the lg_backward call that filled `scratch`, on the same stream: (dL/dviewmatrix [4,4],
+    dL/dprojmatrix [4,4], dL/dcampos [3]) on the Gaussians' device."""
+    f32 = dict(dtype=torch.float32, device=call.dev)
+    g_vm, g_pm, g_cp = torch.empty((4, 4), **f32), torch.empty((4, 4), **f32), torch.empty((3,), **f32)
+    cam_scratch = torch.empty(lib.lg_camera_scratch_bytes(call.N), dtype=torch.uint8, device=call.dev)
+    rc = lib.lg_backward_camera(C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(geom), _ptr(binning), C.c_int64(num_rendered),
+                                _ptr(scratch), _ptr(g_vm), _ptr(g_pm), _ptr(g_cp), _ptr(cam_scratch), stream)
+    _lib.check(rc)
+    return g_vm, g_pm, g_cp
+
+
+def _camera_forward(ctx, cls, viewmatrix, projmatrix, campos, args):
+    # (the kernels read the camera through raster_settings, which holds these same tensors: they are inputs here for autograd's sake)
+    ctx.cam_like = tuple((t.device, t.dtype, tuple(t.shape)) for t in (viewmatrix, projmatrix, campos))
+    ctx.cam_empty = args[0].device if args[0].shape[0] == 0 else None      # an empty model: see _camera_empty_backward
+    return cls.forward(ctx, *args)
+
+
+def _camera_empty_backward(ctx):
+    """The camera gradients of an empty model (the plain backward has nothing to save and nothing to do there): lg_backward_camera
+    with N = 0 writes the zeros."""
+    lib = _lib.load()
+    rs, dev = ctx.raster_settings, ctx.cam_empty
+    view = _lib.lg_view(int(rs.image_height), int(rs.image_width), float(rs.tanfovx), float(rs.tanfovy), None, float(rs.scale_modifier), None, None,
+                        int(rs.sh_degree), None, 0, 0, int(ctx.opts["segment_length"]))
+    g = _lib.lg_gaussians(0, 0, None, None, None, None, None, None, None, None)
+    f32 = dict(dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ctx.cam_grads = (torch.empty((4, 4), **f32), torch.empty((4, 4), **f32), torch.empty((3,), **f32))
+        scratch = torch.empty(lib.lg_camera_scratch_bytes(0), dtype=torch.uint8, device=dev)
+        _lib.check(lib.lg_backward_camera(C.byref(view), C.byref(g), None, None, None, C.c_int64(0), None, _ptr(ctx.cam_grads[0]),
+                                          _ptr(ctx.cam_grads[1]), _ptr(ctx.cam_grads[2]), _ptr(scratch),
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return _camera_grads_out(ctx)
+
+
+def _camera_grads_out(ctx):
+    return tuple(g.to(device=dev, dtype=dt).reshape(shape) for g, (dev, dt, shape) in zip(ctx.cam_grads, ctx.cam_like))
+
+
+class _RasterizeGaussiansCamera(_RasterizeGaussians):
+    """_RasterizeGaussians whose inputs also include the camera (option camera_grad): raster_settings.viewmatrix, .projmatrix and
+    .campos in front of the usual ones.  The backward is the base class's -- which, with the option on, calls lg_backward_camera on
+    the scratch of its lg_backward call -- with the three camera gradients in front."""
+
+    @staticmethod
+    def forward(ctx, viewmatrix, projmatrix, campos, *args):
+        return _camera_forward(ctx, _RasterizeGaussians, viewmatrix, projmatrix, campos, args)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if ctx.cam_empty is not None:
+            return _camera_empty_backward(ctx) + (None,) * 10
+        out = _RasterizeGaussians.backward(ctx, *grads)
+        return _camera_grads_out(ctx) + tuple(out)
+
+
+class _RasterizeGaussiansRawCamera(_RasterizeGaussiansRaw):
+    """The camera_grad twin of _RasterizeGaussiansRaw (see _RasterizeGaussiansCamera)."""
+
+    @staticmethod
+    def forward(ctx, viewmatrix, projmatrix, campos, *args):
+        return _camera_forward(ctx, _RasterizeGaussiansRaw, viewmatrix, projmatrix, campos, args)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if ctx.cam_empty is not None:
+            return _camera_empty_backward(ctx) + (None,) * 9
+        out = _RasterizeGaussiansRaw.backward(ctx, *grads)
+        return _camera_grads_out(ctx) + tuple(out)
+
+
+def option_value(name, overrides=None):
+    """One knob as resolve_options(overrides)[name] would give it, without building the snapshot (a few dictionary look-ups: this
+    sits in front of every render)."""
+    if overrides and name in overrides:
+        _validate(name, overrides[name])
+        return overrides[name]
+    for kw in reversed(getattr(_tls, "stack", ())):
+        if name in kw:
+            return kw[name]
+    return _OPTIONS[name]
+
+
+def _camera_grad_requested(options, rs):
+    """True when the resolved options ask for camera gradients; raises where the option cannot be honoured (before any device call)."""
+    if not option_value("camera_grad", options):
+        return False
+    opts = resolve_options(options)
+    if rs.f_count:
+        raise ValueError("camera_grad is not available for count renders (f_count=True)")
+    if not opts["sh_jacobian"]:
+        raise ValueError("camera_grad needs sh_jacobian=True: the camera centre enters through the saved SH direction Jacobian")
+    if _GRAD_CHUNKS["hook"] is not None:
+        raise ValueError("camera_grad is not available with a gradient-chunk hook installed (set_grad_chunk_hook)")
+    if opts.get("sh_grad_sink") is not None:
+        raise ValueError("camera_grad is not available with an sh_grad_sink (data-parallel steps)")
+    for name in ("viewmatrix", "projmatrix", "campos"):
+        if not torch.is_tensor(getattr(rs, name)):
+            raise TypeError(f"camera_grad: raster_settings.{name} must be a torch tensor")
+    return True
 
 
 def _wants_grad(options, *tensors):
@@ -616,6 +731,12 @@ def _wants_grad(options, *tensors):
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_logit, log_scales, raw_rotations, raster_settings,
                             options=None):
+    if _camera_grad_requested(options, raster_settings):
+        rs = raster_settings
+        options = _wants_grad(options, xyz, means2D, features_dc, features_rest, opacity_logit, log_scales, raw_rotations,
+                              rs.viewmatrix, rs.projmatrix, rs.campos)
+        return _RasterizeGaussiansRawCamera.apply(rs.viewmatrix, rs.projmatrix, rs.campos, xyz, means2D, features_dc, features_rest,
+                                                  opacity_logit, log_scales, raw_rotations, rs, options)
     options = _wants_grad(options, xyz, means2D, features_dc, features_rest, opacity_logit, log_scales, raw_rotations)
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity_logit, log_scales, raw_rotations,
                                         raster_settings, options)
@@ -623,6 +744,12 @@ def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_lo
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, options=None):
+    if _camera_grad_requested(options, raster_settings):
+        rs = raster_settings
+        options = _wants_grad(options, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                              rs.viewmatrix, rs.projmatrix, rs.campos)
+        return _RasterizeGaussiansCamera.apply(rs.viewmatrix, rs.projmatrix, rs.campos, means3D, means2D, sh, colors_precomp, opacities,
+                                               scales, rotations, cov3Ds_precomp, rs, options)
     options = _wants_grad(options, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, options)
