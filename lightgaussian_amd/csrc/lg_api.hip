@@ -4,7 +4,7 @@
 //   lg_plan.h        host-side plans of one forward, plain C++ (also compiled by the CPU tests): KeyPlan (sort-key layout), ForwardPlan (kernel variants)
 //   lg_host.h        error strings, optional hipEvent profiler, scratch carving (GeomView / ImgView / BinView)
 //   lg_wave.h        wave64 primitives (DPP / permlane reductions)
-//   lg_preprocess.h  K1 lg_preprocess<RAW>, K8+K9 lg_preprocess_bwd<RAW>            (per Gaussian, HBM-bound)
+//   lg_preprocess.h  K1 lg_preprocess<RAW>, K8+K9 lg_preprocess_bwd<RAW>            (per Gaussian, HBM-bound); lg_k9_*: K9's read side, shared with lg_camera.h
 //   lg_binning.h     K2 lg_scan_blocks, K3 lg_duplicate, lg_tile_sort / _long (second sort stage), lg_tile_ranges (one-stage cross-check only),
 //                    lg_work_order (K2-K5 all hand-written; lg_sort.h = K4)
 //   lg_loss.h        lg_loss_fwd / lg_loss_bwd: fused L1 + SSIM of the training step             (a wave per 64-column strip, register ring)
@@ -19,9 +19,9 @@
 //   lg_adam.h        lg_adam_step: one Adam / AdamW step over all parameter tensors of the model in one launch (table by value, dwordx4);
 //                    lg_adam_step_rows: the same step over the rows a byte mask names (row index: lg_adam_rows.h)
 //   lg_densify.h     lg_densify_stats / lg_densify_plan / lg_densify_rows: view statistics and clone / split / prune of densify_and_prune
-//   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound)
+//   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound); wave_reduce_via_lds<NV> (also lg_features.h's)
 //   lg_features.h    lg_features_fwd / _bwd / _gather: C further per-Gaussian channels blended over the lists a forward left, and dL/dfeatures
-//   lg_camera.h      lg_camera_bwd<RAW> / lg_camera_reduce: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos from the rows a backward left (float64 ordered sums)
+//   lg_camera.h      lg_camera_bwd<RAW> / lg_camera_reduce: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos from the rows a backward left, through lg_k9_* (float64 ordered sums)
 //
 // Pipeline of one view:
 //   K1 project + EWA + SH->RGB + exact footprint culling  ->  K2 scan of instance counts, blocking read of R
@@ -68,12 +68,22 @@ static ViewGeom view_geom(const lg_view* v, int N)
     return q;
 }
 
+// The tests of the view alone that check_args and features_args both make, in this order; each caller words its own message.
+enum ViewFault { VIEW_OK = 0, VIEW_BAD_SIZE, VIEW_BAD_SEGMENT, VIEW_TOO_LARGE };
+static ViewFault check_view(const lg_view* v, int N)
+{
+    if (v->image_width <= 0 || v->image_height <= 0) return VIEW_BAD_SIZE;
+    if (v->segment_length != 0 && (v->segment_length < 64 || v->segment_length % 64 != 0)) return VIEW_BAD_SEGMENT;
+    const ViewGeom q = view_geom(v, N);
+    return (q.gx >= 65536 || q.gy >= 65536) ? VIEW_TOO_LARGE : VIEW_OK;
+}
+
 static int check_args(const lg_view* v, const lg_gaussians* g)
 {
     if (!v || !g) return fail(LG_ERR_INVALID_ARGUMENT, "null view/gaussians");
-    if (g->N < 0 || v->image_width <= 0 || v->image_height <= 0) return fail(LG_ERR_INVALID_ARGUMENT, "bad sizes");
-    if (v->segment_length != 0 && (v->segment_length < 64 || v->segment_length % 64 != 0))
-        return fail(LG_ERR_INVALID_ARGUMENT, "lg_view.segment_length must be 0 (default 512) or a multiple of 64");
+    const ViewFault vf = check_view(v, g->N);
+    if (g->N < 0 || vf == VIEW_BAD_SIZE) return fail(LG_ERR_INVALID_ARGUMENT, "bad sizes");
+    if (vf == VIEW_BAD_SEGMENT) return fail(LG_ERR_INVALID_ARGUMENT, "lg_view.segment_length must be 0 (default 512) or a multiple of 64");
     if ((v->flags & LG_FLAG_LONG_SERIAL) && (v->flags & LG_FLAG_LONG_PARALLEL))
         return fail(LG_ERR_INVALID_ARGUMENT, "LG_FLAG_LONG_SERIAL and LG_FLAG_LONG_PARALLEL exclude each other");
     if (g->N == 0) return LG_OK; // nothing to validate against: empty tensors carry no pointers
@@ -95,8 +105,7 @@ static int check_args(const lg_view* v, const lg_gaussians* g)
     }
     if (!v->bg || !v->viewmatrix || !v->projmatrix || !v->campos || !g->means3D || !g->opacities)
         return fail(LG_ERR_INVALID_ARGUMENT, "missing required pointer");
-    const ViewGeom q = view_geom(v, g->N);
-    if (q.gx >= 65536 || q.gy >= 65536) return fail(LG_ERR_INVALID_ARGUMENT, "image too large");
+    if (vf == VIEW_TOO_LARGE) return fail(LG_ERR_INVALID_ARGUMENT, "image too large");
     return LG_OK;
 }
 
@@ -495,6 +504,8 @@ static void preprocess_bwd_launch(const lg_view* v, const lg_gaussians* g, const
 // what lg_backward_features adds to a backward: a loss on the feature image and / or on alpha (lg_features_bwd_geom, lg_features.h)
 struct FeatGrad { const float* features; int C; const float* bg; const float* dL_dout; const float* dL_dalpha; };
 static LgFeatView features_view(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const ViewGeom& q);
+// channels of the next walk when rem are left: as many as the registers take -- one walk up to 32 channels, two up to 64
+static int features_channel_group(int rem) { return rem <= 4 ? 4 : rem <= 16 ? 16 : 32; }
 using FeaturesBwdGeomKernel = decltype(&lg_features_bwd_geom<4, true, true>);
 static FeaturesBwdGeomKernel features_bwd_geom_kernel(int cg, bool exact, bool accum)
 {
@@ -549,8 +560,8 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
         if (fg->dL_dout || fg->dL_dalpha || !dL_dcolor) {
             const int nch = fg->dL_dout ? fg->C : 1;     // without dL_dout one walk: dL_dalpha's, or the zero rows
             bool accum = dL_dcolor != nullptr;
-            for (int c0 = 0; c0 < nch;) {
-                const int rem = nch - c0, cg = rem <= 4 ? 4 : rem <= 16 ? 16 : 32;
+            for (int c0 = 0, cg; c0 < nch; c0 += cg) {
+                cg = features_channel_group(nch - c0);
                 {
                     ProfScope ps(prof, "features_bwd_geom", stream);
                     features_bwd_geom_kernel(cg, exact, accum)<<<q.ntiles_pad, 256, 0, stream>>>(f, (uint32_t)S, bin.meta, fg->C, c0, geo.tinfo, fg->features,
@@ -558,7 +569,6 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
                 }
                 KCHECK("lg_features_bwd_geom");
                 accum = true;
-                c0 += cg;
             }
         }
     }
@@ -1376,18 +1386,16 @@ static int features_args(const char* who, const lg_view* v, int32_t N, const voi
 {
     char msg[160];
     const char* what = nullptr;
+    const ViewFault vf = v ? check_view(v, N) : VIEW_OK;
     if (!v) what = "null view";
     else if (C < 1 || C > LG_FEATURES_MAX) what = "C must be 1 .. LG_FEATURES_MAX (64) channels";
     else if (N < 0 || N >= (1 << LG_ID_BITS)) what = "N out of range";
     else if (R < 0 || R >= (1ll << 30)) what = "num_rendered out of range";
-    else if (v->image_width <= 0 || v->image_height <= 0) what = "bad image size";
-    else if (v->segment_length != 0 && (v->segment_length < 64 || v->segment_length % 64 != 0)) what = "lg_view.segment_length must be 0 or a multiple of 64";
+    else if (vf == VIEW_BAD_SIZE) what = "bad image size";
+    else if (vf == VIEW_BAD_SEGMENT) what = "lg_view.segment_length must be 0 or a multiple of 64";
     else if (!geom_p) what = "missing geom buffer";
     else if (N > 0 && R > 0 && !bin_p) what = "missing binning buffer";
-    if (!what) {
-        const ViewGeom q = view_geom(v, N);
-        if (q.gx >= 65536 || q.gy >= 65536) what = "image too large";
-    }
+    else if (vf == VIEW_TOO_LARGE) what = "image too large";
     if (!what) return LG_OK;
     snprintf(msg, sizeof(msg), "%s: %s", who, what);
     return fail(LG_ERR_INVALID_ARGUMENT, msg);
@@ -1439,15 +1447,13 @@ extern "C" int lg_blend_features(const lg_view* v, int32_t N, const void* geom_p
     const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, exact = !(v->flags & LG_FLAG_FAST_EXP);
     const ViewGeom q = view_geom(v, N);
     const LgFeatView f = features_view(v, N, geom_p, bin_p, R, q);
-    // as many channels per walk as the registers take: one walk up to 32 channels, two up to 64
-    for (int c0 = 0; c0 < C;) {
-        const int rem = C - c0, cg = rem <= 4 ? 4 : rem <= 16 ? 16 : 32;
+    for (int c0 = 0, cg; c0 < C; c0 += cg) {
+        cg = features_channel_group(C - c0);
         {
             ProfScope ps(prof, "features_fwd", stream);
             features_fwd_kernel(cg, exact)<<<q.ntiles_pad, 256, 0, stream>>>(f, C, c0, features, bg_features, out, alpha);
         }
         KCHECK("lg_features_fwd");
-        c0 += cg;
     }
     return LG_OK;
 }

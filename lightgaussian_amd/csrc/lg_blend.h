@@ -956,25 +956,34 @@ lg_score_slots(int N, const uint32_t* __restrict__ touched, const uint32_t* __re
 // in order, so the reads see every lane's writes without a barrier; lanes >= 36 redo row 8 (clamped row: no exec masking).
 #define LG_RED_STRIDE 68
 #define LG_RED_FLOATS (9 * LG_RED_STRIDE)
-__device__ __forceinline__ void wave_reduce9_via_lds(const float (&p)[9], float* red, float* dst, uint32_t dst_off, uint32_t lane)
+// One reduction for every width: NV values per lane (1..16, one row per four lanes), total r of the entry handed to store(r, total) by
+// lane 4 r.  Lanes past 4 NV redo the last row.  A fixed order: the sums are reproducible.
+template <int NV, typename Store>
+__device__ __forceinline__ void wave_reduce_via_lds(const float (&p)[NV], float* red, uint32_t lane, Store store)
 {
+    static_assert(NV >= 1 && NV <= 16, "one row per four lanes");
 #pragma unroll
-    for (int v = 0; v < 9; v++) red[v * LG_RED_STRIDE + (int)lane] = p[v];
+    for (int v = 0; v < NV; v++) red[v * LG_RED_STRIDE + (int)lane] = p[v];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const uint32_t r = min(lane >> 2, 8u), q = lane & 3u;
+    const uint32_t r = min(lane >> 2, (uint32_t)(NV - 1)), q = lane & 3u;
     const float4* src = reinterpret_cast<const float4*>(red + r * LG_RED_STRIDE + q * 16u);
     const float4 x0 = src[0], x1 = src[1], x2 = src[2], x3 = src[3];
     float s = (((x0.x + x0.y) + (x0.z + x0.w)) + ((x1.x + x1.y) + (x1.z + x1.w))) +
               (((x2.x + x2.y) + (x2.z + x2.w)) + ((x3.x + x3.y) + (x3.z + x3.w)));
     s = dpp_add<0xB1, 0xf>(s);                      // quad_perm [1,0,3,2]
     s = dpp_add<0x4E, 0xf>(s);                      // quad_perm [2,3,0,1]: every lane of the quad holds the row total
-    // dst is VALUE-major, [9][LG_Q]: total v of entry j at dst[v * LG_Q + j].  (Entry-major, `stage + 9 j` + v, cost a 64-bit
-    // v_mad_u64_u32 per entry for j * 36 + base; here the address is a per-lane constant plus a scalar shift of j.)
-    if (q == 0u && lane < 36u) dst[(lane >> 2) * LG_Q + dst_off] = s;
+    if (q == 0u && lane < 4u * NV) store(lane >> 2, s);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();                // (the next entry overwrites `red`)
+}
+
+// K7's instance.  dst is VALUE-major, [9][LG_Q]: total v of entry j at dst[v * LG_Q + j].  (Entry-major, `stage + 9 j` + v, cost a 64-bit
+// v_mad_u64_u32 per entry for j * 36 + base; here the address is a per-lane constant plus a scalar shift of j.)
+__device__ __forceinline__ void wave_reduce9_via_lds(const float (&p)[9], float* red, float* dst, uint32_t dst_off, uint32_t lane)
+{
+    wave_reduce_via_lds<9>(p, red, lane, [&](uint32_t r, float s) { dst[r * LG_Q + dst_off] = s; });
 }
 
 // (two entries per reduction pass, quads summed in registers first, packed adds: EXPERIMENTS.md, "K7 reduction")

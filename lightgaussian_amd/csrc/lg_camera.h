@@ -2,8 +2,10 @@
 // Part of liblightgaussian_hip.so (single translation unit: lg_api.hip includes the lg_*.h kernel headers; this one after all others).
 //
 // dL/dviewmatrix, dL/dprojmatrix, dL/dcampos of one view: 27 sums over its visible Gaussians of the per-Gaussian camera terms
-// (lg_backward_camera_terms, lg_math.h).  A kernel of its own that gathers the moment rows a blend backward left AGAIN, on purpose: it is
-// opt-in (lg_backward_camera is called only by renders with option camera_grad) and K9 stays exactly as it was.
+// (lg_backward_camera_terms, lg_math.h).  A second pass over the moment rows a blend backward left, through K9's own functions
+// (lg_k9_*, lg_preprocess.h): the view check, both row gathers, the covariance, the clamp-masked dRGB and the Jacobian row are the
+// code K9 runs, so the rows are summed in K9's order whatever its tuning.  A kernel of its own because it is opt-in
+// (lg_backward_camera is called only by renders with option camera_grad).
 //
 // Summation order (fixed: the result is bit-identical run to run, no atomics, no look-back):
 //   per Gaussian     float32 terms, as every per-Gaussian gradient of K9
@@ -52,89 +54,34 @@ lg_camera_bwd(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, f
     // a missing Jacobian marker leave no rows to read -- exact zeros.  R is the device's own count, capped by the rows the caller's
     // scratch holds; a Gaussian whose row range does not lie inside [0, R) contributes nothing (it cannot happen after a forward that
     // was not abandoned: the check keeps every load inside the buffer whatever the buffers hold)
-    const bool view_ok = counters[0] == 0u && meta[2] == S && (!use_sh || counters[9] == LG_SHJAC_MAGIC);
+    const bool view_ok = lg_k9_view_has_rows(counters, meta, S, use_sh);
     const uint32_t R = min(counters[3], rows_cap);
     bool vis = view_ok && (i < N) && radii[i] > 0;
     uint32_t my_t = 0u, my_u0 = 0u;
     if (vis) {
         const uint32_t t = touched[i], off = offsets[i];
         if (off < t || off > R) vis = false;
-        else { my_t = t; my_u0 = off - t; }
+        else { my_t = t; my_u0 = off - t; }      // my_u0 + my_t <= R < 2^30: no wrap
     }
-    float coop[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    {
-        // K9's cooperative form: a splat with more than LG_COOP_ROWS instances is summed by its whole wave, 64 rows per step
-        uint64_t big = __ballot(my_t > LG_COOP_ROWS);
-        while (big) {
-            const int src = (int)__builtin_ctzll(big);
-            big &= big - 1;
-            const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)my_t, src);
-            const uint32_t u0 = (uint32_t)__builtin_amdgcn_readlane((int)my_u0, src);
-            float acc9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-            for (uint32_t u = u0 + lane; u < u0 + t; u += LG_PP) {      // u0 + t <= R < 2^30: no wrap
-                const float4* rp = part + 3 * (size_t)u;
-                const float4 v0 = rp[0], v1 = rp[1], v2 = rp[2];
-                acc9[0] += v0.x; acc9[1] += v0.y; acc9[2] += v0.z; acc9[3] += v0.w; acc9[4] += v1.x; acc9[5] += v1.y; acc9[6] += v1.z;
-                acc9[7] += v1.w; acc9[8] += v2.x;
-            }
-#pragma unroll
-            for (int k9 = 0; k9 < 9; k9++) {
-                const float tot = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_to_lane63(acc9[k9])), 63));
-                if ((int)lane == src) coop[k9] = tot;
-            }
-        }
-    }
+    float coop[9];
+    lg_k9_gather_coop(part, my_t, my_u0, lane, coop);
     float term[LG_CAM_TERMS];
 #pragma unroll
     for (int k = 0; k < LG_CAM_TERMS; k++) term[k] = 0.0f;
     if (vis) {
         float mo[9];
-#pragma unroll
-        for (int k9 = 0; k9 < 9; k9++) mo[k9] = coop[k9];
-        if (my_t <= LG_COOP_ROWS) {
-            const uint32_t ue = my_u0 + my_t;
-            for (uint32_t u = my_u0; u < ue; u += LG_K9_GATHER) {
-                float4 a[LG_K9_GATHER][3];
-#pragma unroll
-                for (int j = 0; j < LG_K9_GATHER; j++) {
-                    const float4* rp = part + 3 * (size_t)min(u + (uint32_t)j, ue - 1u);
-                    a[j][0] = rp[0]; a[j][1] = rp[1]; a[j][2] = rp[2];
-                }
-#pragma unroll
-                for (int j = 0; j < LG_K9_GATHER; j++) {
-                    if (u + (uint32_t)j < ue) {
-                        mo[0] += a[j][0].x; mo[1] += a[j][0].y; mo[2] += a[j][0].z; mo[3] += a[j][0].w; mo[4] += a[j][1].x; mo[5] += a[j][1].y;
-                        mo[6] += a[j][1].z; mo[7] += a[j][1].w; mo[8] += a[j][2].x;
-                    }
-                }
-            }
-        }
+        lg_k9_gather_lane(part, my_t, my_u0, coop, mo);
         const float4 q0 = rec[LG_REC_F4 * (size_t)i], q1 = rec[LG_REC_F4 * (size_t)i + 1], q2 = rec[LG_REC_F4 * (size_t)i + 2];
         const float px = means3D[3 * (size_t)i], py = means3D[3 * (size_t)i + 1], pz = means3D[3 * (size_t)i + 2];
         float a[9];
         lg_rows_to_grads(mo, q0.z, q0.w, q1.x, q1.y, a);
-        float Sg[6];
-        if (cov3D_precomp) {
-#pragma unroll
-            for (int k = 0; k < 6; k++) Sg[k] = cov3D_precomp[6 * (size_t)i + k];
-        } else {
-            float sc[3] = { scales[3 * (size_t)i], scales[3 * (size_t)i + 1], scales[3 * (size_t)i + 2] };
-            const float4 q4 = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)i);
-            float q[4] = { q4.x, q4.y, q4.z, q4.w };
-            if (RAW) {      // K9's expressions, which are K1's
-                sc[0] = expf(sc[0]); sc[1] = expf(sc[1]); sc[2] = expf(sc[2]);
-                const float qn = fmaxf(sqrtf((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3])), 1e-12f);
-                q[0] /= qn; q[1] /= qn; q[2] /= qn; q[3] /= qn;
-            }
-            lg_cov3d(sc, mod, q, Sg);
-        }
+        float Sg[6], sc[3], q[4], qn;
+        lg_k9_cov3d<RAW>(i, mod, cov3D_precomp, scales, rotations, Sg, sc, q, qn);
         float d[3] = {0.0f, 0.0f, 0.0f};
         if (use_sh) {
-            const uint32_t cb = __float_as_uint(q2.w) >> LG_ID_BITS;
-            const float dRGB[3] = { (cb & 1u) ? 0.0f : a[6], (cb & 2u) ? 0.0f : a[7], (cb & 4u) ? 0.0f : a[8] };
-            const float* jr = shjac + 9 * (size_t)i;
-            const lg_f4u j0 = reinterpret_cast<const lg_f4u*>(jr)[0], j1 = reinterpret_cast<const lg_f4u*>(jr)[1];
-            const float J[9] = { j0.x, j0.y, j0.z, j0.w, j1.x, j1.y, j1.z, j1.w, jr[8] };
+            float dRGB[3], J[9];
+            lg_k9_drgb(q2.w, a, dRGB);
+            lg_k9_jac_row(shjac, i, J);
             lg_backward_sh_jac(D, J, px, py, pz, cp, dRGB, d, [](int, int, float) {});
         }
         lg_backward_camera_terms(vm, pm, px, py, pz, Sg, a, W, H, tanfovx, tanfovy, d, term);

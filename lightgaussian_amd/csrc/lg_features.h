@@ -21,9 +21,11 @@
 // up to rounding.
 //
 // Backward: K7's discipline -- no float atomics, no memset.  Per hit entry a wave reduces w g[c] over its 64 pixels through an LDS
-// transpose (lg_feat_reduce: wave_reduce9_via_lds for NV = 4 / 8 / 16 values; entries no lane of the wave hit are skipped), the four waves'
+// transpose (lg_feat_reduce: K7's wave_reduce_via_lds, lg_blend.h, for NV = 4 / 8 / 16 values; entries no lane of the wave hit are skipped), the four waves'
 // partials meet in LDS and one row of NV sums per (tile, Gaussian) instance goes to the instance's pre-sort slot (lg_slot_of), written
 // exactly once, zeros included.  lg_features_gather adds every Gaussian's contiguous rows in slot order: bit-identical run to run.
+// Every step of the walk is one function (lg_feat_list, _front, _alpha, _pair, _stage_rows, _slot, _reduce); only the cross-wave merges
+// of lg_features_bwd (a thread per (entry, value)) and lg_features_bwd_geom (a thread per entry, 12-float rows) stay with their kernels.
 #pragma once
 
 #include "lg_host.h"
@@ -80,16 +82,50 @@ __device__ __forceinline__ uint32_t lg_feat_front(const LgFeatView& v, uint32_t 
     return (uint32_t)__popcll(mask);
 }
 
+// alpha of a (pixel, entry) pair as the forward evaluated it, and the exponential G it is made of (the geometry backward chains through
+// it): lg_alpha_exact with its exp kept (canonical), or the forward's guarded hardware exp.
+template <bool EXACT>
+__device__ __forceinline__ float lg_feat_alpha(float op, float power, float& G)
+{
+    G = EXACT ? lg_exp(fminf(power, 0.0f)) : __expf(power);
+    const float alpha = fminf(LG_ALPHA_MAX, op * G);
+    return EXACT ? alpha : guard_alpha(alpha, op, power);
+}
+
+// The pre-sort slot of list entry idx, where its row goes; 0xFFFFFFFF (past every slot_cap) for !live and for an id that is not below N.
+__device__ __forceinline__ uint32_t lg_feat_slot(const LgFeatView& v, const uint4* tinfo, uint32_t idx, bool live, int tx, int ty)
+{
+    uint32_t sl = 0xFFFFFFFFu;
+    if (live) {
+        const uint32_t id = (uint32_t)v.entries[idx] & v.gid_mask;
+        if (id < (uint32_t)v.N) sl = lg_slot_of(tinfo[id], tx, ty);
+    }
+    return sl;
+}
+
+// The feature rows of a batch's nhit hits into the wave's frow: channels [c0, c0 + CG) of each hit, CG consecutive floats per hit
+// (zeros past channel C), read as coalesced row segments.
+template <int CG>
+__device__ __forceinline__ void lg_feat_stage_rows(const float* features, int C, int c0, const uint32_t* qid, uint32_t nhit, float* frow,
+                                                   uint32_t lane)
+{
+    for (uint32_t i = lane; i < nhit * CG; i += 64u) {
+        const uint32_t j = i / CG, c = i % CG;
+        frow[i] = (c0 + (int)c < C) ? features[(size_t)qid[j] * C + c0 + c] : 0.0f;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // One (pixel, entry) step: power and alpha as the forward's pair step evaluates them (fwd_pair_m), then lg_feature_step.  Called by all
 // 64 lanes (guard_alpha ballots); w = 0 unless the entry contributes to the pixel.
 template <bool EXACT>
 __device__ __forceinline__ int lg_feat_pair(const float4& a, const float4& b, bool done, float pxf, float pyf, float& T, float& w)
 {
-    float dx, dy;
+    float dx, dy, G;
     const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
-    float alpha;
-    if (EXACT) alpha = lg_alpha_exact(b.y, power);
-    else alpha = guard_alpha(fminf(LG_ALPHA_MAX, b.y * __expf(power)), b.y, power);
+    const float alpha = lg_feat_alpha<EXACT>(b.y, power, G);
     w = 0.0f;
     return done ? 0 : lg_feature_step(power, alpha, T, w);
 }
@@ -122,14 +158,7 @@ lg_features_fwd(LgFeatView v, int C, int c0, const float* __restrict__ features,
         if (__ballot(!done) == 0) break;        // every pixel of this wave is saturated or outside
         const uint32_t nhit = lg_feat_front(v, base + lane, hi, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], qid[wave], qpos[wave], lane);
         if (nhit == 0u) continue;
-        // the hits' feature rows: CG consecutive floats per hit (zeros past channel C)
-        for (uint32_t i = lane; i < nhit * CG; i += 64u) {
-            const uint32_t j = i / CG, c = i % CG;
-            frow[wave][i] = (c0 + (int)c < C) ? features[(size_t)qid[wave][j] * C + c0 + c] : 0.0f;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        lg_feat_stage_rows<CG>(features, C, c0, qid[wave], nhit, frow[wave], lane);
         for (uint32_t j = 0; j < nhit; j++) {
             const float4 a = q0[wave][j], b = q1[wave][j];
             float w;
@@ -158,28 +187,11 @@ lg_features_fwd(LgFeatView v, int C, int c0, const float* __restrict__ features,
 
 // ------------------------------------------------------------------------------------------------
 // backward
-// lg_feat_reduce: wave_reduce9_via_lds (lg_blend.h) for NV <= 16 values.  The NV partials of every lane go to an NV x 64 matrix (row stride
-// LG_RED_STRIDE); lane 4 r + q adds columns 16 q .. 16 q + 15 of row r (four ds_read_b128, 15 adds) and two quad-DPP adds join the quarters;
-// total r of the entry is left at dst[r].  A fixed order: the sums are reproducible.  Lanes past 4 NV redo the last row.
+// lg_feat_reduce: K7's LDS wave reduction (wave_reduce_via_lds, lg_blend.h) for NV <= 16 values; total r of the entry is left at dst[r].
 template <int NV>
 __device__ __forceinline__ void lg_feat_reduce(const float (&p)[NV], float* red, float* dst, uint32_t lane)
 {
-    static_assert(NV >= 1 && NV <= 16, "one row per four lanes");
-#pragma unroll
-    for (int k = 0; k < NV; k++) red[k * LG_RED_STRIDE + (int)lane] = p[k];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const uint32_t r = min(lane >> 2, (uint32_t)(NV - 1)), q = lane & 3u;
-    const float4* src = reinterpret_cast<const float4*>(red + r * LG_RED_STRIDE + q * 16u);
-    const float4 x0 = src[0], x1 = src[1], x2 = src[2], x3 = src[3];
-    float s = (((x0.x + x0.y) + (x0.z + x0.w)) + ((x1.x + x1.y) + (x1.z + x1.w))) +
-              (((x2.x + x2.y) + (x2.z + x2.w)) + ((x3.x + x3.y) + (x3.z + x3.w)));
-    s = dpp_add<0xB1, 0xf>(s);                      // quad_perm [1,0,3,2]
-    s = dpp_add<0x4E, 0xf>(s);                      // quad_perm [2,3,0,1]: every lane of the quad holds the row total
-    if (q == 0u && lane < 4u * NV) dst[lane >> 2] = s;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();                // (the next entry overwrites `red`)
+    wave_reduce_via_lds<NV>(p, red, lane, [&](uint32_t r, float s) { dst[r] = s; });
 }
 
 // Channels [c0, c0 + NV) (those below c1) of the partial rows: rows[slot][CW], column (c0 - cb) + k, for every entry of every list.
@@ -218,15 +230,7 @@ lg_features_bwd(LgFeatView v, int c0, int c1, int cb, int CW, const uint4* __res
     bool done = !g.inside;
     for (uint32_t base = lo; base < hi; base += LG_Q) {
         const uint32_t nbt = min((uint32_t)LG_Q, hi - base);
-        if (wave == 0) {
-            // the pre-sort slots of the batch's entries: where their rows go
-            uint32_t sl = 0xFFFFFFFFu;
-            if (lane < nbt) {
-                const uint32_t id = (uint32_t)v.entries[base + lane] & v.gid_mask;
-                if (id < (uint32_t)v.N) sl = lg_slot_of(tinfo[id], tx, ty);
-            }
-            slot[lane] = sl;
-        }
+        if (wave == 0) slot[lane] = lg_feat_slot(v, tinfo, base + lane, lane < nbt, tx, ty);      // where the batch's rows go
         uint64_t hitmask = 0ull;                                  // entries of the batch this wave has a partial row for (scalar)
         if (__ballot(!done) != 0) {
             const uint32_t nhit = lg_feat_front(v, base + lane, hi, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], qid[wave], qpos[wave], lane);
@@ -365,36 +369,18 @@ lg_features_bwd_geom(LgFeatView v, uint32_t S, const uint32_t* __restrict__ meta
         const uint32_t rel0 = (uint32_t)k * LG_Q, base = lo + rel0;
         const uint32_t nbt = min((uint32_t)LG_Q, n_list - rel0);
         // thread e of the workgroup owns entry e of the batch: the pre-sort slot its row lives at
-        uint32_t sl = 0xFFFFFFFFu;
-        if (threadIdx.x < nbt) {
-            const uint32_t id = (uint32_t)v.entries[base + threadIdx.x] & v.gid_mask;
-            if (id < (uint32_t)v.N) sl = lg_slot_of(tinfo[id], tx, ty);
-        }
+        const uint32_t sl = lg_feat_slot(v, tinfo, base + threadIdx.x, threadIdx.x < nbt, tx, ty);
         uint64_t hitmask = 0ull;                                  // entries of the batch this wave has a partial row for (scalar)
         if (wl > rel0) {
             const uint32_t nhit = lg_feat_front(v, base + lane, hi, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], qid[wave], qpos[wave], lane);
-            if (have) {
-                for (uint32_t i = lane; i < nhit * CG; i += 64u) {
-                    const uint32_t j = i / CG, c = i % CG;
-                    frow[wave][i] = (c0 + (int)c < C) ? features[(size_t)qid[wave][j] * C + c0 + c] : 0.0f;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
+            if (have) lg_feat_stage_rows<CG>(features, C, c0, qid[wave], nhit, frow[wave], lane);
             for (int j = (int)nhit - 1; j >= 0; j--) {
                 const float4 a = q0[wave][j], b = q1[wave][j];
                 const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)qpos[wave][j]);
                 float dx, dy;
                 const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
-                float G, alpha;
-                if (EXACT) {
-                    G = lg_exp(fminf(power, 0.0f));
-                    alpha = fminf(LG_ALPHA_MAX, b.y * G);         // lg_alpha_exact, with its exp kept
-                } else {
-                    G = __expf(power);
-                    alpha = guard_alpha(fminf(LG_ALPHA_MAX, b.y * G), b.y, power);
-                }
+                float G;
+                const float alpha = lg_feat_alpha<EXACT>(b.y, power, G);
                 float q = gA;
                 if (have) {
                     const float4* fr = reinterpret_cast<const float4*>(&frow[wave][j * CG]);

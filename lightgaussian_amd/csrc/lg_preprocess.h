@@ -255,6 +255,115 @@ lg_preprocess(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, f
 
 
 // ------------------------------------------------------------------------------------------------
+// K9's read side as functions: lg_camera_bwd (lg_camera.h) makes a second pass over the same rows and has to sum them in the same order
+// and rebuild the same covariance, bit for bit.
+// This view left rows to read.  counters[0] != 0: the forward aborted this view on the device (lg_forward_bounded overflow); there are no rows.
+// meta[2] != S: this backward was given another segment length than the forward that filled the buffers (lg_view.segment_length
+// must match): lg_blend_bwd refused to run, there are no rows either -- zero gradients, and LG_FLAG_DEBUG reports it.  marker: the
+// caller reads the Jacobian rows, which exist only when the forward of THIS view left its marker word.
+__device__ __forceinline__ bool lg_k9_view_has_rows(const uint32_t* counters, const uint32_t* meta, uint32_t S, bool marker)
+{
+    return counters[0] == 0u && meta[2] == S && (!marker || counters[9] == LG_SHJAC_MAGIC);
+}
+
+// Screen-filling splats own thousands of gradient rows; a single lane walking them would stall its wave for
+// milliseconds.  Such lanes (more than LG_COOP_ROWS instances) are served one at a time by the whole wave: 64 rows per step, then a
+// wave reduction.  Called by all 64 lanes; coop is the lane's own sum, zeros for every other lane.
+__device__ __forceinline__ void lg_k9_gather_coop(const float4* part, uint32_t my_t, uint32_t my_u0, uint32_t lane, float (&coop)[9])
+{
+#pragma unroll
+    for (int k9 = 0; k9 < 9; k9++) coop[k9] = 0.0f;
+    uint64_t big = __ballot(my_t > LG_COOP_ROWS);
+    while (big) {
+        const int src = (int)__builtin_ctzll(big);
+        big &= big - 1;
+        const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)my_t, src);
+        const uint32_t u0 = (uint32_t)__builtin_amdgcn_readlane((int)my_u0, src);
+        float acc9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t u = u0 + lane; u < u0 + t; u += LG_PP) {
+            const float4* rp = part + 3 * (size_t)u;
+            const float4 v0 = rp[0], v1 = rp[1], v2 = rp[2];
+            acc9[0] += v0.x; acc9[1] += v0.y; acc9[2] += v0.z; acc9[3] += v0.w; acc9[4] += v1.x; acc9[5] += v1.y; acc9[6] += v1.z;
+            acc9[7] += v1.w; acc9[8] += v2.x;
+        }
+#pragma unroll
+        for (int k9 = 0; k9 < 9; k9++) {
+            const float tot = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_to_lane63(acc9[k9])), 63));
+            if ((int)lane == src) coop[k9] = tot;
+        }
+    }
+}
+
+// This Gaussian's gradient rows (one per tile instance) summed in slot order: deterministic, no atomics.  Splats with more than
+// LG_COOP_ROWS instances were summed cooperatively by the whole wave (coop, above).
+__device__ __forceinline__ void lg_k9_gather_lane(const float4* part, uint32_t my_t, uint32_t my_u0, const float (&coop)[9], float (&mo)[9])
+{
+#pragma unroll
+    for (int k9 = 0; k9 < 9; k9++) mo[k9] = coop[k9];
+    if (my_t <= LG_COOP_ROWS) {
+        // LG_K9_GATHER rows per round trip (round 4): the row-by-row loop waited for every row before it asked for the next one, and a
+        // wave runs as many rounds as its busiest lane has rows -- 4 to 9 dependent round trips.  The loads of a round are issued
+        // together (rows past the lane's last one re-read it and are not added); same additions in the same order, so the gradients
+        // are bit-identical.  K9 0.262 -> 0.249 ms at C3 with 3 or 4 rows per round (2: no change), A/B on one box.
+        // (Requesting the record, the parameters and the Jacobian row in front of the rows as well: 0.233 vs 0.232-0.240 ms, nothing.)
+        const uint32_t ue = my_u0 + my_t;
+        for (uint32_t u = my_u0; u < ue; u += LG_K9_GATHER) {
+            float4 a[LG_K9_GATHER][3];
+#pragma unroll
+            for (int j = 0; j < LG_K9_GATHER; j++) {
+                const float4* rp = part + 3 * (size_t)min(u + (uint32_t)j, ue - 1u);
+                a[j][0] = rp[0]; a[j][1] = rp[1]; a[j][2] = rp[2];
+            }
+#pragma unroll
+            for (int j = 0; j < LG_K9_GATHER; j++) {
+                if (u + (uint32_t)j < ue) {
+                    mo[0] += a[j][0].x; mo[1] += a[j][0].y; mo[2] += a[j][0].z; mo[3] += a[j][0].w; mo[4] += a[j][1].x; mo[5] += a[j][1].y;
+                    mo[6] += a[j][1].z; mo[7] += a[j][1].w; mo[8] += a[j][2].x;
+                }
+            }
+        }
+    }
+}
+
+// 3D covariance of Gaussian i: the precomputed input, or recomputed from the (activated) scales / rotation exactly as K1 did.  sc, q and
+// qn are the activated scales, the normalised rotation and the raw rotation's norm, which K9's chain rule needs afterwards.
+template <bool RAW>
+__device__ __forceinline__ void lg_k9_cov3d(int i, float mod, const float* cov3D_precomp, const float* scales, const float* rotations,
+                                            float (&S)[6], float (&sc)[3], float (&q)[4], float& qn)
+{
+    sc[0] = sc[1] = sc[2] = 0.0f; q[0] = q[1] = q[2] = q[3] = 0.0f; qn = 1.0f;
+    if (cov3D_precomp) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) S[k] = cov3D_precomp[6 * (size_t)i + k];
+    } else {
+        sc[0] = scales[3 * (size_t)i]; sc[1] = scales[3 * (size_t)i + 1]; sc[2] = scales[3 * (size_t)i + 2];
+        const float4 q4 = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)i);
+        q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
+        if (RAW) {
+            sc[0] = expf(sc[0]); sc[1] = expf(sc[1]); sc[2] = expf(sc[2]);
+            qn = fmaxf(sqrtf((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3])), 1e-12f);
+            q[0] /= qn; q[1] /= qn; q[2] /= qn; q[3] /= qn;     // exactly K1's operations (pairwise sum, division: see there)
+        }
+        lg_cov3d(sc, mod, q, S);
+    }
+}
+
+// dL/d(rgb) of an SH colour: a[6..8] without the channels the forward clamped (bits above the id in rec_w, the record's last word)
+__device__ __forceinline__ void lg_k9_drgb(float rec_w, const float (&a)[9], float (&dRGB)[3])
+{
+    const uint32_t cb = __float_as_uint(rec_w) >> LG_ID_BITS;
+    dRGB[0] = (cb & 1u) ? 0.0f : a[6]; dRGB[1] = (cb & 2u) ? 0.0f : a[7]; dRGB[2] = (cb & 4u) ? 0.0f : a[8];
+}
+// Gaussian i's row of d rgb / d direction, as the forward left it (LG_FLAG_SAVE_SH_JACOBIAN)
+__device__ __forceinline__ void lg_k9_jac_row(const float* shjac, int i, float (&J)[9])
+{
+    const float* jr = shjac + 9 * (size_t)i;          // 36-byte rows: dword-aligned 16-byte loads
+    const lg_f4u j0 = reinterpret_cast<const lg_f4u*>(jr)[0], j1 = reinterpret_cast<const lg_f4u*>(jr)[1];
+    J[0] = j0.x; J[1] = j0.y; J[2] = j0.z; J[3] = j0.w; J[4] = j1.x; J[5] = j1.y; J[6] = j1.z; J[7] = j1.w; J[8] = jr[8];
+}
+
+
+// ------------------------------------------------------------------------------------------------
 // K8 + K9 fused: per-Gaussian backward.  One wave per workgroup; SH rows in and dL/dSH rows out go
 // through LDS so that global traffic is coalesced 16-byte accesses.
 // Registers: JAC = false (the SH coefficients are re-read, sh[48] lives in registers) 155 VGPRs -> 3 waves/SIMD; forcing 4
@@ -287,10 +396,7 @@ lg_preprocess_bwd(int N, int first_blk, int M, int D, int W, int H, float tanfov
 #pragma unroll
     for (int k = 0; k < 16; k++) { vm[k] = viewmatrix[k]; pm[k] = projmatrix[k]; }
     cp[0] = campos[0]; cp[1] = campos[1]; cp[2] = campos[2];
-    // counters[0] != 0: the forward aborted this view on the device (lg_forward_bounded overflow); there are no rows.
-    // meta[2] != S: this backward was given another segment length than the forward that filled the buffers (lg_view.segment_length
-    // must match): lg_blend_bwd refused to run, there are no rows either -- zero gradients, and LG_FLAG_DEBUG reports it
-    const bool vis = (i < N) && radii[i] > 0 && counters[0] == 0u && meta[2] == S && (!JAC || counters[9] == LG_SHJAC_MAGIC);
+    const bool vis = (i < N) && radii[i] > 0 && lg_k9_view_has_rows(counters, meta, S, JAC);
     const uint64_t vmask = __ballot(vis);
     const bool split = RAW && shs_rest != nullptr;
     const int rowf = split ? 3 * (M - 1) : 3 * M;
@@ -311,103 +417,40 @@ lg_preprocess_bwd(int N, int first_blk, int M, int D, int W, int H, float tanfov
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
-    // Screen-filling splats own thousands of gradient rows; a single lane walking them would stall its wave for
-    // milliseconds.  Such lanes are served one at a time by the whole wave: 64 rows per step, then a wave reduction.
     const uint32_t my_t = vis ? touched[i] : 0u;
     const uint32_t my_u0 = vis ? offsets[i] - my_t : 0u;
-    float coop[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    {
-        uint64_t big = __ballot(my_t > LG_COOP_ROWS);
-        while (big) {
-            const int src = (int)__builtin_ctzll(big);
-            big &= big - 1;
-            const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)my_t, src);
-            const uint32_t u0 = (uint32_t)__builtin_amdgcn_readlane((int)my_u0, src);
-            float acc9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-            for (uint32_t u = u0 + lane; u < u0 + t; u += LG_PP) {
-                const float4* rp = part + 3 * (size_t)u;
-                const float4 v0 = rp[0], v1 = rp[1], v2 = rp[2];
-                acc9[0] += v0.x; acc9[1] += v0.y; acc9[2] += v0.z; acc9[3] += v0.w; acc9[4] += v1.x; acc9[5] += v1.y; acc9[6] += v1.z;
-                acc9[7] += v1.w; acc9[8] += v2.x;
-            }
-#pragma unroll
-            for (int k9 = 0; k9 < 9; k9++) {
-                const float tot = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_to_lane63(acc9[k9])), 63));
-                if ((int)lane == src) coop[k9] = tot;
-            }
-        }
-    }
+    float coop[9];
+    lg_k9_gather_coop(part, my_t, my_u0, lane, coop);
     float m2[3] = {0, 0, 0}, m3[3] = {0, 0, 0}, dop = 0.0f, dsc[3] = {0, 0, 0}, drot[4] = {0, 0, 0, 0}, dcov[6] = {0, 0, 0, 0, 0, 0};
     float dcol[3] = {0, 0, 0};
     float dsh[LG_SH_MAXF];
 #pragma unroll
     for (int k = 0; k < LG_SH_MAXF; k++) dsh[k] = 0.0f;
     if (vis) {
-        // gather this Gaussian's gradient rows (one per tile instance) in slot order: deterministic, no atomics.
-        // Splats with more than LG_COOP_ROWS instances were summed cooperatively by the whole wave (below).
         float mo[9];
-#pragma unroll
-        for (int k9 = 0; k9 < 9; k9++) mo[k9] = coop[k9];
-        if (my_t <= LG_COOP_ROWS) {
-            // LG_K9_GATHER rows per round trip (round 4): the row-by-row loop waited for every row before it asked for the next one, and a
-            // wave runs as many rounds as its busiest lane has rows -- 4 to 9 dependent round trips.  The loads of a round are issued
-            // together (rows past the lane's last one re-read it and are not added); same additions in the same order, so the gradients
-            // are bit-identical.  K9 0.262 -> 0.249 ms at C3 with 3 or 4 rows per round (2: no change), A/B on one box.
-            // (Requesting the record, the parameters and the Jacobian row in front of the rows as well: 0.233 vs 0.232-0.240 ms, nothing.)
-            const uint32_t ue = my_u0 + my_t;
-            for (uint32_t u = my_u0; u < ue; u += LG_K9_GATHER) {
-                float4 a[LG_K9_GATHER][3];
-#pragma unroll
-                for (int j = 0; j < LG_K9_GATHER; j++) {
-                    const float4* rp = part + 3 * (size_t)min(u + (uint32_t)j, ue - 1u);
-                    a[j][0] = rp[0]; a[j][1] = rp[1]; a[j][2] = rp[2];
-                }
-#pragma unroll
-                for (int j = 0; j < LG_K9_GATHER; j++) {
-                    if (u + (uint32_t)j < ue) {
-                        mo[0] += a[j][0].x; mo[1] += a[j][0].y; mo[2] += a[j][0].z; mo[3] += a[j][0].w; mo[4] += a[j][1].x; mo[5] += a[j][1].y;
-                        mo[6] += a[j][1].z; mo[7] += a[j][1].w; mo[8] += a[j][2].x;
-                    }
-                }
-            }
-        }
+        lg_k9_gather_lane(part, my_t, my_u0, coop, mo);
         // the rows are pixel-offset moments (lg_blend.h): finish them with this Gaussian's conic and opacity, exactly the
         // values the blend kernels used (its blend record)
         const float4 q0 = rec[LG_REC_F4 * (size_t)i], q1 = rec[LG_REC_F4 * (size_t)i + 1], q2 = rec[LG_REC_F4 * (size_t)i + 2];
         const float px = means3D[3 * (size_t)i], py = means3D[3 * (size_t)i + 1], pz = means3D[3 * (size_t)i + 2];
         float a[9];
         lg_rows_to_grads(mo, q0.z, q0.w, q1.x, q1.y, a);
-        // 3D covariance: the precomputed input, or recomputed from the (activated) scales / rotation exactly as K1 did
-        float S[6], sc[3] = {0, 0, 0}, q[4] = {0, 0, 0, 0}, qn = 1.0f;
-        if (cov3D_precomp) {
-#pragma unroll
-            for (int k = 0; k < 6; k++) S[k] = cov3D_precomp[6 * (size_t)i + k];
-        } else {
-            sc[0] = scales[3 * (size_t)i]; sc[1] = scales[3 * (size_t)i + 1]; sc[2] = scales[3 * (size_t)i + 2];
-            const float4 q4 = *reinterpret_cast<const float4*>(rotations + 4 * (size_t)i);
-            q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
-            if (RAW) {
-                sc[0] = expf(sc[0]); sc[1] = expf(sc[1]); sc[2] = expf(sc[2]);
-                qn = fmaxf(sqrtf((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3])), 1e-12f);
-                q[0] /= qn; q[1] /= qn; q[2] /= qn; q[3] /= qn;     // exactly K1's operations (pairwise sum, division: see there)
-            }
-            lg_cov3d(sc, mod, q, S);
-        }
+        float Sg[6], sc[3], q[4], qn;
+        lg_k9_cov3d<RAW>(i, mod, cov3D_precomp, scales, rotations, Sg, sc, q, qn);
         LgGradOut go;
-        lg_backward_geom(vm, pm, px, py, pz, S, a, W, H, tanfovx, tanfovy, go);
+        lg_backward_geom(vm, pm, px, py, pz, Sg, a, W, H, tanfovx, tanfovy, go);
         m2[0] = go.mean2D[0]; m2[1] = go.mean2D[1];
         m3[0] = go.mean3D[0]; m3[1] = go.mean3D[1]; m3[2] = go.mean3D[2];
         dop = a[5];
         if (colors_precomp) {
             dcol[0] = a[6]; dcol[1] = a[7]; dcol[2] = a[8];
         } else if (use_sh) {
-            const uint32_t cb = __float_as_uint(q2.w) >> LG_ID_BITS;
-            float dRGB[3] = { (cb & 1u) ? 0.0f : a[6], (cb & 2u) ? 0.0f : a[7], (cb & 4u) ? 0.0f : a[8] };
+            float dRGB[3];
+            lg_k9_drgb(q2.w, a, dRGB);
             if (rgb_only) { dcol[0] = dRGB[0]; dcol[1] = dRGB[1]; dcol[2] = dRGB[2]; }
             if (JAC) {
-                const float* jr = shjac + 9 * (size_t)i;          // 36-byte rows: dword-aligned 16-byte loads
-                const lg_f4u j0 = reinterpret_cast<const lg_f4u*>(jr)[0], j1 = reinterpret_cast<const lg_f4u*>(jr)[1];
-                const float J[9] = { j0.x, j0.y, j0.z, j0.w, j1.x, j1.y, j1.z, j1.w, jr[8] };
+                float J[9];
+                lg_k9_jac_row(shjac, i, J);
                 lg_backward_sh_jac(D, J, px, py, pz, cp, dRGB, m3, [&](int k, int c, float v) { dsh[k * 3 + c] = v; });
             } else {
             float sh[LG_SH_MAXF];
