@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from . import rasterizer as _rasterizer
-from .rasterizer import _Call, _native_forward, _prep, _ptr
+from .rasterizer import _bare_view, _Call, _finish_forward, _GradSet, _native_forward, _prep, _ptr, _stream
 
 FEATURES_MAX = _lib.FEATURES_MAX
 _warned = [False]
@@ -47,33 +47,43 @@ def _check_features(features, bg_features):
         raise RuntimeError("blend_features needs tensors on a HIP device (torch 'cuda'); there is no CPU path")
 
 
+def _forward_then_blend(features, bg_features, means3D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp, rs, options,
+                        differentiated):
+    """The ordinary forward of the view, then lg_blend_features over the lists it left.  Returns (opts, call, bg, the outputs
+    (out, alpha, color, radii), the buffers (geom, binning, img), num_rendered)."""
+    lib = _lib.load()
+    opts = _rasterizer.resolve_options(options)
+    call = _Call(rs, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, exact=False, opts=opts,
+                 differentiated=differentiated)
+    if features.device != call.dev or features.shape[0] != call.N:
+        raise ValueError("features must hold one row per Gaussian, on the Gaussians' device")
+    dev, c = call.dev, int(features.shape[1])
+    h, w = int(rs.image_height), int(rs.image_width)
+    bg = _prep(bg_features, dev)
+    with torch.cuda.device(dev):
+        color, radii, _gc, _sc, geom, binning, img, num_rendered = _native_forward(lib, call, rs, False)
+        out = torch.empty((c, h, w), dtype=torch.float32, device=dev)
+        alpha = torch.empty((h, w), dtype=torch.float32, device=dev)
+        _lib.check(lib.lg_blend_features(C.byref(call.view), call.N, _ptr(geom), _ptr(binning), C.c_int64(num_rendered), _ptr(features), c,
+                                         _ptr(bg), _ptr(out), _ptr(alpha), _stream()))
+    if binning is None:     # (an empty tensor stands in for it among the saved ones)
+        binning = torch.empty(0, dtype=torch.uint8, device=dev)
+    return opts, call, bg, (out, alpha, color, radii), (geom, binning, img), num_rendered
+
+
 class _BlendFeatures(torch.autograd.Function):
     @staticmethod
     def forward(ctx, features, bg_features, means3D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp, rs, options):
-        lib = _lib.load()
-        opts = _rasterizer.resolve_options(options)
-        call = _Call(rs, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, exact=False, opts=opts,
-                     differentiated=False)
-        if features.device != call.dev or features.shape[0] != call.N:
-            raise ValueError("features must hold one row per Gaussian, on the Gaussians' device")
-        dev, n, c = call.dev, call.N, int(features.shape[1])
-        h, w = int(rs.image_height), int(rs.image_width)
-        bg = _prep(bg_features, dev)
-        with torch.cuda.device(dev):
-            color, radii, _gc, _sc, geom, binning, _img, num_rendered = _native_forward(lib, call, rs, False)
-            out = torch.empty((c, h, w), dtype=torch.float32, device=dev)
-            alpha = torch.empty((h, w), dtype=torch.float32, device=dev)
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(lib.lg_blend_features(C.byref(call.view), n, _ptr(geom), _ptr(binning), C.c_int64(num_rendered), _ptr(features), c,
-                                             _ptr(bg), _ptr(out), _ptr(alpha), stream))
-        ctx.view_args = (h, w, float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier), int(rs.sh_degree), int(call.view.flags),
-                         int(call.view.segment_length))
-        ctx.shape = (n, c)
+        _opts, call, _bg, outputs, (geom, binning, _img), num_rendered = _forward_then_blend(
+            features, bg_features, means3D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp, rs, options, differentiated=False)
+        ctx.raster_settings = rs
+        ctx.view_flags = (int(call.view.flags), int(call.view.segment_length))
+        ctx.shape = tuple(features.shape)
         ctx.num_rendered = num_rendered
-        ctx.save_for_backward(geom, binning if binning is not None else torch.empty(0, dtype=torch.uint8, device=dev))
-        ctx.mark_non_differentiable(alpha, color, radii)       # functions of the geometry, which is a constant here
+        ctx.save_for_backward(geom, binning)
+        ctx.mark_non_differentiable(*outputs[1:])       # alpha, color, radii: functions of the geometry, which is a constant here
         ctx.set_materialize_grads(False)
-        return out, alpha, color, radii
+        return outputs
 
     @staticmethod
     def backward(ctx, grad_out, *_unused):
@@ -83,17 +93,14 @@ class _BlendFeatures(torch.autograd.Function):
         lib = _lib.load()
         geom, binning = ctx.saved_tensors
         n, c = ctx.shape
-        h, w, tanx, tany, mod, deg, flags, seg = ctx.view_args
         dev = geom.device
         grad_out = _prep(grad_out, dev)
-        # only the image size, the flags and the segment length of the forward's view are read
-        view = _lib.lg_view(h, w, tanx, tany, None, mod, None, None, deg, None, 0, flags, seg)
+        view = _bare_view(ctx.raster_settings, *ctx.view_flags)
         with torch.cuda.device(dev):
             d_feat = torch.empty((n, c), dtype=torch.float32, device=dev)
             scratch = torch.empty(max(int(lib.lg_features_scratch_bytes(n, ctx.num_rendered, c)), 1), dtype=torch.uint8, device=dev)
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             _lib.check(lib.lg_blend_features_backward(C.byref(view), n, _ptr(geom), _ptr(binning) if binning.numel() else None,
-                                                      C.c_int64(ctx.num_rendered), _ptr(grad_out), c, _ptr(d_feat), _ptr(scratch), stream))
+                                                      C.c_int64(ctx.num_rendered), _ptr(grad_out), c, _ptr(d_feat), _ptr(scratch), _stream()))
         return (d_feat,) + none
 
 
@@ -103,71 +110,37 @@ class _BlendFeaturesGeom(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, features, bg_features, means3D, means2D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp, rs, options):
-        lib = _lib.load()
-        opts = _rasterizer.resolve_options(options)
-        call = _Call(rs, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, exact=False, opts=opts,
-                     differentiated=True)
-        if features.device != call.dev or features.shape[0] != call.N:
-            raise ValueError("features must hold one row per Gaussian, on the Gaussians' device")
-        dev, n, c = call.dev, call.N, int(features.shape[1])
-        h, w = int(rs.image_height), int(rs.image_width)
-        bg = _prep(bg_features, dev)
-        with torch.cuda.device(dev):
-            color, radii, _gc, _sc, geom, binning, img, num_rendered = _native_forward(lib, call, rs, False)
-            out = torch.empty((c, h, w), dtype=torch.float32, device=dev)
-            alpha = torch.empty((h, w), dtype=torch.float32, device=dev)
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(lib.lg_blend_features(C.byref(call.view), n, _ptr(geom), _ptr(binning), C.c_int64(num_rendered), _ptr(features), c,
-                                             _ptr(bg), _ptr(out), _ptr(alpha), stream))
-        ctx.raster_settings = rs
-        ctx.num_rendered = num_rendered
-        ctx.opts = {k: v for k, v in opts.items() if k not in _rasterizer._PER_CALL_ONLY}    # the backward runs with the forward's options
-        ctx.had = (shs is not None and shs.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
-                   scales is not None and scales.numel() > 0, cov3D_precomp is not None and cov3D_precomp.numel() > 0)
-        empty = torch.empty(0, dtype=torch.uint8, device=dev)
-        ctx.save_for_backward(features, bg if bg is not None else empty, call.means3D, call.sh, call.colors, call.opac, call.scales, call.rots,
-                              call.cov, radii, geom, binning if binning is not None else empty, img)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return out, alpha, color, radii
+        opts, call, bg, outputs, (geom, binning, img), num_rendered = _forward_then_blend(
+            features, bg_features, means3D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp, rs, options, differentiated=True)
+        _finish_forward(ctx, rs, num_rendered, opts)
+        ctx.save_for_backward(features, bg if bg is not None else binning.new_empty(0), call.means3D, call.sh, call.colors, call.opac,
+                              call.scales, call.rots, call.cov, outputs[3], geom, binning, img)
+        ctx.mark_non_differentiable(outputs[3])        # radii
+        return outputs
 
     @staticmethod
     def backward(ctx, grad_out, grad_alpha, grad_color, _grad_radii=None):
         lib = _lib.load()
-        rs = ctx.raster_settings
         features, bg, means3D, sh, colors, opac, scales, rots, cov, radii, geom, binning, img = ctx.saved_tensors
         if features.shape[0] == 0:          # an empty model: nothing was rendered, and the empty inputs were not kept
             z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=features.device)  # noqa: E731
             return (z(0, features.shape[1]), None, z(0, 3), z(0, 3), z(0, 1)) + (None,) * 7
-        call = _Call(rs, means3D, sh, colors, opac, scales, rots, cov, exact=False, opts=ctx.opts, differentiated=True)
-        dev, n, m = call.dev, call.N, call.M
-        c = int(features.shape[1])
-        f32 = dict(dtype=torch.float32, device=dev)
+        call = _Call(ctx.raster_settings, means3D, sh, colors, opac, scales, rots, cov, exact=False, opts=ctx.opts, differentiated=True)
+        dev, n, c = call.dev, call.N, int(features.shape[1])
         grad_out, grad_alpha, grad_color = _prep(grad_out, dev), _prep(grad_alpha, dev), _prep(grad_color, dev)
-        want_feat = ctx.needs_input_grad[0] and grad_out is not None
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             run = n > 0 and binning.numel() > 0       # (no Gaussians, or a forward that left no binning buffer: zero gradients)
             new = torch.empty if run else torch.zeros
-            g_means2D = new((n, 3), **f32)
-            g_means3D = new((n, 3), **f32)
-            g_opac = new((n, 1), **f32)
-            g_sh = new((n, m, 3), **f32) if call.sh is not None else None
-            g_col = new((n, 3), **f32) if call.colors is not None else None
-            g_sc = new((n, 3), **f32) if call.scales is not None else None
-            g_rot = new((n, 4), **f32) if call.rots is not None else None
-            g_cov = new((n, 6), **f32) if call.cov is not None else None
-            g_feat = new((n, c), **f32) if want_feat else None
+            g = _GradSet(call, new=new)
+            g_feat = new((n, c), dtype=torch.float32, device=dev) if (ctx.needs_input_grad[0] and grad_out is not None) else None
             if run:
                 scratch = torch.empty(max(int(lib.lg_backward_features_scratch_bytes(n, ctx.num_rendered, c)), 1), dtype=torch.uint8, device=dev)
                 _lib.check(lib.lg_backward_features(
                     C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img),
                     C.c_int64(ctx.num_rendered), _ptr(grad_color), _ptr(features), c, _ptr(bg) if bg.numel() else None, _ptr(grad_out),
-                    _ptr(grad_alpha), _ptr(g_means2D), _ptr(g_means3D), _ptr(g_sh), _ptr(g_col), _ptr(g_opac), _ptr(g_sc), _ptr(g_rot),
-                    _ptr(g_cov), None, _ptr(g_feat), _ptr(scratch), stream))
-        had_sh, had_col, had_sc, had_cov = ctx.had
-        return (g_feat, None, g_means3D, g_means2D, g_opac, g_sc if had_sc else None, g_rot if had_sc else None, g_cov if had_cov else None,
-                g_sh if had_sh else None, g_col if had_col else None, None, None)
+                    _ptr(grad_alpha), *g.ptrs(), _ptr(g_feat), _ptr(scratch), _stream()))
+        return (g_feat, None, g["means3D"], g["means2D"], g["opacity"], g["scales"], g["rotations"], g["cov3D"], g["shs"], g["colors"],
+                None, None)
 
 
 def blend_features(raster_settings, features, *, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, shs=None,

@@ -79,6 +79,13 @@ def _validate(name, value):
         raise ValueError("segment_length must be 0 (library default, 512) or a multiple of 64")
 
 
+def _check_options(kw):
+    for k, v in kw.items():
+        if k not in _OPTIONS and k not in _PER_CALL_ONLY:
+            raise KeyError(k)
+        _validate(k, v)
+
+
 def set_option(name, value):
     """Process default of one knob; returns the previous value.  (Per call: `options=` of GaussianRasterizer / render /
     count_render; per thread: `with rasterizer.options(...)`.)
@@ -152,10 +159,7 @@ class options:
     with each of them) and `status_override` (a [4] int32 tensor the next sync-free forward writes its status words to)."""
 
     def __init__(self, **kw):
-        for k, v in kw.items():
-            if k not in _OPTIONS and k not in _PER_CALL_ONLY:
-                raise KeyError(k)
-            _validate(k, v)
+        _check_options(kw)
         self.kw = kw
 
     def __enter__(self):
@@ -173,10 +177,7 @@ def resolve_options(overrides=None):
     for kw in getattr(_tls, "stack", ()):
         o.update(kw)
     if overrides:
-        for k, v in overrides.items():
-            if k not in _OPTIONS and k not in _PER_CALL_ONLY:
-                raise KeyError(k)
-            _validate(k, v)
+        _check_options(overrides)
         o.update(overrides)
     return o
 
@@ -219,6 +220,10 @@ def _call_backward(lib, args, grads_by_name):
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _prep(t, dev):
@@ -288,6 +293,12 @@ class _Call:
         self.g = _lib.lg_gaussians(N, M, _ptr(self.means3D), _ptr(self.sh), _ptr(self.colors), _ptr(self.opac),
                                    _ptr(self.scales), _ptr(self.rots), _ptr(self.cov), _ptr(self.sh_rest))
         self.N, self.M = N, M
+
+
+def _bare_view(rs, flags, segment_length):
+    """An lg_view without pointers, for the calls that read only its size, flags and segment length."""
+    return _lib.lg_view(int(rs.image_height), int(rs.image_width), float(rs.tanfovx), float(rs.tanfovy), None, float(rs.scale_modifier),
+                        None, None, int(rs.sh_degree), None, 0, int(flags), int(segment_length))
 
 
 # ---- sync-free forwards: capacity bookkeeping --------------------------------------------------------------------------
@@ -383,6 +394,11 @@ def _note_count(key, R, opts=None):
             _CAPACITY[key] = want
 
 
+def _check_row(name, t, dtype, dev, N):
+    if not (torch.is_tensor(t) and t.dtype == dtype and t.device == dev and t.shape == (N,) and t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[-1]} [N] tensor on the Gaussians' device")
+
+
 def _native_forward(lib, call, rs, count):
     """One forward through the C ABI.  Exact path (lg_forward / lg_forward_count: one blocking read of the instance count,
     as the reference extension) or, with option sync_free and a known capacity for this shape, lg_forward_bounded.
@@ -390,7 +406,7 @@ def _native_forward(lib, call, rs, count):
     opts = call.opts
     dev, N = call.dev, call.N
     H, W = int(rs.image_height), int(rs.image_width)
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = _stream()
     u8 = dict(dtype=torch.uint8, device=dev)
     geom = torch.empty(lib.lg_geom_bytes(N), **u8)
     img = torch.empty(lib.lg_img_bytes(W, H), **u8)
@@ -402,12 +418,11 @@ def _native_forward(lib, call, rs, count):
         score = opts.get("score_out")
         if score is None:
             score = torch.empty((N,), dtype=torch.float32, device=dev)
-        elif not (torch.is_tensor(score) and score.dtype == torch.float32 and score.device == dev and score.shape == (N,) and score.is_contiguous()):
-            raise ValueError("score_out must be a contiguous float32 [N] tensor on the Gaussians' device")
+        else:
+            _check_row("score_out", score, torch.float32, dev, N)
         csum = opts.get("count_sum")
         if csum is not None:
-            if not (torch.is_tensor(csum) and csum.dtype == torch.int32 and csum.device == dev and csum.shape == (N,) and csum.is_contiguous()):
-                raise ValueError("count_sum must be a contiguous int32 [N] tensor on the Gaussians' device")
+            _check_row("count_sum", csum, torch.int32, dev, N)
             call.view.count_sum = csum.data_ptr() if N > 0 else None
     key = (dev.index, N, W, H)
     mode = opts["sync_free"]
@@ -415,34 +430,32 @@ def _native_forward(lib, call, rs, count):
     cap = _CAPACITY.get(key) if (mode and N > 0 and not rs.prefiltered) else None
     if cap is not None and cap > 0:          # (-1: a depth beyond max_depth was seen for this shape -> exact path for good)
         binning = torch.empty(lib.lg_binning_bytes(cap, W, H, S), **u8)
+        # "validated": everything of the view is enqueued, then the host waits for the four status words that left right behind
+        # K2: it knows R and the abort flags before returning (safe drop-in), the device never idled.  Otherwise the words go to a
+        # device tensor nobody waits for (status_override: a caller-owned [4] int32 tensor that receives them)
+        host = status = None
         if mode == "validated":
-            # everything of the view is enqueued, then the host waits for the four status words that left right behind K2:
-            # it knows R and the abort flags before returning (safe drop-in), the device never idled
             host = (C.c_uint32 * 4)()
-            rc = lib.lg_forward_bounded(C.byref(call.view), C.byref(call.g), _ptr(geom), _ptr(img), _ptr(binning), cap,
-                                        float(opts["max_depth"]), weight_policy_id(opts["weight_policy"]), _ptr(color), _ptr(radii),
-                                        _ptr(gcount), _ptr(score), None, C.byref(host), stream)
-            _lib.check(rc)
-            if host[0] == 0:
-                _note_count(key, int(host[3]), opts)
-                return color, radii, gcount, score, geom, binning, img, cap
-            with _CAP_LOCK:                        # the view did not fit (its kernels were no-ops): exact path below, same buffers
-                if host[0] & 2:
-                    _CAPACITY[key] = -1
-                else:
-                    _CAPACITY[key] = int(int(host[3]) * opts["capacity_margin"]) + 4096
-            del binning
         else:
-            # (status_override: a caller-owned [4] int32 tensor that receives the status words)
             status = opts.get("status_override")
             if status is None:
                 status = torch.empty(4, dtype=torch.int32, device=dev)
-            rc = lib.lg_forward_bounded(C.byref(call.view), C.byref(call.g), _ptr(geom), _ptr(img), _ptr(binning), cap,
-                                        float(opts["max_depth"]), weight_policy_id(opts["weight_policy"]), _ptr(color), _ptr(radii),
-                                        _ptr(gcount), _ptr(score), _ptr(status), None, stream)
-            _lib.check(rc)
+        rc = lib.lg_forward_bounded(C.byref(call.view), C.byref(call.g), _ptr(geom), _ptr(img), _ptr(binning), cap,
+                                    float(opts["max_depth"]), weight_policy_id(opts["weight_policy"]), _ptr(color), _ptr(radii),
+                                    _ptr(gcount), _ptr(score), _ptr(status), None if host is None else C.byref(host), stream)
+        _lib.check(rc)
+        if host is None:
             _note_pending(opts, status, key)
             return color, radii, gcount, score, geom, binning, img, cap
+        if host[0] == 0:
+            _note_count(key, int(host[3]), opts)
+            return color, radii, gcount, score, geom, binning, img, cap
+        with _CAP_LOCK:                        # the view did not fit (its kernels were no-ops): exact path below, same buffers
+            if host[0] & 2:
+                _CAPACITY[key] = -1
+            else:
+                _CAPACITY[key] = int(int(host[3]) * opts["capacity_margin"]) + 4096
+        del binning
     holder = {}
 
     def _alloc(_user, nbytes):
@@ -476,6 +489,80 @@ def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp):
         raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
 
 
+class _GradSet:
+    """The per-Gaussian gradient buffers of one backward, by slot.  SLOTS is the order in which lg_backward, lg_backward_chunked
+    and lg_backward_features take their nine dL_d* pointers (include/lightgaussian.h); a slot whose input the call does not have
+    is None.  rgb_only: SH inputs whose backward writes dL/d(rgb) to the `colors` slot INSTEAD of the coefficient gradients (an
+    sh_grad_sink).  new: torch.empty, or torch.zeros where no kernel is going to write the buffers."""
+    SLOTS = ("means2D", "means3D", "shs", "colors", "opacity", "scales", "rotations", "cov3D", "shs_rest")
+    # what the gradient-chunk hook calls them: the rasterizer's argument names, and GaussianModel's parameters on the fused path
+    HOOK_NAMES = {False: (("means3D", "means3D"), ("shs", "shs"), ("colors_precomp", "colors"), ("opacities", "opacity"),
+                          ("scales", "scales"), ("rotations", "rotations"), ("cov3D_precomp", "cov3D")),
+                  True: (("_xyz", "means3D"), ("_features_dc", "shs"), ("_features_rest", "shs_rest"), ("_opacity", "opacity"),
+                         ("_scaling", "scales"), ("_rotation", "rotations"))}
+
+    def __init__(self, call, rgb_only=False, new=torch.empty):
+        f32 = dict(dtype=torch.float32, device=call.dev)
+
+        def rows(have, width):
+            return new((call.N, width), **f32) if have else None
+
+        def coeffs(t):      # ([N, M, 3]; on the fused path `shs` is _features_dc [N, 1, 3] and `shs_rest` the other rows)
+            return None if (t is None or rgb_only) else new((call.N, t.shape[1], 3), **f32)
+
+        self.rgb_only = rgb_only
+        self.by_slot = {"means2D": rows(True, 3), "means3D": rows(True, 3), "shs": coeffs(call.sh),
+                        "colors": rows(call.colors is not None or rgb_only, 3), "opacity": rows(True, 1),
+                        "scales": rows(call.scales is not None, 3), "rotations": rows(call.rots is not None, 4),
+                        "cov3D": rows(call.cov is not None, 6), "shs_rest": coeffs(call.sh_rest)}
+
+    def __getitem__(self, slot):
+        return self.by_slot[slot]
+
+    def ptrs(self):
+        return [_ptr(self.by_slot[s]) for s in self.SLOTS]
+
+    def by_hook_name(self, raw):
+        """name -> tensor, as the gradient-chunk hook receives them (dL/d(rgb) of an rgb_only backward is not a parameter's)."""
+        return {name: self.by_slot[s] for name, s in self.HOOK_NAMES[raw]
+                if self.by_slot[s] is not None and not (self.rgb_only and s == "colors")}
+
+
+def _finish_forward(ctx, rs, num_rendered, opts):
+    """What a differentiated forward leaves on ctx for its backward, besides the saved tensors."""
+    ctx.raster_settings = rs
+    ctx.num_rendered = num_rendered
+    ctx.opts = {k: v for k, v in opts.items() if k not in _PER_CALL_ONLY}   # the backward runs with the forward's options
+    ctx.sh_sink = opts.get("sh_grad_sink")
+    # no zero tensors for outputs nobody differentiated: autograd would hand the backward a materialised int32 [N] zero for
+    # `radii` on every step (12 MB fill at 3M Gaussians, measured 5.9 us per step); the backward accepts None
+    ctx.set_materialize_grads(False)
+
+
+def _backward(ctx, call, grad_color, radii, geom, binning, img, raw):
+    """The backward of one render: lg_backward (or _chunked), then lg_backward_camera on its scratch (option camera_grad), then
+    the sink.  Returns the _GradSet."""
+    lib = _lib.load()
+    rs, dev = ctx.raster_settings, call.dev
+    if grad_color is None:
+        grad_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32, device=dev)
+    grad_color = _prep(grad_color, dev)
+    with torch.cuda.device(dev):
+        stream = _stream()
+        sink = ctx.sh_sink if call.sh is not None else None
+        g = _GradSet(call, rgb_only=sink is not None)
+        scratch = torch.empty(lib.lg_backward_scratch_bytes(call.N, ctx.num_rendered), dtype=torch.uint8, device=dev)
+        rc = _call_backward(lib, (C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img),
+                                  C.c_int64(ctx.num_rendered), _ptr(grad_color), *g.ptrs(), _ptr(scratch), stream), g.by_hook_name(raw))
+        _lib.check(rc)
+        if ctx.opts["camera_grad"]:
+            ctx.cam_grads = _camera_backward(lib, call.view, call.g, dev, radii, geom, binning, ctx.num_rendered, scratch, stream)
+        if sink is not None:        # g["colors"] holds dL/d(rgb of the SH expansion); the coefficient gradients are the sink's business
+            sink.add(g["colors"], call.cp, int(rs.sh_degree))
+            g.by_slot["colors"] = None
+    return g
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, options=None):
@@ -487,18 +574,10 @@ class _RasterizeGaussians(torch.autograd.Function):
                      differentiated=opts.get("differentiated", any(ctx.needs_input_grad)))
         with torch.cuda.device(call.dev):
             color, radii, gcount, score, geom, binning, img, num_rendered = _native_forward(lib, call, rs, count)
-        ctx.raster_settings = rs
-        ctx.num_rendered = num_rendered
-        ctx.opts = {k: v for k, v in opts.items() if k not in _PER_CALL_ONLY}   # the backward runs with the forward's options
-        ctx.sh_sink = opts.get("sh_grad_sink")
-        ctx.had = (sh is not None and sh.numel() > 0, colors_precomp is not None and colors_precomp.numel() > 0,
-                   scales is not None and scales.numel() > 0, cov3Ds_precomp is not None and cov3Ds_precomp.numel() > 0)
+        _finish_forward(ctx, rs, num_rendered, opts)
         ctx.save_for_backward(call.means3D, call.sh, call.colors, call.opac, call.scales, call.rots, call.cov, radii,
                               geom, binning, img)
         ctx.mark_non_differentiable(radii)
-        # no zero tensors for outputs nobody differentiated: autograd would hand the backward a materialised int32 [N] zero for
-        # `radii` on every step (12 MB fill at 3M Gaussians, measured 5.9 us per step); the backward accepts None
-        ctx.set_materialize_grads(False)
         if count:
             ctx.mark_non_differentiable(gcount, score)
             return gcount, score, color, radii
@@ -506,44 +585,11 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        lib = _lib.load()
         rs = ctx.raster_settings
-        grad_color = grads[2] if rs.f_count else grads[0]
         means3D, sh, colors, opac, scales, rots, cov, radii, geom, binning, img = ctx.saved_tensors
         call = _Call(rs, means3D, sh, colors, opac, scales, rots, cov, exact=bool(rs.f_count), opts=ctx.opts, differentiated=True)
-        dev, N, M = call.dev, call.N, call.M
-        H, W = int(rs.image_height), int(rs.image_width)
-        f32 = dict(dtype=torch.float32, device=dev)
-        if grad_color is None:
-            grad_color = torch.zeros((3, H, W), **f32)
-        grad_color = _prep(grad_color, dev)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            g_means2D = torch.empty((N, 3), **f32)
-            g_means3D = torch.empty((N, 3), **f32)
-            g_opac = torch.empty((N, 1), **f32)
-            sink = ctx.sh_sink if call.sh is not None else None
-            g_sh = torch.empty((N, M, 3), **f32) if (call.sh is not None and sink is None) else None
-            g_col = torch.empty((N, 3), **f32) if (call.colors is not None or sink is not None) else None
-            g_sc = torch.empty((N, 3), **f32) if call.scales is not None else None
-            g_rot = torch.empty((N, 4), **f32) if call.rots is not None else None
-            g_cov = torch.empty((N, 6), **f32) if call.cov is not None else None
-            scratch = torch.empty(lib.lg_backward_scratch_bytes(N, ctx.num_rendered), dtype=torch.uint8, device=dev)
-            rc = _call_backward(lib, (C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img),
-                                      C.c_int64(ctx.num_rendered), _ptr(grad_color), _ptr(g_means2D), _ptr(g_means3D),
-                                      _ptr(g_sh), _ptr(g_col), _ptr(g_opac), _ptr(g_sc), _ptr(g_rot), _ptr(g_cov), None,
-                                      _ptr(scratch), stream),
-                                {k: v for k, v in (("means3D", g_means3D), ("shs", g_sh), ("colors_precomp", g_col if call.colors is not None else None), ("opacities", g_opac),
-                                                   ("scales", g_sc), ("rotations", g_rot), ("cov3D_precomp", g_cov)) if v is not None})
-            _lib.check(rc)
-            if ctx.opts["camera_grad"]:
-                ctx.cam_grads = _camera_backward(lib, call, radii, geom, binning, ctx.num_rendered, scratch, stream)
-            if sink is not None:            # rgb_only backward: g_col holds dL/d(rgb of the SH expansion); the coefficient gradients are the sink's business
-                sink.add(g_col, call.cp, int(rs.sh_degree))
-                g_col = None
-        had_sh, had_col, had_sc, had_cov = ctx.had
-        return (g_means3D, g_means2D, g_sh if had_sh else None, g_col if had_col else None, g_opac,
-                g_sc if had_sc else None, g_rot if had_sc else None, g_cov if had_cov else None, None, None)
+        g = _backward(ctx, call, grads[2] if rs.f_count else grads[0], radii, geom, binning, img, raw=False)
+        return (g["means3D"], g["means2D"], g["shs"], g["colors"], g["opacity"], g["scales"], g["rotations"], g["cov3D"], None, None)
 
 
 class _RasterizeGaussiansRaw(torch.autograd.Function):
@@ -563,11 +609,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                      differentiated=opts.get("differentiated", any(ctx.needs_input_grad)))
         with torch.cuda.device(call.dev):
             color, radii, _gc, _sc, geom, binning, img, num_rendered = _native_forward(lib, call, rs, False)
-        ctx.raster_settings = rs
-        ctx.num_rendered = num_rendered
-        ctx.opts = {k: v for k, v in opts.items() if k not in _PER_CALL_ONLY}
-        ctx.sh_sink = opts.get("sh_grad_sink")
-        ctx.has_rest = rest is not None
+        _finish_forward(ctx, rs, num_rendered, opts)
         ctx.rest_shape = None if features_rest is None else tuple(features_rest.shape)
         ctx.save_for_backward(call.means3D, call.sh, call.sh_rest, call.opac, call.scales, call.rots, radii, geom, binning, img)
         # visibility_filter (= radii > 0, gaussian_renderer/__init__.py:121) read in place: K1 leaves it as bytes in the geom buffer
@@ -578,115 +620,67 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         off = lib.lg_geom_visible_offset(call.N)
         visible = geom[off:off + call.N].view(torch.bool)
         ctx.mark_non_differentiable(radii, visible)
-        ctx.set_materialize_grads(False)               # (see _RasterizeGaussians.forward)
         return color, radii, visible
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, _grad_visible=None):
-        lib = _lib.load()
-        rs = ctx.raster_settings
         xyz, dc, rest, opac, scales, rots, radii, geom, binning, img = ctx.saved_tensors
-        call = _Call(rs, xyz, dc, None, opac, scales, rots, None, exact=False, sh_rest=rest, raw=True, opts=ctx.opts, differentiated=True)
-        dev, N = call.dev, call.N
-        H, W = int(rs.image_height), int(rs.image_width)
-        f32 = dict(dtype=torch.float32, device=dev)
-        grad_color = torch.zeros((3, H, W), **f32) if grad_color is None else _prep(grad_color, dev)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            g_means2D = torch.empty((N, 3), **f32); g_xyz = torch.empty((N, 3), **f32); g_opac = torch.empty((N, 1), **f32)
-            sink = ctx.sh_sink
-            g_dc = torch.empty((N, 1, 3), **f32) if sink is None else None
-            g_rest = torch.empty((N, rest.shape[1], 3), **f32) if (rest is not None and sink is None) else None
-            g_rgb = torch.empty((N, 3), **f32) if sink is not None else None
-            g_sc = torch.empty((N, 3), **f32); g_rot = torch.empty((N, 4), **f32)
-            scratch = torch.empty(lib.lg_backward_scratch_bytes(N, ctx.num_rendered), dtype=torch.uint8, device=dev)
-            rc = _call_backward(lib, (C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img),
-                                      C.c_int64(ctx.num_rendered), _ptr(grad_color), _ptr(g_means2D), _ptr(g_xyz), _ptr(g_dc), _ptr(g_rgb),
-                                      _ptr(g_opac), _ptr(g_sc), _ptr(g_rot), None, _ptr(g_rest), _ptr(scratch), stream),
-                                {k: v for k, v in (("_xyz", g_xyz), ("_features_dc", g_dc), ("_features_rest", g_rest), ("_opacity", g_opac),
-                                                   ("_scaling", g_sc), ("_rotation", g_rot)) if v is not None})
-            _lib.check(rc)
-            if ctx.opts["camera_grad"]:
-                ctx.cam_grads = _camera_backward(lib, call, radii, geom, binning, ctx.num_rendered, scratch, stream)
-            if sink is not None:
-                sink.add(g_rgb, call.cp, int(rs.sh_degree))
-                return g_xyz, g_means2D, None, None, g_opac, g_sc, g_rot, None, None
-        if g_rest is None and ctx.rest_shape is not None:
-            g_rest = torch.zeros(ctx.rest_shape, **f32)
-        return g_xyz, g_means2D, g_dc, g_rest, g_opac, g_sc, g_rot, None, None
+        call = _Call(ctx.raster_settings, xyz, dc, None, opac, scales, rots, None, exact=False, sh_rest=rest, raw=True, opts=ctx.opts,
+                     differentiated=True)
+        g = _backward(ctx, call, grad_color, radii, geom, binning, img, raw=True)
+        g_rest = g["shs_rest"]
+        if g_rest is None and ctx.rest_shape is not None and not g.rgb_only:    # a model without rest rows: its empty parameter's zero
+            g_rest = torch.zeros(ctx.rest_shape, dtype=torch.float32, device=call.dev)
+        return g["means3D"], g["means2D"], g["shs"], g_rest, g["opacity"], g["scales"], g["rotations"], None, None
 
 
-def _camera_backward(lib, call, radii, geom, binning, num_rendered, scratch, stream):
+def _camera_backward(lib, view, g, dev, radii, geom, binning, num_rendered, scratch, stream):
     """lg_backward_camera right behind the lg_backward call that filled `scratch`, on the same stream: (dL/dviewmatrix [4,4],
     dL/dprojmatrix [4,4], dL/dcampos [3]) on the Gaussians' device."""
-    f32 = dict(dtype=torch.float32, device=call.dev)
+    f32 = dict(dtype=torch.float32, device=dev)
     g_vm, g_pm, g_cp = torch.empty((4, 4), **f32), torch.empty((4, 4), **f32), torch.empty((3,), **f32)
-    cam_scratch = torch.empty(lib.lg_camera_scratch_bytes(call.N), dtype=torch.uint8, device=call.dev)
-    rc = lib.lg_backward_camera(C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(geom), _ptr(binning), C.c_int64(num_rendered),
+    cam_scratch = torch.empty(lib.lg_camera_scratch_bytes(g.N), dtype=torch.uint8, device=dev)
+    rc = lib.lg_backward_camera(C.byref(view), C.byref(g), _ptr(radii), _ptr(geom), _ptr(binning), C.c_int64(num_rendered),
                                 _ptr(scratch), _ptr(g_vm), _ptr(g_pm), _ptr(g_cp), _ptr(cam_scratch), stream)
     _lib.check(rc)
     return g_vm, g_pm, g_cp
 
 
-def _camera_forward(ctx, cls, viewmatrix, projmatrix, campos, args):
-    # (the kernels read the camera through raster_settings, which holds these same tensors: they are inputs here for autograd's sake)
-    ctx.cam_like = tuple((t.device, t.dtype, tuple(t.shape)) for t in (viewmatrix, projmatrix, campos))
-    ctx.cam_empty = args[0].device if args[0].shape[0] == 0 else None      # an empty model: see _camera_empty_backward
-    return cls.forward(ctx, *args)
-
-
 def _camera_empty_backward(ctx):
     """The camera gradients of an empty model (the plain backward has nothing to save and nothing to do there): lg_backward_camera
     with N = 0 writes the zeros."""
-    lib = _lib.load()
     rs, dev = ctx.raster_settings, ctx.cam_empty
-    view = _lib.lg_view(int(rs.image_height), int(rs.image_width), float(rs.tanfovx), float(rs.tanfovy), None, float(rs.scale_modifier), None, None,
-                        int(rs.sh_degree), None, 0, 0, int(ctx.opts["segment_length"]))
+    view = _bare_view(rs, 0, ctx.opts["segment_length"])
     g = _lib.lg_gaussians(0, 0, None, None, None, None, None, None, None, None)
-    f32 = dict(dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        ctx.cam_grads = (torch.empty((4, 4), **f32), torch.empty((4, 4), **f32), torch.empty((3,), **f32))
-        scratch = torch.empty(lib.lg_camera_scratch_bytes(0), dtype=torch.uint8, device=dev)
-        _lib.check(lib.lg_backward_camera(C.byref(view), C.byref(g), None, None, None, C.c_int64(0), None, _ptr(ctx.cam_grads[0]),
-                                          _ptr(ctx.cam_grads[1]), _ptr(ctx.cam_grads[2]), _ptr(scratch),
-                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    return _camera_grads_out(ctx)
+        return _camera_backward(_lib.load(), view, g, dev, None, None, None, 0, None, _stream())
 
 
-def _camera_grads_out(ctx):
-    return tuple(g.to(device=dev, dtype=dt).reshape(shape) for g, (dev, dt, shape) in zip(ctx.cam_grads, ctx.cam_like))
+def _with_camera_inputs(base, doc):
+    """`base` whose inputs also include the camera (option camera_grad): raster_settings.viewmatrix, .projmatrix and .campos in
+    front of the usual ones.  The backward is the base class's -- which, with the option on, calls lg_backward_camera on the
+    scratch of its lg_backward call -- with the three camera gradients in front."""
 
-
-class _RasterizeGaussiansCamera(_RasterizeGaussians):
-    """_RasterizeGaussians whose inputs also include the camera (option camera_grad): raster_settings.viewmatrix, .projmatrix and
-    .campos in front of the usual ones.  The backward is the base class's -- which, with the option on, calls lg_backward_camera on
-    the scratch of its lg_backward call -- with the three camera gradients in front."""
-
-    @staticmethod
     def forward(ctx, viewmatrix, projmatrix, campos, *args):
-        return _camera_forward(ctx, _RasterizeGaussians, viewmatrix, projmatrix, campos, args)
+        # (the kernels read the camera through raster_settings, which holds these same tensors: they are inputs here for autograd's sake)
+        ctx.cam_like = tuple((t.device, t.dtype, tuple(t.shape)) for t in (viewmatrix, projmatrix, campos))
+        ctx.cam_empty = args[0].device if args[0].shape[0] == 0 else None      # an empty model: see _camera_empty_backward
+        ctx.cam_base_inputs = len(args)
+        return base.forward(ctx, *args)
 
-    @staticmethod
     def backward(ctx, *grads):
         if ctx.cam_empty is not None:
-            return _camera_empty_backward(ctx) + (None,) * 10
-        out = _RasterizeGaussians.backward(ctx, *grads)
-        return _camera_grads_out(ctx) + tuple(out)
+            ctx.cam_grads, out = _camera_empty_backward(ctx), (None,) * ctx.cam_base_inputs
+        else:
+            out = tuple(base.backward(ctx, *grads))
+        return tuple(g.to(device=dev, dtype=dt).reshape(shape) for g, (dev, dt, shape) in zip(ctx.cam_grads, ctx.cam_like)) + out
+
+    return type(base)(base.__name__ + "Camera", (base,), {"__doc__": doc, "__module__": __name__, "forward": staticmethod(forward),
+                                                            "backward": staticmethod(backward)})
 
 
-class _RasterizeGaussiansRawCamera(_RasterizeGaussiansRaw):
-    """The camera_grad twin of _RasterizeGaussiansRaw (see _RasterizeGaussiansCamera)."""
-
-    @staticmethod
-    def forward(ctx, viewmatrix, projmatrix, campos, *args):
-        return _camera_forward(ctx, _RasterizeGaussiansRaw, viewmatrix, projmatrix, campos, args)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        if ctx.cam_empty is not None:
-            return _camera_empty_backward(ctx) + (None,) * 9
-        out = _RasterizeGaussiansRaw.backward(ctx, *grads)
-        return _camera_grads_out(ctx) + tuple(out)
+_RasterizeGaussiansCamera = _with_camera_inputs(_RasterizeGaussians, "_RasterizeGaussians with the camera among its inputs (see _with_camera_inputs).")
+_RasterizeGaussiansRawCamera = _with_camera_inputs(_RasterizeGaussiansRaw, "The camera_grad twin of _RasterizeGaussiansRaw (see _with_camera_inputs).")
 
 
 def option_value(name, overrides=None):
@@ -729,30 +723,23 @@ def _wants_grad(options, *tensors):
     return dict(options or {}, differentiated=want)
 
 
+def _rasterize(function, camera_function, inputs, rs, options):
+    """function.apply on the per-Gaussian inputs of one render, or with option camera_grad camera_function.apply."""
+    if _camera_grad_requested(options, rs):
+        camera = (rs.viewmatrix, rs.projmatrix, rs.campos)
+        return camera_function.apply(*camera, *inputs, rs, _wants_grad(options, *inputs, *camera))
+    return function.apply(*inputs, rs, _wants_grad(options, *inputs))
+
+
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_logit, log_scales, raw_rotations, raster_settings,
                             options=None):
-    if _camera_grad_requested(options, raster_settings):
-        rs = raster_settings
-        options = _wants_grad(options, xyz, means2D, features_dc, features_rest, opacity_logit, log_scales, raw_rotations,
-                              rs.viewmatrix, rs.projmatrix, rs.campos)
-        return _RasterizeGaussiansRawCamera.apply(rs.viewmatrix, rs.projmatrix, rs.campos, xyz, means2D, features_dc, features_rest,
-                                                  opacity_logit, log_scales, raw_rotations, rs, options)
-    options = _wants_grad(options, xyz, means2D, features_dc, features_rest, opacity_logit, log_scales, raw_rotations)
-    return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity_logit, log_scales, raw_rotations,
-                                        raster_settings, options)
+    return _rasterize(_RasterizeGaussiansRaw, _RasterizeGaussiansRawCamera, (xyz, means2D, features_dc, features_rest, opacity_logit, log_scales, raw_rotations), raster_settings, options)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, options=None):
-    if _camera_grad_requested(options, raster_settings):
-        rs = raster_settings
-        options = _wants_grad(options, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                              rs.viewmatrix, rs.projmatrix, rs.campos)
-        return _RasterizeGaussiansCamera.apply(rs.viewmatrix, rs.projmatrix, rs.campos, means3D, means2D, sh, colors_precomp, opacities,
-                                               scales, rotations, cov3Ds_precomp, rs, options)
-    options = _wants_grad(options, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, options)
+    return _rasterize(_RasterizeGaussians, _RasterizeGaussiansCamera, (means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                                                        cov3Ds_precomp), raster_settings, options)
 
 
 class GaussianRasterizer(nn.Module):
