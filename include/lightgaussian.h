@@ -92,6 +92,17 @@ enum {
     LG_FLAG_COUNT_WIDE_BAND = 8192, /* tests only: the parallel long-tile walk of the significance-only pass compares regrouped transmittances with
                                        the 1e-4 threshold through an error band; this widens the band 4096 x, sending a fifth of the saturating pixels
                                        through the exact fix-up pass instead of a handful per view.  Counts must not change. */
+    LG_FLAG_ANTIALIAS = 16384, /* opacity compensation of the fixed 0.3-pixel screen-space blur (Mip-Splatting's 2D filter, the `antialiasing`
+                                  switch of upstream 3DGS): with S the 2D covariance of a splat before the blur, K1 scales its opacity by
+                                  rho = sqrt(max(0.000025, det S / det(S + 0.3 I))) -- in the blend record and in the alpha >= 1/255 footprint
+                                  cull; radii and the reference tile rectangles do not change -- and K9 / lg_camera_bwd carry the gradient
+                                  through rho to the opacity, the covariance, the mean and the camera.  Honoured by lg_forward,
+                                  lg_forward_count, lg_forward_bounded, lg_backward, lg_backward_chunked, lg_backward_features and
+                                  lg_backward_camera; ignored by everything else (lg_blend_features and its backward read the records the
+                                  forward left).  The forward of a view and EVERY backward of that view must carry the same value: a backward
+                                  that disagrees differentiates another function than the one rendered (nothing detects it).  The
+                                  LG_WEIGHT_OPACITY score keeps the raw opacity (a property of the model, not of the view); hit counts and
+                                  the per-hit weights follow the compensated alpha.  Without the flag every kernel launched is unchanged. */
     /* (4096 was LG_FLAG_BWD_SPLAT_PARALLEL, the round-5 prototype of the backward blend on the other parallel axis: removed in ABI 7) */
     LG_FLAG_RAW_PARAMS = 8 /* "fused getters" (SURVEY 8f row 1): the inputs are GaussianModel's RAW parameters and the
                               activations of scene/gaussian_model.py:98-118 run inside the kernels: scales = log-scales (exp),

@@ -24,6 +24,7 @@ FLAG_NARROW_KEY, FLAG_SORT_ALL_BITS, FLAG_K1_LDS = 64, 128, 256
 FLAG_LONG_SERIAL, FLAG_LONG_PARALLEL = 512, 1024
 FLAG_SAVE_SH_JACOBIAN = 2048
 FLAG_COUNT_WIDE_BAND = 8192
+FLAG_ANTIALIAS = 16384
 ADAM_DECOUPLED_WD = 1       # lg_adam_step flags: LG_ADAM_DECOUPLED_WD (AdamW), FLAG_PROFILE
 ADAM_MAX_TENSORS = 8        # LG_ADAM_MAX_TENSORS: tensors per launch of lg_adam_step
 ADAM_SPAN = 4096            # LG_ADAM_SPAN: elements per workgroup of lg_adam_step

@@ -4,7 +4,7 @@
 //   lg_plan.h        host-side plans of one forward, plain C++ (also compiled by the CPU tests): KeyPlan (sort-key layout), ForwardPlan (kernel variants)
 //   lg_host.h        error strings, optional hipEvent profiler, scratch carving (GeomView / ImgView / BinView)
 //   lg_wave.h        wave64 primitives (DPP / permlane reductions)
-//   lg_preprocess.h  K1 lg_preprocess<RAW>, K8+K9 lg_preprocess_bwd<RAW>            (per Gaussian, HBM-bound); lg_k9_*: K9's read side, shared with lg_camera.h
+//   lg_preprocess.h  K1 lg_preprocess<RAW, DIRECT, AA>, K8+K9 lg_preprocess_bwd<RAW, JAC, AA> (AA: LG_FLAG_ANTIALIAS)   (per Gaussian, HBM-bound); lg_k9_*: K9's read side, shared with lg_camera.h
 //   lg_binning.h     K2 lg_scan_blocks, K3 lg_duplicate, lg_tile_sort / _long (second sort stage), lg_tile_ranges (one-stage cross-check only),
 //                    lg_work_order (K2-K5 all hand-written; lg_sort.h = K4)
 //   lg_loss.h        lg_loss_fwd / lg_loss_bwd: fused L1 + SSIM of the training step             (a wave per 64-column strip, register ring)
@@ -21,7 +21,7 @@
 //   lg_densify.h     lg_densify_stats / lg_densify_plan / lg_densify_rows: view statistics and clone / split / prune of densify_and_prune
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound); wave_reduce_via_lds<NV> (also lg_features.h's)
 //   lg_features.h    lg_features_fwd / _bwd / _gather: C further per-Gaussian channels blended over the lists a forward left, and dL/dfeatures
-//   lg_camera.h      lg_camera_bwd<RAW> / lg_camera_reduce: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos from the rows a backward left, through lg_k9_* (float64 ordered sums)
+//   lg_camera.h      lg_camera_bwd<RAW, AA> / lg_camera_reduce: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos from the rows a backward left, through lg_k9_* (float64 ordered sums)
 //
 // Pipeline of one view:
 //   K1 project + EWA + SH->RGB + exact footprint culling  ->  K2 scan of instance counts, blocking read of R
@@ -150,11 +150,14 @@ struct PinnedSlot {
 
 // ---- template selection: one place per kernel, and exactly the instantiations named here ----
 static_assert(LG_W_ALPHA == LG_WEIGHT_ALPHA && LG_W_ALPHA_T == LG_WEIGHT_ALPHA_T, "ForwardPlan::fscore is the kernels' FSCORE");
-using PreprocessKernel = decltype(&lg_preprocess<false, false>);
-static PreprocessKernel preprocess_kernel(bool raw, bool direct)
+using PreprocessKernel = decltype(&lg_preprocess<false, false, false>);
+// (antialias: LG_FLAG_ANTIALIAS of the view -- carried beside the plans: ForwardPlan is pinned field by field)
+static PreprocessKernel preprocess_kernel(bool raw, bool direct, bool antialias)
 {
-    static const PreprocessKernel k[2][2] = { { lg_preprocess<false, false>, lg_preprocess<false, true> }, { lg_preprocess<true, false>, lg_preprocess<true, true> } };
-    return k[raw][direct];
+#define LG_K1(AA) { { lg_preprocess<false, false, AA>, lg_preprocess<false, true, AA> }, { lg_preprocess<true, false, AA>, lg_preprocess<true, true, AA> } }
+    static const PreprocessKernel k[2][2][2] = { LG_K1(false), LG_K1(true) };     // [antialias][raw][direct]
+#undef LG_K1
+    return k[antialias][raw][direct];
 }
 using BlendFwdKernel = decltype(&lg_blend_fwd<false, 0, true, true>);
 static BlendFwdKernel blend_fwd_kernel(const ForwardPlan& p)
@@ -170,12 +173,13 @@ static BlendFwdKernel blend_fwd_kernel(const ForwardPlan& p)
 }
 using BlendBwdKernel = decltype(&lg_blend_bwd<true>);
 static BlendBwdKernel blend_bwd_kernel(bool exact) { return exact ? lg_blend_bwd<true> : lg_blend_bwd<false>; }
-using PreprocessBwdKernel = decltype(&lg_preprocess_bwd<false, false>);
-static PreprocessBwdKernel preprocess_bwd_kernel(bool raw, bool jac)
+using PreprocessBwdKernel = decltype(&lg_preprocess_bwd<false, false, false>);
+static PreprocessBwdKernel preprocess_bwd_kernel(bool raw, bool jac, bool antialias)
 {
-    static const PreprocessBwdKernel k[2][2] = { { lg_preprocess_bwd<false, false>, lg_preprocess_bwd<false, true> },
-                                                 { lg_preprocess_bwd<true, false>, lg_preprocess_bwd<true, true> } };
-    return k[raw][jac];
+#define LG_K9(AA) { { lg_preprocess_bwd<false, false, AA>, lg_preprocess_bwd<false, true, AA> }, { lg_preprocess_bwd<true, false, AA>, lg_preprocess_bwd<true, true, AA> } }
+    static const PreprocessBwdKernel k[2][2][2] = { LG_K9(false), LG_K9(true) };  // [antialias][raw][jac]
+#undef LG_K9
+    return k[antialias][raw][jac];
 }
 
 // Arguments of the capacity-bounded forward (lg_forward_bounded); NULL = exact forward with its one read-back.
@@ -242,7 +246,7 @@ int Forward::front_end()
             // K1 runs faster with FEWER waves in flight where it reads SH rows: unused dynamic LDS caps it at 12 waves per CU there (the sweep,
             // K9's opposite behaviour and the significance pass's A/B: EXPERIMENTS.md, "K1 / K9")
             const size_t k1_dyn = (direct && g->shs && !g->colors_precomp && !plan.k1_skip_color) ? LG_K1_PAD_LDS : 0;
-            preprocess_kernel(raw, direct)<<<nblk, LG_PP, k1_dyn, stream>>>(
+            preprocess_kernel(raw, direct, v->flags & LG_FLAG_ANTIALIAS)<<<nblk, LG_PP, k1_dyn, stream>>>(
                 N, g->M, v->sh_degree, q.W, q.H, v->tanfovx, v->tanfovy, v->scale_modifier, v->prefiltered, plan.k1_skip_color ? 1 : 0, v->viewmatrix,
                 v->projmatrix, v->campos, g->means3D, g->shs, g->shs_rest, g->colors_precomp, g->opacities, g->scales, g->rotations, g->cov3D_precomp, geo,
                 out_radii, plan.k1_clears_count ? out_count : nullptr, out_score, k1_clear, k1_nclear, (v->flags & LG_FLAG_SAVE_SH_JACOBIAN) ? 1 : 0);
@@ -492,7 +496,7 @@ static void preprocess_bwd_launch(const lg_view* v, const lg_gaussians* g, const
         const int nb = std::min(per, nblk - first_blk);
         // (the view of a backward is the view of its forward: LG_FLAG_SAVE_SH_JACOBIAN says K1 left the SH direction Jacobians)
         const bool jac = (v->flags & LG_FLAG_SAVE_SH_JACOBIAN) && g->shs && (dL_dshs || rgb_only);
-        preprocess_bwd_kernel(v->flags & LG_FLAG_RAW_PARAMS, jac)<<<nb, LG_PP, 0, stream>>>(
+        preprocess_bwd_kernel(v->flags & LG_FLAG_RAW_PARAMS, jac, v->flags & LG_FLAG_ANTIALIAS)<<<nb, LG_PP, 0, stream>>>(
             N, first_blk, g->M, v->sh_degree, W, H, v->tanfovx, v->tanfovy, v->scale_modifier, v->viewmatrix, v->projmatrix, v->campos, g->means3D,
             g->shs, g->shs_rest, g->colors_precomp, g->opacities, g->scales, g->rotations, g->cov3D_precomp, radii, geo.rec, geo.counters, bin.meta,
             (uint32_t)S, geo.touched, geo.offsets, reinterpret_cast<const float4*>(rows), geo.shjac, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dshs_rest,
@@ -642,11 +646,15 @@ extern "C" int lg_backward_camera(const lg_view* v, const lg_gaussians* g, const
         BinView bin = carve_bin(const_cast<void*>(bin_p), R, q.W, q.H, q.S);
         {
             ProfScope ps(prof, "camera_bwd", stream);
-            auto kern = (v->flags & LG_FLAG_RAW_PARAMS) ? lg_camera_bwd<true> : lg_camera_bwd<false>;
+            // (LG_FLAG_ANTIALIAS: the compensation factor of the opacity depends on the camera -- those variants read the input opacities)
+            const bool raw = v->flags & LG_FLAG_RAW_PARAMS;
+            auto kern = (v->flags & LG_FLAG_ANTIALIAS) ? (raw ? lg_camera_bwd<true, true> : lg_camera_bwd<false, true>)
+                                                       : (raw ? lg_camera_bwd<true, false> : lg_camera_bwd<false, false>);
             kern<<<nwg, LG_CAM_THREADS, 0, stream>>>(N, g->M, v->sh_degree, q.W, q.H, v->tanfovx, v->tanfovy, v->scale_modifier, (uint32_t)R,
                                                      v->viewmatrix, v->projmatrix, v->campos, g->means3D, g->shs, g->scales, g->rotations,
                                                      g->cov3D_precomp, radii, geo.rec, geo.counters, bin.meta, (uint32_t)q.S, geo.touched,
-                                                     geo.offsets, reinterpret_cast<const float4*>(backward_scratch), geo.shjac, partials);
+                                                     geo.offsets, reinterpret_cast<const float4*>(backward_scratch), geo.shjac, partials,
+                                                     g->opacities);
         }
         KCHECK("lg_camera_bwd");
     }

@@ -1,4 +1,4 @@
-// lg_camera.h -- camera pose gradients: lg_camera_bwd<RAW> (per Gaussian, K9's read side) and lg_camera_reduce (one workgroup).
+// lg_camera.h -- camera pose gradients: lg_camera_bwd<RAW, AA> (per Gaussian, K9's read side) and lg_camera_reduce (one workgroup).
 // Part of liblightgaussian_hip.so (single translation unit: lg_api.hip includes the lg_*.h kernel headers; this one after all others).
 //
 // dL/dviewmatrix, dL/dprojmatrix, dL/dcampos of one view: 27 sums over its visible Gaussians of the per-Gaussian camera terms
@@ -32,7 +32,10 @@ __device__ __forceinline__ double lg_wave_sum_f64(double v)
     return v;
 }
 
-template <bool RAW>
+// AA (LG_FLAG_ANTIALIAS): the compensation factor of the opacity depends on the camera through T2 and the view-space mean; the terms
+// need the input opacity (`opacities`, the last parameter, activated as K1 did; never read when AA = false, whose instantiations are the
+// kernels as they were, instruction for instruction).
+template <bool RAW, bool AA>
 __global__ void __launch_bounds__(LG_CAM_THREADS)
 lg_camera_bwd(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, float mod, uint32_t rows_cap,
               const float* __restrict__ viewmatrix, const float* __restrict__ projmatrix, const float* __restrict__ campos,
@@ -40,7 +43,7 @@ lg_camera_bwd(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, f
               const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, const int32_t* __restrict__ radii,
               const float4* __restrict__ rec, const uint32_t* __restrict__ counters, const uint32_t* __restrict__ meta, uint32_t S,
               const uint32_t* __restrict__ touched, const uint32_t* __restrict__ offsets, const float4* __restrict__ part,
-              const float* __restrict__ shjac, double* __restrict__ partials)
+              const float* __restrict__ shjac, double* __restrict__ partials, const float* __restrict__ opacities)
 {
     __shared__ double wsum[LG_CAM_WAVES][LG_CAM_TERMS];
     const uint32_t lane = threadIdx.x & (LG_PP - 1), wave = threadIdx.x / LG_PP;
@@ -84,7 +87,8 @@ lg_camera_bwd(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, f
             lg_k9_jac_row(shjac, i, J);
             lg_backward_sh_jac(D, J, px, py, pz, cp, dRGB, d, [](int, int, float) {});
         }
-        lg_backward_camera_terms(vm, pm, px, py, pz, Sg, a, W, H, tanfovx, tanfovy, d, term);
+        const float op_in = !AA ? 0.0f : RAW ? lg_sigmoid(opacities[i]) : opacities[i];
+        lg_backward_camera_terms_t<AA>(vm, pm, px, py, pz, Sg, a, W, H, tanfovx, tanfovy, d, term, op_in);
     }
     (void)M;
 #pragma unroll

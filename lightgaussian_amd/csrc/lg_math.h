@@ -146,7 +146,7 @@ LG_HD void lg_ewa(const float* vm, float tx, float ty, float tz, float fx, float
     }
 }
 
-struct LgCov2D { float a, b, c, U[3], V[3]; };
+struct LgCov2D { float a, b, c, U[3], V[3]; float a0, c0; };   // a0, c0: the diagonal before the +0.3 blur (lg_aa_*)
 
 LG_HD void lg_cov2d(const float* T2, const float* S, LgCov2D& o)
 {
@@ -160,6 +160,44 @@ LG_HD void lg_cov2d(const float* T2, const float* S, LgCov2D& o)
     float b = o.U[0] * T2[3] + o.U[1] * T2[4] + o.U[2] * T2[5];
     float c = o.V[0] * T2[3] + o.V[1] * T2[4] + o.V[2] * T2[5];
     o.a = a + 0.3f; o.b = b; o.c = c + 0.3f;
+    o.a0 = a; o.c0 = c;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Opacity compensation of the blur (LG_FLAG_ANTIALIAS; Mip-Splatting's 2D filter, the `antialiasing` switch of upstream 3DGS).  With
+// (a0, b, c0) the 2D covariance before the blur and a = a0 + 0.3f, c = c0 + 0.3f (lg_cov2d's own sums):
+//   det0 = a0 c0 - b b    det1 = a c - b b    x = det0 / det1    rho = sqrt(max(0.000025, x))    op' = op rho
+// Canonical order (every product, difference, the division and the square root rounded on their own).  det1 == 0 is culled before
+// (lg_project); det0 <= 0 (a rank-one covariance, rounding) and a NaN x fall to the floor through fmaxf.
+#define LG_AA_FLOOR 0.000025f
+LG_HD float lg_aa_ratio(float a0, float b, float c0, float a, float c)
+{
+    const float det0 = a0 * c0 - b * b;
+    const float det1 = a * c - b * b;
+    return det0 / det1;
+}
+LG_HD float lg_aa_rho(float x) { return sqrtf(fmaxf(LG_AA_FLOOR, x)); }
+// Backward: gp = dL/dop' (acc[5] of lg_rows_to_grads).  Returns rho (dL/dop = rho gp) and ADDS gx dx/d(a0, b, c0) to the gradients of
+// the blurred covariance entries (a, b, c differ from a0, b, c0 by constants; b counts as one variable, as dL_db does), with
+// gx = dL/dx = op gp / (2 rho) above the floor and 0 at it.  The partials
+//   dx/da0 = (c0 det1 - det0 c) / det1^2     dx/dc0 = (a0 det1 - det0 a) / det1^2     dx/db = -2 b (det1 - det0) / det1^2
+// are evaluated in the form without the cancellation of two nearly equal products (h = 0.3: a = a0 + h, c = c0 + h):
+//   c0 det1 - det0 c = h (c0 c + b b)        a0 det1 - det0 a = h (a0 a + b b)        det1 - det0 = h (a0 + c0) + h h
+LG_HD float lg_aa_backward(float a0, float b, float c0, float a, float c, float op, float gp, float& dL_da, float& dL_db, float& dL_dc)
+{
+    const float det0 = a0 * c0 - b * b;
+    const float det1 = a * c - b * b;
+    const float x = det0 / det1;
+    const float rho = lg_aa_rho(x);
+    if (x > LG_AA_FLOOR) {
+        const float gx = (op * gp) * 0.5f / rho;
+        const float s = gx / (det1 * det1);
+        const float bb = b * b;
+        dL_da += s * (0.3f * (c0 * c + bb));
+        dL_dc += s * (0.3f * (a0 * a + bb));
+        dL_db += s * (-2.0f * b * (0.3f * (a0 + c0) + 0.09f));
+    }
+    return rho;
 }
 
 // Result of projecting one Gaussian (K1).
@@ -174,8 +212,12 @@ struct LgSplat {
 
 // Projection + EWA splat + radius + tile rectangles.  Returns false when the Gaussian is not
 // rasterised (near-culled, singular covariance, empty rectangle) -- radii must then be 0.
-LG_HD bool lg_project(const float* vm, const float* pm, float px, float py, float pz, const float* cov3D, float opacity,
-                      int W, int H, float tanfovx, float tanfovy, LgSplat& o)
+// AA (LG_FLAG_ANTIALIAS): the opacity is compensated for the blur (lg_aa_rho) in front of the footprint cull -- both the
+// `opacity < 1/255: no instances` branch and the tau = log(255 opacity) extents see op' -- and returned in op_out for the blend
+// record; the radius and the reference rectangle do not depend on it.  op_out is written only when AA, and only on `return true`.
+template <bool AA>
+LG_HD bool lg_project_t(const float* vm, const float* pm, float px, float py, float pz, const float* cov3D, float opacity,
+                        int W, int H, float tanfovx, float tanfovy, LgSplat& o, float& op_out)
 {
     float vx = vm[0] * px + vm[4] * py + vm[8] * pz + vm[12];
     float vy = vm[1] * px + vm[5] * py + vm[9] * pz + vm[13];
@@ -195,6 +237,7 @@ LG_HD bool lg_project(const float* vm, const float* pm, float px, float py, floa
     const float a = c2.a, b = c2.b, c = c2.c;
     float det = a * c - b * b;
     if (det == 0.0f) return false;
+    if (AA) { opacity = opacity * lg_aa_rho(lg_aa_ratio(c2.a0, b, c2.c0, a, c)); op_out = opacity; }
     float det_inv = 1.0f / det;
     float A = c * det_inv, B = -b * det_inv, C = a * det_inv;
     float mid = 0.5f * (a + c);
@@ -250,6 +293,12 @@ LG_HD bool lg_project(const float* vm, const float* pm, float px, float py, floa
         }
     }
     return true;
+}
+LG_HD bool lg_project(const float* vm, const float* pm, float px, float py, float pz, const float* cov3D, float opacity,
+                      int W, int H, float tanfovx, float tanfovy, LgSplat& o)
+{
+    float unused;
+    return lg_project_t<false>(vm, pm, px, py, pz, cov3D, opacity, W, H, tanfovx, tanfovy, o, unused);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -435,8 +484,12 @@ LG_HD void lg_rows_to_grads(const float* m, float ha, float nb, float hc, float 
     acc[6] = m[6]; acc[7] = m[7]; acc[8] = m[8];
 }
 
-LG_HD void lg_backward_geom(const float* vm, const float* pm, float px, float py, float pz, const float* S /*cov3D*/,
-                            const float* acc, int W, int H, float tanfovx, float tanfovy, LgGradOut& g)
+// AA (LG_FLAG_ANTIALIAS): acc[5] is dL/dop' of the compensated opacity op' = op rho; op = the input opacity (activated).  The three
+// terms of lg_aa_backward join dL_da, dL_db, dL_dc before they are chained to cov3D, T2 and the mean, and rho_out = rho, so that the
+// caller writes dL/dop = rho acc[5].  The +-1.3 tanfov clamp keeps its no-gradient convention (dtx, dty below).
+template <bool AA>
+LG_HD void lg_backward_geom_t(const float* vm, const float* pm, float px, float py, float pz, const float* S /*cov3D*/,
+                              const float* acc, int W, int H, float tanfovx, float tanfovy, LgGradOut& g, float op, float& rho_out)
 {
     const float fx = (float)W / (2.0f * tanfovx), fy = (float)H / (2.0f * tanfovy);
     const float gndx = acc[0] * (0.5f * (float)W), gndy = acc[1] * (0.5f * (float)H);
@@ -459,6 +512,7 @@ LG_HD void lg_backward_geom(const float* vm, const float* pm, float px, float py
         dL_dc = d2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
         dL_db = d2inv * (2.0f * b * c * gA - (denom + 2.0f * b * b) * gB + 2.0f * a * b * gC);
     }
+    if (AA) rho_out = lg_aa_backward(c2.a0, b, c2.c0, a, c, op, acc[5], dL_da, dL_db, dL_dc);
     g.cov3D[0] = T2[0] * T2[0] * dL_da + T2[0] * T2[3] * dL_db + T2[3] * T2[3] * dL_dc;
     g.cov3D[3] = T2[1] * T2[1] * dL_da + T2[1] * T2[4] * dL_db + T2[4] * T2[4] * dL_dc;
     g.cov3D[5] = T2[2] * T2[2] * dL_da + T2[2] * T2[5] * dL_db + T2[5] * T2[5] * dL_dc;
@@ -491,6 +545,12 @@ LG_HD void lg_backward_geom(const float* vm, const float* pm, float px, float py
     }
     g.mean3D[0] = dmx; g.mean3D[1] = dmy; g.mean3D[2] = dmz;
 }
+LG_HD void lg_backward_geom(const float* vm, const float* pm, float px, float py, float pz, const float* S /*cov3D*/,
+                            const float* acc, int W, int H, float tanfovx, float tanfovy, LgGradOut& g)
+{
+    float unused;
+    lg_backward_geom_t<false>(vm, pm, px, py, pz, S, acc, W, H, tanfovx, tanfovy, g, 0.0f, unused);
+}
 
 // Camera terms of one Gaussian (lg_camera.h: lg_camera_bwd sums them over the visible Gaussians): what lg_backward_geom computes on
 // its way to dL/dmean3D and drops -- dt = dL/d(view-space mean) through the EWA Jacobian, dT = dL/d(T2 = J Wrot), the J entries, the
@@ -505,8 +565,12 @@ LG_HD void lg_backward_geom(const float* vm, const float* pm, float px, float py
 // zeroed dtx / dty on clamped lanes, the 1e-7 in d2inv): duplicated, not shared, so that every existing kernel stays as it was compiled.
 // In real arithmetic  dL/dmean3D = vm[:3,:3] g_vm[3,:3] + pm[:3,:] g_pm[3,:] - g_cp  (tests/test_camera_host.py).
 #define LG_CAM_TERMS 27
-LG_HD void lg_backward_camera_terms(const float* vm, const float* pm, float px, float py, float pz, const float* S /*cov3D*/,
-                                    const float* acc, int W, int H, float tanfovx, float tanfovy, const float d[3], float* out /*[27]*/)
+// AA (LG_FLAG_ANTIALIAS): rho depends on the view matrix through T2 and the view-space mean -- the same three terms as in
+// lg_backward_geom_t join dL_da, dL_db, dL_dc (acc[5] = dL/dop', op = the input opacity).
+template <bool AA>
+LG_HD void lg_backward_camera_terms_t(const float* vm, const float* pm, float px, float py, float pz, const float* S /*cov3D*/,
+                                      const float* acc, int W, int H, float tanfovx, float tanfovy, const float d[3], float* out /*[27]*/,
+                                      float op)
 {
     const float fx = (float)W / (2.0f * tanfovx), fy = (float)H / (2.0f * tanfovy);
     const float gndx = acc[0] * (0.5f * (float)W), gndy = acc[1] * (0.5f * (float)H);
@@ -527,6 +591,7 @@ LG_HD void lg_backward_camera_terms(const float* vm, const float* pm, float px, 
         dL_dc = d2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
         dL_db = d2inv * (2.0f * b * c * gA - (denom + 2.0f * b * b) * gB + 2.0f * a * b * gC);
     }
+    if (AA) lg_aa_backward(c2.a0, b, c2.c0, a, c, op, acc[5], dL_da, dL_db, dL_dc);
     const float* U = c2.U; const float* V = c2.V;
     float dT0[3] = { 2.0f * dL_da * U[0] + dL_db * V[0], 2.0f * dL_da * U[1] + dL_db * V[1], 2.0f * dL_da * U[2] + dL_db * V[2] };
     float dT1[3] = { dL_db * U[0] + 2.0f * dL_dc * V[0], dL_db * U[1] + 2.0f * dL_dc * V[1], dL_db * U[2] + 2.0f * dL_dc * V[2] };
@@ -561,6 +626,11 @@ LG_HD void lg_backward_camera_terms(const float* vm, const float* pm, float px, 
     }
     out[21] = dh[0]; out[22] = dh[1]; out[23] = dh[2];
     out[24] = -d[0]; out[25] = -d[1]; out[26] = -d[2];
+}
+LG_HD void lg_backward_camera_terms(const float* vm, const float* pm, float px, float py, float pz, const float* S /*cov3D*/,
+                                    const float* acc, int W, int H, float tanfovx, float tanfovy, const float d[3], float* out /*[27]*/)
+{
+    lg_backward_camera_terms_t<false>(vm, pm, px, py, pz, S, acc, W, H, tanfovx, tanfovy, d, out, 0.0f);
 }
 
 // dL/dSigma(packed) -> dL/dscale, dL/dquaternion.  Like the published implementation the

@@ -78,7 +78,10 @@ __device__ __forceinline__ void read_row_direct(const float* __restrict__ row, i
 __device__ __forceinline__ float lg_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // 92 VGPRs -> 5 waves/SIMD.  Forcing 6 or 8 (amdgpu_waves_per_eu) spills 43 / 71 registers: measured 0.22 -> 0.28 / 0.45 ms.
-template <bool RAW, bool DIRECT>
+// AA (LG_FLAG_ANTIALIAS): the opacity of the blend record and of the footprint cull is the compensated one (lg_project_t<true>,
+// lg_math.h); everything else is the same code.  The AA = false instantiations are, instruction for instruction, the kernels that
+// existed before the mode did (tools/isa_diff.py).
+template <bool RAW, bool DIRECT, bool AA>
 #ifdef LG_K1_WAVES
 __global__ void __launch_bounds__(LG_PP) __attribute__((amdgpu_waves_per_eu(LG_K1_WAVES, 8)))
 #else
@@ -111,7 +114,7 @@ lg_preprocess(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, f
     for (int k = 0; k < 16; k++) { vm[k] = viewmatrix[k]; pm[k] = projmatrix[k]; }
     cp[0] = campos[0]; cp[1] = campos[1]; cp[2] = campos[2];
     bool vis = false, violation = false;
-    float px = 0, py = 0, pz = 0, op = 0;
+    float px = 0, py = 0, pz = 0, op = 0, op_aa = 0;
     float cov[6] = {0, 0, 0, 0, 0, 0};
     LgSplat sp;
     if (i < N) {
@@ -139,7 +142,7 @@ lg_preprocess(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, f
                 lg_cov3d(sc, mod, q, cov);
             }
             op = RAW ? lg_sigmoid(opacities[i]) : opacities[i];
-            vis = lg_project(vm, pm, px, py, pz, cov, op, W, H, tanfovx, tanfovy, sp);
+            vis = lg_project_t<AA>(vm, pm, px, py, pz, cov, op, W, H, tanfovx, tanfovy, sp, op_aa);
         } else if (prefiltered) {
             violation = true;   // "Point is filtered although prefiltered is set": reported through the per-workgroup word below
         }
@@ -200,7 +203,7 @@ lg_preprocess(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, f
                 }
             }
             st_rec[3 * lane + 0] = make_float4(sp.x, sp.y, sp.ha, sp.nb);
-            st_rec[3 * lane + 1] = make_float4(sp.hc, op, rgb[0], rgb[1]);
+            st_rec[3 * lane + 1] = make_float4(sp.hc, AA ? op_aa : op, rgb[0], rgb[1]);
             // last word: Gaussian id (29 bits) | SH clamp flags (3 bits, for K9).  No separate "backward record": K9 recomputes the
             // 3D covariance from the scales / rotation it reads anyway (the 32-byte aux rows of round 1 were 10 % of K1's traffic)
             st_rec[3 * lane + 2] = make_float4(rgb[2], sp.hx, sp.hy, __uint_as_float((uint32_t)i | (cb << LG_ID_BITS)));
@@ -370,7 +373,10 @@ __device__ __forceinline__ void lg_k9_jac_row(const float* shjac, int i, float (
 // (-DLG_K9_WAVES=4: 128 VGPRs, 76 B/lane of scratch) was measured in round 3: 0.384 -> 0.594 ms -- the spills cost more than the
 // fourth wave hides.  JAC = true (the default of every differentiated render since round 4: no coefficients, no input staging) 107 VGPRs
 // -> 4 waves/SIMD.  Reading the SH rows directly per lane as K1 does (JAC = false only) was measured: 0.380 vs 0.380 ms.
-template <bool RAW, bool JAC>
+// AA (LG_FLAG_ANTIALIAS; the view of a backward is the view of its forward): the record's opacity is op' = op rho, so the rows give
+// dL/dop'; op and rho are recomputed from the inputs, as the covariance is (lg_backward_geom_t<true>, lg_math.h) -- the geom buffer
+// does not grow.  The AA = false instantiations are the kernels that existed before the mode did, instruction for instruction.
+template <bool RAW, bool JAC, bool AA>
 #ifdef LG_K9_WAVES
 __global__ void __launch_bounds__(LG_PP) __attribute__((amdgpu_waves_per_eu(LG_K9_WAVES, 8)))
 #else
@@ -438,10 +444,13 @@ lg_preprocess_bwd(int N, int first_blk, int M, int D, int W, int H, float tanfov
         float Sg[6], sc[3], q[4], qn;
         lg_k9_cov3d<RAW>(i, mod, cov3D_precomp, scales, rotations, Sg, sc, q, qn);
         LgGradOut go;
-        lg_backward_geom(vm, pm, px, py, pz, Sg, a, W, H, tanfovx, tanfovy, go);
+        float rho = 1.0f;
+        // (AA: the input opacity, activated exactly as K1 did)
+        const float op_in = !AA ? 0.0f : RAW ? lg_sigmoid(opacities[i]) : opacities[i];
+        lg_backward_geom_t<AA>(vm, pm, px, py, pz, Sg, a, W, H, tanfovx, tanfovy, go, op_in, rho);
         m2[0] = go.mean2D[0]; m2[1] = go.mean2D[1];
         m3[0] = go.mean3D[0]; m3[1] = go.mean3D[1]; m3[2] = go.mean3D[2];
-        dop = a[5];
+        dop = AA ? rho * a[5] : a[5];
         if (colors_precomp) {
             dcol[0] = a[6]; dcol[1] = a[7]; dcol[2] = a[8];
         } else if (use_sh) {

@@ -67,6 +67,14 @@ def _camera_grad(options):
     return bool(_rasterizer.option_value("camera_grad", options))
 
 
+def _pipe_options(pipe, options):
+    """`options` with "antialiasing" switched on for a `pipe` that asks for it (the `antialiasing` attribute of upstream 3DGS's
+    PipelineParams; the reference's has none, so nothing changes for it) unless the call's own options set the key."""
+    if getattr(pipe, "antialiasing", False) and not (options and "antialiasing" in options):
+        return dict(options or {}, antialiasing=True)
+    return options
+
+
 def _screenspace_points(pc):
     """Zero tensor whose .grad receives the 2D (NDC) mean gradients, gaussian_renderer/__init__.py:37-46.  The reference
     builds it as zeros(..., requires_grad=True) + 0 followed by retain_grad(); a plain leaf gets its .grad the same way
@@ -123,7 +131,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 
     options={"camera_grad": True}: the image is also differentiable with respect to the camera's own world_view_transform,
     full_proj_transform and camera_center tensors, which are handed through as they are -- built under autograd (pose.PoseCamera),
-    the chain continues into the pose parameters.  Fused and unfused paths alike; compressed models are not supported."""
+    the chain continues into the pose parameters.  Fused and unfused paths alike; compressed models are not supported.
+
+    A `pipe` with a true `antialiasing` attribute (upstream 3DGS's spelling) renders with options={"antialiasing": True} -- the opacity
+    compensation of the 0.3-pixel blur, rasterizer.set_option -- unless `options` sets the key itself; count_render and render_features
+    read it the same way."""
+    options = _pipe_options(pipe, options)
     if isinstance(pc, (CompressedGaussians, TrainableCompressed)) and _camera_grad(options):
         raise NotImplementedError("camera_grad is not implemented for compressed models: render pc.to_dense() instead")
     if isinstance(pc, TrainableCompressed) and override_color is None:
@@ -155,6 +168,7 @@ def render_compressed(viewpoint_camera, cg, pipe, bg_color: torch.Tensor, scalin
     them as colors_precomp -- the [N, 3 M] float32 SH tensor is never built.  Same result dict as render(), same image bits as
     render() of cg.to_dense() with fuse_getters off.  Forward-only: runs under torch.no_grad(), nothing requires grad (to train,
     use cg.to_dense()).  The Python-side alternates of `pipe` need the dense tensors and are refused."""
+    options = _pipe_options(pipe, options)
     if _camera_grad(options):
         raise NotImplementedError("camera_grad is not implemented for compressed models: render cg.to_dense() instead")
     if pipe.convert_SHs_python or pipe.compute_cov3D_python:
@@ -170,6 +184,7 @@ def render_compressed_trainable(viewpoint_camera, tc, pipe, bg_color: torch.Tens
     """The grad-enabled twin of render_compressed for a vectree.TrainableCompressed: the same kernels on the same float16 rows
     (the image bits are render_compressed's), with autograd attached -- tc.colors() is differentiable (lg_vq_colors_bwd), the
     rasterizer returns dL/dcolors_precomp and the geometry gradients, viewspace_points stays attached for its .grad."""
+    options = _pipe_options(pipe, options)
     if _camera_grad(options):
         raise NotImplementedError("camera_grad is not implemented for compressed models: render tc.to_dense() instead")
     if pipe.convert_SHs_python or pipe.compute_cov3D_python:
@@ -181,6 +196,7 @@ def render_compressed_trainable(viewpoint_camera, tc, pipe, bg_color: torch.Tens
 def count_render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, *, options=None):
     """render() + per-Gaussian hit count and Global Significance score (f_count=True).  options: as for render(), e.g.
     {"skip_color_in_count": True} for passes that only consume the counts / scores."""
+    options = _pipe_options(pipe, options)
     if _camera_grad(options):
         raise NotImplementedError("camera_grad is not implemented for count renders: use render()")
     screenspace_points = _screenspace_points(pc)
@@ -200,6 +216,7 @@ def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_mod
     3M Gaussians costs as much HBM traffic as the whole rasterizer).  Reads GaussianModel's raw tensors
     (_xyz, _features_dc, _features_rest, _opacity, _scaling, _rotation: scene/gaussian_model.py:45-60) directly; same
     result dict, gradients land on the raw parameters.  Falls back to render() for the Python-side alternates."""
+    options = _pipe_options(pipe, options)
     if override_color is not None or pipe.convert_SHs_python or pipe.compute_cov3D_python:
         return _render_unfused(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, options)
     screenspace_points = _screenspace_points(pc)
@@ -236,6 +253,7 @@ def render_features(viewpoint_camera, pc, pipe, features, bg_features=None, scal
     photometric + depth + alpha loss, one backward (lg_backward_features) carries it to _xyz, _opacity, _scaling, _rotation and the
     colours.  The result gains "viewspace_points", whose .grad is the view-space gradient densification reads.  Compressed models are
     not supported in this mode."""
+    options = _pipe_options(pipe, options)
     from .features import blend_features
     if _camera_grad(options):
         raise NotImplementedError("camera_grad is not implemented for render_features: use render() for the pose gradient")

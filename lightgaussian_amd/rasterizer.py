@@ -44,7 +44,7 @@ class GaussianRasterizationSettings(NamedTuple):
 # the defaults: prune_list_sharded and backward_over_views pass what they need per call / per thread.
 _OPTIONS = {"weight_policy": _lib.WEIGHT_OPACITY, "fast_exp": True, "profile": False, "skip_color_in_count": False,
             "fuse_getters": True, "sync_free": "validated", "max_depth": 100.0, "capacity_margin": 1.25,
-            "segment_length": 0, "long_tiles": "auto", "count_long_tiles": "serial", "camera_grad": False,
+            "segment_length": 0, "long_tiles": "auto", "count_long_tiles": "serial", "camera_grad": False, "antialiasing": False,
             # cross-check switches of the tests: never needed in production, never read from the environment
             "sh_jacobian": True, "narrow_key": False, "sort_all_bits": False, "k1_lds": False, "count_wide_band": False}
 _PER_CALL_ONLY = ("pending", "tag", "status_override", "differentiated", "sh_grad_sink", "score_out", "count_sum")
@@ -75,6 +75,8 @@ def _validate(name, value):
         raise ValueError("count_long_tiles must be 'serial' or 'parallel'")
     if name == "camera_grad" and not isinstance(value, bool):
         raise ValueError("camera_grad must be True or False")
+    if name == "antialiasing" and not isinstance(value, bool):
+        raise ValueError("antialiasing must be True or False")
     if name == "segment_length" and (int(value) < 0 or (int(value) != 0 and (int(value) < 64 or int(value) % 64))):
         raise ValueError("segment_length must be 0 (library default, 512) or a multiple of 64")
 
@@ -135,6 +137,12 @@ def set_option(name, value):
               gather of the gradient rows, float64 ordered sums: deterministic), and the three tensors receive [4,4], [4,4] and [3]
               gradients; the per-Gaussian gradients are bit-identical to those with the option off.  Off: nothing changes.  Not
               available for count renders (f_count), with sh_jacobian=False, or with a gradient-chunk hook / sh_grad_sink installed;
+    antialiasing (default False): opacity compensation of the fixed 0.3-pixel screen-space blur (Mip-Splatting's 2D filter, the
+              `antialiasing` switch of upstream 3DGS): every splat's opacity is scaled by sqrt(max(0.000025, det S / det(S + 0.3 I))) of
+              its 2D covariance S, in K1, and K9 / lg_camera_bwd carry the gradient through the factor (LG_FLAG_ANTIALIAS).  Radii and
+              the reference tile rectangles do not change; images, hit counts and the per-hit significance weights do; the "opacity"
+              weight policy keeps the raw sigma_j.  gaussian_renderer.render / count_render / render_features switch it on for a `pipe`
+              with a true `antialiasing` attribute.  Off: every kernel launched is the one launched before the option existed;
     count_wide_band: tests only -- LG_FLAG_COUNT_WIDE_BAND (the parallel long-tile count walk sends many more pixels through its exact fix-up);
     sh_jacobian / narrow_key / sort_all_bits / k1_lds: cross-check switches for the tests (K9 re-reads the SH coefficients instead
               of K1's saved direction Jacobian; the sort key laid out as if 40 bits were available; every key bit through the
@@ -287,6 +295,8 @@ class _Call:
             flags |= _lib.FLAG_K1_LDS
         if opts["count_wide_band"]:
             flags |= _lib.FLAG_COUNT_WIDE_BAND
+        if opts["antialiasing"]:    # (the backward's _Call is built from the forward's snapshot: the two cannot disagree)
+            flags |= _lib.FLAG_ANTIALIAS
         self.view = _lib.lg_view(int(rs.image_height), int(rs.image_width), float(rs.tanfovx), float(rs.tanfovy),
                                  _ptr(self.bg), float(rs.scale_modifier), _ptr(self.vm), _ptr(self.pm),
                                  int(rs.sh_degree), _ptr(self.cp), int(bool(rs.prefiltered)), flags, int(opts["segment_length"]))

@@ -12,6 +12,9 @@
         (what one (pixel, Gaussian) hit adds to important_score in every count_render of the run: opacity (default, the paper's sigma_j),
          one, alpha or alpha_t -- the weight of the reference's un-vendored fork is not verifiable from its repository, SURVEY section 2.2;
          all four are deterministic and bit-pinned)
+    python -m lightgaussian_amd.run --antialiasing /path/to/prune_finetune.py ...
+        (every render and significance pass of the run compensates the opacities for the 0.3-pixel screen-space blur, as upstream
+         3DGS's `antialiasing` pipeline switch does: the process default of the rasterizer option "antialiasing")
     python -m lightgaussian_amd.run --fused-adam /path/to/prune_finetune.py ...
         (opt-in, outside the replaced path: torch.optim.Adam as the trainers construct it, but with fused=True -- fused_adam() below)
     python -m lightgaussian_amd.run --hip-adam /path/to/prune_finetune.py ...
@@ -551,7 +554,7 @@ def _redirect_model_path(argv, rank):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    distributed = no_patch = verbose = adam = hip = hip_visible = lazy = no_timing = densify = False
+    distributed = no_patch = verbose = adam = hip = hip_visible = lazy = no_timing = densify = antialiasing = False
     backend = "nccl"
     dp_overlap = False
     weight_policy = None
@@ -577,6 +580,8 @@ def main(argv=None):
             lazy = True
         elif flag == "--no-iter-timing":
             lazy = no_timing = True
+        elif flag == "--antialiasing":
+            antialiasing = True
         elif flag.startswith("--weight-policy="):
             from . import rasterizer
             weight_policy = flag.split("=", 1)[1]
@@ -584,7 +589,7 @@ def main(argv=None):
         elif flag.startswith("--backend="):       # gloo: CPU tests of the launcher with a stand-in trainer (the rasterizer has no CPU path)
             backend = flag.split("=", 1)[1]
         else:
-            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --hip-adam=visible --hip-densify --lazy-loss --no-iter-timing --weight-policy=NAME, then the script and ITS arguments)")
+            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --hip-adam=visible --hip-densify --lazy-loss --no-iter-timing --antialiasing --weight-policy=NAME, then the script and ITS arguments)")
     if adam and hip:
         raise SystemExit(f"lightgaussian_amd.run: --fused-adam and {'--hip-adam=visible' if hip_visible else '--hip-adam'} exclude each other (one optimizer step per run)")
     if hip_visible and distributed:
@@ -634,6 +639,9 @@ def main(argv=None):
     if weight_policy is not None:
         from . import rasterizer
         rasterizer.set_option("weight_policy", rasterizer.weight_policy_id(weight_policy))     # process default of every count_render of the run
+    if antialiasing:
+        from . import rasterizer
+        rasterizer.set_option("antialiasing", True)        # process default: every render / count_render of the unmodified trainer and of prune_list
     if adam:
         fused_adam(True)
     if hip:

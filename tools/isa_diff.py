@@ -2,7 +2,11 @@
 """Compare two gfx950 device assembly listings of the library kernel by kernel (CPU only).
 
     hipcc <Makefile HIPFLAGS> -DLG_BUILD_ID='"x"' --cuda-device-only -S lg_api.hip -o a.s     (same for b.s)
-    tools/isa_diff.py a.s b.s
+    tools/isa_diff.py a.s b.s [--alias REGEX=REPLACEMENT ...]
+
+Kernels are matched by their demangled name (up to the parameter list).  --alias rewrites those names in both builds before matching:
+a kernel template that gained a trailing parameter is compared with what it was by
+    --alias 'lg_preprocess(_bwd)?<(\w+, \w+), false>=lg_preprocess\1<\2>' --alias 'lg_camera_bwd<(\w+), false>=lg_camera_bwd<\1>'
 
 Compares instruction TEXT only (labels renumbered in order of appearance, directives and comments dropped): which kernels
 differ, their instruction counts, and both builds' register / LDS / scratch figures from the code-object metadata.
@@ -35,10 +39,26 @@ def parse(path):
     return {k: v for k, v in kernels.items() if k in meta}, meta
 
 
-def main(a, b):
-    (ka, ma), (kb, mb) = parse(a), parse(b)
+def by_pretty_name(kernels, meta, aliases):
+    """Both tables keyed by the demangled name without its parameter list, after the aliases."""
+    names = sorted(kernels)
+    demangled = subprocess.run(["c++filt"], input="\n".join(names), text=True, capture_output=True).stdout.splitlines()
+    key = {}
+    for n, d in zip(names, demangled):
+        d = d.split("(")[0]
+        for pat, repl in aliases:
+            d = re.sub(pat, repl, d)
+        assert d not in key.values(), "two kernels share the name " + d
+        key[n] = d
+    return {key[n]: v for n, v in kernels.items()}, {key[n]: meta[n] for n in kernels}
+
+
+def main(a, b, *rest):
+    aliases = [tuple(r.split("=", 1)) for flag, r in zip(rest[::2], rest[1::2]) if flag == "--alias"]
+    assert len(rest) == 2 * len(aliases), "usage: isa_diff.py a.s b.s [--alias REGEX=REPLACEMENT ...]"
+    (ka, ma), (kb, mb) = by_pretty_name(*parse(a), aliases), by_pretty_name(*parse(b), aliases)
     names = sorted(set(ka) | set(kb))
-    pretty = dict(zip(names, subprocess.run(["c++filt"], input="\n".join(names), text=True, capture_output=True).stdout.splitlines()))
+    pretty = {n: n for n in names}
     differ = [n for n in names if ka.get(n) != kb.get(n)]
     count = lambda k, n: sum(not i.endswith(":") for i in k[n]) if n in k else "-"      # label definitions are not instructions
     print("%d kernels, %d instruction-identical, %d differ" % (len(names), len(names) - len(differ), len(differ)))
@@ -52,4 +72,4 @@ def main(a, b):
 
 
 if __name__ == "__main__":
-    sys.exit(main(*sys.argv[1:3]))
+    sys.exit(main(*sys.argv[1:]))
