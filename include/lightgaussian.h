@@ -517,6 +517,52 @@ int lg_backward_camera(const lg_view* view, const lg_gaussians* g, const int32_t
                        int64_t num_rendered, const void* backward_scratch, float* dL_dviewmatrix, float* dL_dprojmatrix,
                        float* dL_dcampos, void* scratch, void* stream);
 
+/* --- 3D smoothing filter (Mip-Splatting's 3D filter; lg_filter3d.h) -----------
+ * A Gaussian that no training camera samples at more than 1 / t samples per world unit must not be narrower than that sampling
+ * allows: filter3d = sqrtf(0.2f) t is added (as a variance, filter3d^2) to each squared scale, and the opacity is scaled so that the
+ * Gaussian keeps its integral.
+ *
+ * lg_filter3d_update: for every mean p and every camera n of the DEVICE table `cameras` (viewmatrix in the row-vector layout of
+ * lg_view.viewmatrix), in float32 with explicit fmaf and correctly rounded divisions (lg_math.h: lg_filter3d_term):
+ *     (x, y, z) = view-space p     fx = W / (2 tanfovx)   fy = H / (2 tanfovy)     u = x / z * fx + 0.5 W    v = y / z * fy + 0.5 H
+ *     seen_n = z > 0.2 && -0.15 W <= u <= 1.15 W && -0.15 H <= v <= 1.15 H          (a NaN compares false: unseen)
+ *     t_n = z / fx                       world units per pixel at p
+ * filter3d[i] = sqrtf(0.2f) min over the seeing cameras of t_n -- the paper's maximal sampling rate; with cameras of one focal length
+ * it is the published code's min depth / max focal.  A row no camera sees gets the largest filter3d of the seen rows (as published);
+ * when no row is seen at all every value is 0, the identity of the apply (the published code raises there).  seen (optional):
+ * 1 / 0 per row.  Two launches on `stream` ("filter3d_update": one lane per Gaussian, the camera table staged through LDS 64 cameras
+ * at a time, one partial maximum per workgroup with a plain store; "filter3d_reduce": every workgroup takes the maximum of the at
+ * most 2048 partials in a fixed order and fills the unseen rows of its stride).  No atomics, no memset, no host read-back:
+ * bit-identical run to run.  scratch: lg_filter3d_scratch_bytes(N) device bytes, 4-byte aligned.
+ *
+ * lg_filter3d_apply, one elementwise launch ("filter3d_apply").  With LG_FILTER3D_RAW scaling [N,3] holds log-scales r and opacity
+ * [N] logits o, in and out -- the domain LG_FLAG_RAW_PARAMS reads:
+ *     u_k = expf(r_k)^2 + f^2    r'_k = 0.5 logf(u_k)    w_k = expf(r_k)^2 / u_k    c = sqrtf(w_0 w_1 w_2)
+ *     y = sigmoid(o) c           o' = logf(y / (1 - y))                   (y == 0 gives -inf: opacity 0 in K1, culled)
+ * without it scales s and opacities sigma:  s'_k = sqrtf(s_k^2 + f^2),  sigma' = sigma c.  A row with f == 0 is copied bit for bit.
+ * lg_filter3d_apply_bwd ("filter3d_apply_bwd"): the gradients with respect to scaling and opacity from those with respect to the
+ * outputs, w_k, c, y recomputed from the inputs by the forward's operations; the filter takes none.  Raw:
+ *     dL/dr_k = g_r'_k w_k + g_o' (1 - w_k) / (1 - y)       dL/do = g_o' (1 - sigmoid(o)) / (1 - y)
+ * (1 - w_k evaluated as f^2 / u_k and 1 - sigmoid(o) as sigmoid(-o): the same in real arithmetic, no cancellation).  A row with
+ * f == 0 copies its incoming gradients bit for bit.  Outputs must not overlap inputs.  Tensors whose pointers are all 16-byte
+ * aligned go through 16-byte accesses, others one dword at a time.
+ *
+ * All three: LG_ERR_INVALID_ARGUMENT before any device call for N < 0, N >= 2^30, V < 1, a null or misaligned (4 bytes) pointer;
+ * N == 0 is a no-op.  flags: LG_FILTER3D_RAW (apply), LG_FLAG_PROFILE. */
+typedef struct lg_filter_camera {
+    float viewmatrix[16];
+    float tanfovx, tanfovy;
+    int32_t width, height;
+} lg_filter_camera;                     /* 80 bytes */
+#define LG_FILTER3D_RAW 1u              /* scaling = log-scales, opacity = logits, in and out; otherwise activated values */
+size_t lg_filter3d_scratch_bytes(int32_t N);
+int lg_filter3d_update(int32_t N, const float* means3D, int32_t V, const lg_filter_camera* cameras, float* filter3d, uint8_t* seen,
+                       void* scratch, uint32_t flags, void* stream);
+int lg_filter3d_apply(int32_t N, const float* scaling, const float* opacity, const float* filter3d, float* out_scaling,
+                      float* out_opacity, uint32_t flags, void* stream);
+int lg_filter3d_apply_bwd(int32_t N, const float* scaling, const float* opacity, const float* filter3d, const float* dL_dout_scaling,
+                          const float* dL_dout_opacity, float* dL_dscaling, float* dL_dopacity, uint32_t flags, void* stream);
+
 /* out[j] = (((rows[0][j] + rows[1][j]) + rows[2][j]) + ...) over V rows of n floats (row pitch row_stride floats): the
  * sequential in-place float accumulation of per-view scores in prune.py:144-155, in view order, as one launch. */
 int lg_ordered_sum(int32_t V, int64_t n, const float* rows, int64_t row_stride, float* out, void* stream);

@@ -31,6 +31,7 @@ ADAM_SPAN = 4096            # LG_ADAM_SPAN: elements per workgroup of lg_adam_st
 DENSIFY_COPY, DENSIFY_MOMENT, DENSIFY_XYZ, DENSIFY_SCALING, DENSIFY_ZERO = 0, 1, 2, 3, 4     # lg_densify_tensor.role (LG_DENSIFY_*)
 DENSIFY_MAX_TENSORS = 32    # LG_DENSIFY_MAX_TENSORS: tensors per lg_densify_rows call
 FEATURES_MAX = 64           # LG_FEATURES_MAX: channels per lg_blend_features call
+FILTER3D_RAW = 1            # LG_FILTER3D_RAW: lg_filter3d_apply / _bwd on log-scales and opacity logits
 ABI_VERSION = 7     # include/lightgaussian.h LG_ABI_VERSION this binding was written against (load() refuses another)
 
 EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scratch_bytes", "lg_forward",
@@ -45,7 +46,8 @@ EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scr
            "lg_vq_code_index_bytes", "lg_vq_code_index_scratch_bytes", "lg_vq_code_index", "lg_vq_colors_bwd_scratch_bytes",
            "lg_vq_colors_bwd", "lg_adam_step", "lg_adam_step_rows", "lg_densify_scratch_bytes", "lg_densify_stats", "lg_densify_plan", "lg_densify_rows",
            "lg_features_scratch_bytes", "lg_blend_features", "lg_blend_features_backward", "lg_backward_features_scratch_bytes",
-           "lg_backward_features", "lg_camera_scratch_bytes", "lg_backward_camera"]
+           "lg_backward_features", "lg_camera_scratch_bytes", "lg_backward_camera", "lg_filter3d_scratch_bytes", "lg_filter3d_update",
+           "lg_filter3d_apply", "lg_filter3d_apply_bwd"]
 
 
 class lg_view(C.Structure):
@@ -80,6 +82,10 @@ class lg_adam_rows_tensor(C.Structure):
 
 class lg_densify_tensor(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_words", C.c_int32), ("role", C.c_int32)]
+
+
+class lg_filter_camera(C.Structure):
+    _fields_ = [("viewmatrix", C.c_float * 16), ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("width", C.c_int32), ("height", C.c_int32)]
 
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
@@ -191,6 +197,13 @@ def load():
     lib.lg_camera_scratch_bytes.restype = C.c_size_t; lib.lg_camera_scratch_bytes.argtypes = [C.c_int32]
     lib.lg_backward_camera.restype = C.c_int
     lib.lg_backward_camera.argtypes = [P(lg_view), P(lg_gaussians), vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+    lib.lg_filter3d_scratch_bytes.restype = C.c_size_t; lib.lg_filter3d_scratch_bytes.argtypes = [C.c_int32]
+    lib.lg_filter3d_update.restype = C.c_int
+    lib.lg_filter3d_update.argtypes = [C.c_int32, vp, C.c_int32, vp, vp, vp, vp, C.c_uint32, vp]
+    lib.lg_filter3d_apply.restype = C.c_int
+    lib.lg_filter3d_apply.argtypes = [C.c_int32, vp, vp, vp, vp, vp, C.c_uint32, vp]
+    lib.lg_filter3d_apply_bwd.restype = C.c_int
+    lib.lg_filter3d_apply_bwd.argtypes = [C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp]
     lib.lg_debug_sort_temp_bytes.restype = C.c_size_t; lib.lg_debug_sort_temp_bytes.argtypes = [C.c_int64]
     lib.lg_debug_sort_keys.restype = C.c_int
     lib.lg_debug_sort_keys.argtypes = [C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp]

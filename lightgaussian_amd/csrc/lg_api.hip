@@ -22,6 +22,8 @@
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound); wave_reduce_via_lds<NV> (also lg_features.h's)
 //   lg_features.h    lg_features_fwd / _bwd / _gather: C further per-Gaussian channels blended over the lists a forward left, and dL/dfeatures
 //   lg_camera.h      lg_camera_bwd<RAW, AA> / lg_camera_reduce: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos from the rows a backward left, through lg_k9_* (float64 ordered sums)
+//   lg_filter3d.h    lg_filter3d_update / _apply / _apply_bwd: Mip-Splatting's 3D smoothing filter from the training cameras, and its raw -> raw
+//                    (or activated) application to scales and opacity with its backward
 //
 // Pipeline of one view:
 //   K1 project + EWA + SH->RGB + exact footprint culling  ->  K2 scan of instance counts, blocking read of R
@@ -49,6 +51,7 @@
 #include "lg_densify.h"
 #include "lg_features.h"
 #include "lg_camera.h"
+#include "lg_filter3d.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1279,6 +1282,84 @@ extern "C" int lg_densify_rows(int32_t N, int64_t N_out, const void* map, const 
     lg_densify_move<<<dim3((unsigned)std::max<size_t>(blocks, 1), (unsigned)num_tensors), 256, 0, stream>>>(N_out, (const uint2*)map, record, a, rotation,
                                                                                                       scaling, noise, noise_rows);
     KCHECK("lg_densify_move");
+    return LG_OK;
+}
+
+// ---- 3D smoothing filter (lg_filter3d.h) ----
+#define LG_FILTER3D_MAX_ROWS (1 << 30)
+extern "C" size_t lg_filter3d_scratch_bytes(int32_t N) { (void)N; return align_up((size_t)LG_F3D_MAX_WGS * sizeof(float)); }
+
+extern "C" int lg_filter3d_update(int32_t N, const float* means3D, int32_t V, const lg_filter_camera* cameras, float* filter3d, uint8_t* seen,
+                                  void* scratch, uint32_t flags, void* stream_p)
+{
+    if (N < 0 || N >= LG_FILTER3D_MAX_ROWS) return fail(LG_ERR_INVALID_ARGUMENT, "lg_filter3d_update: N outside [0, 2^30)");
+    if (V < 1) return fail(LG_ERR_INVALID_ARGUMENT, "lg_filter3d_update: V < 1 (the filter needs at least one camera)");
+    if (!means3D || !cameras || !filter3d || !scratch) return fail(LG_ERR_INVALID_ARGUMENT, "lg_filter3d_update: null means3D / cameras / filter3d / scratch");
+    if ((((uintptr_t)means3D | (uintptr_t)cameras | (uintptr_t)filter3d | (uintptr_t)scratch) & 3) != 0)
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_filter3d_update: 32-bit tensors must be 4-byte aligned");
+    if (N == 0) return LG_OK;
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    const unsigned wgs = (unsigned)std::min<int64_t>(((int64_t)N + LG_F3D_THREADS - 1) / LG_F3D_THREADS, LG_F3D_MAX_WGS);
+    float* partial = (float*)scratch;
+    {
+        ProfScope ps(prof, "filter3d_update", stream);
+        lg_filter3d_update_kernel<<<wgs, LG_F3D_THREADS, 0, stream>>>(N, means3D, V, cameras, filter3d, seen, partial);
+        KCHECK("lg_filter3d_update_kernel");
+    }
+    {
+        ProfScope ps(prof, "filter3d_reduce", stream);
+        lg_filter3d_fill_kernel<<<wgs, LG_F3D_THREADS, 0, stream>>>(N, (int)wgs, partial, filter3d);
+        KCHECK("lg_filter3d_fill_kernel");
+    }
+    return LG_OK;
+}
+
+static int lg_filter3d_check(const char* who, int32_t N, std::initializer_list<const void*> ptrs, bool* vec)
+{
+    char msg[128];                      // (fail() copies it)
+    if (N < 0 || N >= LG_FILTER3D_MAX_ROWS) { snprintf(msg, sizeof(msg), "%s: N outside [0, 2^30)", who); return fail(LG_ERR_INVALID_ARGUMENT, msg); }
+    uintptr_t all = 0;
+    for (const void* p : ptrs) {
+        if (!p) { snprintf(msg, sizeof(msg), "%s: null tensor", who); return fail(LG_ERR_INVALID_ARGUMENT, msg); }
+        all |= (uintptr_t)p;
+    }
+    if (all & 3) { snprintf(msg, sizeof(msg), "%s: float32 tensors must be 4-byte aligned", who); return fail(LG_ERR_INVALID_ARGUMENT, msg); }
+    *vec = (all & 15) == 0;
+    return LG_OK;
+}
+
+extern "C" int lg_filter3d_apply(int32_t N, const float* scaling, const float* opacity, const float* filter3d, float* out_scaling,
+                                 float* out_opacity, uint32_t flags, void* stream_p)
+{
+    bool vec = false;
+    const int rc = lg_filter3d_check("lg_filter3d_apply", N, { scaling, opacity, filter3d, out_scaling, out_opacity }, &vec);
+    if (rc != LG_OK || N == 0) return rc;
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    ProfScope ps(prof, "filter3d_apply", stream);
+    const unsigned wgs = (unsigned)((((int64_t)N + 3) / 4 + LG_F3D_THREADS - 1) / LG_F3D_THREADS);
+    if (flags & LG_FILTER3D_RAW) lg_filter3d_apply_kernel<true><<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, out_scaling, out_opacity);
+    else lg_filter3d_apply_kernel<false><<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, out_scaling, out_opacity);
+    KCHECK("lg_filter3d_apply_kernel");
+    return LG_OK;
+}
+
+extern "C" int lg_filter3d_apply_bwd(int32_t N, const float* scaling, const float* opacity, const float* filter3d, const float* dL_dout_scaling,
+                                     const float* dL_dout_opacity, float* dL_dscaling, float* dL_dopacity, uint32_t flags, void* stream_p)
+{
+    bool vec = false;
+    const int rc = lg_filter3d_check("lg_filter3d_apply_bwd", N, { scaling, opacity, filter3d, dL_dout_scaling, dL_dout_opacity, dL_dscaling, dL_dopacity }, &vec);
+    if (rc != LG_OK || N == 0) return rc;
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    ProfScope ps(prof, "filter3d_apply_bwd", stream);
+    const unsigned wgs = (unsigned)((((int64_t)N + 3) / 4 + LG_F3D_THREADS - 1) / LG_F3D_THREADS);
+    if (flags & LG_FILTER3D_RAW)
+        lg_filter3d_apply_bwd_kernel<true><<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, dL_dout_scaling, dL_dout_opacity, dL_dscaling, dL_dopacity);
+    else
+        lg_filter3d_apply_bwd_kernel<false><<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, dL_dout_scaling, dL_dout_opacity, dL_dscaling, dL_dopacity);
+    KCHECK("lg_filter3d_apply_bwd_kernel");
     return LG_OK;
 }
 

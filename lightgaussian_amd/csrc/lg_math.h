@@ -829,3 +829,42 @@ LG_HD void lg_densify_child_xyz(const float q_raw[4], const float s[3], const fl
     out[2] = ((R20 * v0 + R21 * v1) + R22 * v2) + xyz[2];
 }
 LG_HD float lg_densify_child_scaling(float s) { return logf(s / LG_DENSIFY_SHRINK); }
+
+// ---------------------------------------------------------------------------------------------
+// 3D smoothing filter (lg_filter3d.h; Mip-Splatting's 3D filter): what ONE camera says about one Gaussian mean.
+//   x, y, z = view-space coordinates: three explicit fmaf each, in K1's term order (x, then y, then z of the mean, the translation
+//             innermost): fmaf(vm[8 + c], pz, fmaf(vm[4 + c], py, fmaf(vm[c], px, vm[12 + c])))
+//   u = fmaf(x / z, fx, 0.5f W)    v = fmaf(y / z, fy, 0.5f H)       fx = W / (2 tanfovx), fy = H / (2 tanfovy)
+//   seen = z > 0.2f && -0.15f W <= u <= 1.15f W && -0.15f H <= v <= 1.15f H          (a NaN compares false: unseen)
+//   t    = z / fx                                                                      world units per pixel at the mean
+// Every division is the correctly rounded one; nothing besides the written fmaf is contracted.
+// LgFilterCam: the per-camera constants, evaluated once per camera (lg_filter3d_camera) and then read by every Gaussian.
+#define LG_FILTER3D_NEAR 0.2f
+#define LG_FILTER3D_VARIANCE 0.2f       // filter_3D = sqrtf(0.2f) t
+struct LgFilterCam {
+    float m[12];                        // view matrix columns 0..2, row-vector layout: m[4 c + k] = vm[4 k + c] (k = 3: translation)
+    float fx, fy, cx, cy;               // focal lengths in pixels, 0.5f W, 0.5f H
+    float ulo, uhi, vlo, vhi;           // -0.15f W, 1.15f W, -0.15f H, 1.15f H
+};
+LG_HD void lg_filter3d_camera(const float* vm, float tanfovx, float tanfovy, int W, int H, LgFilterCam& c)
+{
+    for (int col = 0; col < 3; col++)
+        for (int k = 0; k < 4; k++) c.m[4 * col + k] = vm[4 * k + col];
+    const float w = (float)W, h = (float)H;
+    c.fx = w / (2.0f * tanfovx); c.fy = h / (2.0f * tanfovy);
+    c.cx = 0.5f * w; c.cy = 0.5f * h;
+    c.ulo = -0.15f * w; c.uhi = 1.15f * w;
+    c.vlo = -0.15f * h; c.vhi = 1.15f * h;
+}
+LG_HD float lg_filter3d_value(float t) { return sqrtf(LG_FILTER3D_VARIANCE) * t; }
+// true when the camera sees the mean; t is written either way (the caller takes the minimum over the cameras that see it)
+LG_HD bool lg_filter3d_term(const LgFilterCam& c, float px, float py, float pz, float& t)
+{
+    const float x = fmaf(c.m[2], pz, fmaf(c.m[1], py, fmaf(c.m[0], px, c.m[3])));
+    const float y = fmaf(c.m[6], pz, fmaf(c.m[5], py, fmaf(c.m[4], px, c.m[7])));
+    const float z = fmaf(c.m[10], pz, fmaf(c.m[9], py, fmaf(c.m[8], px, c.m[11])));
+    const float u = fmaf(x / z, c.fx, c.cx);
+    const float v = fmaf(y / z, c.fy, c.cy);
+    t = z / c.fx;
+    return z > LG_FILTER3D_NEAR && u >= c.ulo && u <= c.uhi && v >= c.vlo && v <= c.vhi;
+}

@@ -13,6 +13,7 @@ import threading
 
 import torch
 
+from . import filter3d as _filter3d
 from . import rasterizer as _rasterizer
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_raw
 from .sh_utils import eval_sh
@@ -39,15 +40,28 @@ def _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, f_count):
     )
 
 
-def _inputs(viewpoint_camera, pc, pipe, scaling_modifier, override_color):
+def _filter_3d(pc, pipe, options):
+    """The model's 3D smoothing filter if this call is to honour one (filter3d.model_filter: `pc.filter_3D`, option "filter_3d"), else
+    None -- a model without the attribute, the reference's GaussianModel, takes the code path it always took."""
+    f = _filter3d.model_filter(pc, options)
+    if f is not None and pipe.compute_cov3D_python:
+        raise NotImplementedError("compute_cov3D_python with a filter_3D is not implemented: the filter is applied to the scales "
+                                  "(render with options={'filter_3d': False}, or without compute_cov3D_python)")
+    return f
+
+
+def _inputs(viewpoint_camera, pc, pipe, scaling_modifier, override_color, options=None):
     means3D = pc.get_xyz
     opacity = pc.get_opacity
     scales = rotations = cov3D_precomp = None
+    filter_3d = _filter_3d(pc, pipe, options)
     if pipe.compute_cov3D_python:
         cov3D_precomp = pc.get_covariance(scaling_modifier)
     else:
         scales = pc.get_scaling
         rotations = pc.get_rotation
+        if filter_3d is not None:       # upstream's get_scaling_with_3D_filter / get_opacity_with_3D_filter, one launch
+            scales, opacity = _filter3d.apply_filter_3d_activated(scales, opacity, filter_3d)
     shs = colors_precomp = None
     if override_color is None:
         if pipe.convert_SHs_python:
@@ -135,7 +149,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 
     A `pipe` with a true `antialiasing` attribute (upstream 3DGS's spelling) renders with options={"antialiasing": True} -- the opacity
     compensation of the 0.3-pixel blur, rasterizer.set_option -- unless `options` sets the key itself; count_render and render_features
-    read it the same way."""
+    read it the same way.
+
+    A model with a `filter_3D` attribute (upstream Mip-Splatting's name: one filter size per Gaussian, filter3d.compute_filter_3d) is
+    rendered with the 3D smoothing filter applied to its scales and opacity -- on the fused path raw -> raw in front of the kernels, on
+    every other path on the activated getters -- unless options={"filter_3d": False}.  The reference's GaussianModel has no such
+    attribute: nothing changes for it.  A filter whose row count is not the model's raises ValueError (recompute it after a
+    densification or prune); with pipe.compute_cov3D_python it raises NotImplementedError."""
     options = _pipe_options(pipe, options)
     if isinstance(pc, (CompressedGaussians, TrainableCompressed)) and _camera_grad(options):
         raise NotImplementedError("camera_grad is not implemented for compressed models: render pc.to_dense() instead")
@@ -154,7 +174,7 @@ def _render_unfused(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, 
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, False), options=options)
     means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp = _inputs(
-        viewpoint_camera, pc, pipe, scaling_modifier, override_color)
+        viewpoint_camera, pc, pipe, scaling_modifier, override_color, options)
     rendered_image, radii = rasterizer(
         means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
         scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
@@ -202,7 +222,7 @@ def count_render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_mod
     screenspace_points = _screenspace_points(pc)
     rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, True), options=options)
     means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp = _inputs(
-        viewpoint_camera, pc, pipe, scaling_modifier, override_color)
+        viewpoint_camera, pc, pipe, scaling_modifier, override_color, options)
     gaussians_count, important_score, rendered_image, radii = rasterizer(
         means3D=means3D, means2D=screenspace_points, shs=shs, colors_precomp=colors_precomp, opacities=opacity,
         scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp)
@@ -221,8 +241,14 @@ def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_mod
         return _render_unfused(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, override_color, options)
     screenspace_points = _screenspace_points(pc)
     rs = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, False)
-    rendered_image, radii, visible = rasterize_gaussians_raw(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
-                                                             pc._scaling, pc._rotation, rs, options)
+    opacity_raw, scaling_raw = pc._opacity, pc._scaling
+    filter_3d = _filter_3d(pc, pipe, options)
+    if filter_3d is not None:
+        # raw -> raw (lg_filter3d_apply): log-scales and logits come out in the domain LG_FLAG_RAW_PARAMS reads, so the fused path stays;
+        # autograd carries the gradients on to _scaling / _opacity through lg_filter3d_apply_bwd
+        scaling_raw, opacity_raw = _filter3d.apply_filter_3d(scaling_raw, opacity_raw, filter_3d)
+    rendered_image, radii, visible = rasterize_gaussians_raw(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, opacity_raw,
+                                                             scaling_raw, pc._rotation, rs, options)
     # visibility_filter = radii > 0 (gaussian_renderer/__init__.py:121), as K1 left it in the forward's geom buffer: no compare kernel
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": visible,
             "radii": radii}
@@ -264,7 +290,7 @@ def render_features(viewpoint_camera, pc, pipe, features, bg_features=None, scal
         raise NotImplementedError("convert_SHs_python / compute_cov3D_python need the dequantised tensors: pass pc.to_dense() instead")
     with contextlib.nullcontext() if geometry_grad else torch.no_grad():
         override = pc.colors(viewpoint_camera.camera_center) if compressed else None
-        means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp = _inputs(viewpoint_camera, pc, pipe, scaling_modifier, override)
+        means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp = _inputs(viewpoint_camera, pc, pipe, scaling_modifier, override, options)
         if bg_color is None:
             bg_color = torch.zeros(3, dtype=torch.float32, device=means3D.device)
         want_depth = isinstance(features, str)

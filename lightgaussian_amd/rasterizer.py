@@ -45,6 +45,7 @@ class GaussianRasterizationSettings(NamedTuple):
 _OPTIONS = {"weight_policy": _lib.WEIGHT_OPACITY, "fast_exp": True, "profile": False, "skip_color_in_count": False,
             "fuse_getters": True, "sync_free": "validated", "max_depth": 100.0, "capacity_margin": 1.25,
             "segment_length": 0, "long_tiles": "auto", "count_long_tiles": "serial", "camera_grad": False, "antialiasing": False,
+            "filter_3d": True,
             # cross-check switches of the tests: never needed in production, never read from the environment
             "sh_jacobian": True, "narrow_key": False, "sort_all_bits": False, "k1_lds": False, "count_wide_band": False}
 _PER_CALL_ONLY = ("pending", "tag", "status_override", "differentiated", "sh_grad_sink", "score_out", "count_sum")
@@ -77,6 +78,8 @@ def _validate(name, value):
         raise ValueError("camera_grad must be True or False")
     if name == "antialiasing" and not isinstance(value, bool):
         raise ValueError("antialiasing must be True or False")
+    if name == "filter_3d" and not isinstance(value, bool):
+        raise ValueError("filter_3d must be True or False")
     if name == "segment_length" and (int(value) < 0 or (int(value) != 0 and (int(value) < 64 or int(value) % 64))):
         raise ValueError("segment_length must be 0 (library default, 512) or a multiple of 64")
 
@@ -143,6 +146,11 @@ def set_option(name, value):
               the reference tile rectangles do not change; images, hit counts and the per-hit significance weights do; the "opacity"
               weight policy keeps the raw sigma_j.  gaussian_renderer.render / count_render / render_features switch it on for a `pipe`
               with a true `antialiasing` attribute.  Off: every kernel launched is the one launched before the option existed;
+    filter_3d (default True): honour `pc.filter_3D` when the model has one (upstream Mip-Splatting's attribute, the 3D smoothing filter;
+              lightgaussian_amd.filter3d): gaussian_renderer.render applies it raw -> raw in front of the fused rasterizer call
+              (lg_filter3d_apply; gradients reach _scaling / _opacity through lg_filter3d_apply_bwd), the unfused path, count_render and
+              render_features apply it to the activated getters.  A model without the attribute -- the reference's GaussianModel -- is
+              not touched; False ignores the attribute.  Read by gaussian_renderer only: the rasterizer itself takes what it is handed;
     count_wide_band: tests only -- LG_FLAG_COUNT_WIDE_BAND (the parallel long-tile count walk sends many more pixels through its exact fix-up);
     sh_jacobian / narrow_key / sort_all_bits / k1_lds: cross-check switches for the tests (K9 re-reads the SH coefficients instead
               of K1's saved direction Jacobian; the sort key laid out as if 40 bits were available; every key bit through the

@@ -188,9 +188,12 @@ class SyntheticGaussians:
         return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], dim=1)
 
     def to(self, device):
-        return SyntheticGaussians(self._xyz.to(device), self._features_dc.to(device), self._features_rest.to(device),
-                                  self._scaling.to(device), self._rotation.to(device), self._opacity.to(device),
-                                  self.active_sh_degree, self.max_sh_degree)
+        g = SyntheticGaussians(self._xyz.to(device), self._features_dc.to(device), self._features_rest.to(device),
+                               self._scaling.to(device), self._rotation.to(device), self._opacity.to(device),
+                               self.active_sh_degree, self.max_sh_degree)
+        if getattr(self, "filter_3D", None) is not None:      # (Mip-Splatting's 3D filter travels with the model: filter3d.py)
+            g.filter_3D = self.filter_3D.to(device)
+        return g
 
     def requires_grad_(self, flag=True):
         for t in (self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation, self._opacity):
