@@ -103,6 +103,10 @@ enum {
                                   that disagrees differentiates another function than the one rendered (nothing detects it).  The
                                   LG_WEIGHT_OPACITY score keeps the raw opacity (a property of the model, not of the view); hit counts and
                                   the per-hit weights follow the compensated alpha.  Without the flag every kernel launched is unchanged. */
+    LG_FLAG_ABSGRAD = 32768,   /* this view's backward is lg_backward_abs, which also leaves the ABSOLUTE screen-space mean gradients (AbsGS's
+                                  homodirectional gradient, gsplat's `absgrad`).  Read by lg_backward_abs alone, which refuses a view without it;
+                                  every forward and every other backward ignores it: without lg_backward_abs every kernel launched and every
+                                  bit produced is unchanged. */
     /* (4096 was LG_FLAG_BWD_SPLAT_PARALLEL, the round-5 prototype of the backward blend on the other parallel axis: removed in ABI 7) */
     LG_FLAG_RAW_PARAMS = 8 /* "fused getters" (SURVEY 8f row 1): the inputs are GaussianModel's RAW parameters and the
                               activations of scene/gaussian_model.py:98-118 run inside the kernels: scales = log-scales (exp),
@@ -253,6 +257,25 @@ int lg_backward_chunked(const lg_view* view, const lg_gaussians* g, const int32_
                         float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
                         float* dL_dcov3D, float* dL_dshs_rest, void* scratch, void* stream, int32_t chunks, lg_chunk_fn on_chunk,
                         void* user);
+
+/* lg_backward_chunked that ALSO writes dL_dmeans2D_abs [N,3]: per Gaussian the sum over pixels of |dL/dmean2D| instead of the |sum|
+ * that dL_dmeans2D holds -- signed per-pixel pulls on a large splat straddling fine structure cancel in the latter and it is never
+ * densified (AbsGS; gsplat's `absgrad`).  With t = G dL/dalpha and dx = x_g - px of a (pixel, Gaussian) pair and the splat's conic
+ * (ha, nb, hc) = (-A/2, -B, -C/2) and record opacity op (the compensated one under LG_FLAG_ANTIALIAS):
+ *     abs.x = 0.5 W op sum_pairs |t (2 ha dx + nb dy)|     abs.y = 0.5 H op sum_pairs |t (2 hc dy + nb dx)|     abs.z = 0
+ * in the NDC units of dL_dmeans2D, so abs >= |dL_dmeans2D| component-wise up to rounding.  The per-pair magnitudes exist only inside the
+ * backward blend: its ABS variant carries them in floats 9 and 10 of the 48-byte gradient rows (zeros otherwise), and one more
+ * kernel (lg_absgrad_rows) sums them per Gaussian in slot order between the blend and the first chunk of the per-Gaussian stage:
+ * deterministic, no atomics.  Scratch size and every other output are those of lg_backward_chunked, bit for bit.  Rows of Gaussians with
+ * radii <= 0, and all rows after an abandoned forward or with a segment_length other than the forward's, are exact zeros.
+ * The view must carry LG_FLAG_ABSGRAD and dL_dcolor and dL_dmeans2D_abs must not be NULL (also for N = 0): LG_ERR_INVALID_ARGUMENT otherwise.
+ * lg_backward_camera may follow on the same scratch (it reads floats 0..8 of the rows).  lg_backward_features has no such variant.
+ * LG_FLAG_PROFILE adds an "absgrad_rows" entry. */
+int lg_backward_abs(const lg_view* view, const lg_gaussians* g, const int32_t* radii, const void* geom, const void* binning,
+                    const void* img, int64_t num_rendered, const float* dL_dcolor, float* dL_dmeans2D, float* dL_dmeans3D,
+                    float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
+                    float* dL_dcov3D, float* dL_dshs_rest, void* scratch, void* stream, int32_t chunks, lg_chunk_fn on_chunk,
+                    void* user, float* dL_dmeans2D_abs /* [N,3], z = 0 */);
 
 /* score[j] = seqsum32(weight[j], count[j]) on the device (weight NULL => 1.0).  Used by the sharded
  * prune pass to rebuild per-view scores from integer counts. */

@@ -25,6 +25,7 @@ FLAG_LONG_SERIAL, FLAG_LONG_PARALLEL = 512, 1024
 FLAG_SAVE_SH_JACOBIAN = 2048
 FLAG_COUNT_WIDE_BAND = 8192
 FLAG_ANTIALIAS = 16384
+FLAG_ABSGRAD = 32768       # lg_backward_abs (absolute screen-space mean gradients); ignored by everything else
 ADAM_DECOUPLED_WD = 1       # lg_adam_step flags: LG_ADAM_DECOUPLED_WD (AdamW), FLAG_PROFILE
 ADAM_MAX_TENSORS = 8        # LG_ADAM_MAX_TENSORS: tensors per launch of lg_adam_step
 ADAM_SPAN = 4096            # LG_ADAM_SPAN: elements per workgroup of lg_adam_step
@@ -47,7 +48,7 @@ EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scr
            "lg_vq_colors_bwd", "lg_adam_step", "lg_adam_step_rows", "lg_densify_scratch_bytes", "lg_densify_stats", "lg_densify_plan", "lg_densify_rows",
            "lg_features_scratch_bytes", "lg_blend_features", "lg_blend_features_backward", "lg_backward_features_scratch_bytes",
            "lg_backward_features", "lg_camera_scratch_bytes", "lg_backward_camera", "lg_filter3d_scratch_bytes", "lg_filter3d_update",
-           "lg_filter3d_apply", "lg_filter3d_apply_bwd"]
+           "lg_filter3d_apply", "lg_filter3d_apply_bwd", "lg_backward_abs"]
 
 
 class lg_view(C.Structure):
@@ -131,6 +132,8 @@ def load():
     lib.lg_backward.argtypes = [P(lg_view), P(lg_gaussians), vp, vp, vp, vp, C.c_int64, vp] + [vp] * 9 + [vp, vp]
     lib.lg_backward_chunked.restype = C.c_int
     lib.lg_backward_chunked.argtypes = [P(lg_view), P(lg_gaussians), vp, vp, vp, vp, C.c_int64, vp] + [vp] * 9 + [vp, vp, C.c_int32, CHUNK_FN, vp]
+    lib.lg_backward_abs.restype = C.c_int
+    lib.lg_backward_abs.argtypes = lib.lg_backward_chunked.argtypes + [vp]
     lib.lg_score_from_count.restype = C.c_int
     lib.lg_score_from_count.argtypes = [C.c_int32, vp, vp, vp, vp]
     lib.lg_loss_state_bytes.restype = C.c_size_t; lib.lg_loss_state_bytes.argtypes = [C.c_int32] * 3

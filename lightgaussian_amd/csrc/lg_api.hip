@@ -19,9 +19,10 @@
 //   lg_adam.h        lg_adam_step: one Adam / AdamW step over all parameter tensors of the model in one launch (table by value, dwordx4);
 //                    lg_adam_step_rows: the same step over the rows a byte mask names (row index: lg_adam_rows.h)
 //   lg_densify.h     lg_densify_stats / lg_densify_plan / lg_densify_rows: view statistics and clone / split / prune of densify_and_prune
-//   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT>   (per tile, VALU-bound); wave_reduce_via_lds<NV> (also lg_features.h's)
+//   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT, ABS>   (per tile, VALU-bound); wave_reduce_via_lds<NV> (also lg_features.h's)
 //   lg_features.h    lg_features_fwd / _bwd / _gather: C further per-Gaussian channels blended over the lists a forward left, and dL/dfeatures
 //   lg_camera.h      lg_camera_bwd<RAW, AA> / lg_camera_reduce: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos from the rows a backward left, through lg_k9_* (float64 ordered sums)
+//   lg_absgrad.h     lg_absgrad_rows: absolute screen-space mean gradients per Gaussian from floats 9, 10 of the rows K7<ABS> left (lg_backward_abs)
 //   lg_filter3d.h    lg_filter3d_update / _apply / _apply_bwd: Mip-Splatting's 3D smoothing filter from the training cameras, and its raw -> raw
 //                    (or activated) application to scales and opacity with its backward
 //
@@ -51,6 +52,7 @@
 #include "lg_densify.h"
 #include "lg_features.h"
 #include "lg_camera.h"
+#include "lg_absgrad.h"
 #include "lg_filter3d.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -174,8 +176,13 @@ static BlendFwdKernel blend_fwd_kernel(const ForwardPlan& p)
     const int w = p.fscore == LG_W_ALPHA ? 1 : p.fscore == LG_W_ALPHA_T ? 2 : 0;
     return !p.count ? color[p.exact] : p.color ? count_image[w][p.exact] : significance[w];
 }
-using BlendBwdKernel = decltype(&lg_blend_bwd<true>);
-static BlendBwdKernel blend_bwd_kernel(bool exact) { return exact ? lg_blend_bwd<true> : lg_blend_bwd<false>; }
+using BlendBwdKernel = decltype(&lg_blend_bwd<true, false>);
+// (abs: lg_backward_abs alone -- the rows' floats 9 and 10 carry the absolute mean-gradient sums, lg_absgrad.h)
+static BlendBwdKernel blend_bwd_kernel(bool exact, bool abs)
+{
+    static const BlendBwdKernel k[2][2] = { { lg_blend_bwd<false, false>, lg_blend_bwd<true, false> }, { lg_blend_bwd<false, true>, lg_blend_bwd<true, true> } };   // [abs][exact]
+    return k[abs][exact];
+}
 using PreprocessBwdKernel = decltype(&lg_preprocess_bwd<false, false, false>);
 static PreprocessBwdKernel preprocess_bwd_kernel(bool raw, bool jac, bool antialias)
 {
@@ -526,7 +533,7 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
                          const void* img_p, int64_t R, const float* dL_dcolor, float* dL_dmeans2D, float* dL_dmeans3D,
                          float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
                          float* dL_dcov3D, float* dL_dshs_rest, void* scratch, void* stream_p, int chunks, lg_chunk_fn on_chunk, void* user,
-                         const FeatGrad* fg = nullptr)
+                         const FeatGrad* fg = nullptr, float* dL_dmeans2D_abs = nullptr)
 {
     int rc = check_args(v, g);
     if (rc != LG_OK) return rc;
@@ -555,10 +562,20 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
     // buffer by the forward: one extra workgroup of lg_blend_fwd)
     if (R > 0 && dL_dcolor) {
         ProfScope ps(prof, "blend_bwd", stream);
-        blend_bwd_kernel(!(v->flags & LG_FLAG_FAST_EXP))<<<max_items, 64, 0, stream>>>(W, H, q.gx, S, bin.work, bin.meta, bin.ranges, bin.entries, q.gid_mask, geo.tinfo,
+        blend_bwd_kernel(!(v->flags & LG_FLAG_FAST_EXP), dL_dmeans2D_abs != nullptr)<<<max_items, 64, 0, stream>>>(W, H, q.gx, S, bin.work, bin.meta, bin.ranges, bin.entries, q.gid_mask, geo.tinfo,
                                                                                        geo.rec, v->bg, img.final_T, img.n_contrib, dL_dcolor, bin.ckpt, rows);
     }
     KCHECK("lg_blend_bwd");
+    if (dL_dmeans2D_abs) {
+        // lg_backward_abs: floats 9 and 10 of the rows summed per Gaussian, in front of the first K9 chunk (K9 does not read them)
+        {
+            ProfScope ps(prof, "absgrad_rows", stream);
+            lg_absgrad_rows<<<(N + LG_ABS_THREADS - 1) / LG_ABS_THREADS, LG_ABS_THREADS, 0, stream>>>(
+                N, W, H, (uint32_t)R, radii, geo.rec, geo.counters, bin.meta, (uint32_t)S, geo.touched, geo.offsets,
+                reinterpret_cast<const float4*>(rows), dL_dmeans2D_abs);
+        }
+        KCHECK("lg_absgrad_rows");
+    }
     if (fg && R > 0) {
         // lg_backward_features: the moments of the feature / alpha loss join K7's in the same rows (lg_features.h), CG channels per walk;
         // the first walk writes whole rows, zeros included, when K7 did not run -- also when there is no image gradient at all
@@ -615,6 +632,21 @@ extern "C" int lg_backward_chunked(const lg_view* v, const lg_gaussians* g, cons
 {
     return backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity,
                          dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest, scratch, stream_p, chunks, on_chunk, user);
+}
+
+// lg_backward_chunked that also leaves the absolute screen-space mean gradients (lg_absgrad.h; the view must carry LG_FLAG_ABSGRAD)
+extern "C" int lg_backward_abs(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const void* geom_p, const void* bin_p,
+                               const void* img_p, int64_t R, const float* dL_dcolor, float* dL_dmeans2D, float* dL_dmeans3D,
+                               float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
+                               float* dL_dcov3D, float* dL_dshs_rest, void* scratch, void* stream_p, int32_t chunks,
+                               lg_chunk_fn on_chunk, void* user, float* dL_dmeans2D_abs)
+{
+    if (!v || !(v->flags & LG_FLAG_ABSGRAD)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_abs: the view must carry LG_FLAG_ABSGRAD");
+    if (!dL_dmeans2D_abs) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_abs: missing dL_dmeans2D_abs");
+    if (!dL_dcolor) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_abs: missing dL_dcolor");
+    if (R < 0 || R >= (1ll << 30)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_abs: num_rendered out of range");
+    return backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity,
+                         dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest, scratch, stream_p, chunks, on_chunk, user, nullptr, dL_dmeans2D_abs);
 }
 
 // ---- camera pose gradients (lg_camera.h) ----

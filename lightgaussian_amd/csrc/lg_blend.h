@@ -1000,10 +1000,11 @@ __device__ __forceinline__ void wave_reduce9_via_lds(const float (&p)[9], float*
 
 // One (pixel, Gaussian) step of the back-to-front replay.  EXACT = canonical arithmetic for every include / exclude
 // decision (same sequence as the oracle); otherwise hardware exp / rcp and contraction allowed (training path, 1e-4 contract).
-template <bool EXACT>
+// NP = 9, or 11 (K7's ABS instantiations, LG_FLAG_ABSGRAD): p[9], p[10] += the pair's absolute mean-gradient terms (lg_abs_pair, lg_math.h).
+template <bool EXACT, int NP>
 __device__ __forceinline__ bool bwd_pair(const float4& a, const float4& b, const float4& c, float pxf, float pyf, float& T, float Tfb,
                                          float g0, float g1, float g2, float& a0, float& a1, float& a2, float& last_alpha,
-                                         float& lc0, float& lc1, float& lc2, float (&p)[9])
+                                         float& lc0, float& lc1, float& lc2, float (&p)[NP])
 {
     float dx, dy;
     const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
@@ -1034,6 +1035,7 @@ __device__ __forceinline__ bool bwd_pair(const float4& a, const float4& b, const
         p[4] += tdy * dy;
         p[5] += t;
         p[6] += dch * g0; p[7] += dch * g1; p[8] += dch * g2;
+        if constexpr (NP == 11) lg_abs_pair(t, dx, dy, a.z, a.w, b.x, p[9], p[10]);
         return true;
     }
     return false;
@@ -1044,8 +1046,9 @@ __device__ __forceinline__ bool bwd_pair(const float4& a, const float4& b, const
 // selecting the old state.  (A branchy version makes hipcc copy the 9 accumulators at every nesting level.  A scalar
 // early-out when no lane of the 8x8 block takes the entry -- `if (__ballot(ok) == 0) return` -- was measured: 0.946 vs
 // 0.927 ms; blocks that pass the box test almost always have a contributing pixel.)
+template <int NP>
 __device__ __forceinline__ uint64_t bwd_pair_fast(const float4& a, const float4& b, const float4& c, bool live, float pxf, float pyf,
-                                                  float& T, float Tfb, float g0, float g1, float g2, float& S, float (&p)[9])
+                                                  float& T, float Tfb, float g0, float g1, float g2, float& S, float (&p)[NP])
 {
 #pragma clang fp contract(fast)
     float dx, dy;
@@ -1083,6 +1086,7 @@ __device__ __forceinline__ uint64_t bwd_pair_fast(const float4& a, const float4&
     p[4] += tdy * dy;
     p[5] += t;
     p[6] += dch * g0; p[7] += dch * g1; p[8] += dch * g2;
+    if constexpr (NP == 11) lg_abs_pair(t, dx, dy, a.z, a.w, b.x, p[9], p[10]);     // (invalid lanes: t = 0, the terms vanish without a select)
     // the lanes that contributed: the scalar mask itself (rounds 1-3 balloted the bool `ok`, which hipcc materialises as v_cndmask(0, 1) +
     // v_cmp_ne; round 4 balloted am > 0, one compare; now none)
     return okm;
@@ -1091,7 +1095,11 @@ __device__ __forceinline__ uint64_t bwd_pair_fast(const float4& a, const float4&
 #ifndef LG_K7_WAVES
 #define LG_K7_WAVES 5      // waves per SIMD the register allocation of lg_blend_bwd aims for (84 VGPRs as written: 5)
 #endif
-template <bool EXACT>
+// ABS (LG_FLAG_ABSGRAD, lg_backward_abs): 11 partials per entry instead of 9 -- the two absolute mean-gradient sums (lg_abs_pair, lg_math.h) go
+// through the same reduction into floats 9 and 10 of the entry's row, which the ABS = false kernels write as zeros; lg_absgrad_rows
+// (lg_absgrad.h) sums them per Gaussian.  Row size and scratch are the same.  The ABS = false instantiations are the kernels that existed
+// before the mode did: NP is a compile-time constant, no runtime branch, no extra argument.
+template <bool EXACT, bool ABS>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LG_K7_WAVES, 8)))
 lg_blend_bwd(int W, int H, int gx, int S, const uint2* __restrict__ work, const uint32_t* __restrict__ meta, const uint2* __restrict__ ranges,
              const uint64_t* __restrict__ entries, uint32_t gid_mask, const uint4* __restrict__ tinfo, const float4* __restrict__ rec,
@@ -1099,12 +1107,15 @@ lg_blend_bwd(int W, int H, int gx, int S, const uint2* __restrict__ work, const 
              const float* __restrict__ dL_dpix, const float4* __restrict__ ckpt, float* __restrict__ part)
 {
     __shared__ float4 q0[LG_Q], q1[LG_Q];
-    __shared__ float stage[LG_Q * 9];
+    constexpr int NP = ABS ? 11 : 9;
+    __shared__ float stage[LG_Q * NP];
     // the entry's third colour channel lives in row 8 of `stage` until the entry's own totals overwrite it (its reduction runs after
     // its last read): 256 bytes of LDS less per wave, 6800 in all (round 4: K7 0.692 -> 0.682 ms bracketed.  Six waves per SIMD on top
     // of it -- 80 VGPRs, 24 workgroups per CU now fit -- change nothing further, 0.683: measured again, as in round 3)
+    // (ABS: still row 8.  Word j of rows 9 and 10, like word j of every row, is written by entry j's own reduction alone, so the argument
+    // holds for any row count: nothing but entry j's totals ever lands on q2[j], and they land after the entry's only read of it.)
     float* const q2 = stage + 8 * LG_Q;
-    __shared__ __attribute__((aligned(16))) float red[LG_RED_FLOATS];
+    __shared__ __attribute__((aligned(16))) float red[NP * LG_RED_STRIDE];
     if (blockIdx.x >= meta[0]) return;            // the grid is sized for the worst case: tiles + R / S work items
     if (meta[2] != (uint32_t)S) return;           // another segment length than the forward's (see lg_preprocess_bwd)
     const uint2 item = work[blockIdx.x];          // {tile, segment}, longest first (lg_work_order)
@@ -1208,17 +1219,17 @@ lg_blend_bwd(int W, int H, int gx, int S, const uint2* __restrict__ work, const 
                 const uint32_t m = (uint32_t)((M0 >> jcur) & 1ull) | ((uint32_t)((M1 >> jcur) & 1ull) << 1) | ((uint32_t)((M2 >> jcur) & 1ull) << 2) |
                                    ((uint32_t)((M3 >> jcur) & 1ull) << 3);
                 const uint32_t rel = (uint32_t)k * LG_Q + (uint32_t)jcur + 1u;
-                float p[9];
+                float p[NP];
                 uint64_t cmask = 0;                        // lanes for which the entry contributed in any sub-block (scalar)
                 if (EXACT) {
 #pragma unroll
-                    for (int v = 0; v < 9; v++) p[v] = 0.0f;
+                    for (int v = 0; v < NP; v++) p[v] = 0.0f;
 #pragma unroll
                     for (int s = 0; s < 4; s++) {
                         if (m & (1u << s)) {
                             bool cb = false;
                             if (rel <= last[s])
-                                cb = bwd_pair<true>(a, b, c, pxf[s], pyf[s], T[s], Tfb[s], g0[s], g1[s], g2[s], a0[s], a1[s], a2[s],
+                                cb = bwd_pair<true, NP>(a, b, c, pxf[s], pyf[s], T[s], Tfb[s], g0[s], g1[s], g2[s], a0[s], a1[s], a2[s],
                                                     la[s], lc0[s], lc1[s], lc2[s], p);
                             cmask |= __ballot(cb);
                         }
@@ -1226,14 +1237,16 @@ lg_blend_bwd(int W, int H, int gx, int S, const uint2* __restrict__ work, const 
                 } else {
                     // (dispatch on the lowest hit sub-block instead of zeroing the sums: EXPERIMENTS.md, "K7 structure")
 #pragma unroll
-                    for (int v = 0; v < 9; v++) p[v] = 0.0f;
+                    for (int v = 0; v < NP; v++) p[v] = 0.0f;
 #pragma unroll
                     for (int s = 0; s < 4; s++)
                         if (m & (1u << s))
-                            cmask |= bwd_pair_fast(a, b, c, rel <= last[s], pxf[s], pyf[s], T[s], Tfb[s], g0[s], g1[s], g2[s], Sd[s], p);
+                            cmask |= bwd_pair_fast<NP>(a, b, c, rel <= last[s], pxf[s], pyf[s], T[s], Tfb[s], g0[s], g1[s], g2[s], Sd[s], p);
                 }
                 if (cmask != 0) {
-                    wave_reduce9_via_lds(p, red, stage, (uint32_t)jcur, lane);
+                    // (ABS: the same value-major layout, 11 rows.  The 9-row call stays as it was: the kernel text is the one from before the mode)
+                    if constexpr (ABS) wave_reduce_via_lds<NP>(p, red, lane, [&](uint32_t r, float s) { stage[r * LG_Q + (uint32_t)jcur] = s; });
+                    else wave_reduce9_via_lds(p, red, stage, (uint32_t)jcur, lane);
                     hitmask |= 1ull << jcur;
                 }
             }
@@ -1242,10 +1255,11 @@ lg_blend_bwd(int W, int H, int gx, int S, const uint2* __restrict__ work, const 
         if (lane < nbt) {
             float4 o0 = make_float4(0, 0, 0, 0), o1 = o0, o2 = o0;
             if ((hitmask >> lane) & 1ull) {
-                const float* src = stage + lane;          // value-major: [9][LG_Q]
+                const float* src = stage + lane;          // value-major: [NP][LG_Q]
                 o0 = make_float4(src[0], src[LG_Q], src[2 * LG_Q], src[3 * LG_Q]);
                 o1 = make_float4(src[4 * LG_Q], src[5 * LG_Q], src[6 * LG_Q], src[7 * LG_Q]);
-                o2 = make_float4(src[8 * LG_Q], 0.0f, 0.0f, 0.0f);
+                if constexpr (ABS) o2 = make_float4(src[8 * LG_Q], src[9 * LG_Q], src[10 * LG_Q], 0.0f);
+                else o2 = make_float4(src[8 * LG_Q], 0.0f, 0.0f, 0.0f);
             }
             float4* dst = rows + 3 * (size_t)lg_slot_of(trect, tx, ty);
             // (48 bytes to a slot of its own per lane: three partial-line writes per instance.  Upper bound of what they cost, measured by

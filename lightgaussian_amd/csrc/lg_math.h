@@ -484,6 +484,34 @@ LG_HD void lg_rows_to_grads(const float* m, float ha, float nb, float hc, float 
     acc[6] = m[6]; acc[7] = m[7]; acc[8] = m[8];
 }
 
+// Absolute screen-space mean gradients (LG_FLAG_ABSGRAD, lg_backward_abs): sum over pixels of |dL/dmean2D| per Gaussian
+// instead of the |sum| the moments give.  An absolute value does not pass through the moments' linearity, so the per-pair magnitudes are
+// two more partial sums of K7's pair step (floats 9 and 10 of the gradient row), without the opacity, which is applied once per Gaussian:
+//   ax += |t (2 ha dx + nb dy)|   ay += |t (2 hc dy + nb dx)|        t = G dL/dalpha, dx = x_g - px, as the moments
+// lg_two_prod_sum(a, b, c, d) = a b + c d with ONE rounding of the sum's size (the product c d is carried with its rounding error, both
+// fmas are exact in their products): the two terms have opposite signs wherever nb dx dy > 0 and cancel, and a plain mul + fma
+// leaves an error of an ulp of the larger TERM there.  Two fmas more per component; only the ABS kernels run them.
+LG_HD float lg_two_prod_sum(float a, float b, float c, float d)
+{
+    const float w = c * d;
+    const float e = fmaf(c, d, -w);          // exact: c d = w + e
+    return fmaf(a, b, w) + e;
+}
+LG_HD void lg_abs_pair(float t, float dx, float dy, float ha, float nb, float hc, float& ax, float& ay)
+{
+    ax += fabsf(t * lg_two_prod_sum(2.0f * ha, dx, nb, dy));
+    ay += fabsf(t * lg_two_prod_sum(2.0f * hc, dy, nb, dx));
+}
+// ... finished per Gaussian: sx, sy = its rows' floats 9 and 10 summed in slot order, op = the record's opacity (the value
+// lg_rows_to_grads multiplies by: the compensated one under LG_FLAG_ANTIALIAS).  NDC units, those of dL_dmeans2D (lg_backward_geom:
+// mean2D = 0.5 {W, H} acc), so that out >= |dL_dmeans2D| component-wise up to rounding; z = 0.
+LG_HD void lg_abs_rows_to_grad(float sx, float sy, float op, int W, int H, float* out)
+{
+    out[0] = (op * sx) * (0.5f * (float)W);
+    out[1] = (op * sy) * (0.5f * (float)H);
+    out[2] = 0.0f;
+}
+
 // AA (LG_FLAG_ANTIALIAS): acc[5] is dL/dop' of the compensated opacity op' = op rho; op = the input opacity (activated).  The three
 // terms of lg_aa_backward join dL_da, dL_db, dL_dc before they are chained to cov3D, T2 and the mean, and rho_out = rho, so that the
 // caller writes dL/dop = rho acc[5].  The +-1.3 tanfov clamp keeps its no-gradient convention (dtx, dty below).

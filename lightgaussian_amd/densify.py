@@ -109,12 +109,20 @@ def _stats_ineligible(model, grad, update_filter, radii):
     return None
 
 
-def accumulate_stats(model, viewspace_points, update_filter, radii=None):
+def accumulate_stats(model, viewspace_points, update_filter, radii=None, absgrad=False):
     """xyz_gradient_accum[f] += |viewspace_points.grad[f, :2]|, denom[f] += 1 and, with radii, max_radii2D[f] = max(max_radii2D[f],
-    radii[f]) for f = update_filter, in place.  No host read on either path."""
-    grad = viewspace_points.grad
-    if grad is None:
-        raise ValueError("accumulate_stats: viewspace_points carries no gradient (call it after backward())")
+    radii[f]) for f = update_filter, in place.  No host read on either path.
+    absgrad=True: the norm is taken of viewspace_points.absgrad instead -- the absolute mean gradients a render with option absgrad
+    leaves there (rasterizer.set_option; same [N,3] layout, so the same lg_densify_stats launch) -- ValueError when it is absent."""
+    if absgrad:
+        grad = getattr(viewspace_points, "absgrad", None)
+        if grad is None:
+            raise ValueError("accumulate_stats(absgrad=True): viewspace_points carries no .absgrad (render with option absgrad, "
+                             "call it after backward())")
+    else:
+        grad = viewspace_points.grad
+        if grad is None:
+            raise ValueError("accumulate_stats: viewspace_points carries no gradient (call it after backward())")
     with torch.no_grad():
         why = _stats_ineligible(model, grad, update_filter, radii)
         if why is not None:

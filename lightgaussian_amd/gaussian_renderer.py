@@ -155,7 +155,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     rendered with the 3D smoothing filter applied to its scales and opacity -- on the fused path raw -> raw in front of the kernels, on
     every other path on the activated getters -- unless options={"filter_3d": False}.  The reference's GaussianModel has no such
     attribute: nothing changes for it.  A filter whose row count is not the model's raises ValueError (recompute it after a
-    densification or prune); with pipe.compute_cov3D_python it raises NotImplementedError."""
+    densification or prune); with pipe.compute_cov3D_python it raises NotImplementedError.
+
+    options={"absgrad": True} (rasterizer.set_option): after backward(), result["viewspace_points"].absgrad holds the ABSOLUTE
+    view-space mean gradients, float32 [N,3] in .grad's layout and units (z = 0): per Gaussian the sum over pixels of |dL/dmean2D|
+    where .grad holds the |sum|, in which the signed pulls on a large splat over fine structure cancel (AbsGS; gsplat's `absgrad`).
+    Overwritten by every backward, not accumulated.  densify.accumulate_stats(..., absgrad=True) reads it; the densification threshold
+    usually wants raising 2-4 x with it.  Fused and unfused paths alike; every other output and gradient keeps its bits."""
     options = _pipe_options(pipe, options)
     if isinstance(pc, (CompressedGaussians, TrainableCompressed)) and _camera_grad(options):
         raise NotImplementedError("camera_grad is not implemented for compressed models: render pc.to_dense() instead")

@@ -45,7 +45,7 @@ class GaussianRasterizationSettings(NamedTuple):
 _OPTIONS = {"weight_policy": _lib.WEIGHT_OPACITY, "fast_exp": True, "profile": False, "skip_color_in_count": False,
             "fuse_getters": True, "sync_free": "validated", "max_depth": 100.0, "capacity_margin": 1.25,
             "segment_length": 0, "long_tiles": "auto", "count_long_tiles": "serial", "camera_grad": False, "antialiasing": False,
-            "filter_3d": True,
+            "filter_3d": True, "absgrad": False,
             # cross-check switches of the tests: never needed in production, never read from the environment
             "sh_jacobian": True, "narrow_key": False, "sort_all_bits": False, "k1_lds": False, "count_wide_band": False}
 _PER_CALL_ONLY = ("pending", "tag", "status_override", "differentiated", "sh_grad_sink", "score_out", "count_sum")
@@ -80,6 +80,8 @@ def _validate(name, value):
         raise ValueError("antialiasing must be True or False")
     if name == "filter_3d" and not isinstance(value, bool):
         raise ValueError("filter_3d must be True or False")
+    if name == "absgrad" and not isinstance(value, bool):
+        raise ValueError("absgrad must be True or False")
     if name == "segment_length" and (int(value) < 0 or (int(value) != 0 and (int(value) < 64 or int(value) % 64))):
         raise ValueError("segment_length must be 0 (library default, 512) or a multiple of 64")
 
@@ -151,6 +153,16 @@ def set_option(name, value):
               (lg_filter3d_apply; gradients reach _scaling / _opacity through lg_filter3d_apply_bwd), the unfused path, count_render and
               render_features apply it to the activated getters.  A model without the attribute -- the reference's GaussianModel -- is
               not touched; False ignores the attribute.  Read by gaussian_renderer only: the rasterizer itself takes what it is handed;
+    absgrad (default False): the backward of a render also leaves the ABSOLUTE screen-space mean gradients (AbsGS's homodirectional
+              gradient, gsplat's `absgrad`): per Gaussian the sum over pixels of |dL/dmean2D| instead of the |sum| that means2D.grad
+              holds, in which the signed pulls on a large splat straddling fine structure cancel.  The backward calls lg_backward_abs
+              (K7's ABS variant + lg_absgrad_rows) and sets `means2D.absgrad` on the means2D tensor handed to the forward: float32 [N,3]
+              in .grad's layout and NDC units, z = 0, rows of invisible Gaussians zero; OVERWRITTEN, not accumulated, by every backward
+              (gsplat's convention).  Every other gradient, the image and the radii are bit-identical to those with the option off.
+              Works on the activated and the raw (fused) path, with antialiasing, filter_3d, camera_grad, a gradient-chunk hook and an
+              sh_grad_sink; densify.accumulate_stats(..., absgrad=True) consumes it.  Count renders have no backward and ignore it;
+              features.render_features(geometry_grad=True) does not produce it (lg_backward_features has no ABS variant) and does not
+              raise, so a process-wide default is safe.  Off: every kernel launched is the one launched before the option existed;
     count_wide_band: tests only -- LG_FLAG_COUNT_WIDE_BAND (the parallel long-tile count walk sends many more pixels through its exact fix-up);
     sh_jacobian / narrow_key / sort_all_bits / k1_lds: cross-check switches for the tests (K9 re-reads the SH coefficients instead
               of K1's saved direction Jacobian; the sort key laid out as if 40 bits were available; every key bit through the
@@ -210,13 +222,14 @@ def set_grad_chunk_hook(hook, chunks=4):
     _GRAD_CHUNKS["chunks"] = max(1, int(chunks)) if hook is not None else 1
 
 
-def _call_backward(lib, args, grads_by_name):
-    """lg_backward, or lg_backward_chunked when a gradient-chunk hook is installed.  An exception raised by the hook cannot
+def _call_backward(lib, args, grads_by_name, abs_out=None):
+    """lg_backward, or lg_backward_chunked when a gradient-chunk hook is installed; with abs_out (option absgrad: a float32 [N,3] tensor
+    that receives the absolute mean gradients) lg_backward_abs, which takes the chunked call's arguments.  An exception raised by the hook cannot
     cross the C frame (ctypes would print and swallow it, and the remaining ranges would still be reported): it is recorded,
     the hook is not called again for this backward, and it is re-raised here once the library call has returned."""
     hook = _GRAD_CHUNKS["hook"]
     if hook is None:
-        return lib.lg_backward(*args)
+        return lib.lg_backward(*args) if abs_out is None else lib.lg_backward_abs(*args, 1, _lib.CHUNK_FN(), None, _ptr(abs_out))      # (a NULL callback)
     errors = []
 
     def _cb(_user, first, count):
@@ -228,7 +241,10 @@ def _call_backward(lib, args, grads_by_name):
             errors.append(e)
 
     cb = _lib.CHUNK_FN(_cb)
-    rc = lib.lg_backward_chunked(*args, int(_GRAD_CHUNKS["chunks"]), cb, None)
+    if abs_out is None:
+        rc = lib.lg_backward_chunked(*args, int(_GRAD_CHUNKS["chunks"]), cb, None)
+    else:
+        rc = lib.lg_backward_abs(*args, int(_GRAD_CHUNKS["chunks"]), cb, None, _ptr(abs_out))
     if errors:
         raise errors[0]
     return rc
@@ -305,6 +321,8 @@ class _Call:
             flags |= _lib.FLAG_COUNT_WIDE_BAND
         if opts["antialiasing"]:    # (the backward's _Call is built from the forward's snapshot: the two cannot disagree)
             flags |= _lib.FLAG_ANTIALIAS
+        if opts.get("absgrad") and not exact:   # read by lg_backward_abs alone (_backward); every forward ignores it
+            flags |= _lib.FLAG_ABSGRAD
         self.view = _lib.lg_view(int(rs.image_height), int(rs.image_width), float(rs.tanfovx), float(rs.tanfovy),
                                  _ptr(self.bg), float(rs.scale_modifier), _ptr(self.vm), _ptr(self.pm),
                                  int(rs.sh_degree), _ptr(self.cp), int(bool(rs.prefiltered)), flags, int(opts["segment_length"]))
@@ -546,9 +564,11 @@ class _GradSet:
                 if self.by_slot[s] is not None and not (self.rgb_only and s == "colors")}
 
 
-def _finish_forward(ctx, rs, num_rendered, opts):
+def _finish_forward(ctx, rs, num_rendered, opts, means2D=None):
     """What a differentiated forward leaves on ctx for its backward, besides the saved tensors."""
     ctx.raster_settings = rs
+    # option absgrad: the tensor whose .absgrad the backward sets (a plain reference: the caller's own means2D, not a saved copy)
+    ctx.absgrad_target = means2D if (opts.get("absgrad") and not rs.f_count and torch.is_tensor(means2D)) else None
     ctx.num_rendered = num_rendered
     ctx.opts = {k: v for k, v in opts.items() if k not in _PER_CALL_ONLY}   # the backward runs with the forward's options
     ctx.sh_sink = opts.get("sh_grad_sink")
@@ -558,8 +578,8 @@ def _finish_forward(ctx, rs, num_rendered, opts):
 
 
 def _backward(ctx, call, grad_color, radii, geom, binning, img, raw):
-    """The backward of one render: lg_backward (or _chunked), then lg_backward_camera on its scratch (option camera_grad), then
-    the sink.  Returns the _GradSet."""
+    """The backward of one render: lg_backward (or _chunked; lg_backward_abs with option absgrad, which also sets means2D.absgrad), then
+    lg_backward_camera on its scratch (option camera_grad), then the sink.  Returns the _GradSet."""
     lib = _lib.load()
     rs, dev = ctx.raster_settings, call.dev
     if grad_color is None:
@@ -570,9 +590,15 @@ def _backward(ctx, call, grad_color, radii, geom, binning, img, raw):
         sink = ctx.sh_sink if call.sh is not None else None
         g = _GradSet(call, rgb_only=sink is not None)
         scratch = torch.empty(lib.lg_backward_scratch_bytes(call.N, ctx.num_rendered), dtype=torch.uint8, device=dev)
+        target = getattr(ctx, "absgrad_target", None)
+        # (an empty model: torch hands out NULL for empty tensors, which lg_backward_abs refuses -- the plain call, and an empty .absgrad)
+        abs_out = None if (target is None or call.N == 0) else torch.empty((call.N, 3), dtype=torch.float32, device=dev)
         rc = _call_backward(lib, (C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img),
-                                  C.c_int64(ctx.num_rendered), _ptr(grad_color), *g.ptrs(), _ptr(scratch), stream), g.by_hook_name(raw))
+                                  C.c_int64(ctx.num_rendered), _ptr(grad_color), *g.ptrs(), _ptr(scratch), stream), g.by_hook_name(raw), abs_out)
         _lib.check(rc)
+        if target is not None:
+            # overwritten by every backward, never accumulated
+            target.absgrad = abs_out if abs_out is not None else torch.zeros((0, 3), dtype=torch.float32, device=dev)
         if ctx.opts["camera_grad"]:
             ctx.cam_grads = _camera_backward(lib, call.view, call.g, dev, radii, geom, binning, ctx.num_rendered, scratch, stream)
         if sink is not None:        # g["colors"] holds dL/d(rgb of the SH expansion); the coefficient gradients are the sink's business
@@ -592,7 +618,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                      differentiated=opts.get("differentiated", any(ctx.needs_input_grad)))
         with torch.cuda.device(call.dev):
             color, radii, gcount, score, geom, binning, img, num_rendered = _native_forward(lib, call, rs, count)
-        _finish_forward(ctx, rs, num_rendered, opts)
+        _finish_forward(ctx, rs, num_rendered, opts, means2D)
         ctx.save_for_backward(call.means3D, call.sh, call.colors, call.opac, call.scales, call.rots, call.cov, radii,
                               geom, binning, img)
         ctx.mark_non_differentiable(radii)
@@ -627,7 +653,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                      differentiated=opts.get("differentiated", any(ctx.needs_input_grad)))
         with torch.cuda.device(call.dev):
             color, radii, _gc, _sc, geom, binning, img, num_rendered = _native_forward(lib, call, rs, False)
-        _finish_forward(ctx, rs, num_rendered, opts)
+        _finish_forward(ctx, rs, num_rendered, opts, means2D)
         ctx.rest_shape = None if features_rest is None else tuple(features_rest.shape)
         ctx.save_for_backward(call.means3D, call.sh, call.sh_rest, call.opac, call.scales, call.rots, radii, geom, binning, img)
         # visibility_filter (= radii > 0, gaussian_renderer/__init__.py:121) read in place: K1 leaves it as bytes in the geom buffer

@@ -15,6 +15,11 @@
     python -m lightgaussian_amd.run --antialiasing /path/to/prune_finetune.py ...
         (every render and significance pass of the run compensates the opacities for the 0.3-pixel screen-space blur, as upstream
          3DGS's `antialiasing` pipeline switch does: the process default of the rasterizer option "antialiasing")
+    python -m lightgaussian_amd.run --absgrad /path/to/train_densify_prune.py ...
+        (densify on ABSOLUTE view-space gradients (AbsGS; gsplat's absgrad): the process default of the rasterizer option "absgrad", and
+         GaussianModel.add_densification_stats reads viewspace_point_tensor.absgrad through lightgaussian_amd.densify -- for that one
+         method what --hip-densify does.  The trainer's densify_grad_threshold is left alone: absolute gradients are larger, raise it.
+         Excludes --distributed, whose own add_densification_stats reads .grad)
     python -m lightgaussian_amd.run --fused-adam /path/to/prune_finetune.py ...
         (opt-in, outside the replaced path: torch.optim.Adam as the trainers construct it, but with fused=True -- fused_adam() below)
     python -m lightgaussian_amd.run --hip-adam /path/to/prune_finetune.py ...
@@ -486,6 +491,26 @@ def _densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
     densify.densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size)
 
 
+def _add_densification_stats_abs(self, viewspace_point_tensor, update_filter):
+    """add_densification_stats on the absolute gradients a render with option absgrad left (run.py --absgrad)."""
+    from . import densify
+    densify.accumulate_stats(self, viewspace_point_tensor, update_filter, absgrad=True)
+
+
+def absgrad_densify():
+    """run.py --absgrad: option absgrad becomes the process default of the rasterizer and GaussianModel.add_densification_stats of the
+    reference's scene.gaussian_model is rebound to the absgrad-reading lightgaussian_amd.densify.accumulate_stats (after hip_densify(),
+    when both are given: this one wins for that method).  unpatch_reference() restores the method; the option stays until it is set
+    back.  Returns the report entries."""
+    from . import rasterizer
+    rasterizer.set_option("absgrad", True)
+    gm = _module("scene.gaussian_model")
+    if gm is None or not hasattr(gm, "GaussianModel"):
+        return {k: v for k, v in _REPORT.items() if k == "scene.gaussian_model"}
+    _set(gm.GaussianModel, "add_densification_stats", _add_densification_stats_abs, "scene.gaussian_model.GaussianModel.add_densification_stats")
+    return {k: v for k, v in _REPORT.items() if k.endswith("add_densification_stats")}
+
+
 def hip_densify():
     """run.py --hip-densify (opt-in, like hip_adam()): rebinds GaussianModel.add_densification_stats and GaussianModel.densify_and_prune
     of the reference's scene.gaussian_model to lightgaussian_amd.densify (same positional parameters).  Apply it BEFORE
@@ -554,7 +579,7 @@ def _redirect_model_path(argv, rank):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    distributed = no_patch = verbose = adam = hip = hip_visible = lazy = no_timing = densify = antialiasing = False
+    distributed = no_patch = verbose = adam = hip = hip_visible = lazy = no_timing = densify = antialiasing = absgrad = False
     backend = "nccl"
     dp_overlap = False
     weight_policy = None
@@ -582,6 +607,8 @@ def main(argv=None):
             lazy = no_timing = True
         elif flag == "--antialiasing":
             antialiasing = True
+        elif flag == "--absgrad":
+            absgrad = True
         elif flag.startswith("--weight-policy="):
             from . import rasterizer
             weight_policy = flag.split("=", 1)[1]
@@ -589,7 +616,7 @@ def main(argv=None):
         elif flag.startswith("--backend="):       # gloo: CPU tests of the launcher with a stand-in trainer (the rasterizer has no CPU path)
             backend = flag.split("=", 1)[1]
         else:
-            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --hip-adam=visible --hip-densify --lazy-loss --no-iter-timing --antialiasing --weight-policy=NAME, then the script and ITS arguments)")
+            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --hip-adam=visible --hip-densify --lazy-loss --no-iter-timing --antialiasing --absgrad --weight-policy=NAME, then the script and ITS arguments)")
     if adam and hip:
         raise SystemExit(f"lightgaussian_amd.run: --fused-adam and {'--hip-adam=visible' if hip_visible else '--hip-adam'} exclude each other (one optimizer step per run)")
     if hip_visible and distributed:
@@ -597,6 +624,9 @@ def main(argv=None):
                          "union of the ranks' views, which is not exchanged)")
     if hip_visible and no_patch:
         raise SystemExit("lightgaussian_amd.run: --hip-adam=visible and --no-patch exclude each other (the visibility is recorded by the patched render())")
+    if absgrad and distributed:
+        raise SystemExit("lightgaussian_amd.run: --absgrad and --distributed exclude each other (the data-parallel add_densification_stats "
+                         "reads viewspace_point_tensor.grad)")
     if not argv:
         raise SystemExit(__doc__)
     script = os.path.abspath(argv[0])
@@ -654,6 +684,10 @@ def main(argv=None):
         event_timing("skip" if no_timing else "wait")
     if densify:
         hip_densify()           # before patch_reference: dp.install wraps the densify_and_prune it finds
+    if absgrad:
+        absgrad_densify()       # after hip_densify: add_densification_stats is the absgrad-reading one
+        print("[lightgaussian_amd.run] --absgrad: densification statistics are sums of ABSOLUTE per-pixel gradients, which are larger than the "
+              "signed ones: densify_grad_threshold usually needs raising (AbsGS and gsplat use 2-4 x the default)", file=sys.stderr)
     if not no_patch:
         # --distributed is DATA-PARALLEL training (lightgaussian_amd.dp): a camera shard per rank, the gradients averaged over the
         # ranks in front of every optimizer.step(), prune_list sharded by camera; the ranks stay bit-identical replicas of one model
