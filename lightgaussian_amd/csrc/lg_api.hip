@@ -35,6 +35,10 @@
 //      gradient row per instance at its pre-sort slot, recomputed from the Gaussian's tile rectangle)
 //   K9 per-Gaussian gather of its contiguous rows + cov2D/cov3D/projection/SH backward
 // Written for wave64; no CUDA compatibility paths.
+//
+// Host side, what a new entry point plugs into: refuse(who, what) and check_view / sh_shape_ok for its refusals; view_state for the
+// buffers a forward left; one *_kernel() selector and one launch line per templated kernel, KCHECK / KLAUNCHED behind it; GradOut /
+// BackwardOpts for a backward; lg_sort_error_word (lg_sort.h) for a sort without view counters.
 #include "lg_host.h"
 #include "lg_wave.h"
 #include "lg_preprocess.h"
@@ -83,6 +87,23 @@ static ViewFault check_view(const lg_view* v, int N)
     return (q.gx >= 65536 || q.gy >= 65536) ? VIEW_TOO_LARGE : VIEW_OK;
 }
 
+// The state a forward left, as the entry points behind it see it: what view_geom derives and the three carved buffers.  The callers hold
+// these buffers as const (they read them); this is the one place that casts.  NULL for a buffer the caller does not look at.
+struct ViewState { ViewGeom q; GeomView geo; ImgView img; BinView bin; };
+static ViewState view_state(const lg_view* v, int N, const void* geom_p, const void* img_p, const void* bin_p, int64_t R)
+{
+    ViewState s;
+    s.q = view_geom(v, N);
+    s.geo = carve_geom(const_cast<void*>(geom_p), N);
+    s.img = carve_img(const_cast<void*>(img_p), s.q.W, s.q.H);
+    s.bin = carve_bin(const_cast<void*>(bin_p), R, s.q.W, s.q.H, s.q.S);
+    return s;
+}
+
+// M SH coefficients per channel evaluated up to degree D: what check_args, lg_sh_grad_from_rgb, lg_vq_colors and lg_vq_colors_bwd accept,
+// each with its own message
+static bool sh_shape_ok(int M, int D) { return (M == 1 || M == 4 || M == 9 || M == 16) && D >= 0 && D <= 3 && (D + 1) * (D + 1) <= M; }
+
 static int check_args(const lg_view* v, const lg_gaussians* g)
 {
     if (!v || !g) return fail(LG_ERR_INVALID_ARGUMENT, "null view/gaussians");
@@ -104,9 +125,8 @@ static int check_args(const lg_view* v, const lg_gaussians* g)
     if ((v->flags & LG_FLAG_RAW_PARAMS) && g->shs && g->M > 1 && !g->shs_rest)
         return fail(LG_ERR_INVALID_ARGUMENT, "LG_FLAG_RAW_PARAMS with M > 1 needs shs (dc) and shs_rest");
     if (g->shs) {
-        if (!(g->M == 1 || g->M == 4 || g->M == 9 || g->M == 16)) return fail(LG_ERR_INVALID_ARGUMENT, "M must be 1, 4, 9 or 16");
-        if (v->sh_degree < 0 || v->sh_degree > 3 || (v->sh_degree + 1) * (v->sh_degree + 1) > g->M)
-            return fail(LG_ERR_INVALID_ARGUMENT, "sh_degree needs (D+1)^2 <= M, D <= 3");
+        if (!sh_shape_ok(g->M, 0)) return fail(LG_ERR_INVALID_ARGUMENT, "M must be 1, 4, 9 or 16");       // (degree 0 fits every M there is)
+        if (!sh_shape_ok(g->M, v->sh_degree)) return fail(LG_ERR_INVALID_ARGUMENT, "sh_degree needs (D+1)^2 <= M, D <= 3");
     }
     if (!v->bg || !v->viewmatrix || !v->projmatrix || !v->campos || !g->means3D || !g->opacities)
         return fail(LG_ERR_INVALID_ARGUMENT, "missing required pointer");
@@ -141,12 +161,18 @@ struct PinnedSlot {
     PinnedSlot& operator=(const PinnedSlot&) = delete;
 };
 
-#define KCHECK(name)                                                                         \
+// Behind every launch.  KLAUNCHED: the launch error alone -- the entry points without LG_FLAG_DEBUG never synchronise.
+// KCHECK: the entry points that read LG_FLAG_DEBUG into a local `debug` also wait for `stream` under it and report the execution error.
+#define KLAUNCHED(name)                                                                      \
     do {                                                                                     \
         hipError_t _e = hipGetLastError();                                                   \
         if (_e != hipSuccess) return fail(LG_ERR_DEVICE, name " launch", _e);                \
+    } while (0)
+#define KCHECK(name)                                                                         \
+    do {                                                                                     \
+        KLAUNCHED(name);                                                                     \
         if (debug) {                                                                         \
-            _e = hipStreamSynchronize(stream);                                               \
+            hipError_t _e = hipStreamSynchronize(stream);                                    \
             if (_e != hipSuccess) return fail(LG_ERR_DEVICE, name " execution", _e);         \
         }                                                                                    \
     } while (0)
@@ -191,6 +217,40 @@ static PreprocessBwdKernel preprocess_bwd_kernel(bool raw, bool jac, bool antial
 #undef LG_K9
     return k[antialias][raw][jac];
 }
+using CameraBwdKernel = decltype(&lg_camera_bwd<false, false>);
+static CameraBwdKernel camera_bwd_kernel(bool raw, bool antialias)
+{
+    static const CameraBwdKernel k[2][2] = { { lg_camera_bwd<false, false>, lg_camera_bwd<true, false> }, { lg_camera_bwd<false, true>, lg_camera_bwd<true, true> } };   // [antialias][raw]
+    return k[antialias][raw];
+}
+using VqNearestKernel = decltype(&lg_vq_nearest_kernel<2>);
+static VqNearestKernel vq_nearest_kernel(int dk2)      // dk2: lg_vq_dk2(d), one of these eight
+{
+    switch (dk2) {
+        case 2: return lg_vq_nearest_kernel<2>;
+        case 4: return lg_vq_nearest_kernel<4>;
+        case 7: return lg_vq_nearest_kernel<7>;
+        case 8: return lg_vq_nearest_kernel<8>;
+        case 14: return lg_vq_nearest_kernel<14>;
+        case 16: return lg_vq_nearest_kernel<16>;
+        case 25: return lg_vq_nearest_kernel<25>;
+        default: return lg_vq_nearest_kernel<32>;
+    }
+}
+// the kernels with one variant per SH coefficient count M (1, 4, 9 or 16: sh_shape_ok)
+#define LG_BY_M(KERNEL, M) ((M) == 1 ? KERNEL<1> : (M) == 4 ? KERNEL<4> : (M) == 9 ? KERNEL<9> : KERNEL<16>)
+static decltype(&lg_vq_colors_kernel<1>) vq_colors_kernel(int M) { return LG_BY_M(lg_vq_colors_kernel, M); }
+static decltype(&lg_vq_colors_bwd_rows_kernel<1>) vq_colors_bwd_rows_kernel(int M) { return LG_BY_M(lg_vq_colors_bwd_rows_kernel, M); }
+static decltype(&lg_vq_colors_bwd_chunk_kernel<1>) vq_colors_bwd_chunk_kernel(int M) { return LG_BY_M(lg_vq_colors_bwd_chunk_kernel, M); }
+#undef LG_BY_M
+// the kernels with two variants
+#define LG_BY_FLAG(KERNEL, on) ((on) ? KERNEL<true> : KERNEL<false>)
+static decltype(&lg_vq_chunk_sum<false>) vq_chunk_sum_kernel(bool weighted) { return LG_BY_FLAG(lg_vq_chunk_sum, weighted); }
+static decltype(&lg_adam_kernel<false>) adam_kernel(bool decoupled) { return LG_BY_FLAG(lg_adam_kernel, decoupled); }
+static decltype(&lg_adam_rows_kernel<false>) adam_rows_kernel(bool decoupled) { return LG_BY_FLAG(lg_adam_rows_kernel, decoupled); }
+static decltype(&lg_filter3d_apply_kernel<false>) filter3d_apply_kernel(bool raw) { return LG_BY_FLAG(lg_filter3d_apply_kernel, raw); }
+static decltype(&lg_filter3d_apply_bwd_kernel<false>) filter3d_apply_bwd_kernel(bool raw) { return LG_BY_FLAG(lg_filter3d_apply_bwd_kernel, raw); }
+#undef LG_BY_FLAG
 
 // Arguments of the capacity-bounded forward (lg_forward_bounded); NULL = exact forward with its one read-back.
 struct Bounded { void* binning; int64_t capacity; float max_depth; uint32_t* status; uint32_t* host_status; };
@@ -486,38 +546,41 @@ extern "C" int lg_forward_bounded(const lg_view* view, const lg_gaussians* g, vo
     return forward_impl(view, g, geom, img, nullptr, nullptr, &b, weight_policy, out_color, out_radii, out_count, out_score, nullptr, nullptr, stream);
 }
 
+// the nine per-Gaussian gradient outputs of a backward, in the order of the C ABI's dL_d* arguments (the Python side's _GradSet.SLOTS)
+struct GradOut { float *means2D, *means3D, *shs, *colors, *opacity, *scales, *rotations, *cov3D, *shs_rest; };
+// what lg_backward_features adds to a backward: a loss on the feature image and / or on alpha (lg_features_bwd_geom, lg_features.h)
+struct FeatGrad { const float* features; int C; const float* bg; const float* dL_dout; const float* dL_dalpha; };
+// the rest of a backward call: K9's chunks and their callback (lg_backward_chunked), lg_backward_features' losses, lg_backward_abs' output
+struct BackwardOpts { int chunks; lg_chunk_fn on_chunk; void* user; const FeatGrad* fg = nullptr; float* means2D_abs = nullptr; };
+
 // K9 (lg_preprocess_bwd) over the moment rows [R][12] a blend backward left: sums every Gaussian's rows and chains them to every input.
 // Shared by lg_backward / lg_backward_chunked (rows from K7) and lg_backward_features (rows from K7 and / or lg_features_bwd_geom).
-static void preprocess_bwd_launch(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const ViewGeom& q, const GeomView& geo,
-                                  const BinView& bin, const float* rows, float* dL_dmeans2D, float* dL_dmeans3D, float* dL_dshs,
-                                  float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                                  float* dL_dshs_rest, bool rgb_only, hipStream_t stream, int chunks, lg_chunk_fn on_chunk, void* user)
+static void preprocess_bwd_launch(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const ViewState& s, const float* rows, const GradOut& d,
+                                  bool rgb_only, hipStream_t stream, const BackwardOpts& o)
 {
+    const ViewGeom& q = s.q; const GeomView& geo = s.geo; const BinView& bin = s.bin;
     // K9 runs over Gaussian ranges: `chunks` launches of consecutive 64-Gaussian workgroups.  After each launch is enqueued
     // the caller is told (on_chunk): rows [first, first + count) of every gradient tensor are final once the stream reaches
     // that point -- a data-parallel trainer starts their all-reduce there, while K9 computes the next range.
     const int N = g->N, W = q.W, H = q.H, S = q.S;
     ProfScope ps(v->flags & LG_FLAG_PROFILE, "preprocess_bwd", stream);
     const int nblk = (N + LG_PP - 1) / LG_PP;
-    if (chunks < 1) chunks = 1;
-    if (chunks > nblk) chunks = nblk;
+    const int chunks = std::max(1, std::min(o.chunks, nblk));
     const int per = (nblk + chunks - 1) / chunks;
     for (int first_blk = 0; first_blk < nblk; first_blk += per) {
         const int nb = std::min(per, nblk - first_blk);
         // (the view of a backward is the view of its forward: LG_FLAG_SAVE_SH_JACOBIAN says K1 left the SH direction Jacobians)
-        const bool jac = (v->flags & LG_FLAG_SAVE_SH_JACOBIAN) && g->shs && (dL_dshs || rgb_only);
+        const bool jac = (v->flags & LG_FLAG_SAVE_SH_JACOBIAN) && g->shs && (d.shs || rgb_only);
         preprocess_bwd_kernel(v->flags & LG_FLAG_RAW_PARAMS, jac, v->flags & LG_FLAG_ANTIALIAS)<<<nb, LG_PP, 0, stream>>>(
             N, first_blk, g->M, v->sh_degree, W, H, v->tanfovx, v->tanfovy, v->scale_modifier, v->viewmatrix, v->projmatrix, v->campos, g->means3D,
             g->shs, g->shs_rest, g->colors_precomp, g->opacities, g->scales, g->rotations, g->cov3D_precomp, radii, geo.rec, geo.counters, bin.meta,
-            (uint32_t)S, geo.touched, geo.offsets, reinterpret_cast<const float4*>(rows), geo.shjac, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dshs_rest,
-            dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D);
-        if (on_chunk) on_chunk(user, first_blk * LG_PP, std::min(N - first_blk * LG_PP, nb * LG_PP));
+            (uint32_t)S, geo.touched, geo.offsets, reinterpret_cast<const float4*>(rows), geo.shjac, d.means2D, d.means3D, d.shs, d.shs_rest,
+            d.colors, d.opacity, d.scales, d.rotations, d.cov3D);
+        if (o.on_chunk) o.on_chunk(o.user, first_blk * LG_PP, std::min(N - first_blk * LG_PP, nb * LG_PP));
     }
 }
 
-// what lg_backward_features adds to a backward: a loss on the feature image and / or on alpha (lg_features_bwd_geom, lg_features.h)
-struct FeatGrad { const float* features; int C; const float* bg; const float* dL_dout; const float* dL_dalpha; };
-static LgFeatView features_view(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const ViewGeom& q);
+static LgFeatView features_view(const ViewState& s, int32_t N, int64_t R);
 // channels of the next walk when rem are left: as many as the registers take -- one walk up to 32 channels, two up to 64
 static int features_channel_group(int rem) { return rem <= 4 ? 4 : rem <= 16 ? 16 : 32; }
 using FeaturesBwdGeomKernel = decltype(&lg_features_bwd_geom<4, true, true>);
@@ -530,81 +593,76 @@ static FeaturesBwdGeomKernel features_bwd_geom_kernel(int cg, bool exact, bool a
 }
 
 static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const void* geom_p, const void* bin_p,
-                         const void* img_p, int64_t R, const float* dL_dcolor, float* dL_dmeans2D, float* dL_dmeans3D,
-                         float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
-                         float* dL_dcov3D, float* dL_dshs_rest, void* scratch, void* stream_p, int chunks, lg_chunk_fn on_chunk, void* user,
-                         const FeatGrad* fg = nullptr, float* dL_dmeans2D_abs = nullptr)
+                         const void* img_p, int64_t R, const float* dL_dcolor, const GradOut& d, void* scratch, void* stream_p, const BackwardOpts& o)
 {
     int rc = check_args(v, g);
     if (rc != LG_OK) return rc;
     if (g->N == 0) return LG_OK;   // empty model: torch hands over NULL pointers for empty tensors, and there is nothing to write
     // SH inputs without dL_dshs but WITH dL_dcolors: K9's rgb_only mode (dL/d rgb per Gaussian instead of the coefficient gradients;
     // lg_sh_grad_from_rgb rebuilds them) -- then dL_dshs_rest is not needed either
-    const bool rgb_only = g->shs && !dL_dshs && dL_dcolors;
-    if (g->shs_rest && !dL_dshs_rest && !rgb_only) return fail(LG_ERR_INVALID_ARGUMENT, "missing gradient output for shs_rest");
-    if (rgb_only && dL_dshs_rest) return fail(LG_ERR_INVALID_ARGUMENT, "dL_dshs_rest without dL_dshs");
-    if (!radii || !geom_p || !bin_p || !img_p || (!dL_dcolor && !fg) || !dL_dmeans2D || !dL_dmeans3D || !dL_dopacity || !scratch)
+    const bool rgb_only = g->shs && !d.shs && d.colors;
+    if (g->shs_rest && !d.shs_rest && !rgb_only) return fail(LG_ERR_INVALID_ARGUMENT, "missing gradient output for shs_rest");
+    if (rgb_only && d.shs_rest) return fail(LG_ERR_INVALID_ARGUMENT, "dL_dshs_rest without dL_dshs");
+    if (!radii || !geom_p || !bin_p || !img_p || (!dL_dcolor && !o.fg) || !d.means2D || !d.means3D || !d.opacity || !scratch)
         return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
-    if ((g->shs && !dL_dshs && !rgb_only) || (g->colors_precomp && !dL_dcolors) || (g->scales && (!dL_dscales || !dL_drotations)) ||
-        (g->cov3D_precomp && !dL_dcov3D))
+    if ((g->shs && !d.shs && !rgb_only) || (g->colors_precomp && !d.colors) || (g->scales && (!d.scales || !d.rotations)) ||
+        (g->cov3D_precomp && !d.cov3D))
         return fail(LG_ERR_INVALID_ARGUMENT, "missing gradient output for a provided input");
     hipStream_t stream = (hipStream_t)stream_p;
     const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE;
     const int N = g->N;
-    const ViewGeom q = view_geom(v, N);     // S must be the forward's (same lg_view); the kernels compare it with meta[2] and refuse otherwise
+    // S must be the forward's (same lg_view); the kernels compare it with meta[2] and refuse otherwise
+    const ViewState s = view_state(v, N, geom_p, img_p, bin_p, R);
+    const ViewGeom& q = s.q; const GeomView& geo = s.geo; const ImgView& img = s.img; const BinView& bin = s.bin;
     const int W = q.W, H = q.H, S = q.S;
-    GeomView geo = carve_geom(const_cast<void*>(geom_p), N);
-    ImgView img = carve_img(const_cast<void*>(img_p), W, H);
-    BinView bin = carve_bin(const_cast<void*>(bin_p), R, W, H, S);
     float* rows = (float*)scratch; // [R][12] gradient rows, every row written by lg_blend_bwd
     const uint32_t max_items = (uint32_t)(q.ntiles + R / S + 1);
     // (the work list of the backward blend -- one item per (tile, segment of S entries), longest first -- was left in the binning
     // buffer by the forward: one extra workgroup of lg_blend_fwd)
     if (R > 0 && dL_dcolor) {
         ProfScope ps(prof, "blend_bwd", stream);
-        blend_bwd_kernel(!(v->flags & LG_FLAG_FAST_EXP), dL_dmeans2D_abs != nullptr)<<<max_items, 64, 0, stream>>>(W, H, q.gx, S, bin.work, bin.meta, bin.ranges, bin.entries, q.gid_mask, geo.tinfo,
+        blend_bwd_kernel(!(v->flags & LG_FLAG_FAST_EXP), o.means2D_abs != nullptr)<<<max_items, 64, 0, stream>>>(W, H, q.gx, S, bin.work, bin.meta, bin.ranges, bin.entries, q.gid_mask, geo.tinfo,
                                                                                        geo.rec, v->bg, img.final_T, img.n_contrib, dL_dcolor, bin.ckpt, rows);
     }
     KCHECK("lg_blend_bwd");
-    if (dL_dmeans2D_abs) {
+    if (o.means2D_abs) {
         // lg_backward_abs: floats 9 and 10 of the rows summed per Gaussian, in front of the first K9 chunk (K9 does not read them)
         {
             ProfScope ps(prof, "absgrad_rows", stream);
             lg_absgrad_rows<<<(N + LG_ABS_THREADS - 1) / LG_ABS_THREADS, LG_ABS_THREADS, 0, stream>>>(
                 N, W, H, (uint32_t)R, radii, geo.rec, geo.counters, bin.meta, (uint32_t)S, geo.touched, geo.offsets,
-                reinterpret_cast<const float4*>(rows), dL_dmeans2D_abs);
+                reinterpret_cast<const float4*>(rows), o.means2D_abs);
         }
         KCHECK("lg_absgrad_rows");
     }
-    if (fg && R > 0) {
+    if (o.fg && R > 0) {
         // lg_backward_features: the moments of the feature / alpha loss join K7's in the same rows (lg_features.h), CG channels per walk;
         // the first walk writes whole rows, zeros included, when K7 did not run -- also when there is no image gradient at all
         const bool exact = !(v->flags & LG_FLAG_FAST_EXP);
-        const LgFeatView f = features_view(v, N, geom_p, bin_p, R, q);
-        if (fg->dL_dout || fg->dL_dalpha || !dL_dcolor) {
-            const int nch = fg->dL_dout ? fg->C : 1;     // without dL_dout one walk: dL_dalpha's, or the zero rows
+        const LgFeatView f = features_view(s, N, R);
+        if (o.fg->dL_dout || o.fg->dL_dalpha || !dL_dcolor) {
+            const int nch = o.fg->dL_dout ? o.fg->C : 1;     // without dL_dout one walk: dL_dalpha's, or the zero rows
             bool accum = dL_dcolor != nullptr;
             for (int c0 = 0, cg; c0 < nch; c0 += cg) {
                 cg = features_channel_group(nch - c0);
                 {
                     ProfScope ps(prof, "features_bwd_geom", stream);
-                    features_bwd_geom_kernel(cg, exact, accum)<<<q.ntiles_pad, 256, 0, stream>>>(f, (uint32_t)S, bin.meta, fg->C, c0, geo.tinfo, fg->features,
-                                                                                                fg->bg, fg->dL_dout, fg->dL_dalpha, img.final_T, img.n_contrib, rows);
+                    features_bwd_geom_kernel(cg, exact, accum)<<<q.ntiles_pad, 256, 0, stream>>>(f, (uint32_t)S, bin.meta, o.fg->C, c0, geo.tinfo, o.fg->features,
+                                                                                                o.fg->bg, o.fg->dL_dout, o.fg->dL_dalpha, img.final_T, img.n_contrib, rows);
                 }
                 KCHECK("lg_features_bwd_geom");
                 accum = true;
             }
         }
     }
-    preprocess_bwd_launch(v, g, radii, q, geo, bin, rows, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
-                          dL_dcov3D, dL_dshs_rest, rgb_only, stream, chunks, on_chunk, user);
+    preprocess_bwd_launch(v, g, radii, s, rows, d, rgb_only, stream, o);
     KCHECK("lg_preprocess_bwd");
     if (debug && R > 0) {
         uint32_t h_seg = 0;
         HIP_TRY(hipMemcpyAsync(&h_seg, bin.meta + 2, 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if (h_seg != (uint32_t)S) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward: lg_view.segment_length differs from the forward's (gradients are zero)");
-        if ((v->flags & LG_FLAG_SAVE_SH_JACOBIAN) && g->shs && (dL_dshs || rgb_only)) {
+        if ((v->flags & LG_FLAG_SAVE_SH_JACOBIAN) && g->shs && (d.shs || rgb_only)) {
             uint32_t h_mark = 0;
             HIP_TRY(hipMemcpyAsync(&h_mark, geo.counters + 9, 4, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));
@@ -620,8 +678,8 @@ extern "C" int lg_backward(const lg_view* v, const lg_gaussians* g, const int32_
                            float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations,
                            float* dL_dcov3D, float* dL_dshs_rest, void* scratch, void* stream_p)
 {
-    return backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity,
-                         dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest, scratch, stream_p, 1, nullptr, nullptr);
+    const GradOut d = { dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest };
+    return backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, d, scratch, stream_p, { 1, nullptr, nullptr });
 }
 
 extern "C" int lg_backward_chunked(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const void* geom_p, const void* bin_p,
@@ -630,8 +688,8 @@ extern "C" int lg_backward_chunked(const lg_view* v, const lg_gaussians* g, cons
                                    float* dL_dcov3D, float* dL_dshs_rest, void* scratch, void* stream_p, int32_t chunks,
                                    lg_chunk_fn on_chunk, void* user)
 {
-    return backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity,
-                         dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest, scratch, stream_p, chunks, on_chunk, user);
+    const GradOut d = { dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest };
+    return backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, d, scratch, stream_p, { chunks, on_chunk, user });
 }
 
 // lg_backward_chunked that also leaves the absolute screen-space mean gradients (lg_absgrad.h; the view must carry LG_FLAG_ABSGRAD)
@@ -645,8 +703,8 @@ extern "C" int lg_backward_abs(const lg_view* v, const lg_gaussians* g, const in
     if (!dL_dmeans2D_abs) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_abs: missing dL_dmeans2D_abs");
     if (!dL_dcolor) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_abs: missing dL_dcolor");
     if (R < 0 || R >= (1ll << 30)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_abs: num_rendered out of range");
-    return backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity,
-                         dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest, scratch, stream_p, chunks, on_chunk, user, nullptr, dL_dmeans2D_abs);
+    const GradOut d = { dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest };
+    return backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, d, scratch, stream_p, { chunks, on_chunk, user, nullptr, dL_dmeans2D_abs });
 }
 
 // ---- camera pose gradients (lg_camera.h) ----
@@ -676,20 +734,15 @@ extern "C" int lg_backward_camera(const lg_view* v, const lg_gaussians* g, const
     const uint32_t nwg = N > 0 ? (uint32_t)(((size_t)N + LG_CAM_THREADS - 1) / LG_CAM_THREADS) : 0u;
     double* partials = (double*)scratch;
     if (N > 0) {
-        const ViewGeom q = view_geom(v, N);
-        GeomView geo = carve_geom(const_cast<void*>(geom_p), N);
-        BinView bin = carve_bin(const_cast<void*>(bin_p), R, q.W, q.H, q.S);
+        const ViewState s = view_state(v, N, geom_p, nullptr, bin_p, R);
+        const ViewGeom& q = s.q; const GeomView& geo = s.geo; const BinView& bin = s.bin;
         {
             ProfScope ps(prof, "camera_bwd", stream);
             // (LG_FLAG_ANTIALIAS: the compensation factor of the opacity depends on the camera -- those variants read the input opacities)
-            const bool raw = v->flags & LG_FLAG_RAW_PARAMS;
-            auto kern = (v->flags & LG_FLAG_ANTIALIAS) ? (raw ? lg_camera_bwd<true, true> : lg_camera_bwd<false, true>)
-                                                       : (raw ? lg_camera_bwd<true, false> : lg_camera_bwd<false, false>);
-            kern<<<nwg, LG_CAM_THREADS, 0, stream>>>(N, g->M, v->sh_degree, q.W, q.H, v->tanfovx, v->tanfovy, v->scale_modifier, (uint32_t)R,
-                                                     v->viewmatrix, v->projmatrix, v->campos, g->means3D, g->shs, g->scales, g->rotations,
-                                                     g->cov3D_precomp, radii, geo.rec, geo.counters, bin.meta, (uint32_t)q.S, geo.touched,
-                                                     geo.offsets, reinterpret_cast<const float4*>(backward_scratch), geo.shjac, partials,
-                                                     g->opacities);
+            camera_bwd_kernel(v->flags & LG_FLAG_RAW_PARAMS, v->flags & LG_FLAG_ANTIALIAS)<<<nwg, LG_CAM_THREADS, 0, stream>>>(
+                N, g->M, v->sh_degree, q.W, q.H, v->tanfovx, v->tanfovy, v->scale_modifier, (uint32_t)R, v->viewmatrix, v->projmatrix, v->campos,
+                g->means3D, g->shs, g->scales, g->rotations, g->cov3D_precomp, radii, geo.rec, geo.counters, bin.meta, (uint32_t)q.S, geo.touched,
+                geo.offsets, reinterpret_cast<const float4*>(backward_scratch), geo.shjac, partials, g->opacities);
         }
         KCHECK("lg_camera_bwd");
     }
@@ -705,7 +758,7 @@ extern "C" int lg_sh_grad_from_rgb(int32_t N, int32_t M, int32_t sh_degree, int3
                                    const float* drgb, int64_t view_stride, float divisor, int32_t accumulate, float* dL_dshs, float* dL_dshs_rest,
                                    void* stream_p)
 {
-    if (N < 0 || V < 1 || !(M == 1 || M == 4 || M == 9 || M == 16) || sh_degree < 0 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > M)
+    if (N < 0 || V < 1 || !sh_shape_ok(M, sh_degree))
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_sh_grad_from_rgb: N >= 0, V >= 1, M in {1, 4, 9, 16}, (D + 1)^2 <= M required");
     if (N == 0) return LG_OK;
     if (!means3D || !campos || !drgb || !dL_dshs || view_stride < 3 * (int64_t)N || !(divisor > 0.0f))
@@ -714,8 +767,7 @@ extern "C" int lg_sh_grad_from_rgb(int32_t N, int32_t M, int32_t sh_degree, int3
     hipStream_t stream = (hipStream_t)stream_p;
     lg_sh_grad_from_rgb_kernel<<<(N + LG_PP - 1) / LG_PP, LG_PP, 0, stream>>>(N, M, sh_degree, V, means3D, campos, drgb, (size_t)view_stride, divisor,
                                                                            accumulate ? 1 : 0, dL_dshs, dL_dshs_rest);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_sh_grad_from_rgb_kernel launch", e);
+    KLAUNCHED("lg_sh_grad_from_rgb_kernel");
     return LG_OK;
 }
 
@@ -725,8 +777,7 @@ extern "C" int lg_score_from_count(int32_t N, const int32_t* count, const float*
     if (N == 0) return LG_OK;
     hipStream_t stream = (hipStream_t)stream_p;
     lg_score_kernel<<<(N + 255) / 256, 256, 0, stream>>>(N, count, weight, score, nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_score_kernel launch", e);
+    KLAUNCHED("lg_score_kernel");
     return LG_OK;
 }
 
@@ -776,16 +827,15 @@ extern "C" int lg_select_mask(int32_t N, const float* values, int64_t rank, uint
     if (N <= 0 || rank < 0 || rank >= N) return fail(LG_ERR_INVALID_ARGUMENT, "lg_select_mask needs N >= 1 and 0 <= rank < N");
     if (!values || !out_value || !scratch) return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false;
     LgSelect* st = (LgSelect*)scratch;
     const int blocks = (int)std::min<int64_t>(((int64_t)N + 255) / 256, 2048);
     HIP_TRY(hipMemsetAsync(st, 0, sizeof(LgSelect), stream));
     for (int p = 0; p < 4; p++) {
         lg_select_pass<1><<<blocks, 256, 0, stream>>>(N, p, (uint32_t)rank, values, st);
-        KCHECK("lg_select_pass");
+        KLAUNCHED("lg_select_pass");
     }
     lg_select_finish_kernel<<<mask ? blocks : 1, 256, 0, stream>>>(N, (uint32_t)rank, values, st, mask, out_value);
-    KCHECK("lg_select_finish_kernel");
+    KLAUNCHED("lg_select_finish_kernel");
     return LG_OK;
 }
 
@@ -796,8 +846,7 @@ extern "C" int lg_ordered_sum(int32_t V, int64_t n, const float* rows, int64_t r
     if (!rows || !out) return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
     hipStream_t stream = (hipStream_t)stream_p;
     lg_ordered_sum_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(V, (size_t)n, rows, (size_t)row_stride, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_ordered_sum_kernel launch", e);
+    KLAUNCHED("lg_ordered_sum_kernel");
     return LG_OK;
 }
 
@@ -813,18 +862,24 @@ extern "C" int lg_compact_plan(int32_t N, const uint8_t* keep, int32_t* dest, in
     if (N < 0) return fail(LG_ERR_INVALID_ARGUMENT, "bad row count");
     if (!count || (N > 0 && (!keep || !dest || !scratch))) return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false;
     if (N == 0) { HIP_TRY(hipMemsetAsync(count, 0, 4, stream)); return LG_OK; }
     const int nb = (N + LG_COMPACT_ROWS - 1) / LG_COMPACT_ROWS;
     uint32_t* blk_sum = (uint32_t*)scratch;
     uint32_t* blk_off = (uint32_t*)((char*)scratch + align_up((size_t)nb * 4));
     lg_compact_count<<<nb, 256, 0, stream>>>(N, keep, blk_sum);
-    KCHECK("lg_compact_count");
+    KLAUNCHED("lg_compact_count");
     lg_scan_words<<<1, 1024, 0, stream>>>(nb, blk_sum, blk_off, count);
-    KCHECK("lg_scan_words");
+    KLAUNCHED("lg_scan_words");
     lg_compact_dest<<<nb, 256, 0, stream>>>(N, keep, blk_off, dest);
-    KCHECK("lg_compact_dest");
+    KLAUNCHED("lg_compact_dest");
     return LG_OK;
+}
+
+// grid of the row moves (lg_compact_move, lg_densify_move): x strides over rows * widest words in workgroups of 1024, 8192 at the most; y = tensor
+static dim3 row_move_grid(size_t rows, size_t widest, int num_tensors)
+{
+    const size_t blocks = std::min<size_t>((rows * widest + 1023) / 1024, 8192);
+    return dim3((unsigned)std::max<size_t>(blocks, 1), (unsigned)num_tensors);
 }
 
 extern "C" int lg_compact_rows(int32_t N, const int32_t* dest, int32_t num_tensors, const void* const* src, void* const* dst,
@@ -834,7 +889,6 @@ extern "C" int lg_compact_rows(int32_t N, const int32_t* dest, int32_t num_tenso
     if (N == 0 || num_tensors == 0) return LG_OK;
     if (!dest || !src || !dst || !row_bytes) return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false;
     LgCompactArgs a;
     memset(&a, 0, sizeof(a));
     size_t widest = 1;
@@ -844,9 +898,8 @@ extern "C" int lg_compact_rows(int32_t N, const int32_t* dest, int32_t num_tenso
         a.src[t] = (const uint32_t*)src[t]; a.dst[t] = (uint32_t*)dst[t]; a.words[t] = (uint32_t)(row_bytes[t] / 4);
         widest = std::max<size_t>(widest, a.words[t]);
     }
-    const size_t blocks = std::min<size_t>(((size_t)N * widest + 1023) / 1024, 8192);
-    lg_compact_move<<<dim3((unsigned)std::max<size_t>(blocks, 1), (unsigned)num_tensors), 256, 0, stream>>>(N, dest, a);
-    KCHECK("lg_compact_move");
+    lg_compact_move<<<row_move_grid((size_t)N, widest, num_tensors), 256, 0, stream>>>(N, dest, a);
+    KLAUNCHED("lg_compact_move");
     return LG_OK;
 }
 
@@ -873,18 +926,7 @@ extern "C" int lg_vq_nearest(int32_t n, int32_t d, int32_t K, const float* x, co
     lg_vq_prepare<<<(Kpad + 255) / 256, 256, 0, stream>>>(K, Kpad, d, dk, codebook, cbA);
     KCHECK("lg_vq_prepare");
     const unsigned grid = (unsigned)((n + 127) / 128);
-#define LAUNCH_VQ(D2) lg_vq_nearest_kernel<D2><<<grid, 256, 0, stream>>>(n, d, Kpad, x, cbA, out_index)
-    switch (dk2) {
-        case 2: LAUNCH_VQ(2); break;
-        case 4: LAUNCH_VQ(4); break;
-        case 7: LAUNCH_VQ(7); break;
-        case 8: LAUNCH_VQ(8); break;
-        case 14: LAUNCH_VQ(14); break;
-        case 16: LAUNCH_VQ(16); break;
-        case 25: LAUNCH_VQ(25); break;
-        default: LAUNCH_VQ(32); break;
-    }
-#undef LAUNCH_VQ
+    vq_nearest_kernel(dk2)<<<grid, 256, 0, stream>>>(n, d, Kpad, x, cbA, out_index);
     KCHECK("lg_vq_nearest_kernel");
     return LG_OK;
 }
@@ -893,7 +935,7 @@ extern "C" int lg_vq_nearest(int32_t n, int32_t d, int32_t K, const float* x, co
 extern "C" int lg_vq_colors(int32_t N, int32_t M, int32_t sh_degree, const float* means3D, const float* campos, const uint32_t* slot,
                             const void* rows_f16, int32_t row_stride_bytes, float* out_rgb, uint32_t flags, void* stream_p)
 {
-    if (N < 0 || !(M == 1 || M == 4 || M == 9 || M == 16) || sh_degree < 0 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > M)
+    if (N < 0 || !sh_shape_ok(M, sh_degree))
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_colors: N >= 0, M in {1, 4, 9, 16}, (D + 1)^2 <= M required");
     if (row_stride_bytes < 6 * M || (row_stride_bytes & 15) != 0 || ((uintptr_t)rows_f16 & 15) != 0)
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_colors: rows must be 16-byte aligned, row_stride_bytes a multiple of 16 and >= 6 M");
@@ -904,15 +946,7 @@ extern "C" int lg_vq_colors(int32_t N, int32_t M, int32_t sh_degree, const float
     const uint32_t need = lg_vq_need_mask(M, sh_degree);
     const unsigned grid = (unsigned)((N + LG_PP - 1) / LG_PP);
     ProfScope ps(prof, "vq_colors", stream);
-#define LAUNCH_VQC(MM) lg_vq_colors_kernel<MM><<<grid, LG_PP, 0, stream>>>(N, sh_degree, need, means3D, campos, slot, (const unsigned char*)rows_f16, \
-                                                                          (uint32_t)row_stride_bytes, out_rgb)
-    switch (M) {
-        case 1: LAUNCH_VQC(1); break;
-        case 4: LAUNCH_VQC(4); break;
-        case 9: LAUNCH_VQC(9); break;
-        default: LAUNCH_VQC(16); break;
-    }
-#undef LAUNCH_VQC
+    vq_colors_kernel(M)<<<grid, LG_PP, 0, stream>>>(N, sh_degree, need, means3D, campos, slot, (const unsigned char*)rows_f16, (uint32_t)row_stride_bytes, out_rgb);
     KCHECK("lg_vq_colors_kernel");
     return LG_OK;
 }
@@ -922,6 +956,25 @@ extern "C" size_t lg_vq_ema_scratch_bytes(int32_t n, int32_t K, int32_t d)
 {
     if (n < 0 || n >= (1 << 30) || lg_vq_scratch_bytes(K, d) == 0) return 0;
     return carve_vq_ema(nullptr, (size_t)n, (size_t)K, (size_t)d).total;
+}
+
+// Groups n keys (code << 32 | element) by code: sorts them on the code bits, then leaves the start of each of the `lists` lists and the
+// chunk offsets of the first K.  lg_vq_ema_step: lists = K, with the weight partials lg_vq_keys left; lg_vq_code_index: lists = K + 1 (the
+// pseudo-code K of the non-VQ Gaussians included), without.  b: the caller's keys_in / keys_out / sort_temp (VqEmaView, VqIndexScratch).
+template <class Bufs>
+static int vq_group_by_code(const Bufs& b, uint32_t n, uint32_t K, uint32_t lists, uint32_t* start, uint32_t* chunk_off, uint32_t nwpart,
+                            const float* wpart, float* scal, bool debug, hipStream_t stream)
+{
+    int code_bits = 1;
+    while (code_bits < 31 && (1u << code_bits) < lists) code_bits++;
+    size_t tb = b.sort_temp_bytes;
+    HIP_TRY(lg_sort_keys(b.sort_temp, tb, b.keys_in, b.keys_out, n, 32, 32 + code_bits, nullptr, false, stream));
+    KCHECK("lg_sort_keys");
+    lg_vq_starts<<<(n + 255) / 256, 256, 0, stream>>>(n, lists, b.keys_out, start);
+    KCHECK("lg_vq_starts");
+    lg_vq_chunk_scan<<<1, LG_VQ_RED_THREADS, 0, stream>>>(K, start, chunk_off, nwpart, wpart, scal);
+    KCHECK("lg_vq_chunk_scan");
+    return LG_OK;
 }
 
 extern "C" int lg_vq_ema_step(int32_t n, int32_t d, int32_t K, const float* x, const float* weight, float* embed, float* cluster_size,
@@ -940,27 +993,19 @@ extern "C" int lg_vq_ema_step(int32_t n, int32_t d, int32_t K, const float* x, c
     }
     const uint32_t un = (uint32_t)n, uK = (uint32_t)K;
     const uint32_t nwpart = (un + LG_VQ_WSUM_TILE - 1) / LG_VQ_WSUM_TILE;
-    int code_bits = 1;
-    while (code_bits < 31 && (1u << code_bits) < uK) code_bits++;
-    const uint32_t* sort_err = (const uint32_t*)((char*)v.sort_temp + lg_sort_layout((size_t)n).ticket_off) + 15;
+    const uint32_t* sort_err = lg_sort_error_word(v.sort_temp, (size_t)n);
     {
         ProfScope ps(prof, "vq_ema_index", stream);
         lg_vq_keys<<<nwpart, 256, 0, stream>>>(un, uK, out_index, weight, v.keys_in, v.wpart);
         KCHECK("lg_vq_keys");
-        size_t tb = v.sort_temp_bytes;
-        HIP_TRY(lg_sort_keys(v.sort_temp, tb, v.keys_in, v.keys_out, un, 32, 32 + code_bits, nullptr, false, stream));
-        KCHECK("lg_sort_keys");
-        lg_vq_starts<<<(un + 255) / 256, 256, 0, stream>>>(un, uK, v.keys_out, v.start);
-        KCHECK("lg_vq_starts");
-        lg_vq_chunk_scan<<<1, LG_VQ_RED_THREADS, 0, stream>>>(uK, v.start, v.chunk_off, nwpart, weight ? v.wpart : nullptr, v.scal);
-        KCHECK("lg_vq_chunk_scan");
+        const int rc = vq_group_by_code(v, un, uK, uK, v.start, v.chunk_off, nwpart, weight ? v.wpart : nullptr, v.scal, debug, stream);
+        if (rc != LG_OK) return rc;
     }
     const float decay_f = (float)decay, one_minus = (float)(1.0 - decay);      // what torch makes of mul_(decay).add_(new, alpha = 1 - decay)
     {
         ProfScope ps(prof, "vq_ema_sum", stream);
         const unsigned grid = (unsigned)((v.max_chunks + 3) / 4);
-        if (weight) lg_vq_chunk_sum<true><<<grid, 256, 0, stream>>>(un, d, uK, x, weight, v.scal, v.keys_out, v.start, v.chunk_off, v.partial);
-        else lg_vq_chunk_sum<false><<<grid, 256, 0, stream>>>(un, d, uK, x, weight, v.scal, v.keys_out, v.start, v.chunk_off, v.partial);
+        vq_chunk_sum_kernel(weight != nullptr)<<<grid, 256, 0, stream>>>(un, d, uK, x, weight, v.scal, v.keys_out, v.start, v.chunk_off, v.partial);
         KCHECK("lg_vq_chunk_sum");
         lg_vq_combine<<<(unsigned)(((size_t)K * (d + 1) + 255) / 256), 256, 0, stream>>>(uK, d, v.chunk_off, v.partial, v.esum, cluster_size, decay_f,
                                                                                           one_minus, sort_err);
@@ -995,7 +1040,6 @@ extern "C" int lg_vq_code_index(int32_t N, int32_t K, const uint32_t* slot, void
     if (!vq_index_shape_ok(N, K)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_code_index: need 0 <= N < 2^30, 1 <= K <= 2^24");
     if (!index || (N > 0 && (!slot || !scratch))) return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_code_index: missing buffer");
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false;
     const VqIndexView v = carve_vq_index(index, (size_t)N, (size_t)K);
     if (N == 0) {                                   // every list empty: start = chunk_off = 0, no error
         HIP_TRY(hipMemsetAsync(index, 0, v.total, stream));
@@ -1003,20 +1047,13 @@ extern "C" int lg_vq_code_index(int32_t N, int32_t K, const uint32_t* slot, void
     }
     const VqIndexScratch s = carve_vq_index_scratch(scratch, (size_t)N);
     const uint32_t un = (uint32_t)N, uK = (uint32_t)K;
-    int code_bits = 1;
-    while ((1u << code_bits) <= uK) code_bits++;    // the pseudo-code K of the non-VQ Gaussians included
     lg_vq_slot_keys<<<(un + 255) / 256, 256, 0, stream>>>(un, uK, slot, s.keys_in);
-    KCHECK("lg_vq_slot_keys");
-    size_t tb = s.sort_temp_bytes;
-    HIP_TRY(lg_sort_keys(s.sort_temp, tb, s.keys_in, s.keys_out, un, 32, 32 + code_bits, nullptr, false, stream));
-    KCHECK("lg_sort_keys");
-    lg_vq_starts<<<(un + 255) / 256, 256, 0, stream>>>(un, uK + 1u, s.keys_out, v.start);
-    KCHECK("lg_vq_starts");
-    lg_vq_chunk_scan<<<1, LG_VQ_RED_THREADS, 0, stream>>>(uK, v.start, v.chunk_off, 0u, nullptr, nullptr);
-    KCHECK("lg_vq_chunk_scan");
-    const uint32_t* sort_err = (const uint32_t*)((char*)s.sort_temp + lg_sort_layout((size_t)N).ticket_off) + 15;
+    KLAUNCHED("lg_vq_slot_keys");
+    const int rc = vq_group_by_code(s, un, uK, uK + 1u, v.start, v.chunk_off, 0u, nullptr, nullptr, false, stream);
+    if (rc != LG_OK) return rc;
+    const uint32_t* sort_err = lg_sort_error_word(s.sort_temp, (size_t)N);
     lg_vq_index_ids<<<(un + 255) / 256, 256, 0, stream>>>(un, s.keys_out, sort_err, v.ids, v.err);
-    KCHECK("lg_vq_index_ids");
+    KLAUNCHED("lg_vq_index_ids");
     return LG_OK;
 }
 
@@ -1030,8 +1067,7 @@ extern "C" int lg_vq_colors_bwd(int32_t N, int32_t M, int32_t sh_degree, int32_t
                                 const uint32_t* slot, const void* rows_f16, int32_t row_stride_bytes, const float* dL_drgb, const void* index,
                                 float* dL_drows, float* dL_dmeans3D, void* scratch, uint32_t flags, void* stream_p)
 {
-    if (!vq_index_shape_ok(N, K) || !(M == 1 || M == 4 || M == 9 || M == 16) || sh_degree < 0 || sh_degree > 3 ||
-        (sh_degree + 1) * (sh_degree + 1) > M || n_rows < K || n_rows >= ((int64_t)1 << 31))
+    if (!vq_index_shape_ok(N, K) || !sh_shape_ok(M, sh_degree) || n_rows < K || n_rows >= ((int64_t)1 << 31))
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_colors_bwd: 0 <= N < 2^30, M in {1, 4, 9, 16}, (D + 1)^2 <= M, K <= n_rows < 2^31 required");
     if (row_stride_bytes < 6 * M || (row_stride_bytes & 15) != 0 || ((uintptr_t)rows_f16 & 15) != 0)
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_vq_colors_bwd: rows must be 16-byte aligned, row_stride_bytes a multiple of 16 and >= 6 M");
@@ -1047,30 +1083,16 @@ extern "C" int lg_vq_colors_bwd(int32_t N, int32_t M, int32_t sh_degree, int32_t
     if (N > 0) {
         ProfScope ps(prof, "vq_colors_bwd_rows", stream);
         const unsigned grid = (unsigned)((N + LG_VQ_BWD_WAVE - 1) / LG_VQ_BWD_WAVE);
-#define LAUNCH_VQB(MM) lg_vq_colors_bwd_rows_kernel<MM><<<grid, LG_VQ_BWD_WAVE, 0, stream>>>(N, sh_degree, need, uK, (uint32_t)n_rows, means3D, campos, \
-                                                                                           slot, rows, stride, dL_drgb, dL_drows, dL_dmeans3D)
-        switch (M) {
-            case 1: LAUNCH_VQB(1); break;
-            case 4: LAUNCH_VQB(4); break;
-            case 9: LAUNCH_VQB(9); break;
-            default: LAUNCH_VQB(16); break;
-        }
-#undef LAUNCH_VQB
+        vq_colors_bwd_rows_kernel(M)<<<grid, LG_VQ_BWD_WAVE, 0, stream>>>(N, sh_degree, need, uK, (uint32_t)n_rows, means3D, campos, slot, rows, stride, dL_drgb,
+                                                                          dL_drows, dL_dmeans3D);
         KCHECK("lg_vq_colors_bwd_rows_kernel");
     }
     {
         ProfScope ps(prof, "vq_colors_bwd_codes", stream);
         const unsigned grid = (unsigned)lg_vq_bwd_max_chunks((size_t)N, (size_t)K);
         if (grid > 0) {
-#define LAUNCH_VQB(MM) lg_vq_colors_bwd_chunk_kernel<MM><<<grid, LG_VQ_BWD_WAVE, 0, stream>>>(sh_degree, need, uK, means3D, campos, rows, stride, dL_drgb, \
-                                                                                            v.ids, v.start, v.chunk_off, v.err, partial)
-            switch (M) {
-                case 1: LAUNCH_VQB(1); break;
-                case 4: LAUNCH_VQB(4); break;
-                case 9: LAUNCH_VQB(9); break;
-                default: LAUNCH_VQB(16); break;
-            }
-#undef LAUNCH_VQB
+            vq_colors_bwd_chunk_kernel(M)<<<grid, LG_VQ_BWD_WAVE, 0, stream>>>(sh_degree, need, uK, means3D, campos, rows, stride, dL_drgb, v.ids, v.start,
+                                                                               v.chunk_off, v.err, partial);
             KCHECK("lg_vq_colors_bwd_chunk_kernel");
         }
         lg_vq_colors_bwd_combine<<<(unsigned)(((size_t)K * 3 * M + 255) / 256), 256, 0, stream>>>(uK, (uint32_t)(3 * M), v.chunk_off, partial, v.err,
@@ -1081,50 +1103,86 @@ extern "C" int lg_vq_colors_bwd(int32_t N, int32_t M, int32_t sh_degree, int32_t
 }
 
 // ---- Adam / AdamW step (lg_adam.h) ----
-extern "C" int lg_adam_step(int32_t num_tensors, const lg_adam_tensor* tensors, double beta1, double beta2, double eps, uint32_t flags,
-                            void* stream_p)
+// lg_adam_step and lg_adam_step_rows are one step (adam_step) over two table types.  These overloads are all the two differ in: where
+// the dense part of an entry and of the table sits, the row refusals and row fields of a masked entry, and the kernel with its names.
+static const lg_adam_tensor& adam_dense(const lg_adam_tensor& x) { return x; }
+static const lg_adam_tensor& adam_dense(const lg_adam_rows_tensor& x) { return x.t; }
+static LgAdamTable& adam_dense(LgAdamTable& a) { return a; }
+static LgAdamTable& adam_dense(LgAdamRowsTable& r) { return r.a; }
+static const char* adam_rows_fault(const lg_adam_tensor&) { return nullptr; }
+static const char* adam_rows_fault(const lg_adam_rows_tensor& x)
+{
+    if (!x.row_mask) return nullptr;                // dense entry: rows is not looked at
+    if (x.rows < 1) return "rows < 1 with a row_mask";
+    if (x.t.numel % x.rows != 0) return "numel is not a multiple of rows";
+    if (x.t.numel / x.rows > (int64_t)LG_ADAM_MAX_ROW_LEN) return "a row beyond 2^31 - 1 elements";
+    return nullptr;
+}
+static void adam_rows_reset(LgAdamTable&) {}
+static void adam_rows_reset(LgAdamRowsTable& r) { for (int k = 0; k < LG_ADAM_MAX_TENSORS; k++) r.row_len[k] = 1; }
+static void adam_rows_fill(LgAdamTable&, int, const lg_adam_tensor&) {}
+static void adam_rows_fill(LgAdamRowsTable& r, int k, const lg_adam_rows_tensor& x)
+{
+    if (!x.row_mask) return;
+    r.row_mask[k] = x.row_mask;
+    r.row_len[k] = (uint32_t)(x.t.numel / x.rows);
+    r.row_rcp[k] = lg_adam_row_rcp(r.row_len[k]);
+    r.row_thr[k] = lg_adam_row_thr(r.row_len[k]);
+}
+static int adam_launch(const LgAdamTable& a, uint32_t wgs, bool decoupled, bool prof, hipStream_t stream)
+{
+    ProfScope ps(prof, "adam", stream);
+    adam_kernel(decoupled)<<<wgs, LG_ADAM_THREADS, 0, stream>>>(a);
+    KLAUNCHED("lg_adam_kernel");
+    return LG_OK;
+}
+static int adam_launch(const LgAdamRowsTable& r, uint32_t wgs, bool decoupled, bool prof, hipStream_t stream)
+{
+    ProfScope ps(prof, "adam_rows", stream);
+    adam_rows_kernel(decoupled)<<<wgs, LG_ADAM_THREADS, 0, stream>>>(r);
+    KLAUNCHED("lg_adam_rows_kernel");
+    return LG_OK;
+}
+
+// check -> fill -> split -> launch.  A launch takes LG_ADAM_MAX_TENSORS entries and 2^31 - 1 workgroups; a step with more is split.
+template <class Table, class Tensor>
+static int adam_step(const char* who, int32_t num_tensors, const Tensor* tensors, double beta1, double beta2, double eps, uint32_t flags, void* stream_p)
 {
     // everything is checked before the first HIP call: a refused step has touched nothing
-    if (num_tensors < 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: num_tensors < 0");
-    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: betas must lie in [0, 1)");
-    if (num_tensors > 0 && !tensors) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: missing tensor table");
+    if (num_tensors < 0) return refuse(who, "num_tensors < 0");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return refuse(who, "betas must lie in [0, 1)");
+    if (num_tensors > 0 && !tensors) return refuse(who, "missing tensor table");
     for (int t = 0; t < num_tensors; t++) {
-        const lg_adam_tensor& x = tensors[t];
-        if (x.numel < 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: numel < 0");
-        if (x.step < 1) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: step < 1 (the step being taken counts from 1)");
-        if (x.numel == 0) continue;                     // skipped: its pointers are not looked at
-        if (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq)
-            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: null param / grad / exp_avg / exp_avg_sq with numel > 0");
+        const lg_adam_tensor& x = adam_dense(tensors[t]);
+        if (x.numel < 0) return refuse(who, "numel < 0");
+        if (x.step < 1) return refuse(who, "step < 1 (the step being taken counts from 1)");
+        if (x.numel == 0) continue;                     // skipped: its pointers, its mask and its rows are not looked at
+        if (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq) return refuse(who, "null param / grad / exp_avg / exp_avg_sq with numel > 0");
         if ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 3) != 0)
-            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: float32 tensors must be 4-byte aligned");
-        if ((x.numel + LG_ADAM_SPAN - 1) / LG_ADAM_SPAN > 0x7FFFFFFFll)
-            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step: tensor beyond 2^31 - 1 spans");
+            return refuse(who, "float32 tensors must be 4-byte aligned");
+        if ((x.numel + LG_ADAM_SPAN - 1) / LG_ADAM_SPAN > 0x7FFFFFFFll) return refuse(who, "tensor beyond 2^31 - 1 spans");
+        if (const char* what = adam_rows_fault(tensors[t])) return refuse(who, what);
     }
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false, prof = flags & LG_FLAG_PROFILE, decoupled = flags & LG_ADAM_DECOUPLED_WD;
-    LgAdamTable a;
+    const bool prof = flags & LG_FLAG_PROFILE, decoupled = flags & LG_ADAM_DECOUPLED_WD;
+    Table table;
+    LgAdamTable& a = adam_dense(table);
     int filled = 0;
     uint32_t wgs = 0;
     auto reset = [&]() {
-        memset(&a, 0, sizeof(a));
+        memset(&table, 0, sizeof(table));
         for (int k = 0; k < LG_ADAM_MAX_TENSORS; k++) a.first_wg[k] = 0xFFFFFFFFu;
+        adam_rows_reset(table);
         a.one_minus_beta1 = (float)(1.0 - beta1); a.beta2 = (float)beta2; a.one_minus_beta2 = (float)(1.0 - beta2); a.eps = (float)eps;
         filled = 0; wgs = 0;
     };
-    auto launch = [&]() -> int {
-        ProfScope ps(prof, "adam", stream);
-        if (decoupled) lg_adam_kernel<true><<<wgs, LG_ADAM_THREADS, 0, stream>>>(a);
-        else lg_adam_kernel<false><<<wgs, LG_ADAM_THREADS, 0, stream>>>(a);
-        KCHECK("lg_adam_kernel");
-        return LG_OK;
-    };
     reset();
     for (int t = 0; t < num_tensors; t++) {
-        const lg_adam_tensor& x = tensors[t];
+        const lg_adam_tensor& x = adam_dense(tensors[t]);
         if (x.numel == 0) continue;
         const uint32_t need = (uint32_t)((x.numel + LG_ADAM_SPAN - 1) / LG_ADAM_SPAN);
         if (filled == LG_ADAM_MAX_TENSORS || (filled > 0 && wgs + need > 0x7FFFFFFFu)) {
-            const int rc = launch();
+            const int rc = adam_launch(table, wgs, decoupled, prof, stream);
             if (rc != LG_OK) return rc;
             reset();
         }
@@ -1137,85 +1195,24 @@ extern "C" int lg_adam_step(int32_t num_tensors, const lg_adam_tensor* tensors, 
         a.bc2_sqrt[k] = (float)sqrt(1.0 - pow(beta2, (double)x.step));
         a.decay[k] = decoupled ? (float)(1.0 - x.lr * x.weight_decay) : (float)x.weight_decay;
         if ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 15) == 0) a.vec_mask |= 1u << k;
+        adam_rows_fill(table, k, tensors[t]);
         wgs += need;
     }
-    if (filled > 0) return launch();
+    if (filled > 0) return adam_launch(table, wgs, decoupled, prof, stream);
     return LG_OK;
 }
 
-// lg_adam_step with a byte mask of rows per entry (lg_adam_rows_kernel): the checks, the host-side constants and the split into
-// launches of lg_adam_step, plus the row geometry of the masked entries
+extern "C" int lg_adam_step(int32_t num_tensors, const lg_adam_tensor* tensors, double beta1, double beta2, double eps, uint32_t flags,
+                            void* stream_p)
+{
+    return adam_step<LgAdamTable>("lg_adam_step", num_tensors, tensors, beta1, beta2, eps, flags, stream_p);
+}
+
+// lg_adam_step with a byte mask of rows per entry (lg_adam_rows_kernel): the same step, plus the row geometry of the masked entries
 extern "C" int lg_adam_step_rows(int32_t num_tensors, const lg_adam_rows_tensor* tensors, double beta1, double beta2, double eps,
                                  uint32_t flags, void* stream_p)
 {
-    if (num_tensors < 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: num_tensors < 0");
-    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: betas must lie in [0, 1)");
-    if (num_tensors > 0 && !tensors) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: missing tensor table");
-    for (int t = 0; t < num_tensors; t++) {
-        const lg_adam_tensor& x = tensors[t].t;
-        if (x.numel < 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: numel < 0");
-        if (x.step < 1) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: step < 1 (the step being taken counts from 1)");
-        if (x.numel == 0) continue;                     // skipped: its pointers, its mask and its rows are not looked at
-        if (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq)
-            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: null param / grad / exp_avg / exp_avg_sq with numel > 0");
-        if ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 3) != 0)
-            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: float32 tensors must be 4-byte aligned");
-        if ((x.numel + LG_ADAM_SPAN - 1) / LG_ADAM_SPAN > 0x7FFFFFFFll)
-            return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: tensor beyond 2^31 - 1 spans");
-        if (!tensors[t].row_mask) continue;             // dense entry: rows is not looked at
-        const int64_t rows = tensors[t].rows;
-        if (rows < 1) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: rows < 1 with a row_mask");
-        if (x.numel % rows != 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: numel is not a multiple of rows");
-        if (x.numel / rows > (int64_t)LG_ADAM_MAX_ROW_LEN) return fail(LG_ERR_INVALID_ARGUMENT, "lg_adam_step_rows: a row beyond 2^31 - 1 elements");
-    }
-    hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false, prof = flags & LG_FLAG_PROFILE, decoupled = flags & LG_ADAM_DECOUPLED_WD;
-    LgAdamRowsTable r;
-    LgAdamTable& a = r.a;
-    int filled = 0;
-    uint32_t wgs = 0;
-    auto reset = [&]() {
-        memset(&r, 0, sizeof(r));
-        for (int k = 0; k < LG_ADAM_MAX_TENSORS; k++) { a.first_wg[k] = 0xFFFFFFFFu; r.row_len[k] = 1; }
-        a.one_minus_beta1 = (float)(1.0 - beta1); a.beta2 = (float)beta2; a.one_minus_beta2 = (float)(1.0 - beta2); a.eps = (float)eps;
-        filled = 0; wgs = 0;
-    };
-    auto launch = [&]() -> int {
-        ProfScope ps(prof, "adam_rows", stream);
-        if (decoupled) lg_adam_rows_kernel<true><<<wgs, LG_ADAM_THREADS, 0, stream>>>(r);
-        else lg_adam_rows_kernel<false><<<wgs, LG_ADAM_THREADS, 0, stream>>>(r);
-        KCHECK("lg_adam_rows_kernel");
-        return LG_OK;
-    };
-    reset();
-    for (int t = 0; t < num_tensors; t++) {
-        const lg_adam_tensor& x = tensors[t].t;
-        if (x.numel == 0) continue;
-        const uint32_t need = (uint32_t)((x.numel + LG_ADAM_SPAN - 1) / LG_ADAM_SPAN);
-        if (filled == LG_ADAM_MAX_TENSORS || (filled > 0 && wgs + need > 0x7FFFFFFFu)) {
-            const int rc = launch();
-            if (rc != LG_OK) return rc;
-            reset();
-        }
-        const int k = filled++;
-        a.param[k] = x.param; a.grad[k] = x.grad; a.exp_avg[k] = x.exp_avg; a.exp_avg_sq[k] = x.exp_avg_sq;
-        a.numel[k] = x.numel;
-        a.first_wg[k] = wgs;
-        // lg_adam_step's constants: the three scalars in double, each rounded once to float
-        a.step_size[k] = (float)(x.lr / (1.0 - pow(beta1, (double)x.step)));
-        a.bc2_sqrt[k] = (float)sqrt(1.0 - pow(beta2, (double)x.step));
-        a.decay[k] = decoupled ? (float)(1.0 - x.lr * x.weight_decay) : (float)x.weight_decay;
-        if ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 15) == 0) a.vec_mask |= 1u << k;
-        if (tensors[t].row_mask) {
-            r.row_mask[k] = tensors[t].row_mask;
-            r.row_len[k] = (uint32_t)(x.numel / tensors[t].rows);
-            r.row_rcp[k] = lg_adam_row_rcp(r.row_len[k]);
-            r.row_thr[k] = lg_adam_row_thr(r.row_len[k]);
-        }
-        wgs += need;
-    }
-    if (filled > 0) return launch();
-    return LG_OK;
+    return adam_step<LgAdamRowsTable>("lg_adam_step_rows", num_tensors, tensors, beta1, beta2, eps, flags, stream_p);
 }
 
 // ---- densification (lg_densify.h) ----
@@ -1244,10 +1241,10 @@ extern "C" int lg_densify_stats(int32_t N, const float* viewspace_grad, const ui
     if ((((uintptr_t)viewspace_grad | (uintptr_t)radii | (uintptr_t)max_radii2D | (uintptr_t)accum | (uintptr_t)denom) & 3) != 0)
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_stats: 32-bit tensors must be 4-byte aligned");
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    const bool prof = flags & LG_FLAG_PROFILE;
     ProfScope ps(prof, "densify_stats", stream);
     lg_densify_stats_kernel<<<(unsigned)((N + 255) / 256), 256, 0, stream>>>(N, viewspace_grad, update_filter, radii, max_radii2D, accum, denom);
-    KCHECK("lg_densify_stats_kernel");
+    KLAUNCHED("lg_densify_stats_kernel");
     return LG_OK;
 }
 
@@ -1265,18 +1262,18 @@ extern "C" int lg_densify_plan(int32_t N, const float* scaling, const float* opa
         ((uintptr_t)scratch & 15) != 0)
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_densify_plan: misaligned tensor (float32: 4 bytes, map: 8, scratch: 16)");
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    const bool prof = flags & LG_FLAG_PROFILE;
     ProfScope ps(prof, "densify_plan", stream);
     if (N == 0) { HIP_TRY(lg_zero_async(record, 32, stream)); return LG_OK; }
     const DensifyScratch d = carve_densify(scratch, N);
     const int nb = (N + LG_DENSIFY_ROWS - 1) / LG_DENSIFY_ROWS;
     const LgDensifyThresholds th = { thr_g, thr_d, thr_w, min_opacity, use_extent ? 1 : 0 };
     lg_densify_classify<<<nb, 256, 0, stream>>>(N, scaling, opacity, accum, denom, th, d.flags, d.blk_sum);
-    KCHECK("lg_densify_classify");
+    KLAUNCHED("lg_densify_classify");
     lg_densify_scan<<<1, 1024, 0, stream>>>(nb, d.blk_sum, d.blk_off, record);
-    KCHECK("lg_densify_scan");
+    KLAUNCHED("lg_densify_scan");
     lg_densify_map<<<nb, 256, 0, stream>>>(N, d.flags, d.blk_off, record, (uint2*)map);
-    KCHECK("lg_densify_map");
+    KLAUNCHED("lg_densify_map");
     return LG_OK;
 }
 
@@ -1308,12 +1305,10 @@ extern "C" int lg_densify_rows(int32_t N, int64_t N_out, const void* map, const 
         widest = std::max<size_t>(widest, (size_t)x.row_words);
     }
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    const bool prof = flags & LG_FLAG_PROFILE;
     ProfScope ps(prof, "densify_rows", stream);
-    const size_t blocks = std::min<size_t>(((size_t)N_out * widest + 1023) / 1024, 8192);
-    lg_densify_move<<<dim3((unsigned)std::max<size_t>(blocks, 1), (unsigned)num_tensors), 256, 0, stream>>>(N_out, (const uint2*)map, record, a, rotation,
-                                                                                                      scaling, noise, noise_rows);
-    KCHECK("lg_densify_move");
+    lg_densify_move<<<row_move_grid((size_t)N_out, widest, num_tensors), 256, 0, stream>>>(N_out, (const uint2*)map, record, a, rotation, scaling, noise, noise_rows);
+    KLAUNCHED("lg_densify_move");
     return LG_OK;
 }
 
@@ -1331,32 +1326,31 @@ extern "C" int lg_filter3d_update(int32_t N, const float* means3D, int32_t V, co
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_filter3d_update: 32-bit tensors must be 4-byte aligned");
     if (N == 0) return LG_OK;
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    const bool prof = flags & LG_FLAG_PROFILE;
     const unsigned wgs = (unsigned)std::min<int64_t>(((int64_t)N + LG_F3D_THREADS - 1) / LG_F3D_THREADS, LG_F3D_MAX_WGS);
     float* partial = (float*)scratch;
     {
         ProfScope ps(prof, "filter3d_update", stream);
         lg_filter3d_update_kernel<<<wgs, LG_F3D_THREADS, 0, stream>>>(N, means3D, V, cameras, filter3d, seen, partial);
-        KCHECK("lg_filter3d_update_kernel");
+        KLAUNCHED("lg_filter3d_update_kernel");
     }
     {
         ProfScope ps(prof, "filter3d_reduce", stream);
         lg_filter3d_fill_kernel<<<wgs, LG_F3D_THREADS, 0, stream>>>(N, (int)wgs, partial, filter3d);
-        KCHECK("lg_filter3d_fill_kernel");
+        KLAUNCHED("lg_filter3d_fill_kernel");
     }
     return LG_OK;
 }
 
 static int lg_filter3d_check(const char* who, int32_t N, std::initializer_list<const void*> ptrs, bool* vec)
 {
-    char msg[128];                      // (fail() copies it)
-    if (N < 0 || N >= LG_FILTER3D_MAX_ROWS) { snprintf(msg, sizeof(msg), "%s: N outside [0, 2^30)", who); return fail(LG_ERR_INVALID_ARGUMENT, msg); }
+    if (N < 0 || N >= LG_FILTER3D_MAX_ROWS) return refuse(who, "N outside [0, 2^30)");
     uintptr_t all = 0;
     for (const void* p : ptrs) {
-        if (!p) { snprintf(msg, sizeof(msg), "%s: null tensor", who); return fail(LG_ERR_INVALID_ARGUMENT, msg); }
+        if (!p) return refuse(who, "null tensor");
         all |= (uintptr_t)p;
     }
-    if (all & 3) { snprintf(msg, sizeof(msg), "%s: float32 tensors must be 4-byte aligned", who); return fail(LG_ERR_INVALID_ARGUMENT, msg); }
+    if (all & 3) return refuse(who, "float32 tensors must be 4-byte aligned");
     *vec = (all & 15) == 0;
     return LG_OK;
 }
@@ -1368,12 +1362,11 @@ extern "C" int lg_filter3d_apply(int32_t N, const float* scaling, const float* o
     const int rc = lg_filter3d_check("lg_filter3d_apply", N, { scaling, opacity, filter3d, out_scaling, out_opacity }, &vec);
     if (rc != LG_OK || N == 0) return rc;
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    const bool prof = flags & LG_FLAG_PROFILE;
     ProfScope ps(prof, "filter3d_apply", stream);
     const unsigned wgs = (unsigned)((((int64_t)N + 3) / 4 + LG_F3D_THREADS - 1) / LG_F3D_THREADS);
-    if (flags & LG_FILTER3D_RAW) lg_filter3d_apply_kernel<true><<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, out_scaling, out_opacity);
-    else lg_filter3d_apply_kernel<false><<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, out_scaling, out_opacity);
-    KCHECK("lg_filter3d_apply_kernel");
+    filter3d_apply_kernel(flags & LG_FILTER3D_RAW)<<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, out_scaling, out_opacity);
+    KLAUNCHED("lg_filter3d_apply_kernel");
     return LG_OK;
 }
 
@@ -1384,14 +1377,12 @@ extern "C" int lg_filter3d_apply_bwd(int32_t N, const float* scaling, const floa
     const int rc = lg_filter3d_check("lg_filter3d_apply_bwd", N, { scaling, opacity, filter3d, dL_dout_scaling, dL_dout_opacity, dL_dscaling, dL_dopacity }, &vec);
     if (rc != LG_OK || N == 0) return rc;
     hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = false, prof = flags & LG_FLAG_PROFILE;
+    const bool prof = flags & LG_FLAG_PROFILE;
     ProfScope ps(prof, "filter3d_apply_bwd", stream);
     const unsigned wgs = (unsigned)((((int64_t)N + 3) / 4 + LG_F3D_THREADS - 1) / LG_F3D_THREADS);
-    if (flags & LG_FILTER3D_RAW)
-        lg_filter3d_apply_bwd_kernel<true><<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, dL_dout_scaling, dL_dout_opacity, dL_dscaling, dL_dopacity);
-    else
-        lg_filter3d_apply_bwd_kernel<false><<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, dL_dout_scaling, dL_dout_opacity, dL_dscaling, dL_dopacity);
-    KCHECK("lg_filter3d_apply_bwd_kernel");
+    filter3d_apply_bwd_kernel(flags & LG_FILTER3D_RAW)<<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, dL_dout_scaling, dL_dout_opacity,
+                                                                                           dL_dscaling, dL_dopacity);
+    KLAUNCHED("lg_filter3d_apply_bwd_kernel");
     return LG_OK;
 }
 
@@ -1420,8 +1411,7 @@ extern "C" int lg_knn3_mean_dist2(int32_t P, const float* points, float* mean_di
         HIP_TRY(lg_sort_keys(kv.sort_temp, tb, kv.pairs_in, kv.pairs_out, (uint32_t)P, 32, 32 + key_bits, nullptr, false, stream));
         HIP_TRY(hipMemsetAsync(kv.cell_start, 0, (size_t)kv.cap * 4, stream));
         HIP_TRY(hipMemsetAsync(kv.cell_end, 0, (size_t)kv.cap * 4, stream));
-        lg_knn_ranges<<<nb, 256, 0, stream>>>(P, points, kv.pairs_out, kv.cell_start, kv.cell_end, kv.sorted,
-                                              (const uint32_t*)((char*)kv.sort_temp + lg_sort_layout((size_t)P).ticket_off) + 15, kv.box);
+        lg_knn_ranges<<<nb, 256, 0, stream>>>(P, points, kv.pairs_out, kv.cell_start, kv.cell_end, kv.sorted, lg_sort_error_word(kv.sort_temp, (size_t)P), kv.box);
         KCHECK("lg_knn_ranges");
         uint32_t* open_in = (level & 1) ? kv.open_a : kv.open_b;
         uint32_t* open_out = (level & 1) ? kv.open_b : kv.open_a;
@@ -1444,16 +1434,26 @@ extern "C" size_t lg_loss_state_bytes(int32_t C, int32_t H, int32_t W)
     return carve_loss(nullptr, C, H, W).total;
 }
 
+// what the two loss entry points check and derive: the state carved (the backward reads what the forward left there) and the grid of
+// one wave per (strip of 64 columns, LG_LOSS_TH rows, plane).  out: the buffer the call writes
+static int loss_args(int32_t C, int32_t H, int32_t W, const float* img, const float* gt, const void* state, const float* out, LossView* lv, dim3* grid)
+{
+    if (C <= 0 || H <= 0 || W <= 0 || C > 65535) return fail(LG_ERR_INVALID_ARGUMENT, "bad image shape");
+    if (!img || !gt || !state || !out) return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
+    *lv = carve_loss(const_cast<void*>(state), C, H, W);
+    *grid = dim3(lg_loss_strips(W), lg_loss_segs(H), C);
+    if (grid->y > 65535) return fail(LG_ERR_INVALID_ARGUMENT, "image too large");
+    return LG_OK;
+}
+
 extern "C" int lg_loss_forward(int32_t C, int32_t H, int32_t W, const float* img, const float* gt, void* state, float* out_l1_ssim,
                                uint32_t flags, void* stream_p)
 {
-    if (C <= 0 || H <= 0 || W <= 0 || C > 65535) return fail(LG_ERR_INVALID_ARGUMENT, "bad image shape");
-    if (!img || !gt || !state || !out_l1_ssim) return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
+    LossView lv; dim3 grid;
+    const int rc = loss_args(C, H, W, img, gt, state, out_l1_ssim, &lv, &grid);
+    if (rc != LG_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_p;
     const bool debug = flags & LG_FLAG_DEBUG, prof = flags & LG_FLAG_PROFILE;
-    LossView lv = carve_loss(state, C, H, W);
-    dim3 grid(lg_loss_strips(W), lg_loss_segs(H), C);      // one wave per (strip of 64 columns, LG_LOSS_TH rows, plane)
-    if (grid.y > 65535) return fail(LG_ERR_INVALID_ARGUMENT, "image too large");
     if (flags & LG_FLAG_L1_ONLY) {
         ProfScope ps(prof, "l1_fwd", stream);
         const size_t n = (size_t)C * H * W;
@@ -1478,13 +1478,11 @@ extern "C" int lg_loss_backward(int32_t C, int32_t H, int32_t W, const float* im
                                 const float* dL_dl1, float scale_l1, const float* dL_dssim, float scale_ssim, float* dL_dimg,
                                 uint32_t flags, void* stream_p)
 {
-    if (C <= 0 || H <= 0 || W <= 0 || C > 65535) return fail(LG_ERR_INVALID_ARGUMENT, "bad image shape");
-    if (!img || !gt || !state || !dL_dimg) return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
+    LossView lv; dim3 grid;
+    const int rc = loss_args(C, H, W, img, gt, state, dL_dimg, &lv, &grid);
+    if (rc != LG_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_p;
     const bool debug = flags & LG_FLAG_DEBUG, prof = flags & LG_FLAG_PROFILE;
-    LossView lv = carve_loss(const_cast<void*>(state), C, H, W);
-    dim3 grid(lg_loss_strips(W), lg_loss_segs(H), C);
-    if (grid.y > 65535) return fail(LG_ERR_INVALID_ARGUMENT, "image too large");
     if (flags & LG_FLAG_L1_ONLY) {
         ProfScope ps(prof, "l1_bwd", stream);
         const size_t n = (size_t)C * H * W;
@@ -1505,7 +1503,6 @@ extern "C" int lg_loss_backward(int32_t C, int32_t H, int32_t W, const float* im
 // feature blending over the lists of a forward (lg_features.h)
 static int features_args(const char* who, const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, int32_t C)
 {
-    char msg[160];
     const char* what = nullptr;
     const ViewFault vf = v ? check_view(v, N) : VIEW_OK;
     if (!v) what = "null view";
@@ -1517,23 +1514,17 @@ static int features_args(const char* who, const lg_view* v, int32_t N, const voi
     else if (!geom_p) what = "missing geom buffer";
     else if (N > 0 && R > 0 && !bin_p) what = "missing binning buffer";
     else if (vf == VIEW_TOO_LARGE) what = "image too large";
-    if (!what) return LG_OK;
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return fail(LG_ERR_INVALID_ARGUMENT, msg);
+    return what ? refuse(who, what) : LG_OK;
 }
-static LgFeatView features_view(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const ViewGeom& q)
+static LgFeatView features_view(const ViewState& s, int32_t N, int64_t R)
 {
     LgFeatView f;
-    const GeomView geo = carve_geom(const_cast<void*>(geom_p), N);
+    const ViewGeom& q = s.q; const GeomView& geo = s.geo;
     f.W = q.W; f.H = q.H; f.gx = q.gx; f.ntiles = q.ntiles; f.N = N;
-    f.live = (N > 0 && R > 0 && bin_p) ? 1 : 0;
+    f.live = (N > 0 && R > 0 && s.bin.ranges) ? 1 : 0;      // (ranges is the head of the binning buffer: NULL without one)
     f.cap = (uint32_t)R; f.gid_mask = q.gid_mask;
     f.rec = geo.rec; f.counters = geo.counters;
-    f.ranges = nullptr; f.entries = nullptr;
-    if (f.live) {
-        const BinView bin = carve_bin(const_cast<void*>(bin_p), R, q.W, q.H, q.S);
-        f.ranges = bin.ranges; f.entries = bin.entries;
-    }
+    f.ranges = f.live ? s.bin.ranges : nullptr; f.entries = f.live ? s.bin.entries : nullptr;
     return f;
 }
 using FeaturesFwdKernel = decltype(&lg_features_fwd<4, true>);
@@ -1566,8 +1557,9 @@ extern "C" int lg_blend_features(const lg_view* v, int32_t N, const void* geom_p
     if (!out || (N > 0 && !features)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_blend_features: missing features / out buffer");
     hipStream_t stream = (hipStream_t)stream_p;
     const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, exact = !(v->flags & LG_FLAG_FAST_EXP);
-    const ViewGeom q = view_geom(v, N);
-    const LgFeatView f = features_view(v, N, geom_p, bin_p, R, q);
+    const ViewState s = view_state(v, N, geom_p, nullptr, bin_p, R);
+    const ViewGeom& q = s.q;
+    const LgFeatView f = features_view(s, N, R);
     for (int c0 = 0, cg; c0 < C; c0 += cg) {
         cg = features_channel_group(C - c0);
         {
@@ -1585,9 +1577,9 @@ static int features_backward_run(const lg_view* v, int32_t N, const void* geom_p
 {
     hipStream_t stream = (hipStream_t)stream_p;
     const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, exact = !(v->flags & LG_FLAG_FAST_EXP);
-    const ViewGeom q = view_geom(v, N);
-    const LgFeatView f = features_view(v, N, geom_p, bin_p, R, q);
-    const GeomView geo = carve_geom(const_cast<void*>(geom_p), N);
+    const ViewState s = view_state(v, N, geom_p, nullptr, bin_p, R);
+    const ViewGeom& q = s.q; const GeomView& geo = s.geo;
+    const LgFeatView f = features_view(s, N, R);
     float* rows = (float*)scratch;        // [R][cw] partial rows of the current chunk of channels, every row written by lg_features_bwd
     const int chunk = lg_features_chunk(R, C);
     for (int cb = 0; cb < C; cb += chunk) {
@@ -1645,8 +1637,8 @@ extern "C" int lg_backward_features(const lg_view* v, const lg_gaussians* g, con
     if (g->N > 0 && !features && (dL_dout || dL_dfeatures)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_features: missing features");
     if (g->N > 0 && dL_dfeatures && !dL_dout) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_features: dL_dfeatures without dL_dout");
     const FeatGrad fg = { features, C, bg_features, dL_dout, dL_dalpha };
-    rc = backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales,
-                       dL_drotations, dL_dcov3D, dL_dshs_rest, scratch, stream_p, 1, nullptr, nullptr, &fg);
+    const GradOut d = { dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest };
+    rc = backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, d, scratch, stream_p, { 1, nullptr, nullptr, &fg, nullptr });
     if (rc != LG_OK || g->N == 0 || !dL_dfeatures) return rc;
     return features_backward_run(v, g->N, geom_p, bin_p, R, dL_dout, C, dL_dfeatures, (char*)scratch + lg_backward_scratch_bytes(g->N, R), stream_p);
 }
@@ -1667,8 +1659,8 @@ extern "C" int lg_debug_tile_lists(const lg_view* v, const void* bin_p, int64_t 
 {
     if (!v || !bin_p || !out_ranges || !out_entries || R < 0 || v->image_width <= 0 || v->image_height <= 0)
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_debug_tile_lists: missing buffer");
-    const ViewGeom q = view_geom(v, 0);
-    BinView bin = carve_bin(const_cast<void*>(bin_p), R, q.W, q.H, q.S);
+    const ViewState s = view_state(v, 0, nullptr, nullptr, bin_p, R);
+    const ViewGeom& q = s.q; const BinView& bin = s.bin;
     hipError_t e = hipMemcpyAsync(out_ranges, bin.ranges, (size_t)q.ntiles * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream_p);
     if (e == hipSuccess && R > 0) e = hipMemcpyAsync(out_entries, bin.entries, (size_t)R * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream_p);
     if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_debug_tile_lists copy", e);
@@ -1678,8 +1670,7 @@ extern "C" int lg_debug_tile_lists(const lg_view* v, const void* bin_p, int64_t 
 extern "C" int lg_debug_view_meta(const lg_view* v, const void* bin_p, int64_t R, uint32_t* out_meta16, void* stream_p)
 {
     if (!v || !bin_p || !out_meta16 || R < 0 || v->image_width <= 0 || v->image_height <= 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_debug_view_meta: missing buffer");
-    const ViewGeom q = view_geom(v, 0);
-    BinView bin = carve_bin(const_cast<void*>(bin_p), R, q.W, q.H, q.S);
+    const BinView bin = view_state(v, 0, nullptr, nullptr, bin_p, R).bin;
     hipError_t e = hipMemcpyAsync(out_meta16, bin.meta, 64, hipMemcpyDeviceToDevice, (hipStream_t)stream_p);
     if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_debug_view_meta copy", e);
     return LG_OK;
@@ -1690,16 +1681,13 @@ extern "C" int lg_debug_last_contributor(const lg_view* v, int32_t N, const void
 {
     if (!v || N <= 0 || !geom_p || !bin_p || !img_p || !out_ids || v->image_width <= 0 || v->image_height <= 0)
         return fail(LG_ERR_INVALID_ARGUMENT, "lg_debug_last_contributor: missing buffer");
-    const ViewGeom q = view_geom(v, N);
+    const ViewState s = view_state(v, N, geom_p, img_p, bin_p, R);
+    const ViewGeom& q = s.q; const GeomView& geo = s.geo; const ImgView& img = s.img; const BinView& bin = s.bin;
     const int W = q.W, H = q.H;
-    GeomView geo = carve_geom(const_cast<void*>(geom_p), N);
-    ImgView img = carve_img(const_cast<void*>(img_p), W, H);
-    BinView bin = carve_bin(const_cast<void*>(bin_p), R, W, H, q.S);
     const size_t P = (size_t)W * H;
     lg_debug_last_contributor_kernel<<<(unsigned)((P + 255) / 256), 256, 0, (hipStream_t)stream_p>>>(W, H, q.gx, bin.ranges, bin.entries, q.gid_mask, img.n_contrib,
                                                                                                   geo.counters, out_ids);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_debug_last_contributor launch", e);
+    KLAUNCHED("lg_debug_last_contributor");
     return LG_OK;
 }
 
@@ -1715,7 +1703,7 @@ extern "C" int lg_debug_sort_keys(int64_t n, const uint64_t* keys_in, uint64_t* 
     size_t tb = L.total;
     HIP_TRY(lg_sort_keys(temp, tb, keys_in, keys_out, (uint32_t)n, begin_bit, end_bit, nullptr, false, (hipStream_t)stream_p));
     uint32_t h_err = 0;
-    HIP_TRY(hipMemcpyAsync(&h_err, (char*)temp + L.ticket_off + 15 * 4, 4, hipMemcpyDeviceToHost, (hipStream_t)stream_p));
+    HIP_TRY(hipMemcpyAsync(&h_err, lg_sort_error_word(temp, (size_t)n), 4, hipMemcpyDeviceToHost, (hipStream_t)stream_p));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream_p));
     if (h_err & LG_ABORT_SORT) return fail(LG_ERR_DEVICE, "radix sort look-back gave up (a predecessor tile never published)");
     return LG_OK;
@@ -1735,13 +1723,13 @@ extern "C" int lg_debug_sort_orphan(int64_t n, const uint64_t* keys_in, uint64_t
     const uint32_t one = 1u;
     HIP_TRY(hipMemcpyAsync(base + L.ticket_off, &one, 4, hipMemcpyHostToDevice, stream));
     uint32_t* tickets = (uint32_t*)(base + L.ticket_off);
+    uint32_t* err = lg_sort_error_word(temp, (size_t)2 * LG_SORT_TILE);
     // n_arg = one tile beyond the orphan so that tile 1 is inside the key range; it sorts keys_in[0..n) as its own keys
     lg_onesweep_pass<<<1, LG_SORT_BLOCK, 0, stream>>>(keys_in - LG_SORT_TILE, keys_out - LG_SORT_TILE, nullptr, (uint32_t)(LG_SORT_TILE + n), 0, 8,
-                                                       (uint32_t*)(base + L.hist_off), tickets, (uint32_t*)(base + L.state_off), tickets + 15, 64u, nullptr, 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_onesweep_pass launch", e);
+                                                       (uint32_t*)(base + L.hist_off), tickets, (uint32_t*)(base + L.state_off), err, 64u, nullptr, 0);
+    KLAUNCHED("lg_onesweep_pass");
     uint32_t h_err = 0;
-    HIP_TRY(hipMemcpyAsync(&h_err, tickets + 15, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (h_err & LG_ABORT_SORT) return fail(LG_ERR_DEVICE, "radix sort look-back gave up (a predecessor tile never published)");
     return LG_OK;
@@ -1786,16 +1774,14 @@ extern "C" int lg_debug_activations(int32_t n, const float* s, const float* r, c
 {
     if (n <= 0) return LG_OK;
     lg_debug_activations_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream_p>>>(n, s, r, o, out_s, out_r, out_o);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_debug_activations launch", e);
+    KLAUNCHED("lg_debug_activations");
     return LG_OK;
 }
 
 extern "C" int lg_debug_reduce9(const float* in_64x9, float* out_9, void* stream_p)
 {
     lg_debug_reduce9_kernel<<<1, 64, 0, (hipStream_t)stream_p>>>(in_64x9, out_9);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(LG_ERR_DEVICE, "lg_debug_reduce9 launch", e);
+    KLAUNCHED("lg_debug_reduce9");
     return LG_OK;
 }
 

@@ -31,6 +31,13 @@ static int fail(int code, const char* what, hipError_t e = hipSuccess)
     g_err = buf;
     return code;
 }
+// a refusal worded "<entry point>: <what>", for the checks that several entry points share
+static int refuse(const char* who, const char* what)
+{
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return fail(LG_ERR_INVALID_ARGUMENT, msg);
+}
 #define HIP_TRY(expr)                                                     \
     do {                                                                  \
         hipError_t _e = (expr);                                           \

@@ -71,6 +71,8 @@ static inline size_t lg_sort_clear_bytes(const LgSortLayout& L, unsigned passes)
 {
     return L.state_off + (size_t)passes * L.tiles * 256 * 4;
 }
+// the sort's own error word: word 15 of the ticket block of the temp storage of a sort of n keys (lg_sort_keys without counters)
+static inline uint32_t* lg_sort_error_word(void* temp, size_t n) { return (uint32_t*)((char*)temp + lg_sort_layout(n).ticket_off) + 15; }
 
 // Stand-alone digit histograms of all passes (callers that do not produce the keys themselves; the rasterizer's K3 does).
 __global__ void __launch_bounds__(256)
@@ -294,6 +296,7 @@ static hipError_t lg_sort_keys(void* temp, size_t& temp_bytes, const uint64_t* k
     uint32_t* tickets = (uint32_t*)(base + L.ticket_off);
     uint32_t* states = (uint32_t*)(base + L.state_off);
     uint64_t* keys_tmp = (uint64_t*)(base + L.keys_tmp_off);
+    uint32_t* err = counters ? counters : lg_sort_error_word(temp, n);
     hipError_t e;
     if (!hist_ready) {
         if ((e = lg_zero_async(base, lg_sort_clear_bytes(L, passes), stream)) != hipSuccess) return e;
@@ -306,7 +309,7 @@ static hipError_t lg_sort_keys(void* temp, size_t& temp_bytes, const uint64_t* k
         const int bit = begin_bit + 8 * p, nb = std::min(8, end_bit - bit);
         uint64_t* dst = to_output ? keys_out : keys_tmp;
         lg_onesweep_pass<<<L.tiles, LG_SORT_BLOCK, 0, stream>>>(src, dst, counters, n, bit, nb, hist + (size_t)p * 256, tickets + p,
-                                                                 states + (size_t)p * L.tiles * 256, counters ? counters : tickets + 15,
+                                                                 states + (size_t)p * L.tiles * 256, err,
                                                                  poll_budget, p == passes - 1 ? ranges : nullptr, range_shift);
         src = dst;
         to_output = !to_output;
