@@ -16,67 +16,28 @@ Scenes (the smallest that reach each path of K7's ABS variants and of lg_absgrad
                                                    gather; gimg on 3 pixels of every tile (147)"""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import torch
 
-import antialias_common as aa
 import camera_grad_common as cg
 import common
-from common import syn
-from oracle import torch_dense
+import dense_twin
+import tolerance
+from common import ptr, syn  # noqa: F401  (the tests of this feature take ptr from here)
+from tolerance import TOL, rel_err  # noqa: F401
 
-TOL = cg.TOL
-rel_err = cg.rel_err
 SCENES = ("a", "b", "c", "d")
-
-_HARNESS = None
 
 
 def harness():
-    global _HARNESS
-    if _HARNESS is not None:
-        return _HARNESS
-    d = os.path.join(common.ROOT, "tests", "cpu_harness")
-    so = os.path.join(d, "liblg_absgrad_harness.so")
-    srcs = [os.path.join(d, "lg_absgrad_harness.cpp"), os.path.join(common.ROOT, "lightgaussian_amd", "csrc", "lg_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-                               srcs[0], "-o", so])
-    lib = C.CDLL(so)
     P, F, I = C.c_void_p, C.c_float, C.c_int
-    lib.h_abs_pair.restype = None
-    lib.h_abs_pair.argtypes = [I] + [P] * 7
-    lib.h_abs_pair_sum.restype = None
-    lib.h_abs_pair_sum.argtypes = [I, P, P, P, F, F, F, P]
-    lib.h_abs_rows_to_grad.restype = None
-    lib.h_abs_rows_to_grad.argtypes = [I, P, P, P, I, I, P]
-    lib.h_pair_signed.restype = None
-    lib.h_pair_signed.argtypes = [I] + [P] * 8
-    _HARNESS = lib
-    return lib
-
-
-def ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return common.build_harness("absgrad", headers=(common.LG_MATH_H,), flags=common.STRICT_FP_FMA, signatures={
+        "h_abs_pair": (None, [I] + [P] * 7), "h_abs_pair_sum": (None, [I, P, P, P, F, F, F, P]),
+        "h_abs_rows_to_grad": (None, [I, P, P, P, I, I, P]), "h_pair_signed": (None, [I] + [P] * 8)})
 
 
 # ---- scenes ------------------------------------------------------------------------------------------------------------------------
-def _append(g, cam, extra):
-    """g with Gaussians appended that are placed in VIEW space, as antialias_common.small_scene does: (view position, log-scales, logit)."""
-    inv = torch.linalg.inv(cam.world_view_transform.double())
-    n = len(extra)
-    xyz = torch.stack([(torch.tensor(tuple(pos) + (1.0,), dtype=torch.float64) @ inv)[:3].float() for pos, _ls, _lo in extra])
-    sc = torch.tensor([ls for _p, ls, _lo in extra], dtype=torch.float32)
-    op = torch.tensor([[lo] for _p, _ls, lo in extra], dtype=torch.float32)
-    cat = lambda a, b: torch.cat([a.detach(), b.to(a.dtype)], 0)  # noqa: E731
-    return syn.SyntheticGaussians(cat(g._xyz, xyz), cat(g._features_dc, g._features_dc[:n]), cat(g._features_rest, g._features_rest[:n]),
-                                  cat(g._scaling, sc), cat(g._rotation, torch.randn(n, 4, generator=torch.Generator().manual_seed(5))),
-                                  cat(g._opacity, op), g.max_sh_degree, g.active_sh_degree)
-
-
 _SCENE = {}
 
 
@@ -91,8 +52,8 @@ def scene(name):
     elif name == "b":
         g, cam, W, H = cg.small_scene("N300_70x45")
         tanx = math.tan(cam.FoVx * 0.5)
-        g = _append(g, cam, (((0.1, 0.1, -3.0), (math.log(0.05),) * 3, 2.0),                    # behind the camera
-                             ((3.0 * tanx * 4.0, 0.0, 4.0), (math.log(0.02),) * 3, 2.0)))       # off screen: three half-widths to the right
+        g = common.append_view_space(g, cam, (((0.1, 0.1, -3.0), (math.log(0.05),) * 3, 2.0),           # behind the camera
+                                              ((3.0 * tanx * 4.0, 0.0, 4.0), (math.log(0.02),) * 3, 2.0)))  # off screen: three half-widths to the right
         mask = (torch.arange(H * W) % 5 == 0).reshape(H, W)
     elif name == "c":
         W = H = 16
@@ -105,7 +66,7 @@ def scene(name):
         W = H = 112
         g = syn.make_gaussians(23, seed=13, extent=(1.5, 1.5, 1.0), log_scale_mean=math.log(0.08), opacity_mean=0.0)
         cam = syn.look_at_camera((0.0, 0.0, -4.0), (0.0, 0.0, 0.0), W, H)
-        g = _append(g, cam, (((0.0, 0.0, 4.5), (math.log(2.0),) * 3, 0.0),))                    # sigma ~ 43 pixels: every tile of the image
+        g = common.append_view_space(g, cam, (((0.0, 0.0, 4.5), (math.log(2.0),) * 3, 0.0),))     # sigma ~ 43 pixels: every tile of the image
         gen = torch.Generator().manual_seed(17)
         mask = torch.zeros(H, W, dtype=torch.bool)
         for ty in range(7):
@@ -126,7 +87,6 @@ def scene_kwargs(name):
 
 
 # ---- the dense twin ----------------------------------------------------------------------------------------------------------------
-_PER_GAUSSIAN = ("means3D", "opacities", "shs", "scales", "rotations")
 _REF = {}
 
 
@@ -138,75 +98,36 @@ def abs_reference(name, antialias=False):
     if key in _REF:
         return _REF[key]
     kw, _opts, gimg = scene_kwargs(name)
-    N = kw["means3D"].shape[0]
-    vm32 = kw["viewmatrix"].float()
-    keep = (kw["means3D"].float() @ vm32[:3, 2] + vm32[3, 2]) > 0.19       # cg.dense_render's superset of what the near plane lets through
     pix = torch.nonzero(gimg.abs().sum(0).reshape(-1) > 0).reshape(-1).tolist()
     out = {}
-    for dd in (torch.float64, torch.float32):
-        with torch.no_grad():
-            k2 = aa.twin_kwargs(kw, aa.twin_leaves(kw, dd, grad=False), dd, antialias=antialias)
-        t = {k: k2[k][keep].to(dd) for k in _PER_GAUSSIAN}
-        m2 = torch.zeros(int(keep.sum()), 3, dtype=dd, requires_grad=True)
-        color, _radii, _cnt = torch_dense.render_dense(means2D=m2, W=kw["W"], H=kw["H"], tanfovx=kw["tanfovx"], tanfovy=kw["tanfovy"],
-                                                       bg=kw["bg"].to(dd), viewmatrix=kw["viewmatrix"].to(dd), projmatrix=kw["projmatrix"].to(dd),
-                                                       campos=kw["campos"].to(dd), sh_degree=kw["sh_degree"], **t)
-        s = (color * gimg.to(dd)).sum(0).reshape(-1)
-        a = torch.zeros(m2.shape[0], 2, dtype=torch.float64)
-        sg = torch.zeros(m2.shape[0], 2, dtype=torch.float64)
+    for dd, dname in dense_twin.DTYPES:
+        m2 = torch.zeros(kw["means3D"].shape[0], 3, dtype=dd, requires_grad=True)
+        s = (dense_twin.render(kw, dd, means2D=m2, antialias=antialias)[0] * gimg.to(dd)).sum(0).reshape(-1)
+        a, sg = torch.zeros(m2.shape[0], 2, dtype=torch.float64), torch.zeros(m2.shape[0], 2, dtype=torch.float64)
         for p in pix:
             gp, = torch.autograd.grad(s[p], m2, retain_graph=True)
             a += gp[:, :2].abs().double()
             sg += gp[:, :2].double()
-        full_a, full_s = np.zeros((N, 2)), np.zeros((N, 2))
-        full_a[keep.numpy()] = a.numpy()
-        full_s[keep.numpy()] = sg.numpy()
-        out["float64" if dd == torch.float64 else "float32"] = {"absgrad": full_a, "grad": full_s}
+        out[dname] = {"absgrad": a.numpy(), "grad": sg.numpy()}
     _REF[key] = out
     return out
 
 
 def assert_rule(got, ref, what=""):
-    """got [N,3] (or [N,2]) against ref = abs_reference(...); the figures are printed before they are asserted."""
-    r64, r32 = ref["float64"]["absgrad"], ref["float32"]["absgrad"]
-    g = np.asarray(got, np.float64)[:, :2]
-    floor, err = rel_err(r32, r64), rel_err(g, r64)
-    print(f"{what} absgrad: rel_err {err:.3e} (float32 twin {floor:.3e}, max |d64| {np.abs(r64).max():.3e})")
-    assert np.isfinite(g).all(), f"{what}: not finite"
-    assert np.abs(r64).max() > 0, f"{what}: the reference is zero"
-    assert err <= max(TOL, 3.0 * floor), f"{what} absgrad: rel err {err:.3e} (float32 twin floor {floor:.3e})"
+    """got [N,3] (or [N,2]) against ref = abs_reference(...)."""
+    tolerance.assert_rule3(np.asarray(got)[:, :2], ref["float64"]["absgrad"], ref["float32"]["absgrad"], f"{what} absgrad")
 
 
 # ---- GPU runs (tests/test_gpu_absgrad.py, tools) ------------------------------------------------------------------------------------
 DEV = "cuda:0"
-PER_GAUSSIAN = ("means3D", "opacities", "shs", "scales", "rotations")
 RAW = ("_xyz", "_opacity", "_scaling", "_rotation", "_features_dc", "_features_rest")
 
 
 def run_activated(name, options, camera_grad=False, backwards=1):
-    """Forward + `backwards` backward passes of the scene's loss through GaussianRasterizer (activated inputs).  Returns a dict: image,
-    radii, grads {name: tensor} (means2D among them), camera {name: array} or None, means2D (the leaf: .absgrad is read from it)."""
-    from lightgaussian_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+    """gpu_common.run_rasterizer on the scene, its own rasterizer options underneath `options`."""
+    import gpu_common
     kw, opts, gimg = scene_kwargs(name)
-    dev = torch.device(DEV)
-    t = {k: (v.detach().to(dev).clone() if torch.is_tensor(v) else v) for k, v in kw.items()}
-    for n in PER_GAUSSIAN:
-        t[n].requires_grad_(True)
-    cam = {n: t[n].requires_grad_(camera_grad) for n in cg.NAMES}
-    rs = GaussianRasterizationSettings(image_height=t["H"], image_width=t["W"], tanfovx=t["tanfovx"], tanfovy=t["tanfovy"], bg=t["bg"],
-                                       scale_modifier=1.0, viewmatrix=cam["viewmatrix"], projmatrix=cam["projmatrix"], sh_degree=t["sh_degree"],
-                                       campos=cam["campos"], prefiltered=False, debug=False, f_count=False)
-    means2D = torch.zeros((t["means3D"].shape[0], 3), device=dev, requires_grad=True)
-    color, radii = GaussianRasterizer(rs, options=dict(opts, **options, camera_grad=camera_grad))(
-        means3D=t["means3D"], means2D=means2D, opacities=t["opacities"], shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
-    loss = (color * gimg.to(dev)).sum()
-    for k in range(backwards):
-        loss.backward(retain_graph=k + 1 < backwards)
-    torch.cuda.synchronize()
-    grads = {n: t[n].grad for n in PER_GAUSSIAN}
-    grads["means2D"] = means2D.grad
-    camera = {n: cam[n].grad.detach().cpu().numpy().copy() for n in cg.NAMES} if camera_grad else None
-    return dict(image=color.detach(), radii=radii, grads=grads, camera=camera, means2D=means2D)
+    return gpu_common.run_rasterizer(kw, gimg, dict(opts, **options), camera_grad=camera_grad, backwards=backwards)
 
 
 def gpu_model(name):

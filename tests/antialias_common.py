@@ -9,56 +9,28 @@ Scenes and the tolerance rule are tests/camera_grad_common.py's, unchanged: per 
 "N300_70x45" gets six hand-placed Gaussians appended (EXTRA below); every reference is computed once per key and shared."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import torch
 
 import camera_grad_common as cg
 import common
-from common import syn
-from oracle import torch_dense
+import dense_twin
+import tolerance
+from common import f32, ptr  # noqa: F401  (the tests of this feature take them from here)
+from tolerance import TOL, rel_err  # noqa: F401
 
 FLOOR = 0.000025
-TOL = cg.TOL
-rel_err = cg.rel_err
-
-_HARNESS = None
 
 
 def harness():
-    global _HARNESS
-    if _HARNESS is not None:
-        return _HARNESS
-    d = os.path.join(common.ROOT, "tests", "cpu_harness")
-    so = os.path.join(d, "liblg_antialias_harness.so")
-    srcs = [os.path.join(d, "lg_antialias_harness.cpp"), os.path.join(common.ROOT, "lightgaussian_amd", "csrc", "lg_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-                               srcs[0], "-o", so])
-    lib = C.CDLL(so)
     P, F, I = C.c_void_p, C.c_float, C.c_int
-    lib.h_aa_rho.restype = None
-    lib.h_aa_rho.argtypes = [I, P, P, P, P]
-    lib.h_aa_rho_scene.restype = None
-    lib.h_aa_rho_scene.argtypes = [I, I, I, I, P, P, P, P, P, F, F, P]
-    lib.h_aa_project.restype = None
-    lib.h_aa_project.argtypes = [I, I, I, I, P, P, P, P, P, P, F, F, P]
-    lib.h_aa_backward.restype = None
-    lib.h_aa_backward.argtypes = [I, I, I, I, I] + [P] * 8 + [F, F] + [P] * 6
-    lib.h_aa_camera_terms.restype = None
-    lib.h_aa_camera_terms.argtypes = [I, I, I, I] + [P] * 7 + [F, F, P]
-    _HARNESS = lib
-    return lib
-
-
-def f32(t):
-    return None if t is None else np.ascontiguousarray(t.detach().numpy() if torch.is_tensor(t) else t, np.float32)
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return common.build_harness("antialias", headers=(common.LG_MATH_H,), flags=common.STRICT_FP_FMA, signatures={
+        "h_aa_rho": (None, [I, P, P, P, P]),
+        "h_aa_rho_scene": (None, [I, I, I, I, P, P, P, P, P, F, F, P]),
+        "h_aa_project": (None, [I, I, I, I, P, P, P, P, P, P, F, F, P]),
+        "h_aa_backward": (None, [I, I, I, I, I] + [P] * 8 + [F, F] + [P] * 6),
+        "h_aa_camera_terms": (None, [I, I, I, I] + [P] * 7 + [F, F, P])})
 
 
 # ---- scenes ----------------------------------------------------------------------------------------------------------------
@@ -84,22 +56,8 @@ def small_scene(name):
     g, cam, W, H = cg.small_scene(name)
     if name != "N300_70x45":
         return g, cam, W, H
-    vm = cam.world_view_transform.double()
-    inv = torch.linalg.inv(vm)
-    tanx = math.tan(cam.FoVx * 0.5)
-    xyz, sc, op = [], [], []
-    for pos, ls, logit in _EXTRA:
-        if pos is None:
-            pos = (1.45 * tanx * 4.0, 0.0, 4.0)
-        xyz.append((torch.tensor(pos + (1.0,), dtype=torch.float64) @ inv)[:3].float())
-        sc.append(torch.tensor(ls)); op.append(torch.tensor([logit]))
-    n = len(_EXTRA)
-    gen = torch.Generator().manual_seed(5)
-    cat = lambda a, b: torch.cat([a.detach(), b.to(a.dtype)], 0)  # noqa: E731
-    g2 = syn.SyntheticGaussians(cat(g._xyz, torch.stack(xyz)), cat(g._features_dc, g._features_dc[:n]), cat(g._features_rest, g._features_rest[:n]),
-                                cat(g._scaling, torch.stack(sc)), cat(g._rotation, torch.randn(n, 4, generator=gen)),
-                                cat(g._opacity, torch.stack(op)), g.max_sh_degree, g.active_sh_degree)
-    return g2, cam, W, H
+    far_off_axis = (1.45 * math.tan(cam.FoVx * 0.5) * 4.0, 0.0, 4.0)
+    return common.append_view_space(g, cam, [(pos or far_off_axis, ls, logit) for pos, ls, logit in _EXTRA]), cam, W, H
 
 
 def combo_kwargs(name, combo):
@@ -162,71 +120,29 @@ def rho32_harness(kw, raw=False):
 
 
 # ---- the dense twin --------------------------------------------------------------------------------------------------------
-_GEOM = ("means3D", "opacities", "shs", "colors_precomp", "scales", "rotations", "cov3D_precomp")
-
-
-def twin_leaves(kw, dd, grad=True):
-    return {k: kw[k].to(dd).detach().clone().requires_grad_(grad) for k in _GEOM if k in kw}
-
-
-def twin_kwargs(kw, leaves, dd, camera=None, antialias=True):
-    """kw with the leaves in place of its per-Gaussian tensors and opacities = sigma rho (rho from the leaves and the camera)."""
-    vm = camera[0] if camera is not None else kw["viewmatrix"].to(dd)
-    out = dict(kw)
-    out.update(leaves)
-    if antialias:
-        out["opacities"] = leaves["opacities"] * rho_torch(leaves, vm, kw["W"], kw["H"], kw["tanfovx"], kw["tanfovy"])[:, None]
-    return out
+def compensated_opacities(t, vm, kw):
+    """sigma rho of the per-Gaussian tensors t (one dtype) under the view matrix vm: what dense_twin.render(antialias=True) renders."""
+    return t["opacities"] * rho_torch(t, vm, kw["W"], kw["H"], kw["tanfovx"], kw["tanfovy"])[:, None]
 
 
 def dense_image(kw, dd, antialias=True):
-    """(image [3,H,W], count [N] over the Gaussians cg.dense_render keeps, rho [N]) of the twin in dtype dd, no gradients."""
+    """(image [3,H,W], count [N], rho [N]) of the twin in dtype dd, no gradients."""
     with torch.no_grad():
-        leaves = twin_leaves(kw, dd, grad=False)
-        k2 = twin_kwargs(kw, leaves, dd, antialias=antialias)
-        vm32 = kw["viewmatrix"].float()
-        keep = (kw["means3D"].float() @ vm32[:3, 2] + vm32[3, 2]) > 0.19
-        t = {k: k2[k][keep] for k in _GEOM if k in k2}
-        color, _radii, cnt = torch_dense.render_dense(means2D=torch.zeros(int(keep.sum()), 3, dtype=dd), W=kw["W"], H=kw["H"], tanfovx=kw["tanfovx"],
-                                                      tanfovy=kw["tanfovy"], bg=kw["bg"].to(dd), viewmatrix=kw["viewmatrix"].to(dd),
-                                                      projmatrix=kw["projmatrix"].to(dd), campos=kw["campos"].to(dd), sh_degree=kw["sh_degree"], **t)
-        count = torch.zeros(kw["means3D"].shape[0], dtype=torch.int64)
-        count[keep] = cnt
-        rho = rho_torch(leaves, kw["viewmatrix"].to(dd), kw["W"], kw["H"], kw["tanfovx"], kw["tanfovy"])
+        color, _radii, count = dense_twin.render(kw, dd, antialias=antialias)
+        rho = rho_torch(dense_twin.leaves(kw, dd, grad=False), kw["viewmatrix"].to(dd), kw["W"], kw["H"], kw["tanfovx"], kw["tanfovy"])
     return color, count, rho
-
-
-_REF = {}
 
 
 def dense_reference(key, kw, gimg, camera=False):
     """{"float64": {tensor name: gradient}, "float32": {...}} of sum(image * gimg) by the antialiased twin, with respect to the
     per-Gaussian inputs of kw (and, camera=True, to viewmatrix / projmatrix / campos).  Computed once per key."""
-    if key in _REF:
-        return _REF[key]
-    out = {}
-    for dd in (torch.float64, torch.float32):
-        leaves = twin_leaves(kw, dd)
-        cam = tuple(kw[n].to(dd).detach().clone().requires_grad_() for n in cg.NAMES) if camera else None
-        (cg.dense_render(twin_kwargs(kw, leaves, dd, cam), dd, cam) * gimg.to(dd)).sum().backward()
-        g = {k: v.grad.numpy().astype(np.float64) for k, v in leaves.items()}
-        if camera:
-            g.update({n: (np.zeros(tuple(c.shape)) if c.grad is None else c.grad.numpy().astype(np.float64)) for n, c in zip(cg.NAMES, cam)})
-        out["float64" if dd == torch.float64 else "float32"] = g
-    _REF[key] = out
-    return out
+    return dense_twin.gradients(key, kw, gimg, camera=camera, antialias=True)
 
 
 def assert_rule(got, ref, names, what=""):
-    """The rule of camera_grad_common, per tensor; every figure is printed before it is asserted."""
+    """Rule 3 per tensor."""
     for n in names:
-        r64, r32 = ref["float64"][n], ref["float32"][n]
-        g = np.asarray(got[n], np.float64).reshape(r64.shape)
-        floor, err = rel_err(r32, r64), rel_err(g, r64)
-        print(f"{what} d/d{n}: rel_err {err:.3e} (float32 twin {floor:.3e}, max |d64| {np.abs(r64).max():.3e})")
-        assert np.isfinite(g).all(), f"{what} {n}: not finite"
-        assert np.abs(r64).max() > 0, f"{what} {n}: the reference is zero"
-        assert err <= max(TOL, 3.0 * floor), f"{what} d/d{n}: rel err {err:.3e} (float32 twin floor {floor:.3e})"
+        tolerance.assert_rule3(got[n], ref["float64"][n], ref["float32"][n], f"{what} d/d{n}")
 
 
 _CHECKED = []

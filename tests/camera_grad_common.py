@@ -5,44 +5,28 @@ Reference: oracle/torch_dense.py::render_dense differentiated with respect to vi
 plain torch ops), in float64 (d64) and in float32 (d32), with the same image gradient.  Rule 3 of the project, per output tensor in
 the max norm:   rel_err(g, d64) <= max(1e-4, 3 rel_err(d32, d64)).
 
-The twin is O(pixels x Gaussians): it is handed only the Gaussians in front of z_view = 0.19 (a superset of what the 0.2 near plane
-lets through, by the float32 view transform; the others take no part in the image or in any gradient), and every reference is
-computed once per key and shared."""
+The rule itself is tests/tolerance.py's, the twin's call and its keep mask tests/dense_twin.py's; every reference is computed once per
+key and shared."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import torch
 
 import common
+import dense_twin
+import tolerance
 from common import syn
-from oracle import torch_dense
+from tolerance import TOL, rel_err  # noqa: F401  (the modules built on this one take them from here)
 
-TOL = 1e-4
 BG = (0.1, 0.2, 0.3)
-NAMES = ("viewmatrix", "projmatrix", "campos")
-
-_HARNESS = None
+NAMES = dense_twin.CAMERA
 
 
 def harness():
-    global _HARNESS
-    if _HARNESS is not None:
-        return _HARNESS
-    d = os.path.join(common.ROOT, "tests", "cpu_harness")
-    so = os.path.join(d, "liblg_camera_harness.so")
-    srcs = [os.path.join(d, "lg_camera_harness.cpp"), os.path.join(common.ROOT, "lightgaussian_amd", "csrc", "lg_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-                               srcs[0], "-o", so])
-    lib = C.CDLL(so)
-    P, F = C.c_void_p, C.c_float
-    lib.h_camera_terms.restype = C.c_int
-    lib.h_camera_terms.argtypes = [C.c_int] * 4 + [P] * 9 + [F, F] + [P] * 3
-    _HARNESS = lib
-    return lib
+    P, F, I = C.c_void_p, C.c_float, C.c_int
+    return common.build_harness("camera", headers=(common.LG_MATH_H,), flags=common.STRICT_FP_FMA, signatures={
+        "h_camera_terms": (I, [I] * 4 + [P] * 9 + [F, F] + [P] * 3)})
 
 
 def unpack(sums27):
@@ -54,26 +38,11 @@ def unpack(sums27):
     return vm, pm, s[24:27].copy()
 
 
-def rel_err(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
-
-
 def assert_rule3(got, ref, what=""):
-    """got: {name: array}; ref: {"float64": {...}, "float32": {...}}.  Every figure is printed before it is asserted."""
+    """got: {name: array}; ref: {"float64": {...}, "float32": {...}}.  Rule 3 per camera tensor; with colours as inputs the camera centre
+    takes no part in the render (autograd hands the twin no gradient at all): exact zeros are asked for then."""
     for n in NAMES:
-        r64, r32 = ref["float64"][n], ref["float32"][n]
-        g = np.asarray(got[n], np.float64).reshape(r64.shape)
-        if n == "campos" and not r64.any() and not r32.any():
-            # colours as inputs: the camera centre takes no part in the render (autograd hands the twin no gradient at all)
-            print(f"{what} d/d{n}: the twin's gradient is identically zero")
-            assert not g.any(), f"{what} d/d{n}: must be exact zeros"
-            continue
-        floor, err = rel_err(r32, r64), rel_err(g, r64)
-        print(f"{what} d/d{n}: rel_err {err:.3e} (float32 twin {floor:.3e}, max |d64| {np.abs(r64).max():.3e})")
-        assert np.isfinite(g).all(), f"{what} {n}: not finite"
-        assert np.abs(r64).max() > 0, f"{what} {n}: the reference is zero"
-        assert err <= max(TOL, 3.0 * floor), f"{what} d/d{n}: rel err {err:.3e} (float32 twin floor {floor:.3e})"
+        tolerance.assert_rule3(got[n], ref["float64"][n], ref["float32"][n], f"{what} d/d{n}", zero_means_zero=(n == "campos"))
 
 
 def assert_unused_columns_zero(got, what=""):
@@ -102,7 +71,7 @@ def combo_kwargs(g, cam, W, H, combo, n=None):
     kw = common.scene_kwargs(g, cam, W, H, deg=1 if combo == "sh1" else 3, precolor=pre, precov=(combo == "precov"), bg=BG, as_torch=True)
     kw = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in kw.items()}
     if n is not None:
-        for k in ("means3D", "opacities", "shs", "colors_precomp", "scales", "rotations", "cov3D_precomp"):
+        for k in dense_twin.PER_GAUSSIAN:
             if k in kw:
                 kw[k] = kw[k][:n].contiguous()
     return kw
@@ -112,37 +81,12 @@ def image_gradient(H, W, seed=0):
     return torch.randn(3, H, W, generator=torch.Generator().manual_seed(seed))
 
 
-_PER_GAUSSIAN = ("means3D", "opacities", "shs", "colors_precomp", "scales", "rotations", "cov3D_precomp")
-
-
 def dense_render(kw, dd, camera=None):
-    """render_dense of the Gaussians of kw in front of z_view = 0.19, in dtype dd.  camera: (vm, pm, campos) tensors to use instead
-    of kw's (already of dtype dd, possibly requiring grad).  Returns the [3,H,W] image."""
-    vm32 = kw["viewmatrix"].float()
-    z = kw["means3D"].float() @ vm32[:3, 2] + vm32[3, 2]
-    keep = z > 0.19
-    t = {k: kw[k][keep].to(dd) for k in _PER_GAUSSIAN if k in kw}
-    vm, pm, cp = camera if camera is not None else (kw["viewmatrix"].to(dd), kw["projmatrix"].to(dd), kw["campos"].to(dd))
-    n = int(keep.sum())
-    color, _radii, _cnt = torch_dense.render_dense(means2D=torch.zeros(n, 3, dtype=dd), W=kw["W"], H=kw["H"], tanfovx=kw["tanfovx"],
-                                                   tanfovy=kw["tanfovy"], bg=kw["bg"].to(dd), viewmatrix=vm, projmatrix=pm, campos=cp,
-                                                   sh_degree=kw["sh_degree"], **t)
-    return color
-
-
-_REF = {}
+    """The twin's [3,H,W] image of kw in dtype dd.  camera: (vm, pm, campos) tensors to use instead of kw's (already of dtype dd, possibly
+    requiring grad)."""
+    return dense_twin.render(kw, dd, camera=camera)[0]
 
 
 def dense_camera_reference(key, kw, gimg):
-    """{"float64": {viewmatrix, projmatrix, campos}, "float32": {...}} (numpy float64 arrays) of sum(image * gimg) by the dense twin.
-    key: anything hashable naming (scene, combination, image gradient).  Computed once per key."""
-    if key in _REF:
-        return _REF[key]
-    out = {}
-    for dd in (torch.float64, torch.float32):
-        cam = tuple(kw[n].to(dd).detach().clone().requires_grad_() for n in NAMES)
-        (dense_render(kw, dd, cam) * gimg.to(dd)).sum().backward()
-        out["float64" if dd == torch.float64 else "float32"] = {
-            n: (np.zeros(tuple(c.shape)) if c.grad is None else c.grad.numpy().astype(np.float64)) for n, c in zip(NAMES, cam)}
-    _REF[key] = out
-    return out
+    """{"float64": {viewmatrix, projmatrix, campos}, "float32": {...}} (numpy float64 arrays) of sum(image * gimg) by the dense twin."""
+    return dense_twin.gradients(key, kw, gimg, camera=True, per_gaussian=False)

@@ -33,68 +33,96 @@ def scene_kwargs(g, cam, W, H, *, deg=3, precolor=None, precov=False, bg=(0.0, 0
         kw["rotations"] = g.get_rotation
     if as_torch:
         return kw
+    return to_numpy(kw)
+
+
+def ptr(a):
+    """ctypes pointer to a numpy array's data; None stays None."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def f32(a):
+    """Tensor or array -> contiguous float32 numpy array; None stays None."""
+    return None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, np.float32)
+
+
+def bits(a):
+    """The float32 values of a tensor or array, viewed as uint32."""
+    return f32(a).view(np.uint32)
+
+
+def to_numpy(kw):
     return {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in kw.items()}
 
 
-_HARNESS = None
+def append_view_space(g, cam, extra, seed=5):
+    """g with Gaussians appended that are placed in VIEW space (x, y right / down of the optical axis, z along it) and mapped to the world
+    by the camera's own matrix.  extra: (view position, log-scales, opacity logit) each; colours are copied from g's first rows, the
+    rotations drawn from `seed`."""
+    import torch
+    inv = torch.linalg.inv(cam.world_view_transform.double())
+    n = len(extra)
+    xyz = torch.stack([(torch.tensor(tuple(pos) + (1.0,), dtype=torch.float64) @ inv)[:3].float() for pos, _ls, _lo in extra])
+    sc = torch.tensor([ls for _p, ls, _lo in extra], dtype=torch.float32)
+    op = torch.tensor([[lo] for _p, _ls, lo in extra], dtype=torch.float32)
+    cat = lambda a, b: torch.cat([a.detach(), b.to(a.dtype)], 0)  # noqa: E731
+    return syn.SyntheticGaussians(cat(g._xyz, xyz), cat(g._features_dc, g._features_dc[:n]), cat(g._features_rest, g._features_rest[:n]),
+                                  cat(g._scaling, sc), cat(g._rotation, torch.randn(n, 4, generator=torch.Generator().manual_seed(seed))),
+                                  cat(g._opacity, op), g.max_sh_degree, g.active_sh_degree)
+
+
+# ---- the g++ builds of tests/cpu_harness -----------------------------------------------------------------------------------------
+# The flags decide the bits a harness returns: one of these three sets each.
+STRICT_FP = ("-ffp-contract=off", "-fno-fast-math")         # no contraction: every FMA is one the source asks for
+STRICT_FP_FMA = STRICT_FP + ("-mfma", "-mavx2")             # ... and fmaf() is the hardware instruction
+PLAIN = ()                                                  # integer code
+LG_MATH_H = os.path.join("lightgaussian_amd", "csrc", "lg_math.h")
+LG_API_H = os.path.join("include", "lightgaussian.h")
+_HARNESSES = {}
+
+
+def build_harness(name, *, headers, flags, signatures):
+    """tests/cpu_harness/liblg_<name>_harness.so: compiled with g++ from lg_<name>_harness.cpp if it is missing or older than the source or
+    one of `headers` (paths from the repository root), loaded once per process, with signatures = {symbol: (restype, argtypes)} applied."""
+    if name not in _HARNESSES:
+        d = os.path.join(ROOT, "tests", "cpu_harness")
+        so = os.path.join(d, f"liblg_{name}_harness.so")
+        srcs = [os.path.join(d, f"lg_{name}_harness.cpp")] + [os.path.join(ROOT, h) for h in headers]
+        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+            subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", *flags, srcs[0], "-o", so])
+        lib = C.CDLL(so)
+        for symbol, (restype, argtypes) in signatures.items():
+            getattr(lib, symbol).restype, getattr(lib, symbol).argtypes = restype, list(argtypes)
+        _HARNESSES[name] = lib
+    return _HARNESSES[name]
 
 
 def harness():
-    """g++ build of tests/cpu_harness (the product's lg_math.h compiled for the CPU)."""
-    global _HARNESS
-    if _HARNESS is not None:
-        return _HARNESS
-    d = os.path.join(ROOT, "tests", "cpu_harness")
-    so = os.path.join(d, "liblg_math_harness.so")
-    srcs = [os.path.join(d, "lg_math_harness.cpp"), os.path.join(ROOT, "lightgaussian_amd", "csrc", "lg_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                               "-mfma", "-mavx2", srcs[0], "-o", so])
-    lib = C.CDLL(so)
-    lib.h_exp.restype = C.c_float; lib.h_exp.argtypes = [C.c_float]
-    lib.h_seqsum32.restype = C.c_float; lib.h_seqsum32.argtypes = [C.c_float, C.c_uint32]
-    lib.h_fix40_quant.restype = C.c_uint64; lib.h_fix40_quant.argtypes = [C.c_float]
-    lib.h_fix40_score.restype = C.c_float; lib.h_fix40_score.argtypes = [C.c_uint64]
-    P = C.c_void_p
-    lib.h_forward.restype = C.c_int
-    lib.h_forward.argtypes = [C.c_int] * 5 + [P] * 6 + [C.c_float] + [P] * 5 + [C.c_float, C.c_float, C.c_int] + [P] * 10
-    lib.h_backward_geom.restype = None
-    lib.h_backward_geom.argtypes = [C.c_int] * 5 + [P, P, P, C.c_float, P, P, P, P, P, P, P, C.c_float, C.c_float, P] + [P] * 6
-    _HARNESS = lib
-    return lib
-
-
-_PLAN_HARNESS = None
+    """The product's lg_math.h compiled for the CPU."""
+    P, I, F = C.c_void_p, C.c_int, C.c_float
+    return build_harness("math", headers=(LG_MATH_H,), flags=STRICT_FP_FMA, signatures={
+        "h_exp": (F, [F]), "h_seqsum32": (F, [F, C.c_uint32]), "h_fix40_quant": (C.c_uint64, [F]), "h_fix40_score": (F, [C.c_uint64]),
+        "h_forward": (I, [I] * 5 + [P] * 6 + [F] + [P] * 5 + [F, F, I] + [P] * 10),
+        "h_backward_geom": (None, [I] * 5 + [P, P, P, F, P, P, P, P, P, P, P, F, F, P] + [P] * 6)})
 
 
 def plan_harness():
-    """g++ build of the product's host-side plans (lg_plan.h: KeyPlan, ForwardPlan), next to the math harness."""
-    global _PLAN_HARNESS
-    if _PLAN_HARNESS is not None:
-        return _PLAN_HARNESS
-    d = os.path.join(ROOT, "tests", "cpu_harness")
-    so = os.path.join(d, "liblg_plan_harness.so")
-    srcs = [os.path.join(d, "lg_plan_harness.cpp"), os.path.join(ROOT, "lightgaussian_amd", "csrc", "lg_plan.h"),
-            os.path.join(ROOT, "include", "lightgaussian.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-Wall", "-Wextra", "-Werror", srcs[0], "-o", so])
-    lib = C.CDLL(so)
-    lib.h_key_plan.restype = None
-    lib.h_key_plan.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
-    lib.h_forward_plan.restype = None
-    lib.h_forward_plan.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_int)]
-    _PLAN_HARNESS = lib
-    return lib
+    """The product's host-side plans (lg_plan.h: KeyPlan, ForwardPlan)."""
+    I, U = C.c_int, C.c_uint32
+    return build_harness("plan", headers=(os.path.join("lightgaussian_amd", "csrc", "lg_plan.h"), LG_API_H),
+                         flags=PLAIN + ("-Wall", "-Wextra", "-Werror"), signatures={
+        "h_key_plan": (None, [I, I, U, U, C.POINTER(U)]), "h_forward_plan": (None, [U, I, I, I, C.c_longlong, C.POINTER(I)])})
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+# the ten harnesses as (module, function): the registry __graft_entry__.build() walks
+HARNESSES = (("common", "harness"), ("common", "plan_harness")) + tuple((m, "harness") for m in (
+    "densify_common", "features_common", "features_geom_common", "adam_rows_common", "camera_grad_common", "antialias_common",
+    "filter3d_common", "absgrad_common"))
 
 
 def harness_forward(kw, cull=True, count=True):
     """Run the CPU emulation of the kernels' traversal; kw = scene_kwargs(...) numpy dict."""
     lib = harness()
-    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
     means3D = f32(kw["means3D"]); N = means3D.shape[0]
     shs = f32(kw.get("shs")); colors = f32(kw.get("colors_precomp"))
     M = 0 if shs is None else shs.shape[1]
@@ -106,10 +134,10 @@ def harness_forward(kw, cull=True, count=True):
     op = f32(kw["opacities"]).reshape(-1)
     sc = f32(kw.get("scales")); rot = f32(kw.get("rotations")); cov = f32(kw.get("cov3D_precomp"))
     bg = f32(kw["bg"]); vm = f32(kw["viewmatrix"]); pm = f32(kw["projmatrix"]); cp = f32(kw["campos"])
-    lib.h_forward(N, M, int(kw["sh_degree"]), W, H, _p(bg), _p(means3D), _p(shs), _p(colors), _p(op), _p(sc),
-                  float(kw.get("scale_modifier", 1.0)), _p(rot), _p(cov), _p(vm), _p(pm), _p(cp), float(kw["tanfovx"]),
-                  float(kw["tanfovy"]), int(cull), _p(out["color"]), _p(out["radii"]),
-                  _p(out["count"]) if count else None, _p(out["score"]) if count else None, _p(out["xy"]),
-                  _p(out["conic_opacity"]), _p(out["rgb"]), _p(out["ref_rect"]), _p(out["tight_rect"]), C.byref(ninst))
+    lib.h_forward(N, M, int(kw["sh_degree"]), W, H, ptr(bg), ptr(means3D), ptr(shs), ptr(colors), ptr(op), ptr(sc),
+                  float(kw.get("scale_modifier", 1.0)), ptr(rot), ptr(cov), ptr(vm), ptr(pm), ptr(cp), float(kw["tanfovx"]),
+                  float(kw["tanfovy"]), int(cull), ptr(out["color"]), ptr(out["radii"]),
+                  ptr(out["count"]) if count else None, ptr(out["score"]) if count else None, ptr(out["xy"]),
+                  ptr(out["conic_opacity"]), ptr(out["rgb"]), ptr(out["ref_rect"]), ptr(out["tight_rect"]), C.byref(ninst))
     out["num_instances"] = ninst.value
     return out

@@ -27,7 +27,7 @@ def shapes(n, deg):
     return dict(xyz=(n, 3), f_dc=(n, 1, 3), f_rest=(n, (deg + 1) ** 2 - 1, 3), opacity=(n, 1), scaling=(n, 3), rotation=(n, 4))
 
 
-def bits(t):
+def bits(t):       # (not common.bits: an int32 torch view on the CPU, for torch.equal)
     return t.detach().contiguous().cpu().view(torch.int32)
 
 
@@ -152,24 +152,12 @@ def can_step(model):
         assert p.numel() == 0 or not torch.equal(p.detach(), b), n
 
 
-_HARNESS = {}
-
-
 def harness():
-    """g++ build of tests/cpu_harness/lg_densify_harness.cpp (the product's lg_math.h child formulas compiled for the CPU)."""
+    """The product's lg_math.h child formulas compiled for the CPU (without -mfma: fmaf() is the library's)."""
     import ctypes as C
-    import subprocess
-    if "lib" not in _HARNESS:
-        d = os.path.join(HERE, "cpu_harness")
-        so = os.path.join(d, "liblg_densify_harness.so")
-        srcs = [os.path.join(d, "lg_densify_harness.cpp"), os.path.join(os.path.dirname(HERE), "lightgaussian_amd", "csrc", "lg_math.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", srcs[0], "-o", so])
-        lib = C.CDLL(so)
-        lib.h_densify_children.restype = None
-        lib.h_densify_children.argtypes = [C.c_int] + [C.c_void_p] * 6
-        _HARNESS["lib"] = lib
-    return _HARNESS["lib"]
+    import common
+    return common.build_harness("densify", headers=(common.LG_MATH_H,), flags=common.STRICT_FP, signatures={
+        "h_densify_children": (None, [C.c_int] + [C.c_void_p] * 6)})
 
 
 def random_case(n, deg=1, seed=0, hot=0.6, scale=(0.004, 1.2)):

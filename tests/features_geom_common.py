@@ -3,18 +3,18 @@ the geometry gradient of a loss on feature / alpha / colour maps -- the oracle's
 tolerance rule of tests/test_gpu_parity.py::test_backward_parity, and the g++ build of tests/cpu_harness/lg_features_geom_harness.cpp."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import torch
 
 import common
-from common import syn
+import dense_twin
+import tolerance
+from common import f32, ptr, syn
 from oracle import oracle
+from tolerance import TOL, rel_err  # noqa: F401  (the tests of this feature take them from here)
 
 GEOMETRY = ("means2D", "means3D", "opacities", "scales", "rotations")
-TOL = 1e-4
 
 # tests/test_gpu_features.py's scenes (seed 3, extent (1.5, 1, 1.5), orbit_camera(1, 7, ..., radius 4)), plus an opaque one in which
 # pixels terminate before their list ends (opacity_mean chosen on the CPU: sigmoid(4) = 0.98, test_features_geom_host.py asserts it)
@@ -90,60 +90,25 @@ def reference(name, Cn, bg, kind, color_bg=(0.1, 0.2, 0.3), camera=None):
     return out
 
 
-def rel_err(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
-
-
-def elem_excess(a, b, rtol=1e-4, atol_frac=2e-5):
-    a = np.asarray(a, np.float64).reshape(-1); b = np.asarray(b, np.float64).reshape(-1)
-    bound = rtol * np.abs(b) + atol_frac * (np.abs(b).max() + 1e-300)
-    return float((np.abs(a - b) / bound).max()) if a.size else 0.0
-
-
 def assert_within(got, ref, what="", names=GEOMETRY):
-    """The rule of test_backward_parity: rel_err <= max(1e-4, 3 floor) and elem_excess <= max(1, 3 x the float32 oracle's), floor = the
-    float32 oracle's own error against the float64 one on the same sums.  Every figure is printed before it is asserted."""
-    r64, r32 = ref["float64"], ref["float32"]
+    """The rule of test_backward_parity: rule 3 and the element-wise bound, against the float32 oracle's own error against the float64
+    one on the same sums."""
     for n in names:
-        a = np.asarray(got[n], np.float64).reshape(r64[n].shape)
-        floor, err = rel_err(r32[n], r64[n]), rel_err(a, r64[n])
-        ex, ex32 = elem_excess(a, r64[n]), elem_excess(r32[n], r64[n])
-        print(f"{what} {n}: rel_err {err:.3e} (float32 oracle {floor:.3e})  elem_excess {ex:.3f} (float32 oracle {ex32:.3f})")
-        assert np.isfinite(a).all(), f"{what} {n}: not finite"
-        assert err <= max(TOL, 3.0 * floor), f"{what} grad {n}: rel err {err:.3e} (float32 oracle floor {floor:.3e})"
-        assert ex <= max(1.0, 3.0 * ex32), f"{what} grad {n}: worst element {ex:.2f}x the element-wise bound (float32 oracle {ex32:.2f}x)"
-
-
-_HARNESS = None
+        tolerance.assert_rule3(got[n], ref["float64"][n], ref["float32"][n], f"{what} {n}", ref="oracle", nonzero=False)
+        tolerance.assert_elementwise(got[n], ref["float64"][n], ref["float32"][n], f"{what} {n}")
 
 
 def harness():
-    global _HARNESS
-    if _HARNESS is not None:
-        return _HARNESS
-    d = os.path.join(common.ROOT, "tests", "cpu_harness")
-    so = os.path.join(d, "liblg_features_geom_harness.so")
-    srcs = [os.path.join(d, "lg_features_geom_harness.cpp"), os.path.join(common.ROOT, "lightgaussian_amd", "csrc", "lg_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-                               srcs[0], "-o", so])
-    lib = C.CDLL(so)
-    P, F = C.c_void_p, C.c_float
-    lib.h_feature_bwd_step.restype = C.c_int
-    lib.h_feature_bwd_step.argtypes = [C.c_int] + [F] * 7 + [C.POINTER(F)] * 2 + [P, C.POINTER(F)]
-    lib.h_features_geom.restype = C.c_longlong
-    lib.h_features_geom.argtypes = [C.c_int] * 4 + [P] * 6 + [F, F] + [P] * 13
-    _HARNESS = lib
-    return lib
+    P, F, I = C.c_void_p, C.c_float, C.c_int
+    return common.build_harness("features_geom", headers=(common.LG_MATH_H,), flags=common.STRICT_FP_FMA, signatures={
+        "h_feature_bwd_step": (I, [I] + [F] * 7 + [C.POINTER(F)] * 2 + [P, C.POINTER(F)]),
+        "h_features_geom": (C.c_longlong, [I] * 4 + [P] * 6 + [F, F] + [P] * 13)})
 
 
 def harness_grads(kw, features, bg=None, dL_dout=None, dL_dalpha=None):
     """kw: common.scene_kwargs(...) (numpy, scales / rotations).  Returns ({tensor: array}, out [C,H,W], alpha [H,W], radii, pixels that
     ended before their list did)."""
     lib = harness()
-    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
-    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     means3D = f32(kw["means3D"]); N = means3D.shape[0]
     feats = f32(features); Cn = feats.shape[1]
     W, H = kw["W"], kw["H"]
@@ -154,9 +119,9 @@ def harness_grads(kw, features, bg=None, dL_dout=None, dL_dalpha=None):
     gr = dict(means2D=np.zeros((N, 3), np.float32), means3D=np.zeros((N, 3), np.float32), opacities=np.zeros((N, 1), np.float32),
               scales=np.zeros((N, 3), np.float32), rotations=np.zeros((N, 4), np.float32))
     early = np.zeros(1, np.int64)
-    lib.h_features_geom(N, Cn, W, H, p(means3D), p(op), p(sc), p(rot), p(vm), p(pm), float(kw["tanfovx"]), float(kw["tanfovy"]), p(feats),
-                        p(bgc), p(g), p(ga), p(out), p(alpha), p(radii), p(gr["means2D"]), p(gr["means3D"]), p(gr["opacities"]),
-                        p(gr["scales"]), p(gr["rotations"]), p(early))
+    lib.h_features_geom(N, Cn, W, H, ptr(means3D), ptr(op), ptr(sc), ptr(rot), ptr(vm), ptr(pm), float(kw["tanfovx"]), float(kw["tanfovy"]), ptr(feats),
+                        ptr(bgc), ptr(g), ptr(ga), ptr(out), ptr(alpha), ptr(radii), ptr(gr["means2D"]), ptr(gr["means3D"]), ptr(gr["opacities"]),
+                        ptr(gr["scales"]), ptr(gr["rotations"]), ptr(early))
     return gr, out, alpha, radii, int(early[0])
 
 
@@ -204,33 +169,31 @@ def depth_loss_maps(H, W, seed=5):
 _DEPTH_REF = {}
 
 
-def dense_depth_reference(name, camera=None):
+def dense_depth_reference(name, camera=None, antialias=False):
     """{dtype name: {raw parameter: gradient}} of  sum(depth gd + alpha ga),  depth = num / alpha.clamp_min(1e-6),  by the dense autograd
-    twin (oracle/torch_dense.py) rendering colors_precomp = [z(means3D), 1, 0] from the model's RAW parameters through its activations,
-    in float64 and in float32; plus "maps": the float64 twin's (numerator, alpha, radii).  camera: as for scene().  Computed once per key."""
-    from oracle import torch_dense
-    if (name, camera) in _DEPTH_REF:
-        return _DEPTH_REF[(name, camera)]
+    twin (tests/dense_twin.py, all N Gaussians) rendering colors_precomp = [z(means3D), 1, 0] from the model's RAW parameters through its
+    activations, in float64 and in float32; plus "maps": the float64 twin's (numerator, alpha, radii).  camera: as for scene();
+    antialias: with rho wrapped around the opacity.  Computed once per key."""
+    key = (name, camera, antialias)
+    if key in _DEPTH_REF:
+        return _DEPTH_REF[key]
     c, g, cam = scene(name, camera)
-    W, H = c["W"], c["H"]
-    gd, ga = depth_loss_maps(H, W)
+    kw = common.scene_kwargs(g, cam, c["W"], c["H"], precolor=torch.zeros(c["N"], 3), as_torch=True)
+    gd, ga = depth_loss_maps(c["H"], c["W"])
     out = {}
-    for dd in (torch.float64, torch.float32):
+    for dd, dname in dense_twin.DTYPES:
         raw = {n: getattr(g, n).to(dd).detach().clone().requires_grad_() for n in RAW}
         vm = cam.world_view_transform.to(dd)
         z = raw["_xyz"] @ vm[:3, 2:3] + vm[3, 2]
-        color, radii, _cnt = torch_dense.render_dense(
-            means3D=raw["_xyz"], means2D=torch.zeros(c["N"], 3, dtype=dd), opacities=torch.sigmoid(raw["_opacity"]), W=W, H=H,
-            tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5), bg=torch.zeros(3, dtype=dd), viewmatrix=vm,
-            projmatrix=cam.full_proj_transform.to(dd), campos=cam.camera_center.to(dd),
-            colors_precomp=torch.cat([z, torch.ones_like(z), torch.zeros_like(z)], 1), scales=torch.exp(raw["_scaling"]),
-            rotations=torch.nn.functional.normalize(raw["_rotation"]))
+        act = dict(means3D=raw["_xyz"], opacities=torch.sigmoid(raw["_opacity"]), scales=torch.exp(raw["_scaling"]),
+                   rotations=torch.nn.functional.normalize(raw["_rotation"]), colors_precomp=torch.cat([z, torch.ones_like(z), torch.zeros_like(z)], 1))
+        color, radii, _cnt = dense_twin.render(kw, dd, leaves=act, antialias=antialias, front_only=False)
         depth = color[0] / color[1].clamp_min(1e-6)
         (depth * torch.from_numpy(gd).to(dd) + color[1] * torch.from_numpy(ga).to(dd)).sum().backward()
-        out["float64" if dd == torch.float64 else "float32"] = {n: raw[n].grad.numpy().astype(np.float64) for n in RAW}
+        out[dname] = {n: raw[n].grad.numpy().astype(np.float64) for n in RAW}
         if dd == torch.float64:
             out["maps"] = (color[0].detach().numpy(), color[1].detach().numpy(), radii.numpy())
-    _DEPTH_REF[(name, camera)] = out
+    _DEPTH_REF[key] = out
     return out
 
 

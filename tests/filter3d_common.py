@@ -16,43 +16,23 @@ apply_formula() is the specification written in torch (any dtype, differentiable
     activated  s'_k = sqrt(s_k^2 + f^2),  sigma' = sigma c."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import torch
 
 import common
-from common import syn
+from common import ptr, syn  # noqa: F401  (the tests of this feature take ptr from here)
 
 SIZES = ((70, 45), (33, 17))
 NS = (1, 63, 64, 65, 257, 1000)
 CHUNK = 64                      # LG_F3D_CHUNK: cameras per LDS stage of lg_filter3d_update_kernel
 VS = (1, 3, CHUNK + 1)
 
-_HARNESS = None
-
 
 def harness():
-    global _HARNESS
-    if _HARNESS is not None:
-        return _HARNESS
-    d = os.path.join(common.ROOT, "tests", "cpu_harness")
-    so = os.path.join(d, "liblg_filter3d_harness.so")
-    srcs = [os.path.join(d, "lg_filter3d_harness.cpp"), os.path.join(common.ROOT, "lightgaussian_amd", "csrc", "lg_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-mavx2",
-                               srcs[0], "-o", so])
-    lib = C.CDLL(so)
     P, I = C.c_void_p, C.c_int
-    lib.h_filter3d.restype = None
-    lib.h_filter3d.argtypes = [I, P, I, P, P, P, P, P]
-    _HARNESS = lib
-    return lib
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return common.build_harness("filter3d", headers=(common.LG_MATH_H,), flags=common.STRICT_FP_FMA, signatures={
+        "h_filter3d": (None, [I, P, I, P, P, P, P, P])})
 
 
 # ---- cameras -----------------------------------------------------------------------------------------------------------------

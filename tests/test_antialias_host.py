@@ -20,6 +20,7 @@ import torch
 import antialias_common as aa
 import camera_grad_common as cg
 import common
+import tolerance
 from common import syn
 from lightgaussian_amd import _lib, gaussian_renderer, rasterizer
 
@@ -61,7 +62,7 @@ def test_rho_against_the_float64_formula():
     floor, err = aa.rel_err(d32, d64), aa.rel_err(got, d64)
     print(f"rho: rel_err {err:.3e} (float32 torch {floor:.3e}); range {d64.min():.3f} .. {d64.max():.3f}")
     assert d64.min() < 0.1 and d64.max() > 0.99
-    assert err <= max(aa.TOL, 3.0 * floor)
+    assert err <= tolerance.rule3_bound(floor)
 
 
 def test_rho_edge_cases_are_exact():

@@ -29,7 +29,7 @@ import torch
 import camera_common
 import camera_grad_common as cg
 import common
-from common import syn
+from common import f32, ptr, syn
 from lightgaussian_amd import _lib, gaussian_renderer, pose, rasterizer
 from lightgaussian_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer
 from lightgaussian_amd.vectree import CompressedGaussians, TrainableCompressed
@@ -151,12 +151,10 @@ def test_camera_terms_match_float64_autograd(name):
     rs = np.random.RandomState(17)
     acc5 = rs.randn(N, 5).astype(np.float32)
     drgb = rs.randn(N, 3).astype(np.float32)
-    f32 = lambda t: np.ascontiguousarray(t.detach().numpy(), np.float32)  # noqa: E731
     p, sc, rot, sh = f32(g.get_xyz), f32(g.get_scaling), f32(g.get_rotation), f32(g.get_features)
     vm, pm, cp = f32(cam.world_view_transform), f32(cam.full_proj_transform), f32(cam.camera_center)
     tanx, tany = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
     sums = np.zeros(27, np.float64); dmean = np.zeros((N, 3), np.float32); vis = np.zeros(N, np.int32)
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     n = lib.h_camera_terms(N, 3, W, H, ptr(p), ptr(sc), ptr(rot), ptr(acc5), ptr(drgb), ptr(sh), ptr(vm), ptr(pm), ptr(cp), tanx, tany,
                            ptr(sums), ptr(dmean), ptr(vis))
     assert n == int(vis.sum()) >= 200
@@ -191,8 +189,6 @@ def test_colours_as_inputs_have_no_camera_centre_term():
     N = g.num
     rs = np.random.RandomState(3)
     acc5 = rs.randn(N, 5).astype(np.float32); drgb = rs.randn(N, 3).astype(np.float32)
-    f32 = lambda t: np.ascontiguousarray(t.detach().numpy(), np.float32)  # noqa: E731
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     p, sc, rot = f32(g.get_xyz), f32(g.get_scaling), f32(g.get_rotation)
     vm, pm, cp = f32(cam.world_view_transform), f32(cam.full_proj_transform), f32(cam.camera_center)
     sums = np.zeros(27, np.float64); dmean = np.zeros((N, 3), np.float32); vis = np.zeros(N, np.int32)

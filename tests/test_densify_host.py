@@ -96,7 +96,7 @@ def test_thresholds_are_rounded_once():
     model = dc.model_of(dc.case("deg0"))
     model.percent_dense = 0.01
     th = densify.thresholds(model, 0.0002, 0.005, np.float32(4.8), None)
-    f32 = lambda v: float(np.float32(v))      # noqa: E731
+    f32 = lambda v: float(np.float32(v))      # noqa: E731  (not common.f32: a Python float rounded to float32)
     assert th == dict(thr_g=f32(0.0002), thr_d=f32(0.01 * float(np.float32(4.8))), thr_w=f32(0.1 * float(np.float32(4.8))), min_opacity=f32(0.005),
                       use_extent=False)
     assert densify.thresholds(model, 0.0002, 0.005, 4.8, 20)["use_extent"] is True
@@ -149,7 +149,7 @@ def test_child_formulas_of_lg_math_follow_the_rule(name):
     noise = np.ascontiguousarray(np.concatenate([c["noise"][rank], c["noise"][n_s + rank]]), np.float32)
     xyz, sc = (np.ascontiguousarray(c[k][parents], np.float32) for k in ("in_xyz", "in_scaling"))
     out_xyz, out_sc = np.zeros_like(xyz), np.zeros_like(sc)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    p = common.ptr
     dc.harness().h_densify_children(2 * n_child, p(xyz), p(sc), p(rot), p(noise), p(out_xyz), p(out_sc))
     dc.rule(f"{name} harness xyz", out_xyz, c["out_xyz"][first:], c["r64_xyz"])
     dc.rule(f"{name} harness scaling", out_sc, c["out_scaling"][first:], c["r64_scaling"])

@@ -12,16 +12,13 @@ import torch
 
 import common
 import features_common
+from common import bits as _bits
 from common import syn
 from lightgaussian_amd import _lib, features, gaussian_renderer
 from lightgaussian_amd.rasterizer import GaussianRasterizationSettings
 from oracle import oracle
 
 HDR = os.path.join(common.ROOT, "include", "lightgaussian.h")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def test_symbols_declared_bound_and_exported():

@@ -13,17 +13,12 @@ import torch
 import absgrad_common as ab
 import camera_grad_common as cg
 import densify_common as dc
+from common import bits as _bits
 from lightgaussian_amd import densify, rasterizer
 
 pytestmark = pytest.mark.gpu
 DEV = ab.DEV
 ON = {"absgrad": True}
-
-
-def _bits(a):
-    if torch.is_tensor(a):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _run(path, name, options, **kw):

@@ -30,7 +30,7 @@ def model_shapes(N):
     return dict(xyz=(N, 3), f_dc=(N, 1, 3), f_rest=(N, 15, 3), opacity=(N, 1), scaling=(N, 3), rotation=(N, 4))
 
 
-def bits(t):
+def bits(t):       # (not common.bits: an integer torch view of any element size, on the device)
     return t.detach().contiguous().view({1: torch.uint8, 4: torch.int32, 8: torch.int64}[t.element_size()])
 
 

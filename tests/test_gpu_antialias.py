@@ -11,7 +11,6 @@ active, one removed by the compensation alone, one ten times the mean size) and 
 The "opacity" weight policy keeps the RAW sigma (a property of the model, not of the view): its expected score is the oracle's
 sequential sum of sigma over the oracle's antialiased hit count, not the score of the oracle call that was handed sigma rho32."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -19,54 +18,28 @@ import torch
 
 import antialias_common as aa
 import camera_grad_common as cg
+import dense_twin
 import features_geom_common as fg
 import gpu_common
+from common import bits as _bits
 from common import syn
+from common import to_numpy as _np
 from lightgaussian_amd import _lib, gaussian_renderer, rasterizer, vectree
-from lightgaussian_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer
-from oracle import oracle, torch_dense
+from oracle import oracle
 from test_gpu_full_size import _last_contributor
 from test_gpu_vq_render import packed_scene
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SCENES = ("N300_70x45", "N64_33x17")
-PER_GAUSSIAN = ("means3D", "opacities", "shs", "colors_precomp", "scales", "rotations", "cov3D_precomp")
+PER_GAUSSIAN = dense_twin.PER_GAUSSIAN
 ON = {"antialiasing": True}
 
 
-def _bits(a):
-    if torch.is_tensor(a):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _np(kw):
-    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else v) for k, v in kw.items()}
-
-
 def run(kw, gimg, options, camera_grad=False):
-    """One forward + backward of sum(image * gimg) through GaussianRasterizer (activated inputs).  Returns the image (attached), radii,
-    {name: gradient tensor} and the camera gradients (or None)."""
-    dev = torch.device(DEV)
-    t = {k: (v.detach().to(dev).clone() if torch.is_tensor(v) else v) for k, v in kw.items()}
-    for n in PER_GAUSSIAN:
-        if n in t:
-            t[n].requires_grad_(True)
-    cam = {n: t[n].requires_grad_(camera_grad) for n in cg.NAMES}
-    rs = GaussianRasterizationSettings(image_height=t["H"], image_width=t["W"], tanfovx=t["tanfovx"], tanfovy=t["tanfovy"], bg=t["bg"],
-                                       scale_modifier=1.0, viewmatrix=cam["viewmatrix"], projmatrix=cam["projmatrix"], sh_degree=t["sh_degree"],
-                                       campos=cam["campos"], prefiltered=False, debug=False, f_count=False)
-    means2D = torch.zeros((t["means3D"].shape[0], 3), device=dev, requires_grad=True)
-    color, radii = GaussianRasterizer(rs, options=dict(options, camera_grad=camera_grad))(
-        means3D=t["means3D"], means2D=means2D, opacities=t["opacities"], shs=t.get("shs"), colors_precomp=t.get("colors_precomp"),
-        scales=t.get("scales"), rotations=t.get("rotations"), cov3D_precomp=t.get("cov3D_precomp"))
-    (color * gimg.to(dev)).sum().backward(retain_graph=True)
-    torch.cuda.synchronize()
-    grads = {n: t[n].grad for n in PER_GAUSSIAN if n in t}
-    grads["means2D"] = means2D.grad
-    camera = {n: cam[n].grad.detach().cpu().numpy().copy() for n in cg.NAMES} if camera_grad else None
-    return color, radii, grads, camera
+    """gpu_common.run_rasterizer, the graph kept (the forward's saved state is read after the backward), as (image, radii, grads, camera)."""
+    out = gpu_common.run_rasterizer(kw, gimg, options, camera_grad=camera_grad, retain_graph=True)
+    return out["image"], out["radii"], out["grads"], out["camera"]
 
 
 _ORACLE = {}
@@ -151,12 +124,12 @@ _RAW = ("_xyz", "_opacity", "_scaling", "_rotation", "_features_dc", "_features_
 
 def _raw_reference(name, g, kw, gimg):
     out = {}
-    for dd in (torch.float64, torch.float32):
+    for dd, dname in dense_twin.DTYPES:
         raw = {n: getattr(g, n).to(dd).detach().clone().requires_grad_() for n in _RAW}
         act = dict(means3D=raw["_xyz"], opacities=torch.sigmoid(raw["_opacity"]), scales=torch.exp(raw["_scaling"]),
                    rotations=torch.nn.functional.normalize(raw["_rotation"]), shs=torch.cat([raw["_features_dc"], raw["_features_rest"]], 1))
-        (cg.dense_render(aa.twin_kwargs(kw, act, dd), dd) * gimg.to(dd)).sum().backward()
-        out["float64" if dd == torch.float64 else "float32"] = {n: raw[n].grad.numpy().astype(np.float64) for n in _RAW}
+        (dense_twin.render(kw, dd, leaves=act, antialias=True)[0] * gimg.to(dd)).sum().backward()
+        out[dname] = {n: raw[n].grad.numpy().astype(np.float64) for n in _RAW}
     return out
 
 
@@ -215,36 +188,11 @@ def test_camera_gradients_against_the_dense_twin(combo):
 
 
 # ---- 5. feature maps -----------------------------------------------------------------------------------------------------------------
-def _depth_reference(name):
-    """features_geom_common.dense_depth_reference with rho wrapped around the opacity."""
-    c, g, cam = fg.scene(name)
-    W, H = c["W"], c["H"]
-    gd, ga = fg.depth_loss_maps(H, W)
-    tanx, tany = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
-    out = {}
-    for dd in (torch.float64, torch.float32):
-        raw = {n: getattr(g, n).to(dd).detach().clone().requires_grad_() for n in fg.RAW}
-        vm = cam.world_view_transform.to(dd)
-        z = raw["_xyz"] @ vm[:3, 2:3] + vm[3, 2]
-        act = dict(means3D=raw["_xyz"], scales=torch.exp(raw["_scaling"]), rotations=torch.nn.functional.normalize(raw["_rotation"]))
-        rho = aa.rho_torch(act, vm, W, H, tanx, tany)
-        color, radii, _cnt = torch_dense.render_dense(
-            means2D=torch.zeros(c["N"], 3, dtype=dd), opacities=torch.sigmoid(raw["_opacity"]) * rho[:, None], W=W, H=H, tanfovx=tanx,
-            tanfovy=tany, bg=torch.zeros(3, dtype=dd), viewmatrix=vm, projmatrix=cam.full_proj_transform.to(dd),
-            campos=cam.camera_center.to(dd), colors_precomp=torch.cat([z, torch.ones_like(z), torch.zeros_like(z)], 1), **act)
-        depth = color[0] / color[1].clamp_min(1e-6)
-        (depth * torch.from_numpy(gd).to(dd) + color[1] * torch.from_numpy(ga).to(dd)).sum().backward()
-        out["float64" if dd == torch.float64 else "float32"] = {n: raw[n].grad.numpy().astype(np.float64) for n in fg.RAW}
-        if dd == torch.float64:
-            out["maps"] = (color[0].detach().numpy(), color[1].detach().numpy(), radii.numpy())
-    return out
-
-
 def test_render_features_depth_with_geometry_gradients():
     name = "N64_33x17"
     c, g, cam = fg.scene(name)
     W, H = c["W"], c["H"]
-    ref = _depth_reference(name)
+    ref = fg.dense_depth_reference(name, antialias=True)
     gd, ga = (torch.from_numpy(a).float().to(DEV) for a in fg.depth_loss_maps(H, W))
     model = g.to(DEV)
     for n in fg.RAW:

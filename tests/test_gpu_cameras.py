@@ -27,21 +27,15 @@ import torch
 
 import camera_common as cc
 import common
+from common import bits as _bits
 from common import syn
+from common import to_numpy as _np
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-4
 GIMG_SEED = 11
-
-
-def _np(kw):
-    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else v) for k, v in kw.items()}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _kw(name, variant="sh"):

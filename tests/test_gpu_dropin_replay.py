@@ -14,6 +14,7 @@ import numpy as np
 
 import common
 import gpu_common
+import tolerance
 from common import syn
 from oracle import oracle
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
@@ -90,5 +91,5 @@ def test_recorded_reference_calls_run_through_the_library(which):
                 r = g64[name]
                 floor = gpu_common.rel_err(g32[name], r)
                 err = gpu_common.rel_err(t.grad.cpu().numpy().reshape(r.shape), r)
-                assert err <= max(1e-4, 3.0 * floor), f"{which}: grad {name} rel err {err:.2e} (fp32 oracle floor {floor:.2e})"
+                assert err <= tolerance.rule3_bound(floor), f"{which}: grad {name} rel err {err:.2e} (fp32 oracle floor {floor:.2e})"
         assert float(kwargs["means2D"].grad[:, :2].abs().sum()) > 0 and float(kwargs["means2D"].grad[:, 2].abs().sum()) == 0

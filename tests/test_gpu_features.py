@@ -10,7 +10,7 @@ import torch
 
 import common
 import gpu_common
-from common import syn
+from common import bits, syn
 from lightgaussian_amd import features as lg_features
 from lightgaussian_amd import gaussian_renderer, vectree
 from lightgaussian_amd.rasterizer import GaussianRasterizationSettings
@@ -29,10 +29,6 @@ SCENES = {
     "n400_48x48": (400, 48, 48, dict(log_scale_mean=math.log(0.25), opacity_mean=-2.0), {}),
 }
 MODES = {"canonical": {"fast_exp": False}, "hardware_exp": {"fast_exp": True}}
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def settings(kw, bg):

@@ -25,6 +25,7 @@ import antialias_common as aa
 import camera_grad_common as cg
 import features_geom_common as fg
 import filter3d_common as fc
+from common import bits as _bits
 from common import syn
 from lightgaussian_amd import _lib, filter3d, gaussian_renderer
 
@@ -32,12 +33,6 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SCENES = ("N300_70x45", "N64_33x17")
 RAW = ("_xyz", "_opacity", "_scaling", "_rotation", "_features_dc", "_features_rest")
-
-
-def _bits(a):
-    if torch.is_tensor(a):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _same(a, b):
@@ -96,7 +91,7 @@ def test_update_argument_checks():
     t = filter3d.camera_table(fc.cameras(1, 33, 17)).to(DEV)
     out = torch.zeros(4, device=DEV)
     sc = torch.zeros(lib.lg_filter3d_scratch_bytes(4), dtype=torch.uint8, device=DEV)
-    p = lambda a: C.c_void_p(a.data_ptr())  # noqa: E731
+    p = lambda a: C.c_void_p(a.data_ptr())  # noqa: E731  (not common.ptr: the device pointer of a tensor)
     assert lib.lg_filter3d_update(-1, p(x), 1, p(t), p(out), None, p(sc), 0, None) == _lib.LG_ERR_INVALID_ARGUMENT
     assert lib.lg_filter3d_update(1 << 30, p(x), 1, p(t), p(out), None, p(sc), 0, None) == _lib.LG_ERR_INVALID_ARGUMENT
     assert lib.lg_filter3d_update(4, p(x), 0, p(t), p(out), None, p(sc), 0, None) == _lib.LG_ERR_INVALID_ARGUMENT

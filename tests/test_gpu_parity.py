@@ -11,7 +11,9 @@ import pytest
 import torch
 
 import common
+import tolerance
 from common import syn
+from common import to_numpy as _np
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -45,10 +47,6 @@ def _scene(c):
     pre = torch.rand(c["N"], 3, generator=torch.Generator().manual_seed(7)) if c.get("precolor") else None
     return common.scene_kwargs(g, cam, c["W"], c["H"], deg=c["deg"], precolor=pre, precov=c.get("precov", False),
                                bg=(0.1, 0.2, 0.3), as_torch=True)
-
-
-def _np(kw):
-    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else v) for k, v in kw.items()}
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"N{c['N']}_{c['W']}x{c['H']}_d{c['deg']}")
@@ -637,4 +635,4 @@ def test_elongated_diagonal_splats_and_the_block_reach_test(scale, aspect):
     for name, gr in fast["grads"].items():
         r = g64[name]
         floor = gpu_common.rel_err(g32[name], r)
-        assert gpu_common.rel_err(gr.reshape(r.shape), r) <= max(TOL, 3.0 * floor), name
+        assert gpu_common.rel_err(gr.reshape(r.shape), r) <= tolerance.rule3_bound(floor), name

@@ -41,7 +41,7 @@ def packed_scene(N, deg, vq_ratio, K=256, seed=1, scale=0.02):
     return vectree.pack(feats, mask, codebook, ind)
 
 
-def bits(t):
+def bits(t):       # (not common.bits: an int32 torch view on the device, for torch.equal)
     return t.detach().contiguous().view(torch.int32)
 
 

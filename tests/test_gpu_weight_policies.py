@@ -19,16 +19,13 @@ import torch
 
 import common
 import gpu_common
+from common import bits as _bits
 from common import syn
 from oracle import oracle
 from test_gpu_parity import CASES, _np, _scene
 
 pytestmark = pytest.mark.gpu
 POLICIES = {"alpha": oracle.W_ALPHA, "alpha_t": oracle.W_ALPHA_T}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("pol", sorted(POLICIES))

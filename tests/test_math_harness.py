@@ -10,12 +10,9 @@ import torch
 
 import camera_common
 import common
-from common import syn
+from common import bits as _bits
+from common import f32, syn
 from oracle import oracle
-
-
-def _bits(a):
-    return np.asarray(a, np.float32).view(np.uint32)
 
 
 def test_canonical_exp_bitwise_and_accuracy():
@@ -138,7 +135,6 @@ def test_backward_geometry_stage_matches_oracle_under_general_cameras(name):
 
 
 def _backward_geometry_stage(kw, rowwise=False):
-    import ctypes as C
     lib = common.harness()
     W, H = kw["W"], kw["H"]
     f = oracle.forward(**kw)
@@ -147,10 +143,9 @@ def _backward_geometry_stage(kw, rowwise=False):
     acc = (rs.randn(N, 9) * (f.radii[:, None] > 0)).astype(np.float32)
     # oracle side: re-run its per-Gaussian stage by calling the harness' twin with identical acc is the only
     # way to isolate the stage; the oracle has no such hook, so check the harness against float64 autograd instead
-    f32 = lambda a: np.ascontiguousarray(a, np.float32)
     outs = [np.zeros((N, 3), np.float32), np.zeros((N, 3), np.float32), np.zeros((N, M, 3), np.float32), np.zeros((N, 3), np.float32),
             np.zeros((N, 4), np.float32), np.zeros((N, 6), np.float32)]
-    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    P = common.ptr
     means3D = f32(kw["means3D"]); shs = f32(kw["shs"]); sc = f32(kw["scales"]); rot = f32(kw["rotations"])
     vm = f32(kw["viewmatrix"]); pm = f32(kw["projmatrix"]); cp = f32(kw["campos"])
     lib.h_backward_geom(N, M, 3, W, H, P(means3D), P(shs), P(sc), 1.0, P(rot), P(f.saved["cov3D"]), P(f.saved["clamped"]),

@@ -74,7 +74,7 @@ def packed_case(N, deg, how, seed=1):
     return packed_by_hand(N, deg, seed) if how == "hand" else packed_random(N, deg, how, seed=seed)
 
 
-def bits(t):
+def bits(t):       # (not common.bits: an int32 torch view on the device, for torch.equal)
     return t.detach().contiguous().view(torch.int32)
 
 
