@@ -8,6 +8,8 @@ import ctypes as C
 import os
 import subprocess
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # LIGHTGAUSSIAN_HIP_LIB: A/B builds of the same library on one GPU box (tools/gpu_ab.sh); always an in-tree HIP build
 LIB_PATH = os.environ.get("LIGHTGAUSSIAN_HIP_LIB") or os.path.join(_HERE, "liblightgaussian_hip.so")
@@ -34,21 +36,6 @@ DENSIFY_MAX_TENSORS = 32    # LG_DENSIFY_MAX_TENSORS: tensors per lg_densify_row
 FEATURES_MAX = 64           # LG_FEATURES_MAX: channels per lg_blend_features call
 FILTER3D_RAW = 1            # LG_FILTER3D_RAW: lg_filter3d_apply / _bwd on log-scales and opacity logits
 ABI_VERSION = 7     # include/lightgaussian.h LG_ABI_VERSION this binding was written against (load() refuses another)
-
-EXPORTS = ["lg_geom_bytes", "lg_img_bytes", "lg_binning_bytes", "lg_backward_scratch_bytes", "lg_forward",
-           "lg_forward_count", "lg_backward", "lg_score_from_count", "lg_abi_version", "lg_last_error",
-           "lg_profile_read", "lg_profile_reset", "lg_last_stats", "lg_debug_reduce9", "lg_loss_state_bytes",
-           "lg_loss_forward", "lg_loss_backward", "lg_prune_scratch_bytes", "lg_prune_epilogue", "lg_knn_scratch_bytes",
-           "lg_knn3_mean_dist2", "lg_ordered_sum", "lg_forward_bounded", "lg_select_mask", "lg_compact_scratch_bytes",
-           "lg_compact_plan", "lg_compact_rows", "lg_vq_scratch_bytes", "lg_vq_nearest", "lg_debug_sort_temp_bytes",
-           "lg_debug_sort_keys", "lg_build_id", "lg_backward_chunked", "lg_debug_activations", "lg_view_status",
-           "lg_debug_sort_orphan", "lg_debug_last_contributor", "lg_debug_tile_lists", "lg_geom_visible_offset",
-           "lg_sh_grad_from_rgb", "lg_debug_view_meta", "lg_vq_ema_scratch_bytes", "lg_vq_ema_step", "lg_vq_colors",
-           "lg_vq_code_index_bytes", "lg_vq_code_index_scratch_bytes", "lg_vq_code_index", "lg_vq_colors_bwd_scratch_bytes",
-           "lg_vq_colors_bwd", "lg_adam_step", "lg_adam_step_rows", "lg_densify_scratch_bytes", "lg_densify_stats", "lg_densify_plan", "lg_densify_rows",
-           "lg_features_scratch_bytes", "lg_blend_features", "lg_blend_features_backward", "lg_backward_features_scratch_bytes",
-           "lg_backward_features", "lg_camera_scratch_bytes", "lg_backward_camera", "lg_filter3d_scratch_bytes", "lg_filter3d_update",
-           "lg_filter3d_apply", "lg_filter3d_apply_bwd", "lg_backward_abs"]
 
 
 class lg_view(C.Structure):
@@ -101,6 +88,83 @@ def build(force=False, verbose=False):
     return LIB_PATH
 
 
+# The C ABI of include/lightgaussian.h and include/lightgaussian_debug.h, in header order: name -> (restype, argtypes).
+# tests/test_abi.py holds every entry against the headers.
+i32, i64, u32, f32, f64, sz, vp, P = C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_double, C.c_size_t, C.c_void_p, C.POINTER
+_VIEW, _GAUSSIANS = P(lg_view), P(lg_gaussians)
+_BACKWARD = (_VIEW, _GAUSSIANS, vp, vp, vp, vp, i64) + (vp,) * 12      # ... dL_dcolor, the nine gradients, scratch, stream
+_CHUNKED = _BACKWARD + (i32, CHUNK_FN, vp)
+PROTOTYPES = {
+    "lg_geom_bytes": (sz, (i32,)),
+    "lg_img_bytes": (sz, (i32, i32)),
+    "lg_binning_bytes": (sz, (i64, i32, i32, i32)),
+    "lg_backward_scratch_bytes": (sz, (i32, i64)),
+    "lg_forward": (C.c_int, (_VIEW, _GAUSSIANS, vp, vp, ALLOC_FN, vp, vp, vp, P(vp), P(i64), vp)),
+    "lg_forward_count": (C.c_int, (_VIEW, _GAUSSIANS, vp, vp, ALLOC_FN, vp, i32, vp, vp, vp, vp, P(vp), P(i64), vp)),
+    "lg_forward_bounded": (C.c_int, (_VIEW, _GAUSSIANS, vp, vp, vp, i64, f32, i32, vp, vp, vp, vp, vp, P(u32 * 4), vp)),
+    "lg_backward": (C.c_int, _BACKWARD),
+    "lg_sh_grad_from_rgb": (C.c_int, (i32, i32, i32, i32, vp, vp, vp, i64, f32, i32, vp, vp, vp)),
+    "lg_backward_chunked": (C.c_int, _CHUNKED),
+    "lg_backward_abs": (C.c_int, _CHUNKED + (vp,)),
+    "lg_score_from_count": (C.c_int, (i32, vp, vp, vp, vp)),
+    "lg_prune_scratch_bytes": (sz, (i32,)),
+    "lg_prune_epilogue": (C.c_int, (i32, vp, vp, f32, f64, vp, vp, vp, vp, u32, vp)),
+    "lg_select_mask": (C.c_int, (i32, vp, i64, vp, vp, vp, vp)),
+    "lg_compact_scratch_bytes": (sz, (i32,)),
+    "lg_compact_plan": (C.c_int, (i32, vp, vp, vp, vp, vp)),
+    "lg_compact_rows": (C.c_int, (i32, vp, i32, P(vp), P(vp), P(i32), vp)),
+    "lg_vq_scratch_bytes": (sz, (i32, i32)),
+    "lg_vq_nearest": (C.c_int, (i32, i32, i32, vp, vp, vp, vp, u32, vp)),
+    "lg_vq_ema_scratch_bytes": (sz, (i32, i32, i32)),
+    "lg_vq_ema_step": (C.c_int, (i32, i32, i32, vp, vp, vp, vp, f64, f64, vp, vp, u32, vp)),
+    "lg_vq_colors": (C.c_int, (i32, i32, i32, vp, vp, vp, vp, i32, vp, u32, vp)),
+    "lg_vq_code_index_bytes": (sz, (i32, i32)),
+    "lg_vq_code_index_scratch_bytes": (sz, (i32, i32)),
+    "lg_vq_code_index": (C.c_int, (i32, i32, vp, vp, vp, vp)),
+    "lg_vq_colors_bwd_scratch_bytes": (sz, (i32, i32, i32)),
+    "lg_vq_colors_bwd": (C.c_int, (i32, i32, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, u32, vp)),
+    "lg_adam_step": (C.c_int, (i32, P(lg_adam_tensor), f64, f64, f64, u32, vp)),
+    "lg_adam_step_rows": (C.c_int, (i32, P(lg_adam_rows_tensor), f64, f64, f64, u32, vp)),
+    "lg_densify_scratch_bytes": (sz, (i32,)),
+    "lg_densify_stats": (C.c_int, (i32, vp, vp, vp, vp, vp, vp, u32, vp)),
+    "lg_densify_plan": (C.c_int, (i32, vp, vp, vp, vp, f32, f32, f32, f32, i32, vp, vp, vp, u32, vp)),
+    "lg_densify_rows": (C.c_int, (i32, i64, vp, vp, i32, P(lg_densify_tensor), vp, vp, vp, i64, u32, vp)),
+    "lg_features_scratch_bytes": (sz, (i32, i64, i32)),
+    "lg_blend_features": (C.c_int, (_VIEW, i32, vp, vp, i64, vp, i32, vp, vp, vp, vp)),
+    "lg_blend_features_backward": (C.c_int, (_VIEW, i32, vp, vp, i64, vp, i32, vp, vp, vp)),
+    "lg_backward_features_scratch_bytes": (sz, (i32, i64, i32)),
+    "lg_backward_features": (C.c_int, (_VIEW, _GAUSSIANS, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, vp) + (vp,) * 12),
+    "lg_camera_scratch_bytes": (sz, (i32,)),
+    "lg_backward_camera": (C.c_int, (_VIEW, _GAUSSIANS, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp)),
+    "lg_filter3d_scratch_bytes": (sz, (i32,)),
+    "lg_filter3d_update": (C.c_int, (i32, vp, i32, vp, vp, vp, vp, u32, vp)),
+    "lg_filter3d_apply": (C.c_int, (i32, vp, vp, vp, vp, vp, u32, vp)),
+    "lg_filter3d_apply_bwd": (C.c_int, (i32, vp, vp, vp, vp, vp, vp, vp, u32, vp)),
+    "lg_ordered_sum": (C.c_int, (i32, i64, vp, i64, vp, vp)),
+    "lg_knn_scratch_bytes": (sz, (i32,)),
+    "lg_knn3_mean_dist2": (C.c_int, (i32, vp, vp, vp, u32, vp)),
+    "lg_loss_state_bytes": (sz, (i32, i32, i32)),
+    "lg_loss_forward": (C.c_int, (i32, i32, i32, vp, vp, vp, vp, u32, vp)),
+    "lg_loss_backward": (C.c_int, (i32, i32, i32, vp, vp, vp, vp, f32, vp, f32, vp, u32, vp)),
+    "lg_view_status": (C.c_int, (vp, i32, P(u32 * 4), vp)),
+    "lg_geom_visible_offset": (sz, (i32,)),
+    "lg_abi_version": (C.c_int, ()),
+    "lg_last_error": (C.c_char_p, ()),
+    "lg_build_id": (C.c_char_p, ()),
+    "lg_profile_read": (C.c_int, (P(lg_kernel_time), C.c_int)),
+    "lg_profile_reset": (None, ()),
+    "lg_last_stats": (C.c_int, (P(lg_stats),)),
+    "lg_debug_activations": (C.c_int, (i32, vp, vp, vp, vp, vp, vp, vp)),
+    "lg_debug_sort_temp_bytes": (sz, (i64,)),
+    "lg_debug_sort_keys": (C.c_int, (i64, vp, vp, i32, i32, vp, vp)),
+    "lg_debug_last_contributor": (C.c_int, (_VIEW, i32, vp, vp, vp, i64, vp, vp)),
+    "lg_debug_tile_lists": (C.c_int, (_VIEW, vp, i64, vp, vp, vp)),
+    "lg_debug_view_meta": (C.c_int, (_VIEW, vp, i64, vp, vp)),
+    "lg_debug_sort_orphan": (C.c_int, (i64, vp, vp, vp, vp)),
+    "lg_debug_reduce9": (C.c_int, (vp, vp, vp)),
+}
+EXPORTS = list(PROTOTYPES)
+
 _lib = None
 
 
@@ -114,117 +178,12 @@ def load():
             f"{LIB_PATH} is missing: the MI355X rasterizer has no CPU/PyTorch fallback. "
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950).")
     lib = C.CDLL(LIB_PATH)
-    vp, P = C.c_void_p, C.POINTER
-    lib.lg_abi_version.restype = C.c_int; lib.lg_abi_version.argtypes = []
-    if lib.lg_abi_version() != ABI_VERSION:
+    if lib.lg_abi_version() != ABI_VERSION:         # (ctypes' default prototype, int f(void), is this function's)
         raise RuntimeError(f"{LIB_PATH} reports ABI {lib.lg_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library "
                            "(python -c 'import __graft_entry__ as g; g.build()')")
-    lib.lg_geom_bytes.restype = C.c_size_t; lib.lg_geom_bytes.argtypes = [C.c_int32]
-    lib.lg_img_bytes.restype = C.c_size_t; lib.lg_img_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.lg_binning_bytes.restype = C.c_size_t; lib.lg_binning_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
-    lib.lg_backward_scratch_bytes.restype = C.c_size_t; lib.lg_backward_scratch_bytes.argtypes = [C.c_int32, C.c_int64]
-    lib.lg_forward.restype = C.c_int
-    lib.lg_forward.argtypes = [P(lg_view), P(lg_gaussians), vp, vp, ALLOC_FN, vp, vp, vp, P(vp), P(C.c_int64), vp]
-    lib.lg_forward_count.restype = C.c_int
-    lib.lg_forward_count.argtypes = [P(lg_view), P(lg_gaussians), vp, vp, ALLOC_FN, vp, C.c_int32, vp, vp, vp, vp, P(vp),
-                                     P(C.c_int64), vp]
-    lib.lg_backward.restype = C.c_int
-    lib.lg_backward.argtypes = [P(lg_view), P(lg_gaussians), vp, vp, vp, vp, C.c_int64, vp] + [vp] * 9 + [vp, vp]
-    lib.lg_backward_chunked.restype = C.c_int
-    lib.lg_backward_chunked.argtypes = [P(lg_view), P(lg_gaussians), vp, vp, vp, vp, C.c_int64, vp] + [vp] * 9 + [vp, vp, C.c_int32, CHUNK_FN, vp]
-    lib.lg_backward_abs.restype = C.c_int
-    lib.lg_backward_abs.argtypes = lib.lg_backward_chunked.argtypes + [vp]
-    lib.lg_score_from_count.restype = C.c_int
-    lib.lg_score_from_count.argtypes = [C.c_int32, vp, vp, vp, vp]
-    lib.lg_loss_state_bytes.restype = C.c_size_t; lib.lg_loss_state_bytes.argtypes = [C.c_int32] * 3
-    lib.lg_loss_forward.restype = C.c_int
-    lib.lg_loss_forward.argtypes = [C.c_int32] * 3 + [vp, vp, vp, vp, C.c_uint32, vp]
-    lib.lg_loss_backward.restype = C.c_int
-    lib.lg_loss_backward.argtypes = [C.c_int32] * 3 + [vp, vp, vp, vp, C.c_float, vp, C.c_float, vp, C.c_uint32, vp]
-    lib.lg_prune_scratch_bytes.restype = C.c_size_t; lib.lg_prune_scratch_bytes.argtypes = [C.c_int32]
-    lib.lg_prune_epilogue.restype = C.c_int
-    lib.lg_prune_epilogue.argtypes = [C.c_int32, vp, vp, C.c_float, C.c_double, vp, vp, vp, vp, C.c_uint32, vp]
-    lib.lg_knn_scratch_bytes.restype = C.c_size_t; lib.lg_knn_scratch_bytes.argtypes = [C.c_int32]
-    lib.lg_knn3_mean_dist2.restype = C.c_int
-    lib.lg_knn3_mean_dist2.argtypes = [C.c_int32, vp, vp, vp, C.c_uint32, vp]
-    lib.lg_sh_grad_from_rgb.restype = C.c_int
-    lib.lg_sh_grad_from_rgb.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_int64, C.c_float, C.c_int32, vp, vp, vp]
-    lib.lg_ordered_sum.restype = C.c_int
-    lib.lg_ordered_sum.argtypes = [C.c_int32, C.c_int64, vp, C.c_int64, vp, vp]
-    lib.lg_forward_bounded.restype = C.c_int
-    lib.lg_forward_bounded.argtypes = [P(lg_view), P(lg_gaussians), vp, vp, vp, C.c_int64, C.c_float, C.c_int32, vp, vp, vp, vp, vp,
-                                       P(C.c_uint32 * 4), vp]
-    lib.lg_select_mask.restype = C.c_int
-    lib.lg_select_mask.argtypes = [C.c_int32, vp, C.c_int64, vp, vp, vp, vp]
-    lib.lg_compact_scratch_bytes.restype = C.c_size_t; lib.lg_compact_scratch_bytes.argtypes = [C.c_int32]
-    lib.lg_compact_plan.restype = C.c_int
-    lib.lg_compact_plan.argtypes = [C.c_int32, vp, vp, vp, vp, vp]
-    lib.lg_compact_rows.restype = C.c_int
-    lib.lg_compact_rows.argtypes = [C.c_int32, vp, C.c_int32, P(vp), P(vp), P(C.c_int32), vp]
-    lib.lg_vq_scratch_bytes.restype = C.c_size_t; lib.lg_vq_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.lg_vq_nearest.restype = C.c_int
-    lib.lg_vq_nearest.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_uint32, vp]
-    lib.lg_vq_ema_scratch_bytes.restype = C.c_size_t; lib.lg_vq_ema_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.lg_vq_ema_step.restype = C.c_int
-    lib.lg_vq_ema_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, C.c_uint32, vp]
-    lib.lg_vq_colors.restype = C.c_int
-    lib.lg_vq_colors.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, vp, C.c_uint32, vp]
-    lib.lg_vq_code_index_bytes.restype = C.c_size_t; lib.lg_vq_code_index_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.lg_vq_code_index_scratch_bytes.restype = C.c_size_t; lib.lg_vq_code_index_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.lg_vq_code_index.restype = C.c_int
-    lib.lg_vq_code_index.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp]
-    lib.lg_vq_colors_bwd_scratch_bytes.restype = C.c_size_t; lib.lg_vq_colors_bwd_scratch_bytes.argtypes = [C.c_int32] * 3
-    lib.lg_vq_colors_bwd.restype = C.c_int
-    lib.lg_vq_colors_bwd.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp,
-                                     C.c_uint32, vp]
-    lib.lg_adam_step.restype = C.c_int
-    lib.lg_adam_step.argtypes = [C.c_int32, P(lg_adam_tensor), C.c_double, C.c_double, C.c_double, C.c_uint32, vp]
-    lib.lg_adam_step_rows.restype = C.c_int
-    lib.lg_adam_step_rows.argtypes = [C.c_int32, P(lg_adam_rows_tensor), C.c_double, C.c_double, C.c_double, C.c_uint32, vp]
-    lib.lg_densify_scratch_bytes.restype = C.c_size_t; lib.lg_densify_scratch_bytes.argtypes = [C.c_int32]
-    lib.lg_densify_stats.restype = C.c_int
-    lib.lg_densify_stats.argtypes = [C.c_int32, vp, vp, vp, vp, vp, vp, C.c_uint32, vp]
-    lib.lg_densify_plan.restype = C.c_int
-    lib.lg_densify_plan.argtypes = [C.c_int32, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp, vp, C.c_uint32, vp]
-    lib.lg_densify_rows.restype = C.c_int
-    lib.lg_densify_rows.argtypes = [C.c_int32, C.c_int64, vp, vp, C.c_int32, P(lg_densify_tensor), vp, vp, vp, C.c_int64, C.c_uint32, vp]
-    lib.lg_features_scratch_bytes.restype = C.c_size_t; lib.lg_features_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
-    lib.lg_blend_features.restype = C.c_int
-    lib.lg_blend_features.argtypes = [P(lg_view), C.c_int32, vp, vp, C.c_int64, vp, C.c_int32, vp, vp, vp, vp]
-    lib.lg_blend_features_backward.restype = C.c_int
-    lib.lg_blend_features_backward.argtypes = [P(lg_view), C.c_int32, vp, vp, C.c_int64, vp, C.c_int32, vp, vp, vp]
-    lib.lg_backward_features_scratch_bytes.restype = C.c_size_t; lib.lg_backward_features_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
-    lib.lg_backward_features.restype = C.c_int
-    lib.lg_backward_features.argtypes = ([P(lg_view), P(lg_gaussians), vp, vp, vp, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp] + [vp] * 9
-                                         + [vp, vp, vp])
-    lib.lg_camera_scratch_bytes.restype = C.c_size_t; lib.lg_camera_scratch_bytes.argtypes = [C.c_int32]
-    lib.lg_backward_camera.restype = C.c_int
-    lib.lg_backward_camera.argtypes = [P(lg_view), P(lg_gaussians), vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
-    lib.lg_filter3d_scratch_bytes.restype = C.c_size_t; lib.lg_filter3d_scratch_bytes.argtypes = [C.c_int32]
-    lib.lg_filter3d_update.restype = C.c_int
-    lib.lg_filter3d_update.argtypes = [C.c_int32, vp, C.c_int32, vp, vp, vp, vp, C.c_uint32, vp]
-    lib.lg_filter3d_apply.restype = C.c_int
-    lib.lg_filter3d_apply.argtypes = [C.c_int32, vp, vp, vp, vp, vp, C.c_uint32, vp]
-    lib.lg_filter3d_apply_bwd.restype = C.c_int
-    lib.lg_filter3d_apply_bwd.argtypes = [C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp]
-    lib.lg_debug_sort_temp_bytes.restype = C.c_size_t; lib.lg_debug_sort_temp_bytes.argtypes = [C.c_int64]
-    lib.lg_debug_sort_keys.restype = C.c_int
-    lib.lg_debug_sort_keys.argtypes = [C.c_int64, vp, vp, C.c_int32, C.c_int32, vp, vp]
-    lib.lg_debug_activations.restype = C.c_int; lib.lg_debug_activations.argtypes = [C.c_int32, vp, vp, vp, vp, vp, vp, vp]
-    lib.lg_debug_reduce9.restype = C.c_int; lib.lg_debug_reduce9.argtypes = [vp, vp, vp]
-    lib.lg_abi_version.restype = C.c_int; lib.lg_abi_version.argtypes = []
-    lib.lg_last_error.restype = C.c_char_p; lib.lg_last_error.argtypes = []
-    lib.lg_build_id.restype = C.c_char_p; lib.lg_build_id.argtypes = []
-    lib.lg_view_status.restype = C.c_int; lib.lg_view_status.argtypes = [vp, C.c_int32, P(C.c_uint32 * 4), vp]
-    lib.lg_debug_last_contributor.restype = C.c_int
-    lib.lg_debug_last_contributor.argtypes = [P(lg_view), C.c_int32, vp, vp, vp, C.c_int64, vp, vp]
-    lib.lg_debug_sort_orphan.restype = C.c_int; lib.lg_debug_sort_orphan.argtypes = [C.c_int64, vp, vp, vp, vp]
-    lib.lg_geom_visible_offset.restype = C.c_size_t; lib.lg_geom_visible_offset.argtypes = [C.c_int32]
-    lib.lg_debug_view_meta.restype = C.c_int; lib.lg_debug_view_meta.argtypes = [P(lg_view), vp, C.c_int64, vp, vp]
-    lib.lg_debug_tile_lists.restype = C.c_int; lib.lg_debug_tile_lists.argtypes = [P(lg_view), vp, C.c_int64, vp, vp, vp]
-    lib.lg_profile_read.restype = C.c_int; lib.lg_profile_read.argtypes = [P(lg_kernel_time), C.c_int]
-    lib.lg_profile_reset.restype = None; lib.lg_profile_reset.argtypes = []
-    lib.lg_last_stats.restype = C.c_int; lib.lg_last_stats.argtypes = [P(lg_stats)]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = lib
     return lib
 
@@ -238,6 +197,25 @@ def check(rc):
     if rc == LG_ERR_INVALID_ARGUMENT:
         raise Exception(msg)
     raise RuntimeError(f"lightgaussian_hip error {rc}: {msg}")
+
+
+def ptr(t):
+    """The device address of a tensor as a pointer argument; None (NULL) for None."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(dev=None):
+    """The current stream of `dev` (None: of the current device) as the `stream` argument of a library call."""
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def scratch(nbytes, dev):
+    """A uint8 device buffer for a lg_*_bytes() answer (at least one byte, so that its address is never NULL)."""
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+
+
+def profile_flag(on):
+    return FLAG_PROFILE if on else 0
 
 
 def build_id():

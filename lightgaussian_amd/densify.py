@@ -35,7 +35,6 @@ backend="torch" is the same contract in plain torch ops (CPU tensors too): the f
 back to it, with one warning per reason, for: thr_g <= 0, parameters that are not float32 on the GPU, more than one parameter per
 group, N >= 2^30.  The optimizer surgery is prune.prune_points': new nn.Parameters, the state re-keyed.
 set_profile(True) records the launches under "densify_stats", "densify_plan", "densify_rows" (_lib.profile_read)."""
-import ctypes as C
 import warnings
 
 import torch
@@ -55,11 +54,7 @@ def set_profile(on):
 
 
 def _flags():
-    return _lib.FLAG_PROFILE if _PROFILE[0] else 0
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    return _lib.profile_flag(_PROFILE[0])
 
 
 def _warn_once(model, what, reason):
@@ -141,9 +136,8 @@ def accumulate_stats(model, viewspace_points, update_filter, radii=None, absgrad
         dev = grad.device
         mr = model.max_radii2D if radii is not None else None
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().lg_densify_stats(n, grad.data_ptr(), update_filter.data_ptr(), None if radii is None else radii.data_ptr(),
-                                                    None if mr is None else mr.data_ptr(), model.xyz_gradient_accum.data_ptr(),
-                                                    model.denom.data_ptr(), _flags(), _stream(dev)))
+            _lib.check(_lib.load().lg_densify_stats(n, _lib.ptr(grad), _lib.ptr(update_filter), _lib.ptr(radii), _lib.ptr(mr),
+                                                    _lib.ptr(model.xyz_gradient_accum), _lib.ptr(model.denom), _flags(), _lib.stream(dev)))
         torch.autograd.graph.increment_version([model.xyz_gradient_accum, model.denom] + ([mr] if mr is not None else []))
 
 
@@ -256,13 +250,13 @@ def _rows_hip(model, th, entries, noise):
     opacity = model._opacity.detach().contiguous()
     accum, denom = model.xyz_gradient_accum.contiguous(), model.denom.contiguous()
     with torch.cuda.device(dev):
-        stream = _stream(dev)
+        stream = _lib.stream(dev)
         table_map = torch.empty((2 * max(n, 1), 2), dtype=torch.int32, device=dev)
         record = torch.empty(8, dtype=torch.int32, device=dev)
-        scratch = torch.empty(lib.lg_densify_scratch_bytes(n), dtype=torch.uint8, device=dev)
-        _lib.check(lib.lg_densify_plan(n, raw_s.data_ptr(), opacity.data_ptr(), accum.data_ptr(), denom.data_ptr(), th["thr_g"], th["thr_d"],
-                                       th["thr_w"], th["min_opacity"], int(th["use_extent"]), table_map.data_ptr(), record.data_ptr(),
-                                       scratch.data_ptr(), _flags(), stream))
+        scratch = _lib.scratch(lib.lg_densify_scratch_bytes(n), dev)
+        _lib.check(lib.lg_densify_plan(n, _lib.ptr(raw_s), _lib.ptr(opacity), _lib.ptr(accum), _lib.ptr(denom), th["thr_g"], th["thr_d"],
+                                       th["thr_w"], th["min_opacity"], int(th["use_extent"]), _lib.ptr(table_map), _lib.ptr(record),
+                                       _lib.ptr(scratch), _flags(), stream))
         n_out, n_keep, n_clone, n_s, n_child = record.cpu().tolist()[:5]          # the one host read of the call
         noise = _draw_noise(n_s, dev) if noise is None else _check_noise(noise, n_s, dev)
         out, rows = [], []
@@ -283,8 +277,8 @@ def _rows_hip(model, th, entries, noise):
             table = (_lib.lg_densify_tensor * len(part))()
             for row, (src, dst, words, role) in zip(table, part):
                 row.src, row.dst, row.row_words, row.role = None if src is None else src.data_ptr(), dst.data_ptr(), words, role
-            _lib.check(lib.lg_densify_rows(n, n_out, table_map.data_ptr(), record.data_ptr(), len(part), table, raw_q.data_ptr(), raw_s.data_ptr(),
-                                           noise.data_ptr() if n_s > 0 else None, 2 * n_s, _flags(), stream))
+            _lib.check(lib.lg_densify_rows(n, n_out, _lib.ptr(table_map), _lib.ptr(record), len(part), table, _lib.ptr(raw_q), _lib.ptr(raw_s),
+                                           _lib.ptr(noise) if n_s > 0 else None, 2 * n_s, _flags(), stream))
     return out, dict(N_out=n_out, n_keep=n_keep, n_clone=n_clone, n_s=n_s, n_child=n_child), book
 
 

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from . import rasterizer as _rasterizer
-from .rasterizer import _bare_view, _Call, _finish_forward, _GradSet, _native_forward, _prep, _ptr, _stream
+from .rasterizer import _bare_view, _Call, _finish_forward, _GradSet, _native_forward, _prep
 
 FEATURES_MAX = _lib.FEATURES_MAX
 _warned = [False]
@@ -64,8 +64,8 @@ def _forward_then_blend(features, bg_features, means3D, opacities, scales, rotat
         color, radii, _gc, _sc, geom, binning, img, num_rendered = _native_forward(lib, call, rs, False)
         out = torch.empty((c, h, w), dtype=torch.float32, device=dev)
         alpha = torch.empty((h, w), dtype=torch.float32, device=dev)
-        _lib.check(lib.lg_blend_features(C.byref(call.view), call.N, _ptr(geom), _ptr(binning), C.c_int64(num_rendered), _ptr(features), c,
-                                         _ptr(bg), _ptr(out), _ptr(alpha), _stream()))
+        _lib.check(lib.lg_blend_features(C.byref(call.view), call.N, _lib.ptr(geom), _lib.ptr(binning), C.c_int64(num_rendered), _lib.ptr(features), c,
+                                         _lib.ptr(bg), _lib.ptr(out), _lib.ptr(alpha), _lib.stream()))
     if binning is None:     # (an empty tensor stands in for it among the saved ones)
         binning = torch.empty(0, dtype=torch.uint8, device=dev)
     return opts, call, bg, (out, alpha, color, radii), (geom, binning, img), num_rendered
@@ -98,9 +98,9 @@ class _BlendFeatures(torch.autograd.Function):
         view = _bare_view(ctx.raster_settings, *ctx.view_flags)
         with torch.cuda.device(dev):
             d_feat = torch.empty((n, c), dtype=torch.float32, device=dev)
-            scratch = torch.empty(max(int(lib.lg_features_scratch_bytes(n, ctx.num_rendered, c)), 1), dtype=torch.uint8, device=dev)
-            _lib.check(lib.lg_blend_features_backward(C.byref(view), n, _ptr(geom), _ptr(binning) if binning.numel() else None,
-                                                      C.c_int64(ctx.num_rendered), _ptr(grad_out), c, _ptr(d_feat), _ptr(scratch), _stream()))
+            scratch = _lib.scratch(lib.lg_features_scratch_bytes(n, ctx.num_rendered, c), dev)
+            _lib.check(lib.lg_blend_features_backward(C.byref(view), n, _lib.ptr(geom), _lib.ptr(binning) if binning.numel() else None,
+                                                      C.c_int64(ctx.num_rendered), _lib.ptr(grad_out), c, _lib.ptr(d_feat), _lib.ptr(scratch), _lib.stream()))
         return (d_feat,) + none
 
 
@@ -134,11 +134,11 @@ class _BlendFeaturesGeom(torch.autograd.Function):
             g = _GradSet(call, new=new)
             g_feat = new((n, c), dtype=torch.float32, device=dev) if (ctx.needs_input_grad[0] and grad_out is not None) else None
             if run:
-                scratch = torch.empty(max(int(lib.lg_backward_features_scratch_bytes(n, ctx.num_rendered, c)), 1), dtype=torch.uint8, device=dev)
+                scratch = _lib.scratch(lib.lg_backward_features_scratch_bytes(n, ctx.num_rendered, c), dev)
                 _lib.check(lib.lg_backward_features(
-                    C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img),
-                    C.c_int64(ctx.num_rendered), _ptr(grad_color), _ptr(features), c, _ptr(bg) if bg.numel() else None, _ptr(grad_out),
-                    _ptr(grad_alpha), *g.ptrs(), _ptr(g_feat), _ptr(scratch), _stream()))
+                    C.byref(call.view), C.byref(call.g), _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(img),
+                    C.c_int64(ctx.num_rendered), _lib.ptr(grad_color), _lib.ptr(features), c, _lib.ptr(bg) if bg.numel() else None, _lib.ptr(grad_out),
+                    _lib.ptr(grad_alpha), *g.ptrs(), _lib.ptr(g_feat), _lib.ptr(scratch), _lib.stream()))
         return (g_feat, None, g["means3D"], g["means2D"], g["opacity"], g["scales"], g["rotations"], g["cov3D"], g["shs"], g["colors"],
                 None, None)
 

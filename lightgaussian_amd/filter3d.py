@@ -21,7 +21,7 @@ import math
 import torch
 
 from . import _lib
-from .rasterizer import _prep, _ptr, _stream, option_value
+from .rasterizer import _prep, option_value
 
 
 def camera_table(cameras):
@@ -58,10 +58,10 @@ def compute_filter_3d(xyz, cameras, *, return_seen=False):
     seen = torch.empty((N,), dtype=torch.uint8, device=dev) if return_seen else None
     if N > 0:
         with torch.cuda.device(dev):
-            scratch = torch.empty(lib.lg_filter3d_scratch_bytes(N), dtype=torch.uint8, device=dev)
-            flags = _lib.FLAG_PROFILE if option_value("profile") else 0
-            _lib.check(lib.lg_filter3d_update(N, _ptr(means), int(table.shape[0]), _ptr(table), _ptr(out), _ptr(seen), _ptr(scratch), flags,
-                                              _stream()))
+            scratch = _lib.scratch(lib.lg_filter3d_scratch_bytes(N), dev)
+            flags = _lib.profile_flag(option_value("profile"))
+            _lib.check(lib.lg_filter3d_update(N, _lib.ptr(means), int(table.shape[0]), _lib.ptr(table), _lib.ptr(out), _lib.ptr(seen),
+                                              _lib.ptr(scratch), flags, _lib.stream()))
     return (out, seen.view(torch.bool)) if return_seen else out
 
 
@@ -80,14 +80,15 @@ class _ApplyFilter3D(torch.autograd.Function):
                              f"(got {tuple(scaling.shape)}, {tuple(opacity.shape)}, {tuple(filter_3d.shape)})")
         f32 = dict(dtype=torch.float32, device=dev)
         out_s, out_o = torch.empty((N, 3), **f32), torch.empty(opacity.shape, **f32)
-        ctx.flags = (_lib.FILTER3D_RAW if raw else 0) | (_lib.FLAG_PROFILE if option_value("profile") else 0)
+        ctx.flags = (_lib.FILTER3D_RAW if raw else 0) | _lib.profile_flag(option_value("profile"))
         ctx.opacity_shape = tuple(opacity.shape)
         ctx.set_materialize_grads(False)
         if N == 0:                      # (an empty model: nothing to launch, nothing to save)
             return out_s, out_o
         s, o, f = _prep(scaling.detach(), dev), _prep(opacity.detach(), dev), _prep(filter_3d.detach(), dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.lg_filter3d_apply(N, _ptr(s), _ptr(o), _ptr(f), _ptr(out_s), _ptr(out_o), ctx.flags, _stream()))
+            _lib.check(lib.lg_filter3d_apply(N, _lib.ptr(s), _lib.ptr(o), _lib.ptr(f), _lib.ptr(out_s), _lib.ptr(out_o), ctx.flags,
+                                             _lib.stream()))
         ctx.save_for_backward(s, o, f)
         return out_s, out_o
 
@@ -106,7 +107,8 @@ class _ApplyFilter3D(torch.autograd.Function):
         g_o = torch.zeros(ctx.opacity_shape, **f32) if g_o is None else _prep(g_o, dev)
         d_s, d_o = torch.empty((N, 3), **f32), torch.empty(ctx.opacity_shape, **f32)
         with torch.cuda.device(dev):
-            _lib.check(lib.lg_filter3d_apply_bwd(N, _ptr(s), _ptr(o), _ptr(f), _ptr(g_s), _ptr(g_o), _ptr(d_s), _ptr(d_o), ctx.flags, _stream()))
+            _lib.check(lib.lg_filter3d_apply_bwd(N, _lib.ptr(s), _lib.ptr(o), _lib.ptr(f), _lib.ptr(g_s), _lib.ptr(g_o), _lib.ptr(d_s),
+                                                 _lib.ptr(d_o), ctx.flags, _lib.stream()))
         return d_s, d_o, None, None
 
 

@@ -12,7 +12,6 @@ filters); calling l1_loss(image, gt) and then ssim(image, gt) on the same tensor
 pattern -- runs the kernel once: the second call returns the other output of the same autograd node.
 There is no PyTorch fallback: CPU tensors raise.
 """
-import ctypes as C
 import threading
 import weakref
 
@@ -23,10 +22,7 @@ from . import rasterizer as _rast
 
 
 def _flags():
-    f = 0
-    if _rast.resolve_options().get("profile"):
-        f |= _lib.FLAG_PROFILE
-    return f
+    return _lib.profile_flag(_rast.option_value("profile"))
 
 
 class _L1SSIM(torch.autograd.Function):
@@ -37,11 +33,10 @@ class _L1SSIM(torch.autograd.Function):
         flags = _flags() | (_lib.FLAG_L1_ONLY if l1_only else 0)
         H, W = img.shape[-2], img.shape[-1]
         planes = img.numel() // (H * W)
-        state = torch.empty(lib.lg_loss_state_bytes(planes, H, W), dtype=torch.uint8, device=img.device)
+        state = _lib.scratch(lib.lg_loss_state_bytes(planes, H, W), img.device)
         out = torch.empty(2, dtype=torch.float32, device=img.device)
-        stream = torch.cuda.current_stream(img.device).cuda_stream
-        _lib.check(lib.lg_loss_forward(planes, H, W, img.data_ptr(), gt.data_ptr(), state.data_ptr(), out.data_ptr(), flags,
-                                       C.c_void_p(stream)))
+        _lib.check(lib.lg_loss_forward(planes, H, W, _lib.ptr(img), _lib.ptr(gt), _lib.ptr(state), _lib.ptr(out), flags,
+                                       _lib.stream(img.device)))
         ctx.save_for_backward(img, gt, state)
         ctx.set_materialize_grads(False)     # an unused output's gradient arrives as None (the backward handles it), not as a filled zero
         ctx.dims = (planes, H, W)
@@ -57,11 +52,8 @@ class _L1SSIM(torch.autograd.Function):
         lib = _lib.load()
         grad = torch.empty_like(img)
         keep = [None if g is None else g.contiguous().float() for g in (g_l1, g_ssim)]
-        stream = torch.cuda.current_stream(img.device).cuda_stream
-        _lib.check(lib.lg_loss_backward(planes, H, W, img.data_ptr(), gt.data_ptr(), state.data_ptr(),
-                                        None if keep[0] is None else C.c_void_p(keep[0].data_ptr()), 1.0,
-                                        None if keep[1] is None else C.c_void_p(keep[1].data_ptr()), 1.0,
-                                        grad.data_ptr(), _flags() | (_lib.FLAG_L1_ONLY if ctx.l1_only else 0), C.c_void_p(stream)))
+        _lib.check(lib.lg_loss_backward(planes, H, W, _lib.ptr(img), _lib.ptr(gt), _lib.ptr(state), _lib.ptr(keep[0]), 1.0, _lib.ptr(keep[1]), 1.0,
+                                        _lib.ptr(grad), _flags() | (_lib.FLAG_L1_ONLY if ctx.l1_only else 0), _lib.stream(img.device)))
         return grad, None, None
 
 

@@ -179,10 +179,10 @@ class _HipStep:
                 row.numel, row.lr, row.weight_decay, row.step = p.numel(), lr, wd, step
                 if visible is not None and p.dim() >= 1 and p.shape[0] == visible.shape[0]:     # (else a dense entry of the same launch)
                     entry.row_mask, entry.rows = visible.data_ptr(), visible.shape[0]
-            flags = (_lib.ADAM_DECOUPLED_WD if decoupled else 0) | (_lib.FLAG_PROFILE if _PROFILE[0] else 0)
+            flags = (_lib.ADAM_DECOUPLED_WD if decoupled else 0) | _lib.profile_flag(_PROFILE[0])
             with torch.cuda.device(index):
                 call = lib.lg_adam_step if visible is None else lib.lg_adam_step_rows
-                _lib.check(call(len(entries), table, beta1, beta2, eps, flags, torch.cuda.current_stream().cuda_stream))
+                _lib.check(call(len(entries), table, beta1, beta2, eps, flags, _lib.stream()))
             torch.autograd.graph.increment_version([t for e in entries for t in e[:1] + e[2:4]])
         return loss
 

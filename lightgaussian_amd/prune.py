@@ -20,6 +20,7 @@ replicated, the camera list split into contiguous blocks, and
 import torch
 import torch.distributed as dist
 
+from . import _lib
 from .gaussian_renderer import count_render
 
 
@@ -64,16 +65,13 @@ def prune_mask_select(percent, import_score):
 def _select_mask(values, rank, want_mask=True):
     """rank-th smallest element (0-based) of a 1-D float32 device tensor by the HIP radix select (lg_select_mask: four 8-bit
     histogram passes, no sort, no host read-back) and, optionally, mask = values <= that element.  Returns (value [1], mask)."""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
     n = values.shape[0]
     dev = values.device
     out = torch.empty(1, dtype=torch.float32, device=dev)
     mask = torch.empty(n, dtype=torch.uint8, device=dev) if want_mask else None
-    scratch = torch.empty(lib.lg_prune_scratch_bytes(n), dtype=torch.uint8, device=dev)
-    _lib.check(lib.lg_select_mask(n, values.data_ptr(), int(rank), None if mask is None else mask.data_ptr(), out.data_ptr(),
-                                  scratch.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    scratch = _lib.scratch(lib.lg_prune_scratch_bytes(n), dev)
+    _lib.check(lib.lg_select_mask(n, _lib.ptr(values), int(rank), _lib.ptr(mask), _lib.ptr(out), _lib.ptr(scratch), _lib.stream(dev)))
     return out, mask
 
 
@@ -90,8 +88,6 @@ def prune_epilogue(gaussians, imp_list, v_pow, percent, fused_pow=False):
         Its v_list is within 1 ulp of torch.pow's (the device powf and torch's pow kernel round differently in the last
         bit), so elements exactly at the threshold can fall on the other side: NOT the reference's mask, bit for bit.
     CUDA/HIP tensors only -- no fallback."""
-    import ctypes as C
-    from . import _lib
     from . import rasterizer
     with torch.no_grad():
         scaling = gaussians.get_scaling.detach().contiguous().float()
@@ -118,11 +114,10 @@ def prune_epilogue(gaussians, imp_list, v_pow, percent, fused_pow=False):
     v_list = torch.empty(N, dtype=torch.float32, device=dev)
     mask = torch.empty(N, dtype=torch.uint8, device=dev)
     thresholds = torch.empty(2, dtype=torch.float32, device=dev)
-    scratch = torch.empty(lib.lg_prune_scratch_bytes(N), dtype=torch.uint8, device=dev)
-    flags = _lib.FLAG_PROFILE if rasterizer.resolve_options()["profile"] else 0
-    _lib.check(lib.lg_prune_epilogue(N, scaling.data_ptr(), imp.data_ptr(), float(v_pow), float(percent), v_list.data_ptr(),
-                                     mask.data_ptr(), thresholds.data_ptr(), scratch.data_ptr(), flags,
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    scratch = _lib.scratch(lib.lg_prune_scratch_bytes(N), dev)
+    flags = _lib.profile_flag(rasterizer.option_value("profile"))
+    _lib.check(lib.lg_prune_epilogue(N, _lib.ptr(scaling), _lib.ptr(imp), float(v_pow), float(percent), _lib.ptr(v_list),
+                                     _lib.ptr(mask), _lib.ptr(thresholds), _lib.ptr(scratch), flags, _lib.stream(dev)))
     return v_list, mask.bool(), thresholds
 
 
@@ -292,10 +287,8 @@ def _ordered_sum(rows, out=None):
     if out is None:
         out = torch.empty(rows.shape[1], dtype=rows.dtype, device=rows.device)
     if rows.is_cuda and rows.dtype == torch.float32 and rows.stride(1) == 1 and out.is_contiguous():
-        import ctypes as C
-        from . import _lib
-        _lib.check(_lib.load().lg_ordered_sum(rows.shape[0], rows.shape[1], rows.data_ptr(), rows.stride(0), out.data_ptr(),
-                                              C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)))
+        _lib.check(_lib.load().lg_ordered_sum(rows.shape[0], rows.shape[1], _lib.ptr(rows), rows.stride(0), _lib.ptr(out),
+                                              _lib.stream(rows.device)))
         return out
     if out.data_ptr() != rows[0].data_ptr():
         out.copy_(rows[0])
@@ -437,7 +430,6 @@ def compact_tensors(tensors, keep):
     tensor.  Row order is preserved: results equal t[keep] bit for bit.  HIP tensors only (no fallback); tensors whose rows
     are not a multiple of 4 bytes are indexed by torch with the same destination map."""
     import ctypes as C
-    from . import _lib
     tensors = list(tensors)
     if not tensors:
         return []
@@ -448,12 +440,12 @@ def compact_tensors(tensors, keep):
     if any(t.shape[0] != N or t.device != dev for t in tensors) or keep.shape[0] != N:
         raise ValueError("compact_tensors: all tensors and the mask must share the first dimension and the device")
     lib = _lib.load()
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = _lib.stream(dev)
     keep8 = keep.reshape(-1).to(device=dev, dtype=torch.uint8).contiguous()
     dest = torch.empty(N, dtype=torch.int32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    scratch = torch.empty(lib.lg_compact_scratch_bytes(N), dtype=torch.uint8, device=dev)
-    _lib.check(lib.lg_compact_plan(N, keep8.data_ptr(), dest.data_ptr(), count.data_ptr(), scratch.data_ptr(), stream))
+    scratch = _lib.scratch(lib.lg_compact_scratch_bytes(N), dev)
+    _lib.check(lib.lg_compact_plan(N, _lib.ptr(keep8), _lib.ptr(dest), _lib.ptr(count), _lib.ptr(scratch), stream))
     n_keep = int(count.item())                       # the one host read of the whole compaction
     srcs = [t.detach().contiguous() for t in tensors]
     outs = [torch.empty((n_keep,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in srcs]
@@ -468,7 +460,7 @@ def compact_tensors(tensors, keep):
         dst_arr = (C.c_void_p * n)(*[outs[i].data_ptr() if n_keep else srcs[i].data_ptr() for i in part])
         rb_arr = (C.c_int32 * n)(*[srcs[i][0].numel() * srcs[i].element_size() for i in part])
         if n_keep:
-            _lib.check(lib.lg_compact_rows(N, dest.data_ptr(), n, src_arr, dst_arr, rb_arr, stream))
+            _lib.check(lib.lg_compact_rows(N, _lib.ptr(dest), n, src_arr, dst_arr, rb_arr, stream))
     return outs
 
 

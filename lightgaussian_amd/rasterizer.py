@@ -50,6 +50,7 @@ _OPTIONS = {"weight_policy": _lib.WEIGHT_OPACITY, "fast_exp": True, "profile": F
             "sh_jacobian": True, "narrow_key": False, "sort_all_bits": False, "k1_lds": False, "count_wide_band": False}
 _PER_CALL_ONLY = ("pending", "tag", "status_override", "differentiated", "sh_grad_sink", "score_out", "count_sum")
 _LONG_TILES = ("serial", "auto", "parallel")
+_STRICT_BOOL = ("camera_grad", "antialiasing", "filter_3d", "absgrad")      # options that refuse anything but True / False
 _tls = threading.local()
 
 
@@ -74,14 +75,8 @@ def _validate(name, value):
         raise ValueError(f"long_tiles must be one of {_LONG_TILES}")
     if name == "count_long_tiles" and value not in ("serial", "parallel"):
         raise ValueError("count_long_tiles must be 'serial' or 'parallel'")
-    if name == "camera_grad" and not isinstance(value, bool):
-        raise ValueError("camera_grad must be True or False")
-    if name == "antialiasing" and not isinstance(value, bool):
-        raise ValueError("antialiasing must be True or False")
-    if name == "filter_3d" and not isinstance(value, bool):
-        raise ValueError("filter_3d must be True or False")
-    if name == "absgrad" and not isinstance(value, bool):
-        raise ValueError("absgrad must be True or False")
+    if name in _STRICT_BOOL and not isinstance(value, bool):
+        raise ValueError(f"{name} must be True or False")
     if name == "segment_length" and (int(value) < 0 or (int(value) != 0 and (int(value) < 64 or int(value) % 64))):
         raise ValueError("segment_length must be 0 (library default, 512) or a multiple of 64")
 
@@ -229,7 +224,7 @@ def _call_backward(lib, args, grads_by_name, abs_out=None):
     the hook is not called again for this backward, and it is re-raised here once the library call has returned."""
     hook = _GRAD_CHUNKS["hook"]
     if hook is None:
-        return lib.lg_backward(*args) if abs_out is None else lib.lg_backward_abs(*args, 1, _lib.CHUNK_FN(), None, _ptr(abs_out))      # (a NULL callback)
+        return lib.lg_backward(*args) if abs_out is None else lib.lg_backward_abs(*args, 1, _lib.CHUNK_FN(), None, _lib.ptr(abs_out))      # (a NULL callback)
     errors = []
 
     def _cb(_user, first, count):
@@ -244,18 +239,13 @@ def _call_backward(lib, args, grads_by_name, abs_out=None):
     if abs_out is None:
         rc = lib.lg_backward_chunked(*args, int(_GRAD_CHUNKS["chunks"]), cb, None)
     else:
-        rc = lib.lg_backward_abs(*args, int(_GRAD_CHUNKS["chunks"]), cb, None, _ptr(abs_out))
+        rc = lib.lg_backward_abs(*args, int(_GRAD_CHUNKS["chunks"]), cb, None, _lib.ptr(abs_out))
     if errors:
         raise errors[0]
     return rc
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+_ptr, _stream = _lib.ptr, _lib.stream       # (importable from here as before)
 
 
 def _prep(t, dev):
@@ -302,8 +292,7 @@ class _Call:
             flags |= _lib.FLAG_DEBUG
         if opts["fast_exp"] and not exact:
             flags |= _lib.FLAG_FAST_EXP
-        if opts["profile"]:
-            flags |= _lib.FLAG_PROFILE
+        flags |= _lib.profile_flag(opts["profile"])
         if exact and opts["skip_color_in_count"]:
             flags |= _lib.FLAG_SKIP_COLOR
         if exact:       # count forward: its own switch (the training forward's long_tiles does not reach the significance pass)
@@ -324,10 +313,10 @@ class _Call:
         if opts.get("absgrad") and not exact:   # read by lg_backward_abs alone (_backward); every forward ignores it
             flags |= _lib.FLAG_ABSGRAD
         self.view = _lib.lg_view(int(rs.image_height), int(rs.image_width), float(rs.tanfovx), float(rs.tanfovy),
-                                 _ptr(self.bg), float(rs.scale_modifier), _ptr(self.vm), _ptr(self.pm),
-                                 int(rs.sh_degree), _ptr(self.cp), int(bool(rs.prefiltered)), flags, int(opts["segment_length"]))
-        self.g = _lib.lg_gaussians(N, M, _ptr(self.means3D), _ptr(self.sh), _ptr(self.colors), _ptr(self.opac),
-                                   _ptr(self.scales), _ptr(self.rots), _ptr(self.cov), _ptr(self.sh_rest))
+                                 _lib.ptr(self.bg), float(rs.scale_modifier), _lib.ptr(self.vm), _lib.ptr(self.pm),
+                                 int(rs.sh_degree), _lib.ptr(self.cp), int(bool(rs.prefiltered)), flags, int(opts["segment_length"]))
+        self.g = _lib.lg_gaussians(N, M, _lib.ptr(self.means3D), _lib.ptr(self.sh), _lib.ptr(self.colors), _lib.ptr(self.opac),
+                                   _lib.ptr(self.scales), _lib.ptr(self.rots), _lib.ptr(self.cov), _lib.ptr(self.sh_rest))
         self.N, self.M = N, M
 
 
@@ -442,7 +431,7 @@ def _native_forward(lib, call, rs, count):
     opts = call.opts
     dev, N = call.dev, call.N
     H, W = int(rs.image_height), int(rs.image_width)
-    stream = _stream()
+    stream = _lib.stream()
     u8 = dict(dtype=torch.uint8, device=dev)
     geom = torch.empty(lib.lg_geom_bytes(N), **u8)
     img = torch.empty(lib.lg_img_bytes(W, H), **u8)
@@ -476,9 +465,9 @@ def _native_forward(lib, call, rs, count):
             status = opts.get("status_override")
             if status is None:
                 status = torch.empty(4, dtype=torch.int32, device=dev)
-        rc = lib.lg_forward_bounded(C.byref(call.view), C.byref(call.g), _ptr(geom), _ptr(img), _ptr(binning), cap,
-                                    float(opts["max_depth"]), weight_policy_id(opts["weight_policy"]), _ptr(color), _ptr(radii),
-                                    _ptr(gcount), _ptr(score), _ptr(status), None if host is None else C.byref(host), stream)
+        rc = lib.lg_forward_bounded(C.byref(call.view), C.byref(call.g), _lib.ptr(geom), _lib.ptr(img), _lib.ptr(binning), cap,
+                                    float(opts["max_depth"]), weight_policy_id(opts["weight_policy"]), _lib.ptr(color), _lib.ptr(radii),
+                                    _lib.ptr(gcount), _lib.ptr(score), _lib.ptr(status), None if host is None else C.byref(host), stream)
         _lib.check(rc)
         if host is None:
             _note_pending(opts, status, key)
@@ -495,18 +484,18 @@ def _native_forward(lib, call, rs, count):
     holder = {}
 
     def _alloc(_user, nbytes):
-        holder["t"] = torch.empty(max(int(nbytes), 1), **u8)
+        holder["t"] = _lib.scratch(nbytes, dev)
         return holder["t"].data_ptr()
 
     cb = _lib.ALLOC_FN(_alloc)
     bin_ptr = C.c_void_p()
     R = C.c_int64(0)
     if count:
-        rc = lib.lg_forward_count(C.byref(call.view), C.byref(call.g), _ptr(geom), _ptr(img), cb, None,
-                                  weight_policy_id(opts["weight_policy"]), _ptr(color), _ptr(radii), _ptr(gcount), _ptr(score),
+        rc = lib.lg_forward_count(C.byref(call.view), C.byref(call.g), _lib.ptr(geom), _lib.ptr(img), cb, None,
+                                  weight_policy_id(opts["weight_policy"]), _lib.ptr(color), _lib.ptr(radii), _lib.ptr(gcount), _lib.ptr(score),
                                   C.byref(bin_ptr), C.byref(R), stream)
     else:
-        rc = lib.lg_forward(C.byref(call.view), C.byref(call.g), _ptr(geom), _ptr(img), cb, None, _ptr(color), _ptr(radii),
+        rc = lib.lg_forward(C.byref(call.view), C.byref(call.g), _lib.ptr(geom), _lib.ptr(img), cb, None, _lib.ptr(color), _lib.ptr(radii),
                             C.byref(bin_ptr), C.byref(R), stream)
     _lib.check(rc)
     if mode:
@@ -556,7 +545,7 @@ class _GradSet:
         return self.by_slot[slot]
 
     def ptrs(self):
-        return [_ptr(self.by_slot[s]) for s in self.SLOTS]
+        return [_lib.ptr(self.by_slot[s]) for s in self.SLOTS]
 
     def by_hook_name(self, raw):
         """name -> tensor, as the gradient-chunk hook receives them (dL/d(rgb) of an rgb_only backward is not a parameter's)."""
@@ -586,15 +575,15 @@ def _backward(ctx, call, grad_color, radii, geom, binning, img, raw):
         grad_color = torch.zeros((3, int(rs.image_height), int(rs.image_width)), dtype=torch.float32, device=dev)
     grad_color = _prep(grad_color, dev)
     with torch.cuda.device(dev):
-        stream = _stream()
+        stream = _lib.stream()
         sink = ctx.sh_sink if call.sh is not None else None
         g = _GradSet(call, rgb_only=sink is not None)
-        scratch = torch.empty(lib.lg_backward_scratch_bytes(call.N, ctx.num_rendered), dtype=torch.uint8, device=dev)
+        scratch = _lib.scratch(lib.lg_backward_scratch_bytes(call.N, ctx.num_rendered), dev)
         target = getattr(ctx, "absgrad_target", None)
         # (an empty model: torch hands out NULL for empty tensors, which lg_backward_abs refuses -- the plain call, and an empty .absgrad)
         abs_out = None if (target is None or call.N == 0) else torch.empty((call.N, 3), dtype=torch.float32, device=dev)
-        rc = _call_backward(lib, (C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img),
-                                  C.c_int64(ctx.num_rendered), _ptr(grad_color), *g.ptrs(), _ptr(scratch), stream), g.by_hook_name(raw), abs_out)
+        rc = _call_backward(lib, (C.byref(call.view), C.byref(call.g), _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(img),
+                                  C.c_int64(ctx.num_rendered), _lib.ptr(grad_color), *g.ptrs(), _lib.ptr(scratch), stream), g.by_hook_name(raw), abs_out)
         _lib.check(rc)
         if target is not None:
             # overwritten by every backward, never accumulated
@@ -683,9 +672,9 @@ def _camera_backward(lib, view, g, dev, radii, geom, binning, num_rendered, scra
     dL/dprojmatrix [4,4], dL/dcampos [3]) on the Gaussians' device."""
     f32 = dict(dtype=torch.float32, device=dev)
     g_vm, g_pm, g_cp = torch.empty((4, 4), **f32), torch.empty((4, 4), **f32), torch.empty((3,), **f32)
-    cam_scratch = torch.empty(lib.lg_camera_scratch_bytes(g.N), dtype=torch.uint8, device=dev)
-    rc = lib.lg_backward_camera(C.byref(view), C.byref(g), _ptr(radii), _ptr(geom), _ptr(binning), C.c_int64(num_rendered),
-                                _ptr(scratch), _ptr(g_vm), _ptr(g_pm), _ptr(g_cp), _ptr(cam_scratch), stream)
+    cam_scratch = _lib.scratch(lib.lg_camera_scratch_bytes(g.N), dev)
+    rc = lib.lg_backward_camera(C.byref(view), C.byref(g), _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning), C.c_int64(num_rendered),
+                                _lib.ptr(scratch), _lib.ptr(g_vm), _lib.ptr(g_pm), _lib.ptr(g_cp), _lib.ptr(cam_scratch), stream)
     _lib.check(rc)
     return g_vm, g_pm, g_cp
 
@@ -697,7 +686,7 @@ def _camera_empty_backward(ctx):
     view = _bare_view(rs, 0, ctx.opts["segment_length"])
     g = _lib.lg_gaussians(0, 0, None, None, None, None, None, None, None, None)
     with torch.cuda.device(dev):
-        return _camera_backward(_lib.load(), view, g, dev, None, None, None, 0, None, _stream())
+        return _camera_backward(_lib.load(), view, g, dev, None, None, None, 0, None, _lib.stream())
 
 
 def _with_camera_inputs(base, doc):

@@ -22,7 +22,6 @@ device in its compressed form and colors() / gaussian_renderer.render_compressed
 (TrainableCompressed: float32 masters of the rows and of the other attributes, a straight-through forward on their float16
 values, lg_vq_colors_bwd of csrc/lg_vq_color_bwd.h as the backward of colors()); repack() gives the model back as the seven arrays.
 """
-import ctypes as C
 import math
 import os
 
@@ -312,10 +311,10 @@ class CompressedGaussians:
             raise ValueError("colors: out must be a contiguous float32 [N, 3] tensor on the model's device")
         cam = camera_center.detach().to(device=dev, dtype=torch.float32).contiguous()
         lib = _lib.load()
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.lg_vq_colors(N, self.sh_dim // 3, D, self.xyz.data_ptr(), cam.data_ptr(), self._slot.data_ptr(),
-                                        self.rows.data_ptr(), self.row_stride, out.data_ptr(), int(flags), stream))
+            _lib.check(lib.lg_vq_colors(N, self.sh_dim // 3, D, _lib.ptr(self.xyz), _lib.ptr(cam), _lib.ptr(self._slot),
+                                        _lib.ptr(self.rows), self.row_stride, _lib.ptr(out), int(flags), stream))
         return out
 
 
@@ -348,12 +347,12 @@ class _VqColors(torch.autograd.Function):
         lib = _lib.load()
         drows = torch.empty((m.rows.shape[0], d), dtype=torch.float32, device=dev)
         dxyz = torch.empty((N, 3), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-        scratch = torch.empty(max(int(lib.lg_vq_colors_bwd_scratch_bytes(N, d // 3, K)), 16), dtype=torch.uint8, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        scratch = _lib.scratch(lib.lg_vq_colors_bwd_scratch_bytes(N, d // 3, K), dev)
+        stream = _lib.stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.lg_vq_colors_bwd(N, d // 3, ctx.D, K, m.rows.shape[0], m._xyz.data_ptr(), ctx.cam.data_ptr(), m._slot.data_ptr(),
-                                            m.rows.data_ptr(), m.row_stride, g.data_ptr(), m._index.data_ptr(), drows.data_ptr(),
-                                            dxyz.data_ptr() if dxyz is not None else None, scratch.data_ptr(), 0, stream))
+            _lib.check(lib.lg_vq_colors_bwd(N, d // 3, ctx.D, K, m.rows.shape[0], _lib.ptr(m._xyz), _lib.ptr(ctx.cam), _lib.ptr(m._slot),
+                                            _lib.ptr(m.rows), m.row_stride, _lib.ptr(g), _lib.ptr(m._index), _lib.ptr(drows),
+                                            _lib.ptr(dxyz), _lib.ptr(scratch), 0, stream))
         return (drows if ctx.needs_input_grad[0] else None), dxyz, None, None, None
 
 
@@ -407,11 +406,11 @@ class TrainableCompressed(CompressedGaussians):
         nbytes = int(lib.lg_vq_code_index_bytes(N, K))
         if nbytes == 0:
             raise ValueError(f"trainable: no code index for N = {N}, K = {K}")
-        self._index = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        scratch = torch.empty(max(int(lib.lg_vq_code_index_scratch_bytes(N, K)), 16), dtype=torch.uint8, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        self._index = _lib.scratch(nbytes, dev)
+        scratch = _lib.scratch(lib.lg_vq_code_index_scratch_bytes(N, K), dev)
+        stream = _lib.stream(dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.lg_vq_code_index(N, K, self._slot.data_ptr(), self._index.data_ptr(), scratch.data_ptr(), stream))
+            _lib.check(lib.lg_vq_code_index(N, K, _lib.ptr(self._slot), _lib.ptr(self._index), _lib.ptr(scratch), stream))
 
     def parameters(self):
         """The tensors named in trainable(params=...), for an optimizer."""

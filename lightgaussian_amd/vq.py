@@ -13,8 +13,6 @@ reference writes as F.one_hot(embed_ind, K) -- n x K -- and a dense einsum again
 rows (stable radix sort of (code, row)) and adds them in ascending row order: no n x K intermediate, no float atomics, bit-
 reproducible.  train_codebook() is the loop of vectree/vectree.py:176-204 around it in this package's own words.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -38,12 +36,12 @@ def nearest_code(flatten, embed):
         raise Exception(f"nearest_code: unsupported shape (K={K}, d={d}; need K >= 1, 1 <= d <= 63)")
     dev = x.device
     out = torch.empty((h, n), dtype=torch.int32, device=dev)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    scratch = _lib.scratch(nbytes, dev)
+    stream = _lib.stream(dev)
     for i in range(h):
         xi = x[i].detach().contiguous().float()
         ci = cb[i].detach().contiguous().float()
-        _lib.check(lib.lg_vq_nearest(n, d, K, xi.data_ptr(), ci.data_ptr(), out[i].data_ptr(), scratch.data_ptr(), 0, stream))
+        _lib.check(lib.lg_vq_nearest(n, d, K, _lib.ptr(xi), _lib.ptr(ci), _lib.ptr(out[i]), _lib.ptr(scratch), 0, stream))
     out = out.long()
     return out[0] if squeeze else out
 
@@ -105,14 +103,14 @@ def ema_update(flatten, embed, cluster_size, weight=None, decay=0.8, eps=1e-5, r
         raise Exception(f"ema_update: unsupported shape (n={n}, K={K}, d={d}; need K >= 1, 1 <= d <= 63)")
     dev = x.device
     out = torch.empty((h, n), dtype=torch.int32, device=dev)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    scratch = _lib.scratch(nbytes, dev)
+    stream = _lib.stream(dev)
     pre = cb.detach().clone() if return_quantized else None
     for i in range(h):
         xi = x[i].detach().contiguous().float()
         wi = None if w is None else w[i].detach().contiguous().float()
-        _lib.check(lib.lg_vq_ema_step(n, d, K, xi.data_ptr(), None if wi is None else wi.data_ptr(), cb[i].data_ptr(), cs[i].data_ptr(),
-                                      float(decay), float(eps), out[i].data_ptr(), scratch.data_ptr(), 0, stream))
+        _lib.check(lib.lg_vq_ema_step(n, d, K, _lib.ptr(xi), _lib.ptr(wi), _lib.ptr(cb[i]), _lib.ptr(cs[i]), float(decay), float(eps),
+                                      _lib.ptr(out[i]), _lib.ptr(scratch), 0, stream))
     ind = out.long()
     if not return_quantized:
         return ind[0] if squeeze else ind

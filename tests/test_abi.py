@@ -158,3 +158,155 @@ def test_prune_pass_and_view_runner_do_not_touch_the_process_defaults():
     for mod in (prune, parallel, dp):
         src = inspect.getsource(mod)
         assert "set_option(" not in src and "_OPTIONS[" not in src, mod.__name__
+
+
+# ---- the binding against the headers: every prototype, constant and struct ---------------------------------------------------
+
+_SCALAR_KINDS = {"int": "int32", "int32_t": "int32", "int64_t": "int64", "uint32_t": "uint32", "float": "float", "double": "double",
+                 "size_t": "size_t", "void": "void"}
+_POINTER_TYPES = ("hipStream_t", "lg_alloc_fn", "lg_chunk_fn")
+
+
+def _header_text():
+    """Both headers, comments removed."""
+    src = open(HDR).read() + "\n" + open(HDR_DEBUG).read()
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+
+
+def _c_kind(text, named):
+    """Kind of a C return type (named=False) or of one parameter declaration `type name` (named=True)."""
+    words = [w for w in re.findall(r"\w+", text) if w != "const"]
+    if "*" in text or any(w in _POINTER_TYPES for w in words):
+        return "pointer"
+    assert len(words) == (2 if named else 1), f"cannot read the C type in {text!r}"
+    return _SCALAR_KINDS[words[0]]
+
+
+def _header_prototypes():
+    """name -> (return kind, [parameter kinds]) of every lg_* function the two headers declare."""
+    src = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", _header_text(), flags=re.S)
+    src = re.sub(r"typedef[^;{]*;|enum\s*\{.*?\}\s*;|^\s*#[^\n]*|extern\s+\"C\"\s*\{", "", src, flags=re.S | re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(lg_\w+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in out, f"{name} declared twice"
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (_c_kind(ret, False), [_c_kind(p, True) for p in params])
+    return out
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, (C._Pointer, C._CFuncPtr)):
+        return "pointer"
+    if t is C.c_size_t:           # (before the sized integers: on LP64 it is one class with c_uint64)
+        return "size_t"
+    return {C.c_int32: "int32", C.c_int64: "int64", C.c_uint32: "uint32", C.c_float: "float", C.c_double: "double"}[t]
+
+
+def _prototype_mismatches(declared, table):
+    """One line per function on which the header (`declared`: _header_prototypes()) and a binding table (name -> (restype, argtypes))
+    disagree; every line begins with the function's name."""
+    bad = [f"{n}: declared in the headers, not in the table" for n in sorted(set(declared) - set(table))]
+    bad += [f"{n}: in the table, not declared in the headers" for n in sorted(set(table) - set(declared))]
+    for name in sorted(set(declared) & set(table)):
+        ret, params = declared[name]
+        got_ret, got = _ctypes_kind(table[name][0]), [_ctypes_kind(t) for t in table[name][1]]
+        if got_ret != ret:
+            bad.append(f"{name}: returns {ret}, the table says {got_ret}")
+        if len(got) != len(params):
+            bad.append(f"{name}: {len(params)} parameters, the table has {len(got)}")
+        bad += [f"{name}: parameter {k} is {a}, the table says {b}" for k, (a, b) in enumerate(zip(params, got)) if a != b]
+    return bad
+
+
+def test_every_prototype_of_the_binding_matches_the_headers():
+    declared = _header_prototypes()
+    assert set(declared) == set(_declared_functions()) and len(declared) == 67       # the two parses agree on what is declared
+    assert list(_lib.PROTOTYPES) == _lib.EXPORTS
+    assert _prototype_mismatches(declared, _lib.PROTOTYPES) == []
+    # spot checks of the parse itself, so that an all-"pointer" reading of both sides could not pass
+    assert declared["lg_binning_bytes"] == ("size_t", ["int64", "int32", "int32", "int32"])
+    assert declared["lg_profile_reset"] == ("void", []) and declared["lg_last_error"] == ("pointer", [])
+    assert declared["lg_prune_epilogue"] == ("int32", ["int32", "pointer", "pointer", "float", "double"] + ["pointer"] * 4 + ["uint32", "pointer"])
+    assert declared["lg_compact_rows"][1] == ["int32", "pointer", "int32", "pointer", "pointer", "pointer", "pointer"]
+
+
+def test_the_prototype_check_reports_a_wrong_table():
+    declared, good = _header_prototypes(), dict(_lib.PROTOTYPES)
+    ret, args = good["lg_backward_scratch_bytes"]
+    assert args == (C.c_int32, C.c_int64)
+    widened = dict(good, lg_backward_scratch_bytes=(ret, (C.c_int64, C.c_int64)))                      # int32 -> int64
+    bad = _prototype_mismatches(declared, widened)
+    assert len(bad) == 1 and bad[0].startswith("lg_backward_scratch_bytes: parameter 0 is int32")
+    ret, args = good["lg_densify_rows"]
+    bad = _prototype_mismatches(declared, dict(good, lg_densify_rows=(ret, args[:4] + args[5:])))      # a parameter dropped
+    assert bad and all(line.startswith("lg_densify_rows:") for line in bad) and "12 parameters, the table has 11" in bad[0]
+    swapped = dict(good, lg_vq_nearest=good["lg_vq_ema_step"], lg_vq_ema_step=good["lg_vq_nearest"])   # two entries exchanged
+    bad = _prototype_mismatches(declared, swapped)
+    assert {line.split(":")[0] for line in bad} == {"lg_vq_nearest", "lg_vq_ema_step"}
+    missing = {n: v for n, v in good.items() if n != "lg_forward"}
+    assert _prototype_mismatches(declared, missing) == ["lg_forward: declared in the headers, not in the table"]
+
+
+def _header_constants():
+    src = _header_text()
+    values = {}
+    for body in re.findall(r"enum\s*\{(.*?)\}\s*;", src, flags=re.S):
+        members = [m.strip() for m in body.split(",") if m.strip()]
+        assert all(re.fullmatch(r"LG_\w+\s*=\s*-?\d+", m) for m in members), members        # every member states its value
+        values.update((m.split("=")[0].strip(), int(m.split("=")[1])) for m in members)
+    for name, value in re.findall(r"^\s*#\s*define\s+(LG_\w+)\s+(-?\d+)u?\s*$", src, flags=re.M):
+        assert name not in values, name
+        values[name] = int(value)
+    return values
+
+
+def test_every_constant_of_the_binding_matches_the_headers():
+    values = _header_constants()
+    assert len(values) == 36 and values["LG_ABI_VERSION"] == 7 and values["LG_ERR_PREFILTERED"] == -4 and values["LG_ADAM_DECOUPLED_WD"] == 1
+    for name, value in values.items():
+        mine = name if name == "LG_OK" or name.startswith("LG_ERR_") else name[len("LG_"):]
+        assert hasattr(_lib, mine), f"{name} has no counterpart _lib.{mine}"
+        assert getattr(_lib, mine) == value, f"_lib.{mine} = {getattr(_lib, mine)}, the header says {name} = {value}"
+    flags = {n: v for n, v in values.items() if n.startswith("LG_FLAG_")}
+    assert len(flags) == 15 and all(v > 0 and v & (v - 1) == 0 for v in flags.values()), flags
+    assert len(set(flags.values())) == len(flags), flags
+    # every FLAG_* / WEIGHT_* / ... the binding states exists in the header too
+    prefixes = ("FLAG_", "WEIGHT_", "LG_ERR_", "ADAM_", "DENSIFY_", "FEATURES_", "FILTER3D_")
+    for mine in (n for n in vars(_lib) if n.startswith(prefixes)):
+        assert (mine if mine.startswith("LG_") else "LG_" + mine) in values, f"_lib.{mine} is not in the headers"
+
+
+def _header_structs():
+    """name -> [field names in order] of every `typedef struct lg_* { ... } lg_*;`."""
+    out = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(lg_\w+)\s*\{(.*?)\}\s*\1\s*;", _header_text(), flags=re.S):
+        fields = []
+        for decl in (d.strip() for d in body.split(";") if d.strip()):
+            for part in decl.split(","):
+                fields.append(re.fullmatch(r".*?(\w+)\s*(?:\[\s*\d+\s*\])?", part.strip(), flags=re.S).group(1))
+        out[name] = fields
+    return out
+
+
+def test_every_struct_of_the_binding_has_the_layout_the_compiler_gives_the_header(tmp_path):
+    import subprocess
+    structs = _header_structs()
+    mirrors = {n: t for n, t in vars(_lib).items() if isinstance(t, type) and issubclass(t, C.Structure) and t is not C.Structure}
+    assert set(structs) == set(mirrors) and len(structs) == 8
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "lightgaussian_debug.h"', "int main(void) {"]
+    for name, fields in structs.items():
+        assert fields == [f[0] for f in mirrors[name]._fields_], name
+        lines.append(f'    printf("{name} sizeof %zu\\n", sizeof({name}));')
+        lines += [f'    printf("{name} {f} %zu\\n", offsetof({name}, {f}));' for f in fields]
+    lines += ["    return 0;", "}"]
+    src, exe = tmp_path / "abi_layout.cpp", tmp_path / "abi_layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(common.ROOT, "include"), str(src), "-o", str(exe)])
+    measured = [line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines()]
+    assert len(measured) == sum(len(f) + 1 for f in structs.values())
+    for name, what, value in measured:
+        mine = C.sizeof(mirrors[name]) if what == "sizeof" else getattr(mirrors[name], what).offset
+        assert mine == int(value), f"{name} {what}: ctypes {mine}, the compiler {value}"
+    assert C.sizeof(_lib.lg_filter_camera) == 80 and C.sizeof(_lib.lg_adam_rows_tensor) == C.sizeof(_lib.lg_adam_tensor) + 16
