@@ -62,60 +62,6 @@ __device__ __forceinline__ void lg_adam_element(float& p, float g, float& m, flo
     p = fmaf(-step_size, m / denom, p);
 }
 
-template <bool DECOUPLED>
-__global__ void __launch_bounds__(LG_ADAM_THREADS) lg_adam_kernel(const LgAdamTable a)
-{
-    const uint32_t wg = blockIdx.x;
-    uint32_t t = 0;
-#pragma unroll
-    for (int k = 1; k < LG_ADAM_MAX_TENSORS; k++) t += wg >= a.first_wg[k] ? 1u : 0u;   // first_wg ascends: t = the last entry <= wg
-    float* __restrict__ const P = a.param[t];
-    const float* __restrict__ const G = a.grad[t];
-    float* __restrict__ const M = a.exp_avg[t];
-    float* __restrict__ const V = a.exp_avg_sq[t];
-    const float decay = a.decay[t], step_size = a.step_size[t], bc2_sqrt = a.bc2_sqrt[t];
-    const float om_b1 = a.one_minus_beta1, b2 = a.beta2, om_b2 = a.one_minus_beta2, eps = a.eps;
-    const int64_t base = (int64_t)(wg - a.first_wg[t]) * LG_ADAM_SPAN;
-    const int64_t left = a.numel[t] - base;             // > 0 by the host's workgroup count
-    if (((a.vec_mask >> t) & 1u) && left >= LG_ADAM_SPAN) {
-        lg_adam_f4 p[LG_ADAM_VEC], g[LG_ADAM_VEC], m[LG_ADAM_VEC], v[LG_ADAM_VEC];
-#pragma unroll
-        for (int u = 0; u < LG_ADAM_VEC; u++) {
-            const int64_t i = base + (int64_t)(u * LG_ADAM_THREADS + (int)threadIdx.x) * 4;
-#if LG_ADAM_NT_GRAD
-            g[u] = __builtin_nontemporal_load((const lg_adam_f4*)(G + i));
-#else
-            g[u] = *(const lg_adam_f4*)(G + i);
-#endif
-            p[u] = *(const lg_adam_f4*)(P + i);
-            m[u] = *(const lg_adam_f4*)(M + i);
-            v[u] = *(const lg_adam_f4*)(V + i);
-        }
-        __builtin_amdgcn_sched_barrier(0);              // every load of the span is in flight before the first dependent instruction
-#pragma unroll
-        for (int u = 0; u < LG_ADAM_VEC; u++) {
-            const int64_t i = base + (int64_t)(u * LG_ADAM_THREADS + (int)threadIdx.x) * 4;
-            float pe[4] = { p[u].x, p[u].y, p[u].z, p[u].w }, me[4] = { m[u].x, m[u].y, m[u].z, m[u].w };
-            float ve[4] = { v[u].x, v[u].y, v[u].z, v[u].w };
-            const float ge[4] = { g[u].x, g[u].y, g[u].z, g[u].w };
-#pragma unroll
-            for (int c = 0; c < 4; c++) lg_adam_element<DECOUPLED>(pe[c], ge[c], me[c], ve[c], decay, step_size, bc2_sqrt, om_b1, b2, om_b2, eps);
-            *(lg_adam_f4*)(P + i) = lg_adam_f4{ pe[0], pe[1], pe[2], pe[3] };
-            *(lg_adam_f4*)(M + i) = lg_adam_f4{ me[0], me[1], me[2], me[3] };
-            *(lg_adam_f4*)(V + i) = lg_adam_f4{ ve[0], ve[1], ve[2], ve[3] };
-        }
-    } else {
-        const int n = (int)(left < LG_ADAM_SPAN ? left : LG_ADAM_SPAN);
-        for (int k = (int)threadIdx.x; k < n; k += LG_ADAM_THREADS) {
-            const int64_t i = base + k;
-            float p = P[i], m = M[i], v = V[i];
-            const float g = G[i];
-            lg_adam_element<DECOUPLED>(p, g, m, v, decay, step_size, bc2_sqrt, om_b1, b2, om_b2, eps);
-            P[i] = p; M[i] = m; V[i] = v;
-        }
-    }
-}
-
 // ---- lg_adam_step_rows: the same step over the rows a byte mask names ("visible rows") -----------------------
 // A tensor [rows, ...] with a mask of `rows` bytes: an element of a row whose byte is non-zero takes lg_adam_element exactly as above;
 // an element of a row whose byte is zero is neither loaded nor stored (param and both moments keep their bits, its gradient is never
@@ -134,14 +80,46 @@ struct LgAdamRowsTable {
     uint32_t row_thr[LG_ADAM_MAX_TENSORS];          //   without a division or a branch
 };
 
-template <bool DECOUPLED>
-__global__ void __launch_bounds__(LG_ADAM_THREADS) lg_adam_rows_kernel(const LgAdamRowsTable r)
+// vis[u], bit c: element c of the lane's dwordx4 u lies in a row the mask names (a full, aligned span; rem = the span's first element
+// inside its first row, mask = that row's byte)
+__device__ __forceinline__ void lg_adam_span_vis(const uint8_t* __restrict__ mask, uint32_t rem, uint32_t row_len, uint32_t rcp, uint32_t thr,
+                                                 uint32_t (&vis)[LG_ADAM_VEC])
 {
-    const LgAdamTable& a = r.a;
+    uint32_t row[LG_ADAM_VEC][4], mb[LG_ADAM_VEC][4];
+#pragma unroll
+    for (int u = 0; u < LG_ADAM_VEC; u++) {
+        const uint32_t x = rem + (uint32_t)(u * LG_ADAM_THREADS + (int)threadIdx.x) * 4u;
+#pragma unroll
+        for (int c = 0; c < 4; c++) row[u][c] = lg_adam_local_row(x + (uint32_t)c, rcp, thr);
+    }
+    if (row_len >= 3u) {                        // (uniform) two rows at the most: the middle elements belong to one of them
+#pragma unroll
+        for (int u = 0; u < LG_ADAM_VEC; u++) { mb[u][0] = mask[row[u][0]]; mb[u][3] = mask[row[u][3]]; }
+#pragma unroll
+        for (int u = 0; u < LG_ADAM_VEC; u++) {
+            mb[u][1] = row[u][1] == row[u][0] ? mb[u][0] : mb[u][3];
+            mb[u][2] = row[u][2] == row[u][0] ? mb[u][0] : mb[u][3];
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < LG_ADAM_VEC; u++)
+#pragma unroll
+            for (int c = 0; c < 4; c++) mb[u][c] = mask[row[u][c]];
+    }
+#pragma unroll
+    for (int u = 0; u < LG_ADAM_VEC; u++)
+        vis[u] = (mb[u][0] ? 1u : 0u) | (mb[u][1] ? 2u : 0u) | (mb[u][2] ? 4u : 0u) | (mb[u][3] ? 8u : 0u);
+}
+
+// One workgroup's span: the ONE body behind lg_adam_kernel (ROWS = false: r is not read, and there is no mask, no vis, no zero-fill of
+// the registers and no `continue` -- the dense kernel as it always was) and lg_adam_rows_kernel (ROWS = true).
+template <bool DECOUPLED, bool ROWS>
+__device__ __forceinline__ void lg_adam_span(const LgAdamTable& a, const LgAdamRowsTable* r)
+{
     const uint32_t wg = blockIdx.x;
     uint32_t t = 0;
 #pragma unroll
-    for (int k = 1; k < LG_ADAM_MAX_TENSORS; k++) t += wg >= a.first_wg[k] ? 1u : 0u;
+    for (int k = 1; k < LG_ADAM_MAX_TENSORS; k++) t += wg >= a.first_wg[k] ? 1u : 0u;   // first_wg ascends: t = the last entry <= wg
     float* __restrict__ const P = a.param[t];
     const float* __restrict__ const G = a.grad[t];
     float* __restrict__ const M = a.exp_avg[t];
@@ -150,45 +128,27 @@ __global__ void __launch_bounds__(LG_ADAM_THREADS) lg_adam_rows_kernel(const LgA
     const float om_b1 = a.one_minus_beta1, b2 = a.beta2, om_b2 = a.one_minus_beta2, eps = a.eps;
     const int64_t base = (int64_t)(wg - a.first_wg[t]) * LG_ADAM_SPAN;
     const int64_t left = a.numel[t] - base;             // > 0 by the host's workgroup count
-    const uint32_t row_len = r.row_len[t], rcp = r.row_rcp[t], thr = r.row_thr[t];
-    const uint8_t* __restrict__ mask = r.row_mask[t];
-    uint32_t rem = 0;
-    if (mask) mask += lg_adam_first_row(base, row_len, &rem);      // uniform: the mask byte of the span's first row
+    [[maybe_unused]] uint32_t row_len = 0, rcp = 0, thr = 0, rem = 0;
+    [[maybe_unused]] const uint8_t* __restrict__ mask = nullptr;
+    if constexpr (ROWS) {
+        row_len = r->row_len[t]; rcp = r->row_rcp[t]; thr = r->row_thr[t];
+        mask = r->row_mask[t];
+        if (mask) mask += lg_adam_first_row(base, row_len, &rem);      // uniform: the mask byte of the span's first row
+    }
     if (((a.vec_mask >> t) & 1u) && left >= LG_ADAM_SPAN) {
-        uint32_t vis[LG_ADAM_VEC];                      // bit c: element c of the lane's dwordx4 u is stepped
+        [[maybe_unused]] uint32_t vis[LG_ADAM_VEC];     // ROWS: bit c = element c of the lane's dwordx4 u is stepped
+        if constexpr (ROWS) {
 #pragma unroll
-        for (int u = 0; u < LG_ADAM_VEC; u++) vis[u] = 0xFu;
-        if (mask) {
-            uint32_t row[LG_ADAM_VEC][4], mb[LG_ADAM_VEC][4];
-#pragma unroll
-            for (int u = 0; u < LG_ADAM_VEC; u++) {
-                const uint32_t x = rem + (uint32_t)(u * LG_ADAM_THREADS + (int)threadIdx.x) * 4u;
-#pragma unroll
-                for (int c = 0; c < 4; c++) row[u][c] = lg_adam_local_row(x + (uint32_t)c, rcp, thr);
-            }
-            if (row_len >= 3u) {                        // (uniform) two rows at the most: the middle elements belong to one of them
-#pragma unroll
-                for (int u = 0; u < LG_ADAM_VEC; u++) { mb[u][0] = mask[row[u][0]]; mb[u][3] = mask[row[u][3]]; }
-#pragma unroll
-                for (int u = 0; u < LG_ADAM_VEC; u++) {
-                    mb[u][1] = row[u][1] == row[u][0] ? mb[u][0] : mb[u][3];
-                    mb[u][2] = row[u][2] == row[u][0] ? mb[u][0] : mb[u][3];
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < LG_ADAM_VEC; u++)
-#pragma unroll
-                    for (int c = 0; c < 4; c++) mb[u][c] = mask[row[u][c]];
-            }
-#pragma unroll
-            for (int u = 0; u < LG_ADAM_VEC; u++)
-                vis[u] = (mb[u][0] ? 1u : 0u) | (mb[u][1] ? 2u : 0u) | (mb[u][2] ? 4u : 0u) | (mb[u][3] ? 8u : 0u);
+            for (int u = 0; u < LG_ADAM_VEC; u++) vis[u] = 0xFu;
+            if (mask) lg_adam_span_vis(mask, rem, row_len, rcp, thr, vis);
         }
         lg_adam_f4 p[LG_ADAM_VEC], g[LG_ADAM_VEC], m[LG_ADAM_VEC], v[LG_ADAM_VEC];
 #pragma unroll
         for (int u = 0; u < LG_ADAM_VEC; u++) {
-            p[u] = g[u] = m[u] = v[u] = lg_adam_f4{ 0.0f, 0.0f, 0.0f, 0.0f };
-            if (vis[u] == 0u) continue;
+            if constexpr (ROWS) {
+                p[u] = g[u] = m[u] = v[u] = lg_adam_f4{ 0.0f, 0.0f, 0.0f, 0.0f };
+                if (vis[u] == 0u) continue;
+            }
             const int64_t i = base + (int64_t)(u * LG_ADAM_THREADS + (int)threadIdx.x) * 4;
 #if LG_ADAM_NT_GRAD
             g[u] = __builtin_nontemporal_load((const lg_adam_f4*)(G + i));
@@ -199,20 +159,24 @@ __global__ void __launch_bounds__(LG_ADAM_THREADS) lg_adam_rows_kernel(const LgA
             m[u] = *(const lg_adam_f4*)(M + i);
             v[u] = *(const lg_adam_f4*)(V + i);
         }
-        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);              // every load of the span is in flight before the first dependent instruction
 #pragma unroll
         for (int u = 0; u < LG_ADAM_VEC; u++) {
-            if (vis[u] == 0u) continue;
+            if constexpr (ROWS) { if (vis[u] == 0u) continue; }
             const int64_t i = base + (int64_t)(u * LG_ADAM_THREADS + (int)threadIdx.x) * 4;
             float pe[4] = { p[u].x, p[u].y, p[u].z, p[u].w }, me[4] = { m[u].x, m[u].y, m[u].z, m[u].w };
             float ve[4] = { v[u].x, v[u].y, v[u].z, v[u].w };
             const float ge[4] = { g[u].x, g[u].y, g[u].z, g[u].w };
 #pragma unroll
             for (int c = 0; c < 4; c++) {
-                float pn = pe[c], mn = me[c], vn = ve[c];
-                lg_adam_element<DECOUPLED>(pn, ge[c], mn, vn, decay, step_size, bc2_sqrt, om_b1, b2, om_b2, eps);
-                const bool on = (vis[u] >> c) & 1u;     // an unseen element of a straddling dwordx4 stores the bits it loaded
-                pe[c] = on ? pn : pe[c]; me[c] = on ? mn : me[c]; ve[c] = on ? vn : ve[c];
+                if constexpr (ROWS) {
+                    float pn = pe[c], mn = me[c], vn = ve[c];
+                    lg_adam_element<DECOUPLED>(pn, ge[c], mn, vn, decay, step_size, bc2_sqrt, om_b1, b2, om_b2, eps);
+                    const bool on = (vis[u] >> c) & 1u;     // an unseen element of a straddling dwordx4 stores the bits it loaded
+                    pe[c] = on ? pn : pe[c]; me[c] = on ? mn : me[c]; ve[c] = on ? vn : ve[c];
+                } else {
+                    lg_adam_element<DECOUPLED>(pe[c], ge[c], me[c], ve[c], decay, step_size, bc2_sqrt, om_b1, b2, om_b2, eps);
+                }
             }
             *(lg_adam_f4*)(P + i) = lg_adam_f4{ pe[0], pe[1], pe[2], pe[3] };
             *(lg_adam_f4*)(M + i) = lg_adam_f4{ me[0], me[1], me[2], me[3] };
@@ -221,7 +185,7 @@ __global__ void __launch_bounds__(LG_ADAM_THREADS) lg_adam_rows_kernel(const LgA
     } else {
         const int n = (int)(left < LG_ADAM_SPAN ? left : LG_ADAM_SPAN);
         for (int k = (int)threadIdx.x; k < n; k += LG_ADAM_THREADS) {
-            if (mask && mask[lg_adam_local_row(rem + (uint32_t)k, rcp, thr)] == 0) continue;
+            if constexpr (ROWS) { if (mask && mask[lg_adam_local_row(rem + (uint32_t)k, rcp, thr)] == 0) continue; }
             const int64_t i = base + k;
             float p = P[i], m = M[i], v = V[i];
             const float g = G[i];
@@ -230,3 +194,9 @@ __global__ void __launch_bounds__(LG_ADAM_THREADS) lg_adam_rows_kernel(const LgA
         }
     }
 }
+
+template <bool DECOUPLED>
+__global__ void __launch_bounds__(LG_ADAM_THREADS) lg_adam_kernel(const LgAdamTable a) { lg_adam_span<DECOUPLED, false>(a, nullptr); }
+
+template <bool DECOUPLED>
+__global__ void __launch_bounds__(LG_ADAM_THREADS) lg_adam_rows_kernel(const LgAdamRowsTable r) { lg_adam_span<DECOUPLED, true>(r.a, &r); }

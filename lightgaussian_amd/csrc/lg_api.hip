@@ -1,10 +1,12 @@
 // lg_api.hip -- C ABI (include/lightgaussian.h) of the gfx950 (CDNA4, wave64) LightGaussian rasterizer.
 // The single translation unit of liblightgaussian_hip.so; the kernels live in the headers it includes:
-//   lg_math.h        scalar float arithmetic shared with the CPU test harness (canonical operation order)
+//   lg_math.h        scalar float arithmetic shared with the CPU test harness (canonical operation order); one copy each of the projection steps,
+//                    the backward chain (lg_backward_chain), the SH backward steps (lg_sh_*) and the quaternion matrix (lg_quat_to_rot)
 //   lg_plan.h        host-side plans of one forward, plain C++ (also compiled by the CPU tests): KeyPlan (sort-key layout), ForwardPlan (kernel variants)
 //   lg_host.h        error strings, optional hipEvent profiler, scratch carving (GeomView / ImgView / BinView)
-//   lg_wave.h        wave64 primitives (DPP / permlane reductions)
-//   lg_preprocess.h  K1 lg_preprocess<RAW, DIRECT, AA>, K8+K9 lg_preprocess_bwd<RAW, JAC, AA> (AA: LG_FLAG_ANTIALIAS)   (per Gaussian, HBM-bound); lg_k9_*: K9's read side, shared with lg_camera.h
+//   lg_wave.h        wave64 primitives (DPP / permlane reductions, lg_wave_lds_sync: the LDS hand-over inside a wave)
+//   lg_preprocess.h  K1 lg_preprocess<RAW, DIRECT, AA>, K8+K9 lg_preprocess_bwd<RAW, JAC, AA> (AA: LG_FLAG_ANTIALIAS)   (per Gaussian, HBM-bound); lg_k9_*: K9's read side, shared with lg_camera.h;
+//                    lg_sh_rows_flush: how dL/dSH rows leave LDS (K9 and lg_sh_grad_from_rgb_kernel)
 //   lg_binning.h     K2 lg_scan_blocks, K3 lg_duplicate, lg_tile_sort / _long (second sort stage), lg_tile_ranges (one-stage cross-check only),
 //                    lg_work_order (K2-K5 all hand-written; lg_sort.h = K4)
 //   lg_loss.h        lg_loss_fwd / lg_loss_bwd: fused L1 + SSIM of the training step             (a wave per 64-column strip, register ring)
@@ -17,7 +19,7 @@
 //   lg_vq_color_bwd.h lg_vq_code_index / lg_vq_colors_bwd: its backward -- per-row gradients of the row table (ordered segmented sum over a
 //                    per-model inverted index for the codebook rows) and the colour part of dL/dxyz
 //   lg_adam.h        lg_adam_step: one Adam / AdamW step over all parameter tensors of the model in one launch (table by value, dwordx4);
-//                    lg_adam_step_rows: the same step over the rows a byte mask names (row index: lg_adam_rows.h)
+//                    lg_adam_step_rows: the same step over the rows a byte mask names (row index: lg_adam_rows.h); both kernels are lg_adam_span<DECOUPLED, ROWS>
 //   lg_densify.h     lg_densify_stats / lg_densify_plan / lg_densify_rows: view statistics and clone / split / prune of densify_and_prune
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT, ABS>   (per tile, VALU-bound); wave_reduce_via_lds<NV> (also lg_features.h's)
 //   lg_features.h    lg_features_fwd / _bwd / _gather: C further per-Gaussian channels blended over the lists a forward left, and dL/dfeatures

@@ -200,9 +200,7 @@ lg_duplicate(int N, int nblk, int gx, int stored_depth_bits, int store_drop, int
                 const uint64_t low = ((uint64_t)((r.z - LG_DEPTH_BIAS) >> store_drop) << gid_bits) | (uint32_t)i;
                 s_lo[wave][lane] = (uint32_t)low;
                 s_hi[wave][lane] = (uint32_t)(low >> 32);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                lg_wave_lds_sync();
                 for (uint32_t p = lane; p < total; p += 64u) {
                     uint32_t j = 0;                            // largest j with exc[j] <= p: the Gaussian that owns instance p
 #pragma unroll
@@ -268,10 +266,10 @@ __device__ __forceinline__ void lg_wave_sort_run(uint32_t i, uint32_t e, int low
     for (int shift = 0; shift < low_bits; shift += 8) {
         const uint32_t dmask = (1u << min(8, low_bits - shift)) - 1u;
         for (uint32_t c = lane; c < 256u; c += 64u) cnt[c] = 0u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        lg_wave_lds_sync();
         for (uint32_t a = i + lane; a < e; a += 64u)
             atomicAdd(&cnt[(lg_low_bits(src[a], gid_bits, gid_mask, store_drop, low_mask, tinfo) >> shift) & dmask], 1u);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        lg_wave_lds_sync();
         {   // exclusive scan of the 256 counters: lane l owns digits 4 l .. 4 l + 3
             const uint32_t c0 = cnt[4u * lane], c1 = cnt[4u * lane + 1u], c2 = cnt[4u * lane + 2u], c3 = cnt[4u * lane + 3u];
             uint32_t inc = c0 + c1 + c2 + c3;
@@ -284,7 +282,7 @@ __device__ __forceinline__ void lg_wave_sort_run(uint32_t i, uint32_t e, int low
             const uint32_t ex = inc - own;
             cnt[4u * lane] = ex; cnt[4u * lane + 1u] = ex + c0; cnt[4u * lane + 2u] = ex + c0 + c1; cnt[4u * lane + 3u] = ex + c0 + c1 + c2;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        lg_wave_lds_sync();
         for (uint32_t a0 = i; a0 < e; a0 += 64u) {              // in list order: lanes of one digit keep their relative order
             const uint32_t a = a0 + lane;
             const bool valid = a < e;
@@ -300,9 +298,9 @@ __device__ __forceinline__ void lg_wave_sort_run(uint32_t i, uint32_t e, int low
             const uint32_t below = prefix_popc(peers);
             uint32_t pos = 0;
             if (valid) pos = cnt[d] + below;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            lg_wave_lds_sync();
             if (valid && below == 0u) cnt[d] += (uint32_t)__popcll(peers);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            lg_wave_lds_sync();
             if (valid) dst[i + pos] = k;
         }
         __threadfence();                                        // the next pass (other lanes) reads what this one wrote
@@ -397,7 +395,6 @@ lg_tile_ranges(const uint32_t* __restrict__ counters, int tile_shift, int gid_bi
 #define LG_TS_DIGIT 9
 #define LG_TS_BINS (1 << LG_TS_DIGIT)
 #define LG_TS_RUN 8u                                       // longest run of equal upper bits the wave path finishes by insertion
-#define LG_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
 // bits [shift, shift + popc(dmask)) of the FULL depth pattern (minus bias) of a list entry; an all-ones key (padding) has all-ones digits
 __device__ __forceinline__ uint32_t lg_ts_digit(uint64_t key, int shift, uint32_t dmask, int gid_bits, uint32_t gid_mask, int store_drop,
@@ -414,13 +411,13 @@ __device__ __forceinline__ uint32_t lg_ts_digit(uint64_t key, int shift, uint32_
 __device__ __forceinline__ uint32_t lg_ts_rank(uint32_t d, unsigned long long* mask, unsigned short* wc, unsigned long long mybit)
 {
     atomicOr(&mask[d], mybit);
-    LG_WAVE_SYNC();
+    lg_wave_lds_sync();
     const unsigned long long peers = mask[d];
     const uint32_t prev = wc[d];
     const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(peers >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)peers, 0u));
-    LG_WAVE_SYNC();
+    lg_wave_lds_sync();
     if (below == 0u) { wc[d] = (unsigned short)(prev + (uint32_t)__popcll(peers)); mask[d] = 0ull; }   // the lowest lane of the set
-    LG_WAVE_SYNC();
+    lg_wave_lds_sync();
     return prev + below;
 }
 
@@ -470,7 +467,7 @@ __device__ __forceinline__ void lg_tile_sort_wave(uint32_t tile, uint32_t lane, 
             for (int i = 0; i < (LG_TS_BINS * 8) / (64 * 16); i++) z[(uint32_t)i * 64u + lane] = make_uint4(0, 0, 0, 0);
             reinterpret_cast<uint4*>(cnt)[lane] = make_uint4(0, 0, 0, 0);
         }
-        LG_WAVE_SYNC();
+        lg_wave_lds_sync();
 #pragma unroll
         for (int k = 0; k < LG_TW_ITEMS; k++) {
             if ((uint32_t)k < items) {                                        // wave-uniform
@@ -492,15 +489,15 @@ __device__ __forceinline__ void lg_tile_sort_wave(uint32_t tile, uint32_t lane, 
             const uint32_t e0 = inc - own, e1 = e0 + c0, e2 = e1 + c1, e3 = e2 + c2, e4 = e3 + c3, e5 = e4 + c4, e6 = e5 + c5, e7 = e6 + c6;
             reinterpret_cast<uint4*>(cnt)[lane] = make_uint4(e0 | (e1 << 16), e2 | (e3 << 16), e4 | (e5 << 16), e6 | (e7 << 16));
         }
-        LG_WAVE_SYNC();
+        lg_wave_lds_sync();
 #pragma unroll
         for (int k = 0; k < LG_TW_ITEMS; k++)
             if ((uint32_t)k < items) stage[(uint32_t)cnt[rnk[k] >> 16] + (rnk[k] & 0xFFFFu)] = key[k];
-        LG_WAVE_SYNC();
+        lg_wave_lds_sync();
 #pragma unroll
         for (int k = 0; k < LG_TW_ITEMS; k++)
             if ((uint32_t)k < items) key[k] = stage[(uint32_t)k * 64u + lane];
-        LG_WAVE_SYNC();
+        lg_wave_lds_sync();
     }
     if (first == 0) break;                         // every digit went through the passes
     // ---- runs of equal upper bits: found from the neighbours in LDS, ordered by their first lane ----
@@ -515,7 +512,7 @@ __device__ __forceinline__ void lg_tile_sort_wave(uint32_t tile, uint32_t lane, 
             if (opens && (stage[idx + 1u] >> up) == me) starts |= 1u << k;
         }
     }
-    LG_WAVE_SYNC();
+    lg_wave_lds_sync();
     bool too_long = false;
     while (starts) {                               // (divergent: few lanes own a run at all)
         const uint32_t k = (uint32_t)__builtin_ctz(starts);
@@ -532,12 +529,12 @@ __device__ __forceinline__ void lg_tile_sort_wave(uint32_t tile, uint32_t lane, 
             if (b != a) stage[b] = v;
         }
     }
-    LG_WAVE_SYNC();
+    lg_wave_lds_sync();
     if (__ballot(too_long) == 0ull) break;
 #pragma unroll
     for (int k = 0; k < LG_TW_ITEMS; k++)
         if ((uint32_t)k < items) key[k] = stage[(uint32_t)k * 64u + lane];
-    LG_WAVE_SYNC();
+    lg_wave_lds_sync();
     }
     // `stage` holds the list in its final order (the last pass scattered into it; the finishing step worked in place)
 #pragma unroll
@@ -805,6 +802,7 @@ lg_tile_sort_long(const uint32_t* __restrict__ counters, const uint2* __restrict
         if (src != entries + r.x) {
             for (uint32_t i = tid; i < n; i += LG_TL_THREADS) entries[r.x + i] = src[i];
         }
+        // (workgroup scope around __syncthreads, as above: several waves, so not lg_wave_lds_sync)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");

@@ -213,9 +213,7 @@ __device__ __forceinline__ uint64_t fwd_pair_m(const float4& a, const float4& b,
 #endif                                                // batches of a tile that may be "open" at once (waves of a tile drift apart by at most this many)
 __device__ __forceinline__ uint64_t lg_wq_rowsum(const float* wq, uint32_t lane)
 {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    lg_wave_lds_sync();
     const float4* src = reinterpret_cast<const float4*>(wq + (lane >> 3) * LG_WQ_STRIDE + (lane & 7u) * 8u);
     const float4 x0 = src[0], x1 = src[1];
     // this lane's eight columns; modulo 2^64, minus 8 x bits(4096.0): exactly the sum of 8 quantised weights, below 2^43
@@ -227,6 +225,7 @@ __device__ __forceinline__ uint64_t lg_wq_rowsum(const float* wq, uint32_t lane)
     lo = dpp_add_u32<0xB1>(lo); hi = dpp_add_u32<0xB1>(hi);          // quad_perm [1,0,3,2]
     lo = dpp_add_u32<0x4E>(lo); hi = dpp_add_u32<0x4E>(hi);          // quad_perm [2,3,0,1]
     lo = dpp_add_u32<0x141>(lo); hi = dpp_add_u32<0x141>(hi);        // row_half_mirror: lane i <-> 7 - i of each group of 8 (the other quad)
+    // release + barrier without the acquire (so not lg_wave_lds_sync): the LDS accesses above must be done first; no read below depends on them
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();                // (the next chunk overwrites the rows)
     return ((uint64_t)hi << 24) + lo;
@@ -296,6 +295,7 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
     auto tile_leave = [&](uint32_t bi, auto add) {
         const uint32_t ts = bi % LG_TM_SLOTS, want = bi / LG_TM_SLOTS;
         while (__hip_atomic_load(&tgen[ts], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != want) __builtin_amdgcn_s_sleep(1);
+        // workgroup-scope acquire / release around the ticket atomics: the waves of a workgroup hand a slot to each other (not lg_wave_lds_sync)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         add(ts);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -964,9 +964,7 @@ __device__ __forceinline__ void wave_reduce_via_lds(const float (&p)[NV], float*
     static_assert(NV >= 1 && NV <= 16, "one row per four lanes");
 #pragma unroll
     for (int v = 0; v < NV; v++) red[v * LG_RED_STRIDE + (int)lane] = p[v];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    lg_wave_lds_sync();
     const uint32_t r = min(lane >> 2, (uint32_t)(NV - 1)), q = lane & 3u;
     const float4* src = reinterpret_cast<const float4*>(red + r * LG_RED_STRIDE + q * 16u);
     const float4 x0 = src[0], x1 = src[1], x2 = src[2], x3 = src[3];
@@ -975,6 +973,7 @@ __device__ __forceinline__ void wave_reduce_via_lds(const float (&p)[NV], float*
     s = dpp_add<0xB1, 0xf>(s);                      // quad_perm [1,0,3,2]
     s = dpp_add<0x4E, 0xf>(s);                      // quad_perm [2,3,0,1]: every lane of the quad holds the row total
     if (q == 0u && lane < 4u * NV) store(lane >> 2, s);
+    // release + barrier without the acquire (so not lg_wave_lds_sync): the LDS accesses above must be done first; no read below depends on them
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();                // (the next entry overwrites `red`)
 }

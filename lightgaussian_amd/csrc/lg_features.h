@@ -76,9 +76,7 @@ __device__ __forceinline__ uint32_t lg_feat_front(const LgFeatView& v, uint32_t 
         const uint32_t pos = prefix_popc(mask);
         q0[pos] = r0; q1[pos] = r1; qid[pos] = id; qpos[pos] = lane;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    lg_wave_lds_sync();
     return (uint32_t)__popcll(mask);
 }
 
@@ -113,9 +111,7 @@ __device__ __forceinline__ void lg_feat_stage_rows(const float* features, int C,
         const uint32_t j = i / CG, c = i % CG;
         frow[i] = (c0 + (int)c < C) ? features[(size_t)qid[j] * C + c0 + c] : 0.0f;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    lg_wave_lds_sync();
 }
 
 // One (pixel, entry) step: power and alpha as the forward's pair step evaluates them (fwd_pair_m), then lg_feature_step.  Called by all
@@ -173,6 +169,7 @@ lg_features_fwd(LgFeatView v, int C, int c0, const float* __restrict__ features,
                 F[4 * k + 2] = fmaf(f.z, w, F[4 * k + 2]); F[4 * k + 3] = fmaf(f.w, w, F[4 * k + 3]);
             }
         }
+        // release + barrier without the acquire (so not lg_wave_lds_sync): the LDS accesses above must be done first; no read below depends on them
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();        // (the next batch overwrites the queue)
     }

@@ -71,7 +71,6 @@ __device__ __forceinline__ lg_v2f lg_pk_fma(float w, lg_v2f a, lg_v2f c)
     const lg_v2f ww = {w, w};
     return __builtin_elementwise_fma(ww, a, c);
 }
-#define LG_LOSS_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
 // Loads of the row stream are UNCONDITIONAL (row and column clamped into the image, the value replaced by zero afterwards):
 // a load inside a branch makes hipcc wait for every outstanding load (s_waitcnt vmcnt(0)) before the first use of any of them,
@@ -146,7 +145,7 @@ lg_loss_fwd(int H, int W, const float* __restrict__ img, const float* __restrict
             //  here would keep hipcc from unrolling, and the ring slots must be compile-time register names)
             load_row(i + LG_LOSS_PF, pa[LG_LOSS_PF], pb[LG_LOSS_PF]);
             const lg_v2f a0 = pa[0], b0 = pb[0];
-            LG_LOSS_SYNC();                        // (the previous row's reads are done)
+            lg_wave_lds_sync();                        // (the previous row's reads are done)
             {
                 const int gy = y0 - LG_LOSS_HALO + i;
                 const bool rin = gy >= 0 && gy < H;                    // wave-uniform
@@ -154,7 +153,7 @@ lg_loss_fwd(int H, int W, const float* __restrict__ img, const float* __restrict
                 rb[lane] = lg_v2f{ka ? a0.x : 0.0f, ka ? a0.y : 0.0f};
                 if (lane < 2 * LG_LOSS_HALO) rb[LG_LOSS_STRIP + lane] = lg_v2f{kb ? b0.x : 0.0f, kb ? b0.y : 0.0f};
             }
-            LG_LOSS_SYNC();
+            lg_wave_lds_sync();
             // horizontal filter: taps in ascending order from fma(w[0], v, 0)
             lg_v2f h01 = {0.0f, 0.0f}, h23 = {0.0f, 0.0f};
             float h4 = 0.0f;
@@ -273,7 +272,7 @@ lg_loss_bwd(int H, int W, const float* __restrict__ img, const float* __restrict
             const int i = ib + j;
             load_row(i + LG_LOSS_PF, pr[LG_LOSS_PF]);   // (rows past nrows in the last turn of the ring: see lg_loss_fwd)
             const Row r0 = pr[0];
-            LG_LOSS_SYNC();
+            lg_wave_lds_sync();
             {
                 const int gy = y0 - LG_LOSS_HALO + i;
                 const bool rin = gy >= 0 && gy < H;                    // wave-uniform
@@ -284,7 +283,7 @@ lg_loss_bwd(int H, int W, const float* __restrict__ img, const float* __restrict
                     if (lane < 2 * LG_LOSS_HALO) rb[q][LG_LOSS_STRIP + lane] = kb ? r0.b[q] : 0.0f;
                 }
             }
-            LG_LOSS_SYNC();
+            lg_wave_lds_sync();
             float h[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int t = 0; t < 11; t++)

@@ -105,17 +105,25 @@ LG_HD float lg_seqsum32(float w, uint32_t c)
 }
 
 // ---------------------------------------------------------------------------------------------
+// Rotation matrix of a unit quaternion q = (r, x, y, z), row-major.  The ONE copy: lg_cov3d, lg_backward_cov3d and
+// lg_densify_child_xyz call it (build_rotation, utils/general_utils.py:84-107).
+LG_HD void lg_quat_to_rot(const float q[4], float R[9])
+{
+    const float r = q[0], x = q[1], y = q[2], z = q[3];
+    R[0] = 1.0f - 2.0f * (y * y + z * z); R[1] = 2.0f * (x * y - r * z); R[2] = 2.0f * (x * z + r * y);
+    R[3] = 2.0f * (x * y + r * z); R[4] = 1.0f - 2.0f * (x * x + z * z); R[5] = 2.0f * (y * z - r * x);
+    R[6] = 2.0f * (x * z - r * y); R[7] = 2.0f * (y * z + r * x); R[8] = 1.0f - 2.0f * (x * x + y * y);
+}
+
 // 3D covariance from (scale, quaternion): Sigma = (R S)(R S)^T packed (xx,xy,xz,yy,yz,zz).
 LG_HD void lg_cov3d(const float s_in[3], float mod, const float q[4], float cov[6])
 {
     float s0 = mod * s_in[0], s1 = mod * s_in[1], s2 = mod * s_in[2];
-    float r = q[0], x = q[1], y = q[2], z = q[3];
-    float R00 = 1.0f - 2.0f * (y * y + z * z), R01 = 2.0f * (x * y - r * z), R02 = 2.0f * (x * z + r * y);
-    float R10 = 2.0f * (x * y + r * z), R11 = 1.0f - 2.0f * (x * x + z * z), R12 = 2.0f * (y * z - r * x);
-    float R20 = 2.0f * (x * z - r * y), R21 = 2.0f * (y * z + r * x), R22 = 1.0f - 2.0f * (x * x + y * y);
-    float L00 = R00 * s0, L01 = R01 * s1, L02 = R02 * s2;
-    float L10 = R10 * s0, L11 = R11 * s1, L12 = R12 * s2;
-    float L20 = R20 * s0, L21 = R21 * s1, L22 = R22 * s2;
+    float R[9];
+    lg_quat_to_rot(q, R);
+    float L00 = R[0] * s0, L01 = R[1] * s1, L02 = R[2] * s2;
+    float L10 = R[3] * s0, L11 = R[4] * s1, L12 = R[5] * s2;
+    float L20 = R[6] * s0, L21 = R[7] * s1, L22 = R[8] * s2;
     cov[0] = L00 * L00 + L01 * L01 + L02 * L02;
     cov[1] = L00 * L10 + L01 * L11 + L02 * L12;
     cov[2] = L00 * L20 + L01 * L21 + L02 * L22;
@@ -200,6 +208,28 @@ LG_HD float lg_aa_backward(float a0, float b, float c0, float a, float c, float 
     return rho;
 }
 
+// The three steps lg_project_t (the first and the last; it keeps the second inline, see there) and both backward functions share (row-vector layout m[4 k + c], p = the mean).
+// lg_view_point: v = p vm, the view-space mean.
+LG_HD void lg_view_point(const float* vm, float px, float py, float pz, float& vx, float& vy, float& vz)
+{
+    vx = vm[0] * px + vm[4] * py + vm[8] * pz + vm[12];
+    vy = vm[1] * px + vm[5] * py + vm[9] * pz + vm[13];
+    vz = vm[2] * px + vm[6] * py + vm[10] * pz + vm[14];
+}
+// lg_hom_point: h = p pm, columns 0 and 1, and m_w = 1 / (h_w + 1e-7) of column 3 (ndc = h_xy m_w).
+LG_HD void lg_hom_point(const float* pm, float px, float py, float pz, float& hx, float& hy, float& m_w)
+{
+    hx = pm[0] * px + pm[4] * py + pm[8] * pz + pm[12];
+    hy = pm[1] * px + pm[5] * py + pm[9] * pz + pm[13];
+    const float hw = pm[3] * px + pm[7] * py + pm[11] * pz + pm[15];
+    m_w = 1.0f / (hw + 0.0000001f);
+}
+// lg_focal: focal lengths in pixels.
+LG_HD void lg_focal(int W, int H, float tanfovx, float tanfovy, float& fx, float& fy)
+{
+    fx = (float)W / (2.0f * tanfovx); fy = (float)H / (2.0f * tanfovy);
+}
+
 // Result of projecting one Gaussian (K1).
 struct LgSplat {
     float x, y, depth;       // pixel-space mean, view-space z
@@ -219,17 +249,18 @@ template <bool AA>
 LG_HD bool lg_project_t(const float* vm, const float* pm, float px, float py, float pz, const float* cov3D, float opacity,
                         int W, int H, float tanfovx, float tanfovy, LgSplat& o, float& op_out)
 {
-    float vx = vm[0] * px + vm[4] * py + vm[8] * pz + vm[12];
-    float vy = vm[1] * px + vm[5] * py + vm[9] * pz + vm[13];
-    float vz = vm[2] * px + vm[6] * py + vm[10] * pz + vm[14];
+    float vx, vy, vz;
+    lg_view_point(vm, px, py, pz, vx, vy, vz);
     if (vz <= 0.2f) return false;
+    // (lg_hom_point's four lines, written out for K1: EXPERIMENTS 14)
     float hxm = pm[0] * px + pm[4] * py + pm[8] * pz + pm[12];
     float hym = pm[1] * px + pm[5] * py + pm[9] * pz + pm[13];
     float hwm = pm[3] * px + pm[7] * py + pm[11] * pz + pm[15];
     float p_w = 1.0f / (hwm + 0.0000001f);
     float ndcx = hxm * p_w, ndcy = hym * p_w;
 
-    const float fx = (float)W / (2.0f * tanfovx), fy = (float)H / (2.0f * tanfovy);
+    float fx, fy;
+    lg_focal(W, H, tanfovx, tanfovy, fx, fy);
     LgEwa e;
     lg_ewa(vm, vx, vy, vz, fx, fy, 1.3f * tanfovx, 1.3f * tanfovy, e);
     LgCov2D c2;
@@ -512,25 +543,40 @@ LG_HD void lg_abs_rows_to_grad(float sx, float sy, float op, int W, int H, float
     out[2] = 0.0f;
 }
 
+// The backward chain of one Gaussian from the blend-stage sums acc to dL/d(view-space mean): the ONE copy that lg_backward_geom_t (chains
+// it on to the mean and the 3D covariance) and lg_backward_camera_terms_t (chains it to the camera) call.  In order: the view-space
+// transform, lg_ewa and lg_cov2d; the conic -> (a, b, c) chain with its 1e-7 in d2inv; the antialias terms; dT = dL/d(T2 = J Wrot),
+// dJ, and dt with the clamp convention (the clamped txc / tyc in dtz, zeroed dtx / dty on clamped lanes: the +-1.3 tanfov clamp passes
+// no gradient).  A convention changes HERE, once.
 // AA (LG_FLAG_ANTIALIAS): acc[5] is dL/dop' of the compensated opacity op' = op rho; op = the input opacity (activated).  The three
-// terms of lg_aa_backward join dL_da, dL_db, dL_dc before they are chained to cov3D, T2 and the mean, and rho_out = rho, so that the
-// caller writes dL/dop = rho acc[5].  The +-1.3 tanfov clamp keeps its no-gradient convention (dtx, dty below).
-template <bool AA>
-LG_HD void lg_backward_geom_t(const float* vm, const float* pm, float px, float py, float pz, const float* S /*cov3D*/,
-                              const float* acc, int W, int H, float tanfovx, float tanfovy, LgGradOut& g, float op, float& rho_out)
-{
-    const float fx = (float)W / (2.0f * tanfovx), fy = (float)H / (2.0f * tanfovy);
-    const float gndx = acc[0] * (0.5f * (float)W), gndy = acc[1] * (0.5f * (float)H);
-    g.mean2D[0] = gndx; g.mean2D[1] = gndy;
-    float vx = vm[0] * px + vm[4] * py + vm[8] * pz + vm[12];
-    float vy = vm[1] * px + vm[5] * py + vm[9] * pz + vm[13];
-    float vz = vm[2] * px + vm[6] * py + vm[10] * pz + vm[14];
+// terms of lg_aa_backward join dL_da, dL_db, dL_dc before they are chained on -- rho depends on the view matrix through T2 and the
+// view-space mean as well --, and rho is kept so that the caller writes dL/dop = rho acc[5] (1 without AA).
+struct LgBackChain {
     LgEwa e;
-    lg_ewa(vm, vx, vy, vz, fx, fy, 1.3f * tanfovx, 1.3f * tanfovy, e);
     LgCov2D c2;
+    float fx, fy, vz;
+    float gndx, gndy;                 // dL/d(ndc x, y)
+    float dL_da, dL_db, dL_dc;
+    float dT0[3], dT1[3];             // dL/d(T2 rows)
+    float dtx, dty, dtz;
+    float rho;
+};
+template <bool AA>
+LG_HD void lg_backward_chain(const float* vm, float px, float py, float pz, const float* S /*cov3D*/, const float* acc, int W, int H,
+                             float tanfovx, float tanfovy, float op, LgBackChain& k)
+{
+    float fx, fy;
+    lg_focal(W, H, tanfovx, tanfovy, fx, fy);
+    k.fx = fx; k.fy = fy;
+    k.gndx = acc[0] * (0.5f * (float)W); k.gndy = acc[1] * (0.5f * (float)H);
+    float vx, vy, vz;
+    lg_view_point(vm, px, py, pz, vx, vy, vz);
+    k.vz = vz;
+    LgEwa& e = k.e;
+    lg_ewa(vm, vx, vy, vz, fx, fy, 1.3f * tanfovx, 1.3f * tanfovy, e);
+    LgCov2D& c2 = k.c2;
     lg_cov2d(e.T2, S, c2);
     const float a = c2.a, b = c2.b, c = c2.c;
-    const float* T2 = e.T2;
     const float gA = acc[2], gB = acc[3], gC = acc[4];
     float denom = a * c - b * b;
     float d2inv = 1.0f / (denom * denom + 0.0000001f);
@@ -540,32 +586,51 @@ LG_HD void lg_backward_geom_t(const float* vm, const float* pm, float px, float 
         dL_dc = d2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
         dL_db = d2inv * (2.0f * b * c * gA - (denom + 2.0f * b * b) * gB + 2.0f * a * b * gC);
     }
-    if (AA) rho_out = lg_aa_backward(c2.a0, b, c2.c0, a, c, op, acc[5], dL_da, dL_db, dL_dc);
+    k.rho = 1.0f;
+    if (AA) k.rho = lg_aa_backward(c2.a0, b, c2.c0, a, c, op, acc[5], dL_da, dL_db, dL_dc);
+    k.dL_da = dL_da; k.dL_db = dL_db; k.dL_dc = dL_dc;
+    const float* U = c2.U; const float* V = c2.V;
+    float* dT0 = k.dT0; float* dT1 = k.dT1;
+    for (int j = 0; j < 3; j++) {
+        dT0[j] = 2.0f * dL_da * U[j] + dL_db * V[j];
+        dT1[j] = dL_db * U[j] + 2.0f * dL_dc * V[j];
+    }
+    float dJ00 = dT0[0] * vm[0] + dT0[1] * vm[4] + dT0[2] * vm[8];
+    float dJ02 = dT0[0] * vm[2] + dT0[1] * vm[6] + dT0[2] * vm[10];
+    float dJ11 = dT1[0] * vm[1] + dT1[1] * vm[5] + dT1[2] * vm[9];
+    float dJ12 = dT1[0] * vm[2] + dT1[1] * vm[6] + dT1[2] * vm[10];
+    float tz = 1.0f / vz, tz2 = tz * tz, tz3 = tz2 * tz;
+    k.dtx = (e.xclamp ? 0.0f : 1.0f) * (-fx * tz2 * dJ02);
+    k.dty = (e.yclamp ? 0.0f : 1.0f) * (-fy * tz2 * dJ12);
+    k.dtz = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2.0f * fx * e.txc) * tz3 * dJ02 + (2.0f * fy * e.tyc) * tz3 * dJ12;
+}
+
+// dL/d(mean2D, mean3D, cov3D) of one Gaussian: lg_backward_chain, then its own three steps -- the cov3D assembly from T2, dm = vm^T dt,
+// and the projection term of the NDC gradient through the homogeneous divide.  rho_out is written only when AA.
+template <bool AA>
+LG_HD void lg_backward_geom_t(const float* vm, const float* pm, float px, float py, float pz, const float* S /*cov3D*/,
+                              const float* acc, int W, int H, float tanfovx, float tanfovy, LgGradOut& g, float op, float& rho_out)
+{
+    LgBackChain k;
+    lg_backward_chain<AA>(vm, px, py, pz, S, acc, W, H, tanfovx, tanfovy, op, k);
+    if (AA) rho_out = k.rho;
+    const float gndx = k.gndx, gndy = k.gndy;
+    g.mean2D[0] = gndx; g.mean2D[1] = gndy;
+    const float* T2 = k.e.T2;
+    const float dL_da = k.dL_da, dL_db = k.dL_db, dL_dc = k.dL_dc;
     g.cov3D[0] = T2[0] * T2[0] * dL_da + T2[0] * T2[3] * dL_db + T2[3] * T2[3] * dL_dc;
     g.cov3D[3] = T2[1] * T2[1] * dL_da + T2[1] * T2[4] * dL_db + T2[4] * T2[4] * dL_dc;
     g.cov3D[5] = T2[2] * T2[2] * dL_da + T2[2] * T2[5] * dL_db + T2[5] * T2[5] * dL_dc;
     g.cov3D[1] = 2.0f * T2[0] * T2[1] * dL_da + (T2[0] * T2[4] + T2[1] * T2[3]) * dL_db + 2.0f * T2[3] * T2[4] * dL_dc;
     g.cov3D[2] = 2.0f * T2[0] * T2[2] * dL_da + (T2[0] * T2[5] + T2[2] * T2[3]) * dL_db + 2.0f * T2[3] * T2[5] * dL_dc;
     g.cov3D[4] = 2.0f * T2[1] * T2[2] * dL_da + (T2[1] * T2[5] + T2[2] * T2[4]) * dL_db + 2.0f * T2[4] * T2[5] * dL_dc;
-    const float* U = c2.U; const float* V = c2.V;
-    float dT00 = 2.0f * dL_da * U[0] + dL_db * V[0], dT01 = 2.0f * dL_da * U[1] + dL_db * V[1], dT02 = 2.0f * dL_da * U[2] + dL_db * V[2];
-    float dT10 = dL_db * U[0] + 2.0f * dL_dc * V[0], dT11 = dL_db * U[1] + 2.0f * dL_dc * V[1], dT12 = dL_db * U[2] + 2.0f * dL_dc * V[2];
-    float dJ00 = dT00 * vm[0] + dT01 * vm[4] + dT02 * vm[8];
-    float dJ02 = dT00 * vm[2] + dT01 * vm[6] + dT02 * vm[10];
-    float dJ11 = dT10 * vm[1] + dT11 * vm[5] + dT12 * vm[9];
-    float dJ12 = dT10 * vm[2] + dT11 * vm[6] + dT12 * vm[10];
-    float tz = 1.0f / vz, tz2 = tz * tz, tz3 = tz2 * tz;
-    float dtx = (e.xclamp ? 0.0f : 1.0f) * (-fx * tz2 * dJ02);
-    float dty = (e.yclamp ? 0.0f : 1.0f) * (-fy * tz2 * dJ12);
-    float dtz = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2.0f * fx * e.txc) * tz3 * dJ02 + (2.0f * fy * e.tyc) * tz3 * dJ12;
+    const float dtx = k.dtx, dty = k.dty, dtz = k.dtz;
     float dmx = vm[0] * dtx + vm[1] * dty + vm[2] * dtz;
     float dmy = vm[4] * dtx + vm[5] * dty + vm[6] * dtz;
     float dmz = vm[8] * dtx + vm[9] * dty + vm[10] * dtz;
     {
-        float hxm = pm[0] * px + pm[4] * py + pm[8] * pz + pm[12];
-        float hym = pm[1] * px + pm[5] * py + pm[9] * pz + pm[13];
-        float hwm = pm[3] * px + pm[7] * py + pm[11] * pz + pm[15];
-        float m_w = 1.0f / (hwm + 0.0000001f);
+        float hxm, hym, m_w;
+        lg_hom_point(pm, px, py, pz, hxm, hym, m_w);
         float mul1 = hxm * m_w * m_w, mul2 = hym * m_w * m_w;
         dmx += (pm[0] * m_w - pm[3] * mul1) * gndx + (pm[1] * m_w - pm[3] * mul2) * gndy;
         dmy += (pm[4] * m_w - pm[7] * mul1) * gndx + (pm[5] * m_w - pm[7] * mul2) * gndy;
@@ -589,68 +654,37 @@ LG_HD void lg_backward_geom(const float* vm, const float* pm, float px, float py
 //     g_pm[4k+c] = p_k dh_c              g_pm[12+c] = dh_c
 //   g_cp = -d,  d = the view-direction term lg_backward_sh_jac adds to dmean (zeros for colors_precomp)
 // out[27]: g_vm columns 0..2 of rows 0..3 (12), g_pm columns 0, 1, 3 of rows 0..3 (12), g_cp (3); column 3 of vm and column 2 of pm take
-// no part in the forward.  The lines up to dtz and the projection block are lg_backward_geom's, term for term (the clamped txc / tyc,
-// zeroed dtx / dty on clamped lanes, the 1e-7 in d2inv): duplicated, not shared, so that every existing kernel stays as it was compiled.
+// no part in the forward.  Everything up to dtz is lg_backward_chain, the copy lg_backward_geom_t runs, and the homogeneous point is
+// lg_hom_point: the two functions cannot drift apart.  AA: as in lg_backward_chain.
 // In real arithmetic  dL/dmean3D = vm[:3,:3] g_vm[3,:3] + pm[:3,:] g_pm[3,:] - g_cp  (tests/test_camera_host.py).
 #define LG_CAM_TERMS 27
-// AA (LG_FLAG_ANTIALIAS): rho depends on the view matrix through T2 and the view-space mean -- the same three terms as in
-// lg_backward_geom_t join dL_da, dL_db, dL_dc (acc[5] = dL/dop', op = the input opacity).
 template <bool AA>
 LG_HD void lg_backward_camera_terms_t(const float* vm, const float* pm, float px, float py, float pz, const float* S /*cov3D*/,
                                       const float* acc, int W, int H, float tanfovx, float tanfovy, const float d[3], float* out /*[27]*/,
                                       float op)
 {
-    const float fx = (float)W / (2.0f * tanfovx), fy = (float)H / (2.0f * tanfovy);
-    const float gndx = acc[0] * (0.5f * (float)W), gndy = acc[1] * (0.5f * (float)H);
-    float vx = vm[0] * px + vm[4] * py + vm[8] * pz + vm[12];
-    float vy = vm[1] * px + vm[5] * py + vm[9] * pz + vm[13];
-    float vz = vm[2] * px + vm[6] * py + vm[10] * pz + vm[14];
-    LgEwa e;
-    lg_ewa(vm, vx, vy, vz, fx, fy, 1.3f * tanfovx, 1.3f * tanfovy, e);
-    LgCov2D c2;
-    lg_cov2d(e.T2, S, c2);
-    const float a = c2.a, b = c2.b, c = c2.c;
-    const float gA = acc[2], gB = acc[3], gC = acc[4];
-    float denom = a * c - b * b;
-    float d2inv = 1.0f / (denom * denom + 0.0000001f);
-    float dL_da = 0.0f, dL_db = 0.0f, dL_dc = 0.0f;
-    if (d2inv != 0.0f) {
-        dL_da = d2inv * (-c * c * gA + b * c * gB + (denom - a * c) * gC);
-        dL_dc = d2inv * (-a * a * gC + a * b * gB + (denom - a * c) * gA);
-        dL_db = d2inv * (2.0f * b * c * gA - (denom + 2.0f * b * b) * gB + 2.0f * a * b * gC);
-    }
-    if (AA) lg_aa_backward(c2.a0, b, c2.c0, a, c, op, acc[5], dL_da, dL_db, dL_dc);
-    const float* U = c2.U; const float* V = c2.V;
-    float dT0[3] = { 2.0f * dL_da * U[0] + dL_db * V[0], 2.0f * dL_da * U[1] + dL_db * V[1], 2.0f * dL_da * U[2] + dL_db * V[2] };
-    float dT1[3] = { dL_db * U[0] + 2.0f * dL_dc * V[0], dL_db * U[1] + 2.0f * dL_dc * V[1], dL_db * U[2] + 2.0f * dL_dc * V[2] };
-    float dJ00 = dT0[0] * vm[0] + dT0[1] * vm[4] + dT0[2] * vm[8];
-    float dJ02 = dT0[0] * vm[2] + dT0[1] * vm[6] + dT0[2] * vm[10];
-    float dJ11 = dT1[0] * vm[1] + dT1[1] * vm[5] + dT1[2] * vm[9];
-    float dJ12 = dT1[0] * vm[2] + dT1[1] * vm[6] + dT1[2] * vm[10];
-    float tz = 1.0f / vz, tz2 = tz * tz, tz3 = tz2 * tz;
-    float dtx = (e.xclamp ? 0.0f : 1.0f) * (-fx * tz2 * dJ02);
-    float dty = (e.yclamp ? 0.0f : 1.0f) * (-fy * tz2 * dJ12);
-    float dtz = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2.0f * fx * e.txc) * tz3 * dJ02 + (2.0f * fy * e.tyc) * tz3 * dJ12;
+    LgBackChain k;
+    lg_backward_chain<AA>(vm, px, py, pz, S, acc, W, H, tanfovx, tanfovy, op, k);
+    const float fx = k.fx, fy = k.fy, vz = k.vz, gndx = k.gndx, gndy = k.gndy, dtx = k.dtx, dty = k.dty, dtz = k.dtz;
+    const float* dT0 = k.dT0; const float* dT1 = k.dT1;
     // the J entries, exactly lg_ewa's expressions
-    const float J00 = fx / vz, J02 = -(fx * e.txc) / (vz * vz);
-    const float J11 = fy / vz, J12 = -(fy * e.tyc) / (vz * vz);
+    const float J00 = fx / vz, J02 = -(fx * k.e.txc) / (vz * vz);
+    const float J11 = fy / vz, J12 = -(fy * k.e.tyc) / (vz * vz);
     const float p[3] = { px, py, pz };
-    for (int k = 0; k < 3; k++) {
-        out[3 * k + 0] = p[k] * dtx + dT0[k] * J00;
-        out[3 * k + 1] = p[k] * dty + dT1[k] * J11;
-        out[3 * k + 2] = p[k] * dtz + dT0[k] * J02 + dT1[k] * J12;
+    for (int j = 0; j < 3; j++) {
+        out[3 * j + 0] = p[j] * dtx + dT0[j] * J00;
+        out[3 * j + 1] = p[j] * dty + dT1[j] * J11;
+        out[3 * j + 2] = p[j] * dtz + dT0[j] * J02 + dT1[j] * J12;
     }
     out[9] = dtx; out[10] = dty; out[11] = dtz;
-    float hxm = pm[0] * px + pm[4] * py + pm[8] * pz + pm[12];
-    float hym = pm[1] * px + pm[5] * py + pm[9] * pz + pm[13];
-    float hwm = pm[3] * px + pm[7] * py + pm[11] * pz + pm[15];
-    float m_w = 1.0f / (hwm + 0.0000001f);
+    float hxm, hym, m_w;
+    lg_hom_point(pm, px, py, pz, hxm, hym, m_w);
     float mul1 = hxm * m_w * m_w, mul2 = hym * m_w * m_w;
     const float dh[3] = { gndx * m_w, gndy * m_w, -(mul1 * gndx + mul2 * gndy) };
-    for (int k = 0; k < 3; k++) {
-        out[12 + 3 * k + 0] = p[k] * dh[0];
-        out[12 + 3 * k + 1] = p[k] * dh[1];
-        out[12 + 3 * k + 2] = p[k] * dh[2];
+    for (int j = 0; j < 3; j++) {
+        out[12 + 3 * j + 0] = p[j] * dh[0];
+        out[12 + 3 * j + 1] = p[j] * dh[1];
+        out[12 + 3 * j + 2] = p[j] * dh[2];
     }
     out[21] = dh[0]; out[22] = dh[1]; out[23] = dh[2];
     out[24] = -d[0]; out[25] = -d[1]; out[26] = -d[2];
@@ -667,9 +701,8 @@ LG_HD void lg_backward_cov3d(const float sc[3], float mod, const float q[4], con
 {
     float sv[3] = { mod * sc[0], mod * sc[1], mod * sc[2] };
     float r = q[0], x = q[1], y = q[2], z = q[3];
-    float Rm[9] = { 1.0f - 2.0f * (y * y + z * z), 2.0f * (x * y - r * z), 2.0f * (x * z + r * y),
-                    2.0f * (x * y + r * z), 1.0f - 2.0f * (x * x + z * z), 2.0f * (y * z - r * x),
-                    2.0f * (x * z - r * y), 2.0f * (y * z + r * x), 1.0f - 2.0f * (x * x + y * y) };
+    float Rm[9];
+    lg_quat_to_rot(q, Rm);
     float L[9];
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) L[3 * i + j] = Rm[3 * i + j] * sv[j];
     float Gs[9] = { dS[0], 0.5f * dS[1], 0.5f * dS[2], 0.5f * dS[1], dS[3], 0.5f * dS[4], 0.5f * dS[2], 0.5f * dS[4], dS[5] };
@@ -685,63 +718,82 @@ LG_HD void lg_backward_cov3d(const float sc[3], float mod, const float q[4], con
     drot[3] = 2.0f * (-2.0f * z * g[0] - r * g[1] + x * g[2] + r * g[3] - 2.0f * z * g[4] + y * g[5] + x * g[6] + y * g[7]);
 }
 
-// SH backward: writes dsh[M][3] through `store(k, c, value)` and accumulates the direction path
-// into dmean[3].  dRGB already has clamped channels zeroed.
-template <typename StoreFn>
-LG_HD void lg_backward_sh(int deg, const float* sh, float px, float py, float pz, const float* campos, const float dRGB[3],
-                          float dmean[3], StoreFn store)
+// ---------------------------------------------------------------------------------------------
+// SH backward, in four steps that are written ONCE each:
+//   lg_sh_dir          the offset o = mean - camera centre and the unit view direction (x, y, z) = o / |o|
+//   lg_sh_dir_deriv    d rgb_c / d (x, y, z) of channel c: needs the coefficients
+//   lg_sh_store_basis  dL/dsh[k][c] = basis_k(x, y, z) dRGB_c through store(k, c, value): needs no coefficient
+//   lg_sh_dir_to_mean  the gradient of the direction chained through the normalisation into dmean
+// (lg_sh_to_rgb, the forward, keeps its own direction and polynomial: another association, pinned against the oracle as it is.)
+struct LgShDir { float ox, oy, oz, x, y, z; };
+LG_HD LgShDir lg_sh_dir(float px, float py, float pz, const float* campos)
 {
-    float ox = px - campos[0], oy = py - campos[1], oz = pz - campos[2];
-    float len = sqrtf(ox * ox + oy * oy + oz * oz);
-    float x = ox / len, y = oy / len, z = oz / len;
-    float ddx = 0.0f, ddy = 0.0f, ddz = 0.0f;
-    for (int c = 0; c < 3; c++) {
-        const float d = dRGB[c];
-        float dRdx = 0.0f, dRdy = 0.0f, dRdz = 0.0f;
-        store(0, c, LG_SH_C0 * d);
-        if (deg > 0) {
-            store(1, c, -LG_SH_C1 * y * d);
-            store(2, c, LG_SH_C1 * z * d);
-            store(3, c, -LG_SH_C1 * x * d);
-            dRdx = -LG_SH_C1 * sh[3 * 3 + c];
-            dRdy = -LG_SH_C1 * sh[1 * 3 + c];
-            dRdz = LG_SH_C1 * sh[2 * 3 + c];
-            if (deg > 1) {
-                float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                store(4, c, LG_SH_C2_0 * xy * d);
-                store(5, c, LG_SH_C2_1 * yz * d);
-                store(6, c, LG_SH_C2_2 * (2.0f * zz - xx - yy) * d);
-                store(7, c, LG_SH_C2_3 * xz * d);
-                store(8, c, LG_SH_C2_4 * (xx - yy) * d);
-                dRdx += LG_SH_C2_0 * y * sh[4 * 3 + c] + LG_SH_C2_2 * 2.0f * -x * sh[6 * 3 + c] + LG_SH_C2_3 * z * sh[7 * 3 + c] +
-                        LG_SH_C2_4 * 2.0f * x * sh[8 * 3 + c];
-                dRdy += LG_SH_C2_0 * x * sh[4 * 3 + c] + LG_SH_C2_1 * z * sh[5 * 3 + c] + LG_SH_C2_2 * 2.0f * -y * sh[6 * 3 + c] +
-                        LG_SH_C2_4 * 2.0f * -y * sh[8 * 3 + c];
-                dRdz += LG_SH_C2_1 * y * sh[5 * 3 + c] + LG_SH_C2_2 * 2.0f * 2.0f * z * sh[6 * 3 + c] + LG_SH_C2_3 * x * sh[7 * 3 + c];
-                if (deg > 2) {
-                    store(9, c, LG_SH_C3_0 * y * (3.0f * xx - yy) * d);
-                    store(10, c, LG_SH_C3_1 * xy * z * d);
-                    store(11, c, LG_SH_C3_2 * y * (4.0f * zz - xx - yy) * d);
-                    store(12, c, LG_SH_C3_3 * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * d);
-                    store(13, c, LG_SH_C3_4 * x * (4.0f * zz - xx - yy) * d);
-                    store(14, c, LG_SH_C3_5 * z * (xx - yy) * d);
-                    store(15, c, LG_SH_C3_6 * x * (xx - 3.0f * yy) * d);
-                    dRdx += LG_SH_C3_0 * sh[9 * 3 + c] * 3.0f * 2.0f * xy + LG_SH_C3_1 * sh[10 * 3 + c] * yz +
-                            LG_SH_C3_2 * sh[11 * 3 + c] * -2.0f * xy + LG_SH_C3_3 * sh[12 * 3 + c] * -3.0f * 2.0f * xz +
-                            LG_SH_C3_4 * sh[13 * 3 + c] * (-3.0f * xx + 4.0f * zz - yy) + LG_SH_C3_5 * sh[14 * 3 + c] * 2.0f * xz +
-                            LG_SH_C3_6 * sh[15 * 3 + c] * 3.0f * (xx - yy);
-                    dRdy += LG_SH_C3_0 * sh[9 * 3 + c] * 3.0f * (xx - yy) + LG_SH_C3_1 * sh[10 * 3 + c] * xz +
-                            LG_SH_C3_2 * sh[11 * 3 + c] * (-3.0f * yy + 4.0f * zz - xx) +
-                            LG_SH_C3_3 * sh[12 * 3 + c] * -3.0f * 2.0f * yz + LG_SH_C3_4 * sh[13 * 3 + c] * -2.0f * xy +
-                            LG_SH_C3_5 * sh[14 * 3 + c] * -2.0f * yz + LG_SH_C3_6 * sh[15 * 3 + c] * -3.0f * 2.0f * xy;
-                    dRdz += LG_SH_C3_1 * sh[10 * 3 + c] * xy + LG_SH_C3_2 * sh[11 * 3 + c] * 4.0f * 2.0f * yz +
-                            LG_SH_C3_3 * sh[12 * 3 + c] * 3.0f * (2.0f * zz - xx - yy) +
-                            LG_SH_C3_4 * sh[13 * 3 + c] * 4.0f * 2.0f * xz + LG_SH_C3_5 * sh[14 * 3 + c] * (xx - yy);
-                }
+    LgShDir v;
+    v.ox = px - campos[0]; v.oy = py - campos[1]; v.oz = pz - campos[2];
+    float len = sqrtf(v.ox * v.ox + v.oy * v.oy + v.oz * v.oz);
+    v.x = v.ox / len; v.y = v.oy / len; v.z = v.oz / len;
+    return v;
+}
+LG_HD void lg_sh_dir_deriv(int deg, const float* sh, int c, float x, float y, float z, float& dRdx, float& dRdy, float& dRdz)
+{
+    dRdx = 0.0f; dRdy = 0.0f; dRdz = 0.0f;
+    if (deg > 0) {
+        dRdx = -LG_SH_C1 * sh[3 * 3 + c];
+        dRdy = -LG_SH_C1 * sh[1 * 3 + c];
+        dRdz = LG_SH_C1 * sh[2 * 3 + c];
+        if (deg > 1) {
+            float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            dRdx += LG_SH_C2_0 * y * sh[4 * 3 + c] + LG_SH_C2_2 * 2.0f * -x * sh[6 * 3 + c] + LG_SH_C2_3 * z * sh[7 * 3 + c] +
+                    LG_SH_C2_4 * 2.0f * x * sh[8 * 3 + c];
+            dRdy += LG_SH_C2_0 * x * sh[4 * 3 + c] + LG_SH_C2_1 * z * sh[5 * 3 + c] + LG_SH_C2_2 * 2.0f * -y * sh[6 * 3 + c] +
+                    LG_SH_C2_4 * 2.0f * -y * sh[8 * 3 + c];
+            dRdz += LG_SH_C2_1 * y * sh[5 * 3 + c] + LG_SH_C2_2 * 2.0f * 2.0f * z * sh[6 * 3 + c] + LG_SH_C2_3 * x * sh[7 * 3 + c];
+            if (deg > 2) {
+                dRdx += LG_SH_C3_0 * sh[9 * 3 + c] * 3.0f * 2.0f * xy + LG_SH_C3_1 * sh[10 * 3 + c] * yz +
+                        LG_SH_C3_2 * sh[11 * 3 + c] * -2.0f * xy + LG_SH_C3_3 * sh[12 * 3 + c] * -3.0f * 2.0f * xz +
+                        LG_SH_C3_4 * sh[13 * 3 + c] * (-3.0f * xx + 4.0f * zz - yy) + LG_SH_C3_5 * sh[14 * 3 + c] * 2.0f * xz +
+                        LG_SH_C3_6 * sh[15 * 3 + c] * 3.0f * (xx - yy);
+                dRdy += LG_SH_C3_0 * sh[9 * 3 + c] * 3.0f * (xx - yy) + LG_SH_C3_1 * sh[10 * 3 + c] * xz +
+                        LG_SH_C3_2 * sh[11 * 3 + c] * (-3.0f * yy + 4.0f * zz - xx) +
+                        LG_SH_C3_3 * sh[12 * 3 + c] * -3.0f * 2.0f * yz + LG_SH_C3_4 * sh[13 * 3 + c] * -2.0f * xy +
+                        LG_SH_C3_5 * sh[14 * 3 + c] * -2.0f * yz + LG_SH_C3_6 * sh[15 * 3 + c] * -3.0f * 2.0f * xy;
+                dRdz += LG_SH_C3_1 * sh[10 * 3 + c] * xy + LG_SH_C3_2 * sh[11 * 3 + c] * 4.0f * 2.0f * yz +
+                        LG_SH_C3_3 * sh[12 * 3 + c] * 3.0f * (2.0f * zz - xx - yy) +
+                        LG_SH_C3_4 * sh[13 * 3 + c] * 4.0f * 2.0f * xz + LG_SH_C3_5 * sh[14 * 3 + c] * (xx - yy);
             }
         }
-        ddx += dRdx * d; ddy += dRdy * d; ddz += dRdz * d;
     }
+}
+template <typename StoreFn>
+LG_HD void lg_sh_store_basis(int deg, int c, float x, float y, float z, float d, StoreFn store)
+{
+    store(0, c, LG_SH_C0 * d);
+    if (deg > 0) {
+        store(1, c, -LG_SH_C1 * y * d);
+        store(2, c, LG_SH_C1 * z * d);
+        store(3, c, -LG_SH_C1 * x * d);
+        if (deg > 1) {
+            float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            store(4, c, LG_SH_C2_0 * xy * d);
+            store(5, c, LG_SH_C2_1 * yz * d);
+            store(6, c, LG_SH_C2_2 * (2.0f * zz - xx - yy) * d);
+            store(7, c, LG_SH_C2_3 * xz * d);
+            store(8, c, LG_SH_C2_4 * (xx - yy) * d);
+            if (deg > 2) {
+                store(9, c, LG_SH_C3_0 * y * (3.0f * xx - yy) * d);
+                store(10, c, LG_SH_C3_1 * xy * z * d);
+                store(11, c, LG_SH_C3_2 * y * (4.0f * zz - xx - yy) * d);
+                store(12, c, LG_SH_C3_3 * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * d);
+                store(13, c, LG_SH_C3_4 * x * (4.0f * zz - xx - yy) * d);
+                store(14, c, LG_SH_C3_5 * z * (xx - yy) * d);
+                store(15, c, LG_SH_C3_6 * x * (xx - 3.0f * yy) * d);
+            }
+        }
+    }
+}
+LG_HD void lg_sh_dir_to_mean(const LgShDir& v, float ddx, float ddy, float ddz, float dmean[3])
+{
+    const float ox = v.ox, oy = v.oy, oz = v.oz;
     float sum2 = ox * ox + oy * oy + oz * oz;
     float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
     dmean[0] += ((sum2 - ox * ox) * ddx - oy * ox * ddy - oz * ox * ddz) * invsum32;
@@ -749,90 +801,58 @@ LG_HD void lg_backward_sh(int deg, const float* sh, float px, float py, float pz
     dmean[2] += (-ox * oz * ddx - oy * oz * ddy + (sum2 - oz * oz) * ddz) * invsum32;
 }
 
-
-// The part of lg_backward_sh that needs the SH coefficients -- d rgb_c / d (unit view direction), J[3 c + {0,1,2}] = {dRdx, dRdy, dRdz}
-// of channel c -- depends on forward-time quantities only.  K1 evaluates it next to the colours (the coefficients are in registers
+// d rgb_c / d (unit view direction), J[3 c + {0,1,2}] = {dRdx, dRdy, dRdz} of channel c: the part of the SH backward that needs the
+// coefficients, and it depends on forward-time quantities only.  K1 evaluates it next to the colours (the coefficients are in registers
 // there) and leaves 36 bytes per visible Gaussian; K9 then never reads the 12 M bytes of SH coefficients again (round 4: 388 MB per view at
-// C3).  The expressions are those of lg_backward_sh, term for term, so the values -- and the gradients -- are bit-identical.
+// C3).
 LG_HD void lg_sh_dir_jacobian(int deg, const float* sh, float px, float py, float pz, const float* campos, float J[9])
 {
-    float ox = px - campos[0], oy = py - campos[1], oz = pz - campos[2];
-    float len = sqrtf(ox * ox + oy * oy + oz * oz);
-    float x = ox / len, y = oy / len, z = oz / len;
-    for (int c = 0; c < 3; c++) {
-        float dRdx = 0.0f, dRdy = 0.0f, dRdz = 0.0f;
-        if (deg > 0) {
-            dRdx = -LG_SH_C1 * sh[3 * 3 + c];
-            dRdy = -LG_SH_C1 * sh[1 * 3 + c];
-            dRdz = LG_SH_C1 * sh[2 * 3 + c];
-            if (deg > 1) {
-                float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                dRdx += LG_SH_C2_0 * y * sh[4 * 3 + c] + LG_SH_C2_2 * 2.0f * -x * sh[6 * 3 + c] + LG_SH_C2_3 * z * sh[7 * 3 + c] +
-                        LG_SH_C2_4 * 2.0f * x * sh[8 * 3 + c];
-                dRdy += LG_SH_C2_0 * x * sh[4 * 3 + c] + LG_SH_C2_1 * z * sh[5 * 3 + c] + LG_SH_C2_2 * 2.0f * -y * sh[6 * 3 + c] +
-                        LG_SH_C2_4 * 2.0f * -y * sh[8 * 3 + c];
-                dRdz += LG_SH_C2_1 * y * sh[5 * 3 + c] + LG_SH_C2_2 * 2.0f * 2.0f * z * sh[6 * 3 + c] + LG_SH_C2_3 * x * sh[7 * 3 + c];
-                if (deg > 2) {
-                    dRdx += LG_SH_C3_0 * sh[9 * 3 + c] * 3.0f * 2.0f * xy + LG_SH_C3_1 * sh[10 * 3 + c] * yz +
-                            LG_SH_C3_2 * sh[11 * 3 + c] * -2.0f * xy + LG_SH_C3_3 * sh[12 * 3 + c] * -3.0f * 2.0f * xz +
-                            LG_SH_C3_4 * sh[13 * 3 + c] * (-3.0f * xx + 4.0f * zz - yy) + LG_SH_C3_5 * sh[14 * 3 + c] * 2.0f * xz +
-                            LG_SH_C3_6 * sh[15 * 3 + c] * 3.0f * (xx - yy);
-                    dRdy += LG_SH_C3_0 * sh[9 * 3 + c] * 3.0f * (xx - yy) + LG_SH_C3_1 * sh[10 * 3 + c] * xz +
-                            LG_SH_C3_2 * sh[11 * 3 + c] * (-3.0f * yy + 4.0f * zz - xx) +
-                            LG_SH_C3_3 * sh[12 * 3 + c] * -3.0f * 2.0f * yz + LG_SH_C3_4 * sh[13 * 3 + c] * -2.0f * xy +
-                            LG_SH_C3_5 * sh[14 * 3 + c] * -2.0f * yz + LG_SH_C3_6 * sh[15 * 3 + c] * -3.0f * 2.0f * xy;
-                    dRdz += LG_SH_C3_1 * sh[10 * 3 + c] * xy + LG_SH_C3_2 * sh[11 * 3 + c] * 4.0f * 2.0f * yz +
-                            LG_SH_C3_3 * sh[12 * 3 + c] * 3.0f * (2.0f * zz - xx - yy) +
-                            LG_SH_C3_4 * sh[13 * 3 + c] * 4.0f * 2.0f * xz + LG_SH_C3_5 * sh[14 * 3 + c] * (xx - yy);
-                }
-            }
-        }
-        J[3 * c] = dRdx; J[3 * c + 1] = dRdy; J[3 * c + 2] = dRdz;
-    }
+    const LgShDir v = lg_sh_dir(px, py, pz, campos);
+    for (int c = 0; c < 3; c++) lg_sh_dir_deriv(deg, sh, c, v.x, v.y, v.z, J[3 * c], J[3 * c + 1], J[3 * c + 2]);
 }
 
-// lg_backward_sh with the direction Jacobian handed in (lg_sh_dir_jacobian) instead of the coefficients: dL/dSH through store(k, c, value),
-// the view-direction term into dmean[3].  Same operations in the same order as lg_backward_sh.
+// SH backward with the direction Jacobian handed in (lg_sh_dir_jacobian): dL/dSH through store(k, c, value), the view-direction term into
+// dmean[3].  dRGB already has clamped channels zeroed.
 template <typename StoreFn>
 LG_HD void lg_backward_sh_jac(int deg, const float J[9], float px, float py, float pz, const float* campos, const float dRGB[3],
                               float dmean[3], StoreFn store)
 {
-    float ox = px - campos[0], oy = py - campos[1], oz = pz - campos[2];
-    float len = sqrtf(ox * ox + oy * oy + oz * oz);
-    float x = ox / len, y = oy / len, z = oz / len;
+    const LgShDir v = lg_sh_dir(px, py, pz, campos);
     float ddx = 0.0f, ddy = 0.0f, ddz = 0.0f;
     for (int c = 0; c < 3; c++) {
         const float d = dRGB[c];
-        store(0, c, LG_SH_C0 * d);
-        if (deg > 0) {
-            store(1, c, -LG_SH_C1 * y * d);
-            store(2, c, LG_SH_C1 * z * d);
-            store(3, c, -LG_SH_C1 * x * d);
-            if (deg > 1) {
-                float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                store(4, c, LG_SH_C2_0 * xy * d);
-                store(5, c, LG_SH_C2_1 * yz * d);
-                store(6, c, LG_SH_C2_2 * (2.0f * zz - xx - yy) * d);
-                store(7, c, LG_SH_C2_3 * xz * d);
-                store(8, c, LG_SH_C2_4 * (xx - yy) * d);
-                if (deg > 2) {
-                    store(9, c, LG_SH_C3_0 * y * (3.0f * xx - yy) * d);
-                    store(10, c, LG_SH_C3_1 * xy * z * d);
-                    store(11, c, LG_SH_C3_2 * y * (4.0f * zz - xx - yy) * d);
-                    store(12, c, LG_SH_C3_3 * z * (2.0f * zz - 3.0f * xx - 3.0f * yy) * d);
-                    store(13, c, LG_SH_C3_4 * x * (4.0f * zz - xx - yy) * d);
-                    store(14, c, LG_SH_C3_5 * z * (xx - yy) * d);
-                    store(15, c, LG_SH_C3_6 * x * (xx - 3.0f * yy) * d);
-                }
-            }
-        }
+        lg_sh_store_basis(deg, c, v.x, v.y, v.z, d, store);
         ddx += J[3 * c] * d; ddy += J[3 * c + 1] * d; ddz += J[3 * c + 2] * d;
     }
-    float sum2 = ox * ox + oy * oy + oz * oz;
-    float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-    dmean[0] += ((sum2 - ox * ox) * ddx - oy * ox * ddy - oz * ox * ddz) * invsum32;
-    dmean[1] += (-ox * oy * ddx + (sum2 - oy * oy) * ddy - oz * oy * ddz) * invsum32;
-    dmean[2] += (-ox * oz * ddx - oy * oz * ddy + (sum2 - oz * oz) * ddz) * invsum32;
+    lg_sh_dir_to_mean(v, ddx, ddy, ddz, dmean);
+}
+
+// SH backward from the coefficients: the two functions above, one after the other -- bit-identical to the saved-Jacobian path by
+// construction (tests/test_gpu_call_shapes.py asserts it on the device).
+template <typename StoreFn>
+LG_HD void lg_backward_sh(int deg, const float* sh, float px, float py, float pz, const float* campos, const float dRGB[3],
+                          float dmean[3], StoreFn store)
+{
+    float J[9];
+    lg_sh_dir_jacobian(deg, sh, px, py, pz, campos, J);
+    lg_backward_sh_jac(deg, J, px, py, pz, campos, dRGB, dmean, store);
+}
+// The same values from the same four steps in ONE pass over the channels, for a store that is not a register array (lg_vq_color_bwd.h's
+// LDS tile: EXPERIMENTS 14).
+template <typename StoreFn>
+LG_HD void lg_backward_sh_one_pass(int deg, const float* sh, float px, float py, float pz, const float* campos, const float dRGB[3],
+                                   float dmean[3], StoreFn store)
+{
+    const LgShDir v = lg_sh_dir(px, py, pz, campos);
+    float ddx = 0.0f, ddy = 0.0f, ddz = 0.0f;
+    for (int c = 0; c < 3; c++) {
+        const float d = dRGB[c];
+        float dRdx, dRdy, dRdz;
+        lg_sh_dir_deriv(deg, sh, c, v.x, v.y, v.z, dRdx, dRdy, dRdz);
+        lg_sh_store_basis(deg, c, v.x, v.y, v.z, d, store);
+        ddx += dRdx * d; ddy += dRdy * d; ddz += dRdz * d;
+    }
+    lg_sh_dir_to_mean(v, ddx, ddy, ddz, dmean);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -847,14 +867,13 @@ LG_HD void lg_backward_sh_jac(int deg, const float J[9], float px, float py, flo
 LG_HD void lg_densify_child_xyz(const float q_raw[4], const float s[3], const float noise[3], const float xyz[3], float out[3])
 {
     const float n = sqrtf(q_raw[0] * q_raw[0] + q_raw[1] * q_raw[1] + q_raw[2] * q_raw[2] + q_raw[3] * q_raw[3]);
-    const float r = q_raw[0] / n, x = q_raw[1] / n, y = q_raw[2] / n, z = q_raw[3] / n;
+    const float q[4] = { q_raw[0] / n, q_raw[1] / n, q_raw[2] / n, q_raw[3] / n };
     const float v0 = noise[0] * s[0], v1 = noise[1] * s[1], v2 = noise[2] * s[2];
-    const float R00 = 1.0f - 2.0f * (y * y + z * z), R01 = 2.0f * (x * y - r * z), R02 = 2.0f * (x * z + r * y);
-    const float R10 = 2.0f * (x * y + r * z), R11 = 1.0f - 2.0f * (x * x + z * z), R12 = 2.0f * (y * z - r * x);
-    const float R20 = 2.0f * (x * z - r * y), R21 = 2.0f * (y * z + r * x), R22 = 1.0f - 2.0f * (x * x + y * y);
-    out[0] = ((R00 * v0 + R01 * v1) + R02 * v2) + xyz[0];
-    out[1] = ((R10 * v0 + R11 * v1) + R12 * v2) + xyz[1];
-    out[2] = ((R20 * v0 + R21 * v1) + R22 * v2) + xyz[2];
+    float R[9];
+    lg_quat_to_rot(q, R);
+    out[0] = ((R[0] * v0 + R[1] * v1) + R[2] * v2) + xyz[0];
+    out[1] = ((R[3] * v0 + R[4] * v1) + R[5] * v2) + xyz[1];
+    out[2] = ((R[6] * v0 + R[7] * v1) + R[8] * v2) + xyz[2];
 }
 LG_HD float lg_densify_child_scaling(float s) { return logf(s / LG_DENSIFY_SHRINK); }
 

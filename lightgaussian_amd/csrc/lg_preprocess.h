@@ -154,9 +154,7 @@ lg_preprocess(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, f
     const int rowf = split ? 3 * (M - 1) : 3 * M;          // floats per LDS-staged row
     if (!DIRECT && !skip_color && shs && vmask && rowf > 0) {
         stage_sh_rows(split ? shs_rest : shs, i0, min(LG_PP, N - i0), rowf, vmask, sh_rows, lane);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        lg_wave_lds_sync();
     }
     uint32_t touched = 0;
     if (i < N) {
@@ -218,9 +216,7 @@ lg_preprocess(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, f
     // 16-byte stores (per-lane 48-byte-stride stores measured 0.26 -> 0.22 ms for the whole kernel).  Entries of
     // invisible Gaussians carry stale LDS contents; nothing reads them (touched == 0).
     if (vmask) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        lg_wave_lds_sync();
         const int nrec = min(LG_PP, N - i0);
 #pragma unroll
         for (int k = 0; k < 3; k++)
@@ -366,12 +362,30 @@ __device__ __forceinline__ void lg_k9_jac_row(const float* shjac, int i, float (
 }
 
 
+// How dL/dSH rows leave K9 and lg_sh_grad_from_rgb_kernel: nfl floats from the wave's LDS rows to dst, coalesced -- 16-byte stores and a
+// scalar remainder when dst is 16-byte aligned, scalars otherwise.  NT: non-temporal 16-byte stores.  After lg_wave_lds_sync().
+template <bool NT>
+__device__ __forceinline__ void lg_sh_rows_flush(const float* sh_rows, float* dst, int nfl, uint32_t lane)
+{
+    typedef float lg_f4v __attribute__((ext_vector_type(4)));
+    if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
+        const int nvec = nfl >> 2;
+        for (int q = (int)lane; q < nvec; q += LG_PP) {
+            if (NT) __builtin_nontemporal_store(reinterpret_cast<const lg_f4v*>(sh_rows)[q], reinterpret_cast<lg_f4v*>(dst) + q);
+            else reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(sh_rows)[q];
+        }
+        for (int f = (nvec << 2) + (int)lane; f < nfl; f += LG_PP) dst[f] = sh_rows[f];
+    } else {
+        for (int f = (int)lane; f < nfl; f += LG_PP) dst[f] = sh_rows[f];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K8 + K9 fused: per-Gaussian backward.  One wave per workgroup; SH rows in and dL/dSH rows out go
 // through LDS so that global traffic is coalesced 16-byte accesses.
-// Registers: JAC = false (the SH coefficients are re-read, sh[48] lives in registers) 155 VGPRs -> 3 waves/SIMD; forcing 4
-// (-DLG_K9_WAVES=4: 128 VGPRs, 76 B/lane of scratch) was measured in round 3: 0.384 -> 0.594 ms -- the spills cost more than the
-// fourth wave hides.  JAC = true (the default of every differentiated render since round 4: no coefficients, no input staging) 107 VGPRs
+// Registers: JAC = false (the SH coefficients are re-read, sh[48] lives in registers) 110-114 VGPRs, no scratch: lg_backward_sh is done
+// with sh[48] before dsh[48] fills (EXPERIMENTS 14; 155 VGPRs before, and forcing those into 128 spilled: 0.384 -> 0.594 ms, round 3).
+// JAC = true (the default of every differentiated render since round 4: no coefficients, no input staging) 107 VGPRs
 // -> 4 waves/SIMD.  Reading the SH rows directly per lane as K1 does (JAC = false only) was measured: 0.380 vs 0.380 ms.
 // AA (LG_FLAG_ANTIALIAS; the view of a backward is the view of its forward): the record's opacity is op' = op rho, so the rows give
 // dL/dop'; op and rho are recomputed from the inputs, as the covariance is (lg_backward_geom_t<true>, lg_math.h) -- the geom buffer
@@ -419,9 +433,7 @@ lg_preprocess_bwd(int N, int first_blk, int M, int D, int W, int H, float tanfov
     // a backward with another segment length.
     if (use_sh && !JAC && vmask && rowf > 0) {
         stage_sh_rows(split ? shs_rest : shs, i0, rows, rowf, vmask, sh_rows, lane);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        lg_wave_lds_sync();
     }
     const uint32_t my_t = vis ? touched[i] : 0u;
     const uint32_t my_u0 = vis ? offsets[i] - my_t : 0u;
@@ -514,6 +526,7 @@ lg_preprocess_bwd(int N, int first_blk, int M, int D, int W, int H, float tanfov
 #pragma unroll
         for (int hf = 0; hf < HALVES; hf++) {
             if ((int)(lane / HROWS) == hf) {
+                // (these lines are lg_sh_grad_from_rgb_kernel's too; why they are not one function: EXPERIMENTS 14)
                 float* row = sh_rows + (lane % HROWS) * rowf;
                 if (split) {
 #pragma unroll
@@ -529,30 +542,16 @@ lg_preprocess_bwd(int N, int first_blk, int M, int D, int W, int H, float tanfov
                         if (k < rowf) row[k] = dsh[k];
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            lg_wave_lds_sync();
             const int r0 = hf * HROWS;                                       // first row of this half inside the workgroup
             float* dst = (split ? dL_dshs_rest : dL_dshs) + ((size_t)i0 + r0) * rowf;
             const int nfl = max(0, min(HROWS, rows - r0)) * rowf;
-            if (nfl > 0) {
-                if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-                    const int nvec = nfl >> 2;
-                    // gradient rows are written once and read next by the optimizer, long after this view: non-temporal stores (round 4).
-                    // This kernel itself does not get faster (0.386 vs 0.388 ms) -- the NEXT view's K1 does, 0.204 -> 0.195 ms: 576 MB of
-                    // gradients no longer push its inputs out of the cache
-                    typedef float lg_f4v __attribute__((ext_vector_type(4)));
-                    for (int q = (int)lane; q < nvec; q += LG_PP)
-                        __builtin_nontemporal_store(reinterpret_cast<const lg_f4v*>(sh_rows)[q], reinterpret_cast<lg_f4v*>(dst) + q);
-                    for (int f = (nvec << 2) + (int)lane; f < nfl; f += LG_PP) dst[f] = sh_rows[f];
-                } else {
-                    for (int f = (int)lane; f < nfl; f += LG_PP) dst[f] = sh_rows[f];
-                }
-            }
+            // gradient rows are written once and read next by the optimizer, long after this view: non-temporal stores (round 4).
+            // This kernel itself does not get faster (0.386 vs 0.388 ms) -- the NEXT view's K1 does, 0.204 -> 0.195 ms: 576 MB of
+            // gradients no longer push its inputs out of the cache
+            if (nfl > 0) lg_sh_rows_flush<true>(sh_rows, dst, nfl, lane);
             if (hf + 1 < HALVES) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();             // the copy has read the rows before the next half overwrites them
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                lg_wave_lds_sync();             // the copy has read the rows before the next half overwrites them
             }
         }
     }
@@ -603,9 +602,7 @@ lg_sh_grad_from_rgb_kernel(int N, int M, int D, int V, const float* __restrict__
             const float* src = (split ? dL_dshs_rest : dL_dshs) + (size_t)i0 * rowf;
             const int nfl = rows * rowf;
             for (int f = (int)lane; f < nfl; f += LG_PP) sh_rows[f] = src[f];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            lg_wave_lds_sync();
             const float* row = sh_rows + lane * rowf;
             if (i < N) {
 #pragma unroll
@@ -655,16 +652,6 @@ lg_sh_grad_from_rgb_kernel(int N, int M, int D, int V, const float* __restrict__
         for (int k = 0; k < LG_SH_MAXF; k++)
             if (k < rowf) row[k] = dsh[k];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float* dst = (split ? dL_dshs_rest : dL_dshs) + (size_t)i0 * rowf;
-    const int nfl = rows * rowf;
-    if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-        const int nvec = nfl >> 2;
-        for (int q = (int)lane; q < nvec; q += LG_PP) reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(sh_rows)[q];
-        for (int f = (nvec << 2) + (int)lane; f < nfl; f += LG_PP) dst[f] = sh_rows[f];
-    } else {
-        for (int f = (int)lane; f < nfl; f += LG_PP) dst[f] = sh_rows[f];
-    }
+    lg_wave_lds_sync();
+    lg_sh_rows_flush<false>(sh_rows, (split ? dL_dshs_rest : dL_dshs) + (size_t)i0 * rowf, rows * rowf, lane);
 }

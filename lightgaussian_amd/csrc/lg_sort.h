@@ -23,6 +23,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "lg_wave.h"
 
 #ifndef LG_SORT_BLOCK
 #define LG_SORT_BLOCK 1024
@@ -153,19 +154,19 @@ lg_onesweep_pass(const uint64_t* __restrict__ src, uint64_t* __restrict__ dst, c
         const bool valid = idx < tile_n;
         const uint32_t d = (uint32_t)(key[k] >> shift) & dmask;
         if (valid) atomicOr(&mask[d], mybit);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        lg_wave_lds_sync();
         unsigned long long peers = 0;
         uint32_t prev = 0;
         if (valid) { peers = mask[d]; prev = wcnt[wave][d]; }               // every peer reads the set and the old count ...
         const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(peers >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)peers, 0u));
+        // release + barrier without the acquire (so not lg_wave_lds_sync): the LDS accesses above must be done first; no read below depends on them
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if (valid && below == 0u) {                                         // ... the lowest one bumps the count and clears the set
             wcnt[wave][d] = (unsigned short)(prev + (uint32_t)__popcll(peers));
             mask[d] = 0ull;
         }
+        // release + barrier without the acquire (so not lg_wave_lds_sync): the LDS accesses above must be done first; no read below depends on them
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         rnk[k] = prev + below;

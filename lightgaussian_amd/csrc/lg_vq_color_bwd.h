@@ -97,7 +97,7 @@ lg_vq_index_ids(uint32_t N, const uint64_t* __restrict__ sorted, const uint32_t*
     if (q < N) ids[q] = (uint32_t)sorted[q];
 }
 
-// One Gaussian's share: the fp16 row -> [M][3] floats, the clamp from lg_sh_to_rgb, lg_backward_sh with `store` writing
+// One Gaussian's share: the fp16 row -> [M][3] floats, the clamp from lg_sh_to_rgb, lg_backward_sh (its one-pass form) with `store` writing
 // tile[lg_vq_row_index(M, k, c)] (the file's column order), the direction term into dm.  The caller zeroed the tile row.
 template <int M>
 __device__ __forceinline__ void lg_vq_bwd_one(int D, uint32_t need, const float* __restrict__ means3D, const float* cp,
@@ -126,7 +126,7 @@ __device__ __forceinline__ void lg_vq_bwd_one(int D, uint32_t need, const float*
     lg_sh_to_rgb(D, sh, px, py, pz, cp, rgb, cb);
     const float g0 = dL_drgb[3 * (size_t)i], g1 = dL_drgb[3 * (size_t)i + 1], g2 = dL_drgb[3 * (size_t)i + 2];
     const float dRGB[3] = { (cb & 1u) ? 0.0f : g0, (cb & 2u) ? 0.0f : g1, (cb & 4u) ? 0.0f : g2 };
-    lg_backward_sh(D, sh, px, py, pz, cp, dRGB, dm, [&](int k, int c, float v) { tile_row[lg_vq_row_index(M, k, c)] = v; });
+    lg_backward_sh_one_pass(D, sh, px, py, pz, cp, dRGB, dm, [&](int k, int c, float v) { tile_row[lg_vq_row_index(M, k, c)] = v; });
 }
 
 // lane per Gaussian: dL/dxyz of every Gaussian, the gradient row of a non-VQ one (through LDS, see the head of the file)

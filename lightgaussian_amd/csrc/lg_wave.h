@@ -38,3 +38,13 @@ __device__ __forceinline__ uint32_t dpp_add_u32(uint32_t v)
 {
     return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
 }
+
+// LDS hand-over inside ONE wave: what its lanes wrote to LDS before the call is what every lane reads after it.  Release fence, wave
+// barrier, acquire fence, all at wavefront scope: no s_barrier is issued -- the trio only keeps the compiler (and the LDS counter waits it
+// places) from moving an LDS access across.  Sites with another scope or without the acquire say so where they stand.
+__device__ __forceinline__ void lg_wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}

@@ -9,6 +9,7 @@ the gradients are flattened into buckets of `bucket_bytes` (default 512 MiB, i.e
 """
 import torch
 import torch.distributed as dist
+from . import sh_utils
 
 
 def shard_views(num_views, world_size, rank):
@@ -237,22 +238,12 @@ class OverlappedGradAllReduce:
 # behind that view's K9 and runs while view k + 1 renders (a camera batch per rank: `views_per_rank` in dp / bench.py).
 
 def _sh_basis_rows(dirs, deg):
-    """[V?, N, (deg+1)^2] real SH basis in the reference's convention (utils/sh_utils.py:26-54,74-103), float32 torch ops.
+    """[V?, N, (deg+1)^2] real SH basis in the reference's convention, float32 torch ops: the constants and polynomial forms of sh_utils.
     CHECKER ONLY: the CPU side of the gloo tests; CUDA tensors go through lg_sh_grad_from_rgb."""
-    C0, C1 = 0.28209479177387814, 0.4886025119029199
-    C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396)
-    C3 = (-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154, -0.4570457994644658, 1.445305721320277,
-          -0.5900435899266435)
     x, y, z = dirs[..., 0], dirs[..., 1], dirs[..., 2]
-    out = [torch.full_like(x, C0)]
-    if deg > 0:
-        out += [-C1 * y, C1 * z, -C1 * x]
-    if deg > 1:
-        xx, yy, zz, xy, yz, xz = x * x, y * y, z * z, x * y, y * z, x * z
-        out += [C2[0] * xy, C2[1] * yz, C2[2] * (2.0 * zz - xx - yy), C2[3] * xz, C2[4] * (xx - yy)]
-        if deg > 2:
-            out += [C3[0] * y * (3.0 * xx - yy), C3[1] * xy * z, C3[2] * y * (4.0 * zz - xx - yy), C3[3] * z * (2.0 * zz - 3.0 * xx - 3.0 * yy),
-                    C3[4] * x * (4.0 * zz - xx - yy), C3[5] * z * (xx - yy), C3[6] * x * (xx - 3.0 * yy)]
+    out = [torch.full_like(x, sh_utils.SH_C0)]
+    for k, f1, f2 in sh_utils._basis_table(x, y, z)[:(deg + 1) ** 2 - 1]:     # the table's own association: (k f1) f2
+        out.append(k * f1 if f2 is None else k * f1 * f2)
     return torch.stack(out, dim=-1)
 
 

@@ -97,13 +97,20 @@ def build_harness(name, *, headers, flags, signatures):
     return _HARNESSES[name]
 
 
-def harness():
-    """The product's lg_math.h compiled for the CPU."""
+def math_signatures():
+    """The symbols of lg_math_harness.cpp."""
     P, I, F = C.c_void_p, C.c_int, C.c_float
-    return build_harness("math", headers=(LG_MATH_H,), flags=STRICT_FP_FMA, signatures={
+    return {
         "h_exp": (F, [F]), "h_seqsum32": (F, [F, C.c_uint32]), "h_fix40_quant": (C.c_uint64, [F]), "h_fix40_score": (F, [C.c_uint64]),
         "h_forward": (I, [I] * 5 + [P] * 6 + [F] + [P] * 5 + [F, F, I] + [P] * 10),
-        "h_backward_geom": (None, [I] * 5 + [P, P, P, F, P, P, P, P, P, P, P, F, F, P] + [P] * 6)})
+        "h_backward_geom": (None, [I] * 5 + [P, P, P, F, P, P, P, P, P, P, P, F, F, P] + [P] * 6),
+        "h_geom": (None, [I, I] + [P] * 5 + [I, I, F, F, P, P]), "h_camera": (None, [I, I] + [P] * 5 + [I, I, F, F, P, P, P]),
+        "h_cov3d": (None, [I, P, F] + [P] * 5), "h_sh_bwd": (None, [I, I, I] + [P] * 7), "h_child_xyz": (None, [I] + [P] * 5)}
+
+
+def harness():
+    """The product's lg_math.h compiled for the CPU."""
+    return build_harness("math", headers=(LG_MATH_H,), flags=STRICT_FP_FMA, signatures=math_signatures())
 
 
 def plan_harness():

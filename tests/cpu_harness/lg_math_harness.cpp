@@ -134,4 +134,70 @@ void h_backward_geom(int N, int M, int D, int W, int H, const float* means3D, co
         for (int k = 0; k < 3; k++) dmeans3D[3 * i + k] = m3[k];
     }
 }
+
+// ---- the per-Gaussian backward functions one at a time, over arrays (tests/test_math_frozen_host.py pins their bits) ----
+// aa: -1 = the plain wrapper, 0 / 1 = the template with AA off / on.  out[12]: mean2D (2), mean3D (3), cov3D (6), rho (1.0 unless aa = 1).
+void h_geom(int N, int aa, const float* vm, const float* pm, const float* means3D, const float* cov3D, const float* acc, int W, int H,
+            float tanfovx, float tanfovy, const float* op, float* out)
+{
+    for (int i = 0; i < N; i++) {
+        const float *p = means3D + 3 * i, *S = cov3D + 6 * i, *a = acc + 9 * i;
+        LgGradOut go;
+        float rho = 1.0f;
+        if (aa < 0) lg_backward_geom(vm, pm, p[0], p[1], p[2], S, a, W, H, tanfovx, tanfovy, go);
+        else if (aa) lg_backward_geom_t<true>(vm, pm, p[0], p[1], p[2], S, a, W, H, tanfovx, tanfovy, go, op[i], rho);
+        else lg_backward_geom_t<false>(vm, pm, p[0], p[1], p[2], S, a, W, H, tanfovx, tanfovy, go, op[i], rho);
+        float* o = out + 12 * i;
+        o[0] = go.mean2D[0]; o[1] = go.mean2D[1];
+        for (int k = 0; k < 3; k++) o[2 + k] = go.mean3D[k];
+        for (int k = 0; k < 6; k++) o[5 + k] = go.cov3D[k];
+        o[11] = rho;
+    }
+}
+void h_camera(int N, int aa, const float* vm, const float* pm, const float* means3D, const float* cov3D, const float* acc, int W, int H,
+              float tanfovx, float tanfovy, const float* d, const float* op, float* out /*[N][27]*/)
+{
+    for (int i = 0; i < N; i++) {
+        const float *p = means3D + 3 * i, *S = cov3D + 6 * i, *a = acc + 9 * i;
+        float* o = out + LG_CAM_TERMS * i;
+        if (aa < 0) lg_backward_camera_terms(vm, pm, p[0], p[1], p[2], S, a, W, H, tanfovx, tanfovy, d + 3 * i, o);
+        else if (aa) lg_backward_camera_terms_t<true>(vm, pm, p[0], p[1], p[2], S, a, W, H, tanfovx, tanfovy, d + 3 * i, o, op[i]);
+        else lg_backward_camera_terms_t<false>(vm, pm, p[0], p[1], p[2], S, a, W, H, tanfovx, tanfovy, d + 3 * i, o, op[i]);
+    }
+}
+void h_cov3d(int N, const float* scales, float mod, const float* rotations, const float* dS, float* cov, float* dscale, float* drot)
+{
+    for (int i = 0; i < N; i++) {
+        lg_cov3d(scales + 3 * i, mod, rotations + 4 * i, cov + 6 * i);
+        lg_backward_cov3d(scales + 3 * i, mod, rotations + 4 * i, dS + 6 * i, dscale + 3 * i, drot + 4 * i);
+    }
+}
+// jac = 0: lg_backward_sh; jac = 1: lg_sh_dir_jacobian, then lg_backward_sh_jac with a real store (J [N][9] is written);
+// jac = 2: lg_backward_sh_one_pass.  shs [N][16][3]; dsh [N][(D+1)^2][3] and dmean [N][3] arrive zeroed.
+void h_sh_bwd(int N, int D, int jac, const float* shs, const float* means3D, const float* campos, const float* dRGB, float* dsh,
+              float* dmean, float* J)
+{
+    const int nf = (D + 1) * (D + 1) * 3;
+    for (int i = 0; i < N; i++) {
+        const float* p = means3D + 3 * i;
+        float sh[48];
+        for (int k = 0; k < 48; k++) sh[k] = (k < nf) ? shs[48 * (size_t)i + k] : 0.0f;
+        float* row = dsh + (size_t)nf * i;
+        auto store = [&](int k, int c, float v) { row[k * 3 + c] = v; };
+        if (jac == 1) {
+            lg_sh_dir_jacobian(D, sh, p[0], p[1], p[2], campos, J + 9 * i);
+            lg_backward_sh_jac(D, J + 9 * i, p[0], p[1], p[2], campos, dRGB + 3 * i, dmean + 3 * i, store);
+        } else if (jac == 2) {
+#ifndef LG_HARNESS_NO_ONE_PASS      // (the fixture generator defines it for a header from before the function existed, and asks for 0 and 1 only)
+            lg_backward_sh_one_pass(D, sh, p[0], p[1], p[2], campos, dRGB + 3 * i, dmean + 3 * i, store);
+#endif
+        } else {
+            lg_backward_sh(D, sh, p[0], p[1], p[2], campos, dRGB + 3 * i, dmean + 3 * i, store);
+        }
+    }
+}
+void h_child_xyz(int N, const float* q_raw, const float* s, const float* noise, const float* xyz, float* out)
+{
+    for (int i = 0; i < N; i++) lg_densify_child_xyz(q_raw + 4 * i, s + 3 * i, noise + 3 * i, xyz + 3 * i, out + 3 * i);
+}
 }
