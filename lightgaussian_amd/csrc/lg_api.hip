@@ -21,6 +21,7 @@
 //   lg_adam.h        lg_adam_step: one Adam / AdamW step over all parameter tensors of the model in one launch (table by value, dwordx4);
 //                    lg_adam_step_rows: the same step over the rows a byte mask names (row index: lg_adam_rows.h); both kernels are lg_adam_span<DECOUPLED, ROWS>
 //   lg_densify.h     lg_densify_stats / lg_densify_plan / lg_densify_rows: view statistics and clone / split / prune of densify_and_prune
+//   lg_mcmc.h        lg_mcmc_noise / lg_mcmc_plan / lg_mcmc_rows: 3DGS-MCMC position noise, relocation and growth (include/lightgaussian_mcmc.h)
 //   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT, ABS>   (per tile, VALU-bound); wave_reduce_via_lds<NV> (also lg_features.h's)
 //   lg_features.h    lg_features_fwd / _bwd / _gather: C further per-Gaussian channels blended over the lists a forward left, and dL/dfeatures
 //   lg_camera.h      lg_camera_bwd<RAW, AA> / lg_camera_reduce: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos from the rows a backward left, through lg_k9_* (float64 ordered sums)
@@ -56,6 +57,7 @@
 #include "lg_vq_color_bwd.h"
 #include "lg_adam.h"
 #include "lg_densify.h"
+#include "lg_mcmc.h"
 #include "lg_features.h"
 #include "lg_camera.h"
 #include "lg_absgrad.h"
@@ -1311,6 +1313,115 @@ extern "C" int lg_densify_rows(int32_t N, int64_t N_out, const void* map, const 
     ProfScope ps(prof, "densify_rows", stream);
     lg_densify_move<<<row_move_grid((size_t)N_out, widest, num_tensors), 256, 0, stream>>>(N_out, (const uint2*)map, record, a, rotation, scaling, noise, noise_rows);
     KLAUNCHED("lg_densify_move");
+    return LG_OK;
+}
+
+// ---- 3DGS-MCMC (lg_mcmc.h, include/lightgaussian_mcmc.h) ----
+struct McmcScratch { int32_t* cnt; float4* planned; size_t total; };
+static McmcScratch carve_mcmc(void* base, int32_t N)
+{
+    McmcScratch d; size_t off = 0; char* p = (char*)base;
+    auto take = [&](size_t bytes) { void* r = p ? p + off : nullptr; off += align_up(bytes); return r; };
+    const size_t n = (size_t)(N > 0 ? N : 1);
+    d.cnt = (int32_t*)take(n * 4);
+    d.planned = (float4*)take(n * 16);
+    d.total = off;
+    return d;
+}
+extern "C" size_t lg_mcmc_scratch_bytes(int32_t N) { return carve_mcmc(nullptr, N).total; }
+
+#define LG_MCMC_MAX_ROWS (1 << 30)
+extern "C" int lg_mcmc_noise(int32_t N, float* xyz, const float* scaling, const float* rotation, const float* opacity, const float* noise,
+                             float c, float k, float x0, uint32_t flags, void* stream_p)
+{
+    if (N < 0 || N >= LG_MCMC_MAX_ROWS) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_noise: N outside [0, 2^30)");
+    if (c != c || k != k || x0 != x0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_noise: a NaN among c, k, x0");
+    if (N == 0) return LG_OK;
+    if (!xyz) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_noise: null xyz");
+    if (!scaling) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_noise: null scaling");
+    if (!rotation) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_noise: null rotation");
+    if (!opacity) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_noise: null opacity");
+    if (!noise) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_noise: null noise");
+    if ((((uintptr_t)xyz | (uintptr_t)scaling | (uintptr_t)rotation | (uintptr_t)opacity | (uintptr_t)noise) & 3) != 0)
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_noise: xyz / scaling / rotation / opacity / noise must be 4-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool prof = flags & LG_FLAG_PROFILE;
+    ProfScope ps(prof, "mcmc_noise", stream);
+    lg_mcmc_noise_kernel<<<(unsigned)((N + 255) / 256), 256, 0, stream>>>(N, xyz, scaling, rotation, opacity, noise, c, k, x0);
+    KLAUNCHED("lg_mcmc_noise_kernel");
+    return LG_OK;
+}
+
+extern "C" int lg_mcmc_plan(int32_t N, int32_t n, const int32_t* src, const float* opacity, const float* scaling, float min_opacity,
+                            void* scratch, uint32_t flags, void* stream_p)
+{
+    if (N < 0 || N >= LG_MCMC_MAX_ROWS) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_plan: N outside [0, 2^30)");
+    if (n < 0 || (N == 0 && n > 0)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_plan: n < 0, or draws from an empty model");
+    if (!(min_opacity >= 0.0f && min_opacity < 1.0f)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_plan: min_opacity outside [0, 1)");
+    if (N == 0) return LG_OK;
+    if (n > 0 && !src) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_plan: null src");
+    if (!opacity) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_plan: null opacity");
+    if (!scaling) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_plan: null scaling");
+    if (!scratch) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_plan: null scratch");
+    if ((((uintptr_t)src | (uintptr_t)opacity | (uintptr_t)scaling) & 3) != 0 || ((uintptr_t)scratch & 15) != 0)
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_plan: misaligned src / opacity / scaling (4 bytes) or scratch (16)");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool prof = flags & LG_FLAG_PROFILE;
+    const McmcScratch d = carve_mcmc(scratch, N);
+    {
+        ProfScope ps(prof, "mcmc_count", stream);
+        HIP_TRY(lg_zero_async(d.cnt, (size_t)N * 4, stream));
+        if (n > 0) {
+            lg_mcmc_count_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(N, n, src, d.cnt);
+            KLAUNCHED("lg_mcmc_count_kernel");
+        }
+    }
+    if (n > 0) {
+        ProfScope ps(prof, "mcmc_plan", stream);
+        lg_mcmc_plan_kernel<<<(unsigned)((N + 255) / 256), 256, 0, stream>>>(N, d.cnt, opacity, scaling, min_opacity, d.planned);
+        KLAUNCHED("lg_mcmc_plan_kernel");
+    }
+    return LG_OK;
+}
+
+extern "C" int lg_mcmc_rows(int32_t N, int64_t N_out, int32_t n, const int32_t* dst, const int32_t* src, const void* scratch,
+                            int32_t num_tensors, const lg_densify_tensor* tensors, uint32_t flags, void* stream_p)
+{
+    if (N < 0 || N >= LG_MCMC_MAX_ROWS) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: N outside [0, 2^30)");
+    if (N_out < (int64_t)N || N_out > 0x7FFFFFFFll) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: N_out outside [N, 2^31)");
+    if (n < 0 || (N == 0 && n > 0)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: n < 0, or draws from an empty model");
+    if (num_tensors < 0 || num_tensors > LG_DENSIFY_MAX_TENSORS) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: num_tensors outside [0, 32]");
+    if (num_tensors > 0 && !tensors) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: null tensors");
+    const bool inplace = N_out == (int64_t)N;
+    if (N == 0 || num_tensors == 0 || (inplace && n == 0)) return LG_OK;
+    if (n > 0 && !dst) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: null dst");
+    if (n > 0 && !src) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: null src");
+    if (!scratch) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: null scratch");
+    if ((((uintptr_t)dst | (uintptr_t)src) & 3) != 0 || ((uintptr_t)scratch & 15) != 0)
+        return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: misaligned dst / src (4 bytes) or scratch (16)");
+    LgDensifyArgs a;
+    memset(&a, 0, sizeof(a));
+    size_t widest = 1;
+    for (int t = 0; t < num_tensors; t++) {
+        const lg_densify_tensor& x = tensors[t];
+        if (x.role < LG_MCMC_COPY || x.role > LG_MCMC_SCALING) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: tensors: unknown role");
+        if (x.row_words <= 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: tensors: row_words must be > 0 (leave empty tensors out)");
+        if (!x.src || !x.dst) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: tensors: null src / dst");
+        if ((((uintptr_t)x.src | (uintptr_t)x.dst) & 3) != 0) return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: tensors: src / dst must be 4-byte aligned");
+        if ((x.role == LG_MCMC_OPACITY && x.row_words != 1) || (x.role == LG_MCMC_SCALING && x.row_words != 3))
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: tensors: the opacity role needs row_words == 1, the scaling role 3");
+        if (inplace != (x.src == x.dst))
+            return fail(LG_ERR_INVALID_ARGUMENT, "lg_mcmc_rows: tensors: src == dst exactly when N_out == N (in place)");
+        a.src[t] = (const uint32_t*)x.src; a.dst[t] = (uint32_t*)x.dst; a.words[t] = (uint32_t)x.row_words; a.role[t] = (uint32_t)x.role;
+        widest = std::max<size_t>(widest, (size_t)x.row_words);
+    }
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool prof = flags & LG_FLAG_PROFILE;
+    const McmcScratch d = carve_mcmc(const_cast<void*>(scratch), N);
+    ProfScope ps(prof, "mcmc_rows", stream);
+    lg_mcmc_move<<<row_move_grid((inplace ? 0 : (size_t)N) + (size_t)n, widest, num_tensors), 256, 0, stream>>>(
+        N, N_out, n, dst, src, d.cnt, d.planned, a, inplace ? 1 : 0);
+    KLAUNCHED("lg_mcmc_move");
     return LG_OK;
 }
 

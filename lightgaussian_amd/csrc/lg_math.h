@@ -915,3 +915,64 @@ LG_HD bool lg_filter3d_term(const LgFilterCam& c, float px, float py, float pz, 
     t = z / c.fx;
     return z > LG_FILTER3D_NEAR && u >= c.ulo && u <= c.uhi && v >= c.vlo && v <= c.vhi;
 }
+
+// ---------------------------------------------------------------------------------------------
+// 3DGS-MCMC (lg_mcmc.h; Kheradmand et al. 2024): the per-row formulas of the position noise and of relocation.
+// Noise, float32, every product and sum rounded on its own:
+//   sigma = 1 / (1 + expf(-opacity_raw))     g = 1 / (1 + expf(-k ((1 - sigma) - x0)))     gate = g c
+//   (expf overflowing to +inf gives g = 1 / inf = 0, never NaN)
+//   v = noise * gate      xyz += R (s^2 o (R^T v))      R = R(q / |q|) as lg_densify_child_xyz builds it, s = exp(raw scaling)
+// which is Sigma v for Sigma = L L^T, L = R diag(s), without the 3x3 matrix.
+LG_HD float lg_mcmc_gate(float opacity_raw, float c, float k, float x0)
+{
+    const float sigma = 1.0f / (1.0f + expf(-opacity_raw));
+    const float g = 1.0f / (1.0f + expf(-k * ((1.0f - sigma) - x0)));
+    return g * c;
+}
+LG_HD void lg_mcmc_noise_xyz(const float q_raw[4], const float s[3], const float noise[3], float gate, const float xyz[3], float out[3])
+{
+    const float n = sqrtf(q_raw[0] * q_raw[0] + q_raw[1] * q_raw[1] + q_raw[2] * q_raw[2] + q_raw[3] * q_raw[3]);
+    const float q[4] = { q_raw[0] / n, q_raw[1] / n, q_raw[2] / n, q_raw[3] / n };
+    const float v0 = noise[0] * gate, v1 = noise[1] * gate, v2 = noise[2] * gate;
+    float R[9];
+    lg_quat_to_rot(q, R);
+    const float t0 = (s[0] * s[0]) * ((R[0] * v0 + R[3] * v1) + R[6] * v2);       // s^2 o (R^T v)
+    const float t1 = (s[1] * s[1]) * ((R[1] * v0 + R[4] * v1) + R[7] * v2);
+    const float t2 = (s[2] * s[2]) * ((R[2] * v0 + R[5] * v1) + R[8] * v2);
+    out[0] = xyz[0] + ((R[0] * t0 + R[1] * t1) + R[2] * t2);
+    out[1] = xyz[1] + ((R[3] * t0 + R[4] * t1) + R[5] * t2);
+    out[2] = xyz[2] + ((R[6] * t0 + R[7] * t1) + R[8] * t2);
+}
+
+// Relocation of a row drawn cnt >= 1 times: in DOUBLE from the float32 raw inputs, each output rounded once.
+//   M = min(cnt + 1, 51)     o = sigmoid(opacity_raw)     x = 1 - (1 - o)^(1/M)
+//   D = sum_{k=0..M-1} C(M, k+1) (-1)^k x^(k+1) / sqrt(k+1)
+//       (the published double sum over i = 1..M and k = 0..i-1 of C(i-1, k) ..., collapsed by sum_i C(i-1, k) = C(M, k+1))
+//   opacity_raw' = logit(clamp(x, min_opacity, 1 - 2^-23))          scaling_raw' = scaling_raw + log(o / D), o / D from the unclamped x
+// 1 - o = 1 / (1 + exp(raw)) is formed directly and x = -expm1(-log1p(exp(raw)) / M): no cancellation at o -> 1.  The binomials are
+// integers (C(51, .) < 2^48: each product c (M - k) < 2^54 fits 64 bits and the division is exact); x^(k+1) is a running product.
+#define LG_MCMC_BINOM_MAX 51
+LG_HD double lg_mcmc_binomial_sum(double x, int M)                 // D; 1 <= M <= LG_MCMC_BINOM_MAX
+{
+    double D = 0.0, xp = x;
+    uint64_t c = (uint64_t)M;                                       // C(M, 1)
+    for (int k = 0; k < M; k++) {
+        const double term = (double)c * xp / sqrt((double)(k + 1));
+        D += (k & 1) ? -term : term;
+        xp *= x;
+        c = c * (uint64_t)(M - k - 1) / (uint64_t)(k + 2);          // C(M, k+2)
+    }
+    return D;
+}
+LG_HD void lg_mcmc_relocate(float opacity_raw, const float scaling_raw[3], int cnt, float min_opacity, float& new_opacity, float new_scaling[3])
+{
+    const int M = cnt + 1 < LG_MCMC_BINOM_MAX ? cnt + 1 : LG_MCMC_BINOM_MAX;
+    const double o = 1.0 / (1.0 + exp(-(double)opacity_raw));
+    const double x = -expm1(-log1p(exp((double)opacity_raw)) / (double)M);
+    const double D = lg_mcmc_binomial_sum(x, M);
+    const double hi = 1.0 - 0x1p-23;
+    const double xc = x < (double)min_opacity ? (double)min_opacity : (x > hi ? hi : x);
+    new_opacity = (float)log(xc / (1.0 - xc));
+    const double shift = log(o / D);
+    for (int a = 0; a < 3; a++) new_scaling[a] = (float)((double)scaling_raw[a] + shift);
+}
