@@ -248,7 +248,7 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
     // Significance-only pass with per-hit weights (MERGE): the four waves of a tile add their per-entry {count | weight} words into a ring of
     // LG_TM_SLOTS batch accumulators in LDS; whichever wave is the LAST to pass a batch writes the batch's 64 words to the instances' slots
     // with plain stores -- one store per (tile, Gaussian) instance, zeros included, so the slots need neither atomics nor a clear.
-    constexpr bool MERGE = FSCORE != 0 && !COLOR;
+    constexpr bool MERGE = lg_blend_merges(FSCORE, COLOR);      // (lg_plan.h: the same function decides whether the host clears the slots)
     __shared__ unsigned long long tacc[MERGE ? LG_TM_SLOTS : 1][MERGE ? LG_Q : 1];
     __shared__ uint32_t tarr[MERGE ? LG_TM_SLOTS : 1];      // waves that have passed the batch in the slot
     __shared__ uint32_t tgen[MERGE ? LG_TM_SLOTS : 1];      // flushes the slot has seen: batch b may use slot b % LG_TM_SLOTS once tgen == b / LG_TM_SLOTS

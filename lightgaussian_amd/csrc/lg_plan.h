@@ -59,6 +59,10 @@ static inline KeyPlan make_key_plan(int ntiles, int N, uint32_t dmax_bits, uint3
 // computed here once and read by name everywhere else.
 enum { LG_CHAIN_NONE = 0, LG_CHAIN_COLOR = 1, LG_CHAIN_COUNT = 2 };                                     // ForwardPlan::long_chain
 enum { LG_SCORE_NONE = 0, LG_SCORE_COUNT = 1, LG_SCORE_COUNT_OPACITY = 2, LG_SCORE_SLOTS = 3 };         // ForwardPlan::score
+// The one definition of "this lg_blend_fwd<COUNT, FSCORE, EXACT, COLOR> merges its per-hit words in LDS and stores every slot once": the kernel's
+// MERGE and ForwardPlan::merge (hence clear_slots) both come from here.  A variant that adds into its slots with atomics needs them cleared first;
+// were the two to disagree, lg_score_slots would read stale sort keys as {count | weight} words.
+constexpr bool lg_blend_merges(int fscore, bool color) { return fscore != 0 && !color; }
 struct ForwardPlan {
     // lg_blend_fwd<count, fscore, exact, color>: 11 of the 24 combinations exist (colour forward: exact or not; count forward with an
     // image: 3 policies x exact or not; significance-only: 3 policies)
@@ -94,7 +98,7 @@ static inline ForwardPlan make_forward_plan(uint32_t flags, bool count, int weig
     p.k1_skip_color = flags & LG_FLAG_SKIP_COLOR;
     p.color = !(count && p.exact && p.k1_skip_color);
     p.fscore = (count && (weight_policy == LG_WEIGHT_ALPHA || weight_policy == LG_WEIGHT_ALPHA_T)) ? weight_policy : 0;
-    p.merge = p.fscore && !p.color;
+    p.merge = lg_blend_merges(p.fscore, p.color);
     p.clear_slots = p.fscore && !p.merge && p.live;
     p.k1_clears_count = count && !p.fscore;
     // Long tiles of the hardware-exp colour forward: no history, no host hint -- two renders of the same inputs run the same kernels on

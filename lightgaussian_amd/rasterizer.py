@@ -526,8 +526,10 @@ class _GradSet:
                   True: (("_xyz", "means3D"), ("_features_dc", "shs"), ("_features_rest", "shs_rest"), ("_opacity", "opacity"),
                          ("_scaling", "scales"), ("_rotation", "rotations"))}
 
-    def __init__(self, call, rgb_only=False, new=torch.empty):
+    def __init__(self, call, rgb_only=False, new=None):
         f32 = dict(dtype=torch.float32, device=call.dev)
+        if new is None:             # looked up per call, not bound at import: tests/poison_common.py replaces torch.empty
+            new = torch.empty
 
         def rows(have, width):
             return new((call.N, width), **f32) if have else None
