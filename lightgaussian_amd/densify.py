@@ -33,50 +33,22 @@ torch.cuda.empty_cache() calls are not made.
 
 backend="torch" is the same contract in plain torch ops (CPU tensors too): the fallback and the comparand.  backend="hip" falls
 back to it, with one warning per reason, for: thr_g <= 0, parameters that are not float32 on the GPU, more than one parameter per
-group, N >= 2^30.  The optimizer surgery is prune.prune_points': new nn.Parameters, the state re-keyed.
+group, N >= 2^30.  The optimizer surgery is model_rows.install's, as for prune.prune_points and mcmc.grow: new nn.Parameters, the
+state objects moved to them; an optimizer state without Adam's moments is refused (model_rows.entries).
 set_profile(True) records the launches under "densify_stats", "densify_plan", "densify_rows" (_lib.profile_read)."""
-import warnings
-
 import torch
-from torch import nn
 
-from . import _lib
+from . import _lib, model_rows
+from .model_rows import f32, plain_f32, warn_once
 
 SHRINK = 0.8 * 2
 MAX_ROWS = 1 << 30
-_ATTR = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
-_PROFILE = [False]
-
-
-def set_profile(on):
-    """LG_FLAG_PROFILE on every call of this module."""
-    _PROFILE[0] = bool(on)
-
-
-def _flags():
-    return _lib.profile_flag(_PROFILE[0])
-
-
-def _warn_once(model, what, reason):
-    """One warning per model, entry point and reason."""
-    seen = model.__dict__.setdefault("_lg_densify_warned", set())
-    if (what, reason) not in seen:
-        seen.add((what, reason))
-        warnings.warn(f"lightgaussian_amd.densify.{what}: {reason} is outside the HIP path; taking the torch path", stacklevel=3)
-
-
-def _f32(x):
-    """A Python / numpy scalar evaluated in double, rounded once to float32 (what a float32 tensor compared with it sees)."""
-    return torch.tensor(float(x), dtype=torch.float64).to(torch.float32).item()
+set_profile, _flags = model_rows.profile_switch()
 
 
 def thresholds(model, max_grad, min_opacity, extent, max_screen_size):
-    return dict(thr_g=_f32(max_grad), thr_d=_f32(float(model.percent_dense) * float(extent)), thr_w=_f32(0.1 * float(extent)),
-                min_opacity=_f32(min_opacity), use_extent=bool(max_screen_size))
-
-
-def _plain_f32(t):
-    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.layout == torch.strided
+    return dict(thr_g=f32(max_grad), thr_d=f32(float(model.percent_dense) * float(extent)), thr_w=f32(0.1 * float(extent)),
+                min_opacity=f32(min_opacity), use_extent=bool(max_screen_size))
 
 
 # ---- view statistics --------------------------------------------------------------------------------------------------------------
@@ -84,7 +56,7 @@ def _plain_f32(t):
 def _stats_ineligible(model, grad, update_filter, radii):
     accum, denom = model.xyz_gradient_accum, model.denom
     n = accum.shape[0]
-    if not (_plain_f32(accum) and _plain_f32(denom) and _plain_f32(grad)):
+    if not (plain_f32(accum) and plain_f32(denom) and plain_f32(grad)):
         return "a tensor that is not float32 on the GPU"
     if not (accum.is_contiguous() and denom.is_contiguous() and accum.numel() == n and denom.numel() == n):
         return "a non-contiguous statistics tensor"
@@ -95,7 +67,7 @@ def _stats_ineligible(model, grad, update_filter, radii):
         return "an update filter that is not a contiguous bool / uint8 [N] on the GPU"
     if radii is not None:
         mr = model.max_radii2D
-        if not (_plain_f32(mr) and mr.is_contiguous() and mr.numel() == n):
+        if not (plain_f32(mr) and mr.is_contiguous() and mr.numel() == n):
             return "a max_radii2D that is not a contiguous float32 [N] on the GPU"
         if not (torch.is_tensor(radii) and radii.is_cuda and radii.dtype == torch.int32 and radii.numel() == n and radii.is_contiguous()):
             return "radii that are not a contiguous int32 [N] on the GPU"
@@ -122,7 +94,7 @@ def accumulate_stats(model, viewspace_points, update_filter, radii=None, absgrad
         why = _stats_ineligible(model, grad, update_filter, radii)
         if why is not None:
             if grad.is_cuda:
-                _warn_once(model, "accumulate_stats", why)
+                warn_once(model, "densify", "accumulate_stats", why)
             f = update_filter.reshape(-1).bool()
             accum, denom = model.xyz_gradient_accum, model.denom
             length = torch.linalg.vector_norm(grad[:, :2], dim=-1).reshape(accum.shape)
@@ -143,26 +115,15 @@ def accumulate_stats(model, viewspace_points, update_filter, radii=None, absgrad
 
 # ---- densify_and_prune ------------------------------------------------------------------------------------------------------------
 
-def _entries(model):
-    """[(group, index in the group, parameter, its optimizer state or None)] over every parameter of the optimizer."""
-    opt = model.optimizer
-    out = []
-    for group in opt.param_groups:
-        for j, p in enumerate(group["params"]):
-            st = opt.state.get(p, None)
-            out.append((group, j, p, st if st is not None and "exp_avg" in st else None))
-    return out
-
-
 def _ineligible(model, th, entries):
     if not th["thr_g"] > 0.0:
         return "max_grad <= 0"
     if any(len(g["params"]) != 1 for g in model.optimizer.param_groups):
         return "more than one parameter per group"
-    tensors = [model.xyz_gradient_accum, model.denom, model.max_radii2D]
+    tensors = _bookkeeping(model)
     for _, _, p, st in entries:
-        tensors += [p] + ([st["exp_avg"], st["exp_avg_sq"]] if st is not None else [])
-    if not all(_plain_f32(t) for t in tensors):
+        tensors += [p] + model_rows.moments(st)
+    if not all(plain_f32(t) for t in tensors):
         return "a tensor that is not float32 on the GPU"
     if model._xyz.shape[0] >= MAX_ROWS:
         return "N >= 2^30"
@@ -181,7 +142,7 @@ def _draw_noise(n_s, dev):
 
 
 def _bookkeeping(model):
-    return model.xyz_gradient_accum, model.denom, model.max_radii2D
+    return [getattr(model, name) for name in model_rows.BOOK]
 
 
 def _role(model, p):
@@ -212,19 +173,14 @@ def _rows_torch(model, th, entries, noise):
     clone_rows = torch.nonzero(clone & stays).reshape(-1)
     split_rows = torch.nonzero(split).reshape(-1)
     n_s = split_rows.numel()
-    child_stays = ~pruned(sigma, m / t(_f32(SHRINK)))[split_rows]
+    child_stays = ~pruned(sigma, m / t(f32(SHRINK)))[split_rows]
     parents = split_rows[child_stays]
     rank = torch.arange(n_s, device=dev)[child_stays]
     noise = _draw_noise(n_s, dev).to(xyz.dtype) if noise is None else _check_noise(noise, n_s, dev)
 
-    q = raw_q[parents]
-    q = q / torch.sqrt(q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1] + q[:, 2] * q[:, 2] + q[:, 3] * q[:, 3])[:, None]
-    r, x, y, z = q.unbind(dim=1)
-    rot = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
-                       2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
-                       2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
+    rot = model_rows.rotation_matrices(raw_q[parents])
     child_xyz = [torch.bmm(rot, (noise[rows] * s[parents]).unsqueeze(-1)).squeeze(-1) + xyz[parents] for rows in (rank, n_s + rank)]
-    child_scaling = torch.log(s[parents] / t(_f32(SHRINK)))
+    child_scaling = torch.log(s[parents] / t(f32(SHRINK)))
     n_new = clone_rows.numel() + 2 * parents.numel()
     out = []
     for _, _, p, st in entries:
@@ -270,15 +226,11 @@ def _rows_hip(model, th, entries, noise):
                 rows.append((st[key].contiguous(), new[-1], words, _lib.DENSIFY_MOMENT))
             out.append(tuple(new) if st is not None else (new[0], None, None))
         book = [torch.empty((n_out,) + tuple(old.shape[1:]), dtype=old.dtype, device=dev) for old in _bookkeeping(model)]
-        rows += [(None, b, b[0].numel(), _lib.DENSIFY_ZERO) for b in book if n_out > 0]
-        rows = [r for r in rows if r[2] > 0 and n_out > 0]                        # (rows of zero words, [N, 0, 3], have nothing to write)
-        for lo in range(0, len(rows), _lib.DENSIFY_MAX_TENSORS):
-            part = rows[lo:lo + _lib.DENSIFY_MAX_TENSORS]
-            table = (_lib.lg_densify_tensor * len(part))()
-            for row, (src, dst, words, role) in zip(table, part):
-                row.src, row.dst, row.row_words, row.role = None if src is None else src.data_ptr(), dst.data_ptr(), words, role
-            _lib.check(lib.lg_densify_rows(n, n_out, _lib.ptr(table_map), _lib.ptr(record), len(part), table, _lib.ptr(raw_q), _lib.ptr(raw_s),
-                                           _lib.ptr(noise) if n_s > 0 else None, 2 * n_s, _flags(), stream))
+        if n_out > 0:
+            rows += [(None, b, b[0].numel(), _lib.DENSIFY_ZERO) for b in book]
+            for count, table in model_rows.row_table(rows):
+                _lib.check(lib.lg_densify_rows(n, n_out, _lib.ptr(table_map), _lib.ptr(record), count, table, _lib.ptr(raw_q), _lib.ptr(raw_s),
+                                               _lib.ptr(noise) if n_s > 0 else None, 2 * n_s, _flags(), stream))
     return out, dict(N_out=n_out, n_keep=n_keep, n_clone=n_clone, n_s=n_s, n_child=n_child), book
 
 
@@ -287,29 +239,15 @@ def densify_and_prune(model, max_grad, min_opacity, extent, max_screen_size, noi
     with its attributes: optimizer, _xyz ... _rotation, percent_dense, xyz_gradient_accum, denom, max_radii2D), by the contract in the
     module docstring.  noise: unit-normal float32 [2 n_s, 3] on the model's device, or None for the default draw.
     Returns the record {"N_out", "n_keep", "n_clone", "n_s", "n_child", "backend"}."""
-    if backend not in ("hip", "torch"):
-        raise ValueError(f"densify_and_prune: unknown backend {backend!r} (hip | torch)")
+    model_rows.check_backend(backend, "densify_and_prune")
     th = thresholds(model, max_grad, min_opacity, extent, max_screen_size)
-    entries = _entries(model)
-    n = model._xyz.shape[0]
-    if any(p.shape[0] != n for _, _, p, _ in entries):
-        raise ValueError("densify_and_prune: every parameter of the optimizer must have one row per Gaussian")
+    entries = model_rows.entries(model, "densify_and_prune")
     if backend == "hip":
         why = _ineligible(model, th, entries)
         if why is not None:
-            _warn_once(model, "densify_and_prune", why)
+            warn_once(model, "densify", "densify_and_prune", why)
             backend = "torch"
     with torch.no_grad():
         new, counts, zeros = (_rows_hip if backend == "hip" else _rows_torch)(model, th, entries, noise)
-    opt = model.optimizer
-    for (group, j, p, st), (new_p, exp_avg, exp_avg_sq) in zip(entries, new):
-        param = nn.Parameter(new_p.requires_grad_(True))
-        if st is not None:
-            st["exp_avg"], st["exp_avg_sq"] = exp_avg, exp_avg_sq
-            del opt.state[p]
-            opt.state[param] = st
-        group["params"][j] = param
-        if j == 0 and group.get("name") in _ATTR:
-            setattr(model, _ATTR[group["name"]], param)
-    model.xyz_gradient_accum, model.denom, model.max_radii2D = zeros
+    model_rows.install(model, entries, new, book=dict(zip(model_rows.BOOK, zeros)))
     return dict(counts, backend=backend)

@@ -28,18 +28,17 @@ closed form; backend="torch" is the published float32 op sequence (L @ L^T and b
 table for D), CPU tensors too: the fallback and the comparand.  backend="hip" falls back to it, with one warning per reason, for
 parameters that are not contiguous float32 on the GPU, more than one parameter per group, N >= 2^30.
 relocate keeps the nn.Parameter objects and the optimizer's state keys; grow swaps the Parameters and re-keys the state exactly as
-densify.densify_and_prune does, and xyz_gradient_accum, denom and max_radii2D, where the model has them, keep their first N rows
-and get zero rows behind them.  "n_sources" in the returned records is a 0-dim int64 tensor on the model's device (the number of
+densify.densify_and_prune does (model_rows.install; an optimizer state without Adam's moments is refused by model_rows.entries), and
+xyz_gradient_accum, denom and max_radii2D, where the model has them, keep their first N rows and get zero rows behind them.  "n_sources" in the returned records is a 0-dim int64 tensor on the model's device (the number of
 distinct drawn rows): reading it is the caller's choice, the calls themselves make one host read (relocate: the dead count) or none.
 set_profile(True) records the launches under "mcmc_noise", "mcmc_count", "mcmc_plan", "mcmc_rows" (_lib.profile_read)."""
 import ctypes as C
 import math
-import warnings
 
 import torch
-from torch import nn
 
-from . import _lib
+from . import _lib, model_rows
+from .model_rows import check_backend, f32 as to_f32, moments, plain_f32, rotation_matrices, warn_once      # (f32 here: ctypes c_float)
 
 MCMC_COPY, MCMC_MOMENT, MCMC_OPACITY, MCMC_SCALING = 0, 1, 2, 3      # lg_densify_tensor.role of lg_mcmc_rows (LG_MCMC_*)
 MCMC_MAX_COPIES = 51                                                 # LG_MCMC_MAX_COPIES: M = min(cnt + 1, 51)
@@ -56,9 +55,7 @@ PROTOTYPES = {
     "lg_mcmc_rows": (C.c_int, (i32, i64, i32, vp, vp, vp, i32, C.POINTER(_lib.lg_densify_tensor), u32, vp)),
 }
 
-_ATTR = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation"}
-_BOOK = ("xyz_gradient_accum", "denom", "max_radii2D")
-_PROFILE = [False]
+set_profile, _flags = model_rows.profile_switch()
 _BOUND = []
 
 
@@ -73,52 +70,12 @@ def load():
     return lib
 
 
-def set_profile(on):
-    """LG_FLAG_PROFILE on every call of this module."""
-    _PROFILE[0] = bool(on)
-
-
-def _flags():
-    return _lib.profile_flag(_PROFILE[0])
-
-
-def _warn_once(model, what, reason):
-    """One warning per model, entry point and reason."""
-    seen = model.__dict__.setdefault("_lg_mcmc_warned", set())
-    if (what, reason) not in seen:
-        seen.add((what, reason))
-        warnings.warn(f"lightgaussian_amd.mcmc.{what}: {reason} is outside the HIP path; taking the torch path", stacklevel=3)
-
-
-def _f32(x):
-    """A Python scalar evaluated in double, rounded once to float32."""
-    return torch.tensor(float(x), dtype=torch.float64).to(torch.float32).item()
-
-
-def _plain_f32(t):
-    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.layout == torch.strided and t.is_contiguous()
-
-
-def _backend(backend, what):
-    if backend not in ("hip", "torch"):
-        raise ValueError(f"{what}: unknown backend {backend!r} (hip | torch)")
-
-
-def _rotation_matrices(raw_q):
-    """build_rotation: R(q / |q|), q = (r, x, y, z), [n, 3, 3]."""
-    q = raw_q / torch.sqrt(raw_q[:, 0] * raw_q[:, 0] + raw_q[:, 1] * raw_q[:, 1] + raw_q[:, 2] * raw_q[:, 2] + raw_q[:, 3] * raw_q[:, 3])[:, None]
-    r, x, y, z = q.unbind(dim=1)
-    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
-                        2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
-                        2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).reshape(-1, 3, 3)
-
-
 # ---- position noise ---------------------------------------------------------------------------------------------------------------
 
 def _noise_torch(model, noise, c, k, x0):
     """The published statement: build_scaling_rotation, L @ L^T, the gated noise, bmm, add_."""
     xyz = model._xyz.detach()
-    L = _rotation_matrices(model._rotation.detach()) * torch.exp(model._scaling.detach())[:, None, :]       # R diag(s)
+    L = rotation_matrices(model._rotation.detach()) * torch.exp(model._scaling.detach())[:, None, :]       # R diag(s)
     cov = L @ L.transpose(1, 2)
     sigma = torch.sigmoid(model._opacity.detach()).reshape(-1, 1)
     g = 1 / (1 + torch.exp(-k * ((1 - sigma) - x0)))
@@ -128,7 +85,7 @@ def _noise_torch(model, noise, c, k, x0):
 
 def _noise_ineligible(model):
     n = model._xyz.shape[0]
-    if not all(_plain_f32(t) for t in (model._xyz, model._scaling, model._rotation, model._opacity)):
+    if not all(plain_f32(t, True) for t in (model._xyz, model._scaling, model._rotation, model._opacity)):
         return "a parameter that is not contiguous float32 on the GPU"
     if n >= MAX_ROWS:
         return "N >= 2^30"
@@ -138,18 +95,18 @@ def _noise_ineligible(model):
 def add_noise(model, xyz_lr, noise_lr=5e5, noise=None, k=100.0, x0=0.995, backend="hip"):
     """_xyz += Sigma (noise g c) in place by the contract in the module docstring; xyz_lr is the current learning rate of the positions.
     noise: unit-normal float32 [N, 3] on the model's device, or None for torch.randn_like(model._xyz).  No host read."""
-    _backend(backend, "add_noise")
+    check_backend(backend, "add_noise")
     xyz = model._xyz
     n = xyz.shape[0]
     if noise is None:
         noise = torch.randn_like(xyz.detach())
     elif not (torch.is_tensor(noise) and tuple(noise.shape) == (n, 3) and noise.dtype == xyz.dtype and noise.device == xyz.device):
         raise ValueError(f"add_noise: noise must be a {xyz.dtype} [{n}, 3] tensor on {xyz.device}")
-    c, k, x0 = _f32(float(noise_lr) * float(xyz_lr)), _f32(k), _f32(x0)
+    c, k, x0 = to_f32(float(noise_lr) * float(xyz_lr)), to_f32(k), to_f32(x0)
     if backend == "hip":
         why = _noise_ineligible(model)
         if why is not None:
-            _warn_once(model, "add_noise", why)
+            warn_once(model, "mcmc", "add_noise", why)
             backend = "torch"
     with torch.no_grad():
         if backend == "torch":
@@ -167,25 +124,6 @@ def add_noise(model, xyz_lr, noise_lr=5e5, noise=None, k=100.0, x0=0.995, backen
 
 # ---- row movement: relocation and growth ------------------------------------------------------------------------------------------
 
-def _entries(model):
-    """[(group, index in the group, parameter, its optimizer state or None)] over every parameter of the optimizer."""
-    opt = model.optimizer
-    out = []
-    for group in opt.param_groups:
-        for j, p in enumerate(group["params"]):
-            st = opt.state.get(p, None)
-            out.append((group, j, p, st if st is not None and "exp_avg" in st else None))
-    return out
-
-
-def _checked_entries(model, what):
-    entries = _entries(model)
-    n = model._xyz.shape[0]
-    if any(p.shape[0] != n for _, _, p, _ in entries):
-        raise ValueError(f"{what}: every parameter of the optimizer must have one row per Gaussian")
-    return entries
-
-
 def _role(model, p):
     return MCMC_OPACITY if p is model._opacity else (MCMC_SCALING if p is model._scaling else MCMC_COPY)
 
@@ -193,10 +131,7 @@ def _role(model, p):
 def _rows_ineligible(model, entries, n_out):
     if any(len(g["params"]) != 1 for g in model.optimizer.param_groups):
         return "more than one parameter per group"
-    tensors = []
-    for _, _, p, st in entries:
-        tensors += [p] + ([st["exp_avg"], st["exp_avg_sq"]] if st is not None else [])
-    if not all(_plain_f32(t) for t in tensors):
+    if not all(plain_f32(t, True) for _, _, p, st in entries for t in [p] + moments(st)):
         return "a tensor that is not contiguous float32 on the GPU"
     if model._xyz.shape[0] >= MAX_ROWS or n_out >= (1 << 31):
         return "N >= 2^30"
@@ -246,7 +181,7 @@ def _move_torch(model, entries, dst, src, n_out, min_opacity):
     out = []
     for _, _, p, st in entries:
         role = _role(model, p)
-        tensors = [p.detach()] + ([st["exp_avg"], st["exp_avg_sq"]] if st is not None else [])
+        tensors = [p.detach()] + moments(st)
         if not inplace:
             tensors = [torch.cat([t, torch.zeros((n_out - n,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)], dim=0) for t in tensors]
         value = tensors[0]
@@ -272,21 +207,17 @@ def _move_hip(model, entries, dst, src, n_out, min_opacity):
     with torch.cuda.device(dev):
         stream = _lib.stream(dev)
         scratch = _lib.scratch(lib.lg_mcmc_scratch_bytes(n), dev)
-        _lib.check(lib.lg_mcmc_plan(n, src32.numel(), _lib.ptr(src32), _lib.ptr(model._opacity), _lib.ptr(model._scaling), _f32(min_opacity),
-                                    _lib.ptr(scratch), _flags(), stream))
+        _lib.check(lib.lg_mcmc_plan(n, src32.numel(), _lib.ptr(src32), _lib.ptr(model._opacity), _lib.ptr(model._scaling),
+                                    to_f32(min_opacity), _lib.ptr(scratch), _flags(), stream))
         for _, _, p, st in entries:
-            old = [p.detach()] + ([st["exp_avg"], st["exp_avg_sq"]] if st is not None else [])
+            old = [p.detach()] + moments(st)
             new = old if inplace else [torch.empty((n_out,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in old]
             words = old[0][0].numel()
             roles = [_role(model, p)] + [MCMC_MOMENT] * (len(old) - 1)
-            rows += [(a, b, words, role) for a, b, role in zip(old, new, roles) if words > 0]      # (rows of zero words: nothing to write)
+            rows += [(a, b, words, role) for a, b, role in zip(old, new, roles)]
             out.append(tuple(new) if st is not None else (new[0], None, None))
-        for lo in range(0, len(rows), _lib.DENSIFY_MAX_TENSORS):
-            part = rows[lo:lo + _lib.DENSIFY_MAX_TENSORS]
-            table = (_lib.lg_densify_tensor * len(part))()
-            for row, (a, b, words, role) in zip(table, part):
-                row.src, row.dst, row.row_words, row.role = a.data_ptr(), b.data_ptr(), words, role
-            _lib.check(lib.lg_mcmc_rows(n, n_out, src32.numel(), _lib.ptr(dst32), _lib.ptr(src32), _lib.ptr(scratch), len(part), table,
+        for count, table in model_rows.row_table(rows):
+            _lib.check(lib.lg_mcmc_rows(n, n_out, src32.numel(), _lib.ptr(dst32), _lib.ptr(src32), _lib.ptr(scratch), count, table,
                                         _flags(), stream))
         if inplace:
             torch.autograd.graph.increment_version([a for a, _, _, _ in rows])
@@ -298,7 +229,7 @@ def _move(model, entries, dst, src, n_out, min_opacity, backend, what):
     if backend == "hip":
         why = _rows_ineligible(model, entries, n_out)
         if why is not None:
-            _warn_once(model, what, why)
+            warn_once(model, "mcmc", what, why)
             backend = "torch"
     with torch.no_grad():
         new, n_sources = (_move_hip if backend == "hip" else _move_torch)(model, entries, dst, src, n_out, min_opacity)
@@ -330,13 +261,13 @@ def relocate(model, min_opacity=0.005, draws=None, backend="hip"):
     draws: int64 [n_dead] of live source rows, one per dead row in ascending order of the dead rows, or None for
     torch.multinomial(sigma[alive], n_dead, replacement=True) mapped back through the alive indices.
     Returns {"n_dead", "n_sources", "backend"}; with no dead or no live row nothing is launched."""
-    _backend(backend, "relocate")
-    entries = _checked_entries(model, "relocate")
+    check_backend(backend, "relocate")
+    entries = model_rows.entries(model, "relocate")
     n = model._xyz.shape[0]
     dev = model._xyz.device
     with torch.no_grad():
         sigma = torch.sigmoid(model._opacity.detach()).reshape(-1)
-        dead = sigma <= _f32(min_opacity)                                  # (a Python scalar: no copy to the device)
+        dead = sigma <= to_f32(min_opacity)                                 # (a Python scalar: no copy to the device)
         order = torch.argsort(dead.to(torch.uint8), stable=True)           # the live rows ascending, then the dead rows ascending
         n_dead = int(dead.sum().item())                                     # the one host read of the call
         alive, dst = order[:n - n_dead], order[n - n_dead:]
@@ -352,8 +283,8 @@ def grow(model, cap_max, factor=1.05, draws=None, backend="hip", *, min_opacity=
     contract in the module docstring (min_opacity: the floor of the corrected opacities).  draws: int64 [n] of source rows, or None for
     torch.multinomial(sigma, n, replacement=True).  New tensors of N + n rows: Parameters swapped, the optimizer's state re-keyed.
     Returns {"N_out", "n_new", "n_sources", "backend"}."""
-    _backend(backend, "grow")
-    entries = _checked_entries(model, "grow")
+    check_backend(backend, "grow")
+    entries = model_rows.entries(model, "grow")
     n = model._xyz.shape[0]
     dev = model._xyz.device
     n_new = max(0, min(int(cap_max), int(factor * n)) - n)
@@ -365,20 +296,10 @@ def grow(model, cap_max, factor=1.05, draws=None, backend="hip", *, min_opacity=
         src = _draw(torch.sigmoid(model._opacity.detach()).reshape(-1), n_new) if draws is None else draws
         dst = torch.arange(n, n + n_new, dtype=torch.int64, device=dev)
     new, n_sources, backend = _move(model, entries, dst, src, n + n_new, min_opacity, backend, "grow")
-    opt = model.optimizer
-    for (group, j, p, st), (new_p, exp_avg, exp_avg_sq) in zip(entries, new):
-        param = nn.Parameter(new_p.requires_grad_(True))
-        if st is not None:
-            st["exp_avg"], st["exp_avg_sq"] = exp_avg, exp_avg_sq
-            del opt.state[p]
-            opt.state[param] = st
-        group["params"][j] = param
-        if j == 0 and group.get("name") in _ATTR:
-            setattr(model, _ATTR[group["name"]], param)
-    for name in _BOOK:
-        old = getattr(model, name, None)
-        if torch.is_tensor(old) and old.shape[0] == n:
-            setattr(model, name, torch.cat([old, torch.zeros((n_new,) + tuple(old.shape[1:]), dtype=old.dtype, device=old.device)], dim=0))
+    book = {name: getattr(model, name, None) for name in model_rows.BOOK}
+    book = {name: torch.cat([old, torch.zeros((n_new,) + tuple(old.shape[1:]), dtype=old.dtype, device=old.device)], dim=0)
+            for name, old in book.items() if torch.is_tensor(old) and old.shape[0] == n}
+    model_rows.install(model, entries, new, book=book)
     return dict(N_out=n + n_new, n_new=n_new, n_sources=n_sources, backend=backend)
 
 

@@ -33,17 +33,12 @@ import warnings
 
 import torch
 
-from . import _lib
+from . import _lib, model_rows
 
 MAX_TENSORS = _lib.ADAM_MAX_TENSORS
 SPAN = _lib.ADAM_SPAN
-_PROFILE = [False]
+set_profile, _profile_flag = model_rows.profile_switch()      # one "adam" / "adam_rows" entry per launch in _lib.profile_read()
 _CLASSES = {}
-
-
-def set_profile(on):
-    """LG_FLAG_PROFILE on every lg_adam_step of this module: one "adam" entry per launch in _lib.profile_read()."""
-    _PROFILE[0] = bool(on)
 
 
 def _torch_step(cls):
@@ -179,7 +174,7 @@ class _HipStep:
                 row.numel, row.lr, row.weight_decay, row.step = p.numel(), lr, wd, step
                 if visible is not None and p.dim() >= 1 and p.shape[0] == visible.shape[0]:     # (else a dense entry of the same launch)
                     entry.row_mask, entry.rows = visible.data_ptr(), visible.shape[0]
-            flags = (_lib.ADAM_DECOUPLED_WD if decoupled else 0) | _lib.profile_flag(_PROFILE[0])
+            flags = (_lib.ADAM_DECOUPLED_WD if decoupled else 0) | _profile_flag()
             with torch.cuda.device(index):
                 call = lib.lg_adam_step if visible is None else lib.lg_adam_step_rows
                 _lib.check(call(len(entries), table, beta1, beta2, eps, flags, _lib.stream()))

@@ -20,7 +20,7 @@ replicated, the camera list split into contiguous blocks, and
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, model_rows
 from .gaussian_renderer import count_render
 
 
@@ -469,39 +469,21 @@ def prune_points(model, mask):
     (:564-582): the six parameters, both Adam moments of each and xyz_gradient_accum / denom / max_radii2D are compacted with
     valid = ~mask in ONE compact_tensors call instead of 21 boolean-index kernels.  `model` is a reference GaussianModel (or
     anything with the same attributes: optimizer with one named parameter per group, _xyz ... _rotation, the three
-    bookkeeping tensors).  Same state afterwards as the reference leaves, bit for bit (tests/test_gpu_compact.py)."""
-    from torch import nn
+    bookkeeping tensors).  Same state afterwards as the reference leaves, bit for bit (tests/test_gpu_compact.py); every parameter
+    of every group is compacted, the walk and the surgery being model_rows.entries / install.
+    Returns {group name: its new Parameter}."""
     valid = ~mask.reshape(-1).bool()
-    opt = model.optimizer
-    plan, tensors = [], []
-    for group in opt.param_groups:
-        p = group["params"][0]
-        st = opt.state.get(p, None)
-        plan.append((group, p, st, len(tensors)))
-        tensors.append(p.data)
-        if st is not None:
-            tensors += [st["exp_avg"], st["exp_avg_sq"]]
-    extra0 = len(tensors)
-    tensors += [model.xyz_gradient_accum, model.denom, model.max_radii2D]
-    outs = compact_tensors(tensors, valid)
-    optimizable = {}
-    for group, p, st, i in plan:
-        if st is not None:
-            st["exp_avg"], st["exp_avg_sq"] = outs[i + 1], outs[i + 2]
-            del opt.state[p]
-            group["params"][0] = nn.Parameter(outs[i].requires_grad_(True))
-            opt.state[group["params"][0]] = st
-        else:
-            group["params"][0] = nn.Parameter(outs[i].requires_grad_(True))
-        optimizable[group["name"]] = group["params"][0]
-    model._xyz = optimizable["xyz"]
-    model._features_dc = optimizable["f_dc"]
-    model._features_rest = optimizable["f_rest"]
-    model._opacity = optimizable["opacity"]
-    model._scaling = optimizable["scaling"]
-    model._rotation = optimizable["rotation"]
-    model.xyz_gradient_accum, model.denom, model.max_radii2D = outs[extra0], outs[extra0 + 1], outs[extra0 + 2]
-    return optimizable
+    entries = model_rows.entries(model, "prune_points", n=valid.numel())
+    tensors = []
+    for _, _, p, st in entries:
+        tensors += [p.data] + model_rows.moments(st)
+    outs = compact_tensors(tensors + [getattr(model, name) for name in model_rows.BOOK], valid)
+    new, k = [], 0
+    for _, _, _, st in entries:
+        width = 1 if st is None else 3
+        new.append(tuple(outs[k:k + width]) + (None,) * (3 - width))
+        k += width
+    return model_rows.install(model, entries, new, book=dict(zip(model_rows.BOOK, outs[k:])))
 
 
 def prune_gaussians(model, percent, import_score):
