@@ -107,6 +107,7 @@ enum {
                                   homodirectional gradient, gsplat's `absgrad`).  Read by lg_backward_abs alone, which refuses a view without it;
                                   every forward and every other backward ignores it: without lg_backward_abs every kernel launched and every
                                   bit produced is unchanged. */
+    /* (65536 is LG_FLAG_SCORE_MAX, a flag of the count forwards declared in the extension header lightgaussian_score.h: the bit is taken) */
     /* (4096 was LG_FLAG_BWD_SPLAT_PARALLEL, the round-5 prototype of the backward blend on the other parallel axis: removed in ABI 7) */
     LG_FLAG_RAW_PARAMS = 8 /* "fused getters" (SURVEY 8f row 1): the inputs are GaussianModel's RAW parameters and the
                               activations of scene/gaussian_model.py:98-118 run inside the kernels: scales = log-scales (exp),

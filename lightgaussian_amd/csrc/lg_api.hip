@@ -22,7 +22,7 @@
 //                    lg_adam_step_rows: the same step over the rows a byte mask names (row index: lg_adam_rows.h); both kernels are lg_adam_span<DECOUPLED, ROWS>
 //   lg_densify.h     lg_densify_stats / lg_densify_plan / lg_densify_rows: view statistics and clone / split / prune of densify_and_prune
 //   lg_mcmc.h        lg_mcmc_noise / lg_mcmc_plan / lg_mcmc_rows: 3DGS-MCMC position noise, relocation and growth (include/lightgaussian_mcmc.h)
-//   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR>, lg_score_kernel, K7 lg_blend_bwd<EXACT, ABS>   (per tile, VALU-bound); wave_reduce_via_lds<NV> (also lg_features.h's)
+//   lg_blend.h       K6 lg_blend_fwd<COUNT,FSCORE,EXACT,COLOR,MAX>, lg_score_kernel, K7 lg_blend_bwd<EXACT, ABS>   (per tile, VALU-bound); wave_reduce_via_lds<NV> (also lg_features.h's)
 //   lg_features.h    lg_features_fwd / _bwd / _gather: C further per-Gaussian channels blended over the lists a forward left, and dL/dfeatures
 //   lg_camera.h      lg_camera_bwd<RAW, AA> / lg_camera_reduce: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos from the rows a backward left, through lg_k9_* (float64 ordered sums)
 //   lg_absgrad.h     lg_absgrad_rows: absolute screen-space mean gradients per Gaussian from floats 9, 10 of the rows K7<ABS> left (lg_backward_abs)
@@ -203,7 +203,11 @@ static BlendFwdKernel blend_fwd_kernel(const ForwardPlan& p)
                                                       { lg_blend_fwd<true, LG_W_ALPHA_T, false, true>, lg_blend_fwd<true, LG_W_ALPHA_T, true, true> } };
     static const BlendFwdKernel significance[3] = { lg_blend_fwd<true, 0, true, false>, lg_blend_fwd<true, LG_W_ALPHA, true, false>,
                                                     lg_blend_fwd<true, LG_W_ALPHA_T, true, false> };                           // [policy]
+    // LG_FLAG_SCORE_MAX (ForwardPlan::fmax): the per-hit policies of a canonical count forward, with or without the image
+    static const BlendFwdKernel score_max[2][2] = { { lg_blend_fwd<true, LG_W_ALPHA, true, false, true>, lg_blend_fwd<true, LG_W_ALPHA, true, true, true> },   // [policy][color]
+                                                    { lg_blend_fwd<true, LG_W_ALPHA_T, true, false, true>, lg_blend_fwd<true, LG_W_ALPHA_T, true, true, true> } };
     const int w = p.fscore == LG_W_ALPHA ? 1 : p.fscore == LG_W_ALPHA_T ? 2 : 0;
+    if (p.fmax) return score_max[w - 1][p.color];      // (exact: forward_impl refuses the flag with LG_FLAG_FAST_EXP)
     return !p.count ? color[p.exact] : p.color ? count_image[w][p.exact] : significance[w];
 }
 using BlendBwdKernel = decltype(&lg_blend_bwd<true, false>);
@@ -455,8 +459,10 @@ int Forward::score()
     if (plan.score == LG_SCORE_NONE) return LG_OK;
     {
         ProfScope ps(prof, "score", stream);
-        if (plan.score == LG_SCORE_SLOTS)
-            lg_score_slots<<<(N + 255) / 256, 256, 0, stream>>>(N, geo.touched, geo.offsets, (const unsigned long long*)bin.keys_in, (uint32_t)cap, out_count, out_score, v->count_sum, geo.counters);
+        if (plan.score == LG_SCORE_SLOTS_MAX)
+            lg_score_slots<true><<<(N + 255) / 256, 256, 0, stream>>>(N, geo.touched, geo.offsets, (const unsigned long long*)bin.keys_in, (uint32_t)cap, out_count, out_score, v->count_sum, geo.counters);
+        else if (plan.score == LG_SCORE_SLOTS)
+            lg_score_slots<false><<<(N + 255) / 256, 256, 0, stream>>>(N, geo.touched, geo.offsets, (const unsigned long long*)bin.keys_in, (uint32_t)cap, out_count, out_score, v->count_sum, geo.counters);
         else
             lg_score_kernel<<<(N + 255) / 256, 256, 0, stream>>>(N, out_count, plan.score == LG_SCORE_COUNT_OPACITY ? g->opacities : nullptr, out_score, v->count_sum);
     }
@@ -506,8 +512,13 @@ static int forward_impl(const lg_view* v, const lg_gaussians* g, void* geom_p, v
     const bool count = out_count != nullptr;
     if (count && !out_score) return fail(LG_ERR_INVALID_ARGUMENT, "count needs score");
     if (count && (weight_policy < 0 || weight_policy > 3)) return fail(LG_ERR_INVALID_ARGUMENT, "bad weight policy");
-    // per-hit weights are summed in Q24.40 per view: a Gaussian can collect at most 0.99 per pixel
-    if (count && weight_policy >= LG_WEIGHT_ALPHA && (int64_t)v->image_width * v->image_height > (1ll << 24))
+    // LG_FLAG_SCORE_MAX on a count forward: a per-hit policy (the maximum of equal addends is the addend) with the canonical exp (Python never
+    // issues a hardware-exp count forward, and its maximum could not be pinned).  A colour forward ignores the flag, as it ignores the policy.
+    const bool score_max = count && (v->flags & LG_FLAG_SCORE_MAX);
+    if (score_max && weight_policy < LG_WEIGHT_ALPHA) return fail(LG_ERR_INVALID_ARGUMENT, "LG_FLAG_SCORE_MAX needs LG_WEIGHT_ALPHA or LG_WEIGHT_ALPHA_T");
+    if (score_max && (v->flags & LG_FLAG_FAST_EXP)) return fail(LG_ERR_INVALID_ARGUMENT, "LG_FLAG_SCORE_MAX with LG_FLAG_FAST_EXP in a count forward");
+    // per-hit weights are summed in Q24.40 per view: a Gaussian can collect at most 0.99 per pixel (a maximum has no such limit)
+    if (count && !score_max && weight_policy >= LG_WEIGHT_ALPHA && (int64_t)v->image_width * v->image_height > (1ll << 24))
         return fail(LG_ERR_INVALID_ARGUMENT, "ALPHA / ALPHA_T weights: images beyond 2^24 pixels overflow the Q24.40 per-view sums");
     Forward f{};
     f.v = v; f.g = g; f.bounded = bounded; f.alloc = alloc; f.alloc_user = alloc_user; f.weight_policy = weight_policy;

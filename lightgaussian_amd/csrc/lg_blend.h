@@ -230,9 +230,34 @@ __device__ __forceinline__ uint64_t lg_wq_rowsum(const float* wq, uint32_t lane)
     __builtin_amdgcn_wave_barrier();                // (the next chunk overwrites the rows)
     return ((uint64_t)hi << 24) + lo;
 }
+// LG_FLAG_SCORE_MAX: the row MAXIMUM where lg_wq_rowsum leaves the row total -- same two ds_read_b128 per lane, a maximum over the 8
+// columns and the same three DPP steps; nothing is quantised (no double-precision add, no LG_FIX_MAGIC).  The weights are finite and
+// >= 0, so the maximum of their bit patterns as uint32 is the maximum of the floats: the result is the fp32 value of one hit.
+__device__ __forceinline__ uint32_t lg_wq_rowmax(const float* wq, uint32_t lane)
+{
+    lg_wave_lds_sync();
+    const uint4* src = reinterpret_cast<const uint4*>(wq + (lane >> 3) * LG_WQ_STRIDE + (lane & 7u) * 8u);
+    const uint4 x0 = src[0], x1 = src[1];
+    uint32_t m = max(max(max(x0.x, x0.y), max(x0.z, x0.w)), max(max(x1.x, x1.y), max(x1.z, x1.w)));
+    m = dpp_max_u32<0xB1>(m);           // quad_perm [1,0,3,2]
+    m = dpp_max_u32<0x4E>(m);           // quad_perm [2,3,0,1]
+    m = dpp_max_u32<0x141>(m);          // row_half_mirror
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (as lg_wq_rowsum: the next chunk overwrites the rows)
+    __builtin_amdgcn_wave_barrier();
+    return m;
+}
+// The slot word under LG_FLAG_SCORE_MAX: {count : 16 at bit 48 | fp32 bits of the largest weight : 32 low}.  A count and a maximum cannot
+// share one atomic: two 32-bit atomics, an add on the high half and a max on the low half of the (little-endian) 64-bit word.
+__device__ __forceinline__ void lg_slot_count_max(unsigned long long* word, uint32_t cnt, uint32_t wbits)
+{
+    uint32_t* half = reinterpret_cast<uint32_t*>(word);
+    atomicAdd(half + 1, cnt << (LG_SLOT_COUNT_SHIFT - 32));
+    atomicMax(half, wbits);
+}
 
-// K6 / K6c: forward blend.  FSCORE: 0, or the per-hit weight policy (LG_W_ALPHA / LG_W_ALPHA_T) accumulated into fix[] (Q24.40)
-template <bool COUNT, int FSCORE, bool EXACT, bool COLOR = true>
+// K6 / K6c: forward blend.  FSCORE: 0, or the per-hit weight policy (LG_W_ALPHA / LG_W_ALPHA_T) accumulated into fix[] (Q24.40);
+// MAX (LG_FLAG_SCORE_MAX): the per-hit weights are reduced by a maximum instead -- same walk, same slots, same MERGE ring and arrival protocol
+template <bool COUNT, int FSCORE, bool EXACT, bool COLOR = true, bool MAX = false>
 __global__ void __launch_bounds__(256)
 lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __restrict__ ranges,
              const uint64_t* __restrict__ entries, uint32_t gid_mask, const float4* __restrict__ rec, const float* __restrict__ bg,
@@ -243,6 +268,7 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
              int long_mode, uint32_t* __restrict__ par_arrived)
 {
     static_assert(FSCORE == 0 || ((FSCORE == LG_W_ALPHA || FSCORE == LG_W_ALPHA_T) && COUNT), "FSCORE is 0 or a per-hit weight policy of the count variant");
+    static_assert(!MAX || (FSCORE != 0 && EXACT), "MAX reduces the per-hit weights of a canonical count forward");
     __shared__ float4 q0[4][LG_Q], q1[4][LG_Q], q2[4][LG_Q];
     __shared__ __attribute__((aligned(16))) float wq[FSCORE ? 4 : 1][FSCORE ? LG_WQ_ROWS * LG_WQ_STRIDE : 1];
     // Significance-only pass with per-hit weights (MERGE): the four waves of a tile add their per-entry {count | weight} words into a ring of
@@ -364,6 +390,7 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
             __builtin_amdgcn_wave_barrier();
             int mycnt = 0;
             uint64_t myfix = 0ull;
+            uint32_t mymax = 0u;                                            // MAX: bits of the largest weight of the owned entry
             const uint32_t nhit = (uint32_t)__popcll(mask);
             const uint32_t owned = FSCORE ? LG_WQ_OWNER(lane) : lane;       // the compacted entry whose totals this lane collects
             auto pair = [&](uint32_t j, float* wrow) {
@@ -385,8 +412,13 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
                     const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)min((uint32_t)LG_WQ_ROWS, nhit - c0));
                     float* wrow = &wq[wave][lane];
                     for (uint32_t jj = 0; jj < m; jj++, wrow += LG_WQ_STRIDE) pair(c0 + jj, wrow);
-                    const uint64_t tot = lg_wq_rowsum(wq[wave], lane);
-                    if ((lane & 7u) == (c0 >> 3)) myfix = tot;
+                    if (MAX) {
+                        const uint32_t top = lg_wq_rowmax(wq[wave], lane);
+                        if ((lane & 7u) == (c0 >> 3)) mymax = top;
+                    } else {
+                        const uint64_t tot = lg_wq_rowsum(wq[wave], lane);
+                        if ((lane & 7u) == (c0 >> 3)) myfix = tot;
+                    }
                 }
             } else {
                 for (uint32_t j = 0; j < nhit; j++) pair(j, nullptr);
@@ -403,13 +435,16 @@ lg_blend_fwd(int W, int H, int gx, int ntiles, int ntiles_pad, const uint2* __re
                     tile_leave((base - range.x) / LG_Q, [&](uint32_t ts) {
                         if (owned < nhit && mycnt > 0) {
                             const uint32_t src = __float_as_uint(q2[wave][owned].y) - 1u - (base - range.x);
-                            atomicAdd(&tacc[ts][src], ((unsigned long long)(uint32_t)mycnt << LG_SLOT_COUNT_SHIFT) + myfix);
+                            if (MAX) lg_slot_count_max(&tacc[ts][src], (uint32_t)mycnt, mymax);      // (ds_add_u32 + ds_max_u32)
+                            else atomicAdd(&tacc[ts][src], ((unsigned long long)(uint32_t)mycnt << LG_SLOT_COUNT_SHIFT) + myfix);
                         }
                     });
                 } else if (owned < nhit && mycnt > 0) {
                     // count forwards that also return the image: one atomic per (wave, entry) into the (tile, Gaussian) instance's slot
+                    // (MAX: two -- not the prune pass, no speed is asked of it)
                     const uint32_t slot = __float_as_uint(q2[wave][owned].z);
-                    if (slot < slot_cap) atomicAdd(&slots[slot], ((unsigned long long)(uint32_t)mycnt << LG_SLOT_COUNT_SHIFT) + myfix);
+                    if (MAX) { if (slot < slot_cap) lg_slot_count_max(&slots[slot], (uint32_t)mycnt, mymax); }
+                    else if (slot < slot_cap) atomicAdd(&slots[slot], ((unsigned long long)(uint32_t)mycnt << LG_SLOT_COUNT_SHIFT) + myfix);
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -908,7 +943,10 @@ lg_score_kernel(int N, const int32_t* __restrict__ count, const float* __restric
 // per-view count and score of the ALPHA / ALPHA_T policies: every Gaussian sums the {count : 16 | Q8.40 : 48} words of its own instances
 // (consecutive pre-sort slots, offsets - touched .. offsets) -- integer adds, any order -- and rounds the Q24.40 total to fp32 ONCE (nearest even),
 // times 2^-40 (exact).  A lane walks up to LG_SLOT_SOLO slots itself; Gaussians with more (screen-filling splats) are summed by the whole wave.
+// MAX (LG_FLAG_SCORE_MAX): the words are {count : 16 | fp32 bits of the instance's largest weight : 32 low}; counts are added as before and the score
+// is the largest low word over the Gaussian's slots, reinterpreted as float -- the weight of one hit, 0 without hits (and for a void view).
 #define LG_SLOT_SOLO 16u
+template <bool MAX = false>
 __global__ void __launch_bounds__(256)
 lg_score_slots(int N, const uint32_t* __restrict__ touched, const uint32_t* __restrict__ offsets, const unsigned long long* __restrict__ slots,
                uint32_t slot_cap, int32_t* __restrict__ count, float* __restrict__ score, int32_t* __restrict__ count_sum,
@@ -922,20 +960,31 @@ lg_score_slots(int N, const uint32_t* __restrict__ touched, const uint32_t* __re
     if (counters[0] != 0u || base >= slot_cap || n > slot_cap - base) n = 0;
     uint64_t fix = 0; uint32_t cnt = 0;
     if (n <= LG_SLOT_SOLO)
-        for (uint32_t k = 0; k < n; k++) { const uint64_t w = slots[base + k]; cnt += (uint32_t)(w >> LG_SLOT_COUNT_SHIFT); fix += w & ((1ull << LG_SLOT_COUNT_SHIFT) - 1ull); }
+        for (uint32_t k = 0; k < n; k++) {
+            const uint64_t w = slots[base + k];
+            cnt += (uint32_t)(w >> LG_SLOT_COUNT_SHIFT);
+            if (MAX) fix = max(fix, w & 0xFFFFFFFFull); else fix += w & ((1ull << LG_SLOT_COUNT_SHIFT) - 1ull);
+        }
     uint64_t big = __ballot(n > LG_SLOT_SOLO);
     while (big) {                                                 // wave-uniform
         const int src = __builtin_ctzll(big);
         big &= big - 1;
         const uint32_t bn = (uint32_t)__builtin_amdgcn_readlane((int)n, src), bb = (uint32_t)__builtin_amdgcn_readlane((int)base, src);
         uint64_t f = 0; uint32_t c = 0;
-        for (uint32_t k = lane; k < bn; k += 64u) { const uint64_t w = slots[bb + k]; c += (uint32_t)(w >> LG_SLOT_COUNT_SHIFT); f += w & ((1ull << LG_SLOT_COUNT_SHIFT) - 1ull); }
+        for (uint32_t k = lane; k < bn; k += 64u) {
+            const uint64_t w = slots[bb + k];
+            c += (uint32_t)(w >> LG_SLOT_COUNT_SHIFT);
+            if (MAX) f = max(f, w & 0xFFFFFFFFull); else f += w & ((1ull << LG_SLOT_COUNT_SHIFT) - 1ull);
+        }
 #pragma unroll
-        for (int sft = 32; sft > 0; sft >>= 1) { c += __shfl_xor(c, sft, 64); f += __shfl_xor(f, sft, 64); }
+        for (int sft = 32; sft > 0; sft >>= 1) {
+            c += __shfl_xor(c, sft, 64);
+            if (MAX) f = max((uint32_t)f, __shfl_xor((uint32_t)f, sft, 64)); else f += __shfl_xor(f, sft, 64);
+        }
         if ((int)lane == src) { cnt = c; fix = f; }
     }
     if (i < N) {
-        count[i] = (int32_t)cnt; score[i] = lg_fix40_score(fix);
+        count[i] = (int32_t)cnt; score[i] = MAX ? __uint_as_float((uint32_t)fix) : lg_fix40_score(fix);
         if (count_sum && cnt) count_sum[i] += (int32_t)cnt;
     }
 }

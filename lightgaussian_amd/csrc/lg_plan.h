@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include "../../include/lightgaussian.h"
+#include "../../include/lightgaussian_score.h"   // LG_FLAG_SCORE_MAX
 
 static inline int bits_for(uint32_t n) // smallest b with 2^b >= n
 {
@@ -58,14 +59,14 @@ static inline KeyPlan make_key_plan(int ntiles, int N, uint32_t dmax_bits, uint3
 // Which variant of every kernel one forward launches.  Made by make_forward_plan before the launches that read it; every fact is
 // computed here once and read by name everywhere else.
 enum { LG_CHAIN_NONE = 0, LG_CHAIN_COLOR = 1, LG_CHAIN_COUNT = 2 };                                     // ForwardPlan::long_chain
-enum { LG_SCORE_NONE = 0, LG_SCORE_COUNT = 1, LG_SCORE_COUNT_OPACITY = 2, LG_SCORE_SLOTS = 3 };         // ForwardPlan::score
+enum { LG_SCORE_NONE = 0, LG_SCORE_COUNT = 1, LG_SCORE_COUNT_OPACITY = 2, LG_SCORE_SLOTS = 3, LG_SCORE_SLOTS_MAX = 4 };   // ForwardPlan::score
 // The one definition of "this lg_blend_fwd<COUNT, FSCORE, EXACT, COLOR> merges its per-hit words in LDS and stores every slot once": the kernel's
 // MERGE and ForwardPlan::merge (hence clear_slots) both come from here.  A variant that adds into its slots with atomics needs them cleared first;
 // were the two to disagree, lg_score_slots would read stale sort keys as {count | weight} words.
 constexpr bool lg_blend_merges(int fscore, bool color) { return fscore != 0 && !color; }
 struct ForwardPlan {
-    // lg_blend_fwd<count, fscore, exact, color>: 11 of the 24 combinations exist (colour forward: exact or not; count forward with an
-    // image: 3 policies x exact or not; significance-only: 3 policies)
+    // lg_blend_fwd<count, fscore, exact, color, fmax>: 15 of the 48 combinations exist (colour forward: exact or not; count forward with an
+    // image: 3 policies x exact or not; significance-only: 3 policies; LG_FLAG_SCORE_MAX: the 2 per-hit policies, canonical exp, with or without the image)
     bool live;               // the view has Gaussians and instances (cap > 0 && N > 0): without them the blend kernel still runs (background, zero
                              // counts) but there is nothing to bin, clear or walk in parallel
     bool count;              // count forward: hit counts and scores are wanted (a colour forward ignores the weight policy)
@@ -74,6 +75,9 @@ struct ForwardPlan {
     int fscore;              // per-hit weights: 0, or LG_WEIGHT_ALPHA / LG_WEIGHT_ALPHA_T (= the kernels' LG_W_ALPHA / LG_W_ALPHA_T) -- the kernel is
                              // instantiated per policy and adds {count | Q8.40 weight} words into the instances' pre-sort slots: the radix sort's
                              // input buffer (keys_in), free since lg_tile_sort
+    bool fmax;               // LG_FLAG_SCORE_MAX on a per-hit policy: the slot words are {count : 16 at bit 48 | fp32 bits of the largest weight : 32 low} and
+                             // lg_score_slots<true> takes the maximum over a Gaussian's slots.  Everything else of the plan is the sum's: same slots, same
+                             // merge / clear rule, same serial walk
     bool merge;              // per-hit weights of the significance-only pass: the waves of a tile merge in LDS and write every slot exactly once
     bool clear_slots;        // ... every other per-hit variant adds into its slots with atomics, and the slots are cleared before the blend
     bool k1_skip_color;      // LG_FLAG_SKIP_COLOR as K1 sees it (count forward or not): no SH rows read, no dynamic-LDS pad
@@ -98,6 +102,7 @@ static inline ForwardPlan make_forward_plan(uint32_t flags, bool count, int weig
     p.k1_skip_color = flags & LG_FLAG_SKIP_COLOR;
     p.color = !(count && p.exact && p.k1_skip_color);
     p.fscore = (count && (weight_policy == LG_WEIGHT_ALPHA || weight_policy == LG_WEIGHT_ALPHA_T)) ? weight_policy : 0;
+    p.fmax = p.fscore && (flags & LG_FLAG_SCORE_MAX);
     p.merge = lg_blend_merges(p.fscore, p.color);
     p.clear_slots = p.fscore && !p.merge && p.live;
     p.k1_clears_count = count && !p.fscore;
@@ -121,6 +126,6 @@ static inline ForwardPlan make_forward_plan(uint32_t flags, bool count, int weig
         p.long_chain = LG_CHAIN_COUNT;
     }
     p.work_list_group = p.color || p.long_chain != LG_CHAIN_NONE;
-    p.score = !(count && N > 0) ? LG_SCORE_NONE : p.fscore ? LG_SCORE_SLOTS : weight_policy == LG_WEIGHT_OPACITY ? LG_SCORE_COUNT_OPACITY : LG_SCORE_COUNT;
+    p.score = !(count && N > 0) ? LG_SCORE_NONE : p.fscore ? (p.fmax ? LG_SCORE_SLOTS_MAX : LG_SCORE_SLOTS) : weight_policy == LG_WEIGHT_OPACITY ? LG_SCORE_COUNT_OPACITY : LG_SCORE_COUNT;
     return p;
 }

@@ -39,6 +39,13 @@ __device__ __forceinline__ uint32_t dpp_add_u32(uint32_t v)
     return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
 }
 
+// unsigned maximum across lanes through DPP: every lane receives max(v, v[partner])
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_max_u32(uint32_t v)
+{
+    return max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true));
+}
+
 // LDS hand-over inside ONE wave: what its lanes wrote to LDS before the call is what every lane reads after it.  Release fence, wave
 // barrier, acquire fence, all at wavefront scope: no s_barrier is issued -- the trio only keeps the compiler (and the LDS counter waits it
 // places) from moving an LDS access across.  Sites with another scope or without the acquire say so where they stand.

@@ -151,19 +151,33 @@ def _train_cameras(scene_or_list):
     return list(scene_or_list)
 
 
-def prune_list(gaussians, scene, pipe, background, count_fn=count_render):
+def _score_reduce(score_reduce):
+    """"sum" | "max" of a pass: the argument, or (None) the rasterizer option in force."""
+    from . import rasterizer
+    return rasterizer.score_reduce_name(rasterizer.option_value("score_reduce") if score_reduce is None else score_reduce)
+
+
+def prune_list(gaussians, scene, pipe, background, count_fn=count_render, score_reduce=None):
     """prune.py:133-157: sum of per-view (count, score) over all train cameras, popped from the END
-    of the list; the first view's tensors are the accumulators."""
+    of the list; the first view's tensors are the accumulators.
+    score_reduce: None = the rasterizer option in force ("sum" unless set); "max" = the forwards return the largest per-hit weight of their
+    view (rasterizer option score_reduce, per-hit weight policies only) and the views are folded with torch.maximum -- counts still add."""
+    from . import rasterizer
+    reduce = _score_reduce(score_reduce)
     viewpoint_stack = _train_cameras(scene)
-    viewpoint_cam = viewpoint_stack.pop()
-    render_pkg = count_fn(viewpoint_cam, gaussians, pipe, background)
-    gaussian_list, imp_list = render_pkg["gaussians_count"], render_pkg["important_score"]
-    for _ in range(len(viewpoint_stack)):
+    with rasterizer.options(score_reduce=reduce):
         viewpoint_cam = viewpoint_stack.pop()
         render_pkg = count_fn(viewpoint_cam, gaussians, pipe, background)
-        gaussians_count, important_score = render_pkg["gaussians_count"].detach(), render_pkg["important_score"].detach()
-        gaussian_list += gaussians_count
-        imp_list += important_score
+        gaussian_list, imp_list = render_pkg["gaussians_count"], render_pkg["important_score"]
+        for _ in range(len(viewpoint_stack)):
+            viewpoint_cam = viewpoint_stack.pop()
+            render_pkg = count_fn(viewpoint_cam, gaussians, pipe, background)
+            gaussians_count, important_score = render_pkg["gaussians_count"].detach(), render_pkg["important_score"].detach()
+            gaussian_list += gaussians_count
+            if reduce == "max":
+                torch.maximum(imp_list, important_score, out=imp_list)
+            else:
+                imp_list += important_score
     return gaussian_list, imp_list
 
 
@@ -280,6 +294,12 @@ class _ViewRunner:
         return total
 
 
+def _fold_max(rows, out):
+    """out = elementwise maximum of the rows; `out` may be rows[0] itself (running maximum kept in row 0).  A maximum is associative and
+    commutative: any order, any grouping of the rows gives the same bits."""
+    return out.copy_(torch.amax(rows, dim=0))
+
+
 def _ordered_sum(rows, out=None):
     """out = rows[0]; out += rows[1]; ... : the reference's sequential in-place float adds (prune.py:144-155).  `out` may be
     rows[0] itself (running sum kept in row 0).  On the GPU one lg_ordered_sum launch (same additions, same order); CPU
@@ -298,7 +318,7 @@ def _ordered_sum(rows, out=None):
 
 
 def prune_list_sharded(gaussians, scene, pipe, background, group=None, mode="ordered", count_fn=count_render, force_collectives=False,
-                       streams=4, block=24, local_only=False, host_threads=False, stats=None, weight_policy=None):
+                       streams=4, block=24, local_only=False, host_threads=False, stats=None, weight_policy=None, score_reduce=None):
     """Camera-sharded prune_list.  Every rank passes the SAME full camera list and the same Gaussians; returns the same
     (gaussian_list, imp_list) on every rank, bit-identical to the reference loop (mode="ordered") for every world size.
     Without an initialised process group (or at world size 1 unless force_collectives, or with local_only=True inside a
@@ -311,6 +331,14 @@ def prune_list_sharded(gaussians, scene, pipe, background, group=None, mode="ord
              _lib.WEIGHT_* number; None = the rasterizer option in force, default "opacity").  Every policy gives per-view scores that
              are pure functions of the view (integer-derived or Q24.40 fixed-point sums, no float atomics), so the ordered exchange
              below makes scores and masks bit-identical across world sizes for all four.
+    score_reduce: None = the rasterizer option in force ("sum" unless set).  "max" (per-hit weight policies only; ValueError otherwise, before
+             any forward): every forward returns the LARGEST per-hit weight of its view (rasterizer option score_reduce) and views, blocks and
+             ranks are folded with an elementwise maximum; gaussians_count still adds.  Scores and masks are bit-identical across world
+             sizes, block sizes and stream counts because nothing about a maximum depends on order or grouping: each per-view score is a
+             pure function of the view (the fp32 weight of one hit, taken unrounded from the blend), max is exactly associative and
+             commutative, and the running maximum starts at +0 under scores that are >= 0.  So the exchange is ONE all_reduce(MAX) whatever
+             `mode` says -- the ordered all-to-all exists only because float addition is not associative -- next to the counts'
+             all_reduce(SUM).
     block:   views per rank per round.  The pass keeps a running sum and absorbs the views round by round in the reference's
              order, so scratch memory is O(block * N) floats per rank whatever the number of views (the reference's loop is
              O(N); the first version of this function held all V score vectors, O(V * N)).
@@ -318,10 +346,11 @@ def prune_list_sharded(gaussians, scene, pipe, background, group=None, mode="ord
     4 -> 1326 views/s; round 2, one host thread: 3 -> 1540, 4 -> 1579, 6 -> 1513 (heavy-tailed scene: 1336 / 1412 / 1299)."""
     # the pass discards the images: its forwards do not read 192 B of SH per Gaussian per view (a per-call option of the
     # forwards THIS pass issues -- the process defaults are not touched, other threads render as before)
-    opts = {"skip_color_in_count": True}
+    from . import rasterizer
+    opts = {"skip_color_in_count": True, "score_reduce": _score_reduce(score_reduce)}
     if weight_policy is not None:
-        from . import rasterizer
         opts["weight_policy"] = rasterizer.weight_policy_id(weight_policy)
+    rasterizer.check_score_reduce(opts["score_reduce"], opts.get("weight_policy", rasterizer.option_value("weight_policy")))
     return _prune_list_sharded(gaussians, scene, pipe, background, group, mode, count_fn, force_collectives, streams, max(1, int(block)),
                                local_only, host_threads, opts, stats)
 
@@ -374,6 +403,8 @@ def _prune_list_sharded(gaussians, scene, pipe, background, group, mode, count_f
     f32 = dict(dtype=torch.float32, device=dev)
     runner = _ViewRunner(gaussians, pipe, background, count_fn, N, streams, host_threads, options)
     timed = _CollectiveTimer(dev, stats)
+    fmax = (options or {}).get("score_reduce") == "max"
+    fold = _fold_max if fmax else _ordered_sum      # how the rows of a block join the running row 0 (it starts at +0; scores are >= 0)
     if world == 1 and not (distributed and force_collectives):
         timed.finish(1)
         if V == 0:
@@ -384,13 +415,13 @@ def _prune_list_sharded(gaussians, scene, pipe, background, group, mode, count_f
         for c0 in range(0, V, block):
             views = seq[c0:c0 + block]
             runner.run(views, rows[1:])
-            _ordered_sum(rows[:1 + len(views)], out=rows[0])
+            fold(rows[:1 + len(views)], out=rows[0])
         return runner.count_sum(), rows[0].clone()
 
     chunk = (N + world - 1) // world                   # Gaussian slice owned by each rank in the ordered exchange
     # rows[1:] = my views of the current round (columns >= N stay zero); rows[0] = running local sum (mode "allreduce")
     rows = torch.zeros((block + 1, world * chunk), **f32)
-    if mode == "ordered":
+    if mode == "ordered" and not fmax:
         recv = torch.zeros((1 + block * world, chunk), **f32)   # row 0 = running sum of MY slice over all views so far
     for t in range(num_rounds(V, world, block)):
         spans = [round_views(V, world, r, block, t) for r in range(world)]
@@ -398,9 +429,9 @@ def _prune_list_sharded(gaussians, scene, pipe, background, group, mode, count_f
         lo, hi = spans[rank]
         mine = hi - lo
         runner.run(seq[lo:hi], rows[1:])
-        if mode == "allreduce":
+        if fmax or mode == "allreduce":
             if mine:
-                _ordered_sum(rows[:1 + mine, :N], out=rows[0, :N])
+                fold(rows[:1 + mine, :N], out=rows[0, :N])
             continue
         # ordered: rank j receives Gaussian slice j of every view of the round, in sequence order, and folds them into row 0
         send = rows[1:1 + mine].view(mine, world, chunk).permute(1, 0, 2).contiguous().view(world * mine, chunk)
@@ -409,9 +440,9 @@ def _prune_list_sharded(gaussians, scene, pipe, background, group, mode, count_f
         _ordered_sum(recv[:1 + total], out=recv[0])
     count_sum = runner.count_sum()
     timed(dist.all_reduce, count_sum, op=dist.ReduceOp.SUM, group=group)
-    if mode == "allreduce":
+    if fmax or mode == "allreduce":
         score = rows[0, :N].contiguous()
-        timed(dist.all_reduce, score, op=dist.ReduceOp.SUM, group=group)
+        timed(dist.all_reduce, score, op=dist.ReduceOp.MAX if fmax else dist.ReduceOp.SUM, group=group)
         timed.finish(world)
         return count_sum, score
     gathered = torch.empty(world * chunk, **f32)
@@ -484,6 +515,20 @@ def prune_points(model, mask):
         new.append(tuple(outs[k:k + width]) + (None,) * (3 - width))
         k += width
     return model_rows.install(model, entries, new, book=dict(zip(model_rows.BOOK, outs[k:])))
+
+
+def prune_mask_threshold(score, threshold):
+    """Mask of a fixed-threshold prune: everything with score < threshold goes.  With the "alpha_t" scores of a score_reduce="max" pass this is
+    RadSplat's rule (a Gaussian is kept when it has at least `threshold` of some pixel in some view; 0.01, or 0.25 for the light models)."""
+    return (score < threshold).squeeze()
+
+
+def prune_below(model, score, threshold):
+    """prune_points with prune_mask_threshold(score, threshold): the model and its optimizer state lose every row whose score is below
+    the threshold.  Returns the mask (True = pruned)."""
+    mask = prune_mask_threshold(score.detach().reshape(-1), threshold)
+    prune_points(model, mask)
+    return mask
 
 
 def prune_gaussians(model, percent, import_score):

@@ -45,7 +45,7 @@ class GaussianRasterizationSettings(NamedTuple):
 _OPTIONS = {"weight_policy": _lib.WEIGHT_OPACITY, "fast_exp": True, "profile": False, "skip_color_in_count": False,
             "fuse_getters": True, "sync_free": "validated", "max_depth": 100.0, "capacity_margin": 1.25,
             "segment_length": 0, "long_tiles": "auto", "count_long_tiles": "serial", "camera_grad": False, "antialiasing": False,
-            "filter_3d": True, "absgrad": False,
+            "filter_3d": True, "absgrad": False, "score_reduce": "sum",
             # cross-check switches of the tests: never needed in production, never read from the environment
             "sh_jacobian": True, "narrow_key": False, "sort_all_bits": False, "k1_lds": False, "count_wide_band": False}
 _PER_CALL_ONLY = ("pending", "tag", "status_override", "differentiated", "sh_grad_sink", "score_out", "count_sum")
@@ -54,6 +54,10 @@ _STRICT_BOOL = ("camera_grad", "antialiasing", "filter_3d", "absgrad")      # op
 _tls = threading.local()
 
 
+SCORE_REDUCTIONS = ("sum", "max")
+# LG_FLAG_SCORE_MAX of the extension header include/lightgaussian_score.h (tests/test_scoremax_host.py holds the two together; the
+# constants of _lib are those of lightgaussian.h)
+FLAG_SCORE_MAX = 65536
 WEIGHT_POLICIES = {"one": _lib.WEIGHT_ONE, "opacity": _lib.WEIGHT_OPACITY, "alpha": _lib.WEIGHT_ALPHA, "alpha_t": _lib.WEIGHT_ALPHA_T}
 
 
@@ -68,9 +72,27 @@ def weight_policy_id(value):
     return int(value)
 
 
+def score_reduce_name(value):
+    """"sum" | "max", as given to the option score_reduce (any letter case)."""
+    if not isinstance(value, str) or value.lower() not in SCORE_REDUCTIONS:
+        raise ValueError(f"score_reduce must be one of {SCORE_REDUCTIONS}")
+    return value.lower()
+
+
+def check_score_reduce(score_reduce, weight_policy):
+    """score_reduce="max" is defined for the per-hit policies only: with "one" / "opacity" every hit of a Gaussian adds the same
+    value, and the maximum of equal addends is the addend -- there is nothing to compute.  Raises ValueError; returns the name."""
+    name = score_reduce_name(score_reduce)
+    if name == "max" and weight_policy_id(weight_policy) not in (_lib.WEIGHT_ALPHA, _lib.WEIGHT_ALPHA_T):
+        raise ValueError('score_reduce="max" needs weight_policy "alpha" or "alpha_t" (every hit of "one" / "opacity" adds the same value)')
+    return name
+
+
 def _validate(name, value):
     if name == "weight_policy":
         weight_policy_id(value)
+    if name == "score_reduce":
+        score_reduce_name(value)
     if name == "long_tiles" and value not in _LONG_TILES:
         raise ValueError(f"long_tiles must be one of {_LONG_TILES}")
     if name == "count_long_tiles" and value not in ("serial", "parallel"):
@@ -96,6 +118,11 @@ def set_option(name, value):
               alpha_j of the hit) or "alpha_t" (alpha_j T, the hit's share of the pixel).  Every policy is deterministic and
               bit-pinned by the parity tests: the first two derive the fp32 score from the integer hit count, the per-hit ones add
               64-bit fixed-point weights (Q24.40, DESIGN.md section 5.5) -- no float atomics anywhere;
+    score_reduce: "sum" (default) | "max": how a count forward reduces the per-hit weights of a Gaussian over the view.  "max" (per-hit
+              policies only: "alpha" / "alpha_t"; ValueError with "one" / "opacity" before any native call) makes important_score the LARGEST
+              weight of any hit -- with "alpha_t" the largest share the Gaussian has of any pixel of the view, RadSplat's pruning score once
+              the views are folded with a maximum (prune_list / prune_list_sharded do) -- the fp32 value the blend computed, unrounded
+              (LG_FLAG_SCORE_MAX, DESIGN.md section 10.10).  gaussians_count and the image are unchanged; render() ignores the option;
     fast_exp (default True): hardware exp/rcp in render() -- training renders; set False for the canonical,
               bit-pinned arithmetic.  count renders (f_count=True) ALWAYS use the canonical arithmetic;
     profile: record per-kernel hipEvent timings (read with _lib.profile_read());
@@ -295,6 +322,8 @@ class _Call:
         flags |= _lib.profile_flag(opts["profile"])
         if exact and opts["skip_color_in_count"]:
             flags |= _lib.FLAG_SKIP_COLOR
+        if exact and check_score_reduce(opts.get("score_reduce", "sum"), opts["weight_policy"]) == "max":      # (raises before any native call)
+            flags |= FLAG_SCORE_MAX
         if exact:       # count forward: its own switch (the training forward's long_tiles does not reach the significance pass)
             flags |= _lib.FLAG_LONG_PARALLEL if opts["count_long_tiles"] == "parallel" else _lib.FLAG_LONG_SERIAL
         else:

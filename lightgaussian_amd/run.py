@@ -12,6 +12,10 @@
         (what one (pixel, Gaussian) hit adds to important_score in every count_render of the run: opacity (default, the paper's sigma_j),
          one, alpha or alpha_t -- the weight of the reference's un-vendored fork is not verifiable from its repository, SURVEY section 2.2;
          all four are deterministic and bit-pinned)
+    python -m lightgaussian_amd.run --weight-policy=alpha_t --score-reduce=max /path/to/prune_finetune.py ...
+        (important_score becomes the LARGEST per-hit weight over all hits and views instead of their sum -- with alpha_t the largest share a
+         Gaussian has of any pixel, RadSplat's score: the process default of the rasterizer option "score_reduce".  Needs alpha or alpha_t;
+         an unknown name or an equal-addend policy is refused before the script runs.  DESIGN.md section 10.10)
     python -m lightgaussian_amd.run --antialiasing /path/to/prune_finetune.py ...
         (every render and significance pass of the run compensates the opacities for the 0.3-pixel screen-space blur, as upstream
          3DGS's `antialiasing` pipeline switch does: the process default of the rasterizer option "antialiasing")
@@ -582,7 +586,7 @@ def main(argv=None):
     distributed = no_patch = verbose = adam = hip = hip_visible = lazy = no_timing = densify = antialiasing = absgrad = False
     backend = "nccl"
     dp_overlap = False
-    weight_policy = None
+    weight_policy = score_reduce = None
     while argv and argv[0].startswith("--") and not argv[0].endswith(".py"):
         flag = argv.pop(0)
         if flag == "--distributed":
@@ -613,10 +617,12 @@ def main(argv=None):
             from . import rasterizer
             weight_policy = flag.split("=", 1)[1]
             rasterizer.weight_policy_id(weight_policy)          # (raises on an unknown name before anything is set up)
+        elif flag.startswith("--score-reduce="):
+            score_reduce = flag.split("=", 1)[1]
         elif flag.startswith("--backend="):       # gloo: CPU tests of the launcher with a stand-in trainer (the rasterizer has no CPU path)
             backend = flag.split("=", 1)[1]
         else:
-            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --hip-adam=visible --hip-densify --lazy-loss --no-iter-timing --antialiasing --absgrad --weight-policy=NAME, then the script and ITS arguments)")
+            raise SystemExit(f"lightgaussian_amd.run: unknown option {flag} (options: --distributed --dp-overlap --no-patch --verbose --fused-adam --hip-adam --hip-adam=visible --hip-densify --lazy-loss --no-iter-timing --antialiasing --absgrad --weight-policy=NAME --score-reduce=sum|max, then the script and ITS arguments)")
     if adam and hip:
         raise SystemExit(f"lightgaussian_amd.run: --fused-adam and {'--hip-adam=visible' if hip_visible else '--hip-adam'} exclude each other (one optimizer step per run)")
     if hip_visible and distributed:
@@ -627,6 +633,12 @@ def main(argv=None):
     if absgrad and distributed:
         raise SystemExit("lightgaussian_amd.run: --absgrad and --distributed exclude each other (the data-parallel add_densification_stats "
                          "reads viewspace_point_tensor.grad)")
+    if score_reduce is not None:
+        from . import rasterizer
+        try:        # an unknown name, or "max" over a policy whose hits all add the same value: refused before the script runs
+            score_reduce = rasterizer.check_score_reduce(score_reduce, rasterizer.option_value("weight_policy") if weight_policy is None else weight_policy)
+        except ValueError as e:
+            raise SystemExit(f"lightgaussian_amd.run: --score-reduce={score_reduce}: {e}")
     if not argv:
         raise SystemExit(__doc__)
     script = os.path.abspath(argv[0])
@@ -669,6 +681,9 @@ def main(argv=None):
     if weight_policy is not None:
         from . import rasterizer
         rasterizer.set_option("weight_policy", rasterizer.weight_policy_id(weight_policy))     # process default of every count_render of the run
+    if score_reduce is not None:
+        from . import rasterizer
+        rasterizer.set_option("score_reduce", score_reduce)    # process default: count_render, prune_list and prune_list_sharded of the run reduce this way
     if antialiasing:
         from . import rasterizer
         rasterizer.set_option("antialiasing", True)        # process default: every render / count_render of the unmodified trainer and of prune_list
