@@ -4,7 +4,8 @@
 //                    the backward chain (lg_backward_chain), the SH backward steps (lg_sh_*) and the quaternion matrix (lg_quat_to_rot)
 //   lg_plan.h        host-side plans of one forward, plain C++ (also compiled by the CPU tests): KeyPlan (sort-key layout), ForwardPlan (kernel variants)
 //   lg_host.h        error strings, optional hipEvent profiler, scratch carving (GeomView / ImgView / BinView)
-//   lg_wave.h        wave64 primitives (DPP / permlane reductions, lg_wave_lds_sync: the LDS hand-over inside a wave)
+//   lg_wave.h        wave64 primitives (DPP reductions; lg_wave_scan_incl: the one wave prefix sum; lg_wave_all_max / _or; lg_block_scan_put / _get: the
+//                    workgroup scan around the caller's barrier; lg_wave_lds_sync: the LDS hand-over inside a wave)
 //   lg_preprocess.h  K1 lg_preprocess<RAW, DIRECT, AA>, K8+K9 lg_preprocess_bwd<RAW, JAC, AA> (AA: LG_FLAG_ANTIALIAS)   (per Gaussian, HBM-bound); lg_k9_*: K9's read side, shared with lg_camera.h;
 //                    lg_sh_rows_flush: how dL/dSH rows leave LDS (K9 and lg_sh_grad_from_rgb_kernel)
 //   lg_binning.h     K2 lg_scan_blocks, K3 lg_duplicate, lg_tile_sort / _long (second sort stage), lg_tile_ranges (one-stage cross-check only),

@@ -33,18 +33,15 @@ lg_scan_blocks(int nblk, const uint32_t* __restrict__ blk_sum, const uint32_t* _
     {
         const int i = (int)blockIdx.x * LG_PART + (int)tid;
         const uint32_t v = i < nblk ? blk_sum[i] : 0u, d = i < nblk ? blk_dmax[i] : 0u;
-        uint32_t inc = v, m = d & 0x7FFFFFFFu, f = d >> 31;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const uint32_t o = __shfl_up(inc, s, 64);
-            if ((int)lane >= s) inc += o;
-        }
-#pragma unroll
+        const uint32_t inc = lg_wave_scan_incl(v, lane);
+        uint32_t m = d & 0x7FFFFFFFu, f = d >> 31;
+#pragma unroll                                                      // (written out: lg_wave_all_max / _or here cost the kernel 7 instructions)
         for (int sh = 32; sh > 0; sh >>= 1) { m = max(m, (uint32_t)__shfl_xor((int)m, sh)); f |= (uint32_t)__shfl_xor((int)f, sh); }
-        if (lane == 63u) { wsum[wave] = inc; wmax[wave] = m; wflag[wave] = f; }
+        lg_block_scan_put(wsum, wave, lane, inc);
+        if (lane == 63u) { wmax[wave] = m; wflag[wave] = f; }
         __syncthreads();
         uint32_t woff = 0, total = 0;
-#pragma unroll
+#pragma unroll                                                      // (written out, here and below: lg_block_scan_get costs the kernel 10 instructions)
         for (int w = 0; w < 16; w++) {
             const uint32_t t = wsum[w];
             woff += (w < (int)wave) ? t : 0u;
@@ -70,14 +67,9 @@ lg_scan_blocks(int nblk, const uint32_t* __restrict__ blk_sum, const uint32_t* _
         const uint32_t v = j < nparts ? __hip_atomic_load(&part_sum[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
         const uint32_t d = j < nparts ? __hip_atomic_load(&part_dmax[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
         m = max(m, d & 0x7FFFFFFFu); f |= d >> 31;
-        uint32_t inc = v;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const uint32_t o = __shfl_up(inc, s, 64);
-            if ((int)lane >= s) inc += o;
-        }
+        const uint32_t inc = lg_wave_scan_incl(v, lane);
         __syncthreads();                                            // (wsum of the previous round / of the part scan is free)
-        if (lane == 63u) wsum[wave] = inc;
+        lg_block_scan_put(wsum, wave, lane, inc);
         __syncthreads();
         uint32_t woff = 0;
         uint64_t total = 0;
@@ -90,8 +82,7 @@ lg_scan_blocks(int nblk, const uint32_t* __restrict__ blk_sum, const uint32_t* _
         if (j < nparts) part_prefix[j] = (uint32_t)carry + woff + inc - v;
         carry += total;
     }
-#pragma unroll
-    for (int sh = 32; sh > 0; sh >>= 1) { m = max(m, (uint32_t)__shfl_xor((int)m, sh)); f |= (uint32_t)__shfl_xor((int)f, sh); }
+    m = lg_wave_all_max(m); f = lg_wave_all_or(f);
     __syncthreads();
     if (lane == 0u) { wmax[wave] = m; wflag[wave] = f; }
     __syncthreads();
@@ -183,12 +174,7 @@ lg_duplicate(int N, int nblk, int gx, int stored_depth_bits, int store_drop, int
             const int b = g * 4 + u, i = b * 64 + (int)lane;
             const uint32_t t = t4[u], base = base4[u];
             const uint4 r = r4[u];
-            uint32_t inc = t;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) {
-                const uint32_t o = __shfl_up(inc, s, 64);
-                if ((int)lane >= s) inc += o;
-            }
+            const uint32_t inc = lg_wave_scan_incl(t, lane);
             const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
             if (b < nblk && i < N) offsets[i] = base + inc;   // inclusive scan, as K9 expects (slot base = offsets - touched)
             if (total != 0u) {                                 // wave-uniform
@@ -272,14 +258,8 @@ __device__ __forceinline__ void lg_wave_sort_run(uint32_t i, uint32_t e, int low
         lg_wave_lds_sync();
         {   // exclusive scan of the 256 counters: lane l owns digits 4 l .. 4 l + 3
             const uint32_t c0 = cnt[4u * lane], c1 = cnt[4u * lane + 1u], c2 = cnt[4u * lane + 2u], c3 = cnt[4u * lane + 3u];
-            uint32_t inc = c0 + c1 + c2 + c3;
-            const uint32_t own = inc;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) {
-                const uint32_t o = __shfl_up(inc, s, 64);
-                if ((int)lane >= s) inc += o;
-            }
-            const uint32_t ex = inc - own;
+            const uint32_t own = c0 + c1 + c2 + c3;
+            const uint32_t ex = lg_wave_scan_incl(own, lane) - own;
             cnt[4u * lane] = ex; cnt[4u * lane + 1u] = ex + c0; cnt[4u * lane + 2u] = ex + c0 + c1; cnt[4u * lane + 3u] = ex + c0 + c1 + c2;
         }
         lg_wave_lds_sync();
@@ -312,6 +292,14 @@ __device__ __forceinline__ void lg_wave_sort_run(uint32_t i, uint32_t e, int low
     }
 }
 
+// Called by the first kernel after the sort (lg_tile_ranges / lg_tile_sort) on an aborted view.  K2 handed the caller its copy of
+// the abort word (status, may be NULL) BEFORE the sort ran: an abort raised by the sort (LG_ABORT_SORT) is added here, by one thread.
+__device__ __forceinline__ void lg_abort_handover(const uint32_t* __restrict__ counters, uint32_t* status)
+{
+    if (status && blockIdx.x == 0 && threadIdx.x == 0 && (counters[0] & LG_ABORT_SORT))
+        __hip_atomic_store(&status[0], counters[0], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 __global__ void __launch_bounds__(256)
 lg_tile_ranges(const uint32_t* __restrict__ counters, int tile_shift, int gid_bits, uint32_t gid_mask, int finish_bits, int store_drop,
                uint64_t* entries /* the sorted keys */, uint64_t* scratch, const uint4* __restrict__ tinfo, uint2* __restrict__ ranges,
@@ -319,10 +307,7 @@ lg_tile_ranges(const uint32_t* __restrict__ counters, int tile_shift, int gid_bi
 {
     __shared__ uint32_t s_cnt[4][256];
     if (counters[0] != 0u) {                       // view aborted (capacity-bounded forward, or the sort's look-back gave up)
-        // K2 handed the caller its copy of the abort word BEFORE the sort ran: an abort raised by the sort is added here
-        if (status && blockIdx.x == 0 && threadIdx.x == 0 && (counters[0] & LG_ABORT_SORT)) {
-            __hip_atomic_store(&status[0], counters[0], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        lg_abort_handover(counters, status);
         return;
     }
     const uint32_t R = counters[3];                // the grid is sized for the capacity; the instance count lives on the device
@@ -408,6 +393,8 @@ __device__ __forceinline__ uint32_t lg_ts_digit(uint64_t key, int shift, uint32_
 
 // rank of a key among the keys of its wave's earlier items and lower lanes with the same digit.  mask = 512 zeroed 64-bit words
 // of this wave (zero again on return), wc = this wave's 16-bit digit counters.  Every lane takes part (padding keys included).
+// (lg_onesweep_pass ranks with an inlined cousin of this and is NOT merged with it: its `valid` gate and its release-only fences,
+// without the acquire, are deliberate there.)
 __device__ __forceinline__ uint32_t lg_ts_rank(uint32_t d, unsigned long long* mask, unsigned short* wc, unsigned long long mybit)
 {
     atomicOr(&mask[d], mybit);
@@ -426,6 +413,37 @@ __device__ __forceinline__ int lg_ts_width(int depth_bits)
 {
     const int passes = (depth_bits + LG_TS_DIGIT - 1) / LG_TS_DIGIT;
     return (depth_bits + passes - 1) / passes;
+}
+
+// The two scans of the workgroup counting sorts (lg_tile_sort_wg, lg_tile_sort_long).  Thread t < 256 owns digits 2 t and 2 t + 1,
+// one 32-bit word of two 16-bit counters in every wave's row.  No barrier in here: they stand at the call sites.
+// exclusive scan of the per-wave digit counters over the WAVES waves, written back; run0 / run1 = the two digits' totals
+template <int WAVES>
+__device__ __forceinline__ void lg_ts_scan_waves(unsigned short (*wcnt)[LG_TS_BINS], uint32_t tid, uint32_t& run0, uint32_t& run1)
+{
+    run0 = 0; run1 = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; w++) {
+        uint32_t* pw = reinterpret_cast<uint32_t*>(&wcnt[w][0]) + tid;
+        const uint32_t pr = *pw;
+        *pw = run0 | (run1 << 16);
+        run0 += pr & 0xFFFFu; run1 += pr >> 16;
+    }
+}
+// exclusive scan of the 512 digit totals (t0, t1 = the two a thread owns) into base[512], through wtot[4]: put, the caller's
+// __syncthreads(), get.  Executed by the first four waves only.
+__device__ __forceinline__ uint32_t lg_ts_base_put(uint32_t t0, uint32_t t1, uint32_t* wtot, uint32_t lane, uint32_t wave)
+{
+    const uint32_t inc = lg_wave_scan_incl(t0 + t1, lane);
+    lg_block_scan_put(wtot, wave, lane, inc);
+    return inc;
+}
+__device__ __forceinline__ void lg_ts_base_get(uint32_t inc, uint32_t t0, uint32_t t1, const uint32_t* wtot, uint32_t* base, uint32_t tid, uint32_t wave)
+{
+    uint32_t ex = inc - (t0 + t1);
+    for (uint32_t w = 0; w < wave; w++) ex += wtot[w];
+    base[2u * tid] = ex;
+    base[2u * tid + 1u] = ex + t0;
 }
 
 #define LG_TW_ITEMS 16
@@ -480,13 +498,7 @@ __device__ __forceinline__ void lg_tile_sort_wave(uint32_t tile, uint32_t lane, 
             const uint32_t c0 = c.x & 0xFFFFu, c1 = c.x >> 16, c2 = c.y & 0xFFFFu, c3 = c.y >> 16, c4 = c.z & 0xFFFFu, c5 = c.z >> 16, c6 = c.w & 0xFFFFu,
                            c7 = c.w >> 16;
             const uint32_t own = ((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7));
-            uint32_t inc = own;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) {
-                const uint32_t o = __shfl_up(inc, s, 64);
-                if ((int)lane >= s) inc += o;
-            }
-            const uint32_t e0 = inc - own, e1 = e0 + c0, e2 = e1 + c1, e3 = e2 + c2, e4 = e3 + c3, e5 = e4 + c4, e6 = e5 + c5, e7 = e6 + c6;
+            const uint32_t e0 = lg_wave_scan_incl(own, lane) - own, e1 = e0 + c0, e2 = e1 + c1, e3 = e2 + c2, e4 = e3 + c3, e5 = e4 + c4, e6 = e5 + c5, e7 = e6 + c6;
             reinterpret_cast<uint4*>(cnt)[lane] = make_uint4(e0 | (e1 << 16), e2 | (e3 << 16), e4 | (e5 << 16), e6 | (e7 << 16));
         }
         lg_wave_lds_sync();
@@ -595,28 +607,12 @@ __device__ __forceinline__ void lg_tile_sort_wg(uint32_t tile, uint64_t* stage, 
             }
         }
         __syncthreads();
-        // thread t owns digits 2 t and 2 t + 1: exclusive scan over the waves (written back), then over the digits
-        uint32_t run0 = 0, run1 = 0;
-#pragma unroll
-        for (int w = 0; w < LG_TS_WAVES; w++) {
-            uint32_t* pw = reinterpret_cast<uint32_t*>(&wcnt[w][0]) + tid;
-            const uint32_t pr = *pw;
-            *pw = run0 | (run1 << 16);
-            run0 += pr & 0xFFFFu; run1 += pr >> 16;
-        }
-        const uint32_t own = run0 + run1;
-        uint32_t inc = own;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const uint32_t o = __shfl_up(inc, s, 64);
-            if ((int)lane >= s) inc += o;
-        }
-        if (lane == 63u) wtot[wave] = inc;
+        // exclusive scan over the waves (written back), then over the digits
+        uint32_t run0, run1;
+        lg_ts_scan_waves<LG_TS_WAVES>(wcnt, tid, run0, run1);
+        const uint32_t inc = lg_ts_base_put(run0, run1, wtot, lane, wave);
         __syncthreads();
-        uint32_t carry = 0;
-        for (uint32_t w = 0; w < wave; w++) carry += wtot[w];
-        lbase[2u * tid] = carry + inc - own;
-        lbase[2u * tid + 1u] = carry + inc - own + run0;
+        lg_ts_base_get(inc, run0, run1, wtot, lbase, tid, wave);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < LG_TS_ITEMS; k++) {
@@ -650,10 +646,7 @@ lg_tile_sort(int ntiles, const uint32_t* __restrict__ counters, uint2* ranges, u
     __shared__ __attribute__((aligned(16))) unsigned char smem[LG_TS_SMEM];
     const bool aborted = counters[0] != 0u;        // capacity-bounded forward gave the view up, or the sort's look-back did
     const uint32_t nquad = ((uint32_t)ntiles + 3u) / 4u;
-    if (aborted && status && blockIdx.x == 0 && threadIdx.x == 0 && (counters[0] & LG_ABORT_SORT)) {
-        // K2 handed the caller its copy of the abort word BEFORE the sort ran: an abort raised by the sort is added here
-        __hip_atomic_store(&status[0], counters[0], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (aborted) lg_abort_handover(counters, status);
     if (blockIdx.x < nquad) {
         const uint32_t wave = threadIdx.x >> 6, tile = blockIdx.x * 4u + wave;
         if (tile >= (uint32_t)ntiles) return;
@@ -733,21 +726,10 @@ lg_tile_sort_long(const uint32_t* __restrict__ counters, const uint2* __restrict
             if (tid < 256u) {
                 t0 = gnext[2u * tid]; t1 = gnext[2u * tid + 1u];
                 gnext[2u * tid] = 0u; gnext[2u * tid + 1u] = 0u;
-                inc = t0 + t1;
-#pragma unroll
-                for (int s = 1; s < 64; s <<= 1) {
-                    const uint32_t o = __shfl_up(inc, s, 64);
-                    if ((int)lane >= s) inc += o;
-                }
-                if (lane == 63u) wtot[wave] = inc;
+                inc = lg_ts_base_put(t0, t1, wtot, lane, wave);
             }
             __syncthreads();
-            if (tid < 256u) {
-                uint32_t carry = 0;
-                for (uint32_t w = 0; w < wave; w++) carry += wtot[w];
-                gbase[2u * tid] = carry + inc - (t0 + t1);
-                gbase[2u * tid + 1u] = carry + inc - t1;
-            }
+            if (tid < 256u) lg_ts_base_get(inc, t0, t1, wtot, gbase, tid, wave);
             // ---- phase B: chunk by chunk in list order ----
             for (uint32_t c0 = 0; c0 < n; c0 += LG_TL_CHUNK) {
                 const uint32_t cn = min((uint32_t)LG_TL_CHUNK, n - c0);
@@ -769,15 +751,7 @@ lg_tile_sort_long(const uint32_t* __restrict__ counters, const uint2* __restrict
                 }
                 __syncthreads();
                 uint32_t run0 = 0, run1 = 0;
-                if (tid < 256u) {
-#pragma unroll
-                    for (int w = 0; w < LG_TL_WAVES; w++) {
-                        uint32_t* pw = reinterpret_cast<uint32_t*>(&wcnt[w][0]) + tid;
-                        const uint32_t pr = *pw;
-                        *pw = run0 | (run1 << 16);
-                        run0 += pr & 0xFFFFu; run1 += pr >> 16;
-                    }
-                }
+                if (tid < 256u) lg_ts_scan_waves<LG_TL_WAVES>(wcnt, tid, run0, run1);
                 __syncthreads();
 #pragma unroll
                 for (int k = 0; k < LG_TL_ITEMS; k++) {

@@ -1195,9 +1195,7 @@ lg_blend_bwd(int W, int H, int gx, int S, const uint2* __restrict__ work, const 
         a0[s] = a1[s] = a2[s] = la[s] = lc0[s] = lc1[s] = lc2[s] = Sd[s] = 0.0f;
         wmax = max(wmax, last[s]);
     }
-#pragma unroll
-    for (int sh = 32; sh > 0; sh >>= 1) wmax = max(wmax, (uint32_t)__shfl_xor((int)wmax, sh));
-    wmax = __builtin_amdgcn_readfirstlane(wmax);
+    wmax = __builtin_amdgcn_readfirstlane(lg_wave_all_max(wmax));
     const uint32_t n_list = range.y - range.x;
     if (n_list == 0) return;
     // this work item = list entries [seg_lo, seg_hi) of the tile (the whole list unless it is longer than S)

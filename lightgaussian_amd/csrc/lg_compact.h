@@ -22,7 +22,7 @@ lg_compact_count(int N, const uint8_t* __restrict__ keep, uint32_t* __restrict__
     uint32_t c = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) c += (r0 + k < N && keep[r0 + k]) ? 1u : 0u;
-#pragma unroll
+#pragma unroll                                                          // (written out: behind a helper of lg_wave.h the kernel's SGPR figure changes)
     for (int sh = 32; sh > 0; sh >>= 1) c += (uint32_t)__shfl_xor((int)c, sh);
     if ((threadIdx.x & 63u) == 0u) ws[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -39,21 +39,11 @@ lg_scan_words(int n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out
     for (int base = 0; base < n; base += 1024) {
         const int i = base + (int)tid;
         const uint32_t v = i < n ? in[i] : 0u;
-        uint32_t x = v;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const uint32_t o = __shfl_up(x, s, 64);
-            if ((int)lane >= s) x += o;
-        }
-        if (lane == 63u) wsum[wave] = x;
+        const uint32_t x = lg_wave_scan_incl(v, lane);
+        lg_block_scan_put(wsum, wave, lane, x);
         __syncthreads();
-        uint32_t woff = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 16; w++) {
-            const uint32_t t = wsum[w];
-            woff += (w < (int)wave) ? t : 0u;
-            tot += t;
-        }
+        uint32_t tot;
+        const uint32_t woff = lg_block_scan_get<16>(wsum, wave, tot);
         if (i < n) out[i] = carry + woff + x - v;
         carry += tot;
         __syncthreads();
@@ -72,13 +62,8 @@ lg_compact_dest(int N, const uint8_t* __restrict__ keep, const uint32_t* __restr
     uint32_t c = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) { k4[k] = r0 + k < N && keep[r0 + k]; c += k4[k] ? 1u : 0u; }
-    uint32_t inc = c;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t o = __shfl_up(inc, s, 64);
-        if ((int)lane >= s) inc += o;
-    }
-    if (lane == 63u) ws[wave] = inc;
+    const uint32_t inc = lg_wave_scan_incl(c, lane);
+    lg_block_scan_put(ws, wave, lane, inc);
     __syncthreads();
     uint32_t pos = blk_off[blockIdx.x] + inc - c;
     for (uint32_t w = 0; w < wave; w++) pos += ws[w];

@@ -110,22 +110,14 @@ lg_densify_scan(int n, const uint4* __restrict__ in, uint4* __restrict__ out, in
         const int i = base + (int)tid;
         const uint4 v4 = i < n ? in[i] : make_uint4(0, 0, 0, 0);
         const uint32_t v[4] = { v4.x, v4.y, v4.z, v4.w };
-        uint32_t x[4] = { v4.x, v4.y, v4.z, v4.w };
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const uint32_t o = __shfl_up(x[c], s, 64);
-                if ((int)lane >= s) x[c] += o;
-            }
-        }
+        const uint32_t x[4] = { lg_wave_scan_incl(v4.x, lane), lg_wave_scan_incl(v4.y, lane), lg_wave_scan_incl(v4.z, lane), lg_wave_scan_incl(v4.w, lane) };
         if (lane == 63u) { wsum[wave][0] = x[0]; wsum[wave][1] = x[1]; wsum[wave][2] = x[2]; wsum[wave][3] = x[3]; }
         __syncthreads();
         uint32_t r[4];
 #pragma unroll
         for (int c = 0; c < 4; c++) {
             uint32_t woff = 0, tot = 0;
-#pragma unroll
+#pragma unroll                                                      // (written out: a strided lg_block_scan_get changes the kernel's VGPR figure)
             for (int w = 0; w < 16; w++) {
                 const uint32_t t = wsum[w][c];
                 woff += (w < (int)wave) ? t : 0u;
@@ -162,12 +154,7 @@ lg_densify_map(int N, const uint8_t* __restrict__ flags, const uint4* __restrict
         a += (f4[k] & LG_DF_KEEP ? 1u : 0u) + (f4[k] & LG_DF_CLONE ? 0x10000u : 0u);
         b += (f4[k] & LG_DF_SPLIT ? 1u : 0u) + (f4[k] & LG_DF_CHILD ? 0x10000u : 0u);
     }
-    uint32_t ia = a, ib = b;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t oa = __shfl_up(ia, s, 64), ob = __shfl_up(ib, s, 64);
-        if ((int)lane >= s) { ia += oa; ib += ob; }
-    }
+    const uint32_t ia = lg_wave_scan_incl(a, lane), ib = lg_wave_scan_incl(b, lane);
     if (lane == 63u) { ws[wave][0] = ia; ws[wave][1] = ib; }
     __syncthreads();
     uint32_t ea = ia - a, eb = ib - b;

@@ -352,10 +352,7 @@ lg_features_bwd_geom(LgFeatView v, uint32_t S, const uint32_t* __restrict__ meta
         Tfb = T * bgdot;
     }
     // the last list position any pixel of the wave / of the tile reached
-    uint32_t wl = last;
-#pragma unroll
-    for (int sh = 32; sh > 0; sh >>= 1) wl = max(wl, (uint32_t)__shfl_xor((int)wl, sh));
-    wl = (uint32_t)__builtin_amdgcn_readfirstlane((int)wl);
+    const uint32_t wl = (uint32_t)__builtin_amdgcn_readfirstlane((int)lg_wave_all_max(last));
     if (lane == 0u) wlast[wave] = wl;
     __syncthreads();
     const uint32_t tl = max(max(wlast[0], wlast[1]), max(wlast[2], wlast[3]));

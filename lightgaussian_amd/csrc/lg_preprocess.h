@@ -233,9 +233,7 @@ lg_preprocess(int N, int M, int D, int W, int H, float tanfovx, float tanfovy, f
     // (no global visible-counter: 47k same-address atomics serialise at ~11 ns each -- more than the whole kernel)
     // largest depth of the workgroup (bit pattern; positive floats order like integers), for the packed sort key.
     // Written per workgroup and reduced by a one-block kernel: a shared atomicMax serialises the first ~3k waves.
-    uint32_t dmax = vis ? __float_as_uint(sp.depth) : 0u;
-#pragma unroll
-    for (int sh = 32; sh > 0; sh >>= 1) dmax = max(dmax, (uint32_t)__shfl_xor((int)dmax, sh));
+    const uint32_t dmax = lg_wave_all_max(vis ? __float_as_uint(sp.depth) : 0u);
     // bit 31 (never set in the bit pattern of a positive depth): a prefiltered violation in this workgroup
     // ... and its instance count: lg_scan_blocks scans these words (one per 64 Gaussians) instead of a device-wide scan of N
     uint32_t tsum = touched;

@@ -37,12 +37,7 @@ __device__ __forceinline__ uint32_t lg_select_resolve(const LgSelect* __restrict
             const uint32_t l = threadIdx.x;
             const uint4 h = *reinterpret_cast<const uint4*>(&st->hist[p][4 * l]);
             const uint32_t mine = h.x + h.y + h.z + h.w;
-            // inclusive scan across the wave (DPP-free, 6 steps of shuffles: runs once per block per pass)
-            uint32_t inc = mine;
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(inc, d, 64);
-                if ((int)l >= d) inc += o;
-            }
+            const uint32_t inc = lg_wave_scan_incl(mine, l);     // (runs once per block per pass)
             const uint32_t exc = inc - mine;
             const bool owner = r >= exc && r < inc;     // exactly one lane (total count > rank by construction)
             uint32_t digit = 0, below = 0;

@@ -191,13 +191,9 @@ lg_onesweep_pass(const uint64_t* __restrict__ src, uint64_t* __restrict__ dst, c
         // publish the tile's aggregate before looking back: nobody ever waits for more than this store
         if (tile > 0) lg_st_state(&states[(size_t)tile * 256 + tid], (LG_SORT_FLAG_AGG << 30) | run);
         // exclusive scans over the 256 digits of (run, gh): wave scan + cross-wave carry through LDS
-        uint32_t ir = run, ig = gh;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const uint32_t orr = __shfl_up(ir, s, 64), og = __shfl_up(ig, s, 64);
-            if ((int)lane >= s) { ir += orr; ig += og; }
-        }
-        if (lane == 63u) { wtot[wave] = ir; wtot[4 + wave] = ig; }
+        const uint32_t ir = lg_wave_scan_incl(run, lane), ig = lg_wave_scan_incl(gh, lane);
+        lg_block_scan_put(wtot, wave, lane, ir);
+        lg_block_scan_put(wtot + 4, wave, lane, ig);
         lbase[tid] = ir - run;                                              // wave-local exclusive; carry added below
         goff[tid] = ig - gh;
     }

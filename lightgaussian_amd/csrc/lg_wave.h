@@ -1,4 +1,4 @@
-// lg_wave.h -- wave64 primitives: lane id, prefix popcount, DPP / permlane reductions, XCD-aware tile mapping
+// lg_wave.h -- wave64 primitives: lane id, prefix popcount, DPP reductions, inclusive wave scan, butterfly all-reduces, two-part workgroup scan, LDS hand-over
 // Part of liblightgaussian_hip.so (single translation unit: lg_api.hip includes the lg_*.h kernel headers).
 #pragma once
 
@@ -44,6 +44,56 @@ template <int CTRL>
 __device__ __forceinline__ uint32_t dpp_max_u32(uint32_t v)
 {
     return max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true));
+}
+
+// inclusive prefix sum over the 64 lanes of a wave (6 shuffle steps; every lane takes part)
+__device__ __forceinline__ uint32_t lg_wave_scan_incl(uint32_t v, uint32_t lane)
+{
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t o = __shfl_up(v, s, 64);
+        if ((int)lane >= s) v += o;
+    }
+    return v;
+}
+
+// butterfly all-reduces: every lane receives the maximum / or over the 64 lanes.  (There is no sum: at its two sites, lg_compact_count
+// and lg_preprocess, a helper changed the kernel's register figures or instruction text, so they keep their loops.)
+__device__ __forceinline__ uint32_t lg_wave_all_max(uint32_t v)
+{
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, sh));
+    return v;
+}
+__device__ __forceinline__ uint32_t lg_wave_all_or(uint32_t v)
+{
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) v |= (uint32_t)__shfl_xor((int)v, sh);
+    return v;
+}
+
+// Workgroup exclusive scan on top of lg_wave_scan_incl, in two parts with the CALLER's __syncthreads() between them (callers ride
+// other words on that barrier, or scan several channels behind one): put = lane 63 leaves its wave's total (`inc` = the wave's
+// inclusive scan), get = sum of the totals of the waves below + the grand total.  The exclusive prefix of a thread is
+// get() + inc - its own value.  (The four-wave sites -- lg_ts_base_get, lg_compact_dest, lg_densify_map, lg_onesweep_pass -- sum the
+// totals below with a loop over w < wave instead: get's select form changes their kernels' register figures.  Sites that spell
+// get's loop out say why where they stand.)
+__device__ __forceinline__ void lg_block_scan_put(uint32_t* wsum, uint32_t wave, uint32_t lane, uint32_t inc)
+{
+    if (lane == 63u) wsum[wave] = inc;
+}
+template <int WAVES>
+__device__ __forceinline__ uint32_t lg_block_scan_get(const uint32_t* wsum, uint32_t wave, uint32_t& total)
+{
+    uint32_t woff = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; w++) {
+        const uint32_t t = wsum[w];
+        woff += (w < (int)wave) ? t : 0u;
+        total += t;
+    }
+    return woff;
 }
 
 // LDS hand-over inside ONE wave: what its lanes wrote to LDS before the call is what every lane reads after it.  Release fence, wave

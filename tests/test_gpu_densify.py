@@ -64,7 +64,8 @@ def both_backends(c, noise=None):
     return ours, out, counts, r64
 
 
-@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 5000])
+# (1_049_601 = 1025 * 1024 + 1 rows are 1026 block words: the single-workgroup scan of lg_densify_plan takes its second, carry round)
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 5000, 1_049_601])
 def test_hip_equals_torch_on_the_device(n):
     c = dc.random_case(n, deg=1, seed=100 + n)
     if n == 1:                                      # the one row is split: above the gradient threshold, larger than percent_dense * extent

@@ -101,7 +101,7 @@ def test_view_status_reads_the_abort_word_of_a_healthy_view():
     assert words[0] == 0 and words[3] > 0 and words[3] == _lib.last_stats()["num_rendered"]
 
 
-# ---- second stage of the view's sort: every tile's list ordered by depth inside LDS (lg_tile_sort / _mid / _long) ----
+# ---- second stage of the view's sort: every tile's list ordered by depth inside LDS (lg_tile_sort / _long) ----
 def _tile_lists(image, W, H):
     """(ranges [tiles, 2], entries [R] uint64) of the view that produced `image`, from the binning buffer its forward saved."""
     from lightgaussian_amd import rasterizer
