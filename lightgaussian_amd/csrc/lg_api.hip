@@ -29,6 +29,8 @@
 //   lg_absgrad.h     lg_absgrad_rows: absolute screen-space mean gradients per Gaussian from floats 9, 10 of the rows K7<ABS> left (lg_backward_abs)
 //   lg_filter3d.h    lg_filter3d_update / _apply / _apply_bwd: Mip-Splatting's 3D smoothing filter from the training cameras, and its raw -> raw
 //                    (or activated) application to scales and opacity with its backward
+//   lg_normals.h     lg_normal_rows / lg_depth_normals / lg_normal_loss and their backwards: view-space normals of the Gaussians, normals of a
+//                    depth map, the fused depth-normal consistency loss (include/lightgaussian_normals.h; a wave per strip, register ring)
 //
 // Pipeline of one view:
 //   K1 project + EWA + SH->RGB + exact footprint culling  ->  K2 scan of instance counts, blocking read of R
@@ -63,6 +65,7 @@
 #include "lg_camera.h"
 #include "lg_absgrad.h"
 #include "lg_filter3d.h"
+#include "lg_normals.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1508,6 +1511,144 @@ extern "C" int lg_filter3d_apply_bwd(int32_t N, const float* scaling, const floa
     filter3d_apply_bwd_kernel(flags & LG_FILTER3D_RAW)<<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, dL_dout_scaling, dL_dout_opacity,
                                                                                            dL_dscaling, dL_dopacity);
     KLAUNCHED("lg_filter3d_apply_bwd_kernel");
+    return LG_OK;
+}
+
+// ---- normals and the depth-normal consistency loss (lg_normals.h, include/lightgaussian_normals.h) ----
+#define LG_NORMALS_MAX_ROWS (1 << 30)
+struct NamedPtr { const char* name; const void* p; };
+// null and alignment checks that name the argument; all16: every pointer is 16-byte aligned
+static int normals_ptrs(const char* who, std::initializer_list<NamedPtr> ptrs, bool* all16 = nullptr)
+{
+    char what[96];
+    uintptr_t all = 0;
+    for (const NamedPtr& a : ptrs) {
+        if (!a.p) { snprintf(what, sizeof(what), "null %s", a.name); return refuse(who, what); }
+        if ((uintptr_t)a.p & 3) { snprintf(what, sizeof(what), "%s must be 4-byte aligned", a.name); return refuse(who, what); }
+        all |= (uintptr_t)a.p;
+    }
+    if (all16) *all16 = (all & 15) == 0;
+    return LG_OK;
+}
+static int normals_image(const char* who, int32_t H, int32_t W, float tanfovx, float tanfovy)
+{
+    if (H < 1 || H > LG_NRM_MAX_DIM) return refuse(who, "H outside [1, 32768]");
+    if (W < 1 || W > LG_NRM_MAX_DIM) return refuse(who, "W outside [1, 32768]");
+    if (tanfovx != tanfovx) return refuse(who, "tanfovx is NaN");
+    if (tanfovy != tanfovy) return refuse(who, "tanfovy is NaN");
+    return LG_OK;
+}
+static unsigned normals_rows_wgs(int32_t N) { return (unsigned)((((int64_t)N + 3) / 4 + LG_NRM_THREADS - 1) / LG_NRM_THREADS); }
+
+extern "C" int lg_normal_rows(int32_t N, const float* xyz, const float* scaling, const float* rotation, const float* viewmatrix, float* rows,
+                              uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_normal_rows";
+    if (N < 0 || N >= LG_NORMALS_MAX_ROWS) return refuse(who, "N outside [0, 2^30)");
+    bool vec = false;
+    int rc = normals_ptrs(who, { { "xyz", xyz }, { "scaling", scaling }, { "rotation", rotation }, { "rows", rows } }, &vec);
+    if (rc == LG_OK) rc = normals_ptrs(who, { { "viewmatrix", viewmatrix } });
+    if (rc != LG_OK || N == 0) return rc;
+    hipStream_t stream = (hipStream_t)stream_p;
+    ProfScope ps(flags & LG_FLAG_PROFILE, "normal_rows", stream);
+    lg_normal_rows_kernel<<<normals_rows_wgs(N), LG_NRM_THREADS, 0, stream>>>(N, vec, xyz, scaling, rotation, viewmatrix, rows);
+    KLAUNCHED("lg_normal_rows_kernel");
+    return LG_OK;
+}
+
+extern "C" int lg_normal_rows_bwd(int32_t N, const float* xyz, const float* scaling, const float* rotation, const float* viewmatrix,
+                                  const float* dL_drows, float* dL_dxyz, float* dL_drotation, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_normal_rows_bwd";
+    if (N < 0 || N >= LG_NORMALS_MAX_ROWS) return refuse(who, "N outside [0, 2^30)");
+    bool vec = false;
+    int rc = normals_ptrs(who, { { "xyz", xyz }, { "scaling", scaling }, { "rotation", rotation }, { "dL_drows", dL_drows }, { "dL_dxyz", dL_dxyz },
+                                 { "dL_drotation", dL_drotation } }, &vec);
+    if (rc == LG_OK) rc = normals_ptrs(who, { { "viewmatrix", viewmatrix } });
+    if (rc != LG_OK || N == 0) return rc;
+    hipStream_t stream = (hipStream_t)stream_p;
+    ProfScope ps(flags & LG_FLAG_PROFILE, "normal_rows_bwd", stream);
+    lg_normal_rows_bwd_kernel<<<normals_rows_wgs(N), LG_NRM_THREADS, 0, stream>>>(N, vec, xyz, scaling, rotation, viewmatrix, dL_drows, dL_dxyz, dL_drotation);
+    KLAUNCHED("lg_normal_rows_bwd_kernel");
+    return LG_OK;
+}
+
+extern "C" int lg_depth_normals(int32_t H, int32_t W, const float* depth, float tanfovx, float tanfovy, float* normals, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_depth_normals";
+    int rc = normals_image(who, H, W, tanfovx, tanfovy);
+    if (rc == LG_OK) rc = normals_ptrs(who, { { "depth", depth }, { "normals", normals } });
+    if (rc != LG_OK) return rc;
+    hipStream_t stream = (hipStream_t)stream_p;
+    ProfScope ps(flags & LG_FLAG_PROFILE, "depth_normals", stream);
+    lg_normal_fwd<false><<<dim3(lg_nrm_strips(W, LG_NRM_FWD_COLS), lg_nrm_segs(H)), 64, 0, stream>>>(H, W, tanfovx, tanfovy, depth, nullptr, nullptr, nullptr,
+                                                                                                 normals, nullptr);
+    KLAUNCHED("lg_normal_fwd");
+    return LG_OK;
+}
+
+extern "C" int lg_depth_normals_bwd(int32_t H, int32_t W, const float* depth, float tanfovx, float tanfovy, const float* dL_dnormals,
+                                    float* dL_ddepth, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_depth_normals_bwd";
+    int rc = normals_image(who, H, W, tanfovx, tanfovy);
+    if (rc == LG_OK) rc = normals_ptrs(who, { { "depth", depth }, { "dL_dnormals", dL_dnormals }, { "dL_ddepth", dL_ddepth } });
+    if (rc != LG_OK) return rc;
+    hipStream_t stream = (hipStream_t)stream_p;
+    ProfScope ps(flags & LG_FLAG_PROFILE, "depth_normals_bwd", stream);
+    lg_normal_bwd<false><<<dim3(lg_nrm_strips(W, LG_NRM_BWD_COLS), lg_nrm_segs(H)), 64, 0, stream>>>(H, W, tanfovx, tanfovy, depth, dL_dnormals, nullptr, nullptr,
+                                                                                                 nullptr, 0.0f, nullptr, dL_ddepth);
+    KLAUNCHED("lg_normal_bwd");
+    return LG_OK;
+}
+
+extern "C" size_t lg_normal_loss_scratch_bytes(int32_t H, int32_t W)
+{
+    if (H < 1 || W < 1 || H > LG_NRM_MAX_DIM || W > LG_NRM_MAX_DIM) return 0;
+    return align_up((size_t)lg_nrm_strips(W, LG_NRM_FWD_COLS) * lg_nrm_segs(H) * sizeof(float));
+}
+
+extern "C" int lg_normal_loss(int32_t H, int32_t W, const float* normal_map, const float* depth, const float* alpha, const float* weight,
+                              float tanfovx, float tanfovy, float* loss, float* depth_normals, void* scratch, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_normal_loss";
+    int rc = normals_image(who, H, W, tanfovx, tanfovy);
+    if (rc == LG_OK) rc = normals_ptrs(who, { { "normal_map", normal_map }, { "depth", depth }, { "alpha", alpha }, { "loss", loss }, { "scratch", scratch } });
+    if (rc == LG_OK && weight) rc = normals_ptrs(who, { { "weight", weight } });
+    if (rc == LG_OK && depth_normals) rc = normals_ptrs(who, { { "depth_normals", depth_normals } });
+    if (rc != LG_OK) return rc;
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool prof = flags & LG_FLAG_PROFILE;
+    const dim3 grid(lg_nrm_strips(W, LG_NRM_FWD_COLS), lg_nrm_segs(H));
+    float* partials = (float*)scratch;
+    {
+        ProfScope ps(prof, "normal_loss", stream);
+        lg_normal_fwd<true><<<grid, 64, 0, stream>>>(H, W, tanfovx, tanfovy, depth, normal_map, alpha, weight, depth_normals, partials);
+        KLAUNCHED("lg_normal_fwd");
+    }
+    {
+        ProfScope ps(prof, "normal_loss_reduce", stream);
+        lg_normal_loss_finalize<<<1, 256, 0, stream>>>((int)(grid.x * grid.y), 1.0 / ((double)H * W), partials, loss);
+        KLAUNCHED("lg_normal_loss_finalize");
+    }
+    return LG_OK;
+}
+
+extern "C" int lg_normal_loss_bwd(int32_t H, int32_t W, const float* normal_map, const float* depth, const float* alpha, const float* weight,
+                                  float tanfovx, float tanfovy, const float* dL_dloss, float* dL_dnormal_map, float* dL_ddepth, uint32_t flags,
+                                  void* stream_p)
+{
+    const char* who = "lg_normal_loss_bwd";
+    int rc = normals_image(who, H, W, tanfovx, tanfovy);
+    if (rc == LG_OK) rc = normals_ptrs(who, { { "normal_map", normal_map }, { "depth", depth }, { "alpha", alpha }, { "dL_dloss", dL_dloss },
+                                              { "dL_dnormal_map", dL_dnormal_map }, { "dL_ddepth", dL_ddepth } });
+    if (rc == LG_OK && weight) rc = normals_ptrs(who, { { "weight", weight } });
+    if (rc != LG_OK) return rc;
+    hipStream_t stream = (hipStream_t)stream_p;
+    ProfScope ps(flags & LG_FLAG_PROFILE, "normal_loss_bwd", stream);
+    lg_normal_bwd<true><<<dim3(lg_nrm_strips(W, LG_NRM_BWD_COLS), lg_nrm_segs(H)), 64, 0, stream>>>(
+        H, W, tanfovx, tanfovy, depth, normal_map, alpha, weight, dL_dloss, (float)(1.0 / ((double)H * W)), dL_dnormal_map, dL_ddepth);
+    KLAUNCHED("lg_normal_bwd");
     return LG_OK;
 }
 

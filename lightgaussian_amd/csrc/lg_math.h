@@ -695,12 +695,22 @@ LG_HD void lg_backward_camera_terms(const float* vm, const float* pm, float px, 
     lg_backward_camera_terms_t<false>(vm, pm, px, py, pz, S, acc, W, H, tanfovx, tanfovy, d, out, 0.0f);
 }
 
+// dL/dR (row-major g) -> dL/dq through lg_quat_to_rot, q = (r, x, y, z) taken as free variables.  The ONE copy: lg_backward_cov3d and
+// lg_normal_row_bwd call it.
+LG_HD void lg_quat_rot_bwd(const float q[4], const float g[9], float drot[4])
+{
+    const float r = q[0], x = q[1], y = q[2], z = q[3];
+    drot[0] = 2.0f * (-z * g[1] + y * g[2] + z * g[3] - x * g[5] - y * g[6] + x * g[7]);
+    drot[1] = 2.0f * (y * g[1] + z * g[2] + y * g[3] - 2.0f * x * g[4] - r * g[5] + z * g[6] + r * g[7] - 2.0f * x * g[8]);
+    drot[2] = 2.0f * (-2.0f * y * g[0] + x * g[1] + r * g[2] + x * g[3] + z * g[5] - r * g[6] + z * g[7] - 2.0f * y * g[8]);
+    drot[3] = 2.0f * (-2.0f * z * g[0] - r * g[1] + x * g[2] + r * g[3] - 2.0f * z * g[4] + y * g[5] + x * g[6] + y * g[7]);
+}
+
 // dL/dSigma(packed) -> dL/dscale, dL/dquaternion.  Like the published implementation the
 // scale gradient carries no scale_modifier factor.
 LG_HD void lg_backward_cov3d(const float sc[3], float mod, const float q[4], const float dS[6], float dscale[3], float drot[4])
 {
     float sv[3] = { mod * sc[0], mod * sc[1], mod * sc[2] };
-    float r = q[0], x = q[1], y = q[2], z = q[3];
     float Rm[9];
     lg_quat_to_rot(q, Rm);
     float L[9];
@@ -712,10 +722,7 @@ LG_HD void lg_backward_cov3d(const float sc[3], float mod, const float q[4], con
     for (int j = 0; j < 3; j++) dscale[j] = dLm[j] * Rm[j] + dLm[3 + j] * Rm[3 + j] + dLm[6 + j] * Rm[6 + j];
     float g[9];
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) g[3 * i + j] = dLm[3 * i + j] * sv[j];
-    drot[0] = 2.0f * (-z * g[1] + y * g[2] + z * g[3] - x * g[5] - y * g[6] + x * g[7]);
-    drot[1] = 2.0f * (y * g[1] + z * g[2] + y * g[3] - 2.0f * x * g[4] - r * g[5] + z * g[6] + r * g[7] - 2.0f * x * g[8]);
-    drot[2] = 2.0f * (-2.0f * y * g[0] + x * g[1] + r * g[2] + x * g[3] + z * g[5] - r * g[6] + z * g[7] - 2.0f * y * g[8]);
-    drot[3] = 2.0f * (-2.0f * z * g[0] - r * g[1] + x * g[2] + r * g[3] - 2.0f * z * g[4] + y * g[5] + x * g[6] + y * g[7]);
+    lg_quat_rot_bwd(q, g, drot);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -976,3 +983,114 @@ LG_HD void lg_mcmc_relocate(float opacity_raw, const float scaling_raw[3], int c
     const double shift = log(o / D);
     for (int a = 0; a < 3; a++) new_scaling[a] = (float)((double)scaling_raw[a] + shift);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Normals (lg_normals.h).  Per Gaussian and view, float32, every product and sum rounded on its own, sums left
+// to right unless bracketed:
+//   q^ = q / max(|q|, 1e-12), |q| = sqrtf((q0^2 + q1^2) + (q2^2 + q3^2))       K1's F.normalize (lg_preprocess.h), now lg_quat_normalize
+//   R = lg_quat_to_rot(q^)     k = the first index of the smallest scaling     n_w = column k of R
+//   n_v[c] = (n_w[0] vm[c] + n_w[1] vm[4 + c]) + n_w[2] vm[8 + c]              p_v = lg_view_point(vm, xyz)
+//   s = -1 when (n_v[0] p_v[0] + n_v[1] p_v[1]) + n_v[2] p_v[2] > 0, else +1   (a NaN compares false: +1)
+//   row = (s n_v, p_v.z)
+// Backward, k and s constants:  d xyz[a] = g[3] vm[4 a + 2];  dL/dn_w[a] = s ((vm[4 a] g[0] + vm[4 a + 1] g[1]) + vm[4 a + 2] g[2]) sits in
+// column k of dL/dR, lg_quat_rot_bwd takes it to q^, and K9's statement of the normalisation, (d - q^ (q^ . d)) / |q|, to q.
+LG_HD float lg_quat_normalize(const float q_raw[4], float q[4])
+{
+    const float qn = fmaxf(sqrtf((q_raw[0] * q_raw[0] + q_raw[1] * q_raw[1]) + (q_raw[2] * q_raw[2] + q_raw[3] * q_raw[3])), 1e-12f);
+    q[0] = q_raw[0] / qn; q[1] = q_raw[1] / qn; q[2] = q_raw[2] / qn; q[3] = q_raw[3] / qn;
+    return qn;
+}
+LG_HD int lg_normal_axis(const float sc[3])
+{
+    int k = 0;
+    float m = sc[0];
+    if (sc[1] < m) { k = 1; m = sc[1]; }
+    if (sc[2] < m) k = 2;
+    return k;
+}
+struct LgNormalRow { float q[4], qn, nv[3], pv[3], s; int k; };
+LG_HD void lg_normal_view(const float* vm, const float xyz[3], const float sc[3], const float q_raw[4], LgNormalRow& o)
+{
+    o.qn = lg_quat_normalize(q_raw, o.q);
+    float R[9];
+    lg_quat_to_rot(o.q, R);
+    const int k = o.k = lg_normal_axis(sc);
+    const float n0 = k == 0 ? R[0] : (k == 1 ? R[1] : R[2]);
+    const float n1 = k == 0 ? R[3] : (k == 1 ? R[4] : R[5]);
+    const float n2 = k == 0 ? R[6] : (k == 1 ? R[7] : R[8]);
+    for (int c = 0; c < 3; c++) o.nv[c] = (n0 * vm[c] + n1 * vm[4 + c]) + n2 * vm[8 + c];
+    lg_view_point(vm, xyz[0], xyz[1], xyz[2], o.pv[0], o.pv[1], o.pv[2]);
+    o.s = ((o.nv[0] * o.pv[0] + o.nv[1] * o.pv[1]) + o.nv[2] * o.pv[2]) > 0.0f ? -1.0f : 1.0f;
+}
+LG_HD void lg_normal_row(const float* vm, const float xyz[3], const float sc[3], const float q_raw[4], float row[4])
+{
+    LgNormalRow o;
+    lg_normal_view(vm, xyz, sc, q_raw, o);
+    row[0] = o.s * o.nv[0]; row[1] = o.s * o.nv[1]; row[2] = o.s * o.nv[2]; row[3] = o.pv[2];
+}
+LG_HD void lg_normal_row_bwd(const float* vm, const float xyz[3], const float sc[3], const float q_raw[4], const float g[4], float dxyz[3], float drot[4])
+{
+    LgNormalRow o;
+    lg_normal_view(vm, xyz, sc, q_raw, o);
+    float G[9], d[4];
+    for (int a = 0; a < 3; a++) {
+        dxyz[a] = g[3] * vm[4 * a + 2];
+        const float dn = o.s * ((vm[4 * a] * g[0] + vm[4 * a + 1] * g[1]) + vm[4 * a + 2] * g[2]);
+        for (int j = 0; j < 3; j++) G[3 * a + j] = j == o.k ? dn : 0.0f;
+    }
+    lg_quat_rot_bwd(o.q, G, d);
+    const float qg = o.q[0] * d[0] + o.q[1] * d[1] + o.q[2] * d[2] + o.q[3] * d[3];
+    const float inv = 1.0f / o.qn;
+    for (int j = 0; j < 4; j++) drot[j] = (d[j] - o.q[j] * qg) * inv;
+}
+
+// Per pixel: the normal of the depth surface (2DGS's depth_to_normal).  The un-projected point of pixel (x, y) is depth (rx, ry, 1) with
+//   rx = ((2 x + 1) / W - 1) tanfovx     ry = ((2 y + 1) / H - 1) tanfovy             (lg_pixel_ray: the pixel centre of ndc2Pix)
+// and, with dc the depth of the pixel, du, dd, dl, dr the depths above (y - 1), below, left and right of the pixel and rxm / rxp, rym / ryp the rays of those columns / rows,
+//   a = P(x, y + 1) - P(x, y - 1) = (dd rx - du rx, dd ryp - du rym, dd - du)     b = P(x + 1, y) - P(x - 1, y) = (dr rxp - dl rxm, dr ry - dl ry, dr - dl)
+//   c = a x b = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0)     |c| = sqrtf((c0^2 + c1^2) + c2^2)     N_d = c / max(|c|, 1e-12)
+// A pixel whose c has a non-finite component, or whose own depth dc is not finite (c does not read it), is zero and passes no gradient
+// (ok = false); the caller zeroes the image border.
+#define LG_NORMAL_EPS 1e-12f
+LG_HD float lg_pixel_ray(int x, int W, float tanfov) { return ((float)(2 * x + 1) / (float)W - 1.0f) * tanfov; }
+struct LgDepthNormal { float a[3], b[3], n[3], len; bool ok; };
+LG_HD void lg_depth_normal(float dc, float du, float dd, float dl, float dr, float rx, float rxm, float rxp, float ry, float rym, float ryp, LgDepthNormal& o)
+{
+    o.a[0] = dd * rx - du * rx; o.a[1] = dd * ryp - du * rym; o.a[2] = dd - du;
+    o.b[0] = dr * rxp - dl * rxm; o.b[1] = dr * ry - dl * ry; o.b[2] = dr - dl;
+    const float c0 = o.a[1] * o.b[2] - o.a[2] * o.b[1], c1 = o.a[2] * o.b[0] - o.a[0] * o.b[2], c2 = o.a[0] * o.b[1] - o.a[1] * o.b[0];
+    o.ok = fabsf(dc) < INFINITY && fabsf(c0) < INFINITY && fabsf(c1) < INFINITY && fabsf(c2) < INFINITY;
+    o.len = sqrtf((c0 * c0 + c1 * c1) + c2 * c2);
+    const float m = fmaxf(o.len, LG_NORMAL_EPS);
+    o.n[0] = o.ok ? c0 / m : 0.0f; o.n[1] = o.ok ? c1 / m : 0.0f; o.n[2] = o.ok ? c2 / m : 0.0f;
+}
+// Backward of one pixel q: G = dL/dN_d(q) -> what q adds to dL/ddepth of its four neighbours.  dL/dc = (G - n (n . G)) / |c| (G / 1e-12 under
+// the clamp), dL/da = b x dL/dc, dL/db = dL/dc x a, and the neighbour's depth multiplies its own ray:
+//   up = -(ray(x, y - 1) . dL/da)   down = ray(x, y + 1) . dL/da   left = -(ray(x - 1, y) . dL/db)   right = ray(x + 1, y) . dL/db
+// lg_depth_grad is the GATHER of pixel p: the down tap of the pixel above it, the up tap of the one below, the right tap of its left
+// neighbour and the left tap of its right one, summed in that order.
+struct LgNormalTaps { float up, down, left, right; };
+LG_HD void lg_depth_normal_bwd(const LgDepthNormal& o, const float G[3], float rx, float rxm, float rxp, float ry, float rym, float ryp, LgNormalTaps& t)
+{
+    if (!o.ok) { t.up = t.down = t.left = t.right = 0.0f; return; }
+    const float m = fmaxf(o.len, LG_NORMAL_EPS);
+    float dc[3];
+    if (o.len > LG_NORMAL_EPS) {
+        const float ng = (o.n[0] * G[0] + o.n[1] * G[1]) + o.n[2] * G[2];
+        for (int k = 0; k < 3; k++) dc[k] = (G[k] - o.n[k] * ng) / m;
+    } else {
+        for (int k = 0; k < 3; k++) dc[k] = G[k] / m;
+    }
+    const float da0 = o.b[1] * dc[2] - o.b[2] * dc[1], da1 = o.b[2] * dc[0] - o.b[0] * dc[2], da2 = o.b[0] * dc[1] - o.b[1] * dc[0];
+    const float db0 = dc[1] * o.a[2] - dc[2] * o.a[1], db1 = dc[2] * o.a[0] - dc[0] * o.a[2], db2 = dc[0] * o.a[1] - dc[1] * o.a[0];
+    t.up = -((rx * da0 + rym * da1) + da2);
+    t.down = (rx * da0 + ryp * da1) + da2;
+    t.left = -((rxm * db0 + ry * db1) + db2);
+    t.right = (rxp * db0 + ry * db1) + db2;
+}
+LG_HD float lg_depth_grad(float down_of_above, float up_of_below, float right_of_left, float left_of_right)
+{
+    return ((down_of_above + up_of_below) + right_of_left) + left_of_right;
+}
+// The consistency loss at one pixel: term = 1 - w (N_r . N_d); with coef = -(scale w), scale = dL/dL / (H W): dL/dN_r = coef N_d and G = coef N_r.
+LG_HD float lg_normal_term(float w, const float nr[3], const float nd[3]) { return 1.0f - w * ((nr[0] * nd[0] + nr[1] * nd[1]) + nr[2] * nd[2]); }

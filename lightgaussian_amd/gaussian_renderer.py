@@ -316,3 +316,41 @@ def render_features(viewpoint_camera, pc, pipe, features, bg_features=None, scal
     if want_depth:
         pkg["depth"] = image / alpha.clamp_min(_DEPTH_EPS)
     return pkg
+
+
+def render_geometry(viewpoint_camera, pc, pipe, bg_color=None, *, options=None, geometry_grad=True):
+    """The geometry maps of one view from ONE forward: the four columns of normals.gaussian_normals -- the view-space normal of every
+    Gaussian (the axis of its smallest scale, facing the camera) and its view-space z -- blended with the view's weights in one
+    blend_features call.
+
+    Returns {"render" [3,H,W], "alpha" [H,W], "normal" [3,H,W] (blended, unnormalised: its length is about alpha), "depth" [H,W]
+    (= blended z / alpha.clamp_min(1e-6), the expected depth render_features("depth") gives), "radii", "visibility_filter",
+    "viewspace_points" (None without geometry_grad)}.  normal, depth and alpha are what normals.normal_consistency_loss takes.
+
+    geometry_grad=True (default): every map is differentiable with respect to the model -- the normals reach _rotation and, through
+    z, _xyz directly (lg_normal_rows_bwd), and everything reaches _xyz, _opacity, _scaling, _rotation through the blend
+    (lg_backward_features).  The same models are accepted and refused as by render_features(geometry_grad=True); filter_3D and
+    antialiasing apply through the same options.  pipe.compute_cov3D_python hands the renderer no scales and rotations: refused."""
+    from .features import blend_features
+    from .normals import gaussian_normals
+    options = _pipe_options(pipe, options)
+    if _camera_grad(options):
+        raise NotImplementedError("camera_grad is not implemented for render_geometry: use render() for the pose gradient")
+    if isinstance(pc, (CompressedGaussians, TrainableCompressed)):
+        if geometry_grad:
+            raise NotImplementedError("render_geometry(geometry_grad=True) needs the dense tensors: pass pc.to_dense() instead")
+        raise NotImplementedError("render_geometry needs the dense scales and rotations: pass pc.to_dense() instead")
+    if pipe.compute_cov3D_python:
+        raise NotImplementedError("render_geometry needs scales and rotations: compute_cov3D_python hands the renderer covariances only")
+    with contextlib.nullcontext() if geometry_grad else torch.no_grad():
+        means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp = _inputs(viewpoint_camera, pc, pipe, 1.0, None, options)
+        if bg_color is None:
+            bg_color = torch.zeros(3, dtype=torch.float32, device=means3D.device)
+        rows = gaussian_normals(means3D.contiguous(), scales.contiguous(), rotations.contiguous(), viewpoint_camera)
+    rs = _settings(viewpoint_camera, pc, pipe, bg_color, 1.0, False)
+    screenspace_points = _screenspace_points(pc) if geometry_grad else None
+    image, alpha, color, radii = blend_features(rs, rows, means3D=means3D, opacities=opacity, scales=scales, rotations=rotations,
+                                                cov3D_precomp=cov3D_precomp, shs=shs, colors_precomp=colors_precomp, options=options,
+                                                geometry_grad=geometry_grad, means2D=screenspace_points)
+    return {"render": color, "alpha": alpha, "normal": image[:3], "depth": image[3] / alpha.clamp_min(_DEPTH_EPS), "radii": radii,
+            "visibility_filter": radii > 0, "viewspace_points": screenspace_points}
