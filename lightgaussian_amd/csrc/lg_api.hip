@@ -31,6 +31,8 @@
 //                    (or activated) application to scales and opacity with its backward
 //   lg_normals.h     lg_normal_rows / lg_depth_normals / lg_normal_loss and their backwards: view-space normals of the Gaussians, normals of a
 //                    depth map, the fused depth-normal consistency loss (include/lightgaussian_normals.h; a wave per strip, register ring)
+//   lg_distortion.h  lg_distortion_fwd / _bwd: depth distortion and median depth over the lists a forward left, and their gradient into K7's
+//                    moment rows and a per-instance dm row (include/lightgaussian_distortion.h; lg_features.h's walks)
 //
 // Pipeline of one view:
 //   K1 project + EWA + SH->RGB + exact footprint culling  ->  K2 scan of instance counts, blocking read of R
@@ -66,6 +68,7 @@
 #include "lg_absgrad.h"
 #include "lg_filter3d.h"
 #include "lg_normals.h"
+#include "lg_distortion.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -570,7 +573,9 @@ struct GradOut { float *means2D, *means3D, *shs, *colors, *opacity, *scales, *ro
 // what lg_backward_features adds to a backward: a loss on the feature image and / or on alpha (lg_features_bwd_geom, lg_features.h)
 struct FeatGrad { const float* features; int C; const float* bg; const float* dL_dout; const float* dL_dalpha; };
 // the rest of a backward call: K9's chunks and their callback (lg_backward_chunked), lg_backward_features' losses, lg_backward_abs' output
-struct BackwardOpts { int chunks; lg_chunk_fn on_chunk; void* user; const FeatGrad* fg = nullptr; float* means2D_abs = nullptr; };
+// what lg_backward_distortion adds: a loss on the distortion and / or the median map (lg_distortion_bwd, lg_distortion.h); dm_rows [R]
+struct DistGrad { const float* m; int m_stride; const void* state; const float* dL_dD; const float* dL_dmed; float* dm_rows; };
+struct BackwardOpts { int chunks; lg_chunk_fn on_chunk; void* user; const FeatGrad* fg = nullptr; float* means2D_abs = nullptr; const DistGrad* dg = nullptr; };
 
 // K9 (lg_preprocess_bwd) over the moment rows [R][12] a blend backward left: sums every Gaussian's rows and chains them to every input.
 // Shared by lg_backward / lg_backward_chunked (rows from K7) and lg_backward_features (rows from K7 and / or lg_features_bwd_geom).
@@ -600,6 +605,8 @@ static void preprocess_bwd_launch(const lg_view* v, const lg_gaussians* g, const
 }
 
 static LgFeatView features_view(const ViewState& s, int32_t N, int64_t R);
+// the state of lg_blend_distortion: float4 (A, P1, P2, c) [H W] | uint32 med_pos [H W]
+static size_t distortion_state_head(int W, int H) { return align_up((size_t)W * (size_t)H * sizeof(float4)); }
 // channels of the next walk when rem are left: as many as the registers take -- one walk up to 32 channels, two up to 64
 static int features_channel_group(int rem) { return rem <= 4 ? 4 : rem <= 16 ? 16 : 32; }
 using FeaturesBwdGeomKernel = decltype(&lg_features_bwd_geom<4, true, true>);
@@ -622,7 +629,7 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
     const bool rgb_only = g->shs && !d.shs && d.colors;
     if (g->shs_rest && !d.shs_rest && !rgb_only) return fail(LG_ERR_INVALID_ARGUMENT, "missing gradient output for shs_rest");
     if (rgb_only && d.shs_rest) return fail(LG_ERR_INVALID_ARGUMENT, "dL_dshs_rest without dL_dshs");
-    if (!radii || !geom_p || !bin_p || !img_p || (!dL_dcolor && !o.fg) || !d.means2D || !d.means3D || !d.opacity || !scratch)
+    if (!radii || !geom_p || !bin_p || !img_p || (!dL_dcolor && !o.fg && !o.dg) || !d.means2D || !d.means3D || !d.opacity || !scratch)
         return fail(LG_ERR_INVALID_ARGUMENT, "missing buffer");
     if ((g->shs && !d.shs && !rgb_only) || (g->colors_precomp && !d.colors) || (g->scales && (!d.scales || !d.rotations)) ||
         (g->cov3D_precomp && !d.cov3D))
@@ -673,6 +680,20 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
                 accum = true;
             }
         }
+    }
+    if (o.dg && R > 0) {
+        // lg_backward_distortion: the moments of the distortion / median loss join the rows; the walk writes whole rows when it is the first
+        const bool exact = !(v->flags & LG_FLAG_FAST_EXP), accum = dL_dcolor != nullptr || o.fg != nullptr;
+        const LgFeatView f = features_view(s, N, R);
+        const float4* st = (const float4*)o.dg->state;
+        const uint32_t* st_pos = (const uint32_t*)((const char*)o.dg->state + distortion_state_head(W, H));
+        {
+            ProfScope ps(prof, "distortion_bwd", stream);
+            (exact ? (accum ? lg_distortion_bwd<true, true> : lg_distortion_bwd<true, false>) : (accum ? lg_distortion_bwd<false, true> : lg_distortion_bwd<false, false>))
+                <<<q.ntiles_pad, 256, 0, stream>>>(f, (uint32_t)S, bin.meta, geo.tinfo, o.dg->m, o.dg->m_stride, st, st_pos, o.dg->dL_dD, o.dg->dL_dmed,
+                                                   img.final_T, img.n_contrib, rows, o.dg->dm_rows);
+        }
+        KCHECK("lg_distortion_bwd");
     }
     preprocess_bwd_launch(v, g, radii, s, rows, d, rgb_only, stream, o);
     KCHECK("lg_preprocess_bwd");
@@ -1907,6 +1928,98 @@ extern "C" int lg_backward_features(const lg_view* v, const lg_gaussians* g, con
     rc = backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, d, scratch, stream_p, { 1, nullptr, nullptr, &fg, nullptr });
     if (rc != LG_OK || g->N == 0 || !dL_dfeatures) return rc;
     return features_backward_run(v, g->N, geom_p, bin_p, R, dL_dout, C, dL_dfeatures, (char*)scratch + lg_backward_scratch_bytes(g->N, R), stream_p);
+}
+
+// ---- depth distortion and median depth (lg_distortion.h, include/lightgaussian_distortion.h) ----
+extern "C" size_t lg_distortion_state_bytes(int32_t W, int32_t H)
+{
+    if (W < 1 || H < 1) return 0;
+    return distortion_state_head(W, H) + align_up((size_t)W * (size_t)H * sizeof(uint32_t));
+}
+
+static int distortion_args(const char* who, const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, int32_t C, const float* m,
+                           int32_t m_stride, const void* state)
+{
+    if (C < 0 || C > LG_FEATURES_MAX) return refuse(who, "C must be 0 .. LG_FEATURES_MAX (64) channels");
+    int rc = features_args(who, v, N, geom_p, bin_p, R, C > 0 ? C : 1);
+    if (rc != LG_OK) return rc;
+    if (m_stride < 1) return refuse(who, "m_stride must be at least 1");
+    if (N > 0 && !m) return refuse(who, "missing m");
+    if (!state) return refuse(who, "missing state buffer");
+    return LG_OK;
+}
+
+extern "C" int lg_blend_distortion(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const float* m, int32_t m_stride,
+                                   float* distortion, float* median, void* state, void* stream_p)
+{
+    int rc = distortion_args("lg_blend_distortion", v, N, geom_p, bin_p, R, 0, m, m_stride, state);
+    if (rc != LG_OK) return rc;
+    if (!distortion) return refuse("lg_blend_distortion", "missing distortion map");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, exact = !(v->flags & LG_FLAG_FAST_EXP);
+    const ViewState s = view_state(v, N, geom_p, nullptr, bin_p, R);
+    const ViewGeom& q = s.q;
+    const LgFeatView f = features_view(s, N, R);
+    {
+        ProfScope ps(prof, "distortion_fwd", stream);
+        (exact ? lg_distortion_fwd<true> : lg_distortion_fwd<false>)<<<q.ntiles_pad, 256, 0, stream>>>(
+            f, m, m_stride, distortion, median, (float4*)state, (uint32_t*)((char*)state + distortion_state_head(q.W, q.H)));
+    }
+    KCHECK("lg_distortion_fwd");
+    return LG_OK;
+}
+
+// scratch = the moment rows [R][12] | the partial rows of lg_blend_features_backward (C > 0) | the dm rows [R]
+static size_t distortion_scratch_features(int32_t N, int64_t R, int32_t C) { return C > 0 ? lg_features_scratch_bytes(N, R, C) : 0; }
+extern "C" size_t lg_backward_distortion_scratch_bytes(int32_t N, int64_t num_rendered, int32_t C)
+{
+    if (C < 0 || C > LG_FEATURES_MAX || num_rendered < 0) return 0;
+    return lg_backward_scratch_bytes(N, num_rendered) + distortion_scratch_features(N, num_rendered, C) +
+           align_up((size_t)(num_rendered > 0 ? num_rendered : 1) * sizeof(float));
+}
+
+extern "C" int lg_backward_distortion(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const void* geom_p, const void* bin_p,
+                                      const void* img_p, int64_t R, const float* dL_dcolor, const float* features, int32_t C,
+                                      const float* bg_features, const float* dL_dout, const float* dL_dalpha, float* dL_dmeans2D,
+                                      float* dL_dmeans3D, float* dL_dshs, float* dL_dcolors, float* dL_dopacity, float* dL_dscales,
+                                      float* dL_drotations, float* dL_dcov3D, float* dL_dshs_rest, float* dL_dfeatures, const float* m,
+                                      int32_t m_stride, const void* state, const float* dL_ddistortion, const float* dL_dmedian, float* dL_dm,
+                                      void* scratch, void* stream_p)
+{
+    const char* who = "lg_backward_distortion";
+    if (!g) return refuse(who, "null gaussians");
+    int rc = distortion_args(who, v, g->N, geom_p, bin_p, R, C, m, m_stride, state);
+    if (rc != LG_OK) return rc;
+    const int N = g->N;
+    if (N > 0 && !features && (dL_dout || dL_dfeatures)) return refuse(who, "missing features");
+    if (N > 0 && dL_dfeatures && !dL_dout) return refuse(who, "dL_dfeatures without dL_dout");
+    if (C == 0 && dL_dout) return refuse(who, "dL_dout without channels (C is 0)");
+    if (N > 0 && !dL_dm) return refuse(who, "missing dL_dm");
+    if (N == 0) return LG_OK;       // nothing to write
+    if (!scratch) return refuse(who, "missing scratch buffer");
+    char* feat_scratch = (char*)scratch + lg_backward_scratch_bytes(N, R);
+    float* dm_rows = (float*)(feat_scratch + distortion_scratch_features(N, R, C));
+    const FeatGrad fg = { features, C, bg_features, dL_dout, dL_dalpha };
+    const DistGrad dg = { m, m_stride, state, dL_ddistortion, dL_dmedian, dm_rows };
+    const GradOut d = { dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest };
+    rc = backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, d, scratch, stream_p,
+                       { 1, nullptr, nullptr, (dL_dout || dL_dalpha) ? &fg : nullptr, nullptr, &dg });
+    if (rc != LG_OK) return rc;
+    if (dL_dfeatures) {
+        rc = features_backward_run(v, N, geom_p, bin_p, R, dL_dout, C, dL_dfeatures, feat_scratch, stream_p);
+        if (rc != LG_OK) return rc;
+    }
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE;
+    const ViewState s = view_state(v, N, geom_p, nullptr, bin_p, R);
+    const LgFeatView f = features_view(s, N, R);
+    // (a segment length other than the forward's: lg_distortion_bwd wrote zero dm rows)
+    {
+        ProfScope ps(prof, "distortion_gather", stream);
+        lg_features_gather<<<(unsigned)(((size_t)N + 255) / 256), 256, 0, stream>>>(N, 1, 0, 1, f.live, f.cap, s.geo.touched, s.geo.offsets, s.geo.counters, dm_rows, dL_dm);
+    }
+    KCHECK("lg_features_gather");
+    return LG_OK;
 }
 
 // diagnostics: Gaussian id of the last contributor of every pixel (0xFFFFFFFF: none) from the state a forward saved -- the

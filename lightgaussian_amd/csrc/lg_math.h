@@ -1094,3 +1094,51 @@ LG_HD float lg_depth_grad(float down_of_above, float up_of_below, float right_of
 }
 // The consistency loss at one pixel: term = 1 - w (N_r . N_d); with coef = -(scale w), scale = dL/dL / (H W): dL/dN_r = coef N_d and G = coef N_r.
 LG_HD float lg_normal_term(float w, const float nr[3], const float nd[3]) { return 1.0f - w * ((nr[0] * nd[0] + nr[1] * nd[1]) + nr[2] * nd[2]); }
+
+// ---------------------------------------------------------------------------------------------
+// Depth distortion and median depth over a pixel's contributors (lg_distortion.h).  With the blending weights
+// w_i = alpha_i T_i (lg_feature_step) and a per-Gaussian scalar m_i,
+//   D = sum_{i<j} w_i w_j (m_i - m_j)^2,      median = the m of the entry that carries T across one half (2DGS).
+// D is invariant under a shift of m, and A M2 - M1^2 on the raw m cancels catastrophically for a thin surface far from the camera, so the
+// sums run about the pixel's FIRST contributor: c = its m, u = m - c.  State per pixel, all zero at the start.
+struct LgDistortion { float A, P1, P2, D, c, med; uint32_t med_pos; };
+// One contributing (pixel, entry) pair in list order: w the weight lg_feature_step returned, Tin the T before that step, pos the entry's
+// 1-based position in the tile's list.  The first contributor is the one that finds med_pos == 0 (its Tin is 1 > 0.5, so it sets
+// med_pos).  Order of the float operations, one rounding each (no contraction):
+//   u = m - c;   uu = u u;   t = (uu A + P2) - (2 u) P1;   D = D + w t;   A = A + w;   P1 = P1 + w u;   P2 = P2 + w uu
+// The median rule: the last entry whose incoming T is above 0.5 -- the entry that takes T to 0.5 or below, or the last contributor
+// when T never gets there.  A pixel without contributors keeps D = 0, med = 0, med_pos = 0.
+LG_HD void lg_distortion_step(float w, float Tin, float m, uint32_t pos, LgDistortion& s)
+{
+    if (s.med_pos == 0u) s.c = m;
+    const float u = m - s.c;
+    const float uu = u * u;
+    const float two_u = 2.0f * u;
+    const float t = (uu * s.A + s.P2) - two_u * s.P1;
+    s.D = s.D + w * t;
+    s.A = s.A + w;
+    s.P1 = s.P1 + w * u;
+    s.P2 = s.P2 + w * uu;
+    if (Tin > 0.5f) { s.med = m; s.med_pos = pos; }
+}
+// One contributing pair of the BACK-TO-FRONT replay (lg_distortion_bwd): s holds the pixel's FINAL A, P1, P2, c and med_pos, gD = dL/dD
+// and gM = dL/dmedian of the pixel.  dD/dw_k = u_k^2 A - 2 u_k P1 + P2 is the entry's "feature" q, chained through alpha and T by
+// lg_feature_bwd_step unchanged (no background term); dD/dm_k = 2 w_k (u_k A - P1); the median passes its gradient to the m of the
+// selected entry only (the selection is piecewise constant).  Order:
+//   u = m - c;   q = gD (((u u) A - (2 u) P1) + P2);   [lg_feature_bwd_step -> mom[0..5], w]
+//   dm = ((2 gD) w) (u A - P1) + (pos == med_pos ? gM : 0)
+// Returns false (mom, dm, T, S untouched) when the entry does not contribute.
+template <bool EXACT>
+LG_HD bool lg_distortion_bwd_step(bool live, float power, float G, float alpha, float dx, float dy, float m, uint32_t pos, const LgDistortion& s,
+                                  float gD, float gM, float& T, float& S, float* mom, float& dm)
+{
+    const float u = m - s.c;
+    const float uu = u * u;
+    const float two_u = 2.0f * u;
+    const float q = gD * ((uu * s.A - two_u * s.P1) + s.P2);
+    float w = 0.0f;
+    if (!lg_feature_bwd_step<EXACT>(live, power, G, alpha, dx, dy, q, 0.0f, T, S, mom, w)) return false;
+    const float gw = (2.0f * gD) * w;
+    dm = gw * (u * s.A - s.P1) + (pos == s.med_pos ? gM : 0.0f);
+    return true;
+}

@@ -318,7 +318,7 @@ def render_features(viewpoint_camera, pc, pipe, features, bg_features=None, scal
     return pkg
 
 
-def render_geometry(viewpoint_camera, pc, pipe, bg_color=None, *, options=None, geometry_grad=True):
+def render_geometry(viewpoint_camera, pc, pipe, bg_color=None, *, options=None, geometry_grad=True, distortion=False):
     """The geometry maps of one view from ONE forward: the four columns of normals.gaussian_normals -- the view-space normal of every
     Gaussian (the axis of its smallest scale, facing the camera) and its view-space z -- blended with the view's weights in one
     blend_features call.
@@ -330,7 +330,12 @@ def render_geometry(viewpoint_camera, pc, pipe, bg_color=None, *, options=None, 
     geometry_grad=True (default): every map is differentiable with respect to the model -- the normals reach _rotation and, through
     z, _xyz directly (lg_normal_rows_bwd), and everything reaches _xyz, _opacity, _scaling, _rotation through the blend
     (lg_backward_features).  The same models are accepted and refused as by render_features(geometry_grad=True); filter_3D and
-    antialiasing apply through the same options.  pipe.compute_cov3D_python hands the renderer no scales and rotations: refused."""
+    antialiasing apply through the same options.  pipe.compute_cov3D_python hands the renderer no scales and rotations: refused.
+
+    distortion=True: the result gains "distortion" [H,W], the depth distortion sum_{i<j} w_i w_j (z_i - z_j)^2 over the view-space z (column
+    3 of the rows), and "median_depth" [H,W], the z of the Gaussian that carries the transmittance across one half
+    (lightgaussian_amd.distortion.blend_geometry: the same forward, one more walk of the tile lists; with geometry_grad=True both are
+    differentiable and the one backward, lg_backward_distortion, serves every map).  False is the path above, unchanged."""
     from .features import blend_features
     from .normals import gaussian_normals
     options = _pipe_options(pipe, options)
@@ -349,8 +354,17 @@ def render_geometry(viewpoint_camera, pc, pipe, bg_color=None, *, options=None, 
         rows = gaussian_normals(means3D.contiguous(), scales.contiguous(), rotations.contiguous(), viewpoint_camera)
     rs = _settings(viewpoint_camera, pc, pipe, bg_color, 1.0, False)
     screenspace_points = _screenspace_points(pc) if geometry_grad else None
-    image, alpha, color, radii = blend_features(rs, rows, means3D=means3D, opacities=opacity, scales=scales, rotations=rotations,
-                                                cov3D_precomp=cov3D_precomp, shs=shs, colors_precomp=colors_precomp, options=options,
-                                                geometry_grad=geometry_grad, means2D=screenspace_points)
+    extra = {}
+    if distortion:
+        from .distortion import blend_geometry
+        with contextlib.nullcontext() if geometry_grad else torch.no_grad():
+            image, alpha, color, radii, dist, median = blend_geometry(rs, rows, m_column=3, means3D=means3D, opacities=opacity, scales=scales,
+                                                                      rotations=rotations, cov3D_precomp=cov3D_precomp, shs=shs,
+                                                                      colors_precomp=colors_precomp, options=options, means2D=screenspace_points)
+        extra = {"distortion": dist, "median_depth": median}
+    else:
+        image, alpha, color, radii = blend_features(rs, rows, means3D=means3D, opacities=opacity, scales=scales, rotations=rotations,
+                                                    cov3D_precomp=cov3D_precomp, shs=shs, colors_precomp=colors_precomp, options=options,
+                                                    geometry_grad=geometry_grad, means2D=screenspace_points)
     return {"render": color, "alpha": alpha, "normal": image[:3], "depth": image[3] / alpha.clamp_min(_DEPTH_EPS), "radii": radii,
-            "visibility_filter": radii > 0, "viewspace_points": screenspace_points}
+            "visibility_filter": radii > 0, "viewspace_points": screenspace_points, **extra}
