@@ -265,6 +265,7 @@ static decltype(&lg_adam_kernel<false>) adam_kernel(bool decoupled) { return LG_
 static decltype(&lg_adam_rows_kernel<false>) adam_rows_kernel(bool decoupled) { return LG_BY_FLAG(lg_adam_rows_kernel, decoupled); }
 static decltype(&lg_filter3d_apply_kernel<false>) filter3d_apply_kernel(bool raw) { return LG_BY_FLAG(lg_filter3d_apply_kernel, raw); }
 static decltype(&lg_filter3d_apply_bwd_kernel<false>) filter3d_apply_bwd_kernel(bool raw) { return LG_BY_FLAG(lg_filter3d_apply_bwd_kernel, raw); }
+static decltype(&lg_distortion_fwd<false>) distortion_fwd_kernel(bool exact) { return LG_BY_FLAG(lg_distortion_fwd, exact); }
 #undef LG_BY_FLAG
 
 // Arguments of the capacity-bounded forward (lg_forward_bounded); NULL = exact forward with its one read-back.
@@ -604,11 +605,64 @@ static void preprocess_bwd_launch(const lg_view* v, const lg_gaussians* g, const
     }
 }
 
-static LgFeatView features_view(const ViewState& s, int32_t N, int64_t R);
+// ---- the walks over the lists of a forward (lg_features.h, lg_distortion.h): what their entry points (below) and backward_impl share ----
+static int features_args(const char* who, const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, int32_t C)
+{
+    const char* what = nullptr;
+    const ViewFault vf = v ? check_view(v, N) : VIEW_OK;
+    if (!v) what = "null view";
+    else if (C < 1 || C > LG_FEATURES_MAX) what = "C must be 1 .. LG_FEATURES_MAX (64) channels";
+    else if (N < 0 || N >= (1 << LG_ID_BITS)) what = "N out of range";
+    else if (R < 0 || R >= (1ll << 30)) what = "num_rendered out of range";
+    else if (vf == VIEW_BAD_SIZE) what = "bad image size";
+    else if (vf == VIEW_BAD_SEGMENT) what = "lg_view.segment_length must be 0 or a multiple of 64";
+    else if (!geom_p) what = "missing geom buffer";
+    else if (N > 0 && R > 0 && !bin_p) what = "missing binning buffer";
+    else if (vf == VIEW_TOO_LARGE) what = "image too large";
+    return what ? refuse(who, what) : LG_OK;
+}
+// what a loss on the feature image needs (lg_backward_features, lg_backward_distortion)
+static int features_grad_args(const char* who, int32_t N, const float* features, const float* dL_dout, const float* dL_dfeatures)
+{
+    if (N > 0 && !features && (dL_dout || dL_dfeatures)) return refuse(who, "missing features");
+    if (N > 0 && dL_dfeatures && !dL_dout) return refuse(who, "dL_dfeatures without dL_dout");
+    return LG_OK;
+}
+static LgFeatView features_view(const ViewState& s, int32_t N, int64_t R)
+{
+    LgFeatView f; const ViewGeom& q = s.q; const GeomView& geo = s.geo;
+    f.W = q.W; f.H = q.H; f.gx = q.gx; f.ntiles = q.ntiles; f.N = N;
+    f.live = (N > 0 && R > 0 && s.bin.ranges) ? 1 : 0;      // (ranges is the head of the binning buffer: NULL without one)
+    f.cap = (uint32_t)R; f.gid_mask = q.gid_mask;
+    f.rec = geo.rec; f.counters = geo.counters;
+    f.ranges = f.live ? s.bin.ranges : nullptr; f.entries = f.live ? s.bin.entries : nullptr;
+    return f;
+}
+// what a call that launches walks sets out with, taken apart by name where it is used (KCHECK reads `debug` and `stream`)
+struct WalkCall { hipStream_t stream; bool debug, prof, exact; ViewState s; LgFeatView f; };
+static WalkCall walk_call(const lg_view* v, int32_t N, const void* geom_p, const void* img_p, const void* bin_p, int64_t R, void* stream_p)
+{
+    const ViewState s = view_state(v, N, geom_p, img_p, bin_p, R);
+    return { (hipStream_t)stream_p, bool(v->flags & LG_FLAG_DEBUG), bool(v->flags & LG_FLAG_PROFILE), !(v->flags & LG_FLAG_FAST_EXP), s, features_view(s, N, R) };
+}
 // the state of lg_blend_distortion: float4 (A, P1, P2, c) [H W] | uint32 med_pos [H W]
 static size_t distortion_state_head(int W, int H) { return align_up((size_t)W * (size_t)H * sizeof(float4)); }
 // channels of the next walk when rem are left: as many as the registers take -- one walk up to 32 channels, two up to 64
 static int features_channel_group(int rem) { return rem <= 4 ? 4 : rem <= 16 ? 16 : 32; }
+using FeaturesFwdKernel = decltype(&lg_features_fwd<4, true>);
+static FeaturesFwdKernel features_fwd_kernel(int cg, bool exact)
+{
+    static const FeaturesFwdKernel k[3][2] = { { lg_features_fwd<4, false>, lg_features_fwd<4, true> }, { lg_features_fwd<16, false>, lg_features_fwd<16, true> },
+                                               { lg_features_fwd<32, false>, lg_features_fwd<32, true> } };
+    return k[cg == 4 ? 0 : cg == 16 ? 1 : 2][exact];
+}
+using FeaturesBwdKernel = decltype(&lg_features_bwd<4, true>);
+static FeaturesBwdKernel features_bwd_kernel(int nv, bool exact)
+{
+    static const FeaturesBwdKernel k[3][2] = { { lg_features_bwd<4, false>, lg_features_bwd<4, true> }, { lg_features_bwd<8, false>, lg_features_bwd<8, true> },
+                                               { lg_features_bwd<16, false>, lg_features_bwd<16, true> } };
+    return k[nv == 4 ? 0 : nv == 8 ? 1 : 2][exact];
+}
 using FeaturesBwdGeomKernel = decltype(&lg_features_bwd_geom<4, true, true>);
 static FeaturesBwdGeomKernel features_bwd_geom_kernel(int cg, bool exact, bool accum)
 {
@@ -616,6 +670,12 @@ static FeaturesBwdGeomKernel features_bwd_geom_kernel(int cg, bool exact, bool a
     static const FeaturesBwdGeomKernel k[3][2][2] = { LG_FBG(4), LG_FBG(16), LG_FBG(32) };
 #undef LG_FBG
     return k[cg == 4 ? 0 : cg == 16 ? 1 : 2][exact][accum];
+}
+using DistortionBwdKernel = decltype(&lg_distortion_bwd<true, true>);
+static DistortionBwdKernel distortion_bwd_kernel(bool exact, bool accum)
+{
+    static const DistortionBwdKernel k[2][2] = { { lg_distortion_bwd<false, false>, lg_distortion_bwd<false, true> }, { lg_distortion_bwd<true, false>, lg_distortion_bwd<true, true> } };
+    return k[exact][accum];
 }
 
 static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const void* geom_p, const void* bin_p,
@@ -634,11 +694,9 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
     if ((g->shs && !d.shs && !rgb_only) || (g->colors_precomp && !d.colors) || (g->scales && (!d.scales || !d.rotations)) ||
         (g->cov3D_precomp && !d.cov3D))
         return fail(LG_ERR_INVALID_ARGUMENT, "missing gradient output for a provided input");
-    hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE;
     const int N = g->N;
     // S must be the forward's (same lg_view); the kernels compare it with meta[2] and refuse otherwise
-    const ViewState s = view_state(v, N, geom_p, img_p, bin_p, R);
+    const auto [stream, debug, prof, exact, s, f] = walk_call(v, N, geom_p, img_p, bin_p, R, stream_p);
     const ViewGeom& q = s.q; const GeomView& geo = s.geo; const ImgView& img = s.img; const BinView& bin = s.bin;
     const int W = q.W, H = q.H, S = q.S;
     float* rows = (float*)scratch; // [R][12] gradient rows, every row written by lg_blend_bwd
@@ -647,8 +705,8 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
     // buffer by the forward: one extra workgroup of lg_blend_fwd)
     if (R > 0 && dL_dcolor) {
         ProfScope ps(prof, "blend_bwd", stream);
-        blend_bwd_kernel(!(v->flags & LG_FLAG_FAST_EXP), o.means2D_abs != nullptr)<<<max_items, 64, 0, stream>>>(W, H, q.gx, S, bin.work, bin.meta, bin.ranges, bin.entries, q.gid_mask, geo.tinfo,
-                                                                                       geo.rec, v->bg, img.final_T, img.n_contrib, dL_dcolor, bin.ckpt, rows);
+        blend_bwd_kernel(exact, o.means2D_abs != nullptr)<<<max_items, 64, 0, stream>>>(
+            W, H, q.gx, S, bin.work, bin.meta, bin.ranges, bin.entries, q.gid_mask, geo.tinfo, geo.rec, v->bg, img.final_T, img.n_contrib, dL_dcolor, bin.ckpt, rows);
     }
     KCHECK("lg_blend_bwd");
     if (o.means2D_abs) {
@@ -664,8 +722,6 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
     if (o.fg && R > 0) {
         // lg_backward_features: the moments of the feature / alpha loss join K7's in the same rows (lg_features.h), CG channels per walk;
         // the first walk writes whole rows, zeros included, when K7 did not run -- also when there is no image gradient at all
-        const bool exact = !(v->flags & LG_FLAG_FAST_EXP);
-        const LgFeatView f = features_view(s, N, R);
         if (o.fg->dL_dout || o.fg->dL_dalpha || !dL_dcolor) {
             const int nch = o.fg->dL_dout ? o.fg->C : 1;     // without dL_dout one walk: dL_dalpha's, or the zero rows
             bool accum = dL_dcolor != nullptr;
@@ -683,15 +739,13 @@ static int backward_impl(const lg_view* v, const lg_gaussians* g, const int32_t*
     }
     if (o.dg && R > 0) {
         // lg_backward_distortion: the moments of the distortion / median loss join the rows; the walk writes whole rows when it is the first
-        const bool exact = !(v->flags & LG_FLAG_FAST_EXP), accum = dL_dcolor != nullptr || o.fg != nullptr;
-        const LgFeatView f = features_view(s, N, R);
+        const bool accum = dL_dcolor != nullptr || o.fg != nullptr;
         const float4* st = (const float4*)o.dg->state;
         const uint32_t* st_pos = (const uint32_t*)((const char*)o.dg->state + distortion_state_head(W, H));
         {
             ProfScope ps(prof, "distortion_bwd", stream);
-            (exact ? (accum ? lg_distortion_bwd<true, true> : lg_distortion_bwd<true, false>) : (accum ? lg_distortion_bwd<false, true> : lg_distortion_bwd<false, false>))
-                <<<q.ntiles_pad, 256, 0, stream>>>(f, (uint32_t)S, bin.meta, geo.tinfo, o.dg->m, o.dg->m_stride, st, st_pos, o.dg->dL_dD, o.dg->dL_dmed,
-                                                   img.final_T, img.n_contrib, rows, o.dg->dm_rows);
+            distortion_bwd_kernel(exact, accum)<<<q.ntiles_pad, 256, 0, stream>>>(
+                f, (uint32_t)S, bin.meta, geo.tinfo, o.dg->m, o.dg->m_stride, st, st_pos, o.dg->dL_dD, o.dg->dL_dmed, img.final_T, img.n_contrib, rows, o.dg->dm_rows);
         }
         KCHECK("lg_distortion_bwd");
     }
@@ -1788,47 +1842,6 @@ extern "C" int lg_loss_backward(int32_t C, int32_t H, int32_t W, const float* im
 
 // ------------------------------------------------------------------------------------------------
 // feature blending over the lists of a forward (lg_features.h)
-static int features_args(const char* who, const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, int32_t C)
-{
-    const char* what = nullptr;
-    const ViewFault vf = v ? check_view(v, N) : VIEW_OK;
-    if (!v) what = "null view";
-    else if (C < 1 || C > LG_FEATURES_MAX) what = "C must be 1 .. LG_FEATURES_MAX (64) channels";
-    else if (N < 0 || N >= (1 << LG_ID_BITS)) what = "N out of range";
-    else if (R < 0 || R >= (1ll << 30)) what = "num_rendered out of range";
-    else if (vf == VIEW_BAD_SIZE) what = "bad image size";
-    else if (vf == VIEW_BAD_SEGMENT) what = "lg_view.segment_length must be 0 or a multiple of 64";
-    else if (!geom_p) what = "missing geom buffer";
-    else if (N > 0 && R > 0 && !bin_p) what = "missing binning buffer";
-    else if (vf == VIEW_TOO_LARGE) what = "image too large";
-    return what ? refuse(who, what) : LG_OK;
-}
-static LgFeatView features_view(const ViewState& s, int32_t N, int64_t R)
-{
-    LgFeatView f;
-    const ViewGeom& q = s.q; const GeomView& geo = s.geo;
-    f.W = q.W; f.H = q.H; f.gx = q.gx; f.ntiles = q.ntiles; f.N = N;
-    f.live = (N > 0 && R > 0 && s.bin.ranges) ? 1 : 0;      // (ranges is the head of the binning buffer: NULL without one)
-    f.cap = (uint32_t)R; f.gid_mask = q.gid_mask;
-    f.rec = geo.rec; f.counters = geo.counters;
-    f.ranges = f.live ? s.bin.ranges : nullptr; f.entries = f.live ? s.bin.entries : nullptr;
-    return f;
-}
-using FeaturesFwdKernel = decltype(&lg_features_fwd<4, true>);
-static FeaturesFwdKernel features_fwd_kernel(int cg, bool exact)
-{
-    static const FeaturesFwdKernel k[3][2] = { { lg_features_fwd<4, false>, lg_features_fwd<4, true> }, { lg_features_fwd<16, false>, lg_features_fwd<16, true> },
-                                               { lg_features_fwd<32, false>, lg_features_fwd<32, true> } };
-    return k[cg == 4 ? 0 : cg == 16 ? 1 : 2][exact];
-}
-using FeaturesBwdKernel = decltype(&lg_features_bwd<4, true>);
-static FeaturesBwdKernel features_bwd_kernel(int nv, bool exact)
-{
-    static const FeaturesBwdKernel k[3][2] = { { lg_features_bwd<4, false>, lg_features_bwd<4, true> }, { lg_features_bwd<8, false>, lg_features_bwd<8, true> },
-                                               { lg_features_bwd<16, false>, lg_features_bwd<16, true> } };
-    return k[nv == 4 ? 0 : nv == 8 ? 1 : 2][exact];
-}
-
 extern "C" size_t lg_features_scratch_bytes(int32_t N, int64_t num_rendered, int32_t C)
 {
     (void)N;
@@ -1842,11 +1855,8 @@ extern "C" int lg_blend_features(const lg_view* v, int32_t N, const void* geom_p
     int rc = features_args("lg_blend_features", v, N, geom_p, bin_p, R, C);
     if (rc != LG_OK) return rc;
     if (!out || (N > 0 && !features)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_blend_features: missing features / out buffer");
-    hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, exact = !(v->flags & LG_FLAG_FAST_EXP);
-    const ViewState s = view_state(v, N, geom_p, nullptr, bin_p, R);
+    const auto [stream, debug, prof, exact, s, f] = walk_call(v, N, geom_p, nullptr, bin_p, R, stream_p);
     const ViewGeom& q = s.q;
-    const LgFeatView f = features_view(s, N, R);
     for (int c0 = 0, cg; c0 < C; c0 += cg) {
         cg = features_channel_group(C - c0);
         {
@@ -1862,11 +1872,8 @@ extern "C" int lg_blend_features(const lg_view* v, int32_t N, const void* geom_p
 static int features_backward_run(const lg_view* v, int32_t N, const void* geom_p, const void* bin_p, int64_t R, const float* dL_dout, int32_t C,
                                  float* dL_dfeatures, void* scratch, void* stream_p)
 {
-    hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, exact = !(v->flags & LG_FLAG_FAST_EXP);
-    const ViewState s = view_state(v, N, geom_p, nullptr, bin_p, R);
+    const auto [stream, debug, prof, exact, s, f] = walk_call(v, N, geom_p, nullptr, bin_p, R, stream_p);
     const ViewGeom& q = s.q; const GeomView& geo = s.geo;
-    const LgFeatView f = features_view(s, N, R);
     float* rows = (float*)scratch;        // [R][cw] partial rows of the current chunk of channels, every row written by lg_features_bwd
     const int chunk = lg_features_chunk(R, C);
     for (int cb = 0; cb < C; cb += chunk) {
@@ -1921,8 +1928,7 @@ extern "C" int lg_backward_features(const lg_view* v, const lg_gaussians* g, con
     if (!g) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_features: null gaussians");
     int rc = features_args("lg_backward_features", v, g->N, geom_p, bin_p, R, C);
     if (rc != LG_OK) return rc;
-    if (g->N > 0 && !features && (dL_dout || dL_dfeatures)) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_features: missing features");
-    if (g->N > 0 && dL_dfeatures && !dL_dout) return fail(LG_ERR_INVALID_ARGUMENT, "lg_backward_features: dL_dfeatures without dL_dout");
+    if ((rc = features_grad_args("lg_backward_features", g->N, features, dL_dout, dL_dfeatures)) != LG_OK) return rc;
     const FeatGrad fg = { features, C, bg_features, dL_dout, dL_dalpha };
     const GradOut d = { dL_dmeans2D, dL_dmeans3D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dshs_rest };
     rc = backward_impl(v, g, radii, geom_p, bin_p, img_p, R, dL_dcolor, d, scratch, stream_p, { 1, nullptr, nullptr, &fg, nullptr });
@@ -1955,14 +1961,11 @@ extern "C" int lg_blend_distortion(const lg_view* v, int32_t N, const void* geom
     int rc = distortion_args("lg_blend_distortion", v, N, geom_p, bin_p, R, 0, m, m_stride, state);
     if (rc != LG_OK) return rc;
     if (!distortion) return refuse("lg_blend_distortion", "missing distortion map");
-    hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE, exact = !(v->flags & LG_FLAG_FAST_EXP);
-    const ViewState s = view_state(v, N, geom_p, nullptr, bin_p, R);
+    const auto [stream, debug, prof, exact, s, f] = walk_call(v, N, geom_p, nullptr, bin_p, R, stream_p);
     const ViewGeom& q = s.q;
-    const LgFeatView f = features_view(s, N, R);
     {
         ProfScope ps(prof, "distortion_fwd", stream);
-        (exact ? lg_distortion_fwd<true> : lg_distortion_fwd<false>)<<<q.ntiles_pad, 256, 0, stream>>>(
+        distortion_fwd_kernel(exact)<<<q.ntiles_pad, 256, 0, stream>>>(
             f, m, m_stride, distortion, median, (float4*)state, (uint32_t*)((char*)state + distortion_state_head(q.W, q.H)));
     }
     KCHECK("lg_distortion_fwd");
@@ -1991,8 +1994,7 @@ extern "C" int lg_backward_distortion(const lg_view* v, const lg_gaussians* g, c
     int rc = distortion_args(who, v, g->N, geom_p, bin_p, R, C, m, m_stride, state);
     if (rc != LG_OK) return rc;
     const int N = g->N;
-    if (N > 0 && !features && (dL_dout || dL_dfeatures)) return refuse(who, "missing features");
-    if (N > 0 && dL_dfeatures && !dL_dout) return refuse(who, "dL_dfeatures without dL_dout");
+    if ((rc = features_grad_args(who, N, features, dL_dout, dL_dfeatures)) != LG_OK) return rc;
     if (C == 0 && dL_dout) return refuse(who, "dL_dout without channels (C is 0)");
     if (N > 0 && !dL_dm) return refuse(who, "missing dL_dm");
     if (N == 0) return LG_OK;       // nothing to write
@@ -2009,10 +2011,7 @@ extern "C" int lg_backward_distortion(const lg_view* v, const lg_gaussians* g, c
         rc = features_backward_run(v, N, geom_p, bin_p, R, dL_dout, C, dL_dfeatures, feat_scratch, stream_p);
         if (rc != LG_OK) return rc;
     }
-    hipStream_t stream = (hipStream_t)stream_p;
-    const bool debug = v->flags & LG_FLAG_DEBUG, prof = v->flags & LG_FLAG_PROFILE;
-    const ViewState s = view_state(v, N, geom_p, nullptr, bin_p, R);
-    const LgFeatView f = features_view(s, N, R);
+    const auto [stream, debug, prof, exact, s, f] = walk_call(v, N, geom_p, nullptr, bin_p, R, stream_p);
     // (a segment length other than the forward's: lg_distortion_bwd wrote zero dm rows)
     {
         ProfScope ps(prof, "distortion_gather", stream);

@@ -7,25 +7,20 @@
 // duplication, the radix passes and the tile sort, and the gradient with respect to the channels, dF[j][c] = sum_pixels w[p][j] g[c][p],
 // needs neither K7's back-to-front replay nor K9.
 //
-// Walk (both kernels): K6's -- a workgroup per 16 x 16 tile, a wave per 8 x 8 block, batches of 64 list entries, lg_block_hit against the
-// wave's block, hits compacted in list order into the wave's LDS queue -- but only the 32 bytes of record the pair step reads are queued,
-// next to the Gaussian id.  The pair step is lg_feature_step (lg_math.h) on lg_pair_power and on lg_alpha_exact (canonical) or the
-// forward's guarded hardware exp (LG_FLAG_FAST_EXP): the include / exclude decisions are the forward's.  Each pixel terminates on its own
-// T (1 - alpha) < 1e-4; n_contrib is not read.  Lists of any length are walked serially (no checkpoints).  Nothing spins or waits; every
-// loop is bounded by the tile's range clamped to the view's instance count (geom.counters, as every kernel behind K2), ids are
-// checked against N.  A view the forward abandoned on the device has empty lists here: the image is the background, the gradient zero.
+// Every kernel here and in lg_distortion.h walks the lists as K6 does -- a workgroup per 16 x 16 tile, a wave per 8 x 8 block, batches of
+// LG_Q list entries, lg_block_hit against the wave's block, hits compacted in list order into the wave's LDS queue (LgFeatQueue: only the
+// 32 bytes of record the pair step reads, next to the Gaussian id) -- with power and alpha exactly as the forward evaluated them
+// (lg_feat_alpha): the include / exclude decisions are the forward's.  Lists of any length are walked serially (no checkpoints).  Nothing
+// spins or waits; every loop is bounded by the tile's range clamped to the view's instance count (geom.counters, as every kernel behind
+// K2), ids are checked against N.  A view the forward abandoned on the device has empty lists here: the image is the background, the
+// gradient zero.  The back-to-front walk with its reduction into per-instance rows exists once (lg_feat_back_begin, lg_feat_walk_back): a
+// kernel hands it its staging, its per-hit arithmetic and its sink.  The three front-to-back loops (lg_features_fwd, lg_features_bwd,
+// lg_distortion_fwd) are short and stay with their kernels, on the shared steps lg_feat_front, _pair and _batch_end.
 //
-// Forward: the feature rows of a batch's hits are staged through LDS (coalesced row segments; the pair loop reads them as broadcast
-// ds_read_b128) and CG = 4 / 16 / 32 channels are carried per walk -- one walk up to 32 channels, two up to 64.  out_c = fma(T, bg_c, F_c).
-// alpha is accumulated as one more channel whose feature is 1 (sum of w): bit for bit the blend of a column of ones, equal to 1 - T
-// up to rounding.
-//
-// Backward: K7's discipline -- no float atomics, no memset.  Per hit entry a wave reduces w g[c] over its 64 pixels through an LDS
-// transpose (lg_feat_reduce: K7's wave_reduce_via_lds, lg_blend.h, for NV = 4 / 8 / 16 values; entries no lane of the wave hit are skipped), the four waves'
-// partials meet in LDS and one row of NV sums per (tile, Gaussian) instance goes to the instance's pre-sort slot (lg_slot_of), written
-// exactly once, zeros included.  lg_features_gather adds every Gaussian's contiguous rows in slot order: bit-identical run to run.
-// Every step of the walk is one function (lg_feat_list, _front, _alpha, _pair, _stage_rows, _slot, _reduce); only the cross-wave merges
-// of lg_features_bwd (a thread per (entry, value)) and lg_features_bwd_geom (a thread per entry, 12-float rows) stay with their kernels.
+// The gradients keep K7's discipline -- no float atomics, no memset.  Per hit entry a wave reduces its 64 pixels' values through an LDS
+// transpose (lg_feat_reduce: K7's wave_reduce_via_lds, lg_blend.h; entries no lane of the wave hit are skipped), the four waves' partials
+// meet in LDS (LgFeatMerge) and one row per (tile, Gaussian) instance goes to the instance's pre-sort slot (lg_slot_of), written exactly
+// once per walk, zeros included.  lg_features_gather adds every Gaussian's contiguous rows in slot order: bit-identical run to run.
 #pragma once
 
 #include "lg_host.h"
@@ -53,11 +48,18 @@ __device__ __forceinline__ bool lg_feat_list(const LgFeatView& v, int tile, uint
     return true;
 }
 
+// The hits of a batch, a queue per wave (one __shared__ LgFeatQueue per kernel): record rows 0 and 1, the Gaussian id, the entry's
+// position in the batch.  A wave works on its own view of it.
+struct LgFeatWaveQueue { float4 *q0, *q1; uint32_t *qid, *qpos; };
+struct LgFeatQueue {
+    float4 q0[4][LG_Q], q1[4][LG_Q];
+    uint32_t qid[4][LG_Q], qpos[4][LG_Q];
+    __device__ __forceinline__ LgFeatWaveQueue of(int wave) { return { q0[wave], q1[wave], qid[wave], qpos[wave] }; }
+};
+
 // The front of one batch: lane l takes list entry idx = base + l (when idx < hi), tests its footprint against the wave's 8 x 8 block and
-// the hits are compacted in list order into the wave's queue: record rows 0 and 1, the Gaussian id, the entry's position in the batch.
-// Returns the number of hits.
-__device__ __forceinline__ uint32_t lg_feat_front(const LgFeatView& v, uint32_t idx, uint32_t hi, float bx0, float by0, float4* q0, float4* q1,
-                                                  uint32_t* qid, uint32_t* qpos, uint32_t lane)
+// the hits are compacted in list order into the wave's queue.  Returns the number of hits.
+__device__ __forceinline__ uint32_t lg_feat_front(const LgFeatView& v, uint32_t idx, uint32_t hi, const LgBlock& g, const LgFeatWaveQueue& q)
 {
     bool hit = false;
     float4 r0, r1;
@@ -67,14 +69,14 @@ __device__ __forceinline__ uint32_t lg_feat_front(const LgFeatView& v, uint32_t 
         if (id < (uint32_t)v.N) {
             r0 = v.rec[LG_REC_F4 * (size_t)id]; r1 = v.rec[LG_REC_F4 * (size_t)id + 1];
             const float4 r2 = v.rec[LG_REC_F4 * (size_t)id + 2];
-            hit = lg_block_hit(r0, r1, r2, lg_reach(r0, r1, r2), bx0, by0);
+            hit = lg_block_hit(r0, r1, r2, lg_reach(r0, r1, r2), (float)g.wx0, (float)g.wy0);
         }
     }
     const uint64_t mask = __ballot(hit);
     if (mask == 0) return 0u;
     if (hit) {
         const uint32_t pos = prefix_popc(mask);
-        q0[pos] = r0; q1[pos] = r1; qid[pos] = id; qpos[pos] = lane;
+        q.q0[pos] = r0; q.q1[pos] = r1; q.qid[pos] = id; q.qpos[pos] = g.lane;
     }
     lg_wave_lds_sync();
     return (uint32_t)__popcll(mask);
@@ -126,39 +128,48 @@ __device__ __forceinline__ int lg_feat_pair(const float4& a, const float4& b, bo
     return done ? 0 : lg_feature_step(power, alpha, T, w);
 }
 
+// The end of a batch in a front-to-back walk: release + barrier without the acquire (so not lg_wave_lds_sync) -- the LDS accesses of
+// the batch must be done before the next one overwrites the queue; no read below depends on them.
+__device__ __forceinline__ void lg_feat_batch_end()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 // ------------------------------------------------------------------------------------------------
-// forward: channels [c0, c0 + CG) of out[C][H][W] (those below C), and alpha[H][W] with the first group
+// forward: channels [c0, c0 + CG) of out[C][H][W] (those below C), and alpha[H][W] with the first group.  The feature rows of a batch's
+// hits are staged through LDS (coalesced row segments; the hits read them as broadcast ds_read_b128) and CG = 4 / 16 / 32 channels are
+// carried per walk -- one walk up to 32 channels, two up to 64.  out_c = fma(T, bg_c, F_c).  alpha is accumulated as one more channel
+// whose feature is 1 (sum of w): bit for bit the blend of a column of ones, equal to 1 - T up to rounding.
 template <int CG, bool EXACT>
 __global__ void __launch_bounds__(256)
 lg_features_fwd(LgFeatView v, int C, int c0, const float* __restrict__ features, const float* __restrict__ bg, float* __restrict__ out,
                 float* __restrict__ alpha_out)
 {
     static_assert(CG % 4 == 0, "feature rows are read as float4");
-    __shared__ float4 q0[4][LG_Q], q1[4][LG_Q];
-    __shared__ uint32_t qid[4][LG_Q], qpos[4][LG_Q];
+    __shared__ LgFeatQueue queue;
     __shared__ __attribute__((aligned(16))) float frow[4][LG_Q * CG];
     const int tile = xcd_tile(blockIdx.x);
     if (tile >= v.ntiles) return;
     const int wave = threadIdx.x >> 6;
-    const uint32_t lane = threadIdx.x & 63;
-    const LgBlock g = lg_block(v.W, v.H, tile % v.gx, tile / v.gx, wave, lane);
-    const float pxf = (float)g.pxi, pyf = (float)g.pyi;
+    const LgBlock g = lg_block(v.W, v.H, tile % v.gx, tile / v.gx, wave, threadIdx.x & 63);
+    const LgFeatWaveQueue q = queue.of(wave);
     uint32_t lo, hi;
     (void)lg_feat_list(v, tile, lo, hi);        // an abandoned view has empty lists: background, alpha 0
 
+    const float pxf = (float)g.pxi, pyf = (float)g.pyi;
     float T = 1.0f, A = 0.0f, F[CG];
 #pragma unroll
     for (int c = 0; c < CG; c++) F[c] = 0.0f;
     bool done = !g.inside;
     for (uint32_t base = lo; base < hi; base += LG_Q) {
         if (__ballot(!done) == 0) break;        // every pixel of this wave is saturated or outside
-        const uint32_t nhit = lg_feat_front(v, base + lane, hi, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], qid[wave], qpos[wave], lane);
+        const uint32_t nhit = lg_feat_front(v, base + g.lane, hi, g, q);
         if (nhit == 0u) continue;
-        lg_feat_stage_rows<CG>(features, C, c0, qid[wave], nhit, frow[wave], lane);
+        lg_feat_stage_rows<CG>(features, C, c0, q.qid, nhit, frow[wave], g.lane);
         for (uint32_t j = 0; j < nhit; j++) {
-            const float4 a = q0[wave][j], b = q1[wave][j];
             float w;
-            const int res = lg_feat_pair<EXACT>(a, b, done, pxf, pyf, T, w);
+            const int res = lg_feat_pair<EXACT>(q.q0[j], q.q1[j], done, pxf, pyf, T, w);
             done = done || res == 2;
             A = fmaf(1.0f, w, A);
             const float4* fr = reinterpret_cast<const float4*>(&frow[wave][j * CG]);
@@ -169,9 +180,7 @@ lg_features_fwd(LgFeatView v, int C, int c0, const float* __restrict__ features,
                 F[4 * k + 2] = fmaf(f.z, w, F[4 * k + 2]); F[4 * k + 3] = fmaf(f.w, w, F[4 * k + 3]);
             }
         }
-        // release + barrier without the acquire (so not lg_wave_lds_sync): the LDS accesses above must be done first; no read below depends on them
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();        // (the next batch overwrites the queue)
+        lg_feat_batch_end();
     }
     if (g.inside) {
         const size_t pid = (size_t)g.pyi * v.W + g.pxi, HW = (size_t)v.H * v.W;
@@ -191,27 +200,36 @@ __device__ __forceinline__ void lg_feat_reduce(const float (&p)[NV], float* red,
     wave_reduce_via_lds<NV>(p, red, lane, [&](uint32_t r, float s) { dst[r] = s; });
 }
 
-// Channels [c0, c0 + NV) (those below c1) of the partial rows: rows[slot][CW], column (c0 - cb) + k, for every entry of every list.
-// The four waves of a tile walk the list batch by batch TOGETHER (two workgroup barriers per batch, reached by every thread: the trip
-// count is the tile's); a wave whose pixels are all saturated skips the batch's arithmetic, and the rows of entries nobody hit are zeros.
+// Where the four waves of a workgroup meet per batch: a wave's reduction scratch, its partial row of NV totals per entry it has one for
+// (part[wave][e * LG_FEAT_PART_STRIDE(NV) + r]) and the mask of those entries.  Three LDS arrays, declared by LG_FEAT_MERGE_LDS, and not
+// one struct: the compiler places separate arrays as it always did, one object costs six lg_features_bwd_geom instances two VGPRs.
 #define LG_FEAT_PART_STRIDE(NV) ((NV) + 1)
+template <int NV>
+struct LgFeatMerge { float (*red)[NV * LG_RED_STRIDE]; float (*part)[LG_Q * LG_FEAT_PART_STRIDE(NV)]; unsigned long long* wmask; };
+#define LG_FEAT_MERGE_LDS(NV, mg) \
+    __shared__ __attribute__((aligned(16))) float mg##_red[4][(NV) * LG_RED_STRIDE]; \
+    __shared__ float mg##_part[4][LG_Q * LG_FEAT_PART_STRIDE(NV)]; \
+    __shared__ unsigned long long mg##_wmask[4]; \
+    const LgFeatMerge<NV> mg = { mg##_red, mg##_part, mg##_wmask }
+
+// Channels [c0, c0 + NV) (those below c1) of the partial rows: rows[slot][CW], column (c0 - cb) + k, for every entry of every list:
+// per hit entry a wave reduces w g[c] over its pixels, NV = 4 / 8 / 16 values.  The order is the forward's, but the four waves take every
+// batch TOGETHER (two workgroup barriers per batch, reached by every thread: the trip count is the tile's), a wave whose pixels are all
+// saturated only skips the batch's arithmetic, and a thread per (entry, value) merges -- zeros for entries nobody hit.
 template <int NV, bool EXACT>
 __global__ void __launch_bounds__(256)
 lg_features_bwd(LgFeatView v, int c0, int c1, int cb, int CW, const uint4* __restrict__ tinfo, const float* __restrict__ dL_dout,
                 float* __restrict__ rows)
 {
-    __shared__ float4 q0[4][LG_Q], q1[4][LG_Q];
-    __shared__ uint32_t qid[4][LG_Q], qpos[4][LG_Q];
-    __shared__ __attribute__((aligned(16))) float red[4][NV * LG_RED_STRIDE];
-    __shared__ float part[4][LG_Q * LG_FEAT_PART_STRIDE(NV)];
+    __shared__ LgFeatQueue queue;
+    LG_FEAT_MERGE_LDS(NV, mg);
     __shared__ uint32_t slot[LG_Q];
-    __shared__ unsigned long long wmask[4];
     const int tile = xcd_tile(blockIdx.x);
     if (tile >= v.ntiles) return;
-    const int wave = threadIdx.x >> 6;
+    const int wave = threadIdx.x >> 6, tx = tile % v.gx, ty = tile / v.gx;
     const uint32_t lane = threadIdx.x & 63;
-    const int tx = tile % v.gx, ty = tile / v.gx;
     const LgBlock g = lg_block(v.W, v.H, tx, ty, wave, lane);
+    const LgFeatWaveQueue q = queue.of(wave);
     const float pxf = (float)g.pxi, pyf = (float)g.pyi;
     uint32_t lo, hi;
     if (!lg_feat_list(v, tile, lo, hi) || lo == hi) return;      // workgroup-uniform
@@ -230,29 +248,28 @@ lg_features_bwd(LgFeatView v, int c0, int c1, int cb, int CW, const uint4* __res
         if (wave == 0) slot[lane] = lg_feat_slot(v, tinfo, base + lane, lane < nbt, tx, ty);      // where the batch's rows go
         uint64_t hitmask = 0ull;                                  // entries of the batch this wave has a partial row for (scalar)
         if (__ballot(!done) != 0) {
-            const uint32_t nhit = lg_feat_front(v, base + lane, hi, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], qid[wave], qpos[wave], lane);
+            const uint32_t nhit = lg_feat_front(v, base + lane, hi, g, q);
             for (uint32_t j = 0; j < nhit; j++) {
-                const float4 a = q0[wave][j], b = q1[wave][j];
                 float w;
-                const int res = lg_feat_pair<EXACT>(a, b, done, pxf, pyf, T, w);
+                const int res = lg_feat_pair<EXACT>(q.q0[j], q.q1[j], done, pxf, pyf, T, w);
                 done = done || res == 2;
                 if (__ballot(res == 1) == 0) continue;            // no pixel of the wave took the entry
                 float p[NV];
 #pragma unroll
                 for (int k = 0; k < NV; k++) p[k] = w * gv[k];
-                const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)qpos[wave][j]);
-                lg_feat_reduce<NV>(p, red[wave], &part[wave][e * LG_FEAT_PART_STRIDE(NV)], lane);
+                const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.qpos[j]);
+                lg_feat_reduce<NV>(p, mg.red[wave], &mg.part[wave][e * LG_FEAT_PART_STRIDE(NV)], lane);
                 hitmask |= 1ull << e;
             }
         }
-        if (lane == 0u) wmask[wave] = hitmask;
+        if (lane == 0u) mg.wmask[wave] = hitmask;
         __syncthreads();
         for (uint32_t i = threadIdx.x; i < nbt * NV; i += 256u) {
             const uint32_t e = i / NV, k = i % NV;
             float s = 0.0f;
 #pragma unroll
             for (int u = 0; u < 4; u++)
-                if ((wmask[u] >> e) & 1ull) s += part[u][e * LG_FEAT_PART_STRIDE(NV) + k];
+                if ((mg.wmask[u] >> e) & 1ull) s += mg.part[u][e * LG_FEAT_PART_STRIDE(NV) + k];
             const uint32_t sl = slot[e];
             if (sl < slot_cap && c0 + (int)k < c1) rows[(size_t)sl * CW + (c0 - cb) + k] = s;
         }
@@ -281,26 +298,126 @@ lg_features_gather(int N, int C, int cb, int cw, int live, uint32_t cap, const u
 }
 
 // ------------------------------------------------------------------------------------------------
+// The BACK-TO-FRONT walk of a tile: the replay behind every gradient with respect to the geometry (lg_features_bwd_geom here,
+// lg_distortion_bwd in lg_distortion.h).  The four waves take a batch of LG_Q entries together, from the tile's last batch down to its
+// first, the hits of a batch from the last to the first.  Per pixel T starts at the colour forward's final_T, S at 0, and an entry is
+// live when its list position is <= the pixel's n_contrib (img buffer); power, G and alpha are the forward's own.  Per hit entry NV
+// values are reduced over the wave, the waves' partials meet in LDS and thread e of the workgroup owns entry e of the batch: its
+// four-wave total (lg_feat_merge) and the pre-sort slot of its row.  Walks are stream-ordered and a slot has one writer per walk.  Two
+// workgroup barriers per batch, reached by every thread (the trip count is the tile's): every return in front of them is
+// workgroup-uniform.  A wave none of whose pixels reached a batch skips its arithmetic.
+struct LgBackWalk {
+    uint32_t lo, hi, n_list, slot_cap;          // the tile's entries [lo, hi), n_list of them; rows live at slots below slot_cap
+    uint32_t last, wl; float T;                 // the last list position the pixel / any pixel of its wave reached; the pixel's final_T
+};
+// what the per-hit hook gets: hit j of the wave's queue at 1-based list position pos, live or not, the pair as the forward saw it
+struct LgBackHit { uint32_t j, pos; bool live; float power, G, alpha, dx, dy; };
+
+// False (workgroup-uniform, the kernel returns): the tile's list is empty, the forward abandoned the view, or the segment length is not
+// the forward's (meta[2]: the binning buffer is laid out by it) -- K9 refuses those views too, the gradients are zero.
+__device__ __forceinline__ bool lg_feat_back_begin(const LgFeatView& v, int tile, const LgBlock& g, uint32_t S, const uint32_t* meta,
+                                                   const float* final_T, const uint32_t* n_contrib, LgBackWalk& bw)
+{
+    if (!lg_feat_list(v, tile, bw.lo, bw.hi) || bw.lo == bw.hi) return false;
+    if (meta[2] != S) return false;             // (lo < hi: the view is live, the binning buffer is there)
+    bw.slot_cap = min(v.counters[3], v.cap); bw.n_list = bw.hi - bw.lo;
+    bw.T = 0.0f; bw.last = 0u;                  // (outside the image)
+    if (g.inside) {
+        const size_t pid = (size_t)g.pyi * v.W + g.pxi;
+        bw.T = final_T[pid]; bw.last = min(n_contrib[pid], bw.n_list);
+    }
+    bw.wl = (uint32_t)__builtin_amdgcn_readfirstlane((int)lg_wave_all_max(bw.last));
+    return true;
+}
+
+// the four-wave total t of entry e: waves 0..3 in this order, those that have a partial row for the entry
+template <int NV>
+__device__ __forceinline__ void lg_feat_merge(const LgFeatMerge<NV>& mg, uint32_t e, float (&t)[NV])
+{
+#pragma unroll
+    for (int r = 0; r < NV; r++) t[r] = 0.0f;
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+        if ((mg.wmask[u] >> e) & 1ull) {
+#pragma unroll
+            for (int r = 0; r < NV; r++) t[r] += mg.part[u][e * LG_FEAT_PART_STRIDE(NV) + r];
+        }
+}
+
+// The batches that hold the first n_walk entries of the list (workgroup-uniform), after lg_feat_back_begin.  Per batch a wave reached:
+// stage(nhit) once (also for nhit == 0), then per hit, last to first, ok = hit(h, T, S, p) fills the pixel's p[NV] (zeros on entry)
+// and advances T and S when the pixel takes the entry.  Per entry of every visited batch: sink(slot, t), t the merged totals -- zeros
+// for an entry nobody took.
+template <int NV, bool EXACT, typename Stage, typename Hit, typename Sink>
+__device__ __forceinline__ void lg_feat_walk_back(const LgFeatView& v, int tile, const LgBlock& g, const uint4* tinfo, const LgBackWalk& bw,
+                                                  uint32_t n_walk, const LgFeatWaveQueue& q, const LgFeatMerge<NV>& mg, Stage& stage, Hit& hit, Sink& sink)
+{
+    if (n_walk == 0u) return;
+    const int tx = tile % v.gx, ty = tile / v.gx, wave = g.sub;
+    const float pxf = (float)g.pxi, pyf = (float)g.pyi;
+    float T = bw.T, Sb = 0.0f;
+    for (int k = (int)((n_walk - 1u) / LG_Q); k >= 0; k--) {
+        const uint32_t rel0 = (uint32_t)k * LG_Q, base = bw.lo + rel0;
+        const uint32_t nbt = min((uint32_t)LG_Q, bw.n_list - rel0);
+        const uint32_t sl = lg_feat_slot(v, tinfo, base + threadIdx.x, threadIdx.x < nbt, tx, ty);
+        uint64_t hitmask = 0ull;                                  // entries of the batch this wave has a partial row for (scalar)
+        if (bw.wl > rel0) {
+            const uint32_t nhit = lg_feat_front(v, base + g.lane, bw.hi, g, q);
+            stage(nhit);
+            for (int j = (int)nhit - 1; j >= 0; j--) {
+                const float4 a = q.q0[j], b = q.q1[j];
+                const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.qpos[j]);
+                LgBackHit h;
+                h.j = (uint32_t)j; h.pos = rel0 + e + 1u; h.live = h.pos <= bw.last;
+                h.power = lg_rec_power(a, b, pxf, pyf, h.dx, h.dy);
+                h.alpha = lg_feat_alpha<EXACT>(b.y, h.power, h.G);
+                float p[NV];
+#pragma unroll
+                for (int r = 0; r < NV; r++) p[r] = 0.0f;
+                const bool ok = hit(h, T, Sb, p);
+                if (__ballot(ok) == 0) continue;                  // no pixel of the wave took the entry
+                lg_feat_reduce<NV>(p, mg.red[wave], &mg.part[wave][e * LG_FEAT_PART_STRIDE(NV)], g.lane);
+                hitmask |= 1ull << e;
+            }
+        }
+        if (g.lane == 0u) mg.wmask[wave] = hitmask;
+        __syncthreads();
+        if (threadIdx.x < nbt && sl < bw.slot_cap) {
+            float t[NV];
+            lg_feat_merge<NV>(mg, threadIdx.x, t);
+            sink(sl, t);
+        }
+        __syncthreads();                                          // (the next batch overwrites the queue, the partials and the masks)
+    }
+}
+
+// Columns 0..5 of the 12-float moment row at slot sl (K7's rows, lg_blend_bwd; K9 sums them): t[0..5] added (ACCUM) or the whole row
+// written, zeros behind them (!ACCUM: the first walk into the rows when K7 did not run).
+template <bool ACCUM>
+__device__ __forceinline__ void lg_feat_store_moments(float* rows, uint32_t sl, const float* t)
+{
+    float4* dst = reinterpret_cast<float4*>(rows) + 3 * (size_t)sl;
+    if (ACCUM) {
+        const float4 r0 = dst[0];
+        const float2 r1 = *reinterpret_cast<const float2*>(dst + 1);
+        dst[0] = make_float4(r0.x + t[0], r0.y + t[1], r0.z + t[2], r0.w + t[3]);
+        *reinterpret_cast<float2*>(dst + 1) = make_float2(r1.x + t[4], r1.y + t[5]);
+    } else {
+        dst[0] = make_float4(t[0], t[1], t[2], t[3]);
+        dst[1] = make_float4(t[4], t[5], 0.0f, 0.0f);
+        dst[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // backward with respect to the GEOMETRY: the six pixel-offset moments of a loss on out / alpha, added to (ACCUM) or written as (!ACCUM)
 // the per-instance moment rows [R][12] that K7 (lg_blend_bwd) writes and K9 (lg_preprocess_bwd) sums and chains to every input.
 // The moments are linear in the per-pixel loss gradient, so a colour loss (K7), CG channels of dL_dout per walk and dL_dalpha (with the
 // walk of channel 0) meet in the same rows and K9 runs once.
 //
-// Walk: lg_features_bwd's -- a workgroup per tile, a wave per 8 x 8 block, the four waves take a batch of 64 entries together, hits
-// through lg_feat_front -- but BACK TO FRONT: batches from the tile's last one down to its first, the hits of a batch from the last
-// to the first.  Per pixel T starts at the colour forward's final_T and an entry counts when its list position is <= the pixel's
-// n_contrib (img buffer), then lg_feature_bwd_step (lg_math.h) on the forward's own power / alpha.  Lists of any length are walked
-// serially, no checkpoints are read; every loop is bounded by the tile's range clamped to counters[3], ids are checked against N,
-// nothing spins or waits (two workgroup barriers per batch, reached by every thread: the trip count is the tile's).  A view the
-// forward abandoned and a segment length other than the forward's (meta[2]) return at once: K9 refuses those too, the gradients are
-// zero.  A wave none of whose pixels reached a batch skips its arithmetic; with ACCUM the batches behind the last one any pixel of the
-// tile reached are not visited at all, without it they get their zero rows (K9 reads every row).
-//
 // Channels [c0, c0 + CG) (those below C): g_c in registers, the feature rows of a batch's hits staged through LDS as in lg_features_fwd,
-// q = sum_c f_c g_c (+ dL_dalpha when c0 == 0).  Reduction: K7's discipline -- per hit entry lg_feat_reduce<6> over the wave's 64
-// pixels, the four waves' partials meet in LDS, thread e of the workgroup owns entry e of the batch and updates columns 0..5 of its
-// row at the pre-sort slot (lg_slot_of).  !ACCUM writes all 12 floats.  Walks are stream-ordered and a slot has one writer per walk:
-// no float atomics, no memset, bit-identical run to run.
+// q = sum_c f_c g_c (+ dL_dalpha when c0 == 0), then lg_feature_bwd_step (lg_math.h).  With ACCUM the batches behind the last one any
+// pixel of the tile reached are not visited at all; without it they get their zero rows (K9 reads every row).
 #define LG_FEAT_GEOM_NV 6
 template <int CG, bool EXACT, bool ACCUM>
 __global__ void __launch_bounds__(256)
@@ -311,113 +428,51 @@ lg_features_bwd_geom(LgFeatView v, uint32_t S, const uint32_t* __restrict__ meta
 {
     static_assert(CG % 4 == 0, "feature rows are read as float4");
     constexpr int NV = LG_FEAT_GEOM_NV;
-    __shared__ float4 q0[4][LG_Q], q1[4][LG_Q];
-    __shared__ uint32_t qid[4][LG_Q], qpos[4][LG_Q];
+    __shared__ LgFeatQueue queue;
     __shared__ __attribute__((aligned(16))) float frow[4][LG_Q * CG];
-    __shared__ __attribute__((aligned(16))) float red[4][NV * LG_RED_STRIDE];
-    __shared__ float part[4][LG_Q * LG_FEAT_PART_STRIDE(NV)];
-    __shared__ unsigned long long wmask[4];
+    LG_FEAT_MERGE_LDS(NV, mg);
     __shared__ uint32_t wlast[4];
     const int tile = xcd_tile(blockIdx.x);
     if (tile >= v.ntiles) return;
     const int wave = threadIdx.x >> 6;
-    const uint32_t lane = threadIdx.x & 63;
-    const int tx = tile % v.gx, ty = tile / v.gx;
-    const LgBlock g = lg_block(v.W, v.H, tx, ty, wave, lane);
-    const float pxf = (float)g.pxi, pyf = (float)g.pyi;
-    uint32_t lo, hi;
-    if (!lg_feat_list(v, tile, lo, hi) || lo == hi) return;      // workgroup-uniform
-    if (meta[2] != S) return;                                    // (lo < hi: the view is live, the binning buffer is there)
-    const uint32_t slot_cap = min(v.counters[3], v.cap);
-    const uint32_t n_list = hi - lo;
+    const LgBlock g = lg_block(v.W, v.H, tile % v.gx, tile / v.gx, wave, threadIdx.x & 63);
+    const LgFeatWaveQueue q = queue.of(wave);
+    LgBackWalk bw;
+    if (!lg_feat_back_begin(v, tile, g, S, meta, final_T, n_contrib, bw)) return;
 
-    // per pixel: the gradient of this group of channels, the background term, the replay state
-    float gv[CG];
-    float gA = 0.0f, T = 0.0f, Tfb = 0.0f, Sb = 0.0f;
-    uint32_t last = 0u;
+    // per pixel: the gradient of this group of channels, the background term
+    float gv[CG], gA = 0.0f, bgdot = 0.0f;
     const bool have = dL_dout != nullptr;
-    {
-        const size_t pid = (size_t)g.pyi * v.W + g.pxi, HW = (size_t)v.H * v.W;
-        float bgdot = 0.0f;
+    const size_t pid = (size_t)g.pyi * v.W + g.pxi, HW = (size_t)v.H * v.W;
 #pragma unroll
-        for (int k = 0; k < CG; k++) {
-            gv[k] = (have && g.inside && c0 + k < C) ? dL_dout[(size_t)(c0 + k) * HW + pid] : 0.0f;
-            if (bg && c0 + k < C) bgdot = fmaf(bg[c0 + k], gv[k], bgdot);
-        }
-        if (g.inside) {
-            T = final_T[pid];
-            last = min(n_contrib[pid], n_list);
-            if (dL_dalpha && c0 == 0) gA = dL_dalpha[pid];
-        }
-        Tfb = T * bgdot;
+    for (int k = 0; k < CG; k++) {
+        gv[k] = (have && g.inside && c0 + k < C) ? dL_dout[(size_t)(c0 + k) * HW + pid] : 0.0f;
+        if (bg && c0 + k < C) bgdot = fmaf(bg[c0 + k], gv[k], bgdot);
     }
-    // the last list position any pixel of the wave / of the tile reached
-    const uint32_t wl = (uint32_t)__builtin_amdgcn_readfirstlane((int)lg_wave_all_max(last));
-    if (lane == 0u) wlast[wave] = wl;
+    if (g.inside && dL_dalpha && c0 == 0) gA = dL_dalpha[pid];
+    const float Tfb = bw.T * bgdot;
+    // the last list position any pixel of the tile reached
+    if (g.lane == 0u) wlast[wave] = bw.wl;
     __syncthreads();
     const uint32_t tl = max(max(wlast[0], wlast[1]), max(wlast[2], wlast[3]));
-    const uint32_t n_walk = ACCUM ? tl : n_list;                 // entries this walk visits
-    if (n_walk == 0u) return;                                    // workgroup-uniform
 
-    for (int k = (int)((n_walk - 1u) / LG_Q); k >= 0; k--) {
-        const uint32_t rel0 = (uint32_t)k * LG_Q, base = lo + rel0;
-        const uint32_t nbt = min((uint32_t)LG_Q, n_list - rel0);
-        // thread e of the workgroup owns entry e of the batch: the pre-sort slot its row lives at
-        const uint32_t sl = lg_feat_slot(v, tinfo, base + threadIdx.x, threadIdx.x < nbt, tx, ty);
-        uint64_t hitmask = 0ull;                                  // entries of the batch this wave has a partial row for (scalar)
-        if (wl > rel0) {
-            const uint32_t nhit = lg_feat_front(v, base + lane, hi, (float)g.wx0, (float)g.wy0, q0[wave], q1[wave], qid[wave], qpos[wave], lane);
-            if (have) lg_feat_stage_rows<CG>(features, C, c0, qid[wave], nhit, frow[wave], lane);
-            for (int j = (int)nhit - 1; j >= 0; j--) {
-                const float4 a = q0[wave][j], b = q1[wave][j];
-                const uint32_t e = (uint32_t)__builtin_amdgcn_readfirstlane((int)qpos[wave][j]);
-                float dx, dy;
-                const float power = lg_rec_power(a, b, pxf, pyf, dx, dy);
-                float G;
-                const float alpha = lg_feat_alpha<EXACT>(b.y, power, G);
-                float q = gA;
-                if (have) {
-                    const float4* fr = reinterpret_cast<const float4*>(&frow[wave][j * CG]);
+    auto stage = [&](uint32_t nhit) { if (have) lg_feat_stage_rows<CG>(features, C, c0, q.qid, nhit, frow[wave], g.lane); };
+    auto hit = [&](const LgBackHit& h, float& T, float& Sb, float (&p)[NV]) {
+        float qf = gA;
+        if (have) {
+            const float4* fr = reinterpret_cast<const float4*>(&frow[wave][h.j * CG]);
 #pragma unroll
-                    for (int u = 0; u < CG / 4; u++) {
-                        const float4 f = fr[u];
-                        q = fmaf(f.x, gv[4 * u], q); q = fmaf(f.y, gv[4 * u + 1], q);
-                        q = fmaf(f.z, gv[4 * u + 2], q); q = fmaf(f.w, gv[4 * u + 3], q);
-                    }
-                }
-                float p[NV] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-                float w;
-                const bool ok = lg_feature_bwd_step<EXACT>(rel0 + e + 1u <= last, power, G, alpha, dx, dy, q, Tfb, T, Sb, p, w);
-                if (__ballot(ok) == 0) continue;                  // no pixel of the wave took the entry
-                lg_feat_reduce<NV>(p, red[wave], &part[wave][e * LG_FEAT_PART_STRIDE(NV)], lane);
-                hitmask |= 1ull << e;
+            for (int u = 0; u < CG / 4; u++) {
+                const float4 f = fr[u];
+                qf = fmaf(f.x, gv[4 * u], qf); qf = fmaf(f.y, gv[4 * u + 1], qf);
+                qf = fmaf(f.z, gv[4 * u + 2], qf); qf = fmaf(f.w, gv[4 * u + 3], qf);
             }
         }
-        if (lane == 0u) wmask[wave] = hitmask;
-        __syncthreads();
-        if (threadIdx.x < nbt && sl < slot_cap) {
-            const uint32_t e = threadIdx.x;
-            float s[NV] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-                if ((wmask[u] >> e) & 1ull) {
-#pragma unroll
-                    for (int r = 0; r < NV; r++) s[r] += part[u][e * LG_FEAT_PART_STRIDE(NV) + r];
-                }
-            float4* dst = reinterpret_cast<float4*>(rows) + 3 * (size_t)sl;
-            if (ACCUM) {
-                const float4 r0 = dst[0];
-                const float2 r1 = *reinterpret_cast<const float2*>(dst + 1);
-                dst[0] = make_float4(r0.x + s[0], r0.y + s[1], r0.z + s[2], r0.w + s[3]);
-                *reinterpret_cast<float2*>(dst + 1) = make_float2(r1.x + s[4], r1.y + s[5]);
-            } else {
-                dst[0] = make_float4(s[0], s[1], s[2], s[3]);
-                dst[1] = make_float4(s[4], s[5], 0.0f, 0.0f);
-                dst[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            }
-        }
-        __syncthreads();                                          // (the next batch overwrites the queue, the partials and the masks)
-    }
+        float w;
+        return lg_feature_bwd_step<EXACT>(h.live, h.power, h.G, h.alpha, h.dx, h.dy, qf, Tfb, T, Sb, p, w);
+    };
+    auto sink = [&](uint32_t sl, const float (&t)[NV]) { lg_feat_store_moments<ACCUM>(rows, sl, t); };
+    lg_feat_walk_back<NV, EXACT>(v, tile, g, tinfo, bw, ACCUM ? tl : bw.n_list, q, mg, stage, hit, sink);
 }
 
 // Channels per chunk of the backward: the partial rows of a chunk, [num_rendered][cw] floats, stay within LG_FEAT_SCRATCH_BUDGET bytes

@@ -25,8 +25,8 @@ import torch
 
 from . import _lib
 from . import rasterizer as _rasterizer
-from .features import _check_features, _forward_then_blend
-from .rasterizer import _Call, _finish_forward, _GradSet, _prep
+from .features import _check_features, _forward_then_blend, _geometry_backward
+from .rasterizer import _finish_forward
 
 # The C ABI of include/lightgaussian_distortion.h, in header order: name -> (restype, argtypes).  tests/test_distortion_host.py holds
 # every entry against the header.
@@ -93,34 +93,19 @@ class _BlendGeometry(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out, grad_alpha, grad_color, _grad_radii=None, grad_dist=None, grad_median=None):
         lib = load()
-        features, bg, means3D, sh, colors, opac, scales, rots, cov, radii, geom, binning, img, state = ctx.saved_tensors
-        if features.shape[0] == 0:          # an empty model: nothing was rendered, and the empty inputs were not kept
-            z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=features.device)  # noqa: E731
-            return (z(0, features.shape[1]), None, z(0, 3), z(0, 3), z(0, 1)) + (None,) * 8
-        call = _Call(ctx.raster_settings, means3D, sh, colors, opac, scales, rots, cov, exact=False, opts=ctx.opts, differentiated=True)
-        dev, n, c = call.dev, call.N, int(features.shape[1])
-        grad_out, grad_alpha, grad_color = _prep(grad_out, dev), _prep(grad_alpha, dev), _prep(grad_color, dev)
-        grad_dist, grad_median = _prep(grad_dist, dev), _prep(grad_median, dev)
-        with torch.cuda.device(dev):
-            run = n > 0 and binning.numel() > 0       # (no Gaussians, or a forward that left no binning buffer: zero gradients)
-            new = torch.empty if run else torch.zeros
-            g = _GradSet(call, new=new)
-            g_feat = None
-            if ctx.needs_input_grad[0]:
-                # (without a gradient on the feature image the library writes no dL_dfeatures: zeros, plus the dL_dm column below)
-                g_feat = (new if grad_out is not None else torch.zeros)((n, c), dtype=torch.float32, device=dev)
-            if run:
-                g_m = torch.empty(n, dtype=torch.float32, device=dev)
-                scratch = _lib.scratch(lib.lg_backward_distortion_scratch_bytes(n, ctx.num_rendered, c), dev)
-                _lib.check(lib.lg_backward_distortion(
-                    C.byref(call.view), C.byref(call.g), _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(img),
-                    C.c_int64(ctx.num_rendered), _lib.ptr(grad_color), _lib.ptr(features), c, _lib.ptr(bg) if bg.numel() else None, _lib.ptr(grad_out),
-                    _lib.ptr(grad_alpha), *g.ptrs(), _lib.ptr(g_feat) if grad_out is not None else None, _column_ptr(features, ctx.m_column), c,
-                    _lib.ptr(state), _lib.ptr(grad_dist), _lib.ptr(grad_median), _lib.ptr(g_m), _lib.ptr(scratch), _lib.stream()))
-                if g_feat is not None:
-                    g_feat[:, ctx.m_column] += g_m
-        return (g_feat, None, g["means3D"], g["means2D"], g["opacity"], g["scales"], g["rotations"], g["cov3D"], g["shs"], g["colors"],
-                None, None, None)
+        features, state = ctx.saved_tensors[0], ctx.saved_tensors[13]
+
+        def launch(head, n, c, dev, grads, g_feat):
+            g_m = torch.empty(n, dtype=torch.float32, device=dev)
+            scratch = _lib.scratch(lib.lg_backward_distortion_scratch_bytes(n, ctx.num_rendered, c), dev)
+            _lib.check(lib.lg_backward_distortion(
+                *head, _lib.ptr(g_feat) if grads[0] is not None else None, _column_ptr(features, ctx.m_column), c, _lib.ptr(state),
+                _lib.ptr(grads[3]), _lib.ptr(grads[4]), _lib.ptr(g_m), _lib.ptr(scratch), _lib.stream()))
+            if g_feat is not None:
+                g_feat[:, ctx.m_column] += g_m
+
+        # (without a gradient on the feature image the library writes no dL_dfeatures: zeros, plus the dL_dm column)
+        return _geometry_backward(ctx, (grad_out, grad_alpha, grad_color, grad_dist, grad_median), launch, trailing=3, feat_zeros=True)
 
 
 def blend_geometry(raster_settings, features, *, m_column, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, shs=None,

@@ -104,6 +104,35 @@ class _BlendFeatures(torch.autograd.Function):
         return (d_feat,) + none
 
 
+def _geometry_backward(ctx, grads, launch, *, trailing, feat_zeros):
+    """The backward of _BlendFeaturesGeom and of distortion._BlendGeometry around their library call.  grads: the incoming gradients of
+    the feature image, alpha and colour, then the function's own.  trailing: the inputs behind the ten tensors, a None each.  feat_zeros:
+    dL/dfeatures is wanted (zeros) also without a gradient on the feature image.  launch(head, n, c, dev, grads, g_feat) runs when there
+    is something to walk: head holds the arguments lg_backward_features and lg_backward_distortion share (view .. dL_dshs_rest)."""
+    features, bg, means3D, sh, colors, opac, scales, rots, cov, radii, geom, binning, img = ctx.saved_tensors[:13]
+    if features.shape[0] == 0:          # an empty model: nothing was rendered, and the empty inputs were not kept
+        z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=features.device)  # noqa: E731
+        return (z(0, features.shape[1]), None, z(0, 3), z(0, 3), z(0, 1)) + (None,) * (5 + trailing)
+    call = _Call(ctx.raster_settings, means3D, sh, colors, opac, scales, rots, cov, exact=False, opts=ctx.opts, differentiated=True)
+    dev, n, c = call.dev, call.N, int(features.shape[1])
+    grads = [_prep(t, dev) for t in grads]
+    grad_out, grad_alpha, grad_color = grads[:3]
+    with torch.cuda.device(dev):
+        run = n > 0 and binning.numel() > 0       # (no Gaussians, or a forward that left no binning buffer: zero gradients)
+        new = torch.empty if run else torch.zeros
+        g = _GradSet(call, new=new)
+        g_feat = None
+        if ctx.needs_input_grad[0] and (grad_out is not None or feat_zeros):
+            g_feat = (new if grad_out is not None else torch.zeros)((n, c), dtype=torch.float32, device=dev)
+        if run:
+            head = (C.byref(call.view), C.byref(call.g), _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(img),
+                    C.c_int64(ctx.num_rendered), _lib.ptr(grad_color), _lib.ptr(features), c, _lib.ptr(bg) if bg.numel() else None,
+                    _lib.ptr(grad_out), _lib.ptr(grad_alpha), *g.ptrs())
+            launch(head, n, c, dev, grads, g_feat)
+    return (g_feat, None, g["means3D"], g["means2D"], g["opacity"], g["scales"], g["rotations"], g["cov3D"], g["shs"],
+            g["colors"]) + (None,) * trailing
+
+
 class _BlendFeaturesGeom(torch.autograd.Function):
     """blend_features(geometry_grad=True): a DIFFERENTIATED forward that keeps the img buffer, as _RasterizeGaussians does; out, alpha
     and color are differentiable, radii is not.  The backward is one lg_backward_features call."""
@@ -121,26 +150,12 @@ class _BlendFeaturesGeom(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out, grad_alpha, grad_color, _grad_radii=None):
         lib = _lib.load()
-        features, bg, means3D, sh, colors, opac, scales, rots, cov, radii, geom, binning, img = ctx.saved_tensors
-        if features.shape[0] == 0:          # an empty model: nothing was rendered, and the empty inputs were not kept
-            z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=features.device)  # noqa: E731
-            return (z(0, features.shape[1]), None, z(0, 3), z(0, 3), z(0, 1)) + (None,) * 7
-        call = _Call(ctx.raster_settings, means3D, sh, colors, opac, scales, rots, cov, exact=False, opts=ctx.opts, differentiated=True)
-        dev, n, c = call.dev, call.N, int(features.shape[1])
-        grad_out, grad_alpha, grad_color = _prep(grad_out, dev), _prep(grad_alpha, dev), _prep(grad_color, dev)
-        with torch.cuda.device(dev):
-            run = n > 0 and binning.numel() > 0       # (no Gaussians, or a forward that left no binning buffer: zero gradients)
-            new = torch.empty if run else torch.zeros
-            g = _GradSet(call, new=new)
-            g_feat = new((n, c), dtype=torch.float32, device=dev) if (ctx.needs_input_grad[0] and grad_out is not None) else None
-            if run:
-                scratch = _lib.scratch(lib.lg_backward_features_scratch_bytes(n, ctx.num_rendered, c), dev)
-                _lib.check(lib.lg_backward_features(
-                    C.byref(call.view), C.byref(call.g), _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(img),
-                    C.c_int64(ctx.num_rendered), _lib.ptr(grad_color), _lib.ptr(features), c, _lib.ptr(bg) if bg.numel() else None, _lib.ptr(grad_out),
-                    _lib.ptr(grad_alpha), *g.ptrs(), _lib.ptr(g_feat), _lib.ptr(scratch), _lib.stream()))
-        return (g_feat, None, g["means3D"], g["means2D"], g["opacity"], g["scales"], g["rotations"], g["cov3D"], g["shs"], g["colors"],
-                None, None)
+
+        def launch(head, n, c, dev, _grads, g_feat):
+            scratch = _lib.scratch(lib.lg_backward_features_scratch_bytes(n, ctx.num_rendered, c), dev)
+            _lib.check(lib.lg_backward_features(*head, _lib.ptr(g_feat), _lib.ptr(scratch), _lib.stream()))
+
+        return _geometry_backward(ctx, (grad_out, grad_alpha, grad_color), launch, trailing=2, feat_zeros=False)
 
 
 def blend_features(raster_settings, features, *, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None, shs=None,
