@@ -166,6 +166,18 @@ PROTOTYPES = {
 EXPORTS = list(PROTOTYPES)
 
 _lib = None
+_BOUND = []     # the prototype tables bind() has set
+
+
+def bind(lib, prototypes):
+    """`lib` with the restype / argtypes of a prototype table (name -> (restype, argtypes)) set on it, once per table: the table of
+    this module by load(), the table of an extension header by the load() of its module."""
+    if not any(t is prototypes for t in _BOUND):
+        for name, (restype, argtypes) in prototypes.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, list(argtypes)
+        _BOUND.append(prototypes)
+    return lib
 
 
 def load():
@@ -181,10 +193,7 @@ def load():
     if lib.lg_abi_version() != ABI_VERSION:         # (ctypes' default prototype, int f(void), is this function's)
         raise RuntimeError(f"{LIB_PATH} reports ABI {lib.lg_abi_version()}, this binding needs {ABI_VERSION}: rebuild the library "
                            "(python -c 'import __graft_entry__ as g; g.build()')")
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, list(argtypes)
-    _lib = lib
+    _lib = bind(lib, PROTOTYPES)
     return lib
 
 

@@ -23,6 +23,7 @@
 
 #include "lg_host.h"
 #include "lg_adam_rows.h"
+#include "lg_rows.h"              // lg_f4
 
 // LG_ADAM_MAX_TENSORS (8) and LG_ADAM_SPAN (elements per workgroup: 256 lanes x LG_ADAM_SPAN / 1024 dwordx4 per stream; 4096 by
 // measurement on the MI355X, EXPERIMENTS "Adam step"; -DLG_ADAM_SPAN=... for an A/B build) come from include/lightgaussian.h.
@@ -34,7 +35,6 @@
 #define LG_ADAM_VEC (LG_ADAM_SPAN / (LG_ADAM_THREADS * 4))
 static_assert(LG_ADAM_SPAN % (LG_ADAM_THREADS * 4) == 0 && LG_ADAM_VEC >= 1, "a span is a whole number of dwordx4 per lane");
 
-typedef float lg_adam_f4 __attribute__((ext_vector_type(4)));
 
 struct LgAdamTable {
     float* param[LG_ADAM_MAX_TENSORS];
@@ -142,22 +142,22 @@ __device__ __forceinline__ void lg_adam_span(const LgAdamTable& a, const LgAdamR
             for (int u = 0; u < LG_ADAM_VEC; u++) vis[u] = 0xFu;
             if (mask) lg_adam_span_vis(mask, rem, row_len, rcp, thr, vis);
         }
-        lg_adam_f4 p[LG_ADAM_VEC], g[LG_ADAM_VEC], m[LG_ADAM_VEC], v[LG_ADAM_VEC];
+        lg_f4 p[LG_ADAM_VEC], g[LG_ADAM_VEC], m[LG_ADAM_VEC], v[LG_ADAM_VEC];
 #pragma unroll
         for (int u = 0; u < LG_ADAM_VEC; u++) {
             if constexpr (ROWS) {
-                p[u] = g[u] = m[u] = v[u] = lg_adam_f4{ 0.0f, 0.0f, 0.0f, 0.0f };
+                p[u] = g[u] = m[u] = v[u] = lg_f4{ 0.0f, 0.0f, 0.0f, 0.0f };
                 if (vis[u] == 0u) continue;
             }
             const int64_t i = base + (int64_t)(u * LG_ADAM_THREADS + (int)threadIdx.x) * 4;
 #if LG_ADAM_NT_GRAD
-            g[u] = __builtin_nontemporal_load((const lg_adam_f4*)(G + i));
+            g[u] = __builtin_nontemporal_load((const lg_f4*)(G + i));
 #else
-            g[u] = *(const lg_adam_f4*)(G + i);
+            g[u] = *(const lg_f4*)(G + i);
 #endif
-            p[u] = *(const lg_adam_f4*)(P + i);
-            m[u] = *(const lg_adam_f4*)(M + i);
-            v[u] = *(const lg_adam_f4*)(V + i);
+            p[u] = *(const lg_f4*)(P + i);
+            m[u] = *(const lg_f4*)(M + i);
+            v[u] = *(const lg_f4*)(V + i);
         }
         __builtin_amdgcn_sched_barrier(0);              // every load of the span is in flight before the first dependent instruction
 #pragma unroll
@@ -178,9 +178,9 @@ __device__ __forceinline__ void lg_adam_span(const LgAdamTable& a, const LgAdamR
                     lg_adam_element<DECOUPLED>(pe[c], ge[c], me[c], ve[c], decay, step_size, bc2_sqrt, om_b1, b2, om_b2, eps);
                 }
             }
-            *(lg_adam_f4*)(P + i) = lg_adam_f4{ pe[0], pe[1], pe[2], pe[3] };
-            *(lg_adam_f4*)(M + i) = lg_adam_f4{ me[0], me[1], me[2], me[3] };
-            *(lg_adam_f4*)(V + i) = lg_adam_f4{ ve[0], ve[1], ve[2], ve[3] };
+            *(lg_f4*)(P + i) = lg_f4{ pe[0], pe[1], pe[2], pe[3] };
+            *(lg_f4*)(M + i) = lg_f4{ me[0], me[1], me[2], me[3] };
+            *(lg_f4*)(V + i) = lg_f4{ ve[0], ve[1], ve[2], ve[3] };
         }
     } else {
         const int n = (int)(left < LG_ADAM_SPAN ? left : LG_ADAM_SPAN);

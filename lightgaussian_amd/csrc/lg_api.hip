@@ -6,11 +6,14 @@
 //   lg_host.h        error strings, optional hipEvent profiler, scratch carving (GeomView / ImgView / BinView)
 //   lg_wave.h        wave64 primitives (DPP reductions; lg_wave_scan_incl: the one wave prefix sum; lg_wave_all_max / _or; lg_block_scan_put / _get: the
 //                    workgroup scan around the caller's barrier; lg_wave_lds_sync: the LDS hand-over inside a wave)
+//   lg_rows.h        the four-rows-per-lane walk of the per-Gaussian row kernels (lg_rows4_walk / _load / _store: dwordx4, or dwords for a tail and
+//                    for pointers off 16 bytes), its grid size and row limit; lg_f4, the float vector type of every kernel header
 //   lg_preprocess.h  K1 lg_preprocess<RAW, DIRECT, AA>, K8+K9 lg_preprocess_bwd<RAW, JAC, AA> (AA: LG_FLAG_ANTIALIAS)   (per Gaussian, HBM-bound); lg_k9_*: K9's read side, shared with lg_camera.h;
 //                    lg_sh_rows_flush: how dL/dSH rows leave LDS (K9 and lg_sh_grad_from_rgb_kernel)
 //   lg_binning.h     K2 lg_scan_blocks, K3 lg_duplicate, lg_tile_sort / _long (second sort stage), lg_tile_ranges (one-stage cross-check only),
 //                    lg_work_order (K2-K5 all hand-written; lg_sort.h = K4)
-//   lg_loss.h        lg_loss_fwd / lg_loss_bwd: fused L1 + SSIM of the training step             (a wave per 64-column strip, register ring)
+//   lg_loss.h        lg_loss_fwd / lg_loss_bwd: fused L1 + SSIM of the training step             (a wave per 64-column strip, register ring);
+//                    lg_mean_finalize<Q>: the one ordered sum of per-wave partials in double (also lg_normal_loss's)
 //   lg_prune.h       lg_select_pass, lg_v_imp_score_kernel, lg_prune_mask_kernel: device-resident prune epilogue (radix selects)
 //   lg_knn.h         distCUDA2 (simple-knn): exact 3-nearest-neighbour mean squared distance on a multi-level uniform grid
 //   lg_compact.h     lg_compact_plan / lg_compact_rows: one scan + one launch compacting all Gaussian tensors after a prune
@@ -49,6 +52,7 @@
 // BackwardOpts for a backward; lg_sort_error_word (lg_sort.h) for a sort without view counters.
 #include "lg_host.h"
 #include "lg_wave.h"
+#include "lg_rows.h"
 #include "lg_preprocess.h"
 #include "lg_binning.h"
 #include "lg_blend.h"
@@ -1516,13 +1520,12 @@ extern "C" int lg_mcmc_rows(int32_t N, int64_t N_out, int32_t n, const int32_t* 
 }
 
 // ---- 3D smoothing filter (lg_filter3d.h) ----
-#define LG_FILTER3D_MAX_ROWS (1 << 30)
 extern "C" size_t lg_filter3d_scratch_bytes(int32_t N) { (void)N; return align_up((size_t)LG_F3D_MAX_WGS * sizeof(float)); }
 
 extern "C" int lg_filter3d_update(int32_t N, const float* means3D, int32_t V, const lg_filter_camera* cameras, float* filter3d, uint8_t* seen,
                                   void* scratch, uint32_t flags, void* stream_p)
 {
-    if (N < 0 || N >= LG_FILTER3D_MAX_ROWS) return fail(LG_ERR_INVALID_ARGUMENT, "lg_filter3d_update: N outside [0, 2^30)");
+    if (N < 0 || N >= LG_ROWS_MAX) return fail(LG_ERR_INVALID_ARGUMENT, "lg_filter3d_update: N outside [0, 2^30)");
     if (V < 1) return fail(LG_ERR_INVALID_ARGUMENT, "lg_filter3d_update: V < 1 (the filter needs at least one camera)");
     if (!means3D || !cameras || !filter3d || !scratch) return fail(LG_ERR_INVALID_ARGUMENT, "lg_filter3d_update: null means3D / cameras / filter3d / scratch");
     if ((((uintptr_t)means3D | (uintptr_t)cameras | (uintptr_t)filter3d | (uintptr_t)scratch) & 3) != 0)
@@ -1547,7 +1550,7 @@ extern "C" int lg_filter3d_update(int32_t N, const float* means3D, int32_t V, co
 
 static int lg_filter3d_check(const char* who, int32_t N, std::initializer_list<const void*> ptrs, bool* vec)
 {
-    if (N < 0 || N >= LG_FILTER3D_MAX_ROWS) return refuse(who, "N outside [0, 2^30)");
+    if (N < 0 || N >= LG_ROWS_MAX) return refuse(who, "N outside [0, 2^30)");
     uintptr_t all = 0;
     for (const void* p : ptrs) {
         if (!p) return refuse(who, "null tensor");
@@ -1567,7 +1570,7 @@ extern "C" int lg_filter3d_apply(int32_t N, const float* scaling, const float* o
     hipStream_t stream = (hipStream_t)stream_p;
     const bool prof = flags & LG_FLAG_PROFILE;
     ProfScope ps(prof, "filter3d_apply", stream);
-    const unsigned wgs = (unsigned)((((int64_t)N + 3) / 4 + LG_F3D_THREADS - 1) / LG_F3D_THREADS);
+    const unsigned wgs = lg_rows4_wgs(N, LG_F3D_THREADS);
     filter3d_apply_kernel(flags & LG_FILTER3D_RAW)<<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, out_scaling, out_opacity);
     KLAUNCHED("lg_filter3d_apply_kernel");
     return LG_OK;
@@ -1582,7 +1585,7 @@ extern "C" int lg_filter3d_apply_bwd(int32_t N, const float* scaling, const floa
     hipStream_t stream = (hipStream_t)stream_p;
     const bool prof = flags & LG_FLAG_PROFILE;
     ProfScope ps(prof, "filter3d_apply_bwd", stream);
-    const unsigned wgs = (unsigned)((((int64_t)N + 3) / 4 + LG_F3D_THREADS - 1) / LG_F3D_THREADS);
+    const unsigned wgs = lg_rows4_wgs(N, LG_F3D_THREADS);
     filter3d_apply_bwd_kernel(flags & LG_FILTER3D_RAW)<<<wgs, LG_F3D_THREADS, 0, stream>>>(N, vec, scaling, opacity, filter3d, dL_dout_scaling, dL_dout_opacity,
                                                                                            dL_dscaling, dL_dopacity);
     KLAUNCHED("lg_filter3d_apply_bwd_kernel");
@@ -1590,7 +1593,6 @@ extern "C" int lg_filter3d_apply_bwd(int32_t N, const float* scaling, const floa
 }
 
 // ---- normals and the depth-normal consistency loss (lg_normals.h, include/lightgaussian_normals.h) ----
-#define LG_NORMALS_MAX_ROWS (1 << 30)
 struct NamedPtr { const char* name; const void* p; };
 // null and alignment checks that name the argument; all16: every pointer is 16-byte aligned
 static int normals_ptrs(const char* who, std::initializer_list<NamedPtr> ptrs, bool* all16 = nullptr)
@@ -1613,20 +1615,19 @@ static int normals_image(const char* who, int32_t H, int32_t W, float tanfovx, f
     if (tanfovy != tanfovy) return refuse(who, "tanfovy is NaN");
     return LG_OK;
 }
-static unsigned normals_rows_wgs(int32_t N) { return (unsigned)((((int64_t)N + 3) / 4 + LG_NRM_THREADS - 1) / LG_NRM_THREADS); }
 
 extern "C" int lg_normal_rows(int32_t N, const float* xyz, const float* scaling, const float* rotation, const float* viewmatrix, float* rows,
                               uint32_t flags, void* stream_p)
 {
     const char* who = "lg_normal_rows";
-    if (N < 0 || N >= LG_NORMALS_MAX_ROWS) return refuse(who, "N outside [0, 2^30)");
+    if (N < 0 || N >= LG_ROWS_MAX) return refuse(who, "N outside [0, 2^30)");
     bool vec = false;
     int rc = normals_ptrs(who, { { "xyz", xyz }, { "scaling", scaling }, { "rotation", rotation }, { "rows", rows } }, &vec);
     if (rc == LG_OK) rc = normals_ptrs(who, { { "viewmatrix", viewmatrix } });
     if (rc != LG_OK || N == 0) return rc;
     hipStream_t stream = (hipStream_t)stream_p;
     ProfScope ps(flags & LG_FLAG_PROFILE, "normal_rows", stream);
-    lg_normal_rows_kernel<<<normals_rows_wgs(N), LG_NRM_THREADS, 0, stream>>>(N, vec, xyz, scaling, rotation, viewmatrix, rows);
+    lg_normal_rows_kernel<<<lg_rows4_wgs(N, LG_NRM_THREADS), LG_NRM_THREADS, 0, stream>>>(N, vec, xyz, scaling, rotation, viewmatrix, rows);
     KLAUNCHED("lg_normal_rows_kernel");
     return LG_OK;
 }
@@ -1635,7 +1636,7 @@ extern "C" int lg_normal_rows_bwd(int32_t N, const float* xyz, const float* scal
                                   const float* dL_drows, float* dL_dxyz, float* dL_drotation, uint32_t flags, void* stream_p)
 {
     const char* who = "lg_normal_rows_bwd";
-    if (N < 0 || N >= LG_NORMALS_MAX_ROWS) return refuse(who, "N outside [0, 2^30)");
+    if (N < 0 || N >= LG_ROWS_MAX) return refuse(who, "N outside [0, 2^30)");
     bool vec = false;
     int rc = normals_ptrs(who, { { "xyz", xyz }, { "scaling", scaling }, { "rotation", rotation }, { "dL_drows", dL_drows }, { "dL_dxyz", dL_dxyz },
                                  { "dL_drotation", dL_drotation } }, &vec);
@@ -1643,7 +1644,7 @@ extern "C" int lg_normal_rows_bwd(int32_t N, const float* xyz, const float* scal
     if (rc != LG_OK || N == 0) return rc;
     hipStream_t stream = (hipStream_t)stream_p;
     ProfScope ps(flags & LG_FLAG_PROFILE, "normal_rows_bwd", stream);
-    lg_normal_rows_bwd_kernel<<<normals_rows_wgs(N), LG_NRM_THREADS, 0, stream>>>(N, vec, xyz, scaling, rotation, viewmatrix, dL_drows, dL_dxyz, dL_drotation);
+    lg_normal_rows_bwd_kernel<<<lg_rows4_wgs(N, LG_NRM_THREADS), LG_NRM_THREADS, 0, stream>>>(N, vec, xyz, scaling, rotation, viewmatrix, dL_drows, dL_dxyz, dL_drotation);
     KLAUNCHED("lg_normal_rows_bwd_kernel");
     return LG_OK;
 }
@@ -1703,8 +1704,8 @@ extern "C" int lg_normal_loss(int32_t H, int32_t W, const float* normal_map, con
     }
     {
         ProfScope ps(prof, "normal_loss_reduce", stream);
-        lg_normal_loss_finalize<<<1, 256, 0, stream>>>((int)(grid.x * grid.y), 1.0 / ((double)H * W), partials, loss);
-        KLAUNCHED("lg_normal_loss_finalize");
+        lg_mean_finalize<1><<<1, 256, 0, stream>>>((int)(grid.x * grid.y), 1.0 / ((double)H * W), partials, loss);
+        KLAUNCHED("lg_mean_finalize");
     }
     return LG_OK;
 }
@@ -1801,16 +1802,16 @@ extern "C" int lg_loss_forward(int32_t C, int32_t H, int32_t W, const float* img
         const int blocks = (int)std::min<size_t>((n + 1023) / 1024, (size_t)grid.x * grid.y * grid.z);   // partials has one slot per tile
         lg_l1_fwd<<<blocks, 256, 0, stream>>>(n, img, gt, lv.partials);
         KCHECK("lg_l1_fwd");
-        lg_loss_finalize<<<1, 256, 0, stream>>>(blocks, 1.0 / (double)n, lv.partials, out_l1_ssim);
-        KCHECK("lg_loss_finalize");
+        lg_mean_finalize<2><<<1, 256, 0, stream>>>(blocks, 1.0 / (double)n, (const float*)lv.partials, out_l1_ssim);
+        KCHECK("lg_mean_finalize");
         return LG_OK;
     }
     {
         ProfScope ps(prof, "loss_fwd", stream);
         lg_loss_fwd<<<grid, LG_LOSS_STRIP, 0, stream>>>(H, W, img, gt, lv.dmu1, lv.dsig1, lv.dsig12, lv.partials);
         KCHECK("lg_loss_fwd");
-        lg_loss_finalize<<<1, 256, 0, stream>>>((int)(grid.x * grid.y * grid.z), 1.0 / ((double)C * H * W), lv.partials, out_l1_ssim);
-        KCHECK("lg_loss_finalize");
+        lg_mean_finalize<2><<<1, 256, 0, stream>>>((int)(grid.x * grid.y * grid.z), 1.0 / ((double)C * H * W), (const float*)lv.partials, out_l1_ssim);
+        KCHECK("lg_mean_finalize");
     }
     return LG_OK;
 }

@@ -14,9 +14,8 @@
 //                              order (<= 8 KB from L2) and gives the unseen rows of its stride that maximum, or 0 when no row was seen.
 //                              A maximum of floats is exact, so the order cannot change a bit; it is fixed all the same.
 //   lg_filter3d_apply_kernel / lg_filter3d_apply_bwd_kernel <RAW>
-//                              elementwise, one lane per FOUR consecutive rows: 48 bytes of scaling rows are three dwordx4, opacity,
-//                              filter and the gradients one dwordx4 each, all loads issued before the arithmetic; a tensor set with
-//                              a pointer off 16 bytes and the last N % 4 rows go one dword at a time (lg_densify.h's row pattern).
+//                              elementwise, one lane per FOUR consecutive rows, the walk of lg_rows.h: 48 bytes of scaling rows are
+//                              three dwordx4, opacity, filter and the gradients one dwordx4 each, all loads issued before the arithmetic.
 // No atomics, no memset, no host read-back, no scratch memory; results are bit-identical from run to run.
 //
 // Apply, per row (f = the row's filter; f == 0: the row is copied bit for bit by an explicit branch), float32, nothing contracted:
@@ -33,6 +32,7 @@
 
 #include "lg_host.h"
 #include "lg_preprocess.h"      // lg_sigmoid
+#include "lg_rows.h"
 
 #define LG_F3D_THREADS 256
 #define LG_F3D_CHUNK 64                 // cameras per LDS stage (80 bytes each: 5 KB)
@@ -40,13 +40,10 @@
 static_assert(sizeof(lg_filter_camera) == 80, "lg_filter_camera is 80 bytes");
 static_assert(LG_F3D_CHUNK <= LG_F3D_THREADS, "one lane stages one camera");
 
-typedef float lg_f3d_f4 __attribute__((ext_vector_type(4)));
-
 // maximum over the workgroup's 256 lanes, in every lane (ws: 4 floats of LDS)
 __device__ __forceinline__ float lg_f3d_wg_max(float m, float* ws)
 {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
+    m = lg_wave_all_max(m);
     __syncthreads();                                    // ws may still be read from an earlier call
     if ((threadIdx.x & 63u) == 0u) ws[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -164,38 +161,20 @@ __device__ __forceinline__ void lg_filter3d_row_bwd(const float r[3], float o, f
     }
 }
 
-// one lane per four consecutive rows.  vec (uniform): every pointer is 16-byte aligned
+// one lane per four consecutive rows (lg_rows.h).  vec (uniform): every pointer is 16-byte aligned
 template <bool RAW>
 __global__ void __launch_bounds__(LG_F3D_THREADS)
 lg_filter3d_apply_kernel(int N, int vec, const float* __restrict__ scaling, const float* __restrict__ opacity, const float* __restrict__ filter3d,
                          float* __restrict__ out_scaling, float* __restrict__ out_opacity)
 {
-    const size_t q = (size_t)blockIdx.x * LG_F3D_THREADS + threadIdx.x;
-    const size_t i0 = 4 * q;
-    if (i0 >= (size_t)N) return;
-    if (vec && i0 + 4 <= (size_t)N) {
-        const lg_f3d_f4 a = *(const lg_f3d_f4*)(scaling + 3 * i0), b = *(const lg_f3d_f4*)(scaling + 3 * i0 + 4),
-                        c = *(const lg_f3d_f4*)(scaling + 3 * i0 + 8);
-        const lg_f3d_f4 o = *(const lg_f3d_f4*)(opacity + i0), f = *(const lg_f3d_f4*)(filter3d + i0);
-        const float r[4][3] = { { a.x, a.y, a.z }, { a.w, b.x, b.y }, { b.z, b.w, c.x }, { c.y, c.z, c.w } };
-        const float oe[4] = { o.x, o.y, o.z, o.w }, fe[4] = { f.x, f.y, f.z, f.w };
-        float ro[4][3], oo[4];
+    lg_rows4_walk<LG_F3D_THREADS>(N, vec, [&](size_t i0, auto path) {
+        float r[4][3], o[4][1], f[4][1], ro[4][3], oo[4][1];
+        lg_rows4_load(path, scaling, i0, r); lg_rows4_load(path, opacity, i0, o); lg_rows4_load(path, filter3d, i0, f);
 #pragma unroll
-        for (int k = 0; k < 4; k++) lg_filter3d_row<RAW>(r[k], oe[k], fe[k], ro[k], oo[k]);
-        *(lg_f3d_f4*)(out_scaling + 3 * i0) = lg_f3d_f4{ ro[0][0], ro[0][1], ro[0][2], ro[1][0] };
-        *(lg_f3d_f4*)(out_scaling + 3 * i0 + 4) = lg_f3d_f4{ ro[1][1], ro[1][2], ro[2][0], ro[2][1] };
-        *(lg_f3d_f4*)(out_scaling + 3 * i0 + 8) = lg_f3d_f4{ ro[2][2], ro[3][0], ro[3][1], ro[3][2] };
-        *(lg_f3d_f4*)(out_opacity + i0) = lg_f3d_f4{ oo[0], oo[1], oo[2], oo[3] };
-    } else {
-        const size_t i1 = i0 + 4 <= (size_t)N ? i0 + 4 : (size_t)N;
-        for (size_t i = i0; i < i1; i++) {
-            const float r[3] = { scaling[3 * i], scaling[3 * i + 1], scaling[3 * i + 2] };
-            float ro[3], oo;
-            lg_filter3d_row<RAW>(r, opacity[i], filter3d[i], ro, oo);
-            out_scaling[3 * i] = ro[0]; out_scaling[3 * i + 1] = ro[1]; out_scaling[3 * i + 2] = ro[2];
-            out_opacity[i] = oo;
-        }
-    }
+        for (int k = 0; k < 4; k++)
+            if (k < lg_rows4_live(path)) lg_filter3d_row<RAW>(r[k], o[k][0], f[k][0], ro[k], oo[k][0]);
+        lg_rows4_store(path, out_scaling, i0, ro); lg_rows4_store(path, out_opacity, i0, oo);
+    });
 }
 
 template <bool RAW>
@@ -204,34 +183,13 @@ lg_filter3d_apply_bwd_kernel(int N, int vec, const float* __restrict__ scaling, 
                              const float* __restrict__ filter3d, const float* __restrict__ g_scaling, const float* __restrict__ g_opacity,
                              float* __restrict__ d_scaling, float* __restrict__ d_opacity)
 {
-    const size_t q = (size_t)blockIdx.x * LG_F3D_THREADS + threadIdx.x;
-    const size_t i0 = 4 * q;
-    if (i0 >= (size_t)N) return;
-    if (vec && i0 + 4 <= (size_t)N) {
-        const lg_f3d_f4 a = *(const lg_f3d_f4*)(scaling + 3 * i0), b = *(const lg_f3d_f4*)(scaling + 3 * i0 + 4),
-                        c = *(const lg_f3d_f4*)(scaling + 3 * i0 + 8);
-        const lg_f3d_f4 ga = *(const lg_f3d_f4*)(g_scaling + 3 * i0), gb = *(const lg_f3d_f4*)(g_scaling + 3 * i0 + 4),
-                        gc = *(const lg_f3d_f4*)(g_scaling + 3 * i0 + 8);
-        const lg_f3d_f4 o = *(const lg_f3d_f4*)(opacity + i0), f = *(const lg_f3d_f4*)(filter3d + i0), go = *(const lg_f3d_f4*)(g_opacity + i0);
-        const float r[4][3] = { { a.x, a.y, a.z }, { a.w, b.x, b.y }, { b.z, b.w, c.x }, { c.y, c.z, c.w } };
-        const float gr[4][3] = { { ga.x, ga.y, ga.z }, { ga.w, gb.x, gb.y }, { gb.z, gb.w, gc.x }, { gc.y, gc.z, gc.w } };
-        const float oe[4] = { o.x, o.y, o.z, o.w }, fe[4] = { f.x, f.y, f.z, f.w }, ge[4] = { go.x, go.y, go.z, go.w };
-        float dr[4][3], dq[4];
+    lg_rows4_walk<LG_F3D_THREADS>(N, vec, [&](size_t i0, auto path) {
+        float r[4][3], gr[4][3], o[4][1], f[4][1], go[4][1], dr[4][3], dq[4][1];
+        lg_rows4_load(path, scaling, i0, r); lg_rows4_load(path, g_scaling, i0, gr);
+        lg_rows4_load(path, opacity, i0, o); lg_rows4_load(path, filter3d, i0, f); lg_rows4_load(path, g_opacity, i0, go);
 #pragma unroll
-        for (int k = 0; k < 4; k++) lg_filter3d_row_bwd<RAW>(r[k], oe[k], fe[k], gr[k], ge[k], dr[k], dq[k]);
-        *(lg_f3d_f4*)(d_scaling + 3 * i0) = lg_f3d_f4{ dr[0][0], dr[0][1], dr[0][2], dr[1][0] };
-        *(lg_f3d_f4*)(d_scaling + 3 * i0 + 4) = lg_f3d_f4{ dr[1][1], dr[1][2], dr[2][0], dr[2][1] };
-        *(lg_f3d_f4*)(d_scaling + 3 * i0 + 8) = lg_f3d_f4{ dr[2][2], dr[3][0], dr[3][1], dr[3][2] };
-        *(lg_f3d_f4*)(d_opacity + i0) = lg_f3d_f4{ dq[0], dq[1], dq[2], dq[3] };
-    } else {
-        const size_t i1 = i0 + 4 <= (size_t)N ? i0 + 4 : (size_t)N;
-        for (size_t i = i0; i < i1; i++) {
-            const float r[3] = { scaling[3 * i], scaling[3 * i + 1], scaling[3 * i + 2] };
-            const float gr[3] = { g_scaling[3 * i], g_scaling[3 * i + 1], g_scaling[3 * i + 2] };
-            float dr[3], dq;
-            lg_filter3d_row_bwd<RAW>(r, opacity[i], filter3d[i], gr, g_opacity[i], dr, dq);
-            d_scaling[3 * i] = dr[0]; d_scaling[3 * i + 1] = dr[1]; d_scaling[3 * i + 2] = dr[2];
-            d_opacity[i] = dq;
-        }
-    }
+        for (int k = 0; k < 4; k++)
+            if (k < lg_rows4_live(path)) lg_filter3d_row_bwd<RAW>(r[k], o[k][0], f[k][0], gr[k], go[k][0], dr[k], dq[k][0]);
+        lg_rows4_store(path, d_scaling, i0, dr); lg_rows4_store(path, d_opacity, i0, dq);
+    });
 }

@@ -206,20 +206,34 @@ lg_loss_fwd(int H, int W, const float* __restrict__ img, const float* __restrict
     if (lane == 63) partials[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = make_float2(l1, ss);
 }
 
-// out[0] = mean |x-y|, out[1] = mean ssim_map; one block, fixed summation order, double accumulation
+// out[q] = (sum over the n partials of their q-th float) * inv_count, q < Q: one block, fixed summation order, double accumulation.
+// Q = 2: mean |x-y| and mean ssim_map of the loss; Q = 1: the normal consistency loss (lg_normals.h)
+template <int Q>
 __global__ void __launch_bounds__(256)
-lg_loss_finalize(int nblocks, double inv_count, const float2* __restrict__ partials, float* __restrict__ out)
+lg_mean_finalize(int n, double inv_count, const float* __restrict__ partials, float* __restrict__ out)
 {
-    __shared__ double s0[256], s1[256];
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 256) { const float2 p = partials[i]; a += (double)p.x; b += (double)p.y; }
-    s0[threadIdx.x] = a; s1[threadIdx.x] = b;
+    typedef float part_t __attribute__((ext_vector_type(Q)));
+    __shared__ double s[Q][256];
+    double a[Q] = {};
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const part_t p = ((const part_t*)partials)[i];
+#pragma unroll
+        for (int q = 0; q < Q; q++) a[q] += (double)p[q];
+    }
+#pragma unroll
+    for (int q = 0; q < Q; q++) s[q][threadIdx.x] = a[q];
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { s0[threadIdx.x] += s0[threadIdx.x + s]; s1[threadIdx.x] += s1[threadIdx.x + s]; }
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+#pragma unroll
+            for (int q = 0; q < Q; q++) s[q][threadIdx.x] += s[q][threadIdx.x + h];
+        }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { out[0] = (float)(s0[0] * inv_count); out[1] = (float)(s1[0] * inv_count); }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < Q; q++) out[q] = (float)(s[q][0] * inv_count);
+    }
 }
 
 // backward: dL/dimg = g_l1 * sign(x - y) / n  +  g_ssim / n * [ G*dmu1 + 2 x G*dsig1 + y G*dsig12 ]

@@ -4,6 +4,7 @@
 
 #include "lg_host.h"
 #include "lg_wave.h"
+#include "lg_rows.h"              // lg_f4
 
 // ------------------------------------------------------------------------------------------------
 // K1: preprocess.  One wave per workgroup, 64 consecutive Gaussians.  Default (DIRECT): every visible lane reads its own SH row with
@@ -365,11 +366,10 @@ __device__ __forceinline__ void lg_k9_jac_row(const float* shjac, int i, float (
 template <bool NT>
 __device__ __forceinline__ void lg_sh_rows_flush(const float* sh_rows, float* dst, int nfl, uint32_t lane)
 {
-    typedef float lg_f4v __attribute__((ext_vector_type(4)));
     if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
         const int nvec = nfl >> 2;
         for (int q = (int)lane; q < nvec; q += LG_PP) {
-            if (NT) __builtin_nontemporal_store(reinterpret_cast<const lg_f4v*>(sh_rows)[q], reinterpret_cast<lg_f4v*>(dst) + q);
+            if (NT) __builtin_nontemporal_store(reinterpret_cast<const lg_f4*>(sh_rows)[q], reinterpret_cast<lg_f4*>(dst) + q);
             else reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(sh_rows)[q];
         }
         for (int f = (nvec << 2) + (int)lane; f < nfl; f += LG_PP) dst[f] = sh_rows[f];

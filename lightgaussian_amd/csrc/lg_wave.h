@@ -65,6 +65,12 @@ __device__ __forceinline__ uint32_t lg_wave_all_max(uint32_t v)
     for (int sh = 32; sh > 0; sh >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, sh));
     return v;
 }
+__device__ __forceinline__ float lg_wave_all_max(float v)
+{
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) v = fmaxf(v, __shfl_xor(v, sh, 64));
+    return v;
+}
 __device__ __forceinline__ uint32_t lg_wave_all_or(uint32_t v)
 {
 #pragma unroll

@@ -37,18 +37,9 @@ PROTOTYPES = {
     "lg_backward_distortion_scratch_bytes": (sz, (i32, i64, i32)),
     "lg_backward_distortion": (C.c_int, (vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, vp) + (vp,) * 9 + (vp, vp, i32, vp, vp, vp, vp, vp, vp)),
 }
-_BOUND = []
-
-
 def load():
     """The library object of _lib.load() with the prototypes of include/lightgaussian_distortion.h set on it."""
-    lib = _lib.load()
-    if not _BOUND:
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, list(argtypes)
-        _BOUND.append(True)
-    return lib
+    return _lib.bind(_lib.load(), PROTOTYPES)
 
 
 def ndc_depth(z, near, far):

@@ -56,18 +56,9 @@ PROTOTYPES = {
 }
 
 set_profile, _flags = model_rows.profile_switch()
-_BOUND = []
-
-
 def load():
     """The library object of _lib.load() with the prototypes of include/lightgaussian_mcmc.h set on it."""
-    lib = _lib.load()
-    if not _BOUND:
-        for name, (restype, argtypes) in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = restype, list(argtypes)
-        _BOUND.append(True)
-    return lib
+    return _lib.bind(_lib.load(), PROTOTYPES)
 
 
 # ---- position noise ---------------------------------------------------------------------------------------------------------------

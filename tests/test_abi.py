@@ -167,9 +167,9 @@ _SCALAR_KINDS = {"int": "int32", "int32_t": "int32", "int64_t": "int64", "uint32
 _POINTER_TYPES = ("hipStream_t", "lg_alloc_fn", "lg_chunk_fn")
 
 
-def _header_text():
-    """Both headers, comments removed."""
-    src = open(HDR).read() + "\n" + open(HDR_DEBUG).read()
+def _header_text(headers=None):
+    """The headers (None: the drop-in header and the debug header), comments removed."""
+    src = "\n".join(open(h).read() for h in headers or (HDR, HDR_DEBUG))
     return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
 
 
@@ -182,9 +182,9 @@ def _c_kind(text, named):
     return _SCALAR_KINDS[words[0]]
 
 
-def _header_prototypes():
-    """name -> (return kind, [parameter kinds]) of every lg_* function the two headers declare."""
-    src = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", _header_text(), flags=re.S)
+def _header_prototypes(headers=None):
+    """name -> (return kind, [parameter kinds]) of every lg_* function the headers declare, in the order of the declarations."""
+    src = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", _header_text(headers), flags=re.S)
     src = re.sub(r"typedef[^;{]*;|enum\s*\{.*?\}\s*;|^\s*#[^\n]*|extern\s+\"C\"\s*\{", "", src, flags=re.S | re.M)
     out = {}
     for ret, name, params in re.findall(r"([\w\s\*]+?)\b(lg_\w+)\s*\(([^()]*)\)\s*;", src):
@@ -218,6 +218,20 @@ def _prototype_mismatches(declared, table):
             bad.append(f"{name}: {len(params)} parameters, the table has {len(got)}")
         bad += [f"{name}: parameter {k} is {a}, the table says {b}" for k, (a, b) in enumerate(zip(params, got)) if a != b]
     return bad
+
+
+def check_extension_header(header, table):
+    """What the test of every extension header (include/lightgaussian_<name>.h) holds its module's prototype table against: the
+    table's names are the header's declarations in header order, every return and argument type matches, none of the names is
+    declared in include/lightgaussian.h, and the built library exports every one.  Returns the parsed declarations."""
+    declared = _header_prototypes((os.path.join(common.ROOT, "include", header),))
+    assert list(declared) == list(table)
+    assert _prototype_mismatches(declared, table) == []
+    main = open(HDR).read()
+    assert not any(name in main for name in table), "the extension's functions are declared in the extension header only"
+    lib = C.CDLL(_lib.LIB_PATH)
+    assert all(hasattr(lib, name) for name in table)
+    return declared
 
 
 def test_every_prototype_of_the_binding_matches_the_headers():

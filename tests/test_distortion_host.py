@@ -2,7 +2,6 @@
 against float64, the accuracy on thin slabs that is the reason the kernel exists, the backward replay against float64 autograd, and
 the binding (header, prototype table, exports, Makefile)."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -10,6 +9,7 @@ import torch
 
 import common
 import distortion_common as dc
+import test_abi
 import tolerance
 from lightgaussian_amd import distortion
 
@@ -119,21 +119,12 @@ def test_backward_step_against_float64_autograd(name, gM):
 
 
 def test_header_matches_binding():
+    declared = test_abi.check_extension_header("lightgaussian_distortion.h", distortion.PROTOTYPES)
+    assert len(declared) == 4 and declared["lg_backward_distortion_scratch_bytes"] == ("size_t", ["int32", "int64", "int32"])
     text = open(os.path.join(ROOT, "include", "lightgaussian_distortion.h")).read()
-    body = text[text.index("extern \"C\" {"):]
-    decls = re.findall(r"^(int|size_t)\s+(lg_\w+)\(([^;]*)\);", body, flags=re.M | re.S)
-    assert [name for _r, name, _a in decls] == list(distortion.PROTOTYPES)
-    ctype = {"int32_t": distortion.i32, "int64_t": distortion.i64}
-    for ret, name, args in decls:
-        restype, argtypes = distortion.PROTOTYPES[name]
-        assert restype is (distortion.sz if ret == "size_t" else distortion.C.c_int), name
-        want = [distortion.vp if "*" in a else ctype[a.split()[0]] for a in (x.strip() for x in args.replace("\n", " ").split(","))]
-        assert want == list(argtypes), name
     assert "#define LG_ABI_VERSION" not in text and '#include "lightgaussian.h"' in text
     make = open(os.path.join(ROOT, "lightgaussian_amd", "csrc", "Makefile")).read()
     assert "lg_distortion.h" in make and "lightgaussian_distortion.h" in make
-    main = open(os.path.join(ROOT, "include", "lightgaussian.h")).read()
-    assert not any(name in main for name in distortion.PROTOTYPES), "the new functions are declared in the extension header only"
 
 
 def test_library_exports_the_prototypes():

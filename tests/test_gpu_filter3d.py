@@ -109,8 +109,26 @@ def _apply(a_s, a_o, f, raw):
     return fn(a_s.to(DEV), a_o.to(DEV), f.to(DEV))
 
 
+def _off(t):
+    """A device copy of t whose address is 4 bytes past a 16-byte boundary."""
+    buf = torch.empty(t.numel() + 1, device=DEV)
+    buf[1:] = t.reshape(-1).to(DEV)
+    assert buf.data_ptr() % 16 == 0
+    return buf[1:].view(t.shape)
+
+
+def _apply_bwd(place, a_s, a_o, f, gs, go, raw):
+    """lg_filter3d_apply_bwd called directly on place(tensor) of all seven tensors; (dL/dscaling, dL/dopacity) on the CPU."""
+    ins = [place(t) for t in (a_s, a_o, f, gs, go)]
+    outs = [place(torch.full_like(a_s, float("nan"))), place(torch.full_like(a_o, float("nan")))]
+    _lib.check(_lib.load().lg_filter3d_apply_bwd(a_s.shape[0], *(_lib.ptr(t) for t in ins + outs), _lib.FILTER3D_RAW if raw else 0, _lib.stream()))
+    torch.cuda.synchronize()
+    return outs[0].cpu(), outs[1].cpu()
+
+
+# the row counts below 8 are the branches of the four-rows-per-lane walk: a tail alone (1 - 3), one full lane (4), a full lane and a tail (5, 7)
 @pytest.mark.parametrize("raw", [True, False])
-@pytest.mark.parametrize("N", fc.NS)
+@pytest.mark.parametrize("N", fc.NS + (2, 3, 4, 5, 7))
 def test_apply_against_float64(N, raw):
     e = fc.err32(N, raw)
     a_s, a_o, f = e["inputs"]
@@ -125,11 +143,7 @@ def test_apply_against_float64(N, raw):
     assert zero.any() or N < 4
     assert np.array_equal(_bits(out_s.cpu()[zero]), _bits(a_s[zero])) and np.array_equal(_bits(out_o.cpu()[zero]), _bits(a_o[zero]))
     # pointers off 16 bytes take the dword path: same bits
-    def off(t):
-        buf = torch.empty(t.numel() + 1, device=DEV)
-        buf[1:] = t.reshape(-1).to(DEV)
-        return buf[1:].view(t.shape)
-    m_s, m_o = _apply(off(a_s), off(a_o), off(f), raw)
+    m_s, m_o = _apply(_off(a_s), _off(a_o), _off(f), raw)
     assert np.array_equal(_bits(m_s), _bits(out_s)) and np.array_equal(_bits(m_o), _bits(out_o))
 
 
@@ -163,7 +177,7 @@ def test_apply_hand_placed_rows():
 
 
 @pytest.mark.parametrize("raw", [True, False])
-@pytest.mark.parametrize("N", [65, 1000])
+@pytest.mark.parametrize("N", [65, 1000, 3, 4, 5])
 def test_apply_backward_against_float64_autograd(N, raw):
     ref = fc.grad_reference(N, raw)
     a_s, a_o, f = fc.err32(N, raw)["inputs"]
@@ -174,6 +188,11 @@ def test_apply_backward_against_float64_autograd(N, raw):
     aa.assert_rule({"scaling": s.grad.cpu().numpy(), "opacity": o.grad.cpu().numpy()}, ref, ("scaling", "opacity"), f"N{N} raw={raw}")
     zero = (f == 0).reshape(-1)
     assert np.array_equal(_bits(s.grad.cpu()[zero]), _bits(gs[zero])) and np.array_equal(_bits(o.grad.cpu()[zero]), _bits(go[zero]))
+    # all seven tensors off 16 bytes take the dword path: the same bits as the aligned call, which is the one behind autograd
+    d_s, d_o = _apply_bwd(lambda t: t.to(DEV), a_s, a_o, f, gs, go, raw)
+    assert np.array_equal(_bits(d_s), _bits(s.grad.cpu())) and np.array_equal(_bits(d_o), _bits(o.grad.cpu()))
+    m_s, m_o = _apply_bwd(_off, a_s, a_o, f, gs, go, raw)
+    assert np.array_equal(_bits(m_s), _bits(d_s)) and np.array_equal(_bits(m_o), _bits(d_o))
     # only one output differentiated: the other incoming gradient counts as zero
     s2, o2 = a_s.to(DEV).requires_grad_(), a_o.to(DEV).requires_grad_()
     only_s, _unused = (filter3d.apply_filter_3d if raw else filter3d.apply_filter_3d_activated)(s2, o2, f.to(DEV))

@@ -2,7 +2,6 @@
 tests/normals_common.py, the hand-placed rows and maps of the contract, the header against the binding, and the
 Python surface of lightgaussian_amd.normals / gaussian_renderer.render_geometry."""
 import os
-import re
 import types
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 import torch
 
 import normals_common as nc
+import test_abi
 import tolerance
 from common import ROOT, syn
 from lightgaussian_amd import normals
@@ -151,16 +151,10 @@ def test_hand_placed_maps():
 
 # ---- the header and the binding -----------------------------------------------------------------------------------------------
 def test_header_matches_binding():
+    declared = test_abi.check_extension_header("lightgaussian_normals.h", normals.PROTOTYPES)
+    assert len(declared) == 7 and declared["lg_normal_loss_scratch_bytes"] == ("size_t", ["int32", "int32"])
+    assert declared["lg_depth_normals"] == ("int32", ["int32", "int32", "pointer", "float", "float", "pointer", "uint32", "pointer"])
     text = open(os.path.join(ROOT, "include", "lightgaussian_normals.h")).read()
-    body = text[text.index("extern \"C\" {"):]
-    decls = re.findall(r"^(int|size_t) (lg_\w+)\(([^;]*)\);", body, flags=re.M | re.S)
-    assert [name for _r, name, _a in decls] == list(normals.PROTOTYPES)
-    ctype = {"int32_t": normals.i32, "uint32_t": normals.u32, "float": normals.f32}
-    for ret, name, args in decls:
-        restype, argtypes = normals.PROTOTYPES[name]
-        assert restype is (normals.sz if ret == "size_t" else normals.C.c_int), name
-        want = [normals.vp if "*" in a else ctype[a.split()[0]] for a in (x.strip() for x in args.replace("\n", " ").split(","))]
-        assert want == list(argtypes), name
     assert "#define LG_ABI_VERSION" not in text and '#include "lightgaussian.h"' in text
     make = open(os.path.join(ROOT, "lightgaussian_amd", "csrc", "Makefile")).read()
     assert "lg_normals.h" in make and "lightgaussian_normals.h" in make
