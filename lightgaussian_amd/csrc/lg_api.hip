@@ -36,6 +36,8 @@
 //                    depth map, the fused depth-normal consistency loss (include/lightgaussian_normals.h; a wave per strip, register ring)
 //   lg_distortion.h  lg_distortion_fwd / _bwd: depth distortion and median depth over the lists a forward left, and their gradient into K7's
 //                    moment rows and a per-instance dm row (include/lightgaussian_distortion.h; lg_features.h's walks)
+//   lg_tsdf.h        lg_tsdf_integrate / lg_mesh_count / lg_mesh_emit: depth maps of up to 8 views per pass into a dense TSDF volume, and marching
+//                    tetrahedra over it with indexed vertices (include/lightgaussian_mesh.h; count, scan, emit: no atomics)
 //
 // Pipeline of one view:
 //   K1 project + EWA + SH->RGB + exact footprint culling  ->  K2 scan of instance counts, blocking read of R
@@ -73,6 +75,7 @@
 #include "lg_filter3d.h"
 #include "lg_normals.h"
 #include "lg_distortion.h"
+#include "lg_tsdf.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1725,6 +1728,151 @@ extern "C" int lg_normal_loss_bwd(int32_t H, int32_t W, const float* normal_map,
     lg_normal_bwd<true><<<dim3(lg_nrm_strips(W, LG_NRM_BWD_COLS), lg_nrm_segs(H)), 64, 0, stream>>>(
         H, W, tanfovx, tanfovy, depth, normal_map, alpha, weight, dL_dloss, (float)(1.0 / ((double)H * W)), dL_dnormal_map, dL_ddepth);
     KLAUNCHED("lg_normal_bwd");
+    return LG_OK;
+}
+
+// ---- TSDF fusion and marching tetrahedra (lg_tsdf.h, include/lightgaussian_mesh.h) ----
+static bool positive_finite(float v) { return v > 0.0f && v <= 3.402823466e+38f; }
+static bool finite_f(float v) { return v - v == 0.0f; }
+// the checks of a volume every entry point shares; *vec: tsdf, weight and color are 16-byte aligned
+static int tsdf_volume(const char* who, const lg_tsdf_volume* vol, bool* vec = nullptr)
+{
+    if (!vol) return refuse(who, "null volume");
+    if (vol->nx < 1 || vol->ny < 1 || vol->nz < 1) return refuse(who, "nx, ny, nz must be at least 1");
+    if ((int64_t)vol->nx * vol->ny >= LG_TSDF_MAX_POINTS || (int64_t)vol->nx * vol->ny * vol->nz >= LG_TSDF_MAX_POINTS)
+        return refuse(who, "nx ny nz outside [1, 2^29)");
+    if (!positive_finite(vol->voxel_size)) return refuse(who, "voxel_size must be positive and finite");
+    if (!positive_finite(vol->trunc)) return refuse(who, "trunc must be positive and finite");
+    for (int a = 0; a < 3; a++)
+        if (!finite_f(vol->origin[a])) return refuse(who, "origin must be finite");
+    bool all16 = false;
+    int rc = normals_ptrs(who, { { "tsdf", vol->tsdf }, { "weight", vol->weight } }, &all16);
+    if (rc == LG_OK && vol->color) {
+        rc = normals_ptrs(who, { { "color", vol->color } });
+        all16 = all16 && ((uintptr_t)vol->color & 15) == 0;
+    }
+    if (vec) *vec = all16;
+    return rc;
+}
+static size_t tsdf_points(const lg_tsdf_volume* vol) { return (size_t)vol->nx * (size_t)vol->ny * (size_t)vol->nz; }
+
+extern "C" int lg_tsdf_integrate(const lg_tsdf_volume* vol, int32_t n_views, const lg_tsdf_view* views, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_tsdf_integrate";
+    bool vec = false;
+    int rc = tsdf_volume(who, vol, &vec);
+    if (rc != LG_OK) return rc;
+    if (n_views < 0) return refuse(who, "n_views < 0");
+    if (n_views > 0 && !views) return refuse(who, "null views");
+    for (int i = 0; i < n_views; i++) {
+        const lg_tsdf_view& v = views[i];
+        char what[96];
+        auto bad = [&](const char* text) { snprintf(what, sizeof(what), "views[%d]: %s", i, text); return refuse(who, what); };
+        if (v.H < 1 || v.H > LG_TSDF_MAX_DIM) return bad("H outside [1, 32768]");
+        if (v.W < 1 || v.W > LG_TSDF_MAX_DIM) return bad("W outside [1, 32768]");
+        if (v.tanfovx != v.tanfovx) return bad("tanfovx is NaN");
+        if (v.tanfovy != v.tanfovy) return bad("tanfovy is NaN");
+        if (v.alpha_min != v.alpha_min || v.depth_max != v.depth_max || v.z_min != v.z_min) return bad("alpha_min, depth_max or z_min is NaN");
+        if (!v.viewmatrix) return bad("null viewmatrix");
+        if (!v.depth) return bad("null depth");
+        if (vol->color && !v.color) return bad("null color for a volume that keeps colour");
+        if (((uintptr_t)v.viewmatrix | (uintptr_t)v.depth | (uintptr_t)v.color | (uintptr_t)v.alpha) & 3)
+            return bad("viewmatrix, depth, color and alpha must be 4-byte aligned");
+    }
+    if (n_views == 0) return LG_OK;
+    hipStream_t stream = (hipStream_t)stream_p;
+    const LgTsdfGrid g = { vol->nx, vol->ny, vol->nz, vol->origin[0], vol->origin[1], vol->origin[2], vol->voxel_size, vol->trunc };
+    const unsigned wgs = (unsigned)lg_tsdf_bricks(vol->nx, vol->ny, vol->nz);
+    for (int first = 0; first < n_views; first += LG_TSDF_BATCH) {
+        const int n = std::min(LG_TSDF_BATCH, n_views - first);
+        LgTsdfBatch b;
+        memset(&b, 0, sizeof(b));
+        for (int k = 0; k < n; k++) {
+            const lg_tsdf_view& v = views[first + k];
+            b.v[k] = { v.viewmatrix, v.depth, vol->color ? v.color : nullptr, v.alpha, { v.W, v.H, v.tanfovx, v.tanfovy, v.depth_max, v.z_min, v.alpha_min } };
+        }
+        ProfScope ps(flags & LG_FLAG_PROFILE, "tsdf_integrate", stream);
+        if (vol->color) lg_tsdf_integrate_kernel<true><<<wgs, LG_TSDF_THREADS, 0, stream>>>(g, vec, n, b, vol->tsdf, vol->weight, vol->color);
+        else lg_tsdf_integrate_kernel<false><<<wgs, LG_TSDF_THREADS, 0, stream>>>(g, vec, n, b, vol->tsdf, vol->weight, nullptr);
+        KLAUNCHED("lg_tsdf_integrate_kernel");
+    }
+    return LG_OK;
+}
+
+extern "C" size_t lg_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz)
+{
+    if (nx < 1 || ny < 1 || nz < 1 || (int64_t)nx * ny >= LG_TSDF_MAX_POINTS || (int64_t)nx * ny * nz >= LG_TSDF_MAX_POINTS) return 0;
+    return carve_mesh(nullptr, (size_t)nx * (size_t)ny * (size_t)nz).total;
+}
+
+static int mesh_args(const char* who, const lg_tsdf_volume* vol, float iso, float min_weight, const void* scratch)
+{
+    int rc = tsdf_volume(who, vol);
+    if (rc != LG_OK) return rc;
+    if (!finite_f(iso)) return refuse(who, "iso must be finite");
+    if (!positive_finite(min_weight)) return refuse(who, "min_weight must be positive and finite");
+    if (!scratch) return refuse(who, "null scratch");
+    if ((uintptr_t)scratch & 255) return refuse(who, "scratch must be 256-byte aligned");
+    return LG_OK;
+}
+
+extern "C" int lg_mesh_count(const lg_tsdf_volume* vol, float iso, float min_weight, void* scratch, int64_t* counts, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_mesh_count";
+    int rc = mesh_args(who, vol, iso, min_weight, scratch);
+    if (rc != LG_OK) return rc;
+    if (!counts) return refuse(who, "null counts");
+    if ((uintptr_t)counts & 7) return refuse(who, "counts must be 8-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool prof = flags & LG_FLAG_PROFILE;
+    const size_t P = tsdf_points(vol), nb = lg_mesh_blocks(P);
+    const LgMeshScratch s = carve_mesh(scratch, P);
+    const LgMeshDims d = { vol->nx, vol->ny, vol->nz };
+    {
+        ProfScope ps(prof, "mesh_count", stream);
+        lg_mesh_count_kernel<<<(unsigned)nb, 256, 0, stream>>>(d, P, iso, min_weight, vol->tsdf, vol->weight, s.vmask, s.fcount, s.blk, s.blk + nb);
+        KLAUNCHED("lg_mesh_count_kernel");
+    }
+    {
+        ProfScope ps(prof, "mesh_scan", stream);
+        lg_mesh_scan_kernel<<<2, 1024, 0, stream>>>(nb, s.blk, counts, s.counts);
+        KLAUNCHED("lg_mesh_scan_kernel");
+        lg_mesh_prefix_kernel<<<(unsigned)nb, 256, 0, stream>>>(P, s.vmask, s.fcount, s.blk, s.blk + nb, s.vprefix, s.fprefix);
+        KLAUNCHED("lg_mesh_prefix_kernel");
+    }
+    return LG_OK;
+}
+
+extern "C" int lg_mesh_emit(const lg_tsdf_volume* vol, float iso, float min_weight, void* scratch, int64_t n_vertices, int64_t n_faces, float* vertices,
+                            float* colors, int32_t* faces, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_mesh_emit";
+    int rc = mesh_args(who, vol, iso, min_weight, scratch);
+    if (rc != LG_OK) return rc;
+    if (n_vertices < 0 || n_vertices >= (1ll << 31)) return refuse(who, "n_vertices outside [0, 2^31)");
+    if (n_faces < 0 || n_faces >= (1ll << 31)) return refuse(who, "n_faces outside [0, 2^31)");
+    if (colors && !vol->color) return refuse(who, "colors for a volume that keeps no colour");
+    if (n_vertices > 0) {
+        rc = normals_ptrs(who, { { "vertices", vertices } });
+        if (rc == LG_OK && colors) rc = normals_ptrs(who, { { "colors", colors } });
+    }
+    if (rc == LG_OK && n_faces > 0) rc = normals_ptrs(who, { { "faces", faces } });
+    if (rc != LG_OK) return rc;
+    hipStream_t stream = (hipStream_t)stream_p;
+    const size_t P = tsdf_points(vol);
+    const LgMeshScratch s = carve_mesh(scratch, P);
+    int64_t h_counts[2] = { -1, -1 };
+    HIP_TRY(hipMemcpyAsync(h_counts, s.counts, 16, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (h_counts[0] != n_vertices) return refuse(who, "n_vertices differs from the count lg_mesh_count left in scratch");
+    if (h_counts[1] != n_faces) return refuse(who, "n_faces differs from the count lg_mesh_count left in scratch");
+    if (n_vertices == 0 && n_faces == 0) return LG_OK;
+    const LgMeshDims d = { vol->nx, vol->ny, vol->nz };
+    const LgMeshOrigin org = { { vol->origin[0], vol->origin[1], vol->origin[2] }, vol->voxel_size };
+    ProfScope ps(flags & LG_FLAG_PROFILE, "mesh_emit", stream);
+    lg_mesh_emit_kernel<<<(unsigned)((P + 255) / 256), 256, 0, stream>>>(d, P, org, iso, min_weight, vol->tsdf, vol->weight, vol->color, s.vprefix, s.fprefix,
+                                                                          s.vmask, s.fcount, n_vertices, n_faces, vertices, colors, faces);
+    KLAUNCHED("lg_mesh_emit_kernel");
     return LG_OK;
 }
 

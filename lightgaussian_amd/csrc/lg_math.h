@@ -1142,3 +1142,218 @@ LG_HD bool lg_distortion_bwd_step(bool live, float power, float G, float alpha, 
     dm = gw * (u * s.A - s.P1) + (pos == s.med_pos ? gM : 0.0f);
     return true;
 }
+
+// ---------------------------------------------------------------------------------------------
+// TSDF fusion of depth maps and marching tetrahedra (include/lightgaussian_mesh.h; lg_tsdf.h's kernels and
+// tests/cpu_harness/lg_tsdf_harness.cpp call the same functions).
+//
+// The volume: nx x ny x nz points, x fastest; point (x, y, z) lies at origin + voxel (x, y, z): one product, one sum per axis.
+// One point under one view, in this order (a step that fails leaves the point's values as they are):
+//   p_v = p vm (lg_view_point)                                  z = p_v.z > z_min
+//   fx = (p_v.x / (z tanfovx) + 1) (0.5 W)   px = floor(fx)     fy, py likewise     0 <= px < W, 0 <= py < H   (a NaN fails)
+//   d = depth[py, px]       d > 0, finite, d <= depth_max where depth_max > 0;  alpha[py, px] >= alpha_min where an alpha map is given
+//   sdf = d - z >= -trunc   t = min(1, sdf / trunc)
+//   w' = w + 1   tsdf = (tsdf w + t) / w'   colour_c = (colour_c w + image_c[py, px]) / w'   weight = w'
+struct LgTsdfCam { int W, H; float tanfovx, tanfovy, depth_max, z_min, alpha_min; };
+LG_HD float lg_tsdf_coord(float origin, float voxel, int i) { return origin + voxel * (float)i; }
+// the pixel that contains the projection of the world point p, and its view-space z
+LG_HD bool lg_tsdf_project(const float* vm, const LgTsdfCam& c, float px, float py, float pz, int& ix, int& iy, float& z)
+{
+    float vx, vy, vz;
+    lg_view_point(vm, px, py, pz, vx, vy, vz);
+    if (!(vz > c.z_min)) return false;
+    const float fx = (vx / (vz * c.tanfovx) + 1.0f) * (0.5f * (float)c.W);
+    const float fy = (vy / (vz * c.tanfovy) + 1.0f) * (0.5f * (float)c.H);
+    const float flx = floorf(fx), fly = floorf(fy);
+    if (!(flx >= 0.0f && flx < (float)c.W && fly >= 0.0f && fly < (float)c.H)) return false;
+    ix = (int)flx; iy = (int)fly; z = vz;
+    return true;
+}
+// the truncated signed distance t of a point at depth z under a pixel of depth d
+LG_HD bool lg_tsdf_sample(const LgTsdfCam& c, float trunc, float d, float z, float& t)
+{
+    if (!(d > 0.0f) || !(d <= 3.402823466e+38f)) return false;
+    if (c.depth_max > 0.0f && d > c.depth_max) return false;
+    const float sdf = d - z;
+    if (sdf < -trunc) return false;
+    t = fminf(1.0f, sdf / trunc);
+    return true;
+}
+LG_HD float lg_tsdf_mean(float v, float w, float x, float w1) { return (v * w + x) / w1; }
+// What the pixel under a point holds: its depth, its alpha (read only with has_alpha) and its colour (read only where the point has one).
+struct LgTsdfPixel { float d, alpha, rgb[3]; };
+// One point at view-space depth z under its pixel: rgb = the point's colour or NULL.  Returns whether the point was updated.
+LG_HD bool lg_tsdf_apply(const LgTsdfCam& c, float trunc, const LgTsdfPixel& p, bool has_alpha, float z, float& tsdf, float& weight, float* rgb)
+{
+    float t;
+    if (!lg_tsdf_sample(c, trunc, p.d, z, t)) return false;
+    if (has_alpha && p.alpha < c.alpha_min) return false;
+    const float w = weight, w1 = w + 1.0f;
+    tsdf = lg_tsdf_mean(tsdf, w, t, w1);
+    if (rgb) {
+        rgb[0] = lg_tsdf_mean(rgb[0], w, p.rgb[0], w1);
+        rgb[1] = lg_tsdf_mean(rgb[1], w, p.rgb[1], w1);
+        rgb[2] = lg_tsdf_mean(rgb[2], w, p.rgb[2], w1);
+    }
+    weight = w1;
+    return true;
+}
+// One point under one view, the gathers included: depth [H,W], color [3,H,W] or NULL, alpha [H,W] or NULL; rgb = the point's colour or NULL.
+LG_HD bool lg_tsdf_update(const float* vm, const LgTsdfCam& c, const float* depth, const float* color, const float* alpha, float trunc,
+                          float px, float py, float pz, float& tsdf, float& weight, float* rgb)
+{
+    int ix, iy;
+    float z;
+    if (!lg_tsdf_project(vm, c, px, py, pz, ix, iy, z)) return false;
+    const size_t pix = (size_t)iy * (size_t)c.W + (size_t)ix, plane = (size_t)c.H * (size_t)c.W;
+    LgTsdfPixel p = { depth[pix], alpha ? alpha[pix] : 0.0f, { 0.0f, 0.0f, 0.0f } };
+    const bool colour = rgb && color;
+    if (colour) { p.rgb[0] = color[pix]; p.rgb[1] = color[plane + pix]; p.rgb[2] = color[2 * plane + pix]; }
+    return lg_tsdf_apply(c, trunc, p, alpha != nullptr, z, tsdf, weight, colour ? rgb : nullptr);
+}
+
+// Marching tetrahedra over the volume.  Axis bits x = 1, y = 2, z = 4; a corner or edge mask m stands for the offset (m & 1, m >> 1 & 1,
+// m >> 2 & 1).  A point is observed when weight >= min_weight and inside when tsdf < iso (a NaN is neither).
+//   edge slots      point p owns the edges to p + offset(m) for m = 1, 2, 4, 3, 5, 6, 7 (slot k = 0 .. 6) that stay inside the grid
+//   vertex rule     an edge carries a vertex iff both ends are observed and exactly one is inside; f = tsdf - iso, t = f0 / (f0 - f1)
+//                   (f0 and f1 differ in sign or one is zero and the other negative: f0 - f1 is not zero), grid position p0 + t offset,
+//                   world position origin + voxel * that; colour c0 + t (c1 - c0).  Vertex ids count the carrying edges by (point, slot).
+//   cells           the cube at p < (nx - 1, ny - 1, nz - 1), valid when its eight corners are observed
+//   tetrahedra      six per cell, one per permutation (a, b, c) of the axes in lexicographic order, local corners 0, 1<<a, 1<<a | 1<<b, 7;
+//                   the edge between local corners i < j is the slot of mask_j ^ mask_i at the point of corner i
+//   triangles       by the 4-bit inside mask of the local corners: none for 0 and 15; one corner apart from the other three: the three
+//                   edges from it in ascending order of the other end; two and two (a < b inside, c < d outside): the quad (a,c), (a,d),
+//                   (b,d), (b,c) as (q0, q1, q2), (q0, q2, q3).  LG_MESH_FLIP_* bit `mask`: the triangle as listed has its normal (unit
+//                   cube, edge midpoints) pointing from the outside corners to the inside ones, so its 2nd and 3rd index are swapped: the
+//                   normals of the result point toward larger tsdf.  The bits were derived from that rule (the even permutations share
+//                   one word, the odd ones its complement); the closed-surface tests of tests/test_mesh_host.py hold them.
+#define LG_MESH_SLOTS 7
+#define LG_MESH_SLOT_MASKS 0x7653421u       // nibble k: the offset mask of slot k
+#define LG_MESH_MASK_SLOTS 0x65423100u      // nibble m: the slot of offset mask m (m = 1 .. 7)
+#define LG_MESH_PERM_A 0xA50u               // two bits per tetrahedron: the axis a, and b
+#define LG_MESH_PERM_B 0x489u
+#define LG_MESH_FLIP_EVEN 0x4D24u           // tetrahedra 0, 3, 4
+#define LG_MESH_FLIP_ODD 0x32DAu            // tetrahedra 1, 2, 5
+LG_HD uint32_t lg_mesh_slot_mask(uint32_t k) { return (LG_MESH_SLOT_MASKS >> (4u * k)) & 7u; }
+LG_HD uint32_t lg_mesh_mask_slot(uint32_t m) { return (LG_MESH_MASK_SLOTS >> (4u * m)) & 7u; }
+LG_HD uint32_t lg_mesh_popc8(uint32_t m) { m = (m & 0x55u) + ((m >> 1) & 0x55u); m = (m & 0x33u) + ((m >> 2) & 0x33u); return (m + (m >> 4)) & 0xFu; }
+LG_HD bool lg_mesh_observed(float w, float min_weight) { return w >= min_weight; }
+LG_HD bool lg_mesh_inside(float f, float iso) { return f < iso; }
+LG_HD size_t lg_mesh_index(int nx, int ny, int x, int y, int z) { return ((size_t)z * (size_t)ny + (size_t)y) * (size_t)nx + (size_t)x; }
+
+// bit k: slot k of the point (x, y, z) carries a vertex
+LG_HD uint32_t lg_mesh_edge_mask(const float* tsdf, const float* weight, int nx, int ny, int nz, int x, int y, int z, float iso, float min_weight)
+{
+    const size_t p = lg_mesh_index(nx, ny, x, y, z);
+    if (!lg_mesh_observed(weight[p], min_weight)) return 0u;
+    const bool in0 = lg_mesh_inside(tsdf[p], iso);
+    uint32_t mask = 0u;
+    for (uint32_t k = 0; k < LG_MESH_SLOTS; k++) {
+        const uint32_t m = lg_mesh_slot_mask(k);
+        const int x1 = x + (int)(m & 1u), y1 = y + (int)((m >> 1) & 1u), z1 = z + (int)((m >> 2) & 1u);
+        if (x1 < nx && y1 < ny && z1 < nz) {
+            const size_t q = lg_mesh_index(nx, ny, x1, y1, z1);
+            if (lg_mesh_observed(weight[q], min_weight) && lg_mesh_inside(tsdf[q], iso) != in0) mask |= 1u << k;
+        }
+    }
+    return mask;
+}
+// the vertex on slot k of the point (x, y, z): world position, and colour where the volume keeps one
+LG_HD void lg_mesh_vertex(const float* tsdf, const float* color, int nx, int ny, int x, int y, int z, uint32_t k, float iso, const float* origin,
+                          float voxel, float* pos, float* rgb)
+{
+    const uint32_t m = lg_mesh_slot_mask(k);
+    const int ox = (int)(m & 1u), oy = (int)((m >> 1) & 1u), oz = (int)((m >> 2) & 1u);
+    const size_t p = lg_mesh_index(nx, ny, x, y, z), q = lg_mesh_index(nx, ny, x + ox, y + oy, z + oz);
+    const float f0 = tsdf[p] - iso, f1 = tsdf[q] - iso;
+    const float t = f0 / (f0 - f1);
+    pos[0] = origin[0] + voxel * ((float)x + t * (float)ox);
+    pos[1] = origin[1] + voxel * ((float)y + t * (float)oy);
+    pos[2] = origin[2] + voxel * ((float)z + t * (float)oz);
+    if (rgb && color) {
+        rgb[0] = color[3 * p] + t * (color[3 * q] - color[3 * p]);
+        rgb[1] = color[3 * p + 1] + t * (color[3 * q + 1] - color[3 * p + 1]);
+        rgb[2] = color[3 * p + 2] + t * (color[3 * q + 2] - color[3 * p + 2]);
+    }
+}
+// bit m (0 .. 7): corner offset(m) of the cell at (x, y, z) is inside; false when a corner is unobserved.  x < nx - 1, y < ny - 1, z < nz - 1.
+LG_HD bool lg_mesh_cell_corners(const float* tsdf, const float* weight, int nx, int ny, int x, int y, int z, float iso, float min_weight, uint32_t& inside8)
+{
+    inside8 = 0u;
+    bool valid = true;
+    for (uint32_t m = 0; m < 8u; m++) {
+        const size_t q = lg_mesh_index(nx, ny, x + (int)(m & 1u), y + (int)((m >> 1) & 1u), z + (int)((m >> 2) & 1u));
+        valid = valid && lg_mesh_observed(weight[q], min_weight);
+        inside8 |= (lg_mesh_inside(tsdf[q], iso) ? 1u : 0u) << m;
+    }
+    return valid;
+}
+LG_HD uint32_t lg_mesh_tet_corner(uint32_t t, uint32_t i)        // the cell corner (offset mask) of local corner i of tetrahedron t
+{
+    const uint32_t a = 1u << ((LG_MESH_PERM_A >> (2u * t)) & 3u), b = 1u << ((LG_MESH_PERM_B >> (2u * t)) & 3u);
+    return i == 0u ? 0u : (i == 1u ? a : (i == 2u ? (a | b) : 7u));
+}
+LG_HD uint32_t lg_mesh_tet_inside(uint32_t t, uint32_t inside8)   // bit i: local corner i is inside
+{
+    uint32_t m4 = 0u;
+    for (uint32_t i = 0; i < 4u; i++) m4 |= ((inside8 >> lg_mesh_tet_corner(t, i)) & 1u) << i;
+    return m4;
+}
+LG_HD uint32_t lg_mesh_tet_count(uint32_t m4)
+{
+    const uint32_t n = lg_mesh_popc8(m4);
+    return n == 2u ? 2u : ((n == 1u || n == 3u) ? 1u : 0u);
+}
+LG_HD uint32_t lg_mesh_cell_count(uint32_t inside8)
+{
+    uint32_t n = 0u;
+    for (uint32_t t = 0; t < 6u; t++) n += lg_mesh_tet_count(lg_mesh_tet_inside(t, inside8));
+    return n;
+}
+// the triangles of tetrahedron t under the inside mask m4, winding applied: tri[j][v] = lo | hi << 2, the edge between the local corners
+// lo < hi.  Returns their number.
+LG_HD uint32_t lg_mesh_tet_triangles(uint32_t t, uint32_t m4, uint32_t tri[2][3])
+{
+    const uint32_t n = lg_mesh_tet_count(m4);
+    if (n == 0u) return 0u;
+    const uint32_t w4 = ~m4 & 15u;                                 // the outside corners
+#define LG_MESH_LOWEST(m) (((m) & 1u) ? 0u : (((m) & 2u) ? 1u : (((m) & 4u) ? 2u : 3u)))
+#define LG_MESH_HIGHEST(m) (((m) & 8u) ? 3u : (((m) & 4u) ? 2u : (((m) & 2u) ? 1u : 0u)))
+#define LG_MESH_EDGE(u, v) ((u) < (v) ? ((u) | ((v) << 2)) : ((v) | ((u) << 2)))
+    if (n == 1u) {
+        const uint32_t a = lg_mesh_popc8(m4) == 1u ? LG_MESH_LOWEST(m4) : LG_MESH_LOWEST(w4);
+        for (uint32_t v = 0; v < 3u; v++) { const uint32_t o = v + (v >= a ? 1u : 0u); tri[0][v] = LG_MESH_EDGE(a, o); }
+    } else {
+        const uint32_t in0 = LG_MESH_LOWEST(m4), in1 = LG_MESH_HIGHEST(m4), out0 = LG_MESH_LOWEST(w4), out1 = LG_MESH_HIGHEST(w4);
+        const uint32_t q0 = LG_MESH_EDGE(in0, out0), q1 = LG_MESH_EDGE(in0, out1), q2 = LG_MESH_EDGE(in1, out1), q3 = LG_MESH_EDGE(in1, out0);
+        tri[0][0] = q0; tri[0][1] = q1; tri[0][2] = q2;
+        tri[1][0] = q0; tri[1][1] = q2; tri[1][2] = q3;
+    }
+#undef LG_MESH_EDGE
+#undef LG_MESH_LOWEST
+#undef LG_MESH_HIGHEST
+    const uint32_t word = (t == 0u || t == 3u || t == 4u) ? LG_MESH_FLIP_EVEN : LG_MESH_FLIP_ODD;
+    if ((word >> m4) & 1u)
+        for (uint32_t j = 0; j < n; j++) { const uint32_t s = tri[j][1]; tri[j][1] = tri[j][2]; tri[j][2] = s; }
+    return n;
+}
+// The faces of the valid cell at (x, y, z) with corner bits inside8, written to faces[3 j + v] in order: vprefix[p] = vertex id of the
+// first carrying slot of point p, vmask[p] = its lg_mesh_edge_mask; `room` = faces the buffer holds from `faces` on (one past it is not
+// written).  Returns their number (= lg_mesh_cell_count).
+LG_HD uint32_t lg_mesh_cell_faces(int nx, int ny, int x, int y, int z, uint32_t inside8, const uint32_t* vprefix, const uint8_t* vmask, int32_t* faces,
+                                  int64_t room)
+{
+    uint32_t nf = 0u;
+    for (uint32_t t = 0; t < 6u; t++) {
+        uint32_t tri[2][3];
+        const uint32_t n = lg_mesh_tet_triangles(t, lg_mesh_tet_inside(t, inside8), tri);
+        for (uint32_t j = 0; j < n; j++, nf++)
+            for (uint32_t v = 0; v < 3u; v++) {
+                const uint32_t c0 = lg_mesh_tet_corner(t, tri[j][v] & 3u), c1 = lg_mesh_tet_corner(t, tri[j][v] >> 2);
+                const size_t q = lg_mesh_index(nx, ny, x + (int)(c0 & 1u), y + (int)((c0 >> 1) & 1u), z + (int)((c0 >> 2) & 1u));
+                const uint32_t k = lg_mesh_mask_slot(c1 ^ c0);
+                if ((int64_t)nf < room) faces[3u * nf + v] = (int32_t)(vprefix[q] + lg_mesh_popc8((uint32_t)vmask[q] & ((1u << k) - 1u)));
+            }
+    }
+    return nf;
+}

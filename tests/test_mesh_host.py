@@ -1,0 +1,365 @@
+"""TSDF fusion and marching tetrahedra, host side (no GPU): lg_math.h's arithmetic through the g++ harness against the float64 twin of
+tests/mesh_common.py, the torch backend against the harness, the closed-surface properties of the triangle table, the header against
+the binding and the compiler, the refusals of include/lightgaussian_mesh.h (they precede every device call), and the Python surface of
+lightgaussian_amd.mesh."""
+import ctypes as C
+import os
+import re
+import struct
+import subprocess
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import mesh_common as mc
+import test_abi
+import tolerance
+from common import ROOT, syn
+from lightgaussian_amd import _lib, mesh
+
+OPTIONS = (dict(), dict(use_alpha=True, depth_max=3.6))
+
+
+# ---- integration --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dims", ((24, 20, 16), (32, 32, 32)))
+@pytest.mark.parametrize("opt", range(len(OPTIONS)))
+def test_integrate_against_float64(dims, opt):
+    kw = OPTIONS[opt]
+    origin, voxel, trunc = mc.volume_spec(dims)
+    views = mc.sphere_views(6)
+    start = mc.fresh_volume(dims)
+    got, decided = mc.harness_integrate(dims, origin, voxel, trunc, start, views, decided=True, **kw)
+    r64, d64, near = mc.twin_integrate(dims, origin, voxel, trunc, start, views, **kw)
+    r32, _d, _n = mc.twin_integrate(dims, origin, voxel, trunc, start, views, dtype=np.float32, **kw)
+    share = float(near.mean())
+    print(f"{dims} {kw}: {100 * share:.3f} % of the (point, view) pairs within {mc.MARGIN} of a decision; {100 * d64.mean():.1f} % of the pairs update")
+    assert share <= mc.MAX_LEFT_OUT and d64.mean() > 0.03
+    assert np.array_equal(decided.astype(bool)[~near], d64[~near]), "a decision outside the margins differs from float64"
+    keep = ~near.any(axis=0)
+    assert np.array_equal(got[1].reshape(-1)[keep], r64[1].reshape(-1)[keep]), "weights differ"
+    tolerance.assert_rule3(got[0].reshape(-1)[keep], r64[0].reshape(-1)[keep], r32[0].reshape(-1)[keep], f"{dims} tsdf")
+    tolerance.assert_rule3(got[2].reshape(-1, 3)[keep], r64[2].reshape(-1, 3)[keep], r32[2].reshape(-1, 3)[keep], f"{dims} colour")
+    # a point no view updated keeps its values; a volume without colour gives the same tsdf and weight
+    untouched = ~decided.astype(bool).any(axis=0)
+    assert untouched.any() and (got[0].reshape(-1)[untouched] == 1).all() and (got[1].reshape(-1)[untouched] == 0).all()
+    plain = mc.harness_integrate(dims, origin, voxel, trunc, (start[0], start[1], None), views, **kw)
+    assert plain[2] is None and np.array_equal(mc.bits(plain[0]), mc.bits(got[0])) and np.array_equal(plain[1], got[1])
+
+
+def test_one_call_is_n_calls_in_the_harness():
+    dims = (5, 4, 3)
+    origin, voxel, trunc = mc.volume_spec(dims)
+    views = mc.sphere_views(6)
+    start = mc.seeded_volume(dims)
+    once = mc.harness_integrate(dims, origin, voxel, trunc, start, views)
+    state = start
+    for v in views:
+        state = mc.harness_integrate(dims, origin, voxel, trunc, state, [v])
+    assert all(np.array_equal(mc.bits(a), mc.bits(b)) for a, b in zip(once, state))
+    assert not np.array_equal(mc.bits(once[0]), mc.bits(start[0]))
+    assert all(np.array_equal(mc.bits(a), mc.bits(b)) for a, b in zip(mc.harness_integrate(dims, origin, voxel, trunc, start, []), start))
+
+
+def _torch_volume(dims, origin, voxel, trunc, state):
+    vol = mesh.TSDFVolume(origin, dims, voxel, trunc=trunc, color=state[2] is not None, device="cpu")
+    vol.tsdf.copy_(torch.from_numpy(state[0])); vol.weight.copy_(torch.from_numpy(state[1]))
+    if state[2] is not None:
+        vol.color.copy_(torch.from_numpy(state[2]))
+    return vol
+
+
+def _torch_views(views, color=True, alpha=False, **kw):
+    return [dict(depth=torch.from_numpy(v["depth"]), camera=v["cam"], color=torch.from_numpy(v["color"]) if color else None,
+                 alpha=torch.from_numpy(v["alpha"]) if alpha else None, **kw) for v in views]
+
+
+# ---- the torch backend against the harness ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dims", ((24, 20, 16), (67, 5, 3)))
+def test_torch_backend_against_the_harness(dims):
+    origin, voxel, trunc = mc.volume_spec(dims)
+    views = mc.sphere_views(6)
+    start = mc.seeded_volume(dims) if dims[0] == 67 else mc.fresh_volume(dims)
+    want, decided = mc.harness_integrate(dims, origin, voxel, trunc, start, views, use_alpha=True, alpha_min=0.5, depth_max=3.6, decided=True)
+    vol = _torch_volume(dims, origin, voxel, trunc, start)
+    assert vol.trunc == trunc and vol.voxel_size == voxel and vol.origin == tuple(origin)
+    vol.integrate_many(_torch_views(views, alpha=True, alpha_min=0.5, depth_max=3.6))
+    _r, _d, near = mc.twin_integrate(dims, origin, voxel, trunc, start, views, use_alpha=True, depth_max=3.6)
+    keep = ~near.any(axis=0)
+    assert near.mean() <= mc.MAX_LEFT_OUT
+    assert np.array_equal(vol.weight.numpy().reshape(-1)[keep], want[1].reshape(-1)[keep])
+    for got, ref, name in ((vol.tsdf, want[0], "tsdf"), (vol.color.reshape(-1, 3), want[2].reshape(-1, 3), "colour")):
+        g, r = got.numpy().reshape(len(keep), -1)[keep], ref.reshape(len(keep), -1)[keep]
+        tolerance.assert_rule3(g, r.astype(np.float64), r, f"{dims} torch backend {name}")
+    # meshes compare element-wise: the same vertex and face order
+    vol = _torch_volume(dims, origin, voxel, trunc, want)
+    h = mc.harness_extract(want[0], want[1], want[2], origin, voxel)
+    v, f, c = vol.extract_mesh(drop_unreferenced=False)
+    assert v.shape == h["vertices"].shape and f.dtype == torch.int32 and np.array_equal(f.numpy(), h["faces"])
+    if len(h["vertices"]):
+        tolerance.assert_rule3(v.numpy(), h["vertices"].astype(np.float64), h["vertices"], f"{dims} torch backend vertices")
+        tolerance.assert_rule3(c.numpy(), h["colors"].astype(np.float64), h["colors"], f"{dims} torch backend colours")
+
+
+# ---- the surface properties of section 3 ------------------------------------------------------------------------------------------------
+def _fields():
+    dims = (12, 12, 12)
+    origin, voxel, _t = mc.volume_spec(dims)
+    yield "clipped sphere", dims, origin, voxel, mc.sphere_field(dims, origin, voxel, 1.0), 4 / 3 * np.pi, 2
+    yield "lattice-aligned sphere", dims, (-5.0, -5.0, -5.0), 1.0, mc.sphere_field(dims, (-5.0, -5.0, -5.0), 1.0, 3.0), 36 * np.pi, 2
+    dims = (24, 12, 24)
+    origin, voxel, _t = mc.volume_spec(dims)
+    yield "torus", dims, origin, voxel, mc.torus_field(dims, origin, voxel, 0.9, 0.35), 2 * np.pi ** 2 * 0.9 * 0.35 ** 2, 0
+
+
+@pytest.mark.parametrize("which", ("twin", "harness", "torch"))
+def test_closed_oriented_surfaces(which):
+    for name, dims, origin, voxel, (f, w), volume, euler in _fields():
+        if name.startswith("lattice"):
+            assert int((f == 0).sum()) >= 6, "the field must have points exactly on the surface"
+        if which == "twin":
+            m = mc.twin_extract(f, w, None, origin, voxel)
+            v, faces = m["vertices"], m["faces"]
+        elif which == "harness":
+            m = mc.harness_extract(f, w, None, origin, voxel)
+            v, faces = m["vertices"], m["faces"]
+        else:
+            v, faces, _c = (None if t is None else t.numpy() for t in mesh._extract_torch(torch.from_numpy(f), torch.from_numpy(w), None, origin, voxel, 0.0, 1.0))
+        p = mc.mesh_properties(v, faces)
+        print(f"{which} {name}: {len(v)} vertices, {len(faces)} faces, V - E + F = {p['euler']}, volume {p['volume']:.4f} (analytic {volume:.4f})")
+        assert p["closed"], f"{name}: an edge is not used once in each direction"
+        assert p["euler"] == euler and p["volume"] > 0 and abs(p["volume"] / volume - 1) <= 0.08
+        assert len(np.unique(faces)) == len(v), "a closed surface over a fully observed grid has no unreferenced vertex"
+        if name == "clipped sphere":
+            # the distance g to the sphere along an edge of length L <= sqrt(3) voxel has |g''| <= 1 / rho, rho >= sqrt(R^2 - L^2 / 4) the
+            # distance of the edge from the centre; a vertex is the root of the linear interpolant of g: |g| <= max |g''| L^2 / 8 there
+            L = np.sqrt(3.0) * voxel
+            off, bound = np.abs(np.linalg.norm(v, axis=1) - 1).max(), L * L / (8 * np.sqrt(1 - L * L / 4))
+            print(f"    vertices within {off / voxel:.4f} voxel of the sphere (bound {bound / voxel:.4f})")
+            assert off <= bound + 1e-6
+
+
+def test_harness_equals_twin_and_every_table_entry_is_met():
+    dims = (12, 11, 10)
+    f, w, c = mc.random_field(dims, observed=0.93)
+    origin, voxel, _t = mc.volume_spec(dims)
+    h, t = mc.harness_extract(f, w, c, origin, voxel), mc.twin_extract(f, w, c, origin, voxel)
+    assert (h["used"][:, 1:15] > 0).all(), "the random field must meet all 6 x 14 non-trivial table entries"
+    assert np.array_equal(h["used"], t["used"]) and np.array_equal(h["faces"], t["faces"]) and np.array_equal(h["cell_of_face"], t["cell_of_face"])
+    assert len(h["faces"]) > 500 and h["vertices"].shape == t["vertices"].shape
+    t32 = mc.twin_extract(f, w, c, origin, voxel, dtype=np.float32)
+    tolerance.assert_rule3(h["vertices"], t["vertices"], t32["vertices"], "vertices")
+    tolerance.assert_rule3(h["colors"], t["colors"], t32["colors"], "colours")
+    # normals point toward larger tsdf: the centroid of every face moved along its normal lands on the side of the cell's outside corners
+    v = h["vertices"].astype(np.float64)
+    a, b, cc = (v[h["faces"][:, k]] for k in range(3))
+    n = np.cross(b - a, cc - a)
+    assert (np.linalg.norm(n, axis=1) > 0).mean() > 0.99
+
+
+def test_half_the_points_unobserved():
+    dims = (12, 12, 12)
+    origin, voxel, _t = mc.volume_spec(dims)
+    f, w = mc.sphere_field(dims, origin, voxel, 1.0)
+    w = (np.random.RandomState(4).uniform(0, 1, w.shape) < 0.5).astype(np.float32)
+    h = mc.harness_extract(f, w, None, origin, voxel)
+    nv, nf = len(h["vertices"]), len(h["faces"])
+    assert nv > 0 and nf > 0 and h["faces"].min() >= 0 and h["faces"].max() < nv and np.isfinite(h["vertices"]).all()
+    nx, ny, nz = dims
+    obs = w.reshape(-1) >= 1
+    for cm in range(8):                               # no face in an invalid cell
+        o = mc.offset(cm)
+        assert obs[h["cell_of_face"] + o[0] + o[1] * nx + o[2] * nx * ny].all()
+    assert len(np.unique(h["faces"])) < nv, "with unobserved points some vertices lie on edges without a valid cell"
+    vol = mesh.TSDFVolume(origin, dims, voxel, color=False, device="cpu")
+    vol.tsdf.copy_(torch.from_numpy(f)); vol.weight.copy_(torch.from_numpy(w))
+    v_all, f_all, c_all = vol.extract_mesh(drop_unreferenced=False)
+    v, faces, c = vol.extract_mesh()
+    assert c is None and c_all is None and np.array_equal(f_all.numpy(), h["faces"])
+    assert len(v) == len(np.unique(h["faces"])) and len(np.unique(faces.numpy())) == len(v) and faces.shape == f_all.shape
+    assert np.array_equal(v.numpy()[faces.numpy().astype(np.int64)], v_all.numpy()[f_all.numpy().astype(np.int64)])
+    # a grid thinner than two points has no faces
+    for thin in ((1, 6, 6), (6, 1, 6), (6, 6, 1), (1, 1, 1)):
+        ff, ww = np.random.RandomState(1).uniform(-1, 1, thin[::-1]).astype(np.float32), np.ones(thin[::-1], np.float32)
+        assert mc.harness_counts(ff, ww)[1] == 0
+        assert mesh._extract_torch(torch.from_numpy(ff), torch.from_numpy(ww), None, (0, 0, 0), 1.0, 0.0, 1.0)[1].shape == (0, 3)
+
+
+def test_end_to_end_on_the_cpu_path():
+    """Six analytic sphere views into 24 x 20 x 16: the vertices lie within half a voxel of the sphere on average.  (At this image
+    resolution the fused mesh is not closed: depth discontinuities at the silhouettes leave unobserved points.)"""
+    dims = (24, 20, 16)
+    origin, voxel, _t = mc.volume_spec(dims)
+    vol = mesh.TSDFVolume(origin, dims, voxel, device="cpu")
+    assert vol.trunc == np.float32(4 * voxel) and float(vol.tsdf.min()) == 1 and float(vol.weight.max()) == 0
+    vol.integrate_many(_torch_views(mc.sphere_views(6)))
+    v, f, c = vol.extract_mesh()
+    err = np.abs(np.linalg.norm(v.numpy(), axis=1) - 1) / voxel
+    print(f"{len(v)} vertices, {len(f)} faces: | |v| - 1 | mean {err.mean():.3f}, max {err.max():.3f} voxels")
+    assert len(f) > 1000 and err.mean() < 0.5 and c.shape == v.shape and float(c.min()) >= 0 and float(c.max()) <= 1
+    assert mc.mesh_properties(v.numpy(), f.numpy())["volume"] > 0
+    vol.reset()
+    assert float(vol.tsdf.min()) == 1 and float(vol.weight.max()) == 0 and float(vol.color.abs().max()) == 0
+
+
+# ---- the header, the binding and the compiler -----------------------------------------------------------------------------------------
+def test_header_matches_binding():
+    declared = test_abi.check_extension_header("lightgaussian_mesh.h", mesh.PROTOTYPES)
+    assert len(declared) == 4 and declared["lg_mesh_scratch_bytes"] == ("size_t", ["int32", "int32", "int32"])
+    assert declared["lg_mesh_emit"] == ("int32", ["pointer", "float", "float", "pointer", "int64", "int64", "pointer", "pointer", "pointer", "uint32", "pointer"])
+    text = open(os.path.join(ROOT, "include", "lightgaussian_mesh.h")).read()
+    assert "#define LG_ABI_VERSION" not in text and '#include "lightgaussian.h"' in text
+    make = open(os.path.join(ROOT, "lightgaussian_amd", "csrc", "Makefile")).read()
+    assert "lg_tsdf.h" in make and "lightgaussian_mesh.h" in make
+    assert mesh.BATCH == mc.B == int(re.search(r"#define LG_TSDF_BATCH (\d+)", open(os.path.join(ROOT, "lightgaussian_amd", "csrc", "lg_tsdf.h")).read()).group(1))
+
+
+def test_struct_layouts_against_the_compiler(tmp_path):
+    text = test_abi._header_text((os.path.join(ROOT, "include", "lightgaussian_mesh.h"),))
+    structs = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(lg_\w+)\s*\{(.*?)\}\s*\1\s*;", text, flags=re.S):
+        structs[name] = [re.fullmatch(r".*?(\w+)\s*(?:\[\s*\d+\s*\])?", part.strip(), flags=re.S).group(1)
+                         for decl in body.split(";") if decl.strip() for part in decl.split(",")]
+    mirrors = {"lg_tsdf_volume": mesh.lg_tsdf_volume, "lg_tsdf_view": mesh.lg_tsdf_view}
+    assert set(structs) == set(mirrors)
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "lightgaussian_mesh.h"', "int main(void) {"]
+    for name, fields in structs.items():
+        assert fields == [f[0] for f in mirrors[name]._fields_], name
+        lines.append(f'    printf("{name} sizeof %zu\\n", sizeof({name}));')
+        lines += [f'    printf("{name} {f} %zu\\n", offsetof({name}, {f}));' for f in fields]
+    lines += ["    return 0;", "}"]
+    src, exe = tmp_path / "mesh_layout.cpp", tmp_path / "mesh_layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    measured = [line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines()]
+    assert len(measured) == sum(len(f) + 1 for f in structs.values())
+    for name, what, value in measured:
+        mine = C.sizeof(mirrors[name]) if what == "sizeof" else getattr(mirrors[name], what).offset
+        assert mine == int(value), f"{name} {what}: ctypes {mine}, the compiler {value}"
+    assert C.sizeof(mesh.lg_tsdf_volume) == 56 and C.sizeof(mesh.lg_tsdf_view) == 64
+    # the extension's structs are mirrored in mesh.py, not in _lib.py
+    assert not hasattr(_lib, "lg_tsdf_volume") and not hasattr(_lib, "lg_tsdf_view")
+
+
+# ---- refusals: before any device call, so they run without a device ---------------------------------------------------------------------
+FAKE = 0x10000          # an address nobody dereferences: every call below is refused, or returns, before the first device call
+
+
+def _volume(**kw):
+    f = dict(nx=8, ny=6, nz=4, origin=(0.0, 0.0, 0.0), voxel_size=0.1, trunc=0.4, tsdf=FAKE, weight=FAKE + 4096, color=FAKE + 8192)
+    f.update(kw)
+    return mesh.lg_tsdf_volume(f["nx"], f["ny"], f["nz"], (C.c_float * 3)(*f["origin"]), f["voxel_size"], f["trunc"], f["tsdf"], f["weight"], f["color"])
+
+
+def _view(**kw):
+    f = dict(W=33, H=17, tanfovx=0.5, tanfovy=0.3, viewmatrix=FAKE, depth=FAKE, color=FAKE, alpha=None, alpha_min=0.5, depth_max=0.0, z_min=0.05)
+    f.update(kw)
+    return mesh.lg_tsdf_view(*(f[n] for n, _t in mesh.lg_tsdf_view._fields_))
+
+
+def test_refusals_of_the_library():
+    lib = mesh.load()
+    nan, inf = float("nan"), float("inf")
+
+    def refused(rc, fn, *words):
+        assert rc == _lib.LG_ERR_INVALID_ARGUMENT, (fn, words, rc)
+        msg = lib.lg_last_error().decode()
+        assert msg.startswith(fn + ":") and all(w in msg for w in words), msg
+
+    volumes = [(dict(nx=0), "nx, ny, nz"), (dict(ny=-1), "nx, ny, nz"), (dict(nz=0), "nx, ny, nz"), (dict(nx=1 << 15, ny=1 << 14, nz=1), "2^29"),
+               (dict(nx=1024, ny=1024, nz=512), "2^29"), (dict(voxel_size=0.0), "voxel_size"), (dict(voxel_size=nan), "voxel_size"),
+               (dict(voxel_size=inf), "voxel_size"), (dict(trunc=-1.0), "trunc"), (dict(trunc=nan), "trunc"), (dict(origin=(0.0, nan, 0.0)), "origin"),
+               (dict(tsdf=None), "null tsdf"), (dict(weight=None), "null weight"), (dict(tsdf=FAKE + 2), "tsdf must be 4-byte aligned"),
+               (dict(weight=FAKE + 1), "weight must be 4-byte aligned"), (dict(color=FAKE + 3), "color must be 4-byte aligned")]
+    one = (mesh.lg_tsdf_view * 1)(_view())
+    counts = C.c_void_p(FAKE)
+    for kw, word in volumes:
+        v = _volume(**kw)
+        refused(lib.lg_tsdf_integrate(C.byref(v), 1, one, 0, None), "lg_tsdf_integrate", word)
+        refused(lib.lg_mesh_count(C.byref(v), 0.0, 1.0, C.c_void_p(FAKE), counts, 0, None), "lg_mesh_count", word)
+        refused(lib.lg_mesh_emit(C.byref(v), 0.0, 1.0, C.c_void_p(FAKE), 3, 1, C.c_void_p(FAKE), None, C.c_void_p(FAKE), 0, None), "lg_mesh_emit", word)
+    vol = _volume()
+    refused(lib.lg_tsdf_integrate(None, 1, one, 0, None), "lg_tsdf_integrate", "null volume")
+    refused(lib.lg_tsdf_integrate(C.byref(vol), -1, one, 0, None), "lg_tsdf_integrate", "n_views < 0")
+    refused(lib.lg_tsdf_integrate(C.byref(vol), 1, None, 0, None), "lg_tsdf_integrate", "null views")
+    views = [(dict(W=0), "W outside"), (dict(W=32769), "W outside"), (dict(H=0), "H outside"), (dict(H=-5), "H outside"), (dict(H=32769), "H outside"),
+             (dict(tanfovx=nan), "tanfovx is NaN"), (dict(tanfovy=nan), "tanfovy is NaN"), (dict(z_min=nan), "NaN"), (dict(depth_max=nan), "NaN"),
+             (dict(alpha_min=nan), "NaN"), (dict(viewmatrix=None), "null viewmatrix"), (dict(depth=None), "null depth"), (dict(color=None), "null color"),
+             (dict(depth=FAKE + 2), "4-byte aligned"), (dict(alpha=FAKE + 1), "4-byte aligned"), (dict(viewmatrix=FAKE + 2), "4-byte aligned")]
+    for kw, word in views:
+        arr = (mesh.lg_tsdf_view * 3)(_view(), _view(), _view(**kw))
+        refused(lib.lg_tsdf_integrate(C.byref(vol), 3, arr, 0, None), "lg_tsdf_integrate", "views[2]", word)
+    # a volume without colour takes views without colour; no view at all is LG_OK without a launch
+    assert lib.lg_tsdf_integrate(C.byref(vol), 0, None, 0, None) == _lib.LG_OK
+    assert lib.lg_tsdf_integrate(C.byref(_volume(color=None)), 0, (mesh.lg_tsdf_view * 1)(_view(color=None)), 0, None) == _lib.LG_OK
+    sc = C.c_void_p(FAKE)
+    for iso, mw, word in ((nan, 1.0, "iso"), (inf, 1.0, "iso"), (0.0, 0.0, "min_weight"), (0.0, -1.0, "min_weight"), (0.0, nan, "min_weight"), (0.0, inf, "min_weight")):
+        refused(lib.lg_mesh_count(C.byref(vol), iso, mw, sc, counts, 0, None), "lg_mesh_count", word)
+        refused(lib.lg_mesh_emit(C.byref(vol), iso, mw, sc, 3, 1, sc, None, sc, 0, None), "lg_mesh_emit", word)
+    refused(lib.lg_mesh_count(C.byref(vol), 0.0, 1.0, None, counts, 0, None), "lg_mesh_count", "null scratch")
+    refused(lib.lg_mesh_count(C.byref(vol), 0.0, 1.0, C.c_void_p(FAKE + 16), counts, 0, None), "lg_mesh_count", "scratch must be 256-byte aligned")
+    refused(lib.lg_mesh_count(C.byref(vol), 0.0, 1.0, sc, None, 0, None), "lg_mesh_count", "null counts")
+    refused(lib.lg_mesh_count(C.byref(vol), 0.0, 1.0, sc, C.c_void_p(FAKE + 4), 0, None), "lg_mesh_count", "counts must be 8-byte aligned")
+    refused(lib.lg_mesh_emit(C.byref(vol), 0.0, 1.0, None, 3, 1, sc, None, sc, 0, None), "lg_mesh_emit", "null scratch")
+    refused(lib.lg_mesh_emit(C.byref(vol), 0.0, 1.0, sc, -1, 1, sc, None, sc, 0, None), "lg_mesh_emit", "n_vertices outside")
+    refused(lib.lg_mesh_emit(C.byref(vol), 0.0, 1.0, sc, 3, 1 << 31, sc, None, sc, 0, None), "lg_mesh_emit", "n_faces outside")
+    refused(lib.lg_mesh_emit(C.byref(vol), 0.0, 1.0, sc, 3, 1, None, None, sc, 0, None), "lg_mesh_emit", "null vertices")
+    refused(lib.lg_mesh_emit(C.byref(vol), 0.0, 1.0, sc, 3, 1, sc, None, None, 0, None), "lg_mesh_emit", "null faces")
+    refused(lib.lg_mesh_emit(C.byref(vol), 0.0, 1.0, sc, 3, 1, sc, C.c_void_p(FAKE + 2), sc, 0, None), "lg_mesh_emit", "colors must be 4-byte aligned")
+    refused(lib.lg_mesh_emit(C.byref(vol), 0.0, 1.0, sc, 3, 1, C.c_void_p(FAKE + 2), None, sc, 0, None), "lg_mesh_emit", "vertices must be 4-byte aligned")
+    refused(lib.lg_mesh_emit(C.byref(_volume(color=None)), 0.0, 1.0, sc, 3, 1, sc, sc, sc, 0, None), "lg_mesh_emit", "keeps no colour")
+    assert lib.lg_mesh_scratch_bytes(0, 4, 4) == 0 and lib.lg_mesh_scratch_bytes(1024, 1024, 512) == 0
+    assert lib.lg_mesh_scratch_bytes(8, 6, 4) >= 8 * 6 * 4 * 10 + 16 and lib.lg_mesh_scratch_bytes(8, 6, 4) % 256 == 0
+
+
+def test_refusals_of_the_python_surface():
+    dims = (5, 4, 3)
+    origin, voxel, _t = mc.volume_spec(dims)
+    cam = syn.orbit_camera(0, 6, 6, 5, radius=4.0)
+    depth, color, alpha = torch.rand(5, 6), torch.rand(3, 5, 6), torch.rand(5, 6)
+    vol = mesh.TSDFVolume(origin, dims, voxel, device="cpu")
+    plain = mesh.TSDFVolume(origin, dims, voxel, color=False, device="cpu")
+    plain.integrate(depth, cam)                          # no colour kept: none asked
+    plain.integrate(depth, cam, color=color)             # ... and one given is ignored
+    bad = [lambda: mesh.TSDFVolume(origin, (0, 4, 3), voxel, device="cpu"), lambda: mesh.TSDFVolume(origin, (1024, 1024, 512), voxel, device="meta"),
+           lambda: mesh.TSDFVolume(origin, dims, 0.0, device="cpu"), lambda: mesh.TSDFVolume(origin, dims, voxel, trunc=float("nan"), device="cpu"),
+           lambda: mesh.TSDFVolume(origin[:2], dims, voxel, device="cpu"), lambda: mesh.TSDFVolume(origin, dims, voxel, device="cpu", backend="triton"),
+           lambda: vol.integrate(depth, cam), lambda: vol.integrate(depth.double(), cam, color=color), lambda: vol.integrate(depth[None], cam, color=color),
+           lambda: vol.integrate(depth, cam, color=color[:2]), lambda: vol.integrate(depth, cam, color=color, alpha=alpha[:4]),
+           lambda: vol.integrate(depth.numpy(), cam, color=color), lambda: vol.integrate(depth, cam, color=color, z_min=float("nan")),
+           lambda: vol.integrate(depth.to("meta"), cam, color=color), lambda: vol.integrate_many([dict(depth=depth, camera=cam, color=color, colour=1)]),
+           lambda: vol.extract_mesh(min_weight=0.0), lambda: vol.extract_mesh(iso=float("inf")),
+           lambda: mesh.fuse_views([], None, None, vol, depth="expected")]
+    for k, call in enumerate(bad):
+        with pytest.raises(ValueError):
+            call()
+            pytest.fail(f"call {k} was accepted")
+    vol.integrate_many([])                               # no view: nothing happens
+    assert float(vol.weight.max()) == 0
+    # contiguity is asked of GPU tensors by backend='hip' (no device needed to see the check: a fake .is_cuda)
+    fake = types.SimpleNamespace(backend="hip", tsdf=types.SimpleNamespace(is_cuda=True))
+    with pytest.raises(ValueError, match="contiguous"):
+        mesh.TSDFVolume._resolve(fake, "integrate", (("depth", types.SimpleNamespace(is_contiguous=lambda: False)),))
+    assert vol._resolve("integrate", (("depth", depth.t()),)) == "torch"
+
+
+def test_bounds_and_ply(tmp_path):
+    cams = [syn.orbit_camera(k, 6, 33, 17, radius=4.0, height_y=-1.5) for k in range(6)]
+    origin, dims = mesh.bounds_from_cameras(cams, 0.25, scale=0.5)
+    assert dims[0] == dims[1] == dims[2] and dims[0] % 4 == 0 and dims[0] * 0.25 >= 4.0
+    centre = np.array(origin) + 0.5 * (dims[0] - 1) * 0.25
+    assert np.abs(centre - np.array([0.0, -1.5, 0.0])).max() < 1e-5
+    v = torch.tensor([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.5], [1.0, 1.0, 1.0]])
+    f = torch.tensor([[0, 1, 2], [1, 3, 2]], dtype=torch.int32)
+    c = torch.tensor([[0.0, 0.5, 1.0], [1.0, 1.0, 1.0], [0.25, 0.25, 0.25], [2.0, -1.0, 0.0]])
+    for colors, vsize in ((None, 12), (c, 15)):
+        path = tmp_path / "m.ply"
+        mesh.save_ply(str(path), v, f, colors)
+        raw = path.read_bytes()
+        head, body = raw.split(b"end_header\n", 1)
+        assert head.startswith(b"ply\nformat binary_little_endian 1.0\nelement vertex 4\n") and b"element face 2\n" in head
+        assert (b"property uchar red" in head) == (colors is not None) and len(body) == 4 * vsize + 2 * 13
+        assert struct.unpack_from("<3f", body, 2 * vsize) == (0.0, 1.0, 0.5) and struct.unpack_from("<B3i", body, 4 * vsize + 13) == (3, 1, 3, 2)
+        if colors is not None:
+            assert struct.unpack_from("<3B", body, 12) == (0, 128, 255) and struct.unpack_from("<3B", body, 3 * vsize + 12) == (255, 0, 0)
