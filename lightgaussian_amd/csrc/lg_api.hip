@@ -36,6 +36,8 @@
 //                    depth map, the fused depth-normal consistency loss (include/lightgaussian_normals.h; a wave per strip, register ring)
 //   lg_distortion.h  lg_distortion_fwd / _bwd: depth distortion and median depth over the lists a forward left, and their gradient into K7's
 //                    moment rows and a per-instance dm row (include/lightgaussian_distortion.h; lg_features.h's walks)
+//   lg_sensitivity.h lg_sensitivity_walk / _accum / _score_kernel: the per-Gaussian 6 x 6 Gauss-Newton blocks over (mean, scale) from twelve moments
+//                    per instance, and their log-determinants (include/lightgaussian_sensitivity.h; lg_features.h's back-to-front walk)
 //   lg_tsdf.h        lg_tsdf_integrate / lg_mesh_count / lg_mesh_emit: depth maps of up to 8 views per pass into a dense TSDF volume, and marching
 //                    tetrahedra over it with indexed vertices (include/lightgaussian_mesh.h; count, scan, emit: no atomics)
 //
@@ -75,6 +77,7 @@
 #include "lg_filter3d.h"
 #include "lg_normals.h"
 #include "lg_distortion.h"
+#include "lg_sensitivity.h"
 #include "lg_tsdf.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -273,6 +276,8 @@ static decltype(&lg_adam_rows_kernel<false>) adam_rows_kernel(bool decoupled) { 
 static decltype(&lg_filter3d_apply_kernel<false>) filter3d_apply_kernel(bool raw) { return LG_BY_FLAG(lg_filter3d_apply_kernel, raw); }
 static decltype(&lg_filter3d_apply_bwd_kernel<false>) filter3d_apply_bwd_kernel(bool raw) { return LG_BY_FLAG(lg_filter3d_apply_bwd_kernel, raw); }
 static decltype(&lg_distortion_fwd<false>) distortion_fwd_kernel(bool exact) { return LG_BY_FLAG(lg_distortion_fwd, exact); }
+static decltype(&lg_sensitivity_walk<false>) sensitivity_walk_kernel(bool exact) { return LG_BY_FLAG(lg_sensitivity_walk, exact); }
+static decltype(&lg_sensitivity_accum<false>) sensitivity_accum_kernel(bool raw) { return LG_BY_FLAG(lg_sensitivity_accum, raw); }
 #undef LG_BY_FLAG
 
 // Arguments of the capacity-bounded forward (lg_forward_bounded); NULL = exact forward with its one read-back.
@@ -2167,6 +2172,60 @@ extern "C" int lg_backward_distortion(const lg_view* v, const lg_gaussians* g, c
         lg_features_gather<<<(unsigned)(((size_t)N + 255) / 256), 256, 0, stream>>>(N, 1, 0, 1, f.live, f.cap, s.geo.touched, s.geo.offsets, s.geo.counters, dm_rows, dL_dm);
     }
     KCHECK("lg_features_gather");
+    return LG_OK;
+}
+
+// ---- sensitivity pruning score (lg_sensitivity.h, include/lightgaussian_sensitivity.h) ----
+// scratch = the moment rows [num_rendered][12]
+extern "C" size_t lg_sensitivity_scratch_bytes(int32_t N, int64_t num_rendered)
+{
+    (void)N;
+    if (num_rendered < 0) return 0;
+    return align_up((size_t)(num_rendered > 0 ? num_rendered : 1) * LG_SENS_NV * sizeof(float));
+}
+
+extern "C" int lg_sensitivity_accumulate(const lg_view* v, const lg_gaussians* g, const int32_t* radii, const void* geom_p, const void* bin_p,
+                                         const void* img_p, int64_t R, double* H, void* scratch, void* stream_p)
+{
+    const char* who = "lg_sensitivity_accumulate";
+    int rc = check_args(v, g);
+    if (rc != LG_OK) return rc;
+    if (v->flags & LG_FLAG_ANTIALIAS) return refuse(who, "LG_FLAG_ANTIALIAS is not supported (the compensated opacity depends on the covariance)");
+    if ((v->flags & (LG_FLAG_SKIP_COLOR | LG_FLAG_SCORE_MAX)) || v->count_sum) return refuse(who, "needs the buffers of a colour forward, not of a count forward");
+    if (R < 0 || R >= (1ll << 30)) return refuse(who, "num_rendered out of range");
+    if (g->N == 0) return LG_OK;          // nothing to add
+    if (!H) return refuse(who, "missing H");
+    if (g->cov3D_precomp) return refuse(who, "needs scales and rotations (cov3D_precomp has no scale to differentiate)");
+    if (!radii || !geom_p || !img_p || !scratch) return refuse(who, "missing buffer");
+    if (R > 0 && !bin_p) return refuse(who, "missing binning buffer");
+    const int N = g->N;
+    const auto [stream, debug, prof, exact, s, f] = walk_call(v, N, geom_p, img_p, bin_p, R, stream_p);
+    if (!f.live) return LG_OK;            // no instances: every H keeps its value
+    const ViewGeom& q = s.q; const GeomView& geo = s.geo; const ImgView& img = s.img; const BinView& bin = s.bin;
+    float* rows = (float*)scratch;        // [R][12] moment rows, every row written by lg_sensitivity_walk
+    {
+        ProfScope ps(prof, "sensitivity_walk", stream);
+        sensitivity_walk_kernel(exact)<<<q.ntiles_pad, 256, 0, stream>>>(f, (uint32_t)q.S, bin.meta, geo.tinfo, v->bg, img.final_T, img.n_contrib, rows);
+    }
+    KCHECK("lg_sensitivity_walk");
+    {
+        ProfScope ps(prof, "sensitivity_accum", stream);
+        sensitivity_accum_kernel(v->flags & LG_FLAG_RAW_PARAMS)<<<(unsigned)(((size_t)N + LG_SENS_THREADS - 1) / LG_SENS_THREADS), LG_SENS_THREADS, 0, stream>>>(
+            N, q.W, q.H, v->tanfovx, v->tanfovy, v->scale_modifier, (uint32_t)R, v->viewmatrix, v->projmatrix, g->means3D, g->scales, g->rotations, radii,
+            geo.rec, geo.counters, bin.meta, (uint32_t)q.S, geo.touched, geo.offsets, reinterpret_cast<const float4*>(rows), H);
+    }
+    KCHECK("lg_sensitivity_accum");
+    return LG_OK;
+}
+
+extern "C" int lg_sensitivity_score(int32_t N, const double* H, const float* scales, double* out, void* stream_p)
+{
+    if (N < 0 || N >= LG_ROWS_MAX) return refuse("lg_sensitivity_score", "N out of range");
+    if (N == 0) return LG_OK;
+    if (!H || !out) return refuse("lg_sensitivity_score", "missing H / out");
+    hipStream_t stream = (hipStream_t)stream_p;
+    lg_sensitivity_score_kernel<<<(unsigned)(((size_t)N + LG_SENS_THREADS - 1) / LG_SENS_THREADS), LG_SENS_THREADS, 0, stream>>>(N, H, scales, out);
+    KLAUNCHED("lg_sensitivity_score_kernel");
     return LG_OK;
 }
 

@@ -1357,3 +1357,143 @@ LG_HD uint32_t lg_mesh_cell_faces(int nx, int ny, int x, int y, int z, uint32_t 
     }
     return nf;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Sensitivity pruning score (lg_sensitivity.h, include/lightgaussian_sensitivity.h): the per-Gaussian 6 x 6 block
+//   H_i = sum_views sum_pixels sum_channels (dI_c/dtheta_i)(dI_c/dtheta_i)^T,   theta_i = (mean3D, activated scale),
+// of the Gauss-Newton Hessian of the L2 reconstruction error, colours held constant, and score = log det H_i.  A pixel depends on theta_i
+// through the 2D mean and the conic only, so dI_c/dtheta_i = v_c G u^T B A with
+//   v_c = (c_c - S_c) Tn - T_final bg_c / (1 - alpha)      lg_feature_bwd_step's dL/dalpha with q = c_c, Tfb = T_final bg_c, per channel
+//   u   = (dx, dy, dx^2, dx dy, dy^2)                      the monomials of its moments m[0..4]
+//   B                                                      lg_rows_to_grads' per-Gaussian coefficients: acc[0..4] = B (t u), t = G v_c
+//   A   [5][6]                                             row k = lg_backward_geom_t<false> + lg_backward_cov3d of acc = e_k (the chain is linear in acc)
+// and H_i(view) = A^T M A, M = B U B^T, U = sum_pixels w u u^T, w = |v|^2 G^2.  U's entries are the twelve moments sum w dx^a dy^b,
+// 2 <= a + b <= 4 -- non-negative multiples of monomials, no cancellation in their sums -- in the order of LG_SENS_MOMENTS below.
+#define LG_SENS_NV 12           // dx2, dxdy, dy2 | dx3, dx2dy, dxdy2, dy3 | dx4, dx3dy, dx2dy2, dxdy3, dy4
+#define LG_SENS_H 21            // the upper triangle of a 6 x 6 block, row-major
+#define LG_SENS_PIVOT_MIN 0x1p-26
+
+// One (pixel, entry) step of the back-to-front replay: lg_feature_bwd_step's decisions and recurrences for three colour channels at
+// once (c = the entry's colour, Tfb[k] = T_final bg[k], S[k] = the colour blended behind the entry, starts at 0; T starts at final_T),
+// then m[0..11] += w {monomials}.  Straight through the 0.99 clamp; power > 0 and alpha < 1/255 take no part.  Returns false (nothing
+// touched) when the entry does not contribute.  EXACT = false on the device: v_rcp_f32 for 1 / (1 - alpha), as K7's fast path.
+template <bool EXACT>
+LG_HD bool lg_sensitivity_step(bool live, float power, float G, float alpha, float dx, float dy, const float* c, const float* Tfb, float& T,
+                               float* S, float* m)
+{
+    if (!live || !(power <= 0.0f) || alpha < LG_ALPHA_MIN) return false;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float inv = EXACT ? 1.0f / (1.0f - alpha) : __builtin_amdgcn_rcpf(1.0f - alpha);
+#else
+    const float inv = 1.0f / (1.0f - alpha);
+#endif
+    const float Tn = T * inv;
+    float vv = 0.0f;
+    for (int k = 0; k < 3; k++) {
+        const float d = c[k] - S[k];
+        const float v = d * Tn - Tfb[k] * inv;
+        vv += v * v;
+        S[k] = S[k] + alpha * d;
+    }
+    const float w = vv * (G * G);
+    const float xx = dx * dx, xy = dx * dy, yy = dy * dy;
+    const float wxx = w * xx, wxy = w * xy, wyy = w * yy;
+    m[0] += wxx;
+    m[1] += wxy;
+    m[2] += wyy;
+    m[3] += wxx * dx;
+    m[4] += wxx * dy;
+    m[5] += wyy * dx;
+    m[6] += wyy * dy;
+    m[7] += wxx * xx;
+    m[8] += wxx * xy;
+    m[9] += wxx * yy;
+    m[10] += wyy * xy;
+    m[11] += wyy * yy;
+    T = Tn;
+    return true;
+}
+
+// moments -> M = B U B^T (upper triangle, row-major [15]), float64.  U[a][b] = sum w u_a u_b read from the twelve moments; B from the
+// record's conic (ha = -A/2, nb = -B, hc = -C/2) and opacity, lg_rows_to_grads' coefficients:
+//   acc0 = op (2 ha u0 + nb u1)   acc1 = op (nb u0 + 2 hc u1)   acc2 = -op u2 / 2   acc3 = -op u3   acc4 = -op u4 / 2
+LG_HD void lg_sensitivity_moments_to_M(const double* mo, float ha, float nb, float hc, float op, double* M)
+{
+    const double U[5][5] = {
+        { mo[0], mo[1], mo[3], mo[4], mo[5] },
+        { mo[1], mo[2], mo[4], mo[5], mo[6] },
+        { mo[3], mo[4], mo[7], mo[8], mo[9] },
+        { mo[4], mo[5], mo[8], mo[9], mo[10] },
+        { mo[5], mo[6], mo[9], mo[10], mo[11] } };
+    const double o = (double)op;
+    const double p = 2.0 * (double)ha * o, q = (double)nb * o, r = 2.0 * (double)hc * o;
+    const double d[3] = { -0.5 * o, -o, -0.5 * o };
+    // rows 0, 1 of B U: the 2 x 2 block mixes u0, u1; rows 2..4 scale
+    double BU[5][5];
+    for (int b = 0; b < 5; b++) {
+        BU[0][b] = p * U[0][b] + q * U[1][b];
+        BU[1][b] = q * U[0][b] + r * U[1][b];
+        BU[2][b] = d[0] * U[2][b];
+        BU[3][b] = d[1] * U[3][b];
+        BU[4][b] = d[2] * U[4][b];
+    }
+    int k = 0;
+    for (int a = 0; a < 5; a++)
+        for (int b = a; b < 5; b++, k++) {
+            if (b == 0) M[k] = BU[a][0] * p + BU[a][1] * q;
+            else if (b == 1) M[k] = BU[a][0] * q + BU[a][1] * r;
+            else M[k] = BU[a][b] * d[b - 2];
+        }
+}
+
+// H[21] += A^T M A (upper triangle, row-major), float64: A [5][6] float32 (the chain's own precision), M [15] from above.
+LG_HD void lg_sensitivity_AtMA(const float (*A)[6], const double* M, double* H)
+{
+    double Mf[5][5];
+    int k = 0;
+    for (int a = 0; a < 5; a++)
+        for (int b = a; b < 5; b++, k++) { Mf[a][b] = M[k]; Mf[b][a] = M[k]; }
+    double MA[5][6];
+    for (int a = 0; a < 5; a++)
+        for (int j = 0; j < 6; j++) {
+            double s = 0.0;
+            for (int b = 0; b < 5; b++) s += Mf[a][b] * (double)A[b][j];
+            MA[a][j] = s;
+        }
+    k = 0;
+    for (int i = 0; i < 6; i++)
+        for (int j = i; j < 6; j++, k++) {
+            double s = 0.0;
+            for (int a = 0; a < 5; a++) s += (double)A[a][i] * MA[a][j];
+            H[k] += s;
+        }
+}
+
+// log det of a 6 x 6 block given as its upper triangle [21]: Cholesky H = L L^T in float64, 2 sum_k log L_kk; -inf at the first pivot
+// that is not positive.  "Not positive" is taken up to the rounding the block carries: a pivot must exceed LG_SENS_PIVOT_MIN (2^-26) of
+// its diagonal entry.  A block of rank 5 (one view: A has five rows) leaves a last pivot of either sign, measured up to 5e-11 of the
+// diagonal entry on the golden scene (float64 rounding times the growth of the elimination); and A and the moments are float32, so a
+// pivot below 2^-26 of its diagonal is below what the inputs resolve.
+LG_HD double lg_sensitivity_logdet(const double* H)
+{
+    double L[6][6];
+    int k = 0;
+    for (int i = 0; i < 6; i++)
+        for (int j = i; j < 6; j++, k++) L[j][i] = H[k];        // lower triangle holds the block
+    double s = 0.0;
+    for (int j = 0; j < 6; j++) {
+        const double ajj = L[j][j];
+        double d = ajj;
+        for (int u = 0; u < j; u++) d -= L[j][u] * L[j][u];
+        if (!(d > LG_SENS_PIVOT_MIN * ajj) || !(ajj > 0.0)) return -(double)INFINITY;
+        const double l = sqrt(d);
+        L[j][j] = l;
+        s += log(l);
+        for (int i = j + 1; i < 6; i++) {
+            double t = L[i][j];
+            for (int u = 0; u < j; u++) t -= L[i][u] * L[j][u];
+            L[i][j] = t / l;
+        }
+    }
+    return 2.0 * s;
+}
