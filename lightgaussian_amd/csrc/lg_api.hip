@@ -40,6 +40,8 @@
 //                    per instance, and their log-determinants (include/lightgaussian_sensitivity.h; lg_features.h's back-to-front walk)
 //   lg_tsdf.h        lg_tsdf_integrate / lg_mesh_count / lg_mesh_emit: depth maps of up to 8 views per pass into a dense TSDF volume, and marching
 //                    tetrahedra over it with indexed vertices (include/lightgaussian_mesh.h; count, scan, emit: no atomics)
+//   lg_blocks.h      lg_blocks_touch / _merge / _regrid / _integrate / _mesh_count / _mesh_emit: the same fusion and extraction over a block-sparse
+//                    volume for unbounded scenes, blocks allocated from the depth maps and kept in sorted-key order (include/lightgaussian_blocks.h)
 //
 // Pipeline of one view:
 //   K1 project + EWA + SH->RGB + exact footprint culling  ->  K2 scan of instance counts, blocking read of R
@@ -79,6 +81,7 @@
 #include "lg_distortion.h"
 #include "lg_sensitivity.h"
 #include "lg_tsdf.h"
+#include "lg_blocks.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1878,6 +1881,293 @@ extern "C" int lg_mesh_emit(const lg_tsdf_volume* vol, float iso, float min_weig
     lg_mesh_emit_kernel<<<(unsigned)((P + 255) / 256), 256, 0, stream>>>(d, P, org, iso, min_weight, vol->tsdf, vol->weight, vol->color, s.vprefix, s.fprefix,
                                                                           s.vmask, s.fcount, n_vertices, n_faces, vertices, colors, faces);
     KLAUNCHED("lg_mesh_emit_kernel");
+    return LG_OK;
+}
+
+// ---- block-sparse TSDF volume (lg_blocks.h, include/lightgaussian_blocks.h) ----
+// the checks of a block volume every entry point shares
+static int block_volume(const char* who, const lg_block_volume* vol, const char* name = "volume")
+{
+    char what[96];
+    auto bad = [&](const char* text) { snprintf(what, sizeof(what), "%s: %s", name, text); return refuse(who, what); };
+    if (!vol) return bad("null volume");
+    if (vol->n_blocks < 0 || vol->n_blocks >= LG_BLK_MAX_BLOCKS) return bad("n_blocks outside [0, 2^20): n_blocks 512 must stay below 2^29");
+    if (!positive_finite(vol->voxel_size)) return bad("voxel_size must be positive and finite");
+    if (!(vol->trunc > 0.0f && vol->trunc <= 4.0f * vol->voxel_size)) return bad("trunc must lie in (0, 4 voxel_size]");
+    for (int a = 0; a < 3; a++)
+        if (!finite_f(vol->origin[a])) return bad("origin must be finite");
+    if (vol->n_blocks == 0) return LG_OK;
+    if (!vol->keys) return bad("null keys");
+    if ((uintptr_t)vol->keys & 7) return bad("keys must be 8-byte aligned");
+    if (!vol->tsdf) return bad("null tsdf");
+    if (!vol->weight) return bad("null weight");
+    if ((uintptr_t)vol->tsdf & 15) return bad("tsdf must be 16-byte aligned");
+    if ((uintptr_t)vol->weight & 15) return bad("weight must be 16-byte aligned");
+    if ((uintptr_t)vol->color & 15) return bad("color must be 16-byte aligned");
+    return LG_OK;
+}
+// the checks of the views lg_blocks_touch and lg_blocks_integrate share; need_color: the volume keeps colour and the call reads it
+static int block_views(const char* who, int32_t n_views, const lg_tsdf_view* views, bool need_color)
+{
+    if (n_views < 0) return refuse(who, "n_views < 0");
+    if (n_views > 0 && !views) return refuse(who, "null views");
+    for (int i = 0; i < n_views; i++) {
+        const lg_tsdf_view& v = views[i];
+        char what[96];
+        auto bad = [&](const char* text) { snprintf(what, sizeof(what), "views[%d]: %s", i, text); return refuse(who, what); };
+        if (v.H < 1 || v.H > LG_TSDF_MAX_DIM) return bad("H outside [1, 32768]");
+        if (v.W < 1 || v.W > LG_TSDF_MAX_DIM) return bad("W outside [1, 32768]");
+        if (v.tanfovx != v.tanfovx) return bad("tanfovx is NaN");
+        if (v.tanfovy != v.tanfovy) return bad("tanfovy is NaN");
+        if (v.alpha_min != v.alpha_min || v.depth_max != v.depth_max || v.z_min != v.z_min) return bad("alpha_min, depth_max or z_min is NaN");
+        if (!v.viewmatrix) return bad("null viewmatrix");
+        if (!v.depth) return bad("null depth");
+        if (need_color && !v.color) return bad("null color for a volume that keeps colour");
+        if (((uintptr_t)v.viewmatrix | (uintptr_t)v.depth | (uintptr_t)(need_color ? v.color : nullptr) | (uintptr_t)v.alpha) & 3)
+            return bad("viewmatrix, depth, color and alpha must be 4-byte aligned");
+    }
+    return LG_OK;
+}
+static LgBlkVol block_vol_arg(const lg_block_volume* vol) { return { { vol->origin[0], vol->origin[1], vol->origin[2] }, vol->voxel_size, vol->trunc }; }
+static int64_t block_touch_waves(int32_t n_views, const lg_tsdf_view* views, int64_t* pixels = nullptr)
+{
+    int64_t waves = 0, px = 0;
+    for (int i = 0; i < n_views; i++) { waves += lg_blk_touch_waves(views[i].W, views[i].H); px += (int64_t)views[i].W * views[i].H; }
+    if (pixels) *pixels = px;
+    return waves;
+}
+// scratch of lg_blocks_touch: [2] int64 totals, then wave_n [2][waves]
+static size_t block_touch_bytes(int64_t waves) { return align_up(16) + align_up((size_t)std::max<int64_t>(waves, 1) * 8); }
+
+extern "C" size_t lg_blocks_touch_scratch_bytes(int32_t n_views, const lg_tsdf_view* views)
+{
+    if (n_views < 0 || (n_views > 0 && !views)) return 0;
+    for (int i = 0; i < n_views; i++)
+        if (views[i].W < 1 || views[i].W > LG_TSDF_MAX_DIM || views[i].H < 1 || views[i].H > LG_TSDF_MAX_DIM) return 0;
+    return block_touch_bytes(block_touch_waves(n_views, views));
+}
+
+extern "C" int lg_blocks_touch(const lg_block_volume* vol, int32_t n_views, const lg_tsdf_view* views, int64_t capacity, int64_t* candidates, int64_t* stats,
+                               void* scratch, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_blocks_touch";
+    int rc = block_volume(who, vol);
+    if (rc == LG_OK) rc = block_views(who, n_views, views, false);
+    if (rc != LG_OK) return rc;
+    if (capacity < 0 || capacity >= (1ll << 30)) return refuse(who, "capacity outside [0, 2^30)");
+    if (capacity > 0 && !candidates) return refuse(who, "null candidates");
+    if ((uintptr_t)candidates & 7) return refuse(who, "candidates must be 8-byte aligned");
+    if (!stats) return refuse(who, "null stats");
+    if ((uintptr_t)stats & 7) return refuse(who, "stats must be 8-byte aligned");
+    if (!scratch) return refuse(who, "null scratch");
+    if ((uintptr_t)scratch & 255) return refuse(who, "scratch must be 256-byte aligned");
+    int64_t pixels = 0;
+    const int64_t waves = block_touch_waves(n_views, views, &pixels);
+    if (pixels >= LG_BLK_TOUCH_MAX_PIXELS) return refuse(who, "views: 2^26 pixels or more in one call");
+    hipStream_t stream = (hipStream_t)stream_p;
+    int64_t* totals = (int64_t*)scratch;
+    uint32_t* wave_n = (uint32_t*)((char*)scratch + align_up(16));
+    const LgBlkVol g = block_vol_arg(vol);
+    ProfScope ps(flags & LG_FLAG_PROFILE, "blocks_touch", stream);
+    for (int emit = 0; emit < 2; emit++) {
+        uint32_t wave_base = 0;
+        for (int first = 0; first < n_views; first += LG_TSDF_BATCH) {
+            const int n = std::min(LG_TSDF_BATCH, n_views - first);
+            LgBlkTouchBatch b;
+            memset(&b, 0, sizeof(b));
+            uint32_t end = 0;
+            for (int k = 0; k < n; k++) {
+                const lg_tsdf_view& v = views[first + k];
+                end += lg_blk_touch_waves(v.W, v.H);
+                b.v[k] = { v.viewmatrix, v.depth, v.alpha, { v.W, v.H, v.tanfovx, v.tanfovy, v.depth_max, v.z_min, v.alpha_min }, end,
+                           (uint32_t)((v.W + LG_BLK_TOUCH_TILE - 1) / LG_BLK_TOUCH_TILE) };
+            }
+            const unsigned wgs = (end + 3) / 4;
+            if (emit) lg_blk_touch_kernel<true><<<wgs, 256, 0, stream>>>(g, n, b, end, wave_base, (uint32_t)waves, wave_n, capacity, candidates);
+            else lg_blk_touch_kernel<false><<<wgs, 256, 0, stream>>>(g, n, b, end, wave_base, (uint32_t)waves, wave_n, capacity, candidates);
+            KLAUNCHED("lg_blk_touch_kernel");
+            wave_base += end;
+        }
+        if (!emit) {
+            // channel 0: candidates per wave -> exclusive prefix, total to stats[1]; channel 1: skipped pixels, total to stats[2]
+            lg_mesh_scan_kernel<<<2, 1024, 0, stream>>>((size_t)waves, wave_n, stats + 1, totals);
+            KLAUNCHED("lg_mesh_scan_kernel");
+        }
+    }
+    if (capacity > 0) {
+        lg_blk_pad_kernel<<<(unsigned)std::min<int64_t>((capacity + 255) / 256, 1024), 256, 0, stream>>>(totals, capacity, candidates);
+        KLAUNCHED("lg_blk_pad_kernel");
+    }
+    return LG_OK;
+}
+
+// scratch of lg_blocks_merge: keys_in [n], sorted [n], blk [ceil(n / 1024)], [2] int64, the sort's temp storage
+struct LgBlkMergeScratch { uint64_t* keys_in; uint64_t* sorted; uint32_t* blk; int64_t* copy; void* sort_temp; size_t sort_bytes, total; };
+static LgBlkMergeScratch carve_blk_merge(void* base, size_t n)
+{
+    LgBlkMergeScratch s; size_t off = 0; char* p = (char*)base;
+    auto take = [&](size_t bytes) { void* r = p ? p + off : nullptr; off += align_up(bytes); return r; };
+    const size_t m = std::max<size_t>(n, 1);
+    s.keys_in = (uint64_t*)take(m * 8);
+    s.sorted = (uint64_t*)take(m * 8);
+    s.blk = (uint32_t*)take((m + 1023) / 1024 * 4);
+    s.copy = (int64_t*)take(16);
+    s.sort_bytes = lg_sort_layout(m).total;
+    s.sort_temp = take(s.sort_bytes);
+    s.total = off;
+    return s;
+}
+extern "C" size_t lg_blocks_merge_scratch_bytes(int64_t n) { return (n < 0 || n >= (1ll << 30)) ? 0 : carve_blk_merge(nullptr, (size_t)n).total; }
+
+extern "C" int lg_blocks_merge(int64_t n_old, const int64_t* old_keys, int64_t n_add, const int64_t* add_keys, int64_t* merged, int64_t* count, void* scratch,
+                               uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_blocks_merge";
+    if (n_old < 0 || n_old >= LG_BLK_MAX_BLOCKS) return refuse(who, "n_old outside [0, 2^20)");
+    if (n_add < 0 || n_old + n_add >= (1ll << 30)) return refuse(who, "n_add negative or n_old + n_add >= 2^30");
+    if (n_old > 0 && !old_keys) return refuse(who, "null old_keys");
+    if (n_add > 0 && !add_keys) return refuse(who, "null add_keys");
+    if (n_old + n_add > 0 && !merged) return refuse(who, "null merged");
+    if (!count) return refuse(who, "null count");
+    if (((uintptr_t)old_keys | (uintptr_t)add_keys | (uintptr_t)merged | (uintptr_t)count) & 7) return refuse(who, "old_keys, add_keys, merged and count must be 8-byte aligned");
+    if (!scratch) return refuse(who, "null scratch");
+    if ((uintptr_t)scratch & 255) return refuse(who, "scratch must be 256-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const size_t n = (size_t)(n_old + n_add), nb = (n + 1023) / 1024;
+    const LgBlkMergeScratch s = carve_blk_merge(scratch, n);
+    ProfScope ps(flags & LG_FLAG_PROFILE, "blocks_touch", stream);
+    if (n > 0) {
+        lg_blk_concat_kernel<<<(unsigned)std::min<size_t>((n + 255) / 256, 2048), 256, 0, stream>>>((size_t)n_old, old_keys, (size_t)n_add, add_keys, s.keys_in);
+        KLAUNCHED("lg_blk_concat_kernel");
+        size_t tb = s.sort_bytes;
+        HIP_TRY(lg_sort_keys(s.sort_temp, tb, s.keys_in, s.sorted, (uint32_t)n, 0, 64, nullptr, false, stream));
+        lg_blk_unique_kernel<false><<<(unsigned)nb, 256, 0, stream>>>(n, s.sorted, s.blk, merged, nullptr, count);
+        KLAUNCHED("lg_blk_unique_kernel");
+    }
+    lg_mesh_scan_kernel<<<1, 1024, 0, stream>>>(nb * (n > 0), s.blk, count, s.copy);
+    KLAUNCHED("lg_mesh_scan_kernel");
+    if (n > 0) {
+        lg_blk_unique_kernel<true><<<(unsigned)nb, 256, 0, stream>>>(n, s.sorted, s.blk, merged, lg_sort_error_word(s.sort_temp, n), count);
+        KLAUNCHED("lg_blk_unique_kernel");
+    }
+    return LG_OK;
+}
+
+extern "C" int lg_blocks_regrid(const lg_block_volume* from, const lg_block_volume* to, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_blocks_regrid";
+    int rc = block_volume(who, from, "from");
+    if (rc == LG_OK) rc = block_volume(who, to, "to");
+    if (rc != LG_OK) return rc;
+    if (to->n_blocks == 0) return LG_OK;
+    if (from->n_blocks > 0 && (from->color != nullptr) != (to->color != nullptr)) return refuse(who, "from and to: both keep colour or neither does");
+    hipStream_t stream = (hipStream_t)stream_p;
+    ProfScope ps(flags & LG_FLAG_PROFILE, "blocks_regrid", stream);
+    if (to->color) lg_blk_regrid_kernel<true><<<(unsigned)to->n_blocks, LG_BLK_THREADS, 0, stream>>>(from->n_blocks, from->keys, to->keys, from->tsdf, from->weight, from->color, to->tsdf, to->weight, to->color);
+    else lg_blk_regrid_kernel<false><<<(unsigned)to->n_blocks, LG_BLK_THREADS, 0, stream>>>(from->n_blocks, from->keys, to->keys, from->tsdf, from->weight, nullptr, to->tsdf, to->weight, nullptr);
+    KLAUNCHED("lg_blk_regrid_kernel");
+    return LG_OK;
+}
+
+extern "C" int lg_blocks_integrate(const lg_block_volume* vol, int32_t n_views, const lg_tsdf_view* views, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_blocks_integrate";
+    int rc = block_volume(who, vol);
+    if (rc == LG_OK) rc = block_views(who, n_views, views, vol->color != nullptr);
+    if (rc != LG_OK) return rc;
+    if (n_views == 0 || vol->n_blocks == 0) return LG_OK;
+    hipStream_t stream = (hipStream_t)stream_p;
+    const LgBlkVol g = block_vol_arg(vol);
+    for (int first = 0; first < n_views; first += LG_TSDF_BATCH) {
+        const int n = std::min(LG_TSDF_BATCH, n_views - first);
+        LgTsdfBatch b;
+        memset(&b, 0, sizeof(b));
+        for (int k = 0; k < n; k++) {
+            const lg_tsdf_view& v = views[first + k];
+            b.v[k] = { v.viewmatrix, v.depth, vol->color ? v.color : nullptr, v.alpha, { v.W, v.H, v.tanfovx, v.tanfovy, v.depth_max, v.z_min, v.alpha_min } };
+        }
+        ProfScope ps(flags & LG_FLAG_PROFILE, "blocks_integrate", stream);
+        if (vol->color) lg_blk_integrate_kernel<true><<<(unsigned)vol->n_blocks, LG_BLK_THREADS, 0, stream>>>(g, vol->keys, n, b, vol->tsdf, vol->weight, vol->color);
+        else lg_blk_integrate_kernel<false><<<(unsigned)vol->n_blocks, LG_BLK_THREADS, 0, stream>>>(g, vol->keys, n, b, vol->tsdf, vol->weight, nullptr);
+        KLAUNCHED("lg_blk_integrate_kernel");
+    }
+    return LG_OK;
+}
+
+extern "C" size_t lg_blocks_mesh_scratch_bytes(int32_t n_blocks)
+{
+    return (n_blocks < 0 || n_blocks >= LG_BLK_MAX_BLOCKS) ? 0 : carve_blk_mesh(nullptr, (size_t)n_blocks).total;
+}
+
+static int block_mesh_args(const char* who, const lg_block_volume* vol, float iso, float min_weight, const void* scratch)
+{
+    int rc = block_volume(who, vol);
+    if (rc != LG_OK) return rc;
+    if (!finite_f(iso)) return refuse(who, "iso must be finite");
+    if (!positive_finite(min_weight)) return refuse(who, "min_weight must be positive and finite");
+    if (!scratch) return refuse(who, "null scratch");
+    if ((uintptr_t)scratch & 255) return refuse(who, "scratch must be 256-byte aligned");
+    return LG_OK;
+}
+
+extern "C" int lg_blocks_mesh_count(const lg_block_volume* vol, float iso, float min_weight, void* scratch, int64_t* counts, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_blocks_mesh_count";
+    int rc = block_mesh_args(who, vol, iso, min_weight, scratch);
+    if (rc != LG_OK) return rc;
+    if (!counts) return refuse(who, "null counts");
+    if ((uintptr_t)counts & 7) return refuse(who, "counts must be 8-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_p;
+    const bool prof = flags & LG_FLAG_PROFILE;
+    const uint32_t n = (uint32_t)vol->n_blocks;
+    const LgBlkMeshScratch s = carve_blk_mesh(scratch, n);
+    if (n > 0) {
+        ProfScope ps(prof, "blocks_mesh_count", stream);
+        lg_blk_nbr_kernel<<<(n * 8 + 255) / 256, 256, 0, stream>>>((int)n, vol->keys, s.nbr);
+        KLAUNCHED("lg_blk_nbr_kernel");
+        lg_blk_mesh_count_kernel<<<n, LG_BLK_MESH_THREADS, 0, stream>>>(n, iso, min_weight, s.nbr, vol->tsdf, vol->weight, s.vmask, s.fcount, s.blk, s.blk + n);
+        KLAUNCHED("lg_blk_mesh_count_kernel");
+    }
+    {
+        ProfScope ps(prof, "blocks_mesh_scan", stream);
+        lg_mesh_scan_kernel<<<2, 1024, 0, stream>>>((size_t)n, s.blk, counts, s.counts);
+        KLAUNCHED("lg_mesh_scan_kernel");
+        if (n > 0) {
+            lg_blk_mesh_prefix_kernel<<<n, LG_BLK_MESH_THREADS, 0, stream>>>(s.vmask, s.fcount, s.blk, s.blk + n, s.vprefix, s.fprefix);
+            KLAUNCHED("lg_blk_mesh_prefix_kernel");
+        }
+    }
+    return LG_OK;
+}
+
+extern "C" int lg_blocks_mesh_emit(const lg_block_volume* vol, float iso, float min_weight, void* scratch, int64_t n_vertices, int64_t n_faces, float* vertices,
+                                   float* colors, int32_t* faces, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_blocks_mesh_emit";
+    int rc = block_mesh_args(who, vol, iso, min_weight, scratch);
+    if (rc != LG_OK) return rc;
+    if (n_vertices < 0 || n_vertices >= (1ll << 31)) return refuse(who, "n_vertices outside [0, 2^31)");
+    if (n_faces < 0 || n_faces >= (1ll << 31)) return refuse(who, "n_faces outside [0, 2^31)");
+    if (colors && !vol->color) return refuse(who, "colors for a volume that keeps no colour");
+    if (n_vertices > 0) {
+        rc = normals_ptrs(who, { { "vertices", vertices } });
+        if (rc == LG_OK && colors) rc = normals_ptrs(who, { { "colors", colors } });
+    }
+    if (rc == LG_OK && n_faces > 0) rc = normals_ptrs(who, { { "faces", faces } });
+    if (rc != LG_OK) return rc;
+    hipStream_t stream = (hipStream_t)stream_p;
+    const uint32_t n = (uint32_t)vol->n_blocks;
+    const LgBlkMeshScratch s = carve_blk_mesh(scratch, n);
+    int64_t h_counts[2] = { -1, -1 };
+    HIP_TRY(hipMemcpyAsync(h_counts, s.counts, 16, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (h_counts[0] != n_vertices) return refuse(who, "n_vertices differs from the count lg_blocks_mesh_count left in scratch");
+    if (h_counts[1] != n_faces) return refuse(who, "n_faces differs from the count lg_blocks_mesh_count left in scratch");
+    if (n == 0 || (n_vertices == 0 && n_faces == 0)) return LG_OK;
+    ProfScope ps(flags & LG_FLAG_PROFILE, "blocks_mesh_emit", stream);
+    lg_blk_mesh_emit_kernel<<<n, LG_BLK_MESH_THREADS, 0, stream>>>(n, block_vol_arg(vol), iso, min_weight, vol->keys, s.nbr, vol->tsdf, vol->weight, vol->color,
+                                                                   s.vprefix, s.fprefix, s.vmask, s.fcount, n_vertices, n_faces, vertices, colors, faces);
+    KLAUNCHED("lg_blk_mesh_emit_kernel");
     return LG_OK;
 }
 

@@ -1497,3 +1497,96 @@ LG_HD double lg_sensitivity_logdet(const double* H)
     }
     return 2.0 * s;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Sparse block TSDF volume (include/lightgaussian_blocks.h; lg_blocks.h's kernels and
+// tests/cpu_harness/lg_blocks_harness.cpp call the same functions).
+//
+// The lattice is unbounded: point (i, j, k) lies at lg_tsdf_coord(origin, voxel, i) per axis, the dense expression with the GLOBAL
+// index.  A block is 8 x 8 x 8 points, block coordinate b = floor(i / 8) in [-2^20, 2^20) per axis; the volume is the list of its
+// blocks' keys in strictly ascending order and storage follows that order, x fastest inside a block.  Integration per point is the
+// text of the dense volume above (lg_tsdf_project / _sample / _apply); the marching tetrahedra run lg_mesh_*'s rule functions on the
+// 9 x 9 x 9 halo of a block (its own points and the first layer of its seven + neighbours; a missing neighbour is unobserved).
+#define LG_BLK 8
+#define LG_BLK_POINTS 512
+#define LG_BLK_BIAS (1 << 20)                  // block coordinates are stored as b + 2^20 in 21 bits
+#define LG_BLK_INDEX_LIMIT 8388608.0f          // lattice indices stay in [-2^23, 2^23): exact as floats, block coordinates in range
+#define LG_BLK_MAX_SPAN 4                      // blocks a pixel may touch per axis
+#define LG_BLK_HALO 9
+#define LG_BLK_HALO_POINTS 729
+LG_HD int64_t lg_blk_key(int bx, int by, int bz)
+{
+    return ((int64_t)(bz + LG_BLK_BIAS) << 42) | ((int64_t)(by + LG_BLK_BIAS) << 21) | (int64_t)(bx + LG_BLK_BIAS);
+}
+LG_HD void lg_blk_coords(int64_t key, int& bx, int& by, int& bz)
+{
+    bx = (int)(key & 0x1FFFFF) - LG_BLK_BIAS; by = (int)((key >> 21) & 0x1FFFFF) - LG_BLK_BIAS; bz = (int)((key >> 42) & 0x1FFFFF) - LG_BLK_BIAS;
+}
+LG_HD int lg_blk_of_index(int i) { return i >> 3; }            // floor(i / 8): the shift of a negative int is arithmetic on every target here
+LG_HD int lg_blk_local(int x, int y, int z) { return (z * LG_BLK + y) * LG_BLK + x; }
+
+// The blocks a pixel touches: lo[a] is the first block along axis a and n[a] (1 .. 4) their number.
+struct LgBlkBox { int lo[3], n[3]; };
+// Pixel (ix, iy) with depth d (and alpha, read only with has_alpha) of a view, in this order:
+//   gates        d > 0 and finite; d <= depth_max where depth_max > 0; alpha >= alpha_min where an alpha map is given     else: 0
+//   r            (((2 ix + 1) / W - 1) tanfovx, ((2 iy + 1) / H - 1) tanfovy, 1): the ray through the pixel centre, z = 1
+//   za, zb       d - trunc, d + trunc
+//   pad          voxel + zb sqrt((tanfovx / W)^2 + (tanfovy / H)^2): one voxel for the extraction's + neighbours, and the half
+//                diagonal of the pixel's footprint at the far end of the band
+//   a_w, b_w     the world points of r za and r zb under a RIGID view matrix: p[a] = sum_c (p_v[c] - vm[12 + c]) vm[4 a + c]
+//   per axis     lo = min(a_w, b_w) - pad, hi = max(a_w, b_w) + pad; lattice indices floor((. - origin) / voxel), which must lie in
+//                [-2^23, 2^23) (a NaN fails); blocks floor(. / 8); more than 4 blocks along an axis                           else: 2
+// Returns 1 with the box, 2 for a pixel that is skipped (and counted), 0 for one that takes no part.
+LG_HD int lg_blk_touch(const float* vm, const LgTsdfCam& c, const float* origin, float voxel, float trunc, int ix, int iy, float d, bool has_alpha,
+                       float alpha, LgBlkBox& box)
+{
+    if (!(d > 0.0f) || !(d <= 3.402823466e+38f)) return 0;
+    if (c.depth_max > 0.0f && d > c.depth_max) return 0;
+    if (has_alpha && alpha < c.alpha_min) return 0;
+    const float rx = ((float)(2 * ix + 1) / (float)c.W - 1.0f) * c.tanfovx;
+    const float ry = ((float)(2 * iy + 1) / (float)c.H - 1.0f) * c.tanfovy;
+    const float za = d - trunc, zb = d + trunc;
+    const float fw = c.tanfovx / (float)c.W, fh = c.tanfovy / (float)c.H;
+    const float pad = voxel + zb * sqrtf(fw * fw + fh * fh);
+    const float ax = rx * za - vm[12], ay = ry * za - vm[13], az = za - vm[14];
+    const float bx = rx * zb - vm[12], by = ry * zb - vm[13], bz = zb - vm[14];
+    for (int a = 0; a < 3; a++) {
+        const float wa = ax * vm[4 * a] + ay * vm[4 * a + 1] + az * vm[4 * a + 2];
+        const float wb = bx * vm[4 * a] + by * vm[4 * a + 1] + bz * vm[4 * a + 2];
+        const float lo = fminf(wa, wb) - pad, hi = fmaxf(wa, wb) + pad;
+        const float flo = floorf((lo - origin[a]) / voxel), fhi = floorf((hi - origin[a]) / voxel);
+        if (!(flo >= -LG_BLK_INDEX_LIMIT && fhi < LG_BLK_INDEX_LIMIT && flo <= fhi)) return 2;
+        const int blo = lg_blk_of_index((int)flo), bhi = lg_blk_of_index((int)fhi);
+        if (bhi - blo + 1 > LG_BLK_MAX_SPAN) return 2;
+        box.lo[a] = blo; box.n[a] = bhi - blo + 1;
+    }
+    return 1;
+}
+
+// The halo of a block: point (x, y, z), each 0 .. 8, at (z 9 + y) 9 + x; it lives in the + neighbour m = (x == 8) | (y == 8) << 1 |
+// (z == 8) << 2 of the block (m = 0: the block itself) at the local index of (x & 7, y & 7, z & 7).
+LG_HD int lg_blk_halo_index(int x, int y, int z) { return (z * LG_BLK_HALO + y) * LG_BLK_HALO + x; }
+LG_HD void lg_blk_halo_source(int h, uint32_t& m, int& local)
+{
+    const int x = h % LG_BLK_HALO, y = (h / LG_BLK_HALO) % LG_BLK_HALO, z = h / (LG_BLK_HALO * LG_BLK_HALO);
+    m = (x == LG_BLK ? 1u : 0u) | (y == LG_BLK ? 2u : 0u) | (z == LG_BLK ? 4u : 0u);
+    local = lg_blk_local(x & 7, y & 7, z & 7);
+}
+// The vertex on slot k of the lattice point (gx, gy, gz), GLOBAL indices: lg_mesh_vertex's arithmetic on the values of the two ends
+// (f0, c0 at the point, f1, c1 at the point + offset(slot k)); c0 = NULL: no colour.
+LG_HD void lg_blk_vertex(float f0v, float f1v, const float* c0, const float* c1, int gx, int gy, int gz, uint32_t k, float iso, const float* origin,
+                         float voxel, float* pos, float* rgb)
+{
+    const uint32_t m = lg_mesh_slot_mask(k);
+    const int ox = (int)(m & 1u), oy = (int)((m >> 1) & 1u), oz = (int)((m >> 2) & 1u);
+    const float f0 = f0v - iso, f1 = f1v - iso;
+    const float t = f0 / (f0 - f1);
+    pos[0] = origin[0] + voxel * ((float)gx + t * (float)ox);
+    pos[1] = origin[1] + voxel * ((float)gy + t * (float)oy);
+    pos[2] = origin[2] + voxel * ((float)gz + t * (float)oz);
+    if (rgb && c0) {
+        rgb[0] = c0[0] + t * (c1[0] - c0[0]);
+        rgb[1] = c0[1] + t * (c1[1] - c0[1]);
+        rgb[2] = c0[2] + t * (c1[2] - c0[2]);
+    }
+}
