@@ -42,7 +42,6 @@ MAX_BLOCKS = 1 << 20                # n 512 < 2^29
 INDEX_LIMIT = float(1 << 23)
 MAX_SPAN = 4
 MAX_TOUCH_PIXELS = 1 << 26          # LG_BLK_TOUCH_MAX_PIXELS: per lg_blocks_touch call
-MAX_DIM = mesh.MAX_DIM
 
 
 class lg_block_volume(C.Structure):
@@ -131,130 +130,7 @@ def _touch_torch(vol, depth, vm, tx, ty, alpha, alpha_min, depth_max):
     return torch.unique(torch.cat(found)), int(skipped.sum())
 
 
-def _integrate_torch(vol, depth, vm, tx, ty, color, alpha, alpha_min, depth_max, z_min):
-    """mesh._integrate_torch at the points of the blocks: the same operations on [n,8,8,8] tensors, coordinates from the global index."""
-    dev, dt = vol.tsdf.device, torch.float32
-    H, W = (int(v) for v in depth.shape)
-    g = vol.coords().to(torch.int64)[:, :, None] * BLOCK + torch.arange(BLOCK, device=dev)[None, None, :]          # [n, 3, 8] global indices
-    px = (vol.origin[0] + vol.voxel_size * g[:, 0].to(dt))[:, None, None, :]
-    py = (vol.origin[1] + vol.voxel_size * g[:, 1].to(dt))[:, None, :, None]
-    pz = (vol.origin[2] + vol.voxel_size * g[:, 2].to(dt))[:, :, None, None]
-    vx = vm[0, 0] * px + vm[1, 0] * py + vm[2, 0] * pz + vm[3, 0]
-    vy = vm[0, 1] * px + vm[1, 1] * py + vm[2, 1] * pz + vm[3, 1]
-    vz = vm[0, 2] * px + vm[1, 2] * py + vm[2, 2] * pz + vm[3, 2]
-    ok = vz > z_min
-    flx = torch.floor((vx / (vz * tx) + 1.0) * (0.5 * W))
-    fly = torch.floor((vy / (vz * ty) + 1.0) * (0.5 * H))
-    ok = ok & (flx >= 0) & (flx < W) & (fly >= 0) & (fly < H)
-    zero = torch.zeros((), dtype=dt, device=dev)
-    pix = torch.where(ok, fly, zero).long() * W + torch.where(ok, flx, zero).long()
-    d = depth.reshape(-1)[pix]
-    ok = ok & (d > 0) & torch.isfinite(d)
-    if depth_max > 0:
-        ok = ok & ~(d > depth_max)
-    if alpha is not None:
-        ok = ok & ~(alpha.reshape(-1)[pix] < alpha_min)
-    sdf = d - vz
-    ok = ok & ~(sdf < -vol.trunc)
-    t = torch.clamp_max(sdf / vol.trunc, 1.0)
-    w = vol.weight
-    w1 = w + 1.0
-    vol.tsdf.copy_(torch.where(ok, (vol.tsdf * w + t) / w1, vol.tsdf))
-    if vol.color is not None:
-        img = color.reshape(3, -1)[:, pix].permute(1, 2, 3, 4, 0)
-        vol.color.copy_(torch.where(ok[..., None], (vol.color * w[..., None] + img) / w1[..., None], vol.color))
-    vol.weight.copy_(torch.where(ok, w1, w))
-
-
-def _extract_dense(tsdf, weight, color, origin, voxel, base, iso, min_weight):
-    """mesh._extract_torch over a dense grid whose point (0, 0, 0) is the lattice point `base`: positions from the global index, and with
-    the vertices' (point, slot) and the faces' cells returned, for the reordering.  Faces are int64."""
-    nz, ny, nx = (int(v) for v in tsdf.shape)
-    dev, dt = tsdf.device, tsdf.dtype
-    obs, ins = weight >= min_weight, tsdf < iso
-    carry = torch.stack([obs & mesh._shifted(obs, m, False) & (ins != mesh._shifted(ins, m, False)) for m in mesh.SLOT_MASKS], dim=-1).reshape(-1)
-    ids = torch.cumsum(carry, 0) - carry.long()
-    sel = carry.nonzero().squeeze(1)
-    p, k = sel // 7, sel % 7
-    m = torch.tensor(mesh.SLOT_MASKS, device=dev)[k]
-    off = torch.stack([m & 1, (m >> 1) & 1, (m >> 2) & 1], dim=1)
-    q = p + off[:, 0] + off[:, 1] * nx + off[:, 2] * (nx * ny)
-    flat = tsdf.reshape(-1)
-    f0, f1 = flat[p] - iso, flat[q] - iso
-    t = f0 / (f0 - f1)
-    grid = torch.stack([p % nx + base[0], (p // nx) % ny + base[1], p // (nx * ny) + base[2]], dim=1).to(dt)
-    org = torch.tensor([float(v) for v in origin], dtype=dt, device=dev)
-    vertices = org + voxel * (grid + t[:, None] * off.to(dt))
-    colors = None
-    if color is not None:
-        c = color.reshape(-1, 3)
-        colors = c[p] + t[:, None] * (c[q] - c[p])
-    valid = obs.clone()
-    for cm in range(1, 8):
-        valid &= mesh._shifted(obs, cm, False)
-    cells = valid.reshape(-1).nonzero().squeeze(1)
-    corner = torch.stack([mesh._shifted(ins, cm, False).reshape(-1)[cells] for cm in range(8)], dim=1).long()
-    count, c0, slot = (x.to(dev) for x in mesh._TABLES)
-    tris, keep = [], []
-    for tt in range(6):
-        m4 = sum(corner[:, cm] << i for i, cm in enumerate(mesh.tet_corners(tt)))
-        a, s = c0[tt][m4], slot[tt][m4]
-        owner = cells[:, None, None] + (a & 1) + ((a >> 1) & 1) * nx + ((a >> 2) & 1) * (nx * ny)
-        tris.append(ids[owner * 7 + s])
-        keep.append(torch.arange(2, device=dev)[None, :] < count[tt][m4][:, None])
-    keep = torch.stack(keep, dim=1)
-    faces = torch.stack(tris, dim=1)[keep]
-    cell_of_face = cells[:, None, None].expand(-1, 6, 2)[keep]
-    return vertices, faces, colors, p, k, cell_of_face
-
-
 # ---- the volume -----------------------------------------------------------------------------------------------------------------------
-def _check_views(what, views, like, keep_color):
-    """The checks of mesh.TSDFVolume.integrate_many: [(depth, vm, tx, ty, color, alpha, alpha_min, depth_max, z_min)] and the named tensors."""
-    checked, tensors = [], []
-    for i, v in enumerate(views):
-        unknown = set(v) - {"depth", "camera", "color", "alpha", "alpha_min", "depth_max", "z_min"}
-        if unknown:
-            raise ValueError(f"{what}: views[{i}] has unknown entries {sorted(unknown)}")
-        depth, camera, color, alpha = v["depth"], v["camera"], v.get("color"), v.get("alpha")
-        if not torch.is_tensor(depth) or depth.dim() != 2:
-            raise ValueError(f"{what}: views[{i}]: depth must be a [H, W] tensor")
-        H, W = (int(s) for s in depth.shape)
-        if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM):
-            raise ValueError(f"{what}: views[{i}]: H and W must lie in [1, {MAX_DIM}], not {H} x {W}")
-        mesh._check_map(what, f"views[{i}].depth", depth, (H, W), like)
-        if keep_color:
-            if color is None:
-                raise ValueError(f"{what}: views[{i}]: the volume keeps colour and the view has no color")
-            mesh._check_map(what, f"views[{i}].color", color, (3, H, W), like)
-        else:
-            color = None
-        if alpha is not None:
-            mesh._check_map(what, f"views[{i}].alpha", alpha, (H, W), like)
-        vm = camera.world_view_transform.detach().to(device=like.device, dtype=torch.float32)
-        if tuple(vm.shape) != (4, 4):
-            raise ValueError(f"{what}: views[{i}]: camera.world_view_transform must be [4, 4]")
-        tx, ty = mesh.tanfov(camera)
-        scal = tuple(float(v.get(n, dflt)) for n, dflt in (("alpha_min", 0.5), ("depth_max", 0.0), ("z_min", 0.05)))
-        if any(math.isnan(s) for s in scal + (tx, ty)):
-            raise ValueError(f"{what}: views[{i}]: tanfov, alpha_min, depth_max and z_min must not be NaN")
-        checked.append((depth.detach(), vm.contiguous(), tx, ty, None if color is None else color.detach(), None if alpha is None else alpha.detach()) + scal)
-        tensors += [(f"views[{i}].depth", depth)] + ([] if color is None else [(f"views[{i}].color", color)]) + \
-            ([] if alpha is None else [(f"views[{i}].alpha", alpha)])
-    return checked, tensors
-
-
-def _view_array(checked):
-    arr = (lg_tsdf_view * max(len(checked), 1))()
-    for a, (depth, vm, tx, ty, color, alpha, alpha_min, depth_max, z_min) in zip(arr, checked):
-        a.H, a.W = (int(s) for s in depth.shape)
-        a.tanfovx, a.tanfovy, a.alpha_min, a.depth_max, a.z_min = tx, ty, alpha_min, depth_max, z_min
-        a.viewmatrix, a.depth = vm.data_ptr(), depth.data_ptr()
-        a.color = None if color is None else color.data_ptr()
-        a.alpha = None if alpha is None else alpha.data_ptr()
-    return arr
-
-
 class BlockTSDFVolume:
     """A block-sparse TSDF volume: see the module docstring.  origin: three floats (world position of lattice point (0, 0, 0)); trunc
     defaults to 4 voxel_size, the widest band; color=False keeps no colour.  keys [n], tsdf, weight [n,8,8,8] and color [n,8,8,8,3] (or
@@ -305,26 +181,27 @@ class BlockTSDFVolume:
         """[n,3] int32 block coordinates (bx, by, bz), in key order."""
         return coords_of(self.keys)
 
+    def _global_index(self):
+        """[n,3,8] int64 lattice indices of the points of every block per axis."""
+        return self.coords().to(torch.int64)[:, :, None] * BLOCK + torch.arange(BLOCK, device=self.keys.device)[None, None, :]
+
+    def _points(self):
+        """(px, py, pz): the world coordinates of the points per axis, from the global index, shaped to broadcast over [n,8,8,8]."""
+        g = self._global_index()
+        ax = [self.origin[a] + self.voxel_size * g[:, a].to(torch.float32) for a in range(3)]
+        return ax[0][:, None, None, :], ax[1][:, None, :, None], ax[2][:, :, None, None]
+
     def points(self):
         """[n,8,8,8,3] float32 world positions of the points, [block, z, y, x, (x y z)]."""
-        g = self.coords().to(torch.int64)[:, :, None] * BLOCK + torch.arange(BLOCK, device=self.keys.device)[None, None, :]
-        ax = [self.origin[a] + self.voxel_size * g[:, a].to(torch.float32) for a in range(3)]
-        n = self.n_blocks
-        shape = (n, BLOCK, BLOCK, BLOCK)
-        return torch.stack([ax[0][:, None, None, :].expand(shape), ax[1][:, None, :, None].expand(shape), ax[2][:, :, None, None].expand(shape)], dim=-1)
+        shape = (self.n_blocks, BLOCK, BLOCK, BLOCK)
+        return torch.stack([a.expand(shape) for a in self._points()], dim=-1)
 
     def nbytes(self):
         """Bytes of the keys and the pools."""
         return sum(t.numel() * t.element_size() for t in (self.keys, self.tsdf, self.weight, self.color) if t is not None)
 
     def _resolve(self, what, tensors):
-        if self.backend == "hip" and not self.tsdf.is_cuda:
-            return "torch"
-        if self.backend == "hip":
-            for name, t in tensors:
-                if not t.is_contiguous():
-                    raise ValueError(f"{what}: {name} must be contiguous for backend='hip' (call .contiguous())")
-        return self.backend
+        return mesh._resolve_backend(self.backend, self.tsdf, what, tensors)
 
     def _own(self):
         return [("keys", self.keys), ("tsdf", self.tsdf), ("weight", self.weight)] + ([] if self.color is None else [("color", self.color)])
@@ -399,7 +276,7 @@ class BlockTSDFVolume:
             while last < len(checked) and (last == first or pixels + checked[last][0].numel() < MAX_TOUCH_PIXELS):
                 pixels += checked[last][0].numel(); last += 1
             part = checked[first:last]
-            arr = _view_array(part)
+            arr = mesh._view_array(part)
             capacity = self._capacity(pixels)
             with torch.cuda.device(dev):
                 scratch = _lib.scratch(lib.lg_blocks_touch_scratch_bytes(len(part), arr), dev)
@@ -424,7 +301,7 @@ class BlockTSDFVolume:
         """Allocate the blocks the views touch (dicts of integrate's arguments; depth, alpha, alpha_min, depth_max and the camera matter).
         Returns dict(blocks, new_blocks, skipped_pixels)."""
         what = "BlockTSDFVolume.allocate"
-        checked, tensors = _check_views(what, list(views), self.tsdf, False)
+        checked, tensors = mesh._check_views(what, list(views), self.tsdf, False)
         return self._allocate_checked(checked, self._resolve(what, self._own() + tensors))
 
     def allocate_blocks(self, coords):
@@ -461,7 +338,7 @@ class BlockTSDFVolume:
         """The views, dicts of integrate's arguments, in order: the blocks they touch are allocated first (allocate=True), then one library
         call integrates them, 8 views per pass over the blocks."""
         what = "BlockTSDFVolume.integrate_many"
-        checked, tensors = _check_views(what, list(views), self.tsdf, self.color is not None)
+        checked, tensors = mesh._check_views(what, list(views), self.tsdf, self.color is not None)
         backend = self._resolve(what, self._own() + tensors)
         if not checked:
             return
@@ -470,12 +347,9 @@ class BlockTSDFVolume:
         if self.n_blocks == 0:
             return
         if backend == "torch":
-            with torch.no_grad():
-                for depth, vm, tx, ty, color, alpha, alpha_min, depth_max, z_min in checked:
-                    _integrate_torch(self, depth, vm, model_rows.f32(tx), model_rows.f32(ty), color, alpha, model_rows.f32(alpha_min),
-                                     model_rows.f32(depth_max), model_rows.f32(z_min))
+            mesh._integrate_checked_torch(self, self._points(), checked)
             return
-        arr = _view_array(checked)
+        arr = mesh._view_array(checked)
         dev, vol = self.device, self._struct()
         with torch.cuda.device(dev):
             _lib.check(load().lg_blocks_integrate(C.byref(vol), len(checked), arr, _flags(), _lib.stream(dev)))
@@ -492,9 +366,18 @@ class BlockTSDFVolume:
 
     def _dense_index(self, base, dims):
         """[n,8,8,8] linear index of every point of every block in the dense grid (base, dims)."""
-        g = self.coords().to(torch.int64)[:, :, None] * BLOCK + torch.arange(BLOCK, device=self.keys.device)[None, None, :]
+        g = self._global_index()
         x, y, z = (g[:, a] - base[a] for a in range(3))
         return (z[:, :, None, None] * dims[1] + y[:, None, :, None]) * dims[0] + x[:, None, None, :]
+
+    def _scatter_dense(self, base, dims, tsdf, weight, color):
+        """The blocks' values into the tensors [nz,ny,nx] (color [nz,ny,nx,3]; ignored by a volume without colour) of the dense grid
+        (base, dims), by the one index both to_dense and the torch extraction use; the other points keep what they hold."""
+        at = self._dense_index(base, dims).reshape(-1)
+        tsdf.view(-1)[at] = self.tsdf.reshape(-1)
+        weight.view(-1)[at] = self.weight.reshape(-1)
+        if self.color is not None:
+            color.view(-1, 3)[at] = self.color.reshape(-1, 3)
 
     def to_dense(self, margin=0):
         """A mesh.TSDFVolume over the bounding box of the blocks, `margin` points wider on every side, holding the blocks' values and fresh
@@ -507,11 +390,7 @@ class BlockTSDFVolume:
         base, dims = self._bounding_box(margin, what)
         origin = tuple(float(np.float32(o) + np.float32(self.voxel_size) * np.float32(b)) for o, b in zip(self.origin, base))
         dense = mesh.TSDFVolume(origin, dims, self.voxel_size, trunc=self.trunc, color=self.color is not None, device=self.device, backend=self.backend)
-        at = self._dense_index(base, dims).reshape(-1)
-        dense.tsdf.view(-1)[at] = self.tsdf.reshape(-1)
-        dense.weight.view(-1)[at] = self.weight.reshape(-1)
-        if self.color is not None:
-            dense.color.view(-1, 3)[at] = self.color.reshape(-1, 3)
+        self._scatter_dense(base, dims, dense.tsdf, dense.weight, dense.color)
         return dense
 
     def _extract_torch(self, iso, min_weight):
@@ -521,14 +400,10 @@ class BlockTSDFVolume:
                     None if self.color is None else torch.zeros((0, 3), dtype=torch.float32, device=dev))
         base, dims = self._bounding_box(0, "BlockTSDFVolume.extract_mesh (backend='torch' meshes through the dense bounding box)")
         nx, ny, nz = dims
-        at = self._dense_index(base, dims).reshape(-1)
-        tsdf = torch.ones(nz * ny * nx, dtype=torch.float32, device=dev); tsdf[at] = self.tsdf.reshape(-1)
-        weight = torch.zeros(nz * ny * nx, dtype=torch.float32, device=dev); weight[at] = self.weight.reshape(-1)
-        color = None
-        if self.color is not None:
-            color = torch.zeros((nz * ny * nx, 3), dtype=torch.float32, device=dev); color[at] = self.color.reshape(-1, 3)
-            color = color.view(nz, ny, nx, 3)
-        v, f, c, p, k, cell = _extract_dense(tsdf.view(nz, ny, nx), weight.view(nz, ny, nx), color, self.origin, self.voxel_size, base, iso, min_weight)
+        tsdf, weight = torch.ones((nz, ny, nx), dtype=torch.float32, device=dev), torch.zeros((nz, ny, nx), dtype=torch.float32, device=dev)
+        color = None if self.color is None else torch.zeros((nz, ny, nx, 3), dtype=torch.float32, device=dev)
+        self._scatter_dense(base, dims, tsdf, weight, color)
+        v, f, c, p, k, cell = mesh._extract_grid(tsdf, weight, color, self.origin, self.voxel_size, iso, min_weight, base=base)
 
         def sparse_index(lin):          # dense linear index of a point of an allocated block -> rank 512 + local index
             x, y, z = lin % nx + base[0], (lin // nx) % ny + base[1], lin // (nx * ny) + base[2]
@@ -545,25 +420,14 @@ class BlockTSDFVolume:
         """(vertices [Nv,3] float32 in world space, faces [Nf,3] int32, colors [Nv,3] or None) of the surface tsdf = iso over the points with
         weight >= min_weight, across block borders, normals toward larger tsdf; drop_unreferenced as mesh.TSDFVolume.extract_mesh."""
         what = "BlockTSDFVolume.extract_mesh"
-        iso, min_weight = model_rows.f32(iso), model_rows.f32(min_weight)
-        if not math.isfinite(iso) or not (min_weight > 0 and math.isfinite(min_weight)):
-            raise ValueError(f"{what}: iso must be finite and min_weight positive and finite")
-        backend = self._resolve(what, self._own())
-        if backend == "torch":
+        iso, min_weight = mesh._check_extract_args(what, iso, min_weight)
+        if self._resolve(what, self._own()) == "torch":
             with torch.no_grad():
                 vertices, faces, colors = self._extract_torch(iso, min_weight)
         else:
-            dev, lib, vol = self.device, load(), self._struct()
-            with torch.cuda.device(dev):
-                scratch = _lib.scratch(lib.lg_blocks_mesh_scratch_bytes(self.n_blocks), dev)
-                counts = torch.empty(2, dtype=torch.int64, device=dev)
-                _lib.check(lib.lg_blocks_mesh_count(C.byref(vol), iso, min_weight, _lib.ptr(scratch), _lib.ptr(counts), _flags(), _lib.stream(dev)))
-                nv, nf = (int(c) for c in counts.tolist())                     # the one read-back: the caller allocates the outputs
-                vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-                faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-                colors = None if self.color is None else torch.empty((nv, 3), dtype=torch.float32, device=dev)
-                _lib.check(lib.lg_blocks_mesh_emit(C.byref(vol), iso, min_weight, _lib.ptr(scratch), nv, nf, _lib.ptr(vertices), _lib.ptr(colors), _lib.ptr(faces),
-                                                   _flags(), _lib.stream(dev)))
+            lib = load()
+            vertices, faces, colors = mesh._extract_hip(lib.lg_blocks_mesh_scratch_bytes(self.n_blocks), lib.lg_blocks_mesh_count, lib.lg_blocks_mesh_emit,
+                                                        self._struct(), self.color is not None, self.device, iso, min_weight, _flags())
         if drop_unreferenced:
             vertices, faces, colors = mesh.drop_unreferenced_vertices(vertices, faces, colors)
         return vertices, faces, colors

@@ -41,7 +41,10 @@
 //   lg_tsdf.h        lg_tsdf_integrate / lg_mesh_count / lg_mesh_emit: depth maps of up to 8 views per pass into a dense TSDF volume, and marching
 //                    tetrahedra over it with indexed vertices (include/lightgaussian_mesh.h; count, scan, emit: no atomics)
 //   lg_blocks.h      lg_blocks_touch / _merge / _regrid / _integrate / _mesh_count / _mesh_emit: the same fusion and extraction over a block-sparse
-//                    volume for unbounded scenes, blocks allocated from the depth maps and kept in sorted-key order (include/lightgaussian_blocks.h)
+//                    volume for unbounded scenes, blocks allocated from the depth maps and kept in sorted-key order (include/lightgaussian_blocks.h).
+//                    The host side of the two volumes shares tsdf_views (one view checker), tsdf_batch (the by-value views of an integrate
+//                    launch), mesh_args / mesh_counts_ptr / mesh_emit_args (the checks and the read-back of the count and emit calls) and
+//                    carve_mesh (one scratch layout); each volume keeps its own volume check, tsdf_volume and block_volume
 //
 // Pipeline of one view:
 //   K1 project + EWA + SH->RGB + exact footprint culling  ->  K2 scan of instance counts, blocking read of R
@@ -1764,12 +1767,14 @@ static int tsdf_volume(const char* who, const lg_tsdf_volume* vol, bool* vec = n
 }
 static size_t tsdf_points(const lg_tsdf_volume* vol) { return (size_t)vol->nx * (size_t)vol->ny * (size_t)vol->nz; }
 
-extern "C" int lg_tsdf_integrate(const lg_tsdf_volume* vol, int32_t n_views, const lg_tsdf_view* views, uint32_t flags, void* stream_p)
+static LgTsdfLattice tsdf_lattice(const float* origin, float voxel, float trunc) { return { { origin[0], origin[1], origin[2] }, voxel, trunc }; }
+static LgTsdfCam tsdf_cam(const lg_tsdf_view& v) { return { v.W, v.H, v.tanfovx, v.tanfovy, v.depth_max, v.z_min, v.alpha_min }; }
+
+// The checks of the views lg_tsdf_integrate, lg_blocks_touch and lg_blocks_integrate share.  need_color: the volume keeps colour and the
+// call reads views[i].color.  align_color: views[i].color is held to 4-byte alignment; the dense entry does so even for a volume that
+// keeps no colour, the block entries only when the call reads it.
+static int tsdf_views(const char* who, int32_t n_views, const lg_tsdf_view* views, bool need_color, bool align_color)
 {
-    const char* who = "lg_tsdf_integrate";
-    bool vec = false;
-    int rc = tsdf_volume(who, vol, &vec);
-    if (rc != LG_OK) return rc;
     if (n_views < 0) return refuse(who, "n_views < 0");
     if (n_views > 0 && !views) return refuse(who, "null views");
     for (int i = 0; i < n_views; i++) {
@@ -1783,25 +1788,42 @@ extern "C" int lg_tsdf_integrate(const lg_tsdf_volume* vol, int32_t n_views, con
         if (v.alpha_min != v.alpha_min || v.depth_max != v.depth_max || v.z_min != v.z_min) return bad("alpha_min, depth_max or z_min is NaN");
         if (!v.viewmatrix) return bad("null viewmatrix");
         if (!v.depth) return bad("null depth");
-        if (vol->color && !v.color) return bad("null color for a volume that keeps colour");
-        if (((uintptr_t)v.viewmatrix | (uintptr_t)v.depth | (uintptr_t)v.color | (uintptr_t)v.alpha) & 3)
+        if (need_color && !v.color) return bad("null color for a volume that keeps colour");
+        if (((uintptr_t)v.viewmatrix | (uintptr_t)v.depth | (uintptr_t)(align_color ? v.color : nullptr) | (uintptr_t)v.alpha) & 3)
             return bad("viewmatrix, depth, color and alpha must be 4-byte aligned");
     }
+    return LG_OK;
+}
+// views[first .. first + n) as the by-value argument of an integrate kernel; color: the volume keeps colour
+static LgTsdfBatch tsdf_batch(const lg_tsdf_view* views, int first, int n, bool color)
+{
+    LgTsdfBatch b;
+    memset(&b, 0, sizeof(b));
+    for (int k = 0; k < n; k++) {
+        const lg_tsdf_view& v = views[first + k];
+        b.v[k] = { v.viewmatrix, v.depth, color ? v.color : nullptr, v.alpha, tsdf_cam(v) };
+    }
+    return b;
+}
+
+extern "C" int lg_tsdf_integrate(const lg_tsdf_volume* vol, int32_t n_views, const lg_tsdf_view* views, uint32_t flags, void* stream_p)
+{
+    const char* who = "lg_tsdf_integrate";
+    bool vec = false;
+    int rc = tsdf_volume(who, vol, &vec);
+    if (rc == LG_OK) rc = tsdf_views(who, n_views, views, vol->color != nullptr, true);
+    if (rc != LG_OK) return rc;
     if (n_views == 0) return LG_OK;
     hipStream_t stream = (hipStream_t)stream_p;
-    const LgTsdfGrid g = { vol->nx, vol->ny, vol->nz, vol->origin[0], vol->origin[1], vol->origin[2], vol->voxel_size, vol->trunc };
+    const LgMeshDims d = { vol->nx, vol->ny, vol->nz };
+    const LgTsdfLattice g = tsdf_lattice(vol->origin, vol->voxel_size, vol->trunc);
     const unsigned wgs = (unsigned)lg_tsdf_bricks(vol->nx, vol->ny, vol->nz);
     for (int first = 0; first < n_views; first += LG_TSDF_BATCH) {
         const int n = std::min(LG_TSDF_BATCH, n_views - first);
-        LgTsdfBatch b;
-        memset(&b, 0, sizeof(b));
-        for (int k = 0; k < n; k++) {
-            const lg_tsdf_view& v = views[first + k];
-            b.v[k] = { v.viewmatrix, v.depth, vol->color ? v.color : nullptr, v.alpha, { v.W, v.H, v.tanfovx, v.tanfovy, v.depth_max, v.z_min, v.alpha_min } };
-        }
+        const LgTsdfBatch b = tsdf_batch(views, first, n, vol->color != nullptr);
         ProfScope ps(flags & LG_FLAG_PROFILE, "tsdf_integrate", stream);
-        if (vol->color) lg_tsdf_integrate_kernel<true><<<wgs, LG_TSDF_THREADS, 0, stream>>>(g, vec, n, b, vol->tsdf, vol->weight, vol->color);
-        else lg_tsdf_integrate_kernel<false><<<wgs, LG_TSDF_THREADS, 0, stream>>>(g, vec, n, b, vol->tsdf, vol->weight, nullptr);
+        if (vol->color) lg_tsdf_integrate_kernel<true><<<wgs, LG_TSDF_THREADS, 0, stream>>>(d, g, vec, n, b, vol->tsdf, vol->weight, vol->color);
+        else lg_tsdf_integrate_kernel<false><<<wgs, LG_TSDF_THREADS, 0, stream>>>(d, g, vec, n, b, vol->tsdf, vol->weight, nullptr);
         KLAUNCHED("lg_tsdf_integrate_kernel");
     }
     return LG_OK;
@@ -1810,31 +1832,65 @@ extern "C" int lg_tsdf_integrate(const lg_tsdf_volume* vol, int32_t n_views, con
 extern "C" size_t lg_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz)
 {
     if (nx < 1 || ny < 1 || nz < 1 || (int64_t)nx * ny >= LG_TSDF_MAX_POINTS || (int64_t)nx * ny * nz >= LG_TSDF_MAX_POINTS) return 0;
-    return carve_mesh(nullptr, (size_t)nx * (size_t)ny * (size_t)nz).total;
+    const size_t P = (size_t)nx * (size_t)ny * (size_t)nz;
+    return carve_mesh(nullptr, P, lg_mesh_blocks(P), 0).total;
 }
 
-static int mesh_args(const char* who, const lg_tsdf_volume* vol, float iso, float min_weight, const void* scratch)
+// The checks the count and emit calls of both volumes share, after the volume's own.
+static int mesh_args(const char* who, float iso, float min_weight, const void* scratch)
 {
-    int rc = tsdf_volume(who, vol);
-    if (rc != LG_OK) return rc;
     if (!finite_f(iso)) return refuse(who, "iso must be finite");
     if (!positive_finite(min_weight)) return refuse(who, "min_weight must be positive and finite");
     if (!scratch) return refuse(who, "null scratch");
     if ((uintptr_t)scratch & 255) return refuse(who, "scratch must be 256-byte aligned");
     return LG_OK;
 }
+static int mesh_counts_ptr(const char* who, const int64_t* counts)
+{
+    if (!counts) return refuse(who, "null counts");
+    if ((uintptr_t)counts & 7) return refuse(who, "counts must be 8-byte aligned");
+    return LG_OK;
+}
+// What an emit call does before its launch: the ranges of n_vertices and n_faces, the output pointers, then the read-back of the counts
+// that `count_fn` left in scratch (16 bytes, one synchronise) and the refusal of sizes that differ from them.
+static int mesh_emit_args(const char* who, const char* count_fn, bool keeps_color, const LgMeshScratch& s, int64_t n_vertices, int64_t n_faces,
+                          const float* vertices, const float* colors, const int32_t* faces, hipStream_t stream)
+{
+    if (n_vertices < 0 || n_vertices >= (1ll << 31)) return refuse(who, "n_vertices outside [0, 2^31)");
+    if (n_faces < 0 || n_faces >= (1ll << 31)) return refuse(who, "n_faces outside [0, 2^31)");
+    if (colors && !keeps_color) return refuse(who, "colors for a volume that keeps no colour");
+    int rc = LG_OK;
+    if (n_vertices > 0) {
+        rc = normals_ptrs(who, { { "vertices", vertices } });
+        if (rc == LG_OK && colors) rc = normals_ptrs(who, { { "colors", colors } });
+    }
+    if (rc == LG_OK && n_faces > 0) rc = normals_ptrs(who, { { "faces", faces } });
+    if (rc != LG_OK) return rc;
+    int64_t h_counts[2] = { -1, -1 };
+    HIP_TRY(hipMemcpyAsync(h_counts, s.counts, 16, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const char* names[2] = { "n_vertices", "n_faces" };
+    const int64_t given[2] = { n_vertices, n_faces };
+    for (int c = 0; c < 2; c++)
+        if (h_counts[c] != given[c]) {
+            char what[112];
+            snprintf(what, sizeof(what), "%s differs from the count %s left in scratch", names[c], count_fn);
+            return refuse(who, what);
+        }
+    return LG_OK;
+}
 
 extern "C" int lg_mesh_count(const lg_tsdf_volume* vol, float iso, float min_weight, void* scratch, int64_t* counts, uint32_t flags, void* stream_p)
 {
     const char* who = "lg_mesh_count";
-    int rc = mesh_args(who, vol, iso, min_weight, scratch);
+    int rc = tsdf_volume(who, vol);
+    if (rc == LG_OK) rc = mesh_args(who, iso, min_weight, scratch);
+    if (rc == LG_OK) rc = mesh_counts_ptr(who, counts);
     if (rc != LG_OK) return rc;
-    if (!counts) return refuse(who, "null counts");
-    if ((uintptr_t)counts & 7) return refuse(who, "counts must be 8-byte aligned");
     hipStream_t stream = (hipStream_t)stream_p;
     const bool prof = flags & LG_FLAG_PROFILE;
     const size_t P = tsdf_points(vol), nb = lg_mesh_blocks(P);
-    const LgMeshScratch s = carve_mesh(scratch, P);
+    const LgMeshScratch s = carve_mesh(scratch, P, nb, 0);
     const LgMeshDims d = { vol->nx, vol->ny, vol->nz };
     {
         ProfScope ps(prof, "mesh_count", stream);
@@ -1845,7 +1901,7 @@ extern "C" int lg_mesh_count(const lg_tsdf_volume* vol, float iso, float min_wei
         ProfScope ps(prof, "mesh_scan", stream);
         lg_mesh_scan_kernel<<<2, 1024, 0, stream>>>(nb, s.blk, counts, s.counts);
         KLAUNCHED("lg_mesh_scan_kernel");
-        lg_mesh_prefix_kernel<<<(unsigned)nb, 256, 0, stream>>>(P, s.vmask, s.fcount, s.blk, s.blk + nb, s.vprefix, s.fprefix);
+        lg_mesh_prefix_kernel<4, false><<<(unsigned)nb, 256, 0, stream>>>(P, s.vmask, s.fcount, s.blk, s.blk + nb, s.vprefix, s.fprefix);
         KLAUNCHED("lg_mesh_prefix_kernel");
     }
     return LG_OK;
@@ -1855,31 +1911,20 @@ extern "C" int lg_mesh_emit(const lg_tsdf_volume* vol, float iso, float min_weig
                             float* colors, int32_t* faces, uint32_t flags, void* stream_p)
 {
     const char* who = "lg_mesh_emit";
-    int rc = mesh_args(who, vol, iso, min_weight, scratch);
-    if (rc != LG_OK) return rc;
-    if (n_vertices < 0 || n_vertices >= (1ll << 31)) return refuse(who, "n_vertices outside [0, 2^31)");
-    if (n_faces < 0 || n_faces >= (1ll << 31)) return refuse(who, "n_faces outside [0, 2^31)");
-    if (colors && !vol->color) return refuse(who, "colors for a volume that keeps no colour");
-    if (n_vertices > 0) {
-        rc = normals_ptrs(who, { { "vertices", vertices } });
-        if (rc == LG_OK && colors) rc = normals_ptrs(who, { { "colors", colors } });
-    }
-    if (rc == LG_OK && n_faces > 0) rc = normals_ptrs(who, { { "faces", faces } });
+    int rc = tsdf_volume(who, vol);
+    if (rc == LG_OK) rc = mesh_args(who, iso, min_weight, scratch);
     if (rc != LG_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_p;
     const size_t P = tsdf_points(vol);
-    const LgMeshScratch s = carve_mesh(scratch, P);
-    int64_t h_counts[2] = { -1, -1 };
-    HIP_TRY(hipMemcpyAsync(h_counts, s.counts, 16, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (h_counts[0] != n_vertices) return refuse(who, "n_vertices differs from the count lg_mesh_count left in scratch");
-    if (h_counts[1] != n_faces) return refuse(who, "n_faces differs from the count lg_mesh_count left in scratch");
+    const LgMeshScratch s = carve_mesh(scratch, P, lg_mesh_blocks(P), 0);
+    rc = mesh_emit_args(who, "lg_mesh_count", vol->color != nullptr, s, n_vertices, n_faces, vertices, colors, faces, stream);
+    if (rc != LG_OK) return rc;
     if (n_vertices == 0 && n_faces == 0) return LG_OK;
     const LgMeshDims d = { vol->nx, vol->ny, vol->nz };
-    const LgMeshOrigin org = { { vol->origin[0], vol->origin[1], vol->origin[2] }, vol->voxel_size };
     ProfScope ps(flags & LG_FLAG_PROFILE, "mesh_emit", stream);
-    lg_mesh_emit_kernel<<<(unsigned)((P + 255) / 256), 256, 0, stream>>>(d, P, org, iso, min_weight, vol->tsdf, vol->weight, vol->color, s.vprefix, s.fprefix,
-                                                                          s.vmask, s.fcount, n_vertices, n_faces, vertices, colors, faces);
+    lg_mesh_emit_kernel<<<(unsigned)((P + 255) / 256), 256, 0, stream>>>(d, P, tsdf_lattice(vol->origin, vol->voxel_size, vol->trunc), iso, min_weight, vol->tsdf,
+                                                                          vol->weight, vol->color, s.vprefix, s.fprefix, s.vmask, s.fcount, n_vertices, n_faces,
+                                                                          vertices, colors, faces);
     KLAUNCHED("lg_mesh_emit_kernel");
     return LG_OK;
 }
@@ -1906,29 +1951,7 @@ static int block_volume(const char* who, const lg_block_volume* vol, const char*
     if ((uintptr_t)vol->color & 15) return bad("color must be 16-byte aligned");
     return LG_OK;
 }
-// the checks of the views lg_blocks_touch and lg_blocks_integrate share; need_color: the volume keeps colour and the call reads it
-static int block_views(const char* who, int32_t n_views, const lg_tsdf_view* views, bool need_color)
-{
-    if (n_views < 0) return refuse(who, "n_views < 0");
-    if (n_views > 0 && !views) return refuse(who, "null views");
-    for (int i = 0; i < n_views; i++) {
-        const lg_tsdf_view& v = views[i];
-        char what[96];
-        auto bad = [&](const char* text) { snprintf(what, sizeof(what), "views[%d]: %s", i, text); return refuse(who, what); };
-        if (v.H < 1 || v.H > LG_TSDF_MAX_DIM) return bad("H outside [1, 32768]");
-        if (v.W < 1 || v.W > LG_TSDF_MAX_DIM) return bad("W outside [1, 32768]");
-        if (v.tanfovx != v.tanfovx) return bad("tanfovx is NaN");
-        if (v.tanfovy != v.tanfovy) return bad("tanfovy is NaN");
-        if (v.alpha_min != v.alpha_min || v.depth_max != v.depth_max || v.z_min != v.z_min) return bad("alpha_min, depth_max or z_min is NaN");
-        if (!v.viewmatrix) return bad("null viewmatrix");
-        if (!v.depth) return bad("null depth");
-        if (need_color && !v.color) return bad("null color for a volume that keeps colour");
-        if (((uintptr_t)v.viewmatrix | (uintptr_t)v.depth | (uintptr_t)(need_color ? v.color : nullptr) | (uintptr_t)v.alpha) & 3)
-            return bad("viewmatrix, depth, color and alpha must be 4-byte aligned");
-    }
-    return LG_OK;
-}
-static LgBlkVol block_vol_arg(const lg_block_volume* vol) { return { { vol->origin[0], vol->origin[1], vol->origin[2] }, vol->voxel_size, vol->trunc }; }
+static LgTsdfLattice block_lattice(const lg_block_volume* vol) { return tsdf_lattice(vol->origin, vol->voxel_size, vol->trunc); }
 static int64_t block_touch_waves(int32_t n_views, const lg_tsdf_view* views, int64_t* pixels = nullptr)
 {
     int64_t waves = 0, px = 0;
@@ -1952,7 +1975,7 @@ extern "C" int lg_blocks_touch(const lg_block_volume* vol, int32_t n_views, cons
 {
     const char* who = "lg_blocks_touch";
     int rc = block_volume(who, vol);
-    if (rc == LG_OK) rc = block_views(who, n_views, views, false);
+    if (rc == LG_OK) rc = tsdf_views(who, n_views, views, false, false);
     if (rc != LG_OK) return rc;
     if (capacity < 0 || capacity >= (1ll << 30)) return refuse(who, "capacity outside [0, 2^30)");
     if (capacity > 0 && !candidates) return refuse(who, "null candidates");
@@ -1967,7 +1990,7 @@ extern "C" int lg_blocks_touch(const lg_block_volume* vol, int32_t n_views, cons
     hipStream_t stream = (hipStream_t)stream_p;
     int64_t* totals = (int64_t*)scratch;
     uint32_t* wave_n = (uint32_t*)((char*)scratch + align_up(16));
-    const LgBlkVol g = block_vol_arg(vol);
+    const LgTsdfLattice g = block_lattice(vol);
     ProfScope ps(flags & LG_FLAG_PROFILE, "blocks_touch", stream);
     for (int emit = 0; emit < 2; emit++) {
         uint32_t wave_base = 0;
@@ -1979,8 +2002,7 @@ extern "C" int lg_blocks_touch(const lg_block_volume* vol, int32_t n_views, cons
             for (int k = 0; k < n; k++) {
                 const lg_tsdf_view& v = views[first + k];
                 end += lg_blk_touch_waves(v.W, v.H);
-                b.v[k] = { v.viewmatrix, v.depth, v.alpha, { v.W, v.H, v.tanfovx, v.tanfovy, v.depth_max, v.z_min, v.alpha_min }, end,
-                           (uint32_t)((v.W + LG_BLK_TOUCH_TILE - 1) / LG_BLK_TOUCH_TILE) };
+                b.v[k] = { v.viewmatrix, v.depth, v.alpha, tsdf_cam(v), end, (uint32_t)((v.W + LG_BLK_TOUCH_TILE - 1) / LG_BLK_TOUCH_TILE) };
             }
             const unsigned wgs = (end + 3) / 4;
             if (emit) lg_blk_touch_kernel<true><<<wgs, 256, 0, stream>>>(g, n, b, end, wave_base, (uint32_t)waves, wave_n, capacity, candidates);
@@ -2073,19 +2095,14 @@ extern "C" int lg_blocks_integrate(const lg_block_volume* vol, int32_t n_views, 
 {
     const char* who = "lg_blocks_integrate";
     int rc = block_volume(who, vol);
-    if (rc == LG_OK) rc = block_views(who, n_views, views, vol->color != nullptr);
+    if (rc == LG_OK) rc = tsdf_views(who, n_views, views, vol->color != nullptr, vol->color != nullptr);
     if (rc != LG_OK) return rc;
     if (n_views == 0 || vol->n_blocks == 0) return LG_OK;
     hipStream_t stream = (hipStream_t)stream_p;
-    const LgBlkVol g = block_vol_arg(vol);
+    const LgTsdfLattice g = block_lattice(vol);
     for (int first = 0; first < n_views; first += LG_TSDF_BATCH) {
         const int n = std::min(LG_TSDF_BATCH, n_views - first);
-        LgTsdfBatch b;
-        memset(&b, 0, sizeof(b));
-        for (int k = 0; k < n; k++) {
-            const lg_tsdf_view& v = views[first + k];
-            b.v[k] = { v.viewmatrix, v.depth, vol->color ? v.color : nullptr, v.alpha, { v.W, v.H, v.tanfovx, v.tanfovy, v.depth_max, v.z_min, v.alpha_min } };
-        }
+        const LgTsdfBatch b = tsdf_batch(views, first, n, vol->color != nullptr);
         ProfScope ps(flags & LG_FLAG_PROFILE, "blocks_integrate", stream);
         if (vol->color) lg_blk_integrate_kernel<true><<<(unsigned)vol->n_blocks, LG_BLK_THREADS, 0, stream>>>(g, vol->keys, n, b, vol->tsdf, vol->weight, vol->color);
         else lg_blk_integrate_kernel<false><<<(unsigned)vol->n_blocks, LG_BLK_THREADS, 0, stream>>>(g, vol->keys, n, b, vol->tsdf, vol->weight, nullptr);
@@ -2094,33 +2111,24 @@ extern "C" int lg_blocks_integrate(const lg_block_volume* vol, int32_t n_views, 
     return LG_OK;
 }
 
+// scratch of the mesh calls of n blocks: one workgroup of the count kernel and one row of nbr per block
+static LgMeshScratch carve_blk_mesh(void* base, size_t n) { return carve_mesh(base, n * LG_BLK_POINTS, n, n); }
 extern "C" size_t lg_blocks_mesh_scratch_bytes(int32_t n_blocks)
 {
     return (n_blocks < 0 || n_blocks >= LG_BLK_MAX_BLOCKS) ? 0 : carve_blk_mesh(nullptr, (size_t)n_blocks).total;
 }
 
-static int block_mesh_args(const char* who, const lg_block_volume* vol, float iso, float min_weight, const void* scratch)
-{
-    int rc = block_volume(who, vol);
-    if (rc != LG_OK) return rc;
-    if (!finite_f(iso)) return refuse(who, "iso must be finite");
-    if (!positive_finite(min_weight)) return refuse(who, "min_weight must be positive and finite");
-    if (!scratch) return refuse(who, "null scratch");
-    if ((uintptr_t)scratch & 255) return refuse(who, "scratch must be 256-byte aligned");
-    return LG_OK;
-}
-
 extern "C" int lg_blocks_mesh_count(const lg_block_volume* vol, float iso, float min_weight, void* scratch, int64_t* counts, uint32_t flags, void* stream_p)
 {
     const char* who = "lg_blocks_mesh_count";
-    int rc = block_mesh_args(who, vol, iso, min_weight, scratch);
+    int rc = block_volume(who, vol);
+    if (rc == LG_OK) rc = mesh_args(who, iso, min_weight, scratch);
+    if (rc == LG_OK) rc = mesh_counts_ptr(who, counts);
     if (rc != LG_OK) return rc;
-    if (!counts) return refuse(who, "null counts");
-    if ((uintptr_t)counts & 7) return refuse(who, "counts must be 8-byte aligned");
     hipStream_t stream = (hipStream_t)stream_p;
     const bool prof = flags & LG_FLAG_PROFILE;
     const uint32_t n = (uint32_t)vol->n_blocks;
-    const LgBlkMeshScratch s = carve_blk_mesh(scratch, n);
+    const LgMeshScratch s = carve_blk_mesh(scratch, n);
     if (n > 0) {
         ProfScope ps(prof, "blocks_mesh_count", stream);
         lg_blk_nbr_kernel<<<(n * 8 + 255) / 256, 256, 0, stream>>>((int)n, vol->keys, s.nbr);
@@ -2133,8 +2141,9 @@ extern "C" int lg_blocks_mesh_count(const lg_block_volume* vol, float iso, float
         lg_mesh_scan_kernel<<<2, 1024, 0, stream>>>((size_t)n, s.blk, counts, s.counts);
         KLAUNCHED("lg_mesh_scan_kernel");
         if (n > 0) {
-            lg_blk_mesh_prefix_kernel<<<n, LG_BLK_MESH_THREADS, 0, stream>>>(s.vmask, s.fcount, s.blk, s.blk + n, s.vprefix, s.fprefix);
-            KLAUNCHED("lg_blk_mesh_prefix_kernel");
+            static_assert(LG_BLK_POINTS == LG_BLK_MESH_THREADS * 2, "WHOLE: a block is exactly the points of one workgroup, so P = 512 n has no partial one");
+            lg_mesh_prefix_kernel<2, true><<<n, LG_BLK_MESH_THREADS, 0, stream>>>((size_t)n * LG_BLK_POINTS, s.vmask, s.fcount, s.blk, s.blk + n, s.vprefix, s.fprefix);
+            KLAUNCHED("lg_mesh_prefix_kernel");
         }
     }
     return LG_OK;
@@ -2144,28 +2153,17 @@ extern "C" int lg_blocks_mesh_emit(const lg_block_volume* vol, float iso, float 
                                    float* colors, int32_t* faces, uint32_t flags, void* stream_p)
 {
     const char* who = "lg_blocks_mesh_emit";
-    int rc = block_mesh_args(who, vol, iso, min_weight, scratch);
-    if (rc != LG_OK) return rc;
-    if (n_vertices < 0 || n_vertices >= (1ll << 31)) return refuse(who, "n_vertices outside [0, 2^31)");
-    if (n_faces < 0 || n_faces >= (1ll << 31)) return refuse(who, "n_faces outside [0, 2^31)");
-    if (colors && !vol->color) return refuse(who, "colors for a volume that keeps no colour");
-    if (n_vertices > 0) {
-        rc = normals_ptrs(who, { { "vertices", vertices } });
-        if (rc == LG_OK && colors) rc = normals_ptrs(who, { { "colors", colors } });
-    }
-    if (rc == LG_OK && n_faces > 0) rc = normals_ptrs(who, { { "faces", faces } });
+    int rc = block_volume(who, vol);
+    if (rc == LG_OK) rc = mesh_args(who, iso, min_weight, scratch);
     if (rc != LG_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_p;
     const uint32_t n = (uint32_t)vol->n_blocks;
-    const LgBlkMeshScratch s = carve_blk_mesh(scratch, n);
-    int64_t h_counts[2] = { -1, -1 };
-    HIP_TRY(hipMemcpyAsync(h_counts, s.counts, 16, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (h_counts[0] != n_vertices) return refuse(who, "n_vertices differs from the count lg_blocks_mesh_count left in scratch");
-    if (h_counts[1] != n_faces) return refuse(who, "n_faces differs from the count lg_blocks_mesh_count left in scratch");
+    const LgMeshScratch s = carve_blk_mesh(scratch, n);
+    rc = mesh_emit_args(who, "lg_blocks_mesh_count", vol->color != nullptr, s, n_vertices, n_faces, vertices, colors, faces, stream);
+    if (rc != LG_OK) return rc;
     if (n == 0 || (n_vertices == 0 && n_faces == 0)) return LG_OK;
     ProfScope ps(flags & LG_FLAG_PROFILE, "blocks_mesh_emit", stream);
-    lg_blk_mesh_emit_kernel<<<n, LG_BLK_MESH_THREADS, 0, stream>>>(n, block_vol_arg(vol), iso, min_weight, vol->keys, s.nbr, vol->tsdf, vol->weight, vol->color,
+    lg_blk_mesh_emit_kernel<<<n, LG_BLK_MESH_THREADS, 0, stream>>>(n, block_lattice(vol), iso, min_weight, vol->keys, s.nbr, vol->tsdf, vol->weight, vol->color,
                                                                    s.vprefix, s.fprefix, s.vmask, s.fcount, n_vertices, n_faces, vertices, colors, faces);
     KLAUNCHED("lg_blk_mesh_emit_kernel");
     return LG_OK;

@@ -14,16 +14,19 @@
 //   lg_blk_regrid_kernel         one workgroup per NEW block: binary search of its key among the old ones, then 16-byte loads and stores
 //                                of the old values, or of the fresh ones; every element of the new pool is written
 //   lg_blk_nbr_kernel            nbr [n,8]: the rank of the block at + offset(m), or -1 (binary search)
-//   lg_blk_integrate_kernel <COLOR>  lg_tsdf_integrate_kernel's shape: one workgroup of two waves per block, a lane carries a run of four
-//                                x-consecutive points (rows of 32 contiguous bytes) in registers through up to 8 views, loads once
-//                                and stores once, and stores nothing for an untouched run; a view whose z_min plane the whole block lies
-//                                behind is skipped by the workgroup
+//   lg_blk_integrate_kernel <COLOR>  one workgroup of two waves per block; a lane carries lg_tsdf.h's run of four x-consecutive points
+//                                (LgTsdfRun; rows of 32 contiguous bytes, always the dwordx4 path) in registers through up to 8 views
+//                                (lg_tsdf_fetch, lg_tsdf_apply_view), loads once and stores once, and stores nothing for an untouched
+//                                run; a view whose z_min plane the whole block lies behind is skipped by the workgroup
 //   lg_blk_mesh_count_kernel     one workgroup per block: the 9 x 9 x 9 halo of tsdf and weight staged in LDS through nbr (5.8 KB), lg_math.h's
 //                                rule functions on it as on a dense 9^3 grid, per-point edge-mask and face-count bytes, per-block totals
-//   lg_mesh_scan_kernel (lg_tsdf.h) over the block totals, then lg_blk_mesh_prefix_kernel: per point both exclusive prefixes
-//   lg_blk_mesh_emit_kernel      the halo again, with the halo of vprefix and vmask: vertices at prefix + rank, faces at the cell's face
-//                                prefix with the vertex ids of the neighbour blocks' points read from the halo: plain stores
+//                                (lg_mesh_put_totals)
+//   lg_mesh_scan_kernel (lg_tsdf.h) over the block totals, then lg_mesh_prefix_kernel<2, true> (lg_tsdf.h): per point both exclusive prefixes
+//   lg_blk_mesh_emit_kernel      the halo again, with the halo of vprefix and vmask: vertices at prefix + rank (lg_mesh_put_vertex), faces at
+//                                the cell's face prefix with the vertex ids of the neighbour blocks' points read from the halo: plain stores
 // Every rank read from nbr or found by a search is held against n before it indexes a pool.
+// What this volume has in common with the dense one -- the lattice struct, a lane's run, one view applied to a run, the scratch of the
+// mesh calls, the scan tails, the prefix kernel, the vertex store -- lives in lg_tsdf.h; this header holds what the blocks add.
 // Part of liblightgaussian_hip.so (single translation unit: lg_api.hip includes the lg_*.h kernel headers).
 #pragma once
 
@@ -38,7 +41,6 @@
 #define LG_BLK_THREADS 128                  // integrate, regrid: one run of four points per lane
 #define LG_BLK_MESH_THREADS 256             // mesh kernels: two points per lane
 
-struct LgBlkVol { float o[3]; float voxel, trunc; };
 struct LgBlkTouchView { const float* vm; const float* depth; const float* alpha; LgTsdfCam cam; uint32_t wave_end, tiles_x; };
 struct LgBlkTouchBatch { LgBlkTouchView v[LG_TSDF_BATCH]; };
 
@@ -61,7 +63,7 @@ __device__ __forceinline__ int lg_blk_find(const int64_t* __restrict__ keys, int
 // wave_n [2][total_waves]: channel 0 the candidates of a wave (EMIT: their exclusive prefix), channel 1 its skipped pixels
 template <bool EMIT>
 __global__ void __launch_bounds__(256)
-lg_blk_touch_kernel(LgBlkVol g, int n_views, LgBlkTouchBatch b, uint32_t batch_waves, uint32_t wave_base, uint32_t total_waves, uint32_t* __restrict__ wave_n,
+lg_blk_touch_kernel(LgTsdfLattice g, int n_views, LgBlkTouchBatch b, uint32_t batch_waves, uint32_t wave_base, uint32_t total_waves, uint32_t* __restrict__ wave_n,
                     int64_t capacity, int64_t* __restrict__ cand)
 {
     const uint32_t lane = threadIdx.x & 63u;
@@ -77,8 +79,7 @@ lg_blk_touch_kernel(LgBlkVol g, int n_views, LgBlkTouchBatch b, uint32_t batch_w
     const float d = inside ? a.depth[pix] : 0.0f;
     const float alpha = (inside && a.alpha) ? a.alpha[pix] : 0.0f;
     float vm[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) vm[k] = a.vm[k];
+    lg_tsdf_view_matrix(a.vm, vm);
     LgBlkBox box = { { 0, 0, 0 }, { 0, 0, 0 } };
     const int status = inside ? lg_blk_touch(vm, a.cam, g.o, g.voxel, g.trunc, ix, iy, d, a.alpha != nullptr, alpha, box) : 0;
     // bit (dz 4 + dy) 4 + dx of the to-do mask: block lo + (dx, dy, dz) of the lane's box
@@ -196,7 +197,7 @@ __global__ void __launch_bounds__(256) lg_blk_nbr_kernel(int n, const int64_t* _
 // One workgroup per block, lane = run: x0 = 4 (lane & 1), y = (lane >> 1) & 7, z = lane >> 4; the pools are 16-byte aligned, so is every run.
 template <bool COLOR>
 __global__ void __launch_bounds__(LG_BLK_THREADS)
-lg_blk_integrate_kernel(LgBlkVol g, const int64_t* __restrict__ keys, int n_views, LgTsdfBatch b, float* __restrict__ tsdf, float* __restrict__ weight,
+lg_blk_integrate_kernel(LgTsdfLattice g, const int64_t* __restrict__ keys, int n_views, LgTsdfBatch b, float* __restrict__ tsdf, float* __restrict__ weight,
                         float* __restrict__ color)
 {
     int bx, by, bz;
@@ -225,19 +226,8 @@ lg_blk_integrate_kernel(LgBlkVol g, const int64_t* __restrict__ keys, int n_view
     }
     if (reach == 0u) return;
 
-    float f[4], w[4], c[4][3];
-    {
-        const lg_f4 tf = *(const lg_f4*)(tsdf + p0), tw = *(const lg_f4*)(weight + p0);
-#pragma unroll
-        for (int k = 0; k < 4; k++) { f[k] = tf[k]; w[k] = tw[k]; }
-        if (COLOR) {
-            lg_f4 tc[3];
-#pragma unroll
-            for (int j = 0; j < 3; j++) tc[j] = *(const lg_f4*)(color + 3 * p0 + 4 * j);
-#pragma unroll
-            for (int e = 0; e < 12; e++) c[e / 3][e % 3] = tc[e / 4][e % 4];
-        }
-    }
+    LgTsdfRun<COLOR> run;
+    run.load(tsdf, weight, color, p0, true, 4);
     const float py = lg_tsdf_coord(g.o[1], g.voxel, y), pz = lg_tsdf_coord(g.o[2], g.voxel, z);
     float px[4];
 #pragma unroll
@@ -245,62 +235,14 @@ lg_blk_integrate_kernel(LgBlkVol g, const int64_t* __restrict__ keys, int n_view
     bool touched = false;
     for (int v = 0; v < n_views; v++) {
         if (!((reach >> v) & 1u)) continue;
-        const LgTsdfViewArg& a = b.v[v];
         LgTsdfFetch cur;
-        lg_tsdf_fetch(a, 4, px, py, pz, cur);
-        const size_t plane = (size_t)a.cam.H * (size_t)a.cam.W;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            float t;
-            if (cur.ok[k] && lg_tsdf_sample(a.cam, g.trunc, cur.d[k], cur.z[k], t)) {
-                LgTsdfPixel p = { cur.d[k], a.alpha ? a.alpha[cur.pix[k]] : 0.0f, { 0.0f, 0.0f, 0.0f } };
-                if (COLOR) { p.rgb[0] = a.color[cur.pix[k]]; p.rgb[1] = a.color[plane + cur.pix[k]]; p.rgb[2] = a.color[2 * plane + cur.pix[k]]; }
-                touched |= lg_tsdf_apply(a.cam, g.trunc, p, a.alpha != nullptr, cur.z[k], f[k], w[k], COLOR ? c[k] : nullptr);
-            }
-        }
+        lg_tsdf_fetch(b.v[v], 4, px, py, pz, cur);
+        touched |= lg_tsdf_apply_view<COLOR>(&b.v[v], g.trunc, cur, run);
     }
-    if (!touched) return;
-    *(lg_f4*)(tsdf + p0) = lg_f4{ f[0], f[1], f[2], f[3] };
-    *(lg_f4*)(weight + p0) = lg_f4{ w[0], w[1], w[2], w[3] };
-    if (COLOR) {
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            lg_f4 t;
-#pragma unroll
-            for (int e = 0; e < 4; e++) t[e] = c[(4 * j + e) / 3][(4 * j + e) % 3];
-            *(lg_f4*)(color + 3 * p0 + 4 * j) = t;
-        }
-    }
+    if (touched) run.store(tsdf, weight, color, p0, true, 4);
 }
 
 // ---- marching tetrahedra across block borders -------------------------------------------------------------------------------------
-// scratch of lg_blocks_mesh_count / lg_blocks_mesh_emit; P = 512 n
-struct LgBlkMeshScratch {
-    int64_t* counts;        // [2] vertices, faces
-    int32_t* nbr;           // [n][8]
-    uint32_t* vprefix;      // [P] vertex id of the first carrying slot of the point
-    uint32_t* fprefix;      // [P] index of the first face of the point's cell
-    uint32_t* blk;          // [2][n] block totals, then their exclusive scans, per channel
-    uint8_t* vmask;         // [P]
-    uint8_t* fcount;        // [P]
-    size_t total;
-};
-static LgBlkMeshScratch carve_blk_mesh(void* base, size_t n)
-{
-    LgBlkMeshScratch s; size_t off = 0; char* p = (char*)base;
-    auto take = [&](size_t bytes) { void* r = p ? p + off : nullptr; off += align_up(bytes); return r; };
-    const size_t P = n * LG_BLK_POINTS;
-    s.counts = (int64_t*)take(16);
-    s.nbr = (int32_t*)take(n * 8 * 4);
-    s.vprefix = (uint32_t*)take(P * 4);
-    s.fprefix = (uint32_t*)take(P * 4);
-    s.blk = (uint32_t*)take(2 * n * 4);
-    s.vmask = (uint8_t*)take(P);
-    s.fcount = (uint8_t*)take(P);
-    s.total = off;
-    return s;
-}
-
 // the halo of tsdf and weight of block `blk` into LDS: a point of a missing neighbour is fresh (tsdf 1, weight 0: unobserved under any
 // positive min_weight)
 __device__ __forceinline__ void lg_blk_stage_field(uint32_t blk, uint32_t n, const int32_t* __restrict__ nbr, const float* __restrict__ tsdf,
@@ -321,7 +263,6 @@ lg_blk_mesh_count_kernel(uint32_t n, float iso, float min_weight, const int32_t*
                          uint8_t* __restrict__ vmask, uint8_t* __restrict__ fcount, uint32_t* __restrict__ blk_v, uint32_t* __restrict__ blk_f)
 {
     __shared__ float ht[LG_BLK_HALO_POINTS], hw[LG_BLK_HALO_POINTS];
-    __shared__ uint32_t ws[2][4];
     lg_blk_stage_field(blockIdx.x, n, nbr, tsdf, weight, ht, hw);
     __syncthreads();
     uint32_t nv = 0, nf = 0;
@@ -334,41 +275,12 @@ lg_blk_mesh_count_kernel(uint32_t n, float iso, float min_weight, const int32_t*
         vmask[(size_t)blockIdx.x * LG_BLK_POINTS + p] = (uint8_t)m; fcount[(size_t)blockIdx.x * LG_BLK_POINTS + p] = (uint8_t)faces;
         nv += lg_mesh_popc8(m); nf += faces;
     }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t iv = lg_wave_scan_incl(nv, lane), jf = lg_wave_scan_incl(nf, lane);
-    lg_block_scan_put(ws[0], wave, lane, iv);
-    lg_block_scan_put(ws[1], wave, lane, jf);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        blk_v[blockIdx.x] = ws[0][0] + ws[0][1] + ws[0][2] + ws[0][3];
-        blk_f[blockIdx.x] = ws[1][0] + ws[1][1] + ws[1][2] + ws[1][3];
-    }
-}
-
-// lg_mesh_prefix_kernel with one workgroup per block of 512 points
-__global__ void __launch_bounds__(LG_BLK_MESH_THREADS)
-lg_blk_mesh_prefix_kernel(const uint8_t* __restrict__ vmask, const uint8_t* __restrict__ fcount, const uint32_t* __restrict__ blk_v,
-                          const uint32_t* __restrict__ blk_f, uint32_t* __restrict__ vprefix, uint32_t* __restrict__ fprefix)
-{
-    __shared__ uint32_t ws[2][4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const size_t p0 = (size_t)blockIdx.x * LG_BLK_POINTS + (size_t)threadIdx.x * 2;
-    const uint32_t cv[2] = { lg_mesh_popc8(vmask[p0]), lg_mesh_popc8(vmask[p0 + 1]) }, cf[2] = { fcount[p0], fcount[p0 + 1] };
-    const uint32_t nv = cv[0] + cv[1], nf = cf[0] + cf[1];
-    const uint32_t iv = lg_wave_scan_incl(nv, lane), jf = lg_wave_scan_incl(nf, lane);
-    lg_block_scan_put(ws[0], wave, lane, iv);
-    lg_block_scan_put(ws[1], wave, lane, jf);
-    __syncthreads();
-    uint32_t tv, tf;
-    const uint32_t pv = blk_v[blockIdx.x] + lg_block_scan_get<4>(ws[0], wave, tv) + iv - nv;
-    const uint32_t pf = blk_f[blockIdx.x] + lg_block_scan_get<4>(ws[1], wave, tf) + jf - nf;
-    vprefix[p0] = pv; vprefix[p0 + 1] = pv + cv[0];
-    fprefix[p0] = pf; fprefix[p0 + 1] = pf + cf[0];
+    lg_mesh_put_totals(nv, nf, blk_v, blk_f);
 }
 
 // n_vertices, n_faces: the sizes of the outputs (the host has held them against the counts); a store past them is dropped
 __global__ void __launch_bounds__(LG_BLK_MESH_THREADS)
-lg_blk_mesh_emit_kernel(uint32_t n, LgBlkVol g, float iso, float min_weight, const int64_t* __restrict__ keys, const int32_t* __restrict__ nbr,
+lg_blk_mesh_emit_kernel(uint32_t n, LgTsdfLattice g, float iso, float min_weight, const int64_t* __restrict__ keys, const int32_t* __restrict__ nbr,
                         const float* __restrict__ tsdf, const float* __restrict__ weight, const float* __restrict__ color, const uint32_t* __restrict__ vprefix,
                         const uint32_t* __restrict__ fprefix, const uint8_t* __restrict__ vmask, const uint8_t* __restrict__ fcount, int64_t n_vertices,
                         int64_t n_faces, float* __restrict__ vertices, float* __restrict__ colors, int32_t* __restrict__ faces)
@@ -410,15 +322,8 @@ lg_blk_mesh_emit_kernel(uint32_t n, LgBlkVol g, float iso, float min_weight, con
                         c0 = color + 3 * gp;
                         c1 = rq < n ? color + 3 * ((size_t)rq * LG_BLK_POINTS + ql) : c0;
                     }
-                    lg_blk_vertex(ht[h0], ht[h1], c0, c1, bx * LG_BLK + x, by * LG_BLK + y, bz * LG_BLK + z, k, iso, g.o, g.voxel, pos, rgb);
-                    if ((int64_t)id < n_vertices) {
-#pragma unroll
-                        for (int a = 0; a < 3; a++) vertices[3 * id + a] = pos[a];
-                        if (colors) {
-#pragma unroll
-                            for (int a = 0; a < 3; a++) colors[3 * id + a] = rgb[a];
-                        }
-                    }
+                    lg_mesh_edge_vertex(ht[h0], ht[h1], c0, c1, bx * LG_BLK + x, by * LG_BLK + y, bz * LG_BLK + z, k, iso, g.o, g.voxel, pos, rgb);
+                    lg_mesh_put_vertex(id, n_vertices, pos, rgb, vertices, colors);
                     id++;
                 }
         }

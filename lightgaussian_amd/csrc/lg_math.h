@@ -1258,23 +1258,32 @@ LG_HD uint32_t lg_mesh_edge_mask(const float* tsdf, const float* weight, int nx,
     }
     return mask;
 }
-// the vertex on slot k of the point (x, y, z): world position, and colour where the volume keeps one
-LG_HD void lg_mesh_vertex(const float* tsdf, const float* color, int nx, int ny, int x, int y, int z, uint32_t k, float iso, const float* origin,
-                          float voxel, float* pos, float* rgb)
+// The vertex on slot k of the lattice point (x, y, z) from the values of the edge's two ends: f0v, c0 at the point, f1v, c1 at the point +
+// offset(slot k); c0 = NULL: no colour.  World position, and colour.  (x, y, z) counts from the point `origin` lies at: the grid index of
+// a dense volume, the GLOBAL index of a block volume.
+LG_HD void lg_mesh_edge_vertex(float f0v, float f1v, const float* c0, const float* c1, int x, int y, int z, uint32_t k, float iso, const float* origin,
+                               float voxel, float* pos, float* rgb)
 {
     const uint32_t m = lg_mesh_slot_mask(k);
     const int ox = (int)(m & 1u), oy = (int)((m >> 1) & 1u), oz = (int)((m >> 2) & 1u);
-    const size_t p = lg_mesh_index(nx, ny, x, y, z), q = lg_mesh_index(nx, ny, x + ox, y + oy, z + oz);
-    const float f0 = tsdf[p] - iso, f1 = tsdf[q] - iso;
+    const float f0 = f0v - iso, f1 = f1v - iso;
     const float t = f0 / (f0 - f1);
     pos[0] = origin[0] + voxel * ((float)x + t * (float)ox);
     pos[1] = origin[1] + voxel * ((float)y + t * (float)oy);
     pos[2] = origin[2] + voxel * ((float)z + t * (float)oz);
-    if (rgb && color) {
-        rgb[0] = color[3 * p] + t * (color[3 * q] - color[3 * p]);
-        rgb[1] = color[3 * p + 1] + t * (color[3 * q + 1] - color[3 * p + 1]);
-        rgb[2] = color[3 * p + 2] + t * (color[3 * q + 2] - color[3 * p + 2]);
+    if (rgb && c0) {
+        rgb[0] = c0[0] + t * (c1[0] - c0[0]);
+        rgb[1] = c0[1] + t * (c1[1] - c0[1]);
+        rgb[2] = c0[2] + t * (c1[2] - c0[2]);
     }
+}
+// the vertex on slot k of the point (x, y, z) of a dense grid: world position, and colour where the volume keeps one
+LG_HD void lg_mesh_vertex(const float* tsdf, const float* color, int nx, int ny, int x, int y, int z, uint32_t k, float iso, const float* origin,
+                          float voxel, float* pos, float* rgb)
+{
+    const uint32_t m = lg_mesh_slot_mask(k);
+    const size_t p = lg_mesh_index(nx, ny, x, y, z), q = lg_mesh_index(nx, ny, x + (int)(m & 1u), y + (int)((m >> 1) & 1u), z + (int)((m >> 2) & 1u));
+    lg_mesh_edge_vertex(tsdf[p], tsdf[q], color ? color + 3 * p : nullptr, color ? color + 3 * q : nullptr, x, y, z, k, iso, origin, voxel, pos, rgb);
 }
 // bit m (0 .. 7): corner offset(m) of the cell at (x, y, z) is inside; false when a corner is unobserved.  x < nx - 1, y < ny - 1, z < nz - 1.
 LG_HD bool lg_mesh_cell_corners(const float* tsdf, const float* weight, int nx, int ny, int x, int y, int z, float iso, float min_weight, uint32_t& inside8)
@@ -1572,21 +1581,10 @@ LG_HD void lg_blk_halo_source(int h, uint32_t& m, int& local)
     m = (x == LG_BLK ? 1u : 0u) | (y == LG_BLK ? 2u : 0u) | (z == LG_BLK ? 4u : 0u);
     local = lg_blk_local(x & 7, y & 7, z & 7);
 }
-// The vertex on slot k of the lattice point (gx, gy, gz), GLOBAL indices: lg_mesh_vertex's arithmetic on the values of the two ends
-// (f0, c0 at the point, f1, c1 at the point + offset(slot k)); c0 = NULL: no colour.
+// The vertex on slot k of the lattice point (gx, gy, gz), GLOBAL indices: lg_mesh_edge_vertex under the name that
+// tests/cpu_harness/lg_blocks_harness.cpp calls.  It exists for that harness alone: no kernel calls it.
 LG_HD void lg_blk_vertex(float f0v, float f1v, const float* c0, const float* c1, int gx, int gy, int gz, uint32_t k, float iso, const float* origin,
                          float voxel, float* pos, float* rgb)
 {
-    const uint32_t m = lg_mesh_slot_mask(k);
-    const int ox = (int)(m & 1u), oy = (int)((m >> 1) & 1u), oz = (int)((m >> 2) & 1u);
-    const float f0 = f0v - iso, f1 = f1v - iso;
-    const float t = f0 / (f0 - f1);
-    pos[0] = origin[0] + voxel * ((float)gx + t * (float)ox);
-    pos[1] = origin[1] + voxel * ((float)gy + t * (float)oy);
-    pos[2] = origin[2] + voxel * ((float)gz + t * (float)oz);
-    if (rgb && c0) {
-        rgb[0] = c0[0] + t * (c1[0] - c0[0]);
-        rgb[1] = c0[1] + t * (c1[1] - c0[1]);
-        rgb[2] = c0[2] + t * (c1[2] - c0[2]);
-    }
+    lg_mesh_edge_vertex(f0v, f1v, c0, c1, gx, gy, gz, k, iso, origin, voxel, pos, rgb);
 }

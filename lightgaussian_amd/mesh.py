@@ -136,14 +136,11 @@ _TABLES = _build_tables()
 
 
 # ---- the torch backend ---------------------------------------------------------------------------------------------------------------
-def _integrate_torch(vol, depth, vm, tx, ty, color, alpha, alpha_min, depth_max, z_min):
-    nx, ny, nz = vol.dims
+def _integrate_torch(vol, px, py, pz, depth, vm, tx, ty, color, alpha, alpha_min, depth_max, z_min):
+    """One view into vol.tsdf, vol.weight (and vol.color, one more axis of 3 at the end) in place: px, py, pz are the world coordinates
+    of the points, float32 tensors that broadcast to the shape of vol.tsdf.  Both volumes' torch backend."""
     dev, dt = vol.tsdf.device, torch.float32
     H, W = (int(v) for v in depth.shape)
-    o = [model_rows.f32(v) for v in vol.origin]
-    px = (o[0] + vol.voxel_size * torch.arange(nx, dtype=dt, device=dev))[None, None, :]
-    py = (o[1] + vol.voxel_size * torch.arange(ny, dtype=dt, device=dev))[None, :, None]
-    pz = (o[2] + vol.voxel_size * torch.arange(nz, dtype=dt, device=dev))[:, None, None]
     vx = vm[0, 0] * px + vm[1, 0] * py + vm[2, 0] * pz + vm[3, 0]
     vy = vm[0, 1] * px + vm[1, 1] * py + vm[2, 1] * pz + vm[3, 1]
     vz = vm[0, 2] * px + vm[1, 2] * py + vm[2, 2] * pz + vm[3, 2]
@@ -166,7 +163,7 @@ def _integrate_torch(vol, depth, vm, tx, ty, color, alpha, alpha_min, depth_max,
     w1 = w + 1.0
     vol.tsdf.copy_(torch.where(ok, (vol.tsdf * w + t) / w1, vol.tsdf))
     if vol.color is not None:
-        img = color.reshape(3, -1)[:, pix].permute(1, 2, 3, 0)
+        img = torch.movedim(color.reshape(3, -1)[:, pix], 0, -1)
         vol.color.copy_(torch.where(ok[..., None], (vol.color * w[..., None] + img) / w1[..., None], vol.color))
     vol.weight.copy_(torch.where(ok, w1, w))
 
@@ -180,8 +177,10 @@ def _shifted(t, m, fill):
     return out
 
 
-def _extract_torch(tsdf, weight, color, origin, voxel, iso, min_weight):
-    """(vertices, faces, colors) of the contract, every vertex kept, in the contract's order; the dtype of tsdf."""
+def _extract_grid(tsdf, weight, color, origin, voxel, iso, min_weight, base=(0, 0, 0)):
+    """The mesh of the contract over a dense grid whose point (0, 0, 0) is the lattice point `base` (positions come from the lattice
+    index), every vertex kept, in the contract's order; the dtype of tsdf.  Returns (vertices, faces int64, colors, p, k, cell_of_face):
+    p, k = the (point, slot) of every vertex and cell_of_face the cell of every face, as linear indices of the grid."""
     nz, ny, nx = (int(v) for v in tsdf.shape)
     dev, dt = tsdf.device, tsdf.dtype
     obs, ins = weight >= min_weight, tsdf < iso
@@ -195,14 +194,15 @@ def _extract_torch(tsdf, weight, color, origin, voxel, iso, min_weight):
     flat = tsdf.reshape(-1)
     f0, f1 = flat[p] - iso, flat[q] - iso
     t = f0 / (f0 - f1)
-    grid = torch.stack([p % nx, (p // nx) % ny, p // (nx * ny)], dim=1).to(dt)
+    grid = torch.stack([p % nx + base[0], (p // nx) % ny + base[1], p // (nx * ny) + base[2]], dim=1).to(dt)
     org = torch.tensor([float(v) for v in origin], dtype=dt, device=dev)
     vertices = org + voxel * (grid + t[:, None] * off.to(dt))
     colors = None
     if color is not None:
         c = color.reshape(-1, 3)
         colors = c[p] + t[:, None] * (c[q] - c[p])
-    faces = torch.zeros((0, 3), dtype=torch.int32, device=dev)
+    faces = torch.zeros(0, dtype=torch.int64, device=dev)
+    cell_of_face = torch.zeros(0, dtype=torch.int64, device=dev)
     if min(nx, ny, nz) >= 2:
         valid = obs.clone()
         for cm in range(1, 8):
@@ -217,8 +217,16 @@ def _extract_torch(tsdf, weight, color, origin, voxel, iso, min_weight):
             owner = cells[:, None, None] + (a & 1) + ((a >> 1) & 1) * nx + ((a >> 2) & 1) * (nx * ny)
             tris.append(ids[owner * 7 + s])
             keep.append(torch.arange(2, device=dev)[None, :] < count[tt][m4][:, None])
-        faces = torch.stack(tris, dim=1)[torch.stack(keep, dim=1)].to(torch.int32)
-    return vertices, faces, colors
+        keep = torch.stack(keep, dim=1)
+        faces = torch.stack(tris, dim=1)[keep]
+        cell_of_face = cells[:, None, None].expand(-1, 6, 2)[keep]
+    return vertices, faces.reshape(-1, 3), colors, p, k, cell_of_face
+
+
+def _extract_torch(tsdf, weight, color, origin, voxel, iso, min_weight):
+    """(vertices, faces, colors) of the contract, every vertex kept, in the contract's order; the dtype of tsdf."""
+    vertices, faces, colors = _extract_grid(tsdf, weight, color, origin, voxel, iso, min_weight)[:3]
+    return vertices, faces.to(torch.int32), colors
 
 
 def drop_unreferenced_vertices(vertices, faces, colors=None):
@@ -239,6 +247,98 @@ def _check_map(what, name, t, shape, like):
         raise ValueError(f"{what}: {name} must have shape {list(shape)}, not {list(t.shape)}")
     if t.device != like.device:
         raise ValueError(f"{what}: {name} is on {t.device}, not on {like.device}")
+
+
+def _check_views(what, views, like, keep_color):
+    """The checks of a list of view dicts (integrate's arguments) for a volume whose tensors live where `like` does: [(depth, vm, tx, ty,
+    color, alpha, alpha_min, depth_max, z_min)] and the named tensors a backend may ask to be contiguous.  keep_color: the volume keeps
+    colour, so every view needs one; otherwise a colour given is ignored."""
+    checked, tensors = [], []
+    for i, v in enumerate(views):
+        unknown = set(v) - {"depth", "camera", "color", "alpha", "alpha_min", "depth_max", "z_min"}
+        if unknown:
+            raise ValueError(f"{what}: views[{i}] has unknown entries {sorted(unknown)}")
+        depth, camera, color, alpha = v["depth"], v["camera"], v.get("color"), v.get("alpha")
+        if not torch.is_tensor(depth) or depth.dim() != 2:
+            raise ValueError(f"{what}: views[{i}]: depth must be a [H, W] tensor")
+        H, W = (int(s) for s in depth.shape)
+        if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM):
+            raise ValueError(f"{what}: views[{i}]: H and W must lie in [1, {MAX_DIM}], not {H} x {W}")
+        _check_map(what, f"views[{i}].depth", depth, (H, W), like)
+        if keep_color:
+            if color is None:
+                raise ValueError(f"{what}: views[{i}]: the volume keeps colour and the view has no color")
+            _check_map(what, f"views[{i}].color", color, (3, H, W), like)
+        else:
+            color = None
+        if alpha is not None:
+            _check_map(what, f"views[{i}].alpha", alpha, (H, W), like)
+        vm = camera.world_view_transform.detach().to(device=like.device, dtype=torch.float32)
+        if tuple(vm.shape) != (4, 4):
+            raise ValueError(f"{what}: views[{i}]: camera.world_view_transform must be [4, 4]")
+        tx, ty = tanfov(camera)
+        scal = tuple(float(v.get(n, dflt)) for n, dflt in (("alpha_min", 0.5), ("depth_max", 0.0), ("z_min", 0.05)))
+        if any(math.isnan(s) for s in scal + (tx, ty)):
+            raise ValueError(f"{what}: views[{i}]: tanfov, alpha_min, depth_max and z_min must not be NaN")
+        checked.append((depth.detach(), vm.contiguous(), tx, ty, None if color is None else color.detach(), None if alpha is None else alpha.detach()) + scal)
+        tensors += [(f"views[{i}].depth", depth)] + ([] if color is None else [(f"views[{i}].color", color)]) + \
+            ([] if alpha is None else [(f"views[{i}].alpha", alpha)])
+    return checked, tensors
+
+
+def _view_array(checked):
+    """The lg_tsdf_view array of checked views (at least one element long: ctypes has no empty array to point at)."""
+    arr = (lg_tsdf_view * max(len(checked), 1))()
+    for a, (depth, vm, tx, ty, color, alpha, alpha_min, depth_max, z_min) in zip(arr, checked):
+        a.H, a.W = (int(s) for s in depth.shape)
+        a.tanfovx, a.tanfovy, a.alpha_min, a.depth_max, a.z_min = tx, ty, alpha_min, depth_max, z_min
+        a.viewmatrix, a.depth = vm.data_ptr(), depth.data_ptr()
+        a.color = None if color is None else color.data_ptr()
+        a.alpha = None if alpha is None else alpha.data_ptr()
+    return arr
+
+
+def _integrate_checked_torch(vol, points, checked):
+    """The checked views into vol, in order, by _integrate_torch; points = (px, py, pz)."""
+    with torch.no_grad():
+        for depth, vm, tx, ty, color, alpha, alpha_min, depth_max, z_min in checked:
+            _integrate_torch(vol, *points, depth, vm, model_rows.f32(tx), model_rows.f32(ty), color, alpha, model_rows.f32(alpha_min),
+                             model_rows.f32(depth_max), model_rows.f32(z_min))
+
+
+def _resolve_backend(backend, like, what, tensors):
+    """The backend a call takes: a CPU volume (`like` is one of its tensors) takes the torch path; on the GPU backend="hip" asks for
+    contiguous tensors."""
+    if backend == "hip" and not like.is_cuda:
+        return "torch"
+    if backend == "hip":
+        for name, t in tensors:
+            if not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be contiguous for backend='hip' (call .contiguous())")
+    return backend
+
+
+def _check_extract_args(what, iso, min_weight):
+    """(iso, min_weight) of an extract_mesh call as float32 values, or a ValueError."""
+    iso, min_weight = model_rows.f32(iso), model_rows.f32(min_weight)
+    if not math.isfinite(iso) or not (min_weight > 0 and math.isfinite(min_weight)):
+        raise ValueError(f"{what}: iso must be finite and min_weight positive and finite")
+    return iso, min_weight
+
+
+def _extract_hip(scratch_bytes, count, emit, vol, keeps_color, dev, iso, min_weight, flags):
+    """The extraction of either volume by the library: scratch of scratch_bytes, `count` (lg_mesh_count, or a sparse volume's counterpart) on the
+    volume struct `vol`, the one read-back, the outputs, `emit`; flags: the calling module's profile switch.  Returns (vertices, faces, colors), every vertex kept."""
+    with torch.cuda.device(dev):
+        scratch = _lib.scratch(scratch_bytes, dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(count(C.byref(vol), iso, min_weight, _lib.ptr(scratch), _lib.ptr(counts), flags, _lib.stream(dev)))
+        nv, nf = (int(c) for c in counts.tolist())                     # the one read-back: the caller allocates the outputs
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        colors = torch.empty((nv, 3), dtype=torch.float32, device=dev) if keeps_color else None
+        _lib.check(emit(C.byref(vol), iso, min_weight, _lib.ptr(scratch), nv, nf, _lib.ptr(vertices), _lib.ptr(colors), _lib.ptr(faces), flags, _lib.stream(dev)))
+    return vertices, faces, colors
 
 
 class TSDFVolume:
@@ -275,14 +375,7 @@ class TSDFVolume:
             self.color.fill_(0.0)
 
     def _resolve(self, what, tensors):
-        """The backend a call takes: a CPU volume takes the torch path; on the GPU backend="hip" asks for contiguous tensors."""
-        if self.backend == "hip" and not self.tsdf.is_cuda:
-            return "torch"
-        if self.backend == "hip":
-            for name, t in tensors:
-                if not t.is_contiguous():
-                    raise ValueError(f"{what}: {name} must be contiguous for backend='hip' (call .contiguous())")
-        return self.backend
+        return _resolve_backend(self.backend, self.tsdf, what, tensors)
 
     def _struct(self):
         nx, ny, nz = self.dims
@@ -292,6 +385,15 @@ class TSDFVolume:
     def _own(self):
         return [("tsdf", self.tsdf), ("weight", self.weight)] + ([] if self.color is None else [("color", self.color)])
 
+    def _points(self):
+        """(px, py, pz): the world coordinates of the points per axis, shaped to broadcast over [nz,ny,nx]."""
+        nx, ny, nz = self.dims
+        dev, dt = self.tsdf.device, torch.float32
+        o = [model_rows.f32(v) for v in self.origin]
+        return ((o[0] + self.voxel_size * torch.arange(nx, dtype=dt, device=dev))[None, None, :],
+                (o[1] + self.voxel_size * torch.arange(ny, dtype=dt, device=dev))[None, :, None],
+                (o[2] + self.voxel_size * torch.arange(nz, dtype=dt, device=dev))[:, None, None])
+
     def integrate(self, depth, camera, color=None, alpha=None, alpha_min=0.5, depth_max=0.0, z_min=0.05):
         """One view into the volume: depth [H,W] (view-space z, 0 = nothing), camera (world_view_transform, FoVx, FoVy), color [3,H,W]
         (required by a volume that keeps colour), alpha [H,W] with alpha_min, depth_max (0: none), z_min."""
@@ -300,81 +402,31 @@ class TSDFVolume:
     def integrate_many(self, views):
         """The views, dicts of integrate's arguments, in order: one library call, BATCH views per pass over the volume."""
         what = "TSDFVolume.integrate_many"
-        checked, tensors = [], list(self._own())
-        for i, v in enumerate(views):
-            unknown = set(v) - {"depth", "camera", "color", "alpha", "alpha_min", "depth_max", "z_min"}
-            if unknown:
-                raise ValueError(f"{what}: views[{i}] has unknown entries {sorted(unknown)}")
-            depth, camera, color, alpha = v["depth"], v["camera"], v.get("color"), v.get("alpha")
-            if not torch.is_tensor(depth) or depth.dim() != 2:
-                raise ValueError(f"{what}: views[{i}]: depth must be a [H, W] tensor")
-            H, W = (int(s) for s in depth.shape)
-            if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM):
-                raise ValueError(f"{what}: views[{i}]: H and W must lie in [1, {MAX_DIM}], not {H} x {W}")
-            _check_map(what, f"views[{i}].depth", depth, (H, W), self.tsdf)
-            if self.color is not None:
-                if color is None:
-                    raise ValueError(f"{what}: views[{i}]: the volume keeps colour and the view has no color")
-                _check_map(what, f"views[{i}].color", color, (3, H, W), self.tsdf)
-            else:
-                color = None
-            if alpha is not None:
-                _check_map(what, f"views[{i}].alpha", alpha, (H, W), self.tsdf)
-            vm = camera.world_view_transform.detach().to(device=self.tsdf.device, dtype=torch.float32)
-            if tuple(vm.shape) != (4, 4):
-                raise ValueError(f"{what}: views[{i}]: camera.world_view_transform must be [4, 4]")
-            tx, ty = tanfov(camera)
-            scal = tuple(float(v.get(n, dflt)) for n, dflt in (("alpha_min", 0.5), ("depth_max", 0.0), ("z_min", 0.05)))
-            if any(math.isnan(s) for s in scal + (tx, ty)):
-                raise ValueError(f"{what}: views[{i}]: tanfov, alpha_min, depth_max and z_min must not be NaN")
-            checked.append((depth.detach(), vm.contiguous(), tx, ty, None if color is None else color.detach(), None if alpha is None else alpha.detach()) + scal)
-            tensors += [(f"views[{i}].depth", depth)] + ([] if color is None else [(f"views[{i}].color", color)]) + \
-                ([] if alpha is None else [(f"views[{i}].alpha", alpha)])
-        backend = self._resolve(what, tensors)
+        checked, tensors = _check_views(what, list(views), self.tsdf, self.color is not None)
+        backend = self._resolve(what, self._own() + tensors)
         if not checked:
             return
         if backend == "torch":
-            with torch.no_grad():
-                for depth, vm, tx, ty, color, alpha, alpha_min, depth_max, z_min in checked:
-                    _integrate_torch(self, depth, vm, model_rows.f32(tx), model_rows.f32(ty), color, alpha, model_rows.f32(alpha_min),
-                                     model_rows.f32(depth_max), model_rows.f32(z_min))
+            _integrate_checked_torch(self, self._points(), checked)
             return
-        arr = (lg_tsdf_view * len(checked))()
-        for a, (depth, vm, tx, ty, color, alpha, alpha_min, depth_max, z_min) in zip(arr, checked):
-            a.H, a.W = (int(s) for s in depth.shape)
-            a.tanfovx, a.tanfovy, a.alpha_min, a.depth_max, a.z_min = tx, ty, alpha_min, depth_max, z_min
-            a.viewmatrix, a.depth = vm.data_ptr(), depth.data_ptr()
-            a.color = None if color is None else color.data_ptr()
-            a.alpha = None if alpha is None else alpha.data_ptr()
         dev = self.tsdf.device
         vol = self._struct()
         with torch.cuda.device(dev):
-            _lib.check(load().lg_tsdf_integrate(C.byref(vol), len(checked), arr, _flags(), _lib.stream(dev)))
+            _lib.check(load().lg_tsdf_integrate(C.byref(vol), len(checked), _view_array(checked), _flags(), _lib.stream(dev)))
 
     def extract_mesh(self, iso=0.0, min_weight=1.0, drop_unreferenced=True):
         """(vertices [Nv,3] float32 in world space, faces [Nf,3] int32, colors [Nv,3] or None) of the surface tsdf = iso over the points
         with weight >= min_weight, normals toward larger tsdf.  drop_unreferenced removes the vertices no face names (they lie on edges
         none of whose cells is fully observed) with torch ops and renumbers."""
         what = "TSDFVolume.extract_mesh"
-        iso, min_weight = model_rows.f32(iso), model_rows.f32(min_weight)
-        if not math.isfinite(iso) or not (min_weight > 0 and math.isfinite(min_weight)):
-            raise ValueError(f"{what}: iso must be finite and min_weight positive and finite")
-        backend = self._resolve(what, self._own())
-        if backend == "torch":
+        iso, min_weight = _check_extract_args(what, iso, min_weight)
+        if self._resolve(what, self._own()) == "torch":
             with torch.no_grad():
                 vertices, faces, colors = _extract_torch(self.tsdf, self.weight, self.color, self.origin, self.voxel_size, iso, min_weight)
         else:
-            dev, lib, vol = self.tsdf.device, load(), self._struct()
-            with torch.cuda.device(dev):
-                scratch = _lib.scratch(lib.lg_mesh_scratch_bytes(*self.dims), dev)
-                counts = torch.empty(2, dtype=torch.int64, device=dev)
-                _lib.check(lib.lg_mesh_count(C.byref(vol), iso, min_weight, _lib.ptr(scratch), _lib.ptr(counts), _flags(), _lib.stream(dev)))
-                nv, nf = (int(c) for c in counts.tolist())                     # the one read-back: the caller allocates the outputs
-                vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-                faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-                colors = None if self.color is None else torch.empty((nv, 3), dtype=torch.float32, device=dev)
-                _lib.check(lib.lg_mesh_emit(C.byref(vol), iso, min_weight, _lib.ptr(scratch), nv, nf, _lib.ptr(vertices), _lib.ptr(colors), _lib.ptr(faces),
-                                            _flags(), _lib.stream(dev)))
+            lib = load()
+            vertices, faces, colors = _extract_hip(lib.lg_mesh_scratch_bytes(*self.dims), lib.lg_mesh_count, lib.lg_mesh_emit, self._struct(),
+                                                   self.color is not None, self.tsdf.device, iso, min_weight, _flags())
         if drop_unreferenced:
             vertices, faces, colors = drop_unreferenced_vertices(vertices, faces, colors)
         return vertices, faces, colors

@@ -424,6 +424,10 @@ def test_refusals_of_the_library():
         for kw, word in views:
             refused(call(3, (mesh.lg_tsdf_view * 3)(_view(), _view(), _view(**kw))), fn, "views[2]", word)
     refused(lib.lg_blocks_integrate(C.byref(vol), 1, (mesh.lg_tsdf_view * 1)(_view(color=None)), 0, None), "lg_blocks_integrate", "views[0]", "null color")
+    # a colour pointer the call does not read is not looked at, misaligned or not (lg_tsdf_integrate refuses it: tests/test_mesh_host.py).
+    # lg_blocks_touch uses the same checker and never reads colour, but it launches even without blocks, so the verdict is seen here alone.
+    odd = (mesh.lg_tsdf_view * 1)(_view(color=FAKE + 2))
+    assert lib.lg_blocks_integrate(C.byref(_volume(color=None, n_blocks=0)), 1, odd, 0, None) == _lib.LG_OK
     refused(lib.lg_blocks_touch(None, 1, one, 64, sc, sc, sc, 0, None), "lg_blocks_touch", "null volume")
     refused(lib.lg_blocks_touch(C.byref(vol), 1, one, -1, sc, sc, sc, 0, None), "lg_blocks_touch", "capacity")
     refused(lib.lg_blocks_touch(C.byref(vol), 1, one, 64, None, sc, sc, 0, None), "lg_blocks_touch", "null candidates")

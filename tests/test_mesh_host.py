@@ -293,6 +293,9 @@ def test_refusals_of_the_library():
     # a volume without colour takes views without colour; no view at all is LG_OK without a launch
     assert lib.lg_tsdf_integrate(C.byref(vol), 0, None, 0, None) == _lib.LG_OK
     assert lib.lg_tsdf_integrate(C.byref(_volume(color=None)), 0, (mesh.lg_tsdf_view * 1)(_view(color=None)), 0, None) == _lib.LG_OK
+    # ... but a colour pointer it would not read is still held to 4-byte alignment (the block entries look at it only when they read it)
+    refused(lib.lg_tsdf_integrate(C.byref(_volume(color=None)), 1, (mesh.lg_tsdf_view * 1)(_view(color=FAKE + 2)), 0, None), "lg_tsdf_integrate",
+            "views[0]", "4-byte aligned")
     sc = C.c_void_p(FAKE)
     for iso, mw, word in ((nan, 1.0, "iso"), (inf, 1.0, "iso"), (0.0, 0.0, "min_weight"), (0.0, -1.0, "min_weight"), (0.0, nan, "min_weight"), (0.0, inf, "min_weight")):
         refused(lib.lg_mesh_count(C.byref(vol), iso, mw, sc, counts, 0, None), "lg_mesh_count", word)
